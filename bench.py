@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- frames/s forward+backward of the FFT-mode autoencoder training path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
         (N > 1: either launched by torch.distributed.run, one rank per GPU, or -- run plainly -- it starts its N ranks itself)
 
 Workload (BASELINE.json configs[2], SURVEY 8d "config 3"): 512x512 RGB frames, 4 encoder/decoder
@@ -20,7 +20,10 @@ products; intermediate feature maps are materialised only on request (aefft_net_
 sums as the reference, batch contracted first; `--flags NOOPFORM` runs the per-frame form, and the parity
 tests run both against the oracle.
 
-Prints ONE JSON line (rank 0): metric/value per the driver contract, plus
+Prints ONE JSON line (rank 0): metric/value per the driver contract.  A plain run does only what that headline needs: set-up,
+W warm-up steps, K timed steps, the outputs (--dump-outputs) and the line.  `--full` adds the other measurements:
+  "steady_state": a second timed region of --steady-steps steps right behind the headline one
+  "data_parallel": the step through libaefft_dp.so with per-phase events (20 untimed steps)
   "roofline":     the dominant kernel's algorithmic bytes / its HIP-event-timed duration vs 8 TB/s
   "cpu_baseline": the reference's CPU path (oracle/_ref when built, else the C port) timed on this
                   host on a bounded sample (rank 0, N=1 only)
@@ -84,7 +87,12 @@ def parse():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--preheat", type=int, default=0, help="EXTRA untimed steps in front of the W warm-up steps (reported as preheat_steps; 0 = the contract's protocol)")
-    ap.add_argument("--steady-steps", type=int, default=200, help="steps of the second timed region behind the headline one (reported as steady_state; 0 = skip)")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: steady_state, data_parallel, roofline, variants, "
+                    "cpu_baseline (each still subject to its --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step computed (rank 0) "
+                    "as DIR/<name>.npy: the weights of every pair, the per-pair post-update MSE, the packed batch-mean gradients and a fixed "
+                    "seeded sample of the reconstructions")
+    ap.add_argument("--steady-steps", type=int, default=200, help="--full: steps of the second timed region behind the headline one (reported as steady_state; 0 = skip)")
     ap.add_argument("--force-rccl-step", action="store_true", help="N = 1 with --rccl: run the timed loop through libaefft_dp.so as N > 1 does (rehearsal of the multi-GPU host path on one GPU)")
     ap.add_argument("--torch-dist-loop", action="store_true", help="N > 1: all-reduce through torch.distributed (dp.DataParallelStep) instead of libaefft_dp.so")
     ap.add_argument("--batch", type=int, default=32, help="frames per GPU (weak scaling)")
@@ -277,6 +285,30 @@ def variant_spatial(aefft, torch, np, ctx, steps=20):
                                "note": "aefft_conv_spatial x2 + aefft_backprop_spatial with a caller-supplied hidden layer (what the vector shims run): the hidden layer is read twice"}}
 
 
+DUMP_RECON_SAMPLE = 1 << 21       # reconstruction elements in a --dump-outputs sample (8 MB of float32)
+
+
+def dump_outputs(path, np, net, recon, mse):
+    """--dump-outputs: what a caller of the timed step holds after its last step, one float32 .npy per array under `path`:
+    c<l>, b<l>, f<l>, p<l> (the updated weights of pair l), mse_per_pair (the post-update MSE of every pair), grad_packed (the step's
+    packed kernel-support gradients, dp.grad_layout; N > 1: their sum over ranks) and recon_sample (the reconstructions at the
+    distinct flat indices, ascending, of DUMP_RECON_SAMPLE draws with a fixed seed; the whole flattened tensor when it is not larger)."""
+    import torch
+    dp = importlib.import_module("autoencoder-fft_amd.dp")
+    os.makedirs(path, exist_ok=True)
+    out = {"mse_per_pair": mse.cpu().numpy()}
+    for l in range(net.npairs):
+        out.update(zip((f"c{l}", f"b{l}", f"f{l}", f"p{l}"), net.get_pair(l)))
+    out["grad_packed"] = net.grad_buffer()[:dp.grad_layout(net.dims)[1]].cpu().numpy()
+    flat = recon.reshape(-1)
+    if flat.numel() > DUMP_RECON_SAMPLE:
+        idx = np.unique(np.random.default_rng(0).integers(0, flat.numel(), DUMP_RECON_SAMPLE))
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+    out["recon_sample"] = flat.cpu().numpy()
+    for k, v in out.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(v, np.float32))
+
+
 def spawn_ranks(a):
     """`python bench.py --gpus N` outside a torch.distributed launcher: start the N ranks ourselves (one process per GPU) as a
     CHILD torch.distributed.run and pass its exit code on.  Nothing in this process has touched the GPU yet
@@ -391,8 +423,12 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if a.dump_outputs and rank == 0:
+        net.last_mse(mse); ctx.sync()
+        dump_outputs(a.dump_outputs, np, net, recon, mse)
+    # everything below up to the result line is --full only: measurements the headline does not need
     steady = None
-    if a.steady_steps > 0:
+    if a.full and a.steady_steps > 0:
         fence()
         t1 = time.perf_counter()
         for _ in range(a.steady_steps):
@@ -409,7 +445,7 @@ def main():
     ctx.sync()
     mse_host = mse.cpu().numpy().tolist()
     dp_diag = None
-    if rstep is not None or (world == 1 and not a.no_dp_probe and dist is None):
+    if a.full and (rstep is not None or (world == 1 and not a.no_dp_probe and dist is None)):
         # Data-parallel diagnostics OUTSIDE the timed regions, through libaefft_dp.so: 20 more steps with events on the library's stream
         # around the gradient half, the collective and the update half, and the HOST's time per step (enqueue only, no synchronisation).
         # At N = 1 a communicator of one rank is created just for this: the all-reduce then runs through RCCL on the library's stream
@@ -433,7 +469,7 @@ def main():
                    "note": "events on the library's stream; min / max over ranks; host_us = wall time the host spends enqueueing one step"}
         if rstep is None:
             probe.close()
-    elif dist is not None:
+    elif a.full and dist is not None:
         # Data-parallel diagnostics, OUTSIDE the timed region (20 more steps with events on the library's stream around the two halves and
         # the collective): per-phase milliseconds as min / max over ranks, whether the replicas still hold identical weights, and the
         # global-batch MSE (the floats that ride in the gradient all-reduce)
@@ -456,7 +492,7 @@ def main():
     mse_finite = bool(np.isfinite(mse_host).all())      # flagged in the JSON line, the timing stands (del0 = 0.2 on U(-3,3) weights is the reference's unstable regime)
 
     roof = None
-    if rank == 0 and not a.no_roofline:
+    if rank == 0 and a.full and not a.no_roofline:
         # per-kernel HIP events on the stream the kernels run on, over the same step
         # (side streams off: overlapped kernels would be charged each other's time)
         ctx.prof_enable(True)
@@ -486,7 +522,7 @@ def main():
             roof["step_frac_of_hbm_peak_steady_state"] = step_bytes / (steady["ms_per_step"] * 1e-3) / 1e9 / HBM_PEAK_GBS
 
     variants = None
-    if rank == 0 and world == 1 and not a.no_variants and a.variant == "p2" and a.size == 512:
+    if rank == 0 and world == 1 and a.full and not a.no_variants and a.variant == "p2" and a.size == 512:
         net.close()
         del frames, recon
         torch.cuda.empty_cache()
@@ -506,7 +542,7 @@ def main():
 
     # (the CPU baseline last: its 16 worker processes leave the host's CPU share throttled for a moment, which the launch-bound variants would see)
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline:
         cpu = cpu_baseline(N, s if s > 1 else 2)
 
     if rank == 0:

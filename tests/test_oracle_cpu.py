@@ -1,6 +1,6 @@
 """CPU-path checkers: oracle/cpu_ref.c (port) must be bit-identical to the reference's own
-Conv/backprop/Pool/Portion compiled from /root/reference (oracle/_ref), and both must
-reproduce the committed golden vectors (tests/golden/cpu_path.npz, made by
+Conv/backprop/Pool/Portion compiled from the reference sources (oracle/_ref; where it is not built, its outputs stored
+in tests/golden/ref_pins.npz), and both must reproduce the committed golden vectors (tests/golden/cpu_path.npz, made by
 tests/golden/make_golden.py from the compiled reference)."""
 import os
 
@@ -10,6 +10,7 @@ import pytest
 import cpu
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden", "cpu_path.npz")
+PINS = os.path.join(os.path.dirname(__file__), "golden", "ref_pins.npz")
 
 
 def _case(seed, dD, dM, N, Nk):
@@ -22,25 +23,41 @@ def _case(seed, dD, dM, N, Nk):
     return x, c, b, f, p
 
 
-@pytest.mark.parametrize("shape", [(1, 4, 16, 3), (3, 4, 12, 5), (2, 3, 10, 3), (2, 2, 9, 7)])
-def test_port_bit_identical_to_compiled_reference(shape):
-    ref = cpu.reference()
-    if ref is None:
-        pytest.skip("oracle/_ref not built (no /root/reference here)")
-    port = cpu.port()
+PIN_SHAPES = [(1, 4, 16, 3), (3, 4, 12, 5), (2, 3, 10, 3), (2, 2, 9, 7)]
+
+
+def pin_outputs(L, shape):
+    """Every output the bit-identity pin compares, by name: Conv -> Conv -> backprop(del = 0.2), Pool at scales 1, 2, 3, -2
+    and Portion at q = 1, 2, on the seeded case of `shape`.  tests/golden/make_golden.py stores the compiled reference's
+    outputs as ref_pins.npz (keys cpu<shape index>_<name>)."""
     x, c, b, f, p = _case(7, *shape)
-    h1, h2 = port.conv(x, c, b), ref.conv(x, c, b)
-    assert np.array_equal(h1, h2)
-    o1, o2 = port.conv(h1, f, p), ref.conv(h2, f, p)
-    assert np.array_equal(o1, o2)
-    for a, r in zip(port.backprop(x, o1, h1, c, b, f, p, 0.2), ref.backprop(x, o2, h2, c, b, f, p, 0.2)):
-        assert np.array_equal(a, r)
+    h = L.conv(x, c, b)
+    o = L.conv(h, f, p)
+    out = {"h": h, "o": o}
+    out.update(zip(("c2", "b2", "f2", "p2"), L.backprop(x, o, h, c, b, f, p, 0.2)))
     dD, N = x.shape[0], x.shape[1]
     for s in (1, 2, 3):
-        assert np.array_equal(port.pool(x, (dD, -(-N // s), -(-N // s)), s), ref.pool(x, (dD, -(-N // s), -(-N // s)), s))
-    assert np.array_equal(port.pool(x, (dD, 2 * N, 2 * N), -2), ref.pool(x, (dD, 2 * N, 2 * N), -2))
+        out[f"pool{s}"] = L.pool(x, (dD, -(-N // s), -(-N // s)), s)
+    out["pool-2"] = L.pool(x, (dD, 2 * N, 2 * N), -2)
     for q in (1, 2):
-        assert np.array_equal(port.portion(x, q), ref.portion(x, q))
+        out[f"portion{q}"] = L.portion(x, q)
+    return out
+
+
+@pytest.mark.parametrize("shape", PIN_SHAPES)
+def test_port_bit_identical_to_compiled_reference(shape):
+    """Against the compiled reference's outputs stored in tests/golden/ref_pins.npz; where oracle/_ref is built, the live
+    reference must reproduce them too."""
+    got = pin_outputs(cpu.port(), shape)
+    i = PIN_SHAPES.index(shape)
+    stored = {k: np.load(PINS)[f"cpu{i}_{k}"] for k in got}
+    ref = cpu.reference()
+    if ref is not None:
+        live = pin_outputs(ref, shape)
+        for k in got:
+            assert np.array_equal(live[k], stored[k]), k
+    for k in got:
+        assert np.array_equal(got[k], stored[k]), k
 
 
 def test_pool_truncates_and_clamps():

@@ -1,6 +1,8 @@
 """Cross-pins oracle/np_ref.py (restatement of the CUDA FFT path, which cannot run here) against
 the reference's own CPU code compiled from /root/reference (oracle/_ref), plus the analytic
 known-answer identities listed in SURVEY.md section 8c."""
+import os
+
 import numpy as np
 import pytest
 
@@ -342,8 +344,11 @@ def test_clip_branch_and_mse_normalisation_meet_the_compiled_reference(capfd):
     small = (np.abs(g_cpu) < 9.5) & (np.abs(g_c) < 9.5)
     if small.any():                                       # jointly unclipped elements differ by the Norm ratio only
         assert np.allclose(r[0][small], ratio * c2.astype(np.float64)[small], rtol=1e-4, atol=1e-20)
-    # mse normalisation
-    dist = float(printed.split("mse:")[1].split()[0])
+    # mse normalisation (the port does not print: the reference's printed value on this case is stored, tests/golden/make_golden.py)
+    if L.kind == "reference":
+        dist = float(printed.split("mse:")[1].split()[0])
+    else:
+        dist = float(np.load(os.path.join(os.path.dirname(__file__), "golden", "ref_pins.npz"))["clip_mse_printed"])
     assert R.mse_fft(X, O, dM, dD, N, N) * (2 * dD * dM * N * N) == pytest.approx(dist, rel=2e-5)
 
 
