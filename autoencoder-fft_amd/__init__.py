@@ -23,7 +23,9 @@ OK, EINVAL, EHIP, ENOMEM, ESTATE = 0, 1, 2, 3, 4
 # include/aefft.h AEFFT_F_* (development switches; tests/test_abi.py checks this table against the header)
 FLAGS = {n: 1 << i for i, n in enumerate(
     ["NOLAZY", "NOCOMPACT", "NOQPATH", "NOFUSEMSE", "NOGROUP", "NOMFMA", "NOGFWD", "NOOVERLAP", "NOFUSECROP", "GTAPS",
-     "NOPREFETCH", "NODEFER", "NOTILEDSPATIAL", "NOFAST", "NOSPLITK", "POISON", "NOOPFORM", "NOCHAIN", "NOFUSEUPD", "NOAHEAD", "NORCORR", "NOLAZYMSE", "SMALLOVERLAP", "CHAINMSE"])}
+     "NOPREFETCH", "NODEFER", "NOTILEDSPATIAL", "NOFAST", "NOSPLITK", "POISON", "NOOPFORM", "NOCHAIN", "NOFUSEUPD", "NOAHEAD", "NORCORR", "NOLAZYMSE", "SMALLOVERLAP", "CHAINMSE",
+     "CHIRPZ"])}
+NET_SMOOTH_SIZES = 1 << 0   # include/aefft.h AEFFT_NET_SMOOTH_SIZES (aefft_net_create_ex)
 
 
 class AefftError(RuntimeError):
@@ -67,6 +69,7 @@ SIGNATURES = {
     "aefft_backprop_spatial": (_i, [_vp] + [_fp] * 15 + [_i] * 7 + [_f, _f, _i, _i]),
     "aefft_step_spatial": (_i, [_vp] + [_fp] * 15 + [_i] * 7 + [_f, _f, _i, _i]),
     "aefft_net_create": (_i, [_vp, C.POINTER(NetDesc), C.POINTER(_vp)]),
+    "aefft_net_create_ex": (_i, [_vp, C.POINTER(NetDesc), C.c_uint, C.POINTER(_vp)]),
     "aefft_net_destroy": (None, [_vp]),
     "aefft_net_npairs": (_i, [_vp]),
     "aefft_net_pair_shape": (_i, [_vp, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
@@ -407,7 +410,9 @@ class Context:
 class Net:
     """aefft_net: resident batched autoencoder (autoenc_fft / backprop_fft semantics)."""
 
-    def __init__(self, ctx, D, Nx, Ny, maps, Nk, scale, batch, Nl=None):
+    def __init__(self, ctx, D, Nx, Ny, maps, Nk, scale, batch, Nl=None, smooth_sizes=False):
+        """smooth_sizes: also take Nx, Ny with prime factors 3 and 5 (640 x 480, ...; aefft_net_create_ex with
+        AEFFT_NET_SMOOTH_SIZES) -- such a net trains in the per-frame form."""
         self.ctx, self.L = ctx, ctx.L
         self.D, self.Nx, self.Ny, self.B = D, Nx, Ny, batch
         self.maps = list(maps); self.npairs = len(self.maps)
@@ -418,7 +423,10 @@ class Net:
         self._keep = [arr(self.maps), arr(self.Nk), arr(self.Nl), arr(self.scale)]
         d = NetDesc(D, Nx, Ny, self.npairs, *self._keep, batch)
         h = C.c_void_p()
-        ctx.check(self.L.aefft_net_create(ctx.h, C.byref(d), C.byref(h)))
+        if smooth_sizes:
+            ctx.check(self.L.aefft_net_create_ex(ctx.h, C.byref(d), NET_SMOOTH_SIZES, C.byref(h)))
+        else:
+            ctx.check(self.L.aefft_net_create(ctx.h, C.byref(d), C.byref(h)))
         self.h = h
         # per-pair geometry
         self.dims = []

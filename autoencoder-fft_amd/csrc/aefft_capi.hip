@@ -31,7 +31,7 @@ struct aefft_ctx {
     hipStream_t stream = nullptr;    // the caller-visible stream: every public call is ordered on it
     hipStream_t cur = nullptr;       // stream the helpers enqueue on (== stream except inside a forked section)
     bool own_stream = false;
-    bool in_u8 = false;              // the frames handed to the running call are 8-bit pixels (aefft_net_step_grad_u8 / aefft_net_forward_u8: do_r2c converts on load)
+    bool in_u8 = false;              // the frames handed to the running call are 8-bit pixels (aefft_net_step_grad_u8 / aefft_net_forward_u8: net_forward passes it to the frame transforms)
     int biasColP1 = 0;               // operator form: conv_k biases go to the affine column of the basis frames only (Contract::biasColP1)
     bool recon_join = false;         // a deferred reconstruction (pipelined mode) still has to be joined from aux[0] (ev_join[0])
     static const int NAUX = 2;
@@ -113,7 +113,7 @@ static const struct { const char* name; unsigned bit; } flag_names[] = {
     {"NOFUSECROP", AEFFT_F_NOFUSECROP}, {"GTAPS", AEFFT_F_GTAPS}, {"NOPREFETCH", AEFFT_F_NOPREFETCH}, {"NODEFER", AEFFT_F_NODEFER},
     {"NOTILEDSPATIAL", AEFFT_F_NOTILEDSPATIAL}, {"NOFAST", AEFFT_F_NOFAST}, {"NOSPLITK", AEFFT_F_NOSPLITK}, {"POISON", AEFFT_F_POISON},
     {"NOOPFORM", AEFFT_F_NOOPFORM}, {"NOCHAIN", AEFFT_F_NOCHAIN}, {"NOFUSEUPD", AEFFT_F_NOFUSEUPD}, {"NOAHEAD", AEFFT_F_NOAHEAD}, {"NORCORR", AEFFT_F_NORCORR}, {"NOLAZYMSE", AEFFT_F_NOLAZYMSE},
-    {"SMALLOVERLAP", AEFFT_F_SMALLOVERLAP}, {"CHAINMSE", AEFFT_F_CHAINMSE}};
+    {"SMALLOVERLAP", AEFFT_F_SMALLOVERLAP}, {"CHAINMSE", AEFFT_F_CHAINMSE}, {"CHIRPZ", AEFFT_F_CHIRPZ}};
 // The switches named by AEFFT_FLAGS stay on for the life of the process: aefft_ctx_set_flags ORs its argument onto them (a test fixture
 // that restores "no flags" does not clear an AEFFT_FLAGS=POISON run).  A name the library does not know is an error, not a silent
 // default run: the first aefft_ctx_create fails with AEFFT_EINVAL and says which.
@@ -319,6 +319,20 @@ static int chk_size_any(aefft_ctx* ctx, int Nx, int Ny)
     return fail(ctx, AEFFT_EINVAL, "Nx, Ny must be powers of two in 8..2048, or even sizes in 8..1024");
 }
 static bool pow2_sizes(int Nx, int Ny) { return fft_size_supported(Nx) && fft_size_supported(Ny); }
+// the per-bin ops and the network: powers of two, or smooth sizes (even, 10..2048, no prime factor above 5) on the mixed-radix transforms
+static bool net_size(int n) { return fft_size_supported(n) || fft_size_smooth(n); }
+static int chk_size_smooth(aefft_ctx* ctx, int Nx, int Ny)
+{
+    if (!net_size(Nx) || !net_size(Ny)) return fail(ctx, AEFFT_EINVAL, "Nx, Ny must be powers of two in 8..2048, or even sizes in 10..2048 with no prime factor above 5");
+    return AEFFT_OK;
+}
+// the transforms take the mixed-radix passes (fft_mixed_kernels.hip) on grids with a smooth axis whose other axis has no prime factor above 5
+// either, unless AEFFT_F_CHIRPZ sends sizes Bluestein serves (<= 1024) there.  A power-of-two grid keeps its routes whatever the crop / pad:
+// the power-of-two passes, or Bluestein + resize for a crop to a size that is not a power of two (op-level pooling by 3, 5, ...)
+static bool mixed_route(int Nx, int Ny)
+{
+    return (fft_size_smooth(Nx) || fft_size_smooth(Ny)) && fft_size_mixed(Nx) && fft_size_mixed(Ny) && !(flag(AEFFT_F_CHIRPZ) && Nx <= 1024 && Ny <= 1024);
+}
 static int do_resize(aefft_ctx* ctx, const float2* in, float2* out, long planes, int Nx, int Ny, int Nxs, int Nys);
 
 // sizes that are not powers of two (fft_backproplib.cu:773-779: cufftPlanMany takes any): Bluestein rows + transposes (fft_kernels.hip);
@@ -356,18 +370,18 @@ static int do_c2r_any(aefft_ctx* ctx, const float2* X, float* x, long planes, in
 }
 
 // R2C (+ fused crop to Nxs x Nys).  The two kernels are bracketed separately for profiling.
-// (ctx->in_u8, set by aefft_net_step_grad_u8 for the duration of its call: x holds 8-bit pixels)
-static int do_r2c(aefft_ctx* ctx, const float* x, float2* X, long planes, int Nx, int Ny, int Nxs, int Nys, int ws_id = WS_MID, hipEvent_t done = nullptr)
+// u8: x holds 8-bit pixels (the frame transforms of aefft_net_step_grad_u8 / aefft_net_forward_u8 only; every other transform reads floats)
+static int do_r2c(aefft_ctx* ctx, const float* x, float2* X, long planes, int Nx, int Ny, int Nxs, int Nys, int ws_id = WS_MID, hipEvent_t done = nullptr,
+                  bool u8 = false)
 {
-    const bool u8 = ctx->in_u8;
-    if (!pow2_sizes(Nx, Ny) || !pow2_sizes(Nxs, Nys)) {
+    if ((!pow2_sizes(Nx, Ny) || !pow2_sizes(Nxs, Nys)) && !mixed_route(Nx, Ny)) {
         if (u8) return fail(ctx, AEFFT_EINVAL, "r2c: 8-bit frames need power-of-two sizes");
         RET_IF(chk_size_any(ctx, Nx, Ny));
         if (!aligned16(x) || !aligned16(X)) return fail(ctx, AEFFT_EINVAL, "r2c: pointers must be 16-byte aligned");
         return do_r2c_any(ctx, x, X, planes, Nx, Ny, Nxs, Nys);
     }
-    RET_IF(chk_size(ctx, Nx, Ny));
     if (!aligned16(x) || !aligned16(X)) return fail(ctx, AEFFT_EINVAL, "r2c: pointers must be 16-byte aligned");
+    if (Nxs > Nx || Nys > Ny || Nxs < 2 || Nys < 2 || (Nxs & 1) || (Nys & 1)) return fail(ctx, AEFFT_EINVAL, "r2c: cropped size must be even and inside the grid");
     void* mid;
     RET_IF(ws_get(ctx, ws_id, sizeof(float2) * fft_mid_elems(planes, Nx, Nys / 2), &mid));
     // launch_r2c issues rows then cols; bracket as two launches by splitting the byte accounting:
@@ -391,13 +405,13 @@ static int do_r2c(aefft_ctx* ctx, const float* x, float2* X, long planes, int Nx
 static int do_c2r(aefft_ctx* ctx, const float2* X, float* x, long planes, int Nxi, int Nyi, int Nx, int Ny, float scale, int ws_id = WS_MID,
                   const OpIn* opin = nullptr)
 {
-    if (!opin && (!pow2_sizes(Nx, Ny) || !pow2_sizes(Nxi, Nyi))) {
+    if (!opin && (!pow2_sizes(Nx, Ny) || !pow2_sizes(Nxi, Nyi)) && !mixed_route(Nx, Ny)) {
         RET_IF(chk_size_any(ctx, Nx, Ny));
         if (!aligned16(x) || !aligned16(X)) return fail(ctx, AEFFT_EINVAL, "c2r: pointers must be 16-byte aligned");
         return do_c2r_any(ctx, X, x, planes, Nxi, Nyi, Nx, Ny, scale);
     }
-    RET_IF(chk_size(ctx, Nx, Ny));
     if (!aligned16(x) || (!opin && !aligned16(X))) return fail(ctx, AEFFT_EINVAL, "c2r: pointers must be 16-byte aligned");
+    if (Nxi > Nx || Nyi > Ny || Nxi < 2 || Nyi < 2 || (Nxi & 1) || (Nyi & 1)) return fail(ctx, AEFFT_EINVAL, "c2r: padded-from size must be even and inside the grid");
     void* mid;
     RET_IF(ws_get(ctx, ws_id, sizeof(float2) * fft_mid_elems(planes, Nx, Nyi / 2), &mid));
     const double b_in = (double)planes * bins(Nxi, Nyi) * 8, b_mid = (double)planes * Nx * (Nyi / 2) * 8, b_out = (double)planes * Nx * Ny * 4;
@@ -795,7 +809,7 @@ static int chk_scale(aefft_ctx* ctx, int Nx, int Ny, int scale, int* Nxs, int* N
 extern "C" int aefft_pool(aefft_ctx* ctx, const float* X_d, float* Xs_d, long planes, int Nx, int Ny, int scale, int* Nxs, int* Nys)
 {
     if (!ctx || !X_d || !Xs_d || planes < 0) return fail(ctx, AEFFT_EINVAL, "aefft_pool: bad argument");
-    RET_IF(chk_size_any(ctx, Nx, Ny));
+    if (!(net_size(Nx) && net_size(Ny))) RET_IF(chk_size_any(ctx, Nx, Ny));      // (only a resize: smooth sizes up to 2048 as well)
     int nx, ny;
     RET_IF(chk_scale(ctx, Nx, Ny, scale, &nx, &ny));
     if (Nxs) *Nxs = nx;
@@ -826,7 +840,7 @@ extern "C" int aefft_unpool_c2r(aefft_ctx* ctx, const float* Xs_d, float* x_d, l
 extern "C" int aefft_kernel_spectrum(aefft_ctx* ctx, const float* k_d, float* K_d, int nA, int nB, int Nk, int Nl, int Nx, int Ny)
 {
     if (!ctx || !k_d || !K_d || nA <= 0 || nB <= 0 || Nk <= 0 || Nl <= 0 || Nk > Nx || Nl > Ny) return fail(ctx, AEFFT_EINVAL, "aefft_kernel_spectrum: bad argument");
-    RET_IF(chk_size(ctx, Nx, Ny));
+    RET_IF(chk_size_smooth(ctx, Nx, Ny));
     const long planes = (long)nA * nB;
     void* real = nullptr;
     if (!pruned_supported(Nk, Nl, Nx, Ny)) RET_IF(ws_get(ctx, WS_REAL, sizeof(float) * planes * Nx * Ny, &real));
@@ -836,7 +850,7 @@ extern "C" int aefft_kernel_spectrum(aefft_ctx* ctx, const float* k_d, float* K_
 extern "C" int aefft_kernel_export(aefft_ctx* ctx, const float* K_d, float* k_d, int nA, int nB, int Nk, int Nl, int Nx, int Ny)
 {
     if (!ctx || !k_d || !K_d || nA <= 0 || nB <= 0 || Nk <= 0 || Nl <= 0 || Nk > Nx || Nl > Ny) return fail(ctx, AEFFT_EINVAL, "aefft_kernel_export: bad argument");
-    RET_IF(chk_size(ctx, Nx, Ny));
+    RET_IF(chk_size_smooth(ctx, Nx, Ny));
     const long planes = (long)nA * nB;
     void *real = nullptr, *part = nullptr;
     if (pruned_supported(Nk, Nl, Nx, Ny)) RET_IF(ws_get(ctx, WS_PART, sizeof(float) * kgrad_partial_floats(planes, Nx, Ny, Nk, Nl), &part));
@@ -848,7 +862,7 @@ extern "C" int aefft_kernel_export(aefft_ctx* ctx, const float* K_d, float* k_d,
 extern "C" int aefft_conv(aefft_ctx* ctx, const float* X_d, const float* C_d, const float* bias_d, float* O_d, int B, int dM, int dD, int Nx, int Ny)
 {
     if (!ctx || !X_d || !C_d || !O_d || B <= 0 || dM <= 0 || dD <= 0) return fail(ctx, AEFFT_EINVAL, "aefft_conv: bad argument");
-    RET_IF(chk_size(ctx, Nx, Ny));
+    RET_IF(chk_size_smooth(ctx, Nx, Ny));
     if (!aligned16(X_d) || !aligned16(C_d) || !aligned16(O_d)) return fail(ctx, AEFFT_EINVAL, "aefft_conv: pointers must be 16-byte aligned");
     return do_conv(ctx, CF2(X_d), CF2(C_d), bias_d, F2(O_d), B, dM, dD, Nx, Ny);
 }
@@ -859,7 +873,7 @@ extern "C" int aefft_gradient(aefft_ctx* ctx, const float* Xin_d, const float* X
 {
     if (!ctx || !Xin_d || !Xout_d || !O_d || !C_d || !F_d || !b_d || !dc_d || !df_d || !db_d || !dp_d || B <= 0 || dM <= 0 || dD <= 0)
         return fail(ctx, AEFFT_EINVAL, "aefft_gradient: bad argument");
-    RET_IF(chk_size(ctx, Nx, Ny));
+    RET_IF(chk_size_smooth(ctx, Nx, Ny));
     const long P = bins(Nx, Ny);
     void* S;
     RET_IF(ws_get(ctx, WS_S, sizeof(float2) * dD * dD * P, &S));
@@ -880,7 +894,7 @@ extern "C" int aefft_update(aefft_ctx* ctx, float* c_d, float* f_d, float* b_d, 
 {
     if (!ctx || !c_d || !f_d || !b_d || !p_d || !C_d || !F_d || !dc_d || !df_d || !db_d || !dp_d || !Dc_d || !Df_d || !Db_d || !Dp_d)
         return fail(ctx, AEFFT_EINVAL, "aefft_update: null pointer");
-    RET_IF(chk_size(ctx, Nx, Ny));
+    RET_IF(chk_size_smooth(ctx, Nx, Ny));
     const long planes = (long)dM * dD;
     const size_t nk = (size_t)planes * Nk * Nl;
     void *real = nullptr, *tmp, *part = nullptr;
@@ -1141,12 +1155,17 @@ extern "C" void aefft_net_destroy(aefft_net* net)
     delete net;
 }
 
-extern "C" int aefft_net_create(aefft_ctx* ctx, const aefft_net_desc* d, aefft_net** out)
+// opts = 0: aefft_net_create; AEFFT_NET_SMOOTH_SIZES: smooth Nx, Ny too (mixed-radix transforms), every pooled grid even and >= 8
+static int net_create(aefft_ctx* ctx, const aefft_net_desc* d, unsigned opts, aefft_net** out)
 {
     if (!ctx || !d || !out || d->npairs <= 0 || d->batch <= 0 || d->D <= 0 || !d->maps || !d->Nk || !d->Nl || !d->scale)
         return fail(ctx, AEFFT_EINVAL, "aefft_net_create: bad descriptor");
     *out = nullptr;
-    RET_IF(chk_size(ctx, d->Nx, d->Ny));
+    const bool smooth = (opts & AEFFT_NET_SMOOTH_SIZES) != 0;
+    if (smooth) {
+        if (!net_size(d->Nx) || !net_size(d->Ny))
+            return fail(ctx, AEFFT_EINVAL, "aefft_net_create_ex: Nx, Ny must be powers of two in 8..2048, or even sizes in 10..2048 with no prime factor above 5");
+    } else RET_IF(chk_size(ctx, d->Nx, d->Ny));
     aefft_net* n = new aefft_net();
     n->ctx = ctx; n->D = d->D; n->Nx = d->Nx; n->Ny = d->Ny; n->L = d->npairs; n->B = d->batch;
     n->Bc = std::max(n->B, (int)OPC);
@@ -1161,6 +1180,12 @@ extern "C" int aefft_net_create(aefft_ctx* ctx, const aefft_net_desc* d, aefft_n
         q.Nxin = nx; q.Nyin = ny;
         if (q.dM <= 0 || q.Nk <= 0 || q.Nl <= 0 || q.s < 1 || !pow2(q.s)) { rc = fail(ctx, AEFFT_EINVAL, "aefft_net_create: bad pair parameters"); break; }
         q.Nx = nx / q.s; q.Ny = ny / q.s;
+        if (smooth && (nx % q.s || ny % q.s || (q.Nx & 1) || (q.Ny & 1) || q.Nx < 8 || q.Ny < 8)) {
+            const std::string msg = "aefft_net_create_ex: every pair's pooled grid must be even and >= 8 (pair " + std::to_string(l) + ": " + std::to_string(nx) +
+                                    " x " + std::to_string(ny) + " pooled by " + std::to_string(q.s) + ")";
+            rc = fail(ctx, AEFFT_EINVAL, msg.c_str());
+            break;
+        }
         if (q.Nx < 8 || q.Ny < 8 || q.Nk > q.Nx || q.Nl > q.Ny) { rc = fail(ctx, AEFFT_EINVAL, "aefft_net_create: pooled size < 8 or kernel larger than plane"); break; }
         q.P = bins(q.Nx, q.Ny);
         const size_t nk = (size_t)q.dM * q.dD * q.Nk * q.Nl;
@@ -1198,6 +1223,8 @@ extern "C" int aefft_net_create(aefft_ctx* ctx, const aefft_net_desc* d, aefft_n
         // size the context workspaces once so nothing reallocates inside a step
         if ((rc = ws_get(ctx, WS_MID, sizeof(float2) * maxMid, &dummy)) == AEFFT_OK &&
             (rc = ws_get(ctx, WS_MID3, sizeof(float2) * (size_t)n->B * n->D * n->Nx * (n->Ny / 2), &dummy)) == AEFFT_OK &&
+            // (smooth sizes: the input transform's side-stream workspace of aefft_net_set_input_ready as well)
+            (!smooth || (rc = ws_get(ctx, WS_MID2, sizeof(float2) * (size_t)n->B * n->D * n->Nx * (n->Ny / 2), &dummy)) == AEFFT_OK) &&
             (rc = ws_get(ctx, WS_DEN, sizeof(float) * maxDen, &dummy)) == AEFFT_OK &&
             (rc = ws_get(ctx, WS_SMALL, sizeof(float) * maxSmall, &dummy)) == AEFFT_OK &&
             (rc = net_alloc_t(n, &n->real, n->pruned ? 64 : maxReal)) == AEFFT_OK &&
@@ -1242,9 +1269,23 @@ extern "C" int aefft_net_create(aefft_ctx* ctx, const aefft_net_desc* d, aefft_n
         e = hipMemsetAsync(q.p, 0, q.dD * 4, ctx->stream); if (e) break;
     }
     if (e != hipSuccess) { aefft_net_destroy(n); return fail(ctx, AEFFT_EHIP, "memset weights", e); }
+    if (smooth && (fft_size_smooth(n->Nx) || fft_size_smooth(n->Ny))) {
+        // the mixed-radix twiddle tables of every size the net transforms: built here, not inside a step
+        std::vector<int> sizes{n->Nx, n->Ny};
+        for (const Pair& q : n->pr) { sizes.push_back(q.Nx); sizes.push_back(q.Ny); }
+        for (int m : sizes) if (fft_size_mixed(m) && (e = fft_mixed_prepare(m)) != hipSuccess) break;
+        if (e != hipSuccess) { aefft_net_destroy(n); return fail(ctx, AEFFT_EHIP, "mixed-radix twiddle tables", e); }
+    }
     if (ensure_aux(ctx) != AEFFT_OK) { aefft_net_destroy(n); return AEFFT_EHIP; }
     *out = n;
     return aefft_net_reset_momentum(n);
+}
+
+extern "C" int aefft_net_create(aefft_ctx* ctx, const aefft_net_desc* d, aefft_net** out) { return net_create(ctx, d, 0, out); }
+extern "C" int aefft_net_create_ex(aefft_ctx* ctx, const aefft_net_desc* d, unsigned opts, aefft_net** out)
+{
+    if (opts & ~(unsigned)AEFFT_NET_SMOOTH_SIZES) return fail(ctx, AEFFT_EINVAL, "aefft_net_create_ex: unknown option bits");
+    return net_create(ctx, d, opts, out);
 }
 
 extern "C" int aefft_net_npairs(aefft_net* n) { return n ? n->L : -1; }
@@ -1623,14 +1664,14 @@ static int net_forward(aefft_net* n, const float* frames_d, float* recon_d, bool
         // all-reduce (an otherwise idle gap), and what follows on this stream (update, spectra, MSE) is latency-bound
         if (n->ev_mid_valid) HIPCHK(ctx, hipStreamWaitEvent(ctx->aux[1], n->ev_mid, 0));
         ctx->cur = ctx->aux[1];
-        const int rc = do_r2c(ctx, frames_d, n->Xf, (long)BF * n->D, n->Nx, n->Ny, n->pr[0].Nx, n->pr[0].Ny, WS_MID2);
+        const int rc = do_r2c(ctx, frames_d, n->Xf, (long)BF * n->D, n->Nx, n->Ny, n->pr[0].Nx, n->pr[0].Ny, WS_MID2, nullptr, ctx->in_u8);
         ctx->cur = ctx->stream;
         RET_IF(rc);
         HIPCHK(ctx, hipEventRecord(n->ev_r2c, ctx->aux[1]));
         HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, n->ev_r2c, 0));
     } else {
         const bool fork_r2c = want_fork && !need_chain;
-        RET_IF(do_r2c(ctx, frames_d, n->Xf, (long)BF * n->D, n->Nx, n->Ny, n->pr[0].Nx, n->pr[0].Ny, WS_MID, fork_r2c ? ctx->ev_fork : nullptr));
+        RET_IF(do_r2c(ctx, frames_d, n->Xf, (long)BF * n->D, n->Nx, n->Ny, n->pr[0].Nx, n->pr[0].Ny, WS_MID, fork_r2c ? ctx->ev_fork : nullptr, ctx->in_u8));
         fork_recorded = fork_r2c;
     }
     n->pr[0].X = n->op_state ? n->A0hat : n->Xf;

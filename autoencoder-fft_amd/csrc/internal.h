@@ -42,12 +42,17 @@ bool fft_size_supported_any(int n);
 size_t fft_any_ws_elems(long planes, int Nx, int Ny);
 hipError_t launch_r2c_any(const float* in, float2* out, float2* w1, float2* w2, long planes, int Nx, int Ny, hipStream_t st);
 hipError_t launch_c2r_any(const float2* in, float* out, float2* w1, float2* w2, long planes, int Nx, int Ny, float scale, hipStream_t st);
-// sizes that are not powers of two (cufftPlanMany takes any size, fft.cu:773-779): even n in 8..1024 through Bluestein's chirp-z form on the
-// power-of-two LDS passes; rows -> transpose -> rows -> transpose.  w1, w2: workspaces of fft_any_ws_elems complex each.
-bool fft_size_supported_any(int n);
-size_t fft_any_ws_elems(long planes, int Nx, int Ny);
-hipError_t launch_r2c_any(const float* in, float2* out, float2* w1, float2* w2, long planes, int Nx, int Ny, hipStream_t st);
-hipError_t launch_c2r_any(const float2* in, float* out, float2* w1, float2* w2, long planes, int Nx, int Ny, float scale, hipStream_t st);
+// ---- fft_mixed_kernels.hip -------------------------------------------------------------
+// Mixed-radix (2, 3, 4, 5, 8) passes for sizes with no prime factor above 5.  launch_r2c / launch_c2r pick them per axis: an axis whose
+// size is not a power of two (or whose packed width Wc the power-of-two pass cannot tile) takes the mixed-radix pass, the other axis keeps
+// its power-of-two pass; `mid` and the crop / zero-pad contract are the same.
+bool fft_size_mixed(int n);    // even n in 8..2048 whose prime factors are 2, 3, 5 (powers of two included)
+bool fft_size_smooth(int n);   // ... in 10..2048 and not a power of two: the sizes only the mixed-radix passes serve
+hipError_t fft_mixed_prepare(int n);     // builds the n-point twiddle table of the current device (done on first use otherwise)
+hipError_t launch_mix_r2c_rows(const void* in, float2* mid, long npairs, int Ny, int Wc, hipStream_t st, bool in_u8);
+hipError_t launch_mix_fwd_cols(const float2* mid, float2* out, long planes, int Nx, int Wc, int Nxs, hipStream_t st, hipEvent_t done);
+hipError_t launch_mix_inv_cols(const float2* in, float2* mid, long planes, int Nx, int Wc, int Nxi, hipStream_t st);
+hipError_t launch_mix_c2r_rows(const float2* mid, float* out, long npairs, int Ny, int Wc, float scale, hipStream_t st);
 // the same from a SMALL stored spectrum (the reconstruction's compact support) in one launch: the column pass as a direct Nxi-term sum
 // inside the row-pass workgroups, no `mid` (c2r_small_kernel)
 bool c2r_small_supported(int Nxi, int Nyi, int Nx, int Ny);

@@ -127,7 +127,8 @@ void autoenc_fft(Kernels& layers, KernelStack& net_c, BiasStack& net_cfreq, Bias
     if (!g_net.net || g_net.sig != sig) {
         if (g_net.net) aefft_net_destroy(g_net.net);
         aefft_net_desc d = {D, Nx, Ny, L, maps.data(), Nk.data(), Nl.data(), sc.data(), 1};
-        chk(aefft_net_create(ctx, &d, &g_net.net), "aefft_net_create");
+        // (smooth sizes -- the reference's users feed it camera frames, 640 x 480 -- take the mixed-radix transforms)
+        chk(aefft_net_create_ex(ctx, &d, AEFFT_NET_SMOOTH_SIZES, &g_net.net), "aefft_net_create_ex");
         g_net.sig = sig; rebuilt = true;
     }
     aefft_net* net = g_net.net;

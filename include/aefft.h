@@ -15,9 +15,13 @@
  *   - encoder kernel: c[dM][dD][Nk][Nl], bias b[dM]; decoder kernel f[dD][dM][Nk][Nl], bias p[dD]
  *   - batches add an outermost [B] dimension.  B = 1 reproduces the reference call exactly.
  *   - Nx, Ny: powers of two in 8..2048; pooling scales: powers of two -- for the resident network and the per-bin ops.
- *     The transforms and the spectral resize at op level (aefft_r2c, aefft_c2r, aefft_pool, aefft_r2c_pool, aefft_unpool_c2r) also serve
- *     EVEN sizes in 8..1024 that are not powers of two (cufftPlanMany takes any size, fft_backproplib.cu:773-779) and any integer scale,
- *     sized as the reference sizes it (:980-984: int(Nx / l) in float arithmetic; the resized grid must be even).
+ *     "Smooth" sizes -- even, 10..2048, no prime factor other than 2, 3, 5 (640, 480, 720, 1920, ...: camera frames) -- go through
+ *     mixed-radix transforms and are taken by the per-bin ops (aefft_kernel_spectrum, aefft_kernel_export, aefft_conv, aefft_gradient,
+ *     aefft_update) and, opted in with AEFFT_NET_SMOOTH_SIZES, by the resident network (aefft_net_create_ex), mixed freely with
+ *     power-of-two axes.  The transforms and the spectral resize at op level (aefft_r2c, aefft_c2r, aefft_pool, aefft_r2c_pool,
+ *     aefft_unpool_c2r) take smooth sizes up to 2048 and, through Bluestein's chirp-z form, every other EVEN size in 8..1024 (cufftPlanMany
+ *     takes any size, fft_backproplib.cu:773-779), with any integer scale, sized as the reference sizes it (:980-984: int(Nx / l) in float
+ *     arithmetic; the resized grid must be even).
  *   - every function returns AEFFT_OK (0) or an error code; aefft_last_error() gives the text.
  *     Work is enqueued on the context's stream; nothing blocks unless stated.
  *   - there is NO CPU fallback: every call fails with AEFFT_EHIP when no MI355X is present.
@@ -87,8 +91,10 @@ enum {
     AEFFT_F_NORCORR = 1 << 20,    /* spatial mode: dC through the back-convolved error (a dM-plane tensor) instead of the error-input correlation R */
     AEFFT_F_NOLAZYMSE = 1 << 21,   /* aefft_net_step_apply(mse_d = NULL) still sums the MSE slots in a launch of its own instead of leaving them to the next step's gradient launch */
     AEFFT_F_SMALLOVERLAP = 1 << 22, /* reconstructions below 8 MB take the side stream as well (the test suite's small nets then run the two-stream path of the large ones) */
-    AEFFT_F_CHAINMSE = 1 << 23     /* operator form with the chain: the innermost pair's post-update MSE inside the chain's per-bin items whatever the launch's size
+    AEFFT_F_CHAINMSE = 1 << 23,    /* operator form with the chain: the innermost pair's post-update MSE inside the chain's per-bin items whatever the launch's size
                                    * (by default only in launches of more than ~6 000 workgroups, which are bound by their resident slots) */
+    AEFFT_F_CHIRPZ = 1 << 24       /* grids with a smooth axis, both axes up to 1024, through Bluestein's chirp-z transforms instead of the mixed-radix ones (the two
+                                   * paths compared; power-of-two grids never take the mixed-radix passes) */
 };
 int aefft_ctx_set_flags(aefft_ctx* ctx, unsigned flags);
 unsigned aefft_ctx_get_flags(const aefft_ctx* ctx);
@@ -200,6 +206,15 @@ typedef struct {
 } aefft_net_desc;
 
 int aefft_net_create(aefft_ctx* ctx, const aefft_net_desc* desc, aefft_net** out);
+/* aefft_net_create with options.  opts = 0 is exactly aefft_net_create.  AEFFT_NET_SMOOTH_SIZES: Nx, Ny may also be smooth sizes
+ * (even, 10..2048, no prime factor above 5: 640 x 480, 1280 x 720, ...), mixed freely with power-of-two axes; every pair's pooled grid
+ * must be even and >= 8 (pooling scales powers of two, kernels no larger than the grid as always) -- AEFFT_EINVAL names the rule otherwise
+ * (480 over 5 pairs of scale 2: the 5th grid is 15).  A net with a smooth axis runs every step in the per-frame form: aefft_net_step_form
+ * returns AEFFT_FORM_PER_FRAME (the operator forms need the pruned kernel transforms, which take power-of-two grids); a power-of-two net
+ * created with the option runs exactly as one from aefft_net_create.  Every aefft_net_* entry
+ * point works on it, and the net sizes all its workspaces here. */
+enum { AEFFT_NET_SMOOTH_SIZES = 1u << 0 };
+int aefft_net_create_ex(aefft_ctx* ctx, const aefft_net_desc* desc, unsigned opts, aefft_net** out);
 void aefft_net_destroy(aefft_net* net);
 /* the descriptor back: number of pairs (negative for a null net); channels / maps / kernel support of pair l (any pointer nullable) */
 int aefft_net_npairs(aefft_net* net);
