@@ -1,4 +1,4 @@
-// Internal launch interface between the HIP kernel files and the C-ABI layer (aefft_capi.hip).
+// Internal launch interface between the HIP kernel files and the C-ABI layer (aefft_capi.hip, ops.hip, net.hip, net_step.hip).
 // Nothing here is exported; the public boundary is include/aefft.h and the three C++ headers.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -53,10 +53,6 @@ hipError_t launch_mix_r2c_rows(const void* in, float2* mid, long npairs, int Ny,
 hipError_t launch_mix_fwd_cols(const float2* mid, float2* out, long planes, int Nx, int Wc, int Nxs, hipStream_t st, hipEvent_t done);
 hipError_t launch_mix_inv_cols(const float2* in, float2* mid, long planes, int Nx, int Wc, int Nxi, hipStream_t st);
 hipError_t launch_mix_c2r_rows(const float2* mid, float* out, long npairs, int Ny, int Wc, float scale, hipStream_t st);
-// the same from a SMALL stored spectrum (the reconstruction's compact support) in one launch: the column pass as a direct Nxi-term sum
-// inside the row-pass workgroups, no `mid` (c2r_small_kernel)
-bool c2r_small_supported(int Nxi, int Nyi, int Nx, int Ny);
-hipError_t launch_c2r_small(const float2* in, float* out, long planes, int Nxi, int Nyi, int Nx, int Ny, float scale, hipStream_t st);
 
 // ---- spectral_kernels.hip --------------------------------------------------------------
 // Per-bin complex contraction  Out[r][c][bin] = alpha * sum_k opA(A[r][k][bin]) * opB(B[k][c][bin])

@@ -1,0 +1,104 @@
+// The resident network (aefft_net) and its pairs, shared by net.hip (lifetime, weights and spectra, chain set-up, layer exports)
+// and net_step.hip (forward, bursts, training step), with the helpers one of the two defines for the other.  Nothing here is exported.
+#pragma once
+#include "host.h"
+
+struct Pair {
+    int dD, dM, Nk, Nl, s;
+    int Nxin, Nyin;          // resolution before this pair's pooling
+    int Nx, Ny;              // working resolution (after pooling)
+    long P;
+    float *c, *f, *b, *p;
+    float *Dc, *Df, *Db, *Dp;
+    float2 *C, *F;
+    bool spectra_valid;
+    bool H_stale = false;    // the last (lazy) forward produced only the pooled part of H: recompute before reading H
+    float2* G = nullptr;     // [dD][dD][P] collapsed pair operator F.C/(dM dD) (post-update MSE; innermost pair's forward)
+    bool G_valid = false;    // G and beta (its DC bias) belong to the CURRENT weights (left by aefft_net_step_apply)
+    float* beta = nullptr;   // [dD]
+    float* Q = nullptr;      // [dD][dD][Qn][T*T], T = 2Nk-1: pruned inverse transform of S (weight_kernels.hip), Qn row-chunk partial sums
+    int Qn = 1;
+    float2* Oc = nullptr;    // [B][dD][Pc] decoder output on the support of the up-sampled spectra (the coarsest pair's grid); last pair: == O
+    float2* opA[2] = {nullptr, nullptr};   // [OPC][dD][P]  operator chain: the pair's input on the basis frames, two sets (the step in progress / the next step's)
+    float2* opO[2] = {nullptr, nullptr};   // [OPC][dD][Pc] ... its decoder output on the coarsest grid's support
+    float2* Cc = nullptr;    // [dM][dD][P of the next pair] C sampled where the next pair's grid lands (operator chain: its planar tiles read nothing else of C)
+    bool O_stale = false;    // the last (lazy) forward produced Oc only: expand before reading O
+    float2 *X, *H, *O;       // [B][dD][P], [B][dM][P], [B][dD][P] (X aliases the previous pair's H when s == 1)
+    size_t goff;             // offset (floats) of this pair's segment in the packed gradient buffer
+    float* es;               // [2*dD] DC bins of the error summed over the batch (inside the net scratch)
+    float2 *S, *dc, *df;     // per-pair gradient workspaces (pairs run concurrently on side streams); df == dc + W
+    float* part;             // kgrad partial sums
+};
+
+struct aefft_net {
+    aefft_ctx* ctx;
+    int D, Nx, Ny, L, B;
+    std::vector<Pair> pr;
+    std::vector<void*> allocs;
+    // operator form of the training step (opform_kernels.hip)
+    int Bc = 0;                // columns every activation buffer is allocated for: max(B, OPC)
+    float2* Xf = nullptr;      // [B][D][P0] input spectra of the frames (pair 0's X in the per-frame form)
+    float2* A0hat = nullptr;   // [OPC][D][P0] basis frames (pair 0's X in the operator form); null: D > OPC-1
+    float2* Mhat = nullptr;    // [OPC][OPC][P0] second moments of the batch
+    bool op_state = false;     // the activation buffers hold OPERATORS (basis-frame responses) of the last step_grad, not frames
+    // chain mode (the step's forward is chain_kernel): the operators live in their OWN buffers (Pair::opA / opO), two sets, because the
+    // tail launch of a step already runs the NEXT step's chain on the updated weights (it depends on the weights only) while the
+    // post-update MSE still reads this step's operators
+    bool op_chain = false;     // the last step_grad ran in chain mode: operators in set op_fwd, activation buffers NOT refreshed (act_stale)
+    bool act_stale = false;    // the activation buffers do not hold the last forward's frames (ensure_frames expands them from the operators)
+    bool upd_after_fwd = false; // aefft_net_step_apply has changed the weights since the step's forward: a layer export forms a skipped hidden layer with
+                               // the encoder of THAT forward, recovered as w + D (the momentum buffer holds the step that was applied)
+    bool chain_valid = false;  // set op_set holds the operators of the CURRENT weights
+    int op_set = 0, op_fwd = 0;
+    float2* Wp = nullptr;      // [Pc][packE] bin-major copy of the kernel spectra the coarsest-grid chain items read (kspec_packed_kernel)
+    aefft::PackArgs pack{};    // its description (static per net)
+    bool packed_valid = false; // Wp belongs to the current weights
+    float* grad = nullptr; size_t grad_n = 0;
+    float* scratch = nullptr;  // [mse_pre[L] | mse_post[L] | es of pair 0 (2*dD) | es of pair 1 | ...], zeroed once per step
+    size_t scratch_n = 0;
+    float* mse_pre = nullptr;  // = scratch
+    float* mse_post = nullptr; // = scratch + L
+    float* gtaps = nullptr;      // G' from the stored taps on HBM-sized grids: the (2Nk-1)^2 taps of every plane of every pair (gprime_from_taps)
+    float *gd_out = nullptr, *gd_part = nullptr;   // multiobjective mode: [cd | fd | bd | pd] per pair, and the chunk partial sums (gradient_diff_ws_floats)
+    bool mse_pending = false;   // the slots hold the unsummed post-update MSE of the last aefft_net_step_apply (mse_d == NULL): summed by the next step's wgrad launch or mse_flush
+    float mse_pending_scale = 1.f;
+    float* mse_slots = nullptr; // [L][MSE_SLOTS*MSE_SLOT_STRIDE] accumulators of the fused re-forward MSE (zero between uses)
+    float* mse_dev = nullptr;  // scratch for bursts
+    size_t mse_cap = 0;
+    const float* last_frames = nullptr;
+    bool last_frames_u8 = false;     // ... and they were 8-bit pixels
+    bool have_forward = false, have_grad = false;
+    int NxC = 0, NyC = 0; long Pc = 0;   // grid of the coarsest pair = support of every decoder output
+    bool compact = true;                 // the training step may keep decoder outputs on that support only
+    // input prefetch (aefft_net_set_input_ready): second buffer for pair 0's input spectra, end-of-step events, step counter
+    bool input_ready = false;
+    float2* X0alt = nullptr;
+    hipEvent_t ev_end[2] = {nullptr, nullptr}, ev_r2c = nullptr, ev_mid = nullptr;
+    bool ev_mid_valid = false;
+    bool ev_end_valid[2] = {false, false};
+    unsigned long step_no = 0;
+    float2* recon_exp = nullptr;  // [B][D][PO] per-frame output spectra of the reconstruction when they are written out (large supports, launch_recon)
+    unsigned ox_done = 0;         // bit l: the forward already launched pair l's support term S += sum_b Oc X^H
+    bool xx_done = false;         // the forward already launched S = -sum_b X X^H (grouped with the innermost decoder conv)
+    bool recon_pending = false;   // the reconstruction's inverse FFT is still running on aux[0]
+    float* recon_deferred = nullptr;   // pipelined mode: the reconstruction is launched at the end of the gradient half
+    bool burst = false;        // inside aefft_net_train_pair (its MSE slots are zeroed up front, not by the update kernel)
+    // shared scratch sized for the largest pair
+    bool fuse_crop = true;     // encoder convs also write the next pair's cropped input (no resize launches)
+    bool pruned = true;        // every pair's kernel support has a pruned transform -> no shared FFT workspace in the backward
+    float* real;
+};
+
+namespace aefft {
+
+// ---- net.hip ---------------------------------------------------------------------------
+int net_alloc(aefft_net* n, void** p, size_t bytes);
+template <typename T> int net_alloc_t(aefft_net* n, T** p, size_t count) { return net_alloc(n, reinterpret_cast<void**>(p), count * sizeof(T)); }
+int pair_spectra(aefft_net* n, Pair& q);
+int ensure_spectra(aefft_net* n, Pair& q);
+
+// ---- net_step.hip ----------------------------------------------------------------------
+int ensure_frames(aefft_net* n);
+int mark_step_point(aefft_net* n);
+
+}  // namespace aefft

@@ -1,0 +1,1113 @@
+// C-ABI layer (include/aefft.h), the resident network at work: the forward (net_forward, the reconstruction launch_recon, the operator
+// chain), the per-frame expansion of an operator-form step (ensure_frames), bursts (aefft_net_train_pair), the grouped gradient and
+// update phases (grads_grouped, apply_grouped, reforward_mse), input prefetch, and the aefft_net_forward* / aefft_net_step_* entry points.
+#include "net.h"
+
+#include <algorithm>
+#include <vector>
+
+using namespace aefft;
+
+// problems of the spectra launch that serve the operator chain: Cc_l for l < L-1 (C sampled where the next pair's grid lands)
+static int cc_problems(aefft_net* n, PrunedGroup& pg, int first, double* bytes)
+{
+    int k = first;
+    for (int l = 0; l + 1 < n->L; ++l) {
+        Pair& q = n->pr[l];
+        const Pair& nx = n->pr[l + 1];
+        pg.q[k] = PrunedProb{q.c, q.Cc, (long)q.dM * q.dD, nx.Nx, nx.Ny, 1.0f, q.Nx, q.Ny};
+        if (bytes) *bytes += (double)q.dM * q.dD * (nx.P * 8.0 + q.Nk * q.Nl * 4.0);
+        ++k;
+    }
+    return k;
+}
+
+// G'_l = F_l.C_l / (dM dD) [dD][dD][P] of the STORED weights of every pair, into Pair::G: the spectrum of the (2Nk-1)^2-tap kernel f (*) c, taps
+// formed inside the transforming workgroups (gspec_gbody).  false: shapes not served.
+static int gprime_from_taps(aefft_net* n, bool* done)
+{
+    *done = false;
+    aefft_ctx* ctx = n->ctx;
+    if (n->L > 8 || n->pr[0].Nk != n->pr[0].Nl || (n->pr[0].Nk != 3 && n->pr[0].Nk != 5)) return AEFFT_OK;
+    PrunedGroup pg{};
+    GtapsGroup tg{};
+    double bytes = 0;
+    const int TT = (2 * n->pr[0].Nk - 1) * (2 * n->pr[0].Nk - 1);
+    bool chunked = false;                                  // some plane is transformed by several row-chunk workgroups: the taps are formed once, in a launch in front
+    for (int l = 0; l < n->L; ++l) {
+        Pair& q = n->pr[l];
+        if (q.Nk != n->pr[0].Nk || q.Nl != n->pr[0].Nk || !pruned_supported(q.Nk, q.Nl, q.Nx, q.Ny) || (double)q.dD * q.dD * q.P * 8.0 >= 4294967296.0) return AEFFT_OK;
+        pg.q[l] = PrunedProb{nullptr, q.G, (long)q.dD * q.dD, q.Nx, q.Ny, 1.0f, 0, 0};
+        pg.gsrc[l] = GtapSrc{q.c, q.f, q.dM, q.dD, 1.0f / ((float)q.dM * (float)q.dD)};
+        bytes += (double)q.dD * q.dD * q.P * 8.0 + 2.0 * q.dM * q.dD * q.Nk * q.Nl * 4.0;
+        chunked = chunked || q.Nx > 64;
+    }
+    if (chunked) {
+        // taps once per plane, then their spectra as an ordinary pruned transform of (2Nk-1)^2-tap kernels (its own kernel instantiation:
+        // the planar-spectra launch keeps its code)
+        if (!n->gtaps) {
+            size_t nt = 0;
+            for (const Pair& q : n->pr) nt += (size_t)q.dD * q.dD * TT;
+            RET_IF(net_alloc_t(n, &n->gtaps, nt));
+        }
+        PrunedGroup pt{};
+        float* o = n->gtaps;
+        for (int l = 0; l < n->L; ++l) {
+            const Pair& q = n->pr[l];
+            tg.gs[l] = pg.gsrc[l]; tg.out[l] = o;
+            pt.q[l] = PrunedProb{o, q.G, (long)q.dD * q.dD, q.Nx, q.Ny, 1.0f, 0, 0};
+            o += (size_t)q.dD * q.dD * TT;
+        }
+        tg.n = pt.n = n->L;
+        hipError_t e;
+        {
+            Bracket br(ctx, KID_KSPEC, bytes);
+            e = launch_gtaps_group(tg, n->pr[0].Nk, ctx->cur);
+            if (e == hipSuccess) e = launch_kspec_group_taps(pt, ctx->tw, 2 * n->pr[0].Nk - 1, ctx->cur);
+        }
+        if (e == hipSuccess) { *done = true; return AEFFT_OK; }
+        if (e != hipErrorInvalidValue) return fail(ctx, AEFFT_EHIP, "G'(stored taps)", e);
+        (void)hipGetLastError();                           // (shapes these launches do not serve: taps formed in the transforming workgroups, below)
+    }
+    pg.n = n->L;
+    hipError_t e;
+    {
+        Bracket br(ctx, KID_KSPEC, bytes);
+        e = launch_kspec_group(pg, ctx->tw, n->pr[0].Nk, n->pr[0].Nl, ctx->cur, nullptr, nullptr);
+    }
+    if (e == hipSuccess) { *done = true; return AEFFT_OK; }
+    if (e != hipErrorInvalidValue) return fail(ctx, AEFFT_EHIP, "G'(taps)", e);
+    (void)hipGetLastError();
+    return AEFFT_OK;
+}
+
+// the bin-major record Wp (and the compact Cc planes) of the CURRENT weights
+static int ensure_packed(aefft_net* n)
+{
+    if (!n->Wp || n->packed_valid) return AEFFT_OK;
+    aefft_ctx* ctx = n->ctx;
+    double bytes = (double)n->pack.Pc * n->pack.E * 8.0;
+    hipError_t e;
+    if (n->pr[0].Cc) {
+        PrunedGroup pg{};
+        pg.n = cc_problems(n, pg, 0, &bytes);
+        n->pack.upd = 0;
+        Bracket br(ctx, KID_KSPEC, bytes);
+        e = launch_kspec_group(pg, ctx->tw, n->pr[0].Nk, n->pr[0].Nl, ctx->cur, &n->pack, nullptr);
+    } else {
+        Bracket br(ctx, KID_KSPEC, bytes);
+        e = launch_kspec_packed(n->pack, ctx->cur);
+    }
+    if (e != hipSuccess) return fail(ctx, AEFFT_EHIP, "kspec_packed", e);
+    n->packed_valid = true;
+    return AEFFT_OK;
+}
+
+// the training step's forward runs as ONE chain launch on the basis frames (chain_kernel) under these switches
+static bool chain_switches_ok() { return !(dev_flags & (AEFFT_F_NOCHAIN | AEFFT_F_NOLAZY | AEFFT_F_NOCOMPACT | AEFFT_F_NOGROUP | AEFFT_F_NOMFMA | AEFFT_F_NOFUSECROP)); }
+
+// The training step runs in operator form (opform_kernels.hip) when every pair has the Q-path gradient (equal square 3x3 / 5x5
+// supports with pruned transforms) and the input has at most OPC-1 channels.
+static bool op_eligible(const aefft_net* n)
+{
+    if (flag(AEFFT_F_NOOPFORM) || flag(AEFFT_F_NOQPATH) || !n->A0hat || n->L > 8) return false;
+    const Pair& q0 = n->pr[0];
+    if (q0.Nk != q0.Nl || (q0.Nk != 3 && q0.Nk != 5)) return false;
+    for (const Pair& q : n->pr) if (q.Nk != q0.Nk || q.Nl != q0.Nl || !q.Q || !pruned_supported(q.Nk, q.Nl, q.Nx, q.Ny)) return false;
+    // channel counts the operator-form kernels' LDS tiles take (msgrad_kernel: 2*OPC*dD*8 complex; opmse: OPC*(dD+dM)*4 complex): a
+    // launch declined in the middle of step_apply would leave a fused update half applied, so the step form is decided here
+    for (const Pair& q : n->pr) if (q.dD > 256 || q.dM > 512 || q.dD + q.dM > 1024) return false;
+    return true;
+}
+
+// operator form: where pair l's operators of the step in progress are (A_l [OPC][dD][P], O^_l [OPC][dD][PO] on the grid nxo x nyo)
+struct OpView { const float2 *A, *O; int nxo, nyo; long PO; };
+static bool op_mode(const aefft_net* n) { return n->op_state || n->op_chain; }
+static OpView op_view(const aefft_net* n, int l)
+{
+    const Pair& q = n->pr[l];
+    if (n->op_chain) return OpView{l == 0 ? n->A0hat : q.opA[n->op_fwd], q.opO[n->op_fwd], n->NxC, n->NyC, n->Pc};
+    const bool st = q.O_stale;
+    return OpView{q.X, st ? q.Oc : q.O, st ? n->NxC : q.Nx, st ? n->NyC : q.Ny, st ? n->Pc : q.P};
+}
+static void fill_chain(aefft_net* n, ChainArgs& ca, int set, double* bytes)
+{
+    const int L = n->L;
+    const bool cc = L == 1 || n->pr[0].Cc != nullptr;
+    for (int l = 0; l < L; ++l) {
+        Pair& q = n->pr[l];
+        ca.lv[l] = ChainLevel{q.C, q.F, q.b, q.p, l == 0 ? n->A0hat : q.opA[set], q.opO[set], q.dD, q.dM, q.Nx, q.Ny, q.P, cc ? q.Cc : nullptr};
+        const double cb = (l + 1 < L) ? (double)n->pr[l + 1].P : (double)q.P;
+        if (bytes) *bytes += ((double)q.dM * q.dD * (cb + n->Pc) + (double)OPC * q.dD * (q.P + n->Pc)) * 8.0;
+    }
+    ca.L = L; ca.D0 = n->D; ca.Pc = n->Pc; ca.Wp = n->Wp; ca.E = n->pack.E;
+}
+
+// the reconstruction's inverse FFT (fft_backproplib.cu:1373) on ctx->cur; operator form: the per-frame spectra are expanded first
+static int launch_recon(aefft_net* n, float* recon_d, int wsid)
+{
+    aefft_ctx* ctx = n->ctx;
+    Pair& q = n->pr[0];
+    const OpView ov = op_mode(n) ? op_view(n, 0) : OpView{nullptr, q.O_stale ? q.Oc : q.O, q.O_stale ? n->NxC : q.Nx, q.O_stale ? n->NyC : q.Ny, 0};
+    const float2* src = ov.O;
+    const int nxo = ov.nxo, nyo = ov.nyo;
+    if (op_mode(n)) {
+        static_assert(OPIN_COLS == OPC, "operator width");
+        const long PO = bins(nxo, nyo);
+        if ((double)n->B * q.dD * PO * 8.0 > 16e6) {
+            // large supports (no pooling: the decoder output lives on the whole grid): the per-frame spectra O_0,b = O^_0 [x_b; 1] are
+            // written out once by a coalesced pass (7 plane-ordered loads per output) and the inverse transform reads them back.  Evaluated
+            // inside the column pass instead, the same 7 loads are strided 128-byte pieces: 1.1 ms against 0.2 ms at cfg3-P1.
+            if (!n->recon_exp) RET_IF(net_alloc_t(n, &n->recon_exp, (size_t)n->B * q.dD * PO));
+            {
+                Bracket br(ctx, KID_OPFORM, ((double)OPC * q.dD * PO + (double)n->B * q.dD * PO + (double)n->B * q.dD * q.P) * 8.0);
+                hipError_t e = launch_recon_expand(src, n->Xf, n->recon_exp, n->B, q.dD, q.Nx, q.Ny, nxo, nyo, ctx->cur);
+                if (e != hipSuccess) return fail(ctx, AEFFT_EHIP, "recon_expand", e);
+            }
+            return do_c2r(ctx, n->recon_exp, recon_d, (long)n->B * q.dD, nxo, nyo, n->Nx, n->Ny, 1.0f / ((float)n->Nx * (float)n->Ny), wsid);
+        }
+        // small supports: O_0,b = O^_0 [x_b; 1] is evaluated inside the column pass of the inverse transform (no stored planes)
+        const OpIn op{src, n->Xf, q.dD, q.Nx, q.Ny};
+        return do_c2r(ctx, nullptr, recon_d, (long)n->B * q.dD, nxo, nyo, n->Nx, n->Ny, 1.0f / ((float)n->Nx * (float)n->Ny), wsid, &op);
+    }
+    return do_c2r(ctx, src, recon_d, (long)n->B * q.dD, nxo, nyo, n->Nx, n->Ny, 1.0f / ((float)n->Nx * (float)n->Ny), wsid);
+}
+
+// lazy: encoder outputs that are only consumed through pool_fft are computed on the pooled grid alone (the bins the crop
+// discards are never formed; aefft_net_get_layer recomputes such a layer on demand).  The training step uses it.
+// op: run the network on the OPC basis frames (the activation buffers then hold the per-bin operators A_l, O^_l) -- the
+// frames themselves only go through the input transform, the second moments and the reconstruction.
+static int net_forward(aefft_net* n, const float* frames_d, float* recon_d, bool lazy, bool op = false)
+{
+    if (!n || !frames_d) return fail(n ? n->ctx : nullptr, AEFFT_EINVAL, "aefft_net_forward: bad argument");
+    aefft_ctx* ctx = n->ctx;
+    const int BF = n->B;                       // frames
+    const int B = op ? (int)OPC : n->B;        // columns of the activation buffers
+    const int L = n->L;
+    struct BiasColGuard { aefft_ctx* c; ~BiasColGuard() { c->biasColP1 = 0; } } guard{ctx};
+    ctx->biasColP1 = op ? (int)OPC : 0;        // conv_k biases: the affine column only
+    RET_IF(join_recon(ctx));
+    n->xx_done = false; n->ox_done = 0;
+    n->upd_after_fwd = false;
+    // the whole network on the basis frames in one launch (chain_kernel): hidden layers not materialised, decoder outputs on the
+    // coarsest grid's support, operators in their own buffers
+    const bool chain_plan = op && lazy && n->Wp && (n->compact || L == 1) && chain_switches_ok();
+    // (the chain launch reads the bin-major record Wp and the compact Cc planes only: planar spectra that a training step in operator
+    // form does not refresh are formed when something else asks for them)
+    const bool chain_cc = chain_plan && (L == 1 || n->pr[0].Cc != nullptr);
+    n->op_state = op && !chain_plan;
+    n->op_chain = chain_plan;
+    n->act_stale = chain_plan;
+    for (int l = 0; l < L; ++l) if (!(chain_cc || (chain_plan && l == L - 1 && L > 1))) RET_IF(ensure_spectra(n, n->pr[l]));
+    // the reconstruction's side stream forks behind the last launch in front of the gradient kernels -- the input transform's column
+    // pass, or the chain launch when the operators of the current weights are not at hand (first step, weights set from outside) --
+    // through that dispatch's own completion signal
+    // (reconstructions beyond ~256 MB -- 32 frames of 1024^2 -- stay on the context stream: beside their row pass the pruned inverse transform
+    // of S stretches from 42 to 145 us and the side stream costs more than it hides, 1.084 vs 1.057 ms per cfg5 step; at cfg3 it saves 15 of 203 us)
+    // ... and reconstructions below ~8 MB (cfg2: one 256^2 frame, 11 us of kernels) stay there as well: the fork and join packets cost more than the
+    // two kernels they would hide (0.074 vs 0.076 ms per cfg2 step)
+    const double recon_bytes = (double)n->B * n->D * n->Nx * n->Ny * 4.0;
+    const bool overlap_pays = recon_bytes <= 256e6 && (recon_bytes >= 8e6 || flag(AEFFT_F_SMALLOVERLAP));
+    const bool want_fork = chain_plan && recon_d && ctx->aux[0] != nullptr && !flag(AEFFT_F_NOOVERLAP) && overlap_pays && !ctx->prof &&
+                           !(n->input_ready && !flag(AEFFT_F_NODEFER)) && ctx->cur == ctx->stream;
+    const bool need_chain = chain_plan && !n->chain_valid;
+    bool fork_recorded = false;
+    // encoder (fft_backproplib.cu:1340-1357): R2C fused with pair 0's pooling, then pool -> conv per pair
+    const bool prefetch = lazy && n->input_ready && n->X0alt && ctx->aux[1] != nullptr && !ctx->prof && !flag(AEFFT_F_NOPREFETCH);
+    if (prefetch) {
+        // The caller guarantees the frames are complete: their R2C goes to a side stream and may overlap the tail of the previous
+        // step.  It writes the OTHER input-spectra buffer (the current one is still read by that tail), which was last read two
+        // steps ago: wait for that step's end only.
+        std::swap(n->Xf, n->X0alt);
+        if (n->ev_end_valid[n->step_no & 1]) HIPCHK(ctx, hipStreamWaitEvent(ctx->aux[1], n->ev_end[n->step_no & 1], 0));
+        // not earlier than the end of the previous step's gradient half: that is where a data-parallel run waits for its
+        // all-reduce (an otherwise idle gap), and what follows on this stream (update, spectra, MSE) is latency-bound
+        if (n->ev_mid_valid) HIPCHK(ctx, hipStreamWaitEvent(ctx->aux[1], n->ev_mid, 0));
+        ctx->cur = ctx->aux[1];
+        const int rc = do_r2c(ctx, frames_d, n->Xf, (long)BF * n->D, n->Nx, n->Ny, n->pr[0].Nx, n->pr[0].Ny, WS_MID2, nullptr, ctx->in_u8);
+        ctx->cur = ctx->stream;
+        RET_IF(rc);
+        HIPCHK(ctx, hipEventRecord(n->ev_r2c, ctx->aux[1]));
+        HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, n->ev_r2c, 0));
+    } else {
+        const bool fork_r2c = want_fork && !need_chain;
+        RET_IF(do_r2c(ctx, frames_d, n->Xf, (long)BF * n->D, n->Nx, n->Ny, n->pr[0].Nx, n->pr[0].Ny, WS_MID, fork_r2c ? ctx->ev_fork : nullptr, ctx->in_u8));
+        fork_recorded = fork_r2c;
+    }
+    n->pr[0].X = n->op_state ? n->A0hat : n->Xf;
+    bool chained = false;
+    if (chain_plan) {
+        if (need_chain) {
+            RET_IF(ensure_packed(n));
+            ChainArgs ca{};
+            double bytes = 0;
+            fill_chain(n, ca, n->op_set, &bytes);
+            Bracket br(ctx, KID_CHAIN, bytes);
+            const bool fork_here = want_fork && !fork_recorded;
+            hipError_t e = launch_chain(ca, ctx->cur, fork_here ? ctx->ev_fork : nullptr);
+            if (e != hipSuccess) return fail(ctx, AEFFT_EHIP, "chain", e);
+            fork_recorded = fork_recorded || fork_here;
+            n->chain_valid = true;
+        }
+        n->op_fwd = n->op_set;
+        for (int l = 0; l < L; ++l) { Pair& q = n->pr[l]; q.H_stale = true; q.O_stale = q.P != n->Pc; }      // (what ensure_frames leaves in the activation buffers)
+        chained = true;
+    }
+    for (int l = 0; l < L && !chained; ++l) {
+        Pair& q = n->pr[l];
+        // the next pair's spectral down-sampling (pool_fft, :1346) is written by this conv's epilogue: no resize launch
+        const bool fuse = (l + 1 < L) && n->pr[l + 1].s != 1 && n->fuse_crop && !flag(AEFFT_F_NOFUSECROP);
+        q.H_stale = false;
+        if (lazy && !op && l == L - 1 && q.G_valid && !flag(AEFFT_F_NOGFWD)) {
+            // innermost pair of a training step: its hidden layer feeds only its own decoder conv, and the previous step left
+            // the collapsed operator of the CURRENT weights behind (G = F.C/(dM dD) in S, DC bias in beta): O = G X + beta below,
+            // a quarter of the arithmetic and bytes of conv_k o conv_k, no H.
+            q.H_stale = true;
+            continue;
+        }
+        if (fuse && lazy) {
+            const bool nolazy = flag(AEFFT_F_NOLAZY);
+            const Pair& nx = n->pr[l + 1];
+            bool done = false;
+            if (!nolazy) RET_IF(do_conv_pooled(ctx, q.X, q.C, q.b, nx.X, B, q.dM, q.dD, q.Nx, q.Ny, nx.Nx, nx.Ny, &done));
+            if (done) { q.H_stale = true; continue; }
+        }
+        if (fuse) { const Pair& nx = n->pr[l + 1]; RET_IF(do_conv(ctx, q.X, q.C, q.b, q.H, B, q.dM, q.dD, q.Nx, q.Ny, nx.X, nx.Nx, nx.Ny)); }
+        else RET_IF(do_conv(ctx, q.X, q.C, q.b, q.H, B, q.dM, q.dD, q.Nx, q.Ny));
+        if (!fuse && l + 1 < L && n->pr[l + 1].s != 1) {
+            const Pair& nx = n->pr[l + 1];
+            RET_IF(do_resize(ctx, q.H, nx.X, (long)B * nx.dD, nx.Nxin, nx.Nyin, nx.Nx, nx.Ny));
+        }
+    }
+    // decoder (:1356-1361): conv then zero-pad up-sampling.  The up-sampled tensor is never stored: the next
+    // decoder conv (and the final C2R) read the small spectrum through the zero-pad index map.
+    const bool nocompact = flag(AEFFT_F_NOCOMPACT);
+    bool compact = lazy && n->compact && !nocompact && L > 1;
+    for (int l = L - 1; l >= 0 && !chained; --l) {
+        Pair& q = n->pr[l];
+        q.O_stale = false;
+        if (l == L - 1) {
+            if (q.H_stale) {                       // (set above: G route)
+                Contract k{};
+                k.A = q.G; k.a_r = (long)q.dD * q.P; k.a_k = q.P;
+                k.B = q.X; k.b_k = q.P; k.b_c = (long)q.dD * q.P;
+                k.Out = q.O; k.o_r = q.P; k.o_c = (long)q.dD * q.P;
+                k.R = q.dD; k.C = B; k.K = q.dD; k.P = q.P;
+                k.bias = q.beta; k.biasScale = (float)q.Nx * (float)q.Ny; k.biasAfterFirst = true;
+                // the batch-first gradient term S = -sum_b X X^H needs only the encoder outputs: it shares this launch
+                // (the decoder chain that follows is a sequence of small dependent launches)
+                n->xx_done = false; n->ox_done = 0;
+                if (compact && n->pr[0].P != n->Pc && L + 1 <= 8 && !flag(AEFFT_F_NOGROUP)) {
+                    Contract qs[8];
+                    qs[0] = k;
+                    for (int l2 = 0; l2 < L; ++l2) { Pair& q2 = n->pr[l2]; qs[1 + l2] = mk_XXneg(q2.X, q2.S, B, q2.dD, q2.P); }
+                    RET_IF(do_contract_group(ctx, qs, L + 1, L + 1, 0));
+                    n->xx_done = true;
+                } else
+                RET_IF(do_contract(ctx, k));
+            } else RET_IF(do_conv(ctx, q.H, q.F, q.p, q.O, B, q.dD, q.dM, q.Nx, q.Ny));
+            continue;
+        }
+        const Pair& in = n->pr[l + 1];
+        if (compact && q.P != n->Pc) {
+            // Up-sampled spectra are zero outside the image of the coarsest grid, and conv_k maps zero to zero (the bias sits on
+            // the DC bin, inside it): every decoder output lives on those Pc bins.  The training step computes and stores only them:
+            //   Oc_l[b][d][s] = sum_m F_l[d][m][map_l(s)] * Oc_{l+1}[b][m][s] / dD + p[d] Nx Ny [s == 0]
+            Contract k{};
+            k.A = q.F; k.a_r = (long)q.dM * q.P; k.a_k = q.P;
+            k.B = in.Oc; k.b_k = n->Pc; k.b_c = (long)q.dM * n->Pc;
+            k.Out = q.Oc; k.o_r = n->Pc; k.o_c = (long)q.dD * n->Pc;
+            k.R = q.dD; k.C = B; k.K = q.dM; k.P = n->Pc;
+            k.preDivB = (float)q.dD;
+            k.bias = q.p; k.biasScale = (float)q.Nx * (float)q.Ny; k.biasAfterFirst = true;
+            k.gdNx = q.Nx; k.gdNy = q.Ny; k.gdNxs = n->NxC; k.gdNys = n->NyC; k.gdMask = 1;
+            if (n->xx_done && !op && !flag(AEFFT_F_NOGROUP) && !flag(AEFFT_F_NOMFMA)) {
+                // S = -sum_b X X^H is already out: the support term of the NEXT-inner pair (its decoder output is final) rides along
+                Pair& qi = n->pr[l + 1];
+                Contract qs[2] = {k, qi.O_stale ? mk_OX(qi.Oc, qi.X, qi.S, B, qi.dD, qi.P, n->Pc, qi.Nx, qi.Ny, n->NxC, n->NyC)
+                                                : mk_OX(qi.O, qi.X, qi.S, B, qi.dD, qi.P, qi.P, qi.Nx, qi.Ny, qi.Nx, qi.Ny)};
+                RET_IF(do_contract_group(ctx, qs, 2, 2, 0));
+                n->ox_done |= 1u << (l + 1);
+                q.O_stale = true;
+                continue;
+            }
+            hipError_t e;
+            {
+                Bracket br(ctx, KID_CONTRACT, ((double)k.R * k.K + (double)k.K * k.C + (double)k.R * k.C) * k.P * 8.0);
+                e = launch_contract(bc(ctx, k), ctx->cur);
+            }
+            if (e == hipSuccess) { q.O_stale = true; continue; }
+            if (e != hipErrorInvalidValue) return fail(ctx, AEFFT_EHIP, "contract(compact decoder)", e);
+            (void)hipGetLastError();
+            // declined: from here down the full-grid decoder; the levels already done are expanded first
+            n->compact = compact = false;
+            for (int l2 = L - 2; l2 > l; --l2) {
+                Pair& q2 = n->pr[l2];
+                RET_IF(do_resize(ctx, q2.Oc, q2.O, (long)B * q2.dD, n->NxC, n->NyC, q2.Nx, q2.Ny));
+                q2.O_stale = false;
+            }
+        }
+        RET_IF(do_conv_up(ctx, in.O, q.F, q.p, q.O, B, q.dD, q.dM, q.Nx, q.Ny, in.Nx, in.Ny));
+    }
+    if (recon_d) {   // :1373 fft_inv of the up-sampled last output, fused zero-pad
+        const bool nooverlap = flag(AEFFT_F_NOOVERLAP);
+        const bool async = lazy && ctx->aux[0] != nullptr && !nooverlap && overlap_pays && !ctx->prof;
+        n->recon_deferred = nullptr;
+        if (async && n->input_ready && !flag(AEFFT_F_NODEFER)) {
+            // pipelined loop (aefft_net_set_input_ready): launched by aefft_net_step_grad after the gradient half instead
+            n->recon_deferred = recon_d;
+            n->last_frames = frames_d; n->last_frames_u8 = ctx->in_u8;
+            n->have_forward = true; n->have_grad = false;
+            return AEFFT_OK;
+        }
+        if (async) {
+            // training step: nothing downstream reads the reconstruction, so its (bandwidth-bound) inverse FFT runs on a side
+            // stream underneath the latency-bound gradient contractions; aefft_net_step_grad joins it before returning
+            if (!fork_recorded) HIPCHK(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
+            HIPCHK(ctx, hipStreamWaitEvent(ctx->aux[0], ctx->ev_fork, 0));
+            ctx->cur = ctx->aux[0];
+        }
+        // (a side-stream transform has its own column/row workspace: the main stream's FFTs of non-pruned kernel supports use WS_MID)
+        const int rc = launch_recon(n, recon_d, async ? WS_MID3 : WS_MID);
+        ctx->cur = ctx->stream;
+        RET_IF(rc);
+        n->recon_pending = async;
+    }
+    n->last_frames = frames_d; n->last_frames_u8 = ctx->in_u8;
+    n->have_forward = true; n->have_grad = false;
+    return AEFFT_OK;
+}
+
+// Layer exports and bursts read per-frame spectra: after a training step in operator form the activation buffers hold operators,
+// so the per-frame forward of the same frames is run first (with the CURRENT weights; the step's gradient state is kept).
+int aefft::ensure_frames(aefft_net* n)
+{
+    if (n->op_chain && n->act_stale) {
+        // chain mode: X_l,b = A_l [x_b; 1], O_l,b = O^_l [x_b; 1] from the RESIDENT input spectra and the operators of the last
+        // step_grad (set op_fwd: intact until the step after next's tail launch) -- neither the caller's frame buffer nor the
+        // current (possibly updated) weights enter.  Hidden layers stay to be formed on request (H_stale).
+        aefft_ctx* ctx = n->ctx;
+        const Pair& q0 = n->pr[0];
+        for (int l = 0; l < n->L; ++l) {
+            Pair& q = n->pr[l];
+            hipError_t e = hipSuccess;
+            if (l > 0) {
+                Bracket br(ctx, KID_OPFORM, ((double)OPC * q.dD + (double)n->B * (q.dD + n->D)) * q.P * 8.0);
+                e = launch_op_expand(q.opA[n->op_fwd], n->Xf, q.X, n->B, n->D, q.dD, q0.Nx, q0.Ny, q.Nx, q.Ny, ctx->cur);
+            }
+            if (e == hipSuccess) {
+                Bracket br(ctx, KID_OPFORM, ((double)OPC * q.dD + (double)n->B * (q.dD + n->D)) * n->Pc * 8.0);
+                e = launch_op_expand(q.opO[n->op_fwd], n->Xf, q.P != n->Pc ? q.Oc : q.O, n->B, n->D, q.dD, q0.Nx, q0.Ny, n->NxC, n->NyC, ctx->cur);
+            }
+            if (e != hipSuccess) return fail(ctx, AEFFT_EHIP, "op_expand", e);
+            q.H_stale = true; q.O_stale = q.P != n->Pc;
+        }
+        n->pr[0].X = n->Xf;
+        n->act_stale = false;
+        return AEFFT_OK;
+    }
+    if (!n->op_state) return AEFFT_OK;
+    // (operator form without the chain launch: the activation buffers hold the operators themselves; the per-frame forward of the
+    // same frames is run -- the caller's frame buffer must still hold them, include/aefft.h)
+    const bool hg = n->have_grad, u8 = n->ctx->in_u8;
+    n->ctx->in_u8 = n->last_frames_u8;
+    const int rcf = net_forward(n, n->last_frames, nullptr, false, false);
+    n->ctx->in_u8 = u8;
+    RET_IF(rcf);
+    n->have_grad = hg;
+    return AEFFT_OK;
+}
+
+extern "C" int aefft_net_forward(aefft_net* n, const float* frames_d, float* recon_d)
+{
+    RET_IF(net_forward(n, frames_d, recon_d, false));
+    return mark_step_point(n);
+}
+
+// expand a decoder output that the training-step forward kept on its support only
+static int ensure_O(aefft_net* n, Pair& q)
+{
+    if (!q.O_stale) return AEFFT_OK;
+    RET_IF(do_resize(n->ctx, q.Oc, q.O, (long)n->B * q.dD, n->NxC, n->NyC, q.Nx, q.Ny));
+    q.O_stale = false;
+    return AEFFT_OK;
+}
+
+// The slot sums of the last step's post-update MSE when aefft_net_step_apply was told not to deliver them (mse_d == NULL): they ride as a
+// trailing workgroup of the next step's gradient launch (grads_grouped); anything else that needs them first calls this.
+static int mse_flush(aefft_net* n)
+{
+    if (!n->mse_pending) return AEFFT_OK;
+    aefft_ctx* ctx = n->ctx;
+    Bracket br(ctx, KID_DIFFMSE, 4.0 * n->L * MSE_SLOTS);
+    hipError_t e = launch_mse_finish(n->mse_slots, n->mse_post, nullptr, n->L, ctx->cur, nullptr, n->grad + n->grad_n, n->mse_pending_scale);
+    if (e != hipSuccess) return fail(ctx, AEFFT_EHIP, "mse_finish(deferred)", e);
+    n->mse_pending = false;
+    return AEFFT_OK;
+}
+
+// gradient half of one loop-body iteration on pair q: needs X (= T, autoencoder.cpp:194) and the current O.
+static int pair_grad(aefft_net* n, Pair& q)
+{
+    aefft_ctx* ctx = n->ctx;
+    float* g = n->grad + q.goff;
+    const size_t nk = (size_t)q.dM * q.dD * q.Nk * q.Nl;
+    RET_IF(ensure_O(n, q));
+    RET_IF(do_gradient(ctx, q.X, q.X, q.O, q.C, q.F, q.b, q.S, q.dc, q.df, g + 2 * nk, g + 2 * nk + q.dM, n->B, q.dM, q.dD, q.Nx, q.Ny));
+    const long planes = (long)q.dM * q.dD;
+    if (q.part) return do_c2r_shrink(ctx, q.dc, g, nullptr, q.part, 2 * planes, q.Nx, q.Ny, q.Nk, q.Nl);   // dc|df -> dck|dfk, one launch
+    RET_IF(do_c2r_shrink(ctx, q.dc, g, n->real, nullptr, planes, q.Nx, q.Ny, q.Nk, q.Nl));
+    return do_c2r_shrink(ctx, q.df, g + nk, n->real, nullptr, planes, q.Nx, q.Ny, q.Nk, q.Nl);
+}
+
+// update half: weights, new spectra, re-forward of the pair alone, post-update MSE accumulated into *mse_slot (pre-zeroed)
+static int pair_apply(aefft_net* n, Pair& q, float del, int maxdiff, int sym, float gscale, float* mse_slot)
+{
+    aefft_ctx* ctx = n->ctx;
+    float* g = n->grad + q.goff;
+    const size_t nk = (size_t)q.dM * q.dD * q.Nk * q.Nl;
+    RET_IF(do_update(ctx, q.c, q.f, q.b, q.p, g, g + nk, g + 2 * nk, g + 2 * nk + q.dM, Momentum{q.Dc, q.Df, q.Db, q.Dp},
+                     q.dM, q.dD, q.Nk, q.Nl, del, maxdiff, sym, gscale, n->burst ? nullptr : mse_slot));
+    RET_IF(pair_spectra(n, q));
+    // re-forward of this pair alone (fft_backproplib.cu:1460-1461) and its MSE (:1463)
+    RET_IF(do_conv(ctx, q.X, q.C, q.b, q.H, n->B, q.dM, q.dD, q.Nx, q.Ny));
+    RET_IF(do_conv(ctx, q.H, q.F, q.p, q.O, n->B, q.dD, q.dM, q.Nx, q.Ny));
+    if (mse_slot) RET_IF(do_diff_mse(ctx, q.X, q.O, nullptr, mse_slot, nullptr, n->B, q.dM, q.dD, q.Nx, q.Ny));
+    return AEFFT_OK;
+}
+
+extern "C" int aefft_net_train_pair(aefft_net* n, int l, int n_iter, float del0, int maxdiff, int sym, float* mse_h)
+{
+    if (!n || l < 0 || l >= n->L || n_iter < 0) return fail(n ? n->ctx : nullptr, AEFFT_EINVAL, "aefft_net_train_pair: bad argument");
+    n->upd_after_fwd = false;
+    aefft_ctx* ctx = n->ctx;
+    if (!n->have_forward) return fail(ctx, AEFFT_ESTATE, "aefft_net_train_pair: run aefft_net_forward first (the burst trains on its layers)");
+    RET_IF(mse_flush(n));
+    RET_IF(join_recon(ctx));
+    RET_IF(ensure_frames(n));
+    Pair& q = n->pr[l];
+    RET_IF(ensure_spectra(n, q));
+    RET_IF(ensure_O(n, q));
+    if ((size_t)(n_iter + 1) > n->mse_cap) {
+        float* nm;
+        RET_IF(net_alloc_t(n, &nm, (size_t)n_iter + 1));
+        n->mse_dev = nm; n->mse_cap = (size_t)n_iter + 1;
+    }
+    const size_t nk = (size_t)q.dM * q.dD * q.Nk * q.Nl;
+    // momentum lives only inside the burst (fft_backproplib.cu:1420-1423)
+    HIPCHK(ctx, hipMemsetAsync(q.Dc, 0, nk * 4, ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(q.Df, 0, nk * 4, ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(q.Db, 0, q.dM * 4, ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(q.Dp, 0, q.dD * 4, ctx->stream));
+    const float del = 0.1f * del0;                      // :1445
+    HIPCHK(ctx, hipMemsetAsync(n->mse_dev, 0, sizeof(float) * (n_iter + 1), ctx->stream));
+    RET_IF(do_diff_mse(ctx, q.X, q.O, nullptr, n->mse_dev, nullptr, n->B, q.dM, q.dD, q.Nx, q.Ny));     // :1440
+    n->burst = true;
+    int rcb = AEFFT_OK;
+    for (int it = 0; it < n_iter && rcb == AEFFT_OK; ++it) {
+        rcb = pair_grad(n, q);
+        if (rcb == AEFFT_OK) rcb = pair_apply(n, q, del, maxdiff, sym, 1.0f, n->mse_dev + it + 1);
+    }
+    n->burst = false;
+    RET_IF(rcb);
+    n->have_grad = false;
+    if (mse_h) {
+        HIPCHK(ctx, hipMemcpyAsync(mse_h, n->mse_dev, sizeof(float) * (n_iter + 1), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    q.G_valid = false; n->packed_valid = false; n->chain_valid = false;         // the burst changed this pair's weights (and used S)
+    return mark_step_point(n);
+}
+
+// Step mode runs the same per-pair sequences as pair_grad / pair_apply, phase by phase over ALL pairs, so that
+// the independent contractions of a phase (4 x S, 4 x dc + 4 x df, 4 + 4 re-forward convs) go out as one launch each.
+static int bias_and_kgrad(aefft_net* n, Pair& q)
+{
+    RET_IF(ensure_O(n, q));
+    aefft_ctx* ctx = n->ctx;
+    float* g = n->grad + q.goff;
+    const size_t nk = (size_t)q.dM * q.dD * q.Nk * q.Nl;
+    const float norm = (float)q.Nx * (float)q.Ny, Norm = grad_norm(q.dM, q.dD, q.Nx, q.Ny);
+    {
+        Bracket br(ctx, KID_BIASGRAD, ((double)(q.dM * q.dD + q.dM + q.dD) + 2.0 * n->B * q.dD) * 8.0);
+        hipError_t e = launch_bias_grad(q.O, q.X, q.F, q.b, q.df, g + 2 * nk, g + 2 * nk + q.dM, n->B, q.dM, q.dD, q.P, norm, Norm, ctx->cur);
+        if (e != hipSuccess) return fail(ctx, AEFFT_EHIP, "bias_grad", e);
+    }
+    const long planes = (long)q.dM * q.dD;
+    if (q.part) return do_c2r_shrink(ctx, q.dc, g, nullptr, q.part, 2 * planes, q.Nx, q.Ny, q.Nk, q.Nl);
+    RET_IF(do_c2r_shrink(ctx, q.dc, g, n->real, nullptr, planes, q.Nx, q.Ny, q.Nk, q.Nl));
+    return do_c2r_shrink(ctx, q.df, g + nk, n->real, nullptr, planes, q.Nx, q.Ny, q.Nk, q.Nl);
+}
+
+static int grads_grouped(aefft_net* n)
+{
+    aefft_ctx* ctx = n->ctx;
+    Contract qs[8];
+    const bool op = op_mode(n);
+    if (op) {
+        // the batch moments, S_l = sum_b (O_b - X_b) X_b^H and the DC error sums of every pair from the operators: one launch
+        SgradGroup sg{};
+        double bytes = ((double)n->B * n->D + (double)OPC * OPC) * n->pr[0].P * 8.0;      // the input spectra in, the moments out
+        for (int l = 0; l < n->L; ++l) {
+            Pair& q = n->pr[l];
+            const OpView ov = op_view(n, l);
+            const int nxo = ov.nxo, nyo = ov.nyo;
+            sg.q[l] = OpPair{ov.A, ov.O, q.S, q.es, q.dD, q.Nx, q.Ny, nxo, nyo, q.P, bins(nxo, nyo)};
+            bytes += ((double)OPC * q.dD * (q.P + bins(nxo, nyo)) + (double)q.dD * q.dD * q.P) * 8.0;
+        }
+        sg.n = n->L; sg.Xf = n->Xf; sg.Mout = n->Mhat; sg.B = n->B; sg.D0 = n->D; sg.Nx0 = n->pr[0].Nx; sg.Ny0 = n->pr[0].Ny; sg.P0 = n->pr[0].P;
+        Bracket br(ctx, KID_SGRAD, bytes);
+        hipError_t e = launch_msgrad_group(sg, ctx->cur);
+        if (e != hipSuccess) return fail(ctx, AEFFT_EHIP, "sgrad", e);
+    }
+    bool comp = false;
+    for (int l = 0; l < n->L; ++l) comp = comp || n->pr[l].O_stale;
+    for (int l0 = 0; l0 < n->L && !op; l0 += 4) {
+        const int m = std::min(4, n->L - l0);
+        if (!comp) {
+            for (int i = 0; i < m; ++i) { Pair& q = n->pr[l0 + i]; qs[i] = mk_S(q.X, q.X, q.O, q.S, n->B, q.dD, q.P); }
+            RET_IF(do_contract_group(ctx, qs, m, m, 1));
+            continue;
+        }
+        if (!n->xx_done) {
+            for (int i = 0; i < m; ++i) { Pair& q = n->pr[l0 + i]; qs[i] = mk_XXneg(q.X, q.S, n->B, q.dD, q.P); }
+            RET_IF(do_contract_group(ctx, qs, m, m, 1));
+        }
+        int mo = 0;
+        for (int i = 0; i < m; ++i) {
+            Pair& q = n->pr[l0 + i];
+            if (n->xx_done && (n->ox_done >> (l0 + i) & 1u)) continue;          // rode along with a decoder launch of the forward
+            qs[mo++] = q.O_stale ? mk_OX(q.Oc, q.X, q.S, n->B, q.dD, q.P, n->Pc, q.Nx, q.Ny, n->NxC, n->NyC)
+                                 : mk_OX(q.O, q.X, q.S, n->B, q.dD, q.P, q.P, q.Nx, q.Ny, q.Nx, q.Ny);
+        }
+        if (mo == 1) RET_IF(do_contract(ctx, qs[0]));
+        else if (mo > 1) RET_IF(do_contract_group(ctx, qs, mo, mo, 1));
+    }
+    n->xx_done = false; n->ox_done = 0;
+    // DC-bin terms and the pruned inverse transforms of all pairs: one launch each when the pairs share (Nk, Nl)
+    const bool nogroup = flag(AEFFT_F_NOGROUP);
+    bool same = op || (n->L > 1 && n->L <= 8 && !nogroup);
+    for (int l = 0; l < n->L && same; ++l) {
+        const Pair& q = n->pr[l];
+        same = q.Nk == n->pr[0].Nk && q.Nl == n->pr[0].Nl && pruned_supported(q.Nk, q.Nl, q.Nx, q.Ny);
+    }
+    const bool noq = flag(AEFFT_F_NOQPATH);
+    bool qpath = op || (same && !noq && n->pr[0].Nk == n->pr[0].Nl && (n->pr[0].Nk == 3 || n->pr[0].Nk == 5));
+    for (int l = 0; l < n->L && qpath; ++l) qpath = n->pr[l].Q != nullptr;
+    if (same) {
+        BiasGradGroup bg{};
+        PrunedGroup pg{};
+        WgradGroup wg{};
+        double bbytes = 0, kbytes = 0, wbytes = 0;
+        const int T = 2 * n->pr[0].Nk - 1;
+        for (int l = 0; l < n->L; ++l) {
+            Pair& q = n->pr[l];
+            float* g = n->grad + q.goff;
+            const size_t nk = (size_t)q.dM * q.dD * q.Nk * q.Nl;
+            const float Norm = grad_norm(q.dM, q.dD, q.Nx, q.Ny);
+            bg.a[l] = BiasGradArgs{q.O_stale ? q.Oc : q.O, q.X, q.F, q.b, qpath ? nullptr : q.df, g + 2 * nk, g + 2 * nk + q.dM, n->B, q.dM, q.dD, q.P,
+                                   (float)q.Nx * (float)q.Ny, Norm, q.O_stale ? n->Pc : q.P, qpath ? q.es : nullptr, op ? q.es : nullptr};
+            if (!q.spectra_valid) {
+                // (operator form: the step left the planar spectra stale; F at the DC bin is record 0 of the
+                // bin-major copy -- element (d1*dM + m) of the pair's F segment, stride 1.  Only F is read through P in this form.)
+                if (!(op && qpath && n->Wp && n->packed_valid)) return fail(ctx, AEFFT_ESTATE, "gradient: stale kernel spectra");
+                bg.a[l].F = n->Wp + n->pack.seg[2 * n->L - 1 - l].off;      // (segments: C_0 .. C_{L-1}, F_{L-1} .. F_0)
+                bg.a[l].P = 1;
+            }
+            bbytes += ((double)(q.dM * q.dD + q.dM + q.dD) + 2.0 * n->B * q.dD) * 8.0;
+            if (qpath) {
+                // weight gradients through Q = pruned inverse transform of S on the (2Nk-1)^2 offsets (weight_kernels.hip): no dc|df spectra
+                pg.q[l] = PrunedProb{q.S, q.Q, (long)q.dD * q.dD, q.Nx, q.Ny, 1.0f};
+                pg.chunks[l] = q.Qn;
+                wg.q[l] = WgradProb{q.c, q.f, q.Q, q.es, q.b, g, g + nk, q.dM, q.dD, 1.0f / (Norm * (float)n->B), (float)q.Nx * (float)q.Ny, 1};
+                kbytes += (double)q.dD * q.dD * (q.P * 8.0 + T * T * 4.0);
+                wbytes += (2.0 * nk + (double)q.dD * q.dD * T * T) * 4.0 + 2.0 * nk * 4.0;
+            } else {
+                pg.q[l] = PrunedProb{q.dc, g, 2L * q.dM * q.dD, q.Nx, q.Ny, 1.0f};
+                kbytes += 2.0 * q.dM * q.dD * (q.P * 8.0 + q.Nk * q.Nl * 4.0);
+            }
+        }
+        bg.n = pg.n = wg.n = n->L;
+        if (!qpath) {
+            // dc | df of every pair in one launch (8 problems)
+            for (int l0 = 0; l0 < n->L; l0 += 4) {
+                const int m = std::min(4, n->L - l0);
+                for (int i = 0; i < m; ++i) {
+                    Pair& q = n->pr[l0 + i];
+                    const float Norm = grad_norm(q.dM, q.dD, q.Nx, q.Ny);
+                    qs[i] = mk_dc(q.F, q.S, q.dc, n->B, q.dM, q.dD, q.P, Norm);
+                    qs[m + i] = mk_df(q.C, q.S, q.df, n->B, q.dM, q.dD, q.P, Norm);
+                }
+                RET_IF(do_contract_group(ctx, qs, 2 * m, m, 2));
+            }
+        }
+        if (!qpath) {
+            Bracket br(ctx, KID_BIASGRAD, bbytes);
+            hipError_t e = launch_bias_grad_group(bg, ctx->cur);
+            if (e != hipSuccess) return fail(ctx, AEFFT_EHIP, "bias_grad(group)", e);
+        }
+        hipError_t e;
+        {
+            Bracket br(ctx, KID_KGRAD, kbytes + (qpath ? bbytes : 0.0));
+            e = qpath ? launch_kgrad_group_taps(pg, ctx->tw, T, ctx->cur, &bg)      // (the DC-bin terms ride along as extra workgroups)
+                      : launch_kgrad_group(pg, ctx->tw, n->pr[0].Nk, n->pr[0].Nl, ctx->cur);
+        }
+        if (e == hipSuccess && qpath) {
+            for (int l = 0; l < n->L; ++l) wg.q[l].nq = pg.chunks[l];
+            if (n->mse_pending) {      // the previous step's MSE sums: one more workgroup of this launch (they reach the packed buffer's tail before the all-reduce)
+                wg.fin_slots = n->mse_slots; wg.fin_out = n->mse_post; wg.fin_tail = n->grad + n->grad_n; wg.fin_L = n->L; wg.fin_scale = n->mse_pending_scale;
+            }
+            Bracket br(ctx, KID_WGRAD, wbytes);
+            e = launch_wgrad_taps_group(wg, n->pr[0].Nk, ctx->cur);
+            if (e != hipSuccess) return fail(ctx, AEFFT_EHIP, "wgrad(group)", e);
+            n->mse_pending = false;
+            return AEFFT_OK;
+        }
+        if (e == hipSuccess) return AEFFT_OK;
+        if (e != hipErrorInvalidValue || qpath) return fail(ctx, AEFFT_EHIP, "kgrad(group)", e);
+        (void)hipGetLastError();
+        for (int l = 0; l < n->L; ++l) {          // bias terms are done; only the transforms pair by pair
+            Pair& q = n->pr[l];
+            float* g = n->grad + q.goff;
+            const size_t nk = (size_t)q.dM * q.dD * q.Nk * q.Nl;
+            const long planes = (long)q.dM * q.dD;
+            if (q.part) { RET_IF(do_c2r_shrink(ctx, q.dc, g, nullptr, q.part, 2 * planes, q.Nx, q.Ny, q.Nk, q.Nl)); continue; }
+            RET_IF(do_c2r_shrink(ctx, q.dc, g, n->real, nullptr, planes, q.Nx, q.Ny, q.Nk, q.Nl));
+            RET_IF(do_c2r_shrink(ctx, q.df, g + nk, n->real, nullptr, planes, q.Nx, q.Ny, q.Nk, q.Nl));
+        }
+        return AEFFT_OK;
+    }
+    // pairs with different kernel supports: dc | df per group of pairs, then pair by pair
+    for (int l0 = 0; l0 < n->L; l0 += 4) {
+        const int m = std::min(4, n->L - l0);
+        for (int i = 0; i < m; ++i) {
+            Pair& q = n->pr[l0 + i];
+            const float Norm = grad_norm(q.dM, q.dD, q.Nx, q.Ny);
+            qs[i] = mk_dc(q.F, q.S, q.dc, n->B, q.dM, q.dD, q.P, Norm);
+            qs[m + i] = mk_df(q.C, q.S, q.df, n->B, q.dM, q.dD, q.P, Norm);
+        }
+        RET_IF(do_contract_group(ctx, qs, 2 * m, m, 2));
+    }
+    for (int l = 0; l < n->L; ++l) RET_IF(bias_and_kgrad(n, n->pr[l]));
+    return AEFFT_OK;
+}
+
+// post-update MSE of pair q on the current frames (fft_backproplib.cu:1460-1463).  Step mode never reads the
+// re-forward's H and O again (the next forward overwrites them), so they are not materialised: G = F.C per bin
+// (into the dead S workspace), then one pass over X with the MSE epilogue.  Falls back to conv, conv, diff_mse
+// for shapes the lean kernel does not serve (dD == 1 or B == 1).
+static int reforward_mse(aefft_net* n, Pair& q, float* mse_slots, bool* g_left_in_S = nullptr)
+{
+    if (g_left_in_S) *g_left_in_S = false;
+    aefft_ctx* ctx = n->ctx;
+    const bool nofuse = flag(AEFFT_F_NOFUSEMSE);
+    if (!nofuse && q.dD >= 2 && n->B >= 2) {
+        RET_IF(do_contract(ctx, mk_G(q.F, q.C, q.G, q.dM, q.dD, q.P)));
+        const Contract m = mk_gmse(q.G, q.X, q.F, q.b, q.p, mse_slots, n->B, q.dM, q.dD, q.Nx, q.Ny);
+        hipError_t e;
+        {
+            Bracket br(ctx, KID_CONTRACT, contract_bytes(m));
+            e = launch_contract(m, ctx->cur);
+        }
+        if (e == hipSuccess) { if (g_left_in_S) *g_left_in_S = true; return AEFFT_OK; }
+        if (e != hipErrorInvalidValue) return fail(ctx, AEFFT_EHIP, "contract(mse)", e);
+        (void)hipGetLastError();
+    }
+    RET_IF(join_recon(ctx));                                                  // a deferred reconstruction may still be reading q.O (== Oc when P == Pc)
+    RET_IF(do_conv(ctx, q.X, q.C, q.b, q.H, n->B, q.dM, q.dD, q.Nx, q.Ny));   // :1460
+    RET_IF(do_conv(ctx, q.H, q.F, q.p, q.O, n->B, q.dD, q.dM, q.Nx, q.Ny));   // :1461
+    return do_diff_mse(ctx, q.X, q.O, nullptr, n->mse_post + (&q - n->pr.data()), nullptr, n->B, q.dM, q.dD, q.Nx, q.Ny);   // :1463
+}
+
+static int apply_grouped(aefft_net* n, float del, int maxdiff, int sym, float gscale, float* mse_d)
+{
+    aefft_ctx* ctx = n->ctx;
+    for (auto& q : n->pr) q.G_valid = false;          // the weights are about to change
+    n->packed_valid = false; n->chain_valid = false;
+    const bool nogroup1 = flag(AEFFT_F_NOGROUP);
+    bool fused_upd = false;                                                // the tap half of the update rides in the tail launch (below)
+    bool gp_route = false;                                                 // the spectra launch wrote G' = F'.C'/(dM dD) for every pair but the innermost
+    UpdateGroup wupd{};
+    bool grouped_w = n->L > 1 && n->L <= 8 && !nogroup1;
+    for (int l = 0; l < n->L && grouped_w; ++l) {
+        const Pair& q = n->pr[l];
+        grouped_w = q.Nk == n->pr[0].Nk && q.Nl == n->pr[0].Nl && pruned_supported(q.Nk, q.Nl, q.Nx, q.Ny);
+    }
+    // multiobjective terms (fft_backproplib.cu:709-753) of every pair in one grouped launch; their outputs and the chunk partial sums
+    // live in per-net buffers (allocated the first time maxdiff is asked for)
+    GdiffGroup gd{};
+    if (grouped_w && maxdiff) {
+        const int kl = n->pr[0].Nk * n->pr[0].Nl;
+        grouped_w = kl == 9 || kl == 25 || kl == 49;
+        if (grouped_w && !n->gd_out) {
+            size_t no = 0, np_ = 0;
+            for (const Pair& q : n->pr) { no += 2 * (size_t)q.dM * q.dD * kl + q.dM + q.dD; np_ += gradient_diff_ws_floats(q.dM, q.dD, q.Nk, q.Nl); }
+            RET_IF(net_alloc_t(n, &n->gd_out, no));
+            RET_IF(net_alloc_t(n, &n->gd_part, np_));
+        }
+        if (grouped_w) {
+            float *o = n->gd_out, *pw = n->gd_part;
+            double gbytes = 0;
+            for (int l = 0; l < n->L; ++l) {
+                Pair& q = n->pr[l];
+                const size_t nk = (size_t)q.dM * q.dD * kl;
+                gd.q[l] = GdiffProb{q.c, q.f, q.b, q.p, o, o + nk, o + 2 * nk, o + 2 * nk + q.dM, pw, q.dM, q.dD, 0, 0};
+                o += 2 * nk + q.dM + q.dD; pw += gradient_diff_ws_floats(q.dM, q.dD, q.Nk, q.Nl);
+                gbytes += (double)nk * 16.0;
+            }
+            gd.n = n->L;
+            Bracket br(ctx, KID_GDIFF, gbytes);
+            hipError_t e = launch_gradient_diff_group(gd, n->pr[0].Nk, n->pr[0].Nl, ctx->cur);
+            if (e != hipSuccess) return fail(ctx, AEFFT_EHIP, "gradient_diff(group)", e);
+        }
+    }
+    if (grouped_w) {
+        UpdateGroup ug{};
+        PrunedGroup pg{};
+        double ubytes = 0, kbytes = 0;
+        for (int l = 0; l < n->L; ++l) {
+            Pair& q = n->pr[l];
+            float* g = n->grad + q.goff;
+            const size_t nk = (size_t)q.dM * q.dD * q.Nk * q.Nl;
+            ug.a[l] = mk_update(q.c, q.f, q.b, q.p, g, g + nk, g + 2 * nk, g + 2 * nk + q.dM, Momentum{q.Dc, q.Df, q.Db, q.Dp},
+                                q.dM, q.dD, q.Nk, q.Nl, del, sym, gscale, n->mse_post + l);
+            if (maxdiff) { ug.a[l].cd = gd.q[l].cd; ug.a[l].fd = gd.q[l].fd; ug.a[l].bd = gd.q[l].bd; ug.a[l].pd = gd.q[l].pd; }
+            ubytes += (double)nk * 4.0 * 8;
+        }
+        ug.n = n->L;
+        const bool ride = op_mode(n) && n->Wp != nullptr;                  // the bin-major copy for the next step's chain: same taps, same launch
+        // Fused update (operator form, plain gradients): no update launch.  The spectra launch reads every tap THROUGH the pending
+        // update (w - clip_step(g, D): TapUpd) and carries the bias half as a trailing workgroup per pair; the taps and their momentum
+        // are stored in place by trailing workgroups of the tail launch (tail_kernel) -- nothing in between reads them.
+        fused_upd = ride && !sym && !maxdiff && !flag(AEFFT_F_NOFUSEUPD) && !ctx->prof;
+        // Operator form with the chain launch: NO planar spectra are written.  The next step's chain reads the bin-major record Wp
+        // and the compact planes Cc_l (C_l where the next pair's grid lands); the post-update MSE reads G'_l = F'_l.C'_l/(dM dD) --
+        // dD*dD planes per pair, the spectrum of the (2Nk-1)^2 kernel f' (*) c' whose taps the transforming workgroups form
+        // themselves (gspec_gbody) -- and the innermost pair from Wp.  Planar C|F are formed when something else asks (ensure_spectra).
+        gp_route = ride && n->pr[0].Cc != nullptr && 2 * (n->L - 1) <= 8 && chain_switches_ok() && n->compact &&
+                   n->pr[n->L - 1].P == n->pack.Pc && n->pr[n->L - 1].dD <= CH_VMAX && n->pr[n->L - 1].dM <= CH_VMAX;
+        BiasUpdGroup bu{};
+        TapUpd tu[8] = {};
+        if (fused_upd) {
+            for (int l = 0; l < n->L; ++l) {
+                Pair& q = n->pr[l];
+                float* g = n->grad + q.goff;
+                const size_t nk = (size_t)q.dM * q.dD * q.Nk * q.Nl;
+                tu[l] = TapUpd{g, q.Dc, ug.a[l].del, ug.a[l].alpha, ug.a[l].gscale};        // (c|f, dck|dfk, Dc|Df: each pair contiguous)
+                bu.a[l] = BiasUpd{q.b, q.p, q.Db, q.Dp, g + 2 * nk, g + 2 * nk + q.dM, n->mse_post + l, q.dM, q.dD};
+            }
+            bu.n = n->L; bu.del = ug.a[0].del; bu.alpha = ug.a[0].alpha; bu.gscale = ug.a[0].gscale;
+            n->pack.upd = 1; n->pack.upd_del = ug.a[0].del; n->pack.upd_alpha = ug.a[0].alpha; n->pack.upd_gscale = ug.a[0].gscale;
+            wupd = ug;
+        } else {
+            n->pack.upd = 0;
+            Bracket br(ctx, KID_UPDATE, ubytes);
+            hipError_t e = launch_update_group(ug, ctx->cur);
+            if (e != hipSuccess) return fail(ctx, AEFFT_EHIP, "update(group)", e);
+        }
+        bool skip_inner = false;
+        if (gp_route) {
+            int k = 0;
+            for (int l = 0; l + 1 < n->L; ++l) {
+                Pair& q = n->pr[l];
+                pg.q[k] = PrunedProb{nullptr, q.G, (long)q.dD * q.dD, q.Nx, q.Ny, 1.0f, 0, 0};
+                pg.gsrc[k] = GtapSrc{q.c, q.f, q.dM, q.dD, 1.0f / ((float)q.dM * (float)q.dD)};
+                pg.upd[k] = tu[l];
+                kbytes += (double)q.dD * q.dD * q.P * 8.0 + 2.0 * q.dM * q.dD * q.Nk * q.Nl * 4.0;
+                ++k;
+            }
+            const int k0 = k;
+            k = cc_problems(n, pg, k0, &kbytes);
+            for (int l = 0; l + 1 < n->L; ++l) pg.upd[k0 + l] = tu[l];
+            pg.n = k;
+        } else {
+            for (int l = 0; l < n->L; ++l) {
+                Pair& q = n->pr[l];
+                pg.q[l] = PrunedProb{q.c, q.C, 2L * q.dM * q.dD, q.Nx, q.Ny, 1.0f};
+                pg.upd[l] = tu[l];
+                kbytes += 2.0 * q.dM * q.dD * (q.P * 8.0 + q.Nk * q.Nl * 4.0);
+            }
+            pg.n = n->L;
+            // Without the compact planes: the innermost pair's PLANAR spectra are not written (the chain, the post-update MSE and the
+            // DC-bin gradient terms take that pair from the bin-major record)
+            skip_inner = ride && n->L > 1 && n->pr[n->L - 1].P == n->pack.Pc && n->pr[n->L - 1].dD <= CH_VMAX && n->pr[n->L - 1].dM <= CH_VMAX &&
+                         !flag(AEFFT_F_NOCHAIN) && !flag(AEFFT_F_NOFUSEUPD) && !ctx->prof;
+            if (skip_inner) {
+                const Pair& qi = n->pr[n->L - 1];
+                pg.n = n->L - 1;
+                kbytes -= 2.0 * qi.dM * qi.dD * (qi.P * 8.0 + qi.Nk * qi.Nl * 4.0);
+            }
+        }
+        hipError_t e;
+        {
+            Bracket br(ctx, KID_KSPEC, kbytes + ((op_mode(n) && n->Wp) ? (double)n->pack.Pc * n->pack.E * 8.0 : 0.0));
+            e = launch_kspec_group(pg, ctx->tw, n->pr[0].Nk, n->pr[0].Nl, ctx->cur, ride ? &n->pack : nullptr, fused_upd ? &bu : nullptr);
+            if (e == hipSuccess && ride) n->packed_valid = true;
+            if (e == hipSuccess && skip_inner) n->pr[n->L - 1].spectra_valid = false;
+            if (e == hipSuccess && gp_route) for (auto& q : n->pr) q.spectra_valid = false;
+            if (e == hipSuccess && !gp_route) for (int l = 0; l < pg.n; ++l) n->pr[l].spectra_valid = true;
+        }
+        n->pack.upd = 0;
+        if (e != hipSuccess) {
+            if (e != hipErrorInvalidValue) return fail(ctx, AEFFT_EHIP, "kspec(group)", e);
+            (void)hipGetLastError();
+            gp_route = false;
+            if (fused_upd) {                                               // declined before anything ran: the separate update after all
+                fused_upd = false;
+                hipError_t e2 = launch_update_group(ug, ctx->cur);
+                if (e2 != hipSuccess) return fail(ctx, AEFFT_EHIP, "update(group)", e2);
+            }
+            for (int l = 0; l < n->L; ++l) RET_IF(pair_spectra(n, n->pr[l]));
+            for (auto& q : n->pr) q.spectra_valid = true;
+        }
+    } else for (int l = 0; l < n->L; ++l) {
+        Pair& q = n->pr[l];
+        float* g = n->grad + q.goff;
+        const size_t nk = (size_t)q.dM * q.dD * q.Nk * q.Nl;
+        RET_IF(do_update(ctx, q.c, q.f, q.b, q.p, g, g + nk, g + 2 * nk, g + 2 * nk + q.dM, Momentum{q.Dc, q.Df, q.Db, q.Dp},
+                         q.dM, q.dD, q.Nk, q.Nl, del, maxdiff, sym, gscale, n->mse_post + l));
+        RET_IF(pair_spectra(n, q));
+        q.spectra_valid = true;
+    }
+    if (op_mode(n) && n->Wp) RET_IF(ensure_packed(n));     // the next step's chain reads the bin-major copy of the NEW weights
+    bool g_taps = false;                                   // G' of EVERY pair at hand (operator form without the chain launch, HBM-sized spectra)
+    if (op_mode(n) && !gp_route) {
+        // HBM-sized kernel spectra (no pooling): the post-update MSE would read all 2*dM*dD planes of C'|F' back (6 GB at cfg3-P1).  G' =
+        // F'.C'/(dM dD) as the spectrum of the (2Nk-1)^2-tap kernel f' (*) c' (weight_kernels.hip) is dD*dD planes written and read once.
+        double cf_bytes = 0;
+        for (int l = 0; l < n->L; ++l) cf_bytes += 2.0 * n->pr[l].dM * n->pr[l].dD * n->pr[l].P * 8.0;
+        const bool want = (cf_bytes > 256e6 || flag(AEFFT_F_GTAPS)) && !fused_upd /* the taps are stored */ && !flag(AEFFT_F_NOQPATH);
+        if (want) RET_IF(gprime_from_taps(n, &g_taps));
+    }
+    if (op_mode(n)) {
+        // post-update MSE (fft_backproplib.cu:1460-1463) in operator form: R = A - F'(C' A / dM + b^) / dD - p^ per bin, then
+        // sum_a R[a] M^ R[a]^H; the updated spectra (or their product G') are read once, nothing is stored (opform_kernels.hip)
+        OpMseGroup og{};
+        double bytes = 0;
+        const bool inner_packed = n->Wp && n->packed_valid && n->pr[n->L - 1].P == n->pack.Pc;
+        for (int l = 0; l < n->L; ++l) {
+            Pair& q = n->pr[l];
+            const float scale = 1.0f / ((float)(2 * q.dM) * (float)q.Nx * (float)q.Ny * (float)n->B) / ((float)q.dD * q.Nx * q.Ny);   // as mk_gmse
+            OpMsePair o{};
+            o.A = op_view(n, l).A; o.C = q.C; o.F = q.F; o.b = q.b; o.p = q.p;
+            o.slots = n->mse_slots + (size_t)l * MSE_SLOTS * MSE_SLOT_STRIDE;
+            o.dD = q.dD; o.dM = q.dM; o.Nx = q.Nx; o.Ny = q.Ny; o.P = q.P; o.scale = scale;
+            if (gp_route && l + 1 < n->L) {
+                o.G = q.G; o.Fdc = n->Wp + n->pack.seg[2 * n->L - 1 - l].off; o.fdc_stride = 1;      // (F' at the DC bin: record 0 of the bin-major copy)
+                bytes += ((double)q.dD * q.dD + (double)OPC * q.dD + (double)OPC * OPC) * q.P * 8.0;
+            } else if (g_taps && !(l == n->L - 1 && inner_packed)) {
+                RET_IF(ensure_spectra(n, q));
+                o.G = q.G; o.Fdc = q.F; o.fdc_stride = q.P;                                            // (the planar F', DC bin)
+                bytes += ((double)q.dD * q.dD + (double)OPC * q.dD + (double)OPC * OPC) * q.P * 8.0;
+            } else {
+                if (!(l == n->L - 1 && inner_packed)) RET_IF(ensure_spectra(n, q));
+                bytes += (2.0 * q.dM * q.dD + (double)OPC * q.dD + (double)OPC * OPC) * q.P * 8.0;
+            }
+            og.q[l] = o;
+        }
+        og.n = n->L; og.Mhat = n->Mhat; og.Nx0 = n->pr[0].Nx; og.Ny0 = n->pr[0].Ny; og.P0 = n->pr[0].P;
+        if (inner_packed) {      // the innermost pair reads the bin-major copy the kspec launch just refreshed
+            og.Wp = n->Wp; og.E = n->pack.E;
+            og.offC = n->pack.seg[n->L - 1].off; og.offF = n->pack.seg[n->L].off;
+        }
+        // The NEXT step's operator chain depends on the updated weights only (the record Wp and the planes Cc the spectra launch has just
+        // written): it shares this launch, writing the other set of operator buffers, and the next aefft_net_step_grad starts from it.
+        const bool ahead = n->op_chain && n->Wp && n->packed_valid && chain_switches_ok() && (n->compact || n->L == 1) && !flag(AEFFT_F_NOAHEAD);
+        ChainArgs ca{};
+        if (ahead) fill_chain(n, ca, n->op_set ^ 1, &bytes);
+        {
+            Bracket br(ctx, KID_OPMSE, bytes);
+            hipError_t e = launch_opmse_group(og, ctx->cur, ahead ? &ca : nullptr, fused_upd ? &wupd : nullptr);
+            if (e != hipSuccess) return fail(ctx, AEFFT_EHIP, "opmse", e);
+        }
+        if (ahead) { n->op_set ^= 1; n->chain_valid = true; }
+        if (!mse_d && !ctx->prof && !flag(AEFFT_F_NOLAZYMSE)) {
+            // nobody asked for the sums now: they are formed by one more workgroup of the next step's gradient launch (before its
+            // all-reduce), by aefft_net_last_mse, or by whatever needs the slots next -- not by a launch of their own
+            n->mse_pending = true; n->mse_pending_scale = gscale;
+            return AEFFT_OK;
+        }
+        Bracket br(ctx, KID_DIFFMSE, 4.0 * n->L * MSE_SLOTS);
+        hipError_t e = launch_mse_finish(n->mse_slots, n->mse_post, mse_d, n->L, ctx->cur, nullptr, n->grad + n->grad_n, gscale);
+        if (e != hipSuccess) return fail(ctx, AEFFT_EHIP, "mse_finish", e);
+        return AEFFT_OK;
+    }
+    if (fused_upd) return fail(ctx, AEFFT_ESTATE, "apply: fused update without the operator-form tail");      // (cannot happen: fused_upd implies op_state)
+    // post-update MSE (fft_backproplib.cu:1460-1463): G = F.C of every eligible pair in one launch, then every pair's pass
+    // over X with the MSE epilogue in one launch; pairs the fused form does not serve (dD == 1, B == 1) go pair by pair
+    std::vector<char> g_in_S(n->L, 0);       // pair l: S holds G of the updated weights after this call
+    {
+        const bool nofuse = flag(AEFFT_F_NOFUSEMSE), nogroup = flag(AEFFT_F_NOGROUP);
+        Contract gq[8], mq[8];
+        int m = 0;
+        std::vector<int> rest;
+        for (int l = 0; l < n->L; ++l) {
+            Pair& q = n->pr[l];
+            if (!nofuse && !nogroup && q.dD >= 2 && n->B >= 2 && m < 8) {
+                gq[m] = mk_G(q.F, q.C, q.G, q.dM, q.dD, q.P);
+                mq[m] = mk_gmse(q.G, q.X, q.F, q.b, q.p, n->mse_slots + (size_t)l * MSE_SLOTS * MSE_SLOT_STRIDE, n->B, q.dM, q.dD, q.Nx, q.Ny);
+                ++m;
+            } else rest.push_back(l);
+        }
+        bool grouped = false;
+        if (m > 1) {
+            // G = F.C/(dM dD).  HBM-sized kernel spectra (no pooling): as the spectrum of the (2Nk-1)^2-tap kernel f (*) c
+            // (weight_kernels.hip), which reads the kernels and writes dD*dD planes instead of reading all 2*dM*dD planes of C|F;
+            // cache-sized ones: as a per-bin contraction of the spectra (measured faster there).
+            const bool noq = flag(AEFFT_F_NOQPATH);
+            double cf_bytes = 0;
+            for (int l = 0; l < n->L; ++l) cf_bytes += 2.0 * n->pr[l].dM * n->pr[l].dD * n->pr[l].P * 8.0;
+            bool gtaps = false;
+            if (!noq && (cf_bytes > 256e6 || flag(AEFFT_F_GTAPS)) && m == n->L) RET_IF(gprime_from_taps(n, &gtaps));
+            if (!gtaps) RET_IF(do_contract_group(ctx, gq, m, m, 0));
+            ContractN g{};
+            double bytes = 0;
+            for (int i = 0; i < m; ++i) { g.q[i] = mq[i]; bytes += contract_bytes(mq[i]); }
+            g.n = m;
+            hipError_t e;
+            {
+                Bracket br(ctx, KID_CONTRACT, bytes);
+                e = launch_contract_mfma(g, ctx->cur);
+            }
+            if (e == hipSuccess) grouped = true;
+            else if (e != hipErrorInvalidValue) return fail(ctx, AEFFT_EHIP, "contract(mse group)", e);
+            else (void)hipGetLastError();
+        }
+        for (int l = 0; l < n->L; ++l) {
+            const bool in_group = grouped && std::find(rest.begin(), rest.end(), l) == rest.end();
+            bool left = in_group;
+            if (!in_group) RET_IF(reforward_mse(n, n->pr[l], n->mse_slots + (size_t)l * MSE_SLOTS * MSE_SLOT_STRIDE, &left));
+            g_in_S[l] = left;
+        }
+    }
+    {
+        Bracket br(ctx, KID_DIFFMSE, 4.0 * n->L * MSE_SLOTS);
+        Pair& ql = n->pr[n->L - 1];
+        BetaArgs ba{ql.beta, ql.F, ql.b, ql.p, ql.dM, ql.dD, ql.P};
+        const bool want_beta = g_in_S[n->L - 1] && ql.beta && ql.dD <= 256;
+        hipError_t e = launch_mse_finish(n->mse_slots, n->mse_post, mse_d, n->L, ctx->cur, want_beta ? &ba : nullptr, n->grad + n->grad_n, gscale);     // also the copy-out to mse_d and to the packed buffer's tail
+        ql.G_valid = want_beta && e == hipSuccess;
+        if (e != hipSuccess) return fail(ctx, AEFFT_EHIP, "mse_finish", e);
+    }
+    return AEFFT_OK;
+}
+
+// input prefetch bookkeeping: everything of step k that reads this step's input-spectra buffer has been enqueued
+int aefft::mark_step_point(aefft_net* n)
+{
+    if (!n->input_ready || !n->ev_end[0]) return AEFFT_OK;
+    HIPCHK(n->ctx, hipEventRecord(n->ev_end[n->step_no & 1], n->ctx->stream));
+    n->ev_end_valid[n->step_no & 1] = true;
+    return AEFFT_OK;
+}
+
+extern "C" int aefft_net_set_input_ready(aefft_net* n, int enable)
+{
+    if (!n) return AEFFT_EINVAL;
+    aefft_ctx* ctx = n->ctx;
+    if (enable && !n->X0alt) {
+        const Pair& q = n->pr[0];
+        RET_IF(net_alloc_t(n, &n->X0alt, (size_t)n->B * q.dD * q.P));
+        for (int i = 0; i < 2; ++i) HIPCHK(ctx, hipEventCreateWithFlags(&n->ev_end[i], hipEventDisableTiming));
+        HIPCHK(ctx, hipEventCreateWithFlags(&n->ev_r2c, hipEventDisableTiming));
+        HIPCHK(ctx, hipEventCreateWithFlags(&n->ev_mid, hipEventDisableTiming));
+    }
+    n->input_ready = enable != 0;
+    return AEFFT_OK;
+}
+
+extern "C" int aefft_net_step_grad(aefft_net* n, const float* frames_d, float* recon_d)
+{
+    if (!n) return AEFFT_EINVAL;
+    aefft_ctx* ctx = n->ctx;
+    ++n->step_no;
+    RET_IF(net_forward(n, frames_d, recon_d, true, op_eligible(n)));
+    {
+        int rcg = grads_grouped(n);
+        if (rcg == AEFFT_OK) rcg = mse_flush(n);      // (a gradient route without the wgrad launch: the deferred MSE sums as their own launch after all)
+        if (rcg != AEFFT_OK) { n->recon_deferred = nullptr; return rcg; }
+    }
+    if (n->recon_deferred) {
+        // The reconstruction's inverse FFT starts HERE: where a data-parallel run waits for its all-reduce the GPU is otherwise
+        // idle, and what follows on this stream (update, spectra, MSE) is latency-bound.  Joined by aefft_net_step_apply,
+        // aefft_sync or the next call on this net.
+        float* recon = n->recon_deferred;
+        n->recon_deferred = nullptr;
+        HIPCHK(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
+        HIPCHK(ctx, hipStreamWaitEvent(ctx->aux[0], ctx->ev_fork, 0));
+        ctx->cur = ctx->aux[0];
+        const int rc = launch_recon(n, recon, WS_MID3);
+        ctx->cur = ctx->stream;
+        RET_IF(rc);
+        HIPCHK(ctx, hipEventRecord(ctx->ev_join[0], ctx->aux[0]));
+        ctx->recon_join = true;
+    }
+    if (n->recon_pending) {
+        // the documented default: recon_d is complete, in stream order on the context stream, when this call's work is
+        // (include/aefft.h; the pipelined mode relaxes it).  Joining later -- behind the update half -- was measured: see DESIGN.md 6.
+        HIPCHK(ctx, hipEventRecord(ctx->ev_join[0], ctx->aux[0]));
+        HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join[0], 0));
+        n->recon_pending = false;
+    }
+    n->have_grad = true;
+    if (n->input_ready && n->ev_mid) { HIPCHK(ctx, hipEventRecord(n->ev_mid, ctx->stream)); n->ev_mid_valid = true; }
+    return mark_step_point(n);
+}
+
+// 8-bit frames: the same calls with the input transform converting on load (fft_kernels.hip r2c_rows_kernel<N, true>); nothing else reads the frames
+extern "C" int aefft_net_step_grad_u8(aefft_net* n, const unsigned char* frames_d, float* recon_d)
+{
+    if (!n) return AEFFT_EINVAL;
+    n->ctx->in_u8 = true;
+    const int rc = aefft_net_step_grad(n, reinterpret_cast<const float*>(frames_d), recon_d);
+    n->ctx->in_u8 = false;
+    return rc;
+}
+extern "C" int aefft_net_forward_u8(aefft_net* n, const unsigned char* frames_d, float* recon_d)
+{
+    if (!n) return AEFFT_EINVAL;
+    n->ctx->in_u8 = true;
+    const int rc = aefft_net_forward(n, reinterpret_cast<const float*>(frames_d), recon_d);
+    n->ctx->in_u8 = false;
+    return rc;
+}
+
+extern "C" int aefft_net_step_form(aefft_net* n)
+{
+    if (!n) return -1;
+    if (!op_eligible(n)) return AEFFT_FORM_PER_FRAME;
+    const bool chain = n->Wp && (n->compact || n->L == 1) && chain_switches_ok();
+    return chain ? AEFFT_FORM_OPERATOR_CHAIN : AEFFT_FORM_OPERATOR;
+}
+
+extern "C" int aefft_net_grad_buffer(aefft_net* n, float** buf_d, size_t* nfloats)
+{
+    if (!n) return AEFFT_EINVAL;
+    if (buf_d) *buf_d = n->grad;
+    if (nfloats) *nfloats = n->grad_n + (size_t)n->L;
+    return AEFFT_OK;
+}
+
+extern "C" int aefft_net_last_mse(aefft_net* n, float* mse_d)
+{
+    if (!n || !mse_d) return AEFFT_EINVAL;
+    aefft_ctx* ctx = n->ctx;
+    RET_IF(mse_flush(n));
+    HIPCHK(ctx, hipMemcpyAsync(mse_d, n->mse_post, sizeof(float) * n->L, hipMemcpyDeviceToDevice, ctx->stream));
+    return AEFFT_OK;
+}
+
+extern "C" int aefft_net_step_apply(aefft_net* n, float del0, int maxdiff, int sym, float grad_scale, float* mse_d)
+{
+    if (!n) return AEFFT_EINVAL;
+    aefft_ctx* ctx = n->ctx;
+    if (!n->have_grad) return fail(ctx, AEFFT_ESTATE, "aefft_net_step_apply: call aefft_net_step_grad first");
+    RET_IF(mse_flush(n));
+    for (auto& q : n->pr) q.G_valid = false;          // the weights are about to change (the grouped path re-derives G and sets it again)
+    const float del = 0.1f * del0;
+    RET_IF(apply_grouped(n, del, maxdiff, sym, grad_scale, mse_d));
+    n->have_grad = false;
+    n->upd_after_fwd = true;
+    RET_IF(join_recon(ctx));
+    return mark_step_point(n);
+}

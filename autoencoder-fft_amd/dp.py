@@ -17,7 +17,7 @@ import numpy as np
 
 def grad_layout(dims):
     """Offsets (in floats) of each pair's segments inside the packed gradient buffer; mirrors
-    aefft_net_create (aefft_capi.hip: goff += 2*nk + dM + dD).  dims: list of dict(dM, dD, Nk, Nl).
+    aefft_net_create (net.hip: goff += 2*nk + dM + dD).  dims: list of dict(dM, dD, Nk, Nl).
     Returns (layout, n): n = floats of the gradient part; the buffer the library exposes is n + len(dims) long (mse_tail_slice)."""
     out, off = [], 0
     for g in dims:
