@@ -23,7 +23,6 @@ struct aefft_ctx {
     hipStream_t stream = nullptr;    // the caller-visible stream: every public call is ordered on it
     hipStream_t cur = nullptr;       // stream the helpers enqueue on (== stream except inside a forked section)
     bool own_stream = false;
-    bool in_u8 = false;              // the frames handed to the running call are 8-bit pixels (aefft_net_step_grad_u8 / aefft_net_forward_u8: net_forward passes it to the frame transforms)
     int biasColP1 = 0;               // operator form: conv_k biases go to the affine column of the basis frames only (Contract::biasColP1)
     bool recon_join = false;         // a deferred reconstruction (pipelined mode) still has to be joined from aux[0] (ev_join[0])
     static const int NAUX = 2;
@@ -65,6 +64,20 @@ struct Bracket {
         (void)hipEventRecord(c->pool[idx].a, c->cur);
     }
     ~Bracket() { if (idx >= 0) (void)hipEventRecord(ctx->pool[idx].b, ctx->cur); }
+};
+
+// helpers enqueue on a side stream for one scope: ctx->cur is the context stream again on every return path
+struct OnStream {
+    aefft_ctx* ctx;
+    OnStream(aefft_ctx* c, hipStream_t s) : ctx(c) { c->cur = s; }
+    ~OnStream() { ctx->cur = ctx->stream; }
+};
+
+// operator form: conv_k biases go to the affine column of the basis frames only, for one scope
+struct BiasColGuard {
+    aefft_ctx* ctx;
+    BiasColGuard(aefft_ctx* c, int col) : ctx(c) { c->biasColP1 = col; }
+    ~BiasColGuard() { ctx->biasColP1 = 0; }
 };
 
 #define CF2(p) reinterpret_cast<const float2*>(p)
@@ -120,3 +133,29 @@ UpdateArgs mk_update(float* c, float* f, float* b, float* p, const float* dck, c
                      Momentum mo, int dM, int dD, int Nk, int Nl, float del, int sym, float gscale, float* zero);
 
 }  // namespace aefft
+
+// launch() (one or more launches returning hipError_t) inside one profiling bracket: AEFFT_OK or the fail() code of its error
+template <typename Launch> int launch_or_fail(aefft_ctx* ctx, int kid, double bytes, const char* what, Launch launch)
+{
+    hipError_t e;
+    {
+        Bracket br(ctx, kid, bytes);
+        e = launch();
+    }
+    return e == hipSuccess ? AEFFT_OK : aefft::fail(ctx, AEFFT_EHIP, what, e);
+}
+
+// ... for launches that may decline shapes they do not serve (hipErrorInvalidValue): AEFFT_OK (launched), DECLINED (the error is
+// cleared; the caller falls back) or the fail() code of any other error
+enum { DECLINED = -1 };
+template <typename Launch> int launch_or_decline(aefft_ctx* ctx, int kid, double bytes, const char* what, Launch launch)
+{
+    hipError_t e;
+    {
+        Bracket br(ctx, kid, bytes);
+        e = launch();
+    }
+    if (e != hipErrorInvalidValue) return e == hipSuccess ? AEFFT_OK : aefft::fail(ctx, AEFFT_EHIP, what, e);
+    (void)hipGetLastError();
+    return DECLINED;
+}

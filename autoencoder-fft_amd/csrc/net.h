@@ -3,6 +3,9 @@
 #pragma once
 #include "host.h"
 
+// one pair's segment of the packed gradient buffer: dck [dM][dD][Nk][Nl] | dfk [dD][dM][Nk][Nl] | db [dM] | dp [dD]
+struct GradSeg { float *dck, *dfk, *db, *dp; };
+
 struct Pair {
     int dD, dM, Nk, Nl, s;
     int Nxin, Nyin;          // resolution before this pair's pooling
@@ -28,6 +31,8 @@ struct Pair {
     float* es;               // [2*dD] DC bins of the error summed over the batch (inside the net scratch)
     float2 *S, *dc, *df;     // per-pair gradient workspaces (pairs run concurrently on side streams); df == dc + W
     float* part;             // kgrad partial sums
+    size_t nk() const { return (size_t)dM * dD * Nk * Nl; }     // taps of each of the two kernels
+    GradSeg grads(float* buf) const { float* g = buf + goff; return GradSeg{g, g + nk(), g + 2 * nk(), g + 2 * nk() + dM}; }   // its segment of buf (aefft_net::grad)
 };
 
 struct aefft_net {
@@ -62,7 +67,7 @@ struct aefft_net {
     float *gd_out = nullptr, *gd_part = nullptr;   // multiobjective mode: [cd | fd | bd | pd] per pair, and the chunk partial sums (gradient_diff_ws_floats)
     bool mse_pending = false;   // the slots hold the unsummed post-update MSE of the last aefft_net_step_apply (mse_d == NULL): summed by the next step's wgrad launch or mse_flush
     float mse_pending_scale = 1.f;
-    float* mse_slots = nullptr; // [L][MSE_SLOTS*MSE_SLOT_STRIDE] accumulators of the fused re-forward MSE (zero between uses)
+    float* mse_slots = nullptr; // [L][MSE_PAIR_FLOATS] accumulators of the fused re-forward MSE (zero between uses)
     float* mse_dev = nullptr;  // scratch for bursts
     size_t mse_cap = 0;
     const float* last_frames = nullptr;
@@ -90,6 +95,10 @@ struct aefft_net {
 };
 
 namespace aefft {
+
+// pair l's accumulators of the fused re-forward MSE (aefft_net::mse_slots)
+constexpr size_t MSE_PAIR_FLOATS = (size_t)MSE_SLOTS * MSE_SLOT_STRIDE;
+inline float* mse_slot(const aefft_net* n, int l) { return n->mse_slots + (size_t)l * MSE_PAIR_FLOATS; }
 
 // ---- net.hip ---------------------------------------------------------------------------
 int net_alloc(aefft_net* n, void** p, size_t bytes);

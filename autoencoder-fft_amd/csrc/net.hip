@@ -40,10 +40,10 @@ static int build_chain_items(aefft_net* n)
         PackArgs& pa = n->pack;
         int off = 0, ns = 0;
         // (with each tensor the gradient and momentum of the same taps: a fused update reads the taps through them, TapUpd)
-        for (int l = 0; l < L; ++l) { const Pair& q = n->pr[l]; pa.seg[ns++] = PackSeg{q.c, q.dM * q.dD, l, off, n->grad + q.goff, q.Dc}; off += (q.dM * q.dD + 1) & ~1; }
+        for (int l = 0; l < L; ++l) { const Pair& q = n->pr[l]; pa.seg[ns++] = PackSeg{q.c, q.dM * q.dD, l, off, q.grads(n->grad).dck, q.Dc}; off += (q.dM * q.dD + 1) & ~1; }
         for (int l = L - 1; l >= 0; --l) {
             const Pair& q = n->pr[l];
-            pa.seg[ns++] = PackSeg{q.f, q.dM * q.dD, l, off, n->grad + q.goff + (size_t)q.dM * q.dD * q.Nk * q.Nl, q.Df};
+            pa.seg[ns++] = PackSeg{q.f, q.dM * q.dD, l, off, q.grads(n->grad).dfk, q.Df};
             off += (q.dM * q.dD + 1) & ~1;
         }
         pa.nseg = ns; pa.L = L; pa.E = off; pa.Nk = n->pr[0].Nk;
@@ -149,7 +149,7 @@ static int net_create(aefft_ctx* ctx, const aefft_net_desc* d, unsigned opts, ae
             (rc = ws_get(ctx, WS_DEN, sizeof(float) * maxDen, &dummy)) == AEFFT_OK &&
             (rc = ws_get(ctx, WS_SMALL, sizeof(float) * maxSmall, &dummy)) == AEFFT_OK &&
             (rc = net_alloc_t(n, &n->real, n->pruned ? 64 : maxReal)) == AEFFT_OK &&
-            (rc = net_alloc_t(n, &n->mse_slots, (size_t)n->L * MSE_SLOTS * MSE_SLOT_STRIDE)) == AEFFT_OK &&
+            (rc = net_alloc_t(n, &n->mse_slots, n->L * MSE_PAIR_FLOATS)) == AEFFT_OK &&
             (rc = net_alloc_t(n, &n->grad, goff + 2 * (size_t)n->L)) == AEFFT_OK && (rc = net_alloc_t(n, &n->scratch, soff)) == AEFFT_OK) {
             n->scratch_n = soff; n->mse_pre = n->scratch; n->mse_post = n->scratch + n->L;
             for (int l = 0; l < n->L; ++l) n->pr[l].es = n->scratch + esoff[l];
@@ -179,7 +179,7 @@ static int net_create(aefft_ctx* ctx, const aefft_net_desc* d, unsigned opts, ae
         }
     }
     if (rc != AEFFT_OK) { aefft_net_destroy(n); return rc; }
-    hipError_t e = hipMemsetAsync(n->mse_slots, 0, sizeof(float) * n->L * MSE_SLOTS * MSE_SLOT_STRIDE, ctx->stream);
+    hipError_t e = hipMemsetAsync(n->mse_slots, 0, sizeof(float) * n->L * MSE_PAIR_FLOATS, ctx->stream);
     if (e == hipSuccess) e = hipMemsetAsync(n->grad + n->grad_n, 0, sizeof(float) * 2 * n->L, ctx->stream);      // (the MSE tail of the packed buffer: zero before the first step)
     if (e != hipSuccess) { aefft_net_destroy(n); return fail(ctx, AEFFT_EHIP, "memset(mse slots)", e); }
     for (auto& q : n->pr) {

@@ -4,7 +4,6 @@
 #include "net.h"
 
 #include <algorithm>
-#include <vector>
 
 using namespace aefft;
 
@@ -20,6 +19,14 @@ static int cc_problems(aefft_net* n, PrunedGroup& pg, int first, double* bytes)
         ++k;
     }
     return k;
+}
+
+// every pair has pair 0's kernel support (Nk, Nl), and a pruned transform of it
+static bool shared_supports(const aefft_net* n)
+{
+    for (const Pair& q : n->pr)
+        if (q.Nk != n->pr[0].Nk || q.Nl != n->pr[0].Nl || !pruned_supported(q.Nk, q.Nl, q.Nx, q.Ny)) return false;
+    return true;
 }
 
 // G'_l = F_l.C_l / (dM dD) [dD][dD][P] of the STORED weights of every pair, into Pair::G: the spectrum of the (2Nk-1)^2-tap kernel f (*) c, taps
@@ -59,26 +66,30 @@ static int gprime_from_taps(aefft_net* n, bool* done)
             o += (size_t)q.dD * q.dD * TT;
         }
         tg.n = pt.n = n->L;
-        hipError_t e;
-        {
-            Bracket br(ctx, KID_KSPEC, bytes);
-            e = launch_gtaps_group(tg, n->pr[0].Nk, ctx->cur);
-            if (e == hipSuccess) e = launch_kspec_group_taps(pt, ctx->tw, 2 * n->pr[0].Nk - 1, ctx->cur);
-        }
-        if (e == hipSuccess) { *done = true; return AEFFT_OK; }
-        if (e != hipErrorInvalidValue) return fail(ctx, AEFFT_EHIP, "G'(stored taps)", e);
-        (void)hipGetLastError();                           // (shapes these launches do not serve: taps formed in the transforming workgroups, below)
+        const int rc = launch_or_decline(ctx, KID_KSPEC, bytes, "G'(stored taps)", [&] {
+            const hipError_t e = launch_gtaps_group(tg, n->pr[0].Nk, ctx->cur);
+            return e == hipSuccess ? launch_kspec_group_taps(pt, ctx->tw, 2 * n->pr[0].Nk - 1, ctx->cur) : e;
+        });
+        *done = rc == AEFFT_OK;
+        if (rc != DECLINED) return rc;
+        // (shapes these launches do not serve: taps formed in the transforming workgroups, below)
     }
     pg.n = n->L;
-    hipError_t e;
-    {
-        Bracket br(ctx, KID_KSPEC, bytes);
-        e = launch_kspec_group(pg, ctx->tw, n->pr[0].Nk, n->pr[0].Nl, ctx->cur, nullptr, nullptr);
-    }
-    if (e == hipSuccess) { *done = true; return AEFFT_OK; }
-    if (e != hipErrorInvalidValue) return fail(ctx, AEFFT_EHIP, "G'(taps)", e);
-    (void)hipGetLastError();
-    return AEFFT_OK;
+    const int rc = launch_or_decline(ctx, KID_KSPEC, bytes, "G'(taps)",
+                                     [&] { return launch_kspec_group(pg, ctx->tw, n->pr[0].Nk, n->pr[0].Nl, ctx->cur, nullptr, nullptr); });
+    *done = rc == AEFFT_OK;
+    return rc == DECLINED ? AEFFT_OK : rc;
+}
+
+// Does the post-update MSE take G' = F.C/(dM dD) from the stored taps (gprime_from_taps)?  HBM-sized kernel spectra (no pooling): the MSE
+// would read all 2*dM*dD planes of C|F back (6 GB at cfg3-P1), while the spectrum of the (2Nk-1)^2-tap kernel f (*) c (weight_kernels.hip)
+// reads the kernels and writes dD*dD planes, read once.  Cache-sized ones: a per-bin contraction of the spectra (measured faster there).
+static bool gprime_taps_pay(const aefft_net* n)
+{
+    if (flag(AEFFT_F_NOQPATH)) return false;
+    double cf_bytes = 0;
+    for (const Pair& q : n->pr) cf_bytes += 2.0 * q.dM * q.dD * q.P * 8.0;
+    return cf_bytes > 256e6 || flag(AEFFT_F_GTAPS);
 }
 
 // the bin-major record Wp (and the compact Cc planes) of the CURRENT weights
@@ -87,18 +98,14 @@ static int ensure_packed(aefft_net* n)
     if (!n->Wp || n->packed_valid) return AEFFT_OK;
     aefft_ctx* ctx = n->ctx;
     double bytes = (double)n->pack.Pc * n->pack.E * 8.0;
-    hipError_t e;
+    PrunedGroup pg{};
     if (n->pr[0].Cc) {
-        PrunedGroup pg{};
         pg.n = cc_problems(n, pg, 0, &bytes);
         n->pack.upd = 0;
-        Bracket br(ctx, KID_KSPEC, bytes);
-        e = launch_kspec_group(pg, ctx->tw, n->pr[0].Nk, n->pr[0].Nl, ctx->cur, &n->pack, nullptr);
-    } else {
-        Bracket br(ctx, KID_KSPEC, bytes);
-        e = launch_kspec_packed(n->pack, ctx->cur);
     }
-    if (e != hipSuccess) return fail(ctx, AEFFT_EHIP, "kspec_packed", e);
+    RET_IF(launch_or_fail(ctx, KID_KSPEC, bytes, "kspec_packed", [&] {
+        return n->pr[0].Cc ? launch_kspec_group(pg, ctx->tw, n->pr[0].Nk, n->pr[0].Nl, ctx->cur, &n->pack, nullptr) : launch_kspec_packed(n->pack, ctx->cur);
+    }));
     n->packed_valid = true;
     return AEFFT_OK;
 }
@@ -159,11 +166,8 @@ static int launch_recon(aefft_net* n, float* recon_d, int wsid)
             // written out once by a coalesced pass (7 plane-ordered loads per output) and the inverse transform reads them back.  Evaluated
             // inside the column pass instead, the same 7 loads are strided 128-byte pieces: 1.1 ms against 0.2 ms at cfg3-P1.
             if (!n->recon_exp) RET_IF(net_alloc_t(n, &n->recon_exp, (size_t)n->B * q.dD * PO));
-            {
-                Bracket br(ctx, KID_OPFORM, ((double)OPC * q.dD * PO + (double)n->B * q.dD * PO + (double)n->B * q.dD * q.P) * 8.0);
-                hipError_t e = launch_recon_expand(src, n->Xf, n->recon_exp, n->B, q.dD, q.Nx, q.Ny, nxo, nyo, ctx->cur);
-                if (e != hipSuccess) return fail(ctx, AEFFT_EHIP, "recon_expand", e);
-            }
+            RET_IF(launch_or_fail(ctx, KID_OPFORM, ((double)OPC * q.dD * PO + (double)n->B * q.dD * PO + (double)n->B * q.dD * q.P) * 8.0, "recon_expand",
+                                  [&] { return launch_recon_expand(src, n->Xf, n->recon_exp, n->B, q.dD, q.Nx, q.Ny, nxo, nyo, ctx->cur); }));
             return do_c2r(ctx, n->recon_exp, recon_d, (long)n->B * q.dD, nxo, nyo, n->Nx, n->Ny, 1.0f / ((float)n->Nx * (float)n->Ny), wsid);
         }
         // small supports: O_0,b = O^_0 [x_b; 1] is evaluated inside the column pass of the inverse transform (no stored planes)
@@ -173,87 +177,98 @@ static int launch_recon(aefft_net* n, float* recon_d, int wsid)
     return do_c2r(ctx, src, recon_d, (long)n->B * q.dD, nxo, nyo, n->Nx, n->Ny, 1.0f / ((float)n->Nx * (float)n->Ny), wsid);
 }
 
-// lazy: encoder outputs that are only consumed through pool_fft are computed on the pooled grid alone (the bins the crop
-// discards are never formed; aefft_net_get_layer recomputes such a layer on demand).  The training step uses it.
-// op: run the network on the OPC basis frames (the activation buffers then hold the per-bin operators A_l, O^_l) -- the
-// frames themselves only go through the input transform, the second moments and the reconstruction.
-static int net_forward(aefft_net* n, const float* frames_d, float* recon_d, bool lazy, bool op = false)
+// How net_forward runs, decided in front of its first launch.
+struct FwdPlan {
+    bool chain;        // the whole network on the basis frames in one launch (chain_kernel)
+    bool chain_cc;     // ... reading the bin-major record Wp and the compact Cc planes only
+    bool need_chain;   // ... and the operators of the current weights are not at hand (first step, weights set from outside)
+    bool prefetch;     // the input transform runs on the side stream aux[1] (aefft_net_set_input_ready)
+    bool async;        // the reconstruction runs on the side stream aux[0]
+    bool defer;        // ... launched by aefft_net_step_grad after the gradient half (pipelined mode)
+    bool want_fork;    // ... forked behind the last launch in front of the gradient kernels
+};
+
+static FwdPlan forward_plan(const aefft_net* n, bool recon, bool lazy, bool op)
 {
-    if (!n || !frames_d) return fail(n ? n->ctx : nullptr, AEFFT_EINVAL, "aefft_net_forward: bad argument");
-    aefft_ctx* ctx = n->ctx;
-    const int BF = n->B;                       // frames
-    const int B = op ? (int)OPC : n->B;        // columns of the activation buffers
-    const int L = n->L;
-    struct BiasColGuard { aefft_ctx* c; ~BiasColGuard() { c->biasColP1 = 0; } } guard{ctx};
-    ctx->biasColP1 = op ? (int)OPC : 0;        // conv_k biases: the affine column only
-    RET_IF(join_recon(ctx));
-    n->xx_done = false; n->ox_done = 0;
-    n->upd_after_fwd = false;
+    const aefft_ctx* ctx = n->ctx;
+    FwdPlan f{};
     // the whole network on the basis frames in one launch (chain_kernel): hidden layers not materialised, decoder outputs on the
     // coarsest grid's support, operators in their own buffers
-    const bool chain_plan = op && lazy && n->Wp && (n->compact || L == 1) && chain_switches_ok();
+    f.chain = op && lazy && n->Wp && (n->compact || n->L == 1) && chain_switches_ok();
     // (the chain launch reads the bin-major record Wp and the compact Cc planes only: planar spectra that a training step in operator
     // form does not refresh are formed when something else asks for them)
-    const bool chain_cc = chain_plan && (L == 1 || n->pr[0].Cc != nullptr);
-    n->op_state = op && !chain_plan;
-    n->op_chain = chain_plan;
-    n->act_stale = chain_plan;
-    for (int l = 0; l < L; ++l) if (!(chain_cc || (chain_plan && l == L - 1 && L > 1))) RET_IF(ensure_spectra(n, n->pr[l]));
-    // the reconstruction's side stream forks behind the last launch in front of the gradient kernels -- the input transform's column
-    // pass, or the chain launch when the operators of the current weights are not at hand (first step, weights set from outside) --
-    // through that dispatch's own completion signal
+    f.chain_cc = f.chain && (n->L == 1 || n->pr[0].Cc != nullptr);
+    f.need_chain = f.chain && !n->chain_valid;
+    f.prefetch = lazy && n->input_ready && n->X0alt && ctx->aux[1] != nullptr && !ctx->prof && !flag(AEFFT_F_NOPREFETCH);
     // (reconstructions beyond ~256 MB -- 32 frames of 1024^2 -- stay on the context stream: beside their row pass the pruned inverse transform
     // of S stretches from 42 to 145 us and the side stream costs more than it hides, 1.084 vs 1.057 ms per cfg5 step; at cfg3 it saves 15 of 203 us)
     // ... and reconstructions below ~8 MB (cfg2: one 256^2 frame, 11 us of kernels) stay there as well: the fork and join packets cost more than the
     // two kernels they would hide (0.074 vs 0.076 ms per cfg2 step)
     const double recon_bytes = (double)n->B * n->D * n->Nx * n->Ny * 4.0;
     const bool overlap_pays = recon_bytes <= 256e6 && (recon_bytes >= 8e6 || flag(AEFFT_F_SMALLOVERLAP));
-    const bool want_fork = chain_plan && recon_d && ctx->aux[0] != nullptr && !flag(AEFFT_F_NOOVERLAP) && overlap_pays && !ctx->prof &&
-                           !(n->input_ready && !flag(AEFFT_F_NODEFER)) && ctx->cur == ctx->stream;
-    const bool need_chain = chain_plan && !n->chain_valid;
-    bool fork_recorded = false;
-    // encoder (fft_backproplib.cu:1340-1357): R2C fused with pair 0's pooling, then pool -> conv per pair
-    const bool prefetch = lazy && n->input_ready && n->X0alt && ctx->aux[1] != nullptr && !ctx->prof && !flag(AEFFT_F_NOPREFETCH);
-    if (prefetch) {
-        // The caller guarantees the frames are complete: their R2C goes to a side stream and may overlap the tail of the previous
-        // step.  It writes the OTHER input-spectra buffer (the current one is still read by that tail), which was last read two
-        // steps ago: wait for that step's end only.
-        std::swap(n->Xf, n->X0alt);
-        if (n->ev_end_valid[n->step_no & 1]) HIPCHK(ctx, hipStreamWaitEvent(ctx->aux[1], n->ev_end[n->step_no & 1], 0));
-        // not earlier than the end of the previous step's gradient half: that is where a data-parallel run waits for its
-        // all-reduce (an otherwise idle gap), and what follows on this stream (update, spectra, MSE) is latency-bound
-        if (n->ev_mid_valid) HIPCHK(ctx, hipStreamWaitEvent(ctx->aux[1], n->ev_mid, 0));
-        ctx->cur = ctx->aux[1];
-        const int rc = do_r2c(ctx, frames_d, n->Xf, (long)BF * n->D, n->Nx, n->Ny, n->pr[0].Nx, n->pr[0].Ny, WS_MID2, nullptr, ctx->in_u8);
-        ctx->cur = ctx->stream;
-        RET_IF(rc);
-        HIPCHK(ctx, hipEventRecord(n->ev_r2c, ctx->aux[1]));
-        HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, n->ev_r2c, 0));
-    } else {
-        const bool fork_r2c = want_fork && !need_chain;
-        RET_IF(do_r2c(ctx, frames_d, n->Xf, (long)BF * n->D, n->Nx, n->Ny, n->pr[0].Nx, n->pr[0].Ny, WS_MID, fork_r2c ? ctx->ev_fork : nullptr, ctx->in_u8));
-        fork_recorded = fork_r2c;
+    f.async = lazy && ctx->aux[0] != nullptr && !flag(AEFFT_F_NOOVERLAP) && overlap_pays && !ctx->prof;
+    f.defer = f.async && n->input_ready && !flag(AEFFT_F_NODEFER);
+    // the reconstruction's side stream forks behind the last launch in front of the gradient kernels -- the input transform's column
+    // pass, or the chain launch when the operators of the current weights are not at hand (first step, weights set from outside) --
+    // through that dispatch's own completion signal
+    f.want_fork = f.chain && recon && f.async && !f.defer && ctx->cur == ctx->stream;
+    return f;
+}
+
+// R2C of the frames fused with pair 0's pooling, into the input spectra Xf.  *forked: ctx->ev_fork is recorded behind it.
+static int forward_input(aefft_net* n, const float* frames_d, bool u8, const FwdPlan& plan, bool* forked)
+{
+    aefft_ctx* ctx = n->ctx;
+    const long planes = (long)n->B * n->D;
+    const Pair& q0 = n->pr[0];
+    if (!plan.prefetch) {
+        const bool fork_r2c = plan.want_fork && !plan.need_chain;
+        RET_IF(do_r2c(ctx, frames_d, n->Xf, planes, n->Nx, n->Ny, q0.Nx, q0.Ny, WS_MID, fork_r2c ? ctx->ev_fork : nullptr, u8));
+        *forked = fork_r2c;
+        return AEFFT_OK;
     }
-    n->pr[0].X = n->op_state ? n->A0hat : n->Xf;
-    bool chained = false;
-    if (chain_plan) {
-        if (need_chain) {
-            RET_IF(ensure_packed(n));
-            ChainArgs ca{};
-            double bytes = 0;
-            fill_chain(n, ca, n->op_set, &bytes);
-            Bracket br(ctx, KID_CHAIN, bytes);
-            const bool fork_here = want_fork && !fork_recorded;
-            hipError_t e = launch_chain(ca, ctx->cur, fork_here ? ctx->ev_fork : nullptr);
-            if (e != hipSuccess) return fail(ctx, AEFFT_EHIP, "chain", e);
-            fork_recorded = fork_recorded || fork_here;
-            n->chain_valid = true;
-        }
-        n->op_fwd = n->op_set;
-        for (int l = 0; l < L; ++l) { Pair& q = n->pr[l]; q.H_stale = true; q.O_stale = q.P != n->Pc; }      // (what ensure_frames leaves in the activation buffers)
-        chained = true;
+    // The caller guarantees the frames are complete: their R2C goes to a side stream and may overlap the tail of the previous
+    // step.  It writes the OTHER input-spectra buffer (the current one is still read by that tail), which was last read two
+    // steps ago: wait for that step's end only.
+    std::swap(n->Xf, n->X0alt);
+    if (n->ev_end_valid[n->step_no & 1]) HIPCHK(ctx, hipStreamWaitEvent(ctx->aux[1], n->ev_end[n->step_no & 1], 0));
+    // not earlier than the end of the previous step's gradient half: that is where a data-parallel run waits for its
+    // all-reduce (an otherwise idle gap), and what follows on this stream (update, spectra, MSE) is latency-bound
+    if (n->ev_mid_valid) HIPCHK(ctx, hipStreamWaitEvent(ctx->aux[1], n->ev_mid, 0));
+    {
+        OnStream on(ctx, ctx->aux[1]);
+        RET_IF(do_r2c(ctx, frames_d, n->Xf, planes, n->Nx, n->Ny, q0.Nx, q0.Ny, WS_MID2, nullptr, u8));
     }
-    for (int l = 0; l < L && !chained; ++l) {
+    HIPCHK(ctx, hipEventRecord(n->ev_r2c, ctx->aux[1]));
+    HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, n->ev_r2c, 0));
+    return AEFFT_OK;
+}
+
+// the chain launch, unless the previous step's tail launch already ran it on the current weights
+static int forward_chain(aefft_net* n, const FwdPlan& plan, bool* forked)
+{
+    if (plan.need_chain) {
+        aefft_ctx* ctx = n->ctx;
+        RET_IF(ensure_packed(n));
+        ChainArgs ca{};
+        double bytes = 0;
+        fill_chain(n, ca, n->op_set, &bytes);
+        const bool fork_here = plan.want_fork && !*forked;
+        RET_IF(launch_or_fail(ctx, KID_CHAIN, bytes, "chain", [&] { return launch_chain(ca, ctx->cur, fork_here ? ctx->ev_fork : nullptr); }));
+        *forked = *forked || fork_here;
+        n->chain_valid = true;
+    }
+    n->op_fwd = n->op_set;
+    for (Pair& q : n->pr) { q.H_stale = true; q.O_stale = q.P != n->Pc; }      // (what ensure_frames leaves in the activation buffers)
+    return AEFFT_OK;
+}
+
+// pool -> conv per pair; B columns of the activation buffers
+static int forward_encoder(aefft_net* n, int B, bool lazy, bool op)
+{
+    aefft_ctx* ctx = n->ctx;
+    const int L = n->L;
+    for (int l = 0; l < L; ++l) {
         Pair& q = n->pr[l];
         // the next pair's spectral down-sampling (pool_fft, :1346) is written by this conv's epilogue: no resize launch
         const bool fuse = (l + 1 < L) && n->pr[l + 1].s != 1 && n->fuse_crop && !flag(AEFFT_F_NOFUSECROP);
@@ -279,66 +294,83 @@ static int net_forward(aefft_net* n, const float* frames_d, float* recon_d, bool
             RET_IF(do_resize(ctx, q.H, nx.X, (long)B * nx.dD, nx.Nxin, nx.Nyin, nx.Nx, nx.Ny));
         }
     }
-    // decoder (:1356-1361): conv then zero-pad up-sampling.  The up-sampled tensor is never stored: the next
-    // decoder conv (and the final C2R) read the small spectrum through the zero-pad index map.
+    return AEFFT_OK;
+}
+
+// innermost decoder output on the G route: O = G X + beta, one contraction
+static int decoder_inner_g(aefft_net* n, int B, bool compact)
+{
+    Pair& q = n->pr[n->L - 1];
+    Contract k{};
+    k.A = q.G; k.a_r = (long)q.dD * q.P; k.a_k = q.P;
+    k.B = q.X; k.b_k = q.P; k.b_c = (long)q.dD * q.P;
+    k.Out = q.O; k.o_r = q.P; k.o_c = (long)q.dD * q.P;
+    k.R = q.dD; k.C = B; k.K = q.dD; k.P = q.P;
+    k.bias = q.beta; k.biasScale = (float)q.Nx * (float)q.Ny; k.biasAfterFirst = true;
+    // the batch-first gradient term S = -sum_b X X^H needs only the encoder outputs: it shares this launch
+    // (the decoder chain that follows is a sequence of small dependent launches)
+    n->xx_done = false; n->ox_done = 0;
+    if (compact && n->pr[0].P != n->Pc && n->L + 1 <= 8 && !flag(AEFFT_F_NOGROUP)) {
+        Contract qs[8];
+        qs[0] = k;
+        for (int l2 = 0; l2 < n->L; ++l2) { Pair& q2 = n->pr[l2]; qs[1 + l2] = mk_XXneg(q2.X, q2.S, B, q2.dD, q2.P); }
+        RET_IF(do_contract_group(n->ctx, qs, n->L + 1, n->L + 1, 0));
+        n->xx_done = true;
+        return AEFFT_OK;
+    }
+    return do_contract(n->ctx, k);
+}
+
+// Up-sampled spectra are zero outside the image of the coarsest grid, and conv_k maps zero to zero (the bias sits on
+// the DC bin, inside it): every decoder output lives on those Pc bins.  The training step computes and stores only them:
+//   Oc_l[b][d][s] = sum_m F_l[d][m][map_l(s)] * Oc_{l+1}[b][m][s] / dD + p[d] Nx Ny [s == 0]
+// DECLINED: shapes the contraction does not serve.
+static int decoder_compact(aefft_net* n, int l, int B, bool op)
+{
+    aefft_ctx* ctx = n->ctx;
+    Pair& q = n->pr[l];
+    const Pair& in = n->pr[l + 1];
+    Contract k{};
+    k.A = q.F; k.a_r = (long)q.dM * q.P; k.a_k = q.P;
+    k.B = in.Oc; k.b_k = n->Pc; k.b_c = (long)q.dM * n->Pc;
+    k.Out = q.Oc; k.o_r = n->Pc; k.o_c = (long)q.dD * n->Pc;
+    k.R = q.dD; k.C = B; k.K = q.dM; k.P = n->Pc;
+    k.preDivB = (float)q.dD;
+    k.bias = q.p; k.biasScale = (float)q.Nx * (float)q.Ny; k.biasAfterFirst = true;
+    k.gdNx = q.Nx; k.gdNy = q.Ny; k.gdNxs = n->NxC; k.gdNys = n->NyC; k.gdMask = 1;
+    if (n->xx_done && !op && !flag(AEFFT_F_NOGROUP) && !flag(AEFFT_F_NOMFMA)) {
+        // S = -sum_b X X^H is already out: the support term of the NEXT-inner pair (its decoder output is final) rides along
+        Pair& qi = n->pr[l + 1];
+        Contract qs[2] = {k, qi.O_stale ? mk_OX(qi.Oc, qi.X, qi.S, B, qi.dD, qi.P, n->Pc, qi.Nx, qi.Ny, n->NxC, n->NyC)
+                                        : mk_OX(qi.O, qi.X, qi.S, B, qi.dD, qi.P, qi.P, qi.Nx, qi.Ny, qi.Nx, qi.Ny)};
+        RET_IF(do_contract_group(ctx, qs, 2, 2, 0));
+        n->ox_done |= 1u << (l + 1);
+        return AEFFT_OK;
+    }
+    return launch_or_decline(ctx, KID_CONTRACT, ((double)k.R * k.K + (double)k.K * k.C + (double)k.R * k.C) * k.P * 8.0, "contract(compact decoder)",
+                             [&] { return launch_contract(bc(ctx, k), ctx->cur); });
+}
+
+// decoder (:1356-1361): conv then zero-pad up-sampling.  The up-sampled tensor is never stored: the next
+// decoder conv (and the final C2R) read the small spectrum through the zero-pad index map.
+static int forward_decoder(aefft_net* n, int B, bool lazy, bool op)
+{
+    aefft_ctx* ctx = n->ctx;
+    const int L = n->L;
     const bool nocompact = flag(AEFFT_F_NOCOMPACT);
     bool compact = lazy && n->compact && !nocompact && L > 1;
-    for (int l = L - 1; l >= 0 && !chained; --l) {
+    Pair& qi = n->pr[L - 1];
+    qi.O_stale = false;
+    if (qi.H_stale) RET_IF(decoder_inner_g(n, B, compact));      // (set by the encoder: G route)
+    else RET_IF(do_conv(ctx, qi.H, qi.F, qi.p, qi.O, B, qi.dD, qi.dM, qi.Nx, qi.Ny));
+    for (int l = L - 2; l >= 0; --l) {
         Pair& q = n->pr[l];
-        q.O_stale = false;
-        if (l == L - 1) {
-            if (q.H_stale) {                       // (set above: G route)
-                Contract k{};
-                k.A = q.G; k.a_r = (long)q.dD * q.P; k.a_k = q.P;
-                k.B = q.X; k.b_k = q.P; k.b_c = (long)q.dD * q.P;
-                k.Out = q.O; k.o_r = q.P; k.o_c = (long)q.dD * q.P;
-                k.R = q.dD; k.C = B; k.K = q.dD; k.P = q.P;
-                k.bias = q.beta; k.biasScale = (float)q.Nx * (float)q.Ny; k.biasAfterFirst = true;
-                // the batch-first gradient term S = -sum_b X X^H needs only the encoder outputs: it shares this launch
-                // (the decoder chain that follows is a sequence of small dependent launches)
-                n->xx_done = false; n->ox_done = 0;
-                if (compact && n->pr[0].P != n->Pc && L + 1 <= 8 && !flag(AEFFT_F_NOGROUP)) {
-                    Contract qs[8];
-                    qs[0] = k;
-                    for (int l2 = 0; l2 < L; ++l2) { Pair& q2 = n->pr[l2]; qs[1 + l2] = mk_XXneg(q2.X, q2.S, B, q2.dD, q2.P); }
-                    RET_IF(do_contract_group(ctx, qs, L + 1, L + 1, 0));
-                    n->xx_done = true;
-                } else
-                RET_IF(do_contract(ctx, k));
-            } else RET_IF(do_conv(ctx, q.H, q.F, q.p, q.O, B, q.dD, q.dM, q.Nx, q.Ny));
-            continue;
-        }
         const Pair& in = n->pr[l + 1];
+        q.O_stale = false;
         if (compact && q.P != n->Pc) {
-            // Up-sampled spectra are zero outside the image of the coarsest grid, and conv_k maps zero to zero (the bias sits on
-            // the DC bin, inside it): every decoder output lives on those Pc bins.  The training step computes and stores only them:
-            //   Oc_l[b][d][s] = sum_m F_l[d][m][map_l(s)] * Oc_{l+1}[b][m][s] / dD + p[d] Nx Ny [s == 0]
-            Contract k{};
-            k.A = q.F; k.a_r = (long)q.dM * q.P; k.a_k = q.P;
-            k.B = in.Oc; k.b_k = n->Pc; k.b_c = (long)q.dM * n->Pc;
-            k.Out = q.Oc; k.o_r = n->Pc; k.o_c = (long)q.dD * n->Pc;
-            k.R = q.dD; k.C = B; k.K = q.dM; k.P = n->Pc;
-            k.preDivB = (float)q.dD;
-            k.bias = q.p; k.biasScale = (float)q.Nx * (float)q.Ny; k.biasAfterFirst = true;
-            k.gdNx = q.Nx; k.gdNy = q.Ny; k.gdNxs = n->NxC; k.gdNys = n->NyC; k.gdMask = 1;
-            if (n->xx_done && !op && !flag(AEFFT_F_NOGROUP) && !flag(AEFFT_F_NOMFMA)) {
-                // S = -sum_b X X^H is already out: the support term of the NEXT-inner pair (its decoder output is final) rides along
-                Pair& qi = n->pr[l + 1];
-                Contract qs[2] = {k, qi.O_stale ? mk_OX(qi.Oc, qi.X, qi.S, B, qi.dD, qi.P, n->Pc, qi.Nx, qi.Ny, n->NxC, n->NyC)
-                                                : mk_OX(qi.O, qi.X, qi.S, B, qi.dD, qi.P, qi.P, qi.Nx, qi.Ny, qi.Nx, qi.Ny)};
-                RET_IF(do_contract_group(ctx, qs, 2, 2, 0));
-                n->ox_done |= 1u << (l + 1);
-                q.O_stale = true;
-                continue;
-            }
-            hipError_t e;
-            {
-                Bracket br(ctx, KID_CONTRACT, ((double)k.R * k.K + (double)k.K * k.C + (double)k.R * k.C) * k.P * 8.0);
-                e = launch_contract(bc(ctx, k), ctx->cur);
-            }
-            if (e == hipSuccess) { q.O_stale = true; continue; }
-            if (e != hipErrorInvalidValue) return fail(ctx, AEFFT_EHIP, "contract(compact decoder)", e);
-            (void)hipGetLastError();
+            const int rc = decoder_compact(n, l, B, op);
+            if (rc == AEFFT_OK) { q.O_stale = true; continue; }
+            if (rc != DECLINED) return rc;
             // declined: from here down the full-grid decoder; the levels already done are expanded first
             n->compact = compact = false;
             for (int l2 = L - 2; l2 > l; --l2) {
@@ -349,31 +381,64 @@ static int net_forward(aefft_net* n, const float* frames_d, float* recon_d, bool
         }
         RET_IF(do_conv_up(ctx, in.O, q.F, q.p, q.O, B, q.dD, q.dM, q.Nx, q.Ny, in.Nx, in.Ny));
     }
-    if (recon_d) {   // :1373 fft_inv of the up-sampled last output, fused zero-pad
-        const bool nooverlap = flag(AEFFT_F_NOOVERLAP);
-        const bool async = lazy && ctx->aux[0] != nullptr && !nooverlap && overlap_pays && !ctx->prof;
-        n->recon_deferred = nullptr;
-        if (async && n->input_ready && !flag(AEFFT_F_NODEFER)) {
-            // pipelined loop (aefft_net_set_input_ready): launched by aefft_net_step_grad after the gradient half instead
-            n->recon_deferred = recon_d;
-            n->last_frames = frames_d; n->last_frames_u8 = ctx->in_u8;
-            n->have_forward = true; n->have_grad = false;
-            return AEFFT_OK;
-        }
-        if (async) {
-            // training step: nothing downstream reads the reconstruction, so its (bandwidth-bound) inverse FFT runs on a side
-            // stream underneath the latency-bound gradient contractions; aefft_net_step_grad joins it before returning
-            if (!fork_recorded) HIPCHK(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
-            HIPCHK(ctx, hipStreamWaitEvent(ctx->aux[0], ctx->ev_fork, 0));
-            ctx->cur = ctx->aux[0];
-        }
-        // (a side-stream transform has its own column/row workspace: the main stream's FFTs of non-pruned kernel supports use WS_MID)
-        const int rc = launch_recon(n, recon_d, async ? WS_MID3 : WS_MID);
-        ctx->cur = ctx->stream;
-        RET_IF(rc);
-        n->recon_pending = async;
+    return AEFFT_OK;
+}
+
+// :1373 fft_inv of the up-sampled last output, fused zero-pad
+static int forward_recon(aefft_net* n, float* recon_d, const FwdPlan& plan, bool forked)
+{
+    aefft_ctx* ctx = n->ctx;
+    n->recon_deferred = nullptr;
+    if (plan.defer) {
+        // pipelined loop (aefft_net_set_input_ready): launched by aefft_net_step_grad after the gradient half instead
+        n->recon_deferred = recon_d;
+        return AEFFT_OK;
     }
-    n->last_frames = frames_d; n->last_frames_u8 = ctx->in_u8;
+    if (plan.async) {
+        // training step: nothing downstream reads the reconstruction, so its (bandwidth-bound) inverse FFT runs on a side
+        // stream underneath the latency-bound gradient contractions; aefft_net_step_grad joins it before returning
+        if (!forked) HIPCHK(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
+        HIPCHK(ctx, hipStreamWaitEvent(ctx->aux[0], ctx->ev_fork, 0));
+    }
+    {
+        // (a side-stream transform has its own column/row workspace: the main stream's FFTs of non-pruned kernel supports use WS_MID)
+        OnStream on(ctx, plan.async ? ctx->aux[0] : ctx->cur);
+        RET_IF(launch_recon(n, recon_d, plan.async ? WS_MID3 : WS_MID));
+    }
+    n->recon_pending = plan.async;
+    return AEFFT_OK;
+}
+
+// lazy: encoder outputs that are only consumed through pool_fft are computed on the pooled grid alone (the bins the crop
+// discards are never formed; aefft_net_get_layer recomputes such a layer on demand).  The training step uses it.
+// op: run the network on the OPC basis frames (the activation buffers then hold the per-bin operators A_l, O^_l) -- the
+// frames themselves only go through the input transform, the second moments and the reconstruction.
+// u8: the frames are 8-bit pixels (the input transform converts on load).
+static int net_forward(aefft_net* n, const float* frames_d, bool u8, float* recon_d, bool lazy, bool op = false)
+{
+    if (!n || !frames_d) return fail(n ? n->ctx : nullptr, AEFFT_EINVAL, "aefft_net_forward: bad argument");
+    aefft_ctx* ctx = n->ctx;
+    const int B = op ? (int)OPC : n->B;        // columns of the activation buffers
+    BiasColGuard bias_col(ctx, op ? (int)OPC : 0);     // conv_k biases: the affine column only
+    RET_IF(join_recon(ctx));
+    n->xx_done = false; n->ox_done = 0;
+    n->upd_after_fwd = false;
+    const FwdPlan plan = forward_plan(n, recon_d != nullptr, lazy, op);
+    n->op_state = op && !plan.chain;
+    n->op_chain = plan.chain;
+    n->act_stale = plan.chain;
+    for (int l = 0; l < n->L; ++l) if (!(plan.chain_cc || (plan.chain && l == n->L - 1 && n->L > 1))) RET_IF(ensure_spectra(n, n->pr[l]));
+    // encoder (fft_backproplib.cu:1340-1357): R2C fused with pair 0's pooling, then pool -> conv per pair
+    bool forked = false;
+    RET_IF(forward_input(n, frames_d, u8, plan, &forked));
+    n->pr[0].X = n->op_state ? n->A0hat : n->Xf;
+    if (plan.chain) RET_IF(forward_chain(n, plan, &forked));
+    else {
+        RET_IF(forward_encoder(n, B, lazy, op));
+        RET_IF(forward_decoder(n, B, lazy, op));
+    }
+    if (recon_d) RET_IF(forward_recon(n, recon_d, plan, forked));
+    n->last_frames = frames_d; n->last_frames_u8 = u8;
     n->have_forward = true; n->have_grad = false;
     return AEFFT_OK;
 }
@@ -390,16 +455,13 @@ int aefft::ensure_frames(aefft_net* n)
         const Pair& q0 = n->pr[0];
         for (int l = 0; l < n->L; ++l) {
             Pair& q = n->pr[l];
-            hipError_t e = hipSuccess;
-            if (l > 0) {
-                Bracket br(ctx, KID_OPFORM, ((double)OPC * q.dD + (double)n->B * (q.dD + n->D)) * q.P * 8.0);
-                e = launch_op_expand(q.opA[n->op_fwd], n->Xf, q.X, n->B, n->D, q.dD, q0.Nx, q0.Ny, q.Nx, q.Ny, ctx->cur);
-            }
-            if (e == hipSuccess) {
-                Bracket br(ctx, KID_OPFORM, ((double)OPC * q.dD + (double)n->B * (q.dD + n->D)) * n->Pc * 8.0);
-                e = launch_op_expand(q.opO[n->op_fwd], n->Xf, q.P != n->Pc ? q.Oc : q.O, n->B, n->D, q.dD, q0.Nx, q0.Ny, n->NxC, n->NyC, ctx->cur);
-            }
-            if (e != hipSuccess) return fail(ctx, AEFFT_EHIP, "op_expand", e);
+            const double rows = (double)OPC * q.dD + (double)n->B * (q.dD + n->D);
+            if (l > 0)
+                RET_IF(launch_or_fail(ctx, KID_OPFORM, rows * q.P * 8.0, "op_expand",
+                                      [&] { return launch_op_expand(q.opA[n->op_fwd], n->Xf, q.X, n->B, n->D, q.dD, q0.Nx, q0.Ny, q.Nx, q.Ny, ctx->cur); }));
+            RET_IF(launch_or_fail(ctx, KID_OPFORM, rows * n->Pc * 8.0, "op_expand", [&] {
+                return launch_op_expand(q.opO[n->op_fwd], n->Xf, q.P != n->Pc ? q.Oc : q.O, n->B, n->D, q.dD, q0.Nx, q0.Ny, n->NxC, n->NyC, ctx->cur);
+            }));
             q.H_stale = true; q.O_stale = q.P != n->Pc;
         }
         n->pr[0].X = n->Xf;
@@ -409,18 +471,23 @@ int aefft::ensure_frames(aefft_net* n)
     if (!n->op_state) return AEFFT_OK;
     // (operator form without the chain launch: the activation buffers hold the operators themselves; the per-frame forward of the
     // same frames is run -- the caller's frame buffer must still hold them, include/aefft.h)
-    const bool hg = n->have_grad, u8 = n->ctx->in_u8;
-    n->ctx->in_u8 = n->last_frames_u8;
-    const int rcf = net_forward(n, n->last_frames, nullptr, false, false);
-    n->ctx->in_u8 = u8;
-    RET_IF(rcf);
+    const bool hg = n->have_grad;
+    RET_IF(net_forward(n, n->last_frames, n->last_frames_u8, nullptr, false, false));
     n->have_grad = hg;
     return AEFFT_OK;
 }
 
 extern "C" int aefft_net_forward(aefft_net* n, const float* frames_d, float* recon_d)
 {
-    RET_IF(net_forward(n, frames_d, recon_d, false));
+    RET_IF(net_forward(n, frames_d, false, recon_d, false));
+    return mark_step_point(n);
+}
+
+// 8-bit frames: the same calls with the input transform converting on load (fft_kernels.hip r2c_rows_kernel<N, true>); nothing else reads the frames
+extern "C" int aefft_net_forward_u8(aefft_net* n, const unsigned char* frames_d, float* recon_d)
+{
+    if (!n) return AEFFT_EINVAL;
+    RET_IF(net_forward(n, reinterpret_cast<const float*>(frames_d), true, recon_d, false));
     return mark_step_point(n);
 }
 
@@ -439,34 +506,39 @@ static int mse_flush(aefft_net* n)
 {
     if (!n->mse_pending) return AEFFT_OK;
     aefft_ctx* ctx = n->ctx;
-    Bracket br(ctx, KID_DIFFMSE, 4.0 * n->L * MSE_SLOTS);
-    hipError_t e = launch_mse_finish(n->mse_slots, n->mse_post, nullptr, n->L, ctx->cur, nullptr, n->grad + n->grad_n, n->mse_pending_scale);
-    if (e != hipSuccess) return fail(ctx, AEFFT_EHIP, "mse_finish(deferred)", e);
+    RET_IF(launch_or_fail(ctx, KID_DIFFMSE, 4.0 * n->L * MSE_SLOTS, "mse_finish(deferred)", [&] {
+        return launch_mse_finish(n->mse_slots, n->mse_post, nullptr, n->L, ctx->cur, nullptr, n->grad + n->grad_n, n->mse_pending_scale);
+    }));
     n->mse_pending = false;
     return AEFFT_OK;
+}
+
+// dc|df spectra of pair q -> its dck|dfk taps (inverse transform and shrink to the kernel support)
+static int shrink_dcdf(aefft_net* n, const Pair& q)
+{
+    aefft_ctx* ctx = n->ctx;
+    const GradSeg gs = q.grads(n->grad);
+    const long planes = (long)q.dM * q.dD;
+    if (q.part) return do_c2r_shrink(ctx, q.dc, gs.dck, nullptr, q.part, 2 * planes, q.Nx, q.Ny, q.Nk, q.Nl);   // dc|df -> dck|dfk, one launch
+    RET_IF(do_c2r_shrink(ctx, q.dc, gs.dck, n->real, nullptr, planes, q.Nx, q.Ny, q.Nk, q.Nl));
+    return do_c2r_shrink(ctx, q.df, gs.dfk, n->real, nullptr, planes, q.Nx, q.Ny, q.Nk, q.Nl);
 }
 
 // gradient half of one loop-body iteration on pair q: needs X (= T, autoencoder.cpp:194) and the current O.
 static int pair_grad(aefft_net* n, Pair& q)
 {
-    aefft_ctx* ctx = n->ctx;
-    float* g = n->grad + q.goff;
-    const size_t nk = (size_t)q.dM * q.dD * q.Nk * q.Nl;
+    const GradSeg gs = q.grads(n->grad);
     RET_IF(ensure_O(n, q));
-    RET_IF(do_gradient(ctx, q.X, q.X, q.O, q.C, q.F, q.b, q.S, q.dc, q.df, g + 2 * nk, g + 2 * nk + q.dM, n->B, q.dM, q.dD, q.Nx, q.Ny));
-    const long planes = (long)q.dM * q.dD;
-    if (q.part) return do_c2r_shrink(ctx, q.dc, g, nullptr, q.part, 2 * planes, q.Nx, q.Ny, q.Nk, q.Nl);   // dc|df -> dck|dfk, one launch
-    RET_IF(do_c2r_shrink(ctx, q.dc, g, n->real, nullptr, planes, q.Nx, q.Ny, q.Nk, q.Nl));
-    return do_c2r_shrink(ctx, q.df, g + nk, n->real, nullptr, planes, q.Nx, q.Ny, q.Nk, q.Nl);
+    RET_IF(do_gradient(n->ctx, q.X, q.X, q.O, q.C, q.F, q.b, q.S, q.dc, q.df, gs.db, gs.dp, n->B, q.dM, q.dD, q.Nx, q.Ny));
+    return shrink_dcdf(n, q);
 }
 
 // update half: weights, new spectra, re-forward of the pair alone, post-update MSE accumulated into *mse_slot (pre-zeroed)
 static int pair_apply(aefft_net* n, Pair& q, float del, int maxdiff, int sym, float gscale, float* mse_slot)
 {
     aefft_ctx* ctx = n->ctx;
-    float* g = n->grad + q.goff;
-    const size_t nk = (size_t)q.dM * q.dD * q.Nk * q.Nl;
-    RET_IF(do_update(ctx, q.c, q.f, q.b, q.p, g, g + nk, g + 2 * nk, g + 2 * nk + q.dM, Momentum{q.Dc, q.Df, q.Db, q.Dp},
+    const GradSeg gs = q.grads(n->grad);
+    RET_IF(do_update(ctx, q.c, q.f, q.b, q.p, gs.dck, gs.dfk, gs.db, gs.dp, Momentum{q.Dc, q.Df, q.Db, q.Dp},
                      q.dM, q.dD, q.Nk, q.Nl, del, maxdiff, sym, gscale, n->burst ? nullptr : mse_slot));
     RET_IF(pair_spectra(n, q));
     // re-forward of this pair alone (fft_backproplib.cu:1460-1461) and its MSE (:1463)
@@ -493,7 +565,7 @@ extern "C" int aefft_net_train_pair(aefft_net* n, int l, int n_iter, float del0,
         RET_IF(net_alloc_t(n, &nm, (size_t)n_iter + 1));
         n->mse_dev = nm; n->mse_cap = (size_t)n_iter + 1;
     }
-    const size_t nk = (size_t)q.dM * q.dD * q.Nk * q.Nl;
+    const size_t nk = q.nk();
     // momentum lives only inside the burst (fft_backproplib.cu:1420-1423)
     HIPCHK(ctx, hipMemsetAsync(q.Dc, 0, nk * 4, ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(q.Df, 0, nk * 4, ctx->stream));
@@ -525,44 +597,56 @@ static int bias_and_kgrad(aefft_net* n, Pair& q)
 {
     RET_IF(ensure_O(n, q));
     aefft_ctx* ctx = n->ctx;
-    float* g = n->grad + q.goff;
-    const size_t nk = (size_t)q.dM * q.dD * q.Nk * q.Nl;
+    const GradSeg gs = q.grads(n->grad);
     const float norm = (float)q.Nx * (float)q.Ny, Norm = grad_norm(q.dM, q.dD, q.Nx, q.Ny);
-    {
-        Bracket br(ctx, KID_BIASGRAD, ((double)(q.dM * q.dD + q.dM + q.dD) + 2.0 * n->B * q.dD) * 8.0);
-        hipError_t e = launch_bias_grad(q.O, q.X, q.F, q.b, q.df, g + 2 * nk, g + 2 * nk + q.dM, n->B, q.dM, q.dD, q.P, norm, Norm, ctx->cur);
-        if (e != hipSuccess) return fail(ctx, AEFFT_EHIP, "bias_grad", e);
-    }
-    const long planes = (long)q.dM * q.dD;
-    if (q.part) return do_c2r_shrink(ctx, q.dc, g, nullptr, q.part, 2 * planes, q.Nx, q.Ny, q.Nk, q.Nl);
-    RET_IF(do_c2r_shrink(ctx, q.dc, g, n->real, nullptr, planes, q.Nx, q.Ny, q.Nk, q.Nl));
-    return do_c2r_shrink(ctx, q.df, g + nk, n->real, nullptr, planes, q.Nx, q.Ny, q.Nk, q.Nl);
+    RET_IF(launch_or_fail(ctx, KID_BIASGRAD, ((double)(q.dM * q.dD + q.dM + q.dD) + 2.0 * n->B * q.dD) * 8.0, "bias_grad",
+                          [&] { return launch_bias_grad(q.O, q.X, q.F, q.b, q.df, gs.db, gs.dp, n->B, q.dM, q.dD, q.P, norm, Norm, ctx->cur); }));
+    return shrink_dcdf(n, q);
 }
 
-static int grads_grouped(aefft_net* n)
+// dc | df of every pair, four pairs (8 problems) per launch
+static int dcdf_batch(aefft_net* n)
+{
+    Contract qs[8];
+    for (int l0 = 0; l0 < n->L; l0 += 4) {
+        const int m = std::min(4, n->L - l0);
+        for (int i = 0; i < m; ++i) {
+            Pair& q = n->pr[l0 + i];
+            const float Norm = grad_norm(q.dM, q.dD, q.Nx, q.Ny);
+            qs[i] = mk_dc(q.F, q.S, q.dc, n->B, q.dM, q.dD, q.P, Norm);
+            qs[m + i] = mk_df(q.C, q.S, q.df, n->B, q.dM, q.dD, q.P, Norm);
+        }
+        RET_IF(do_contract_group(n->ctx, qs, 2 * m, m, 2));
+    }
+    return AEFFT_OK;
+}
+
+// operator form: the batch moments, S_l = sum_b (O_b - X_b) X_b^H and the DC error sums of every pair from the operators: one launch
+static int opform_moments(aefft_net* n)
+{
+    aefft_ctx* ctx = n->ctx;
+    SgradGroup sg{};
+    double bytes = ((double)n->B * n->D + (double)OPC * OPC) * n->pr[0].P * 8.0;      // the input spectra in, the moments out
+    for (int l = 0; l < n->L; ++l) {
+        Pair& q = n->pr[l];
+        const OpView ov = op_view(n, l);
+        const int nxo = ov.nxo, nyo = ov.nyo;
+        sg.q[l] = OpPair{ov.A, ov.O, q.S, q.es, q.dD, q.Nx, q.Ny, nxo, nyo, q.P, bins(nxo, nyo)};
+        bytes += ((double)OPC * q.dD * (q.P + bins(nxo, nyo)) + (double)q.dD * q.dD * q.P) * 8.0;
+    }
+    sg.n = n->L; sg.Xf = n->Xf; sg.Mout = n->Mhat; sg.B = n->B; sg.D0 = n->D; sg.Nx0 = n->pr[0].Nx; sg.Ny0 = n->pr[0].Ny; sg.P0 = n->pr[0].P;
+    return launch_or_fail(ctx, KID_SGRAD, bytes, "sgrad", [&] { return launch_msgrad_group(sg, ctx->cur); });
+}
+
+// per-frame form: S_l = sum_b (O_b - X_b) X_b^H of every pair, four pairs per launch.  With decoder outputs on the coarsest grid's
+// support it is -sum_b X X^H + sum_b Oc X^H, and the forward may have launched either term already (xx_done, ox_done).
+static int support_terms(aefft_net* n)
 {
     aefft_ctx* ctx = n->ctx;
     Contract qs[8];
-    const bool op = op_mode(n);
-    if (op) {
-        // the batch moments, S_l = sum_b (O_b - X_b) X_b^H and the DC error sums of every pair from the operators: one launch
-        SgradGroup sg{};
-        double bytes = ((double)n->B * n->D + (double)OPC * OPC) * n->pr[0].P * 8.0;      // the input spectra in, the moments out
-        for (int l = 0; l < n->L; ++l) {
-            Pair& q = n->pr[l];
-            const OpView ov = op_view(n, l);
-            const int nxo = ov.nxo, nyo = ov.nyo;
-            sg.q[l] = OpPair{ov.A, ov.O, q.S, q.es, q.dD, q.Nx, q.Ny, nxo, nyo, q.P, bins(nxo, nyo)};
-            bytes += ((double)OPC * q.dD * (q.P + bins(nxo, nyo)) + (double)q.dD * q.dD * q.P) * 8.0;
-        }
-        sg.n = n->L; sg.Xf = n->Xf; sg.Mout = n->Mhat; sg.B = n->B; sg.D0 = n->D; sg.Nx0 = n->pr[0].Nx; sg.Ny0 = n->pr[0].Ny; sg.P0 = n->pr[0].P;
-        Bracket br(ctx, KID_SGRAD, bytes);
-        hipError_t e = launch_msgrad_group(sg, ctx->cur);
-        if (e != hipSuccess) return fail(ctx, AEFFT_EHIP, "sgrad", e);
-    }
     bool comp = false;
     for (int l = 0; l < n->L; ++l) comp = comp || n->pr[l].O_stale;
-    for (int l0 = 0; l0 < n->L && !op; l0 += 4) {
+    for (int l0 = 0; l0 < n->L; l0 += 4) {
         const int m = std::min(4, n->L - l0);
         if (!comp) {
             for (int i = 0; i < m; ++i) { Pair& q = n->pr[l0 + i]; qs[i] = mk_S(q.X, q.X, q.O, q.S, n->B, q.dD, q.P); }
@@ -583,113 +667,104 @@ static int grads_grouped(aefft_net* n)
         if (mo == 1) RET_IF(do_contract(ctx, qs[0]));
         else if (mo > 1) RET_IF(do_contract_group(ctx, qs, mo, mo, 1));
     }
+    return AEFFT_OK;
+}
+
+// the DC-bin terms of every pair for the grouped launches (on the Q path they also read the DC error sums es)
+static int fill_bias_grads(aefft_net* n, bool op, bool qpath, BiasGradGroup& bg, double* bytes)
+{
+    for (int l = 0; l < n->L; ++l) {
+        Pair& q = n->pr[l];
+        const GradSeg gs = q.grads(n->grad);
+        const float Norm = grad_norm(q.dM, q.dD, q.Nx, q.Ny);
+        bg.a[l] = BiasGradArgs{q.O_stale ? q.Oc : q.O, q.X, q.F, q.b, qpath ? nullptr : q.df, gs.db, gs.dp, n->B, q.dM, q.dD, q.P,
+                               (float)q.Nx * (float)q.Ny, Norm, q.O_stale ? n->Pc : q.P, qpath ? q.es : nullptr, op ? q.es : nullptr};
+        if (!q.spectra_valid) {
+            // (operator form: the step left the planar spectra stale; F at the DC bin is record 0 of the
+            // bin-major copy -- element (d1*dM + m) of the pair's F segment, stride 1.  Only F is read through P in this form.)
+            if (!(op && qpath && n->Wp && n->packed_valid)) return fail(n->ctx, AEFFT_ESTATE, "gradient: stale kernel spectra");
+            bg.a[l].F = n->Wp + n->pack.seg[2 * n->L - 1 - l].off;      // (segments: C_0 .. C_{L-1}, F_{L-1} .. F_0)
+            bg.a[l].P = 1;
+        }
+        *bytes += ((double)(q.dM * q.dD + q.dM + q.dD) + 2.0 * n->B * q.dD) * 8.0;
+    }
+    bg.n = n->L;
+    return AEFFT_OK;
+}
+
+// grouped weight gradients through Q = pruned inverse transform of S on the (2Nk-1)^2 offsets (weight_kernels.hip): no dc|df spectra
+static int wgrads_qpath(aefft_net* n, bool op)
+{
+    aefft_ctx* ctx = n->ctx;
+    BiasGradGroup bg{};
+    PrunedGroup pg{};
+    WgradGroup wg{};
+    double bbytes = 0, kbytes = 0, wbytes = 0;
+    RET_IF(fill_bias_grads(n, op, true, bg, &bbytes));
+    const int T = 2 * n->pr[0].Nk - 1;
+    for (int l = 0; l < n->L; ++l) {
+        Pair& q = n->pr[l];
+        const GradSeg gs = q.grads(n->grad);
+        const size_t nk = q.nk();
+        const float Norm = grad_norm(q.dM, q.dD, q.Nx, q.Ny);
+        pg.q[l] = PrunedProb{q.S, q.Q, (long)q.dD * q.dD, q.Nx, q.Ny, 1.0f};
+        pg.chunks[l] = q.Qn;
+        wg.q[l] = WgradProb{q.c, q.f, q.Q, q.es, q.b, gs.dck, gs.dfk, q.dM, q.dD, 1.0f / (Norm * (float)n->B), (float)q.Nx * (float)q.Ny, 1};
+        kbytes += (double)q.dD * q.dD * (q.P * 8.0 + T * T * 4.0);
+        wbytes += (2.0 * nk + (double)q.dD * q.dD * T * T) * 4.0 + 2.0 * nk * 4.0;
+    }
+    pg.n = wg.n = n->L;
+    // (the DC-bin terms ride along as extra workgroups)
+    RET_IF(launch_or_fail(ctx, KID_KGRAD, kbytes + bbytes, "kgrad(group)", [&] { return launch_kgrad_group_taps(pg, ctx->tw, T, ctx->cur, &bg); }));
+    for (int l = 0; l < n->L; ++l) wg.q[l].nq = pg.chunks[l];
+    if (n->mse_pending) {      // the previous step's MSE sums: one more workgroup of this launch (they reach the packed buffer's tail before the all-reduce)
+        wg.fin_slots = n->mse_slots; wg.fin_out = n->mse_post; wg.fin_tail = n->grad + n->grad_n; wg.fin_L = n->L; wg.fin_scale = n->mse_pending_scale;
+    }
+    RET_IF(launch_or_fail(ctx, KID_WGRAD, wbytes, "wgrad(group)", [&] { return launch_wgrad_taps_group(wg, n->pr[0].Nk, ctx->cur); }));
+    n->mse_pending = false;
+    return AEFFT_OK;
+}
+
+// grouped weight gradients through the dc|df spectra: their contractions, the DC-bin terms, then one pruned inverse transform of
+// every pair (pair by pair where that launch declines)
+static int wgrads_dcdf(aefft_net* n, bool op)
+{
+    aefft_ctx* ctx = n->ctx;
+    BiasGradGroup bg{};
+    PrunedGroup pg{};
+    double bbytes = 0, kbytes = 0;
+    RET_IF(fill_bias_grads(n, op, false, bg, &bbytes));
+    for (int l = 0; l < n->L; ++l) {
+        Pair& q = n->pr[l];
+        pg.q[l] = PrunedProb{q.dc, q.grads(n->grad).dck, 2L * q.dM * q.dD, q.Nx, q.Ny, 1.0f};
+        kbytes += 2.0 * q.dM * q.dD * (q.P * 8.0 + q.Nk * q.Nl * 4.0);
+    }
+    pg.n = n->L;
+    RET_IF(dcdf_batch(n));
+    RET_IF(launch_or_fail(ctx, KID_BIASGRAD, bbytes, "bias_grad(group)", [&] { return launch_bias_grad_group(bg, ctx->cur); }));
+    const int rc = launch_or_decline(ctx, KID_KGRAD, kbytes, "kgrad(group)",
+                                     [&] { return launch_kgrad_group(pg, ctx->tw, n->pr[0].Nk, n->pr[0].Nl, ctx->cur); });
+    if (rc != DECLINED) return rc;
+    for (const Pair& q : n->pr) RET_IF(shrink_dcdf(n, q));          // bias terms are done; only the transforms pair by pair
+    return AEFFT_OK;
+}
+
+static int grads_grouped(aefft_net* n)
+{
+    const bool op = op_mode(n);
+    RET_IF(op ? opform_moments(n) : support_terms(n));
     n->xx_done = false; n->ox_done = 0;
     // DC-bin terms and the pruned inverse transforms of all pairs: one launch each when the pairs share (Nk, Nl)
-    const bool nogroup = flag(AEFFT_F_NOGROUP);
-    bool same = op || (n->L > 1 && n->L <= 8 && !nogroup);
-    for (int l = 0; l < n->L && same; ++l) {
-        const Pair& q = n->pr[l];
-        same = q.Nk == n->pr[0].Nk && q.Nl == n->pr[0].Nl && pruned_supported(q.Nk, q.Nl, q.Nx, q.Ny);
-    }
-    const bool noq = flag(AEFFT_F_NOQPATH);
-    bool qpath = op || (same && !noq && n->pr[0].Nk == n->pr[0].Nl && (n->pr[0].Nk == 3 || n->pr[0].Nk == 5));
-    for (int l = 0; l < n->L && qpath; ++l) qpath = n->pr[l].Q != nullptr;
-    if (same) {
-        BiasGradGroup bg{};
-        PrunedGroup pg{};
-        WgradGroup wg{};
-        double bbytes = 0, kbytes = 0, wbytes = 0;
-        const int T = 2 * n->pr[0].Nk - 1;
-        for (int l = 0; l < n->L; ++l) {
-            Pair& q = n->pr[l];
-            float* g = n->grad + q.goff;
-            const size_t nk = (size_t)q.dM * q.dD * q.Nk * q.Nl;
-            const float Norm = grad_norm(q.dM, q.dD, q.Nx, q.Ny);
-            bg.a[l] = BiasGradArgs{q.O_stale ? q.Oc : q.O, q.X, q.F, q.b, qpath ? nullptr : q.df, g + 2 * nk, g + 2 * nk + q.dM, n->B, q.dM, q.dD, q.P,
-                                   (float)q.Nx * (float)q.Ny, Norm, q.O_stale ? n->Pc : q.P, qpath ? q.es : nullptr, op ? q.es : nullptr};
-            if (!q.spectra_valid) {
-                // (operator form: the step left the planar spectra stale; F at the DC bin is record 0 of the
-                // bin-major copy -- element (d1*dM + m) of the pair's F segment, stride 1.  Only F is read through P in this form.)
-                if (!(op && qpath && n->Wp && n->packed_valid)) return fail(ctx, AEFFT_ESTATE, "gradient: stale kernel spectra");
-                bg.a[l].F = n->Wp + n->pack.seg[2 * n->L - 1 - l].off;      // (segments: C_0 .. C_{L-1}, F_{L-1} .. F_0)
-                bg.a[l].P = 1;
-            }
-            bbytes += ((double)(q.dM * q.dD + q.dM + q.dD) + 2.0 * n->B * q.dD) * 8.0;
-            if (qpath) {
-                // weight gradients through Q = pruned inverse transform of S on the (2Nk-1)^2 offsets (weight_kernels.hip): no dc|df spectra
-                pg.q[l] = PrunedProb{q.S, q.Q, (long)q.dD * q.dD, q.Nx, q.Ny, 1.0f};
-                pg.chunks[l] = q.Qn;
-                wg.q[l] = WgradProb{q.c, q.f, q.Q, q.es, q.b, g, g + nk, q.dM, q.dD, 1.0f / (Norm * (float)n->B), (float)q.Nx * (float)q.Ny, 1};
-                kbytes += (double)q.dD * q.dD * (q.P * 8.0 + T * T * 4.0);
-                wbytes += (2.0 * nk + (double)q.dD * q.dD * T * T) * 4.0 + 2.0 * nk * 4.0;
-            } else {
-                pg.q[l] = PrunedProb{q.dc, g, 2L * q.dM * q.dD, q.Nx, q.Ny, 1.0f};
-                kbytes += 2.0 * q.dM * q.dD * (q.P * 8.0 + q.Nk * q.Nl * 4.0);
-            }
-        }
-        bg.n = pg.n = wg.n = n->L;
-        if (!qpath) {
-            // dc | df of every pair in one launch (8 problems)
-            for (int l0 = 0; l0 < n->L; l0 += 4) {
-                const int m = std::min(4, n->L - l0);
-                for (int i = 0; i < m; ++i) {
-                    Pair& q = n->pr[l0 + i];
-                    const float Norm = grad_norm(q.dM, q.dD, q.Nx, q.Ny);
-                    qs[i] = mk_dc(q.F, q.S, q.dc, n->B, q.dM, q.dD, q.P, Norm);
-                    qs[m + i] = mk_df(q.C, q.S, q.df, n->B, q.dM, q.dD, q.P, Norm);
-                }
-                RET_IF(do_contract_group(ctx, qs, 2 * m, m, 2));
-            }
-        }
-        if (!qpath) {
-            Bracket br(ctx, KID_BIASGRAD, bbytes);
-            hipError_t e = launch_bias_grad_group(bg, ctx->cur);
-            if (e != hipSuccess) return fail(ctx, AEFFT_EHIP, "bias_grad(group)", e);
-        }
-        hipError_t e;
-        {
-            Bracket br(ctx, KID_KGRAD, kbytes + (qpath ? bbytes : 0.0));
-            e = qpath ? launch_kgrad_group_taps(pg, ctx->tw, T, ctx->cur, &bg)      // (the DC-bin terms ride along as extra workgroups)
-                      : launch_kgrad_group(pg, ctx->tw, n->pr[0].Nk, n->pr[0].Nl, ctx->cur);
-        }
-        if (e == hipSuccess && qpath) {
-            for (int l = 0; l < n->L; ++l) wg.q[l].nq = pg.chunks[l];
-            if (n->mse_pending) {      // the previous step's MSE sums: one more workgroup of this launch (they reach the packed buffer's tail before the all-reduce)
-                wg.fin_slots = n->mse_slots; wg.fin_out = n->mse_post; wg.fin_tail = n->grad + n->grad_n; wg.fin_L = n->L; wg.fin_scale = n->mse_pending_scale;
-            }
-            Bracket br(ctx, KID_WGRAD, wbytes);
-            e = launch_wgrad_taps_group(wg, n->pr[0].Nk, ctx->cur);
-            if (e != hipSuccess) return fail(ctx, AEFFT_EHIP, "wgrad(group)", e);
-            n->mse_pending = false;
-            return AEFFT_OK;
-        }
-        if (e == hipSuccess) return AEFFT_OK;
-        if (e != hipErrorInvalidValue || qpath) return fail(ctx, AEFFT_EHIP, "kgrad(group)", e);
-        (void)hipGetLastError();
-        for (int l = 0; l < n->L; ++l) {          // bias terms are done; only the transforms pair by pair
-            Pair& q = n->pr[l];
-            float* g = n->grad + q.goff;
-            const size_t nk = (size_t)q.dM * q.dD * q.Nk * q.Nl;
-            const long planes = (long)q.dM * q.dD;
-            if (q.part) { RET_IF(do_c2r_shrink(ctx, q.dc, g, nullptr, q.part, 2 * planes, q.Nx, q.Ny, q.Nk, q.Nl)); continue; }
-            RET_IF(do_c2r_shrink(ctx, q.dc, g, n->real, nullptr, planes, q.Nx, q.Ny, q.Nk, q.Nl));
-            RET_IF(do_c2r_shrink(ctx, q.df, g + nk, n->real, nullptr, planes, q.Nx, q.Ny, q.Nk, q.Nl));
-        }
+    const bool same = (op || (n->L > 1 && n->L <= 8 && !flag(AEFFT_F_NOGROUP))) && shared_supports(n);
+    if (!same) {
+        // pairs with different kernel supports: dc | df per group of pairs, then pair by pair
+        RET_IF(dcdf_batch(n));
+        for (int l = 0; l < n->L; ++l) RET_IF(bias_and_kgrad(n, n->pr[l]));
         return AEFFT_OK;
     }
-    // pairs with different kernel supports: dc | df per group of pairs, then pair by pair
-    for (int l0 = 0; l0 < n->L; l0 += 4) {
-        const int m = std::min(4, n->L - l0);
-        for (int i = 0; i < m; ++i) {
-            Pair& q = n->pr[l0 + i];
-            const float Norm = grad_norm(q.dM, q.dD, q.Nx, q.Ny);
-            qs[i] = mk_dc(q.F, q.S, q.dc, n->B, q.dM, q.dD, q.P, Norm);
-            qs[m + i] = mk_df(q.C, q.S, q.df, n->B, q.dM, q.dD, q.P, Norm);
-        }
-        RET_IF(do_contract_group(ctx, qs, 2 * m, m, 2));
-    }
-    for (int l = 0; l < n->L; ++l) RET_IF(bias_and_kgrad(n, n->pr[l]));
-    return AEFFT_OK;
+    bool qpath = op || (!flag(AEFFT_F_NOQPATH) && n->pr[0].Nk == n->pr[0].Nl && (n->pr[0].Nk == 3 || n->pr[0].Nk == 5));
+    for (const Pair& q : n->pr) qpath = qpath && q.Q != nullptr;
+    return qpath ? wgrads_qpath(n, op) : wgrads_dcdf(n, op);
 }
 
 // post-update MSE of pair q on the current frames (fft_backproplib.cu:1460-1463).  Step mode never reads the
@@ -704,14 +779,9 @@ static int reforward_mse(aefft_net* n, Pair& q, float* mse_slots, bool* g_left_i
     if (!nofuse && q.dD >= 2 && n->B >= 2) {
         RET_IF(do_contract(ctx, mk_G(q.F, q.C, q.G, q.dM, q.dD, q.P)));
         const Contract m = mk_gmse(q.G, q.X, q.F, q.b, q.p, mse_slots, n->B, q.dM, q.dD, q.Nx, q.Ny);
-        hipError_t e;
-        {
-            Bracket br(ctx, KID_CONTRACT, contract_bytes(m));
-            e = launch_contract(m, ctx->cur);
-        }
-        if (e == hipSuccess) { if (g_left_in_S) *g_left_in_S = true; return AEFFT_OK; }
-        if (e != hipErrorInvalidValue) return fail(ctx, AEFFT_EHIP, "contract(mse)", e);
-        (void)hipGetLastError();
+        const int rc = launch_or_decline(ctx, KID_CONTRACT, contract_bytes(m), "contract(mse)", [&] { return launch_contract(m, ctx->cur); });
+        if (rc == AEFFT_OK && g_left_in_S) *g_left_in_S = true;
+        if (rc != DECLINED) return rc;
     }
     RET_IF(join_recon(ctx));                                                  // a deferred reconstruction may still be reading q.O (== Oc when P == Pc)
     RET_IF(do_conv(ctx, q.X, q.C, q.b, q.H, n->B, q.dM, q.dD, q.Nx, q.Ny));   // :1460
@@ -719,277 +789,311 @@ static int reforward_mse(aefft_net* n, Pair& q, float* mse_slots, bool* g_left_i
     return do_diff_mse(ctx, q.X, q.O, nullptr, n->mse_post + (&q - n->pr.data()), nullptr, n->B, q.dM, q.dD, q.Nx, q.Ny);   // :1463
 }
 
-static int apply_grouped(aefft_net* n, float del, int maxdiff, int sym, float gscale, float* mse_d)
+// The routes of one aefft_net_step_apply, decided in front of its first launch.  A declined spectra launch drops fused_upd and gp_route.
+struct ApplyRoute {
+    bool grouped;      // the update and the spectra of every pair in grouped launches
+    bool ride;         // operator form: the spectra launch also writes the bin-major copy Wp
+    bool fused_upd;    // the tap half of the update rides in the tail launch (opmse)
+    bool gp_route;     // the spectra launch writes G' = F'.C'/(dM dD) for every pair but the innermost
+    bool skip_inner;   // the spectra launch leaves out the innermost pair's planar spectra
+};
+
+static ApplyRoute apply_route(const aefft_net* n, int maxdiff, int sym)
+{
+    const aefft_ctx* ctx = n->ctx;
+    ApplyRoute r{};
+    // (with maxdiff: kernel supports the grouped multiobjective launch serves)
+    const int kl = n->pr[0].Nk * n->pr[0].Nl;
+    r.grouped = n->L > 1 && n->L <= 8 && !flag(AEFFT_F_NOGROUP) && shared_supports(n) && (!maxdiff || kl == 9 || kl == 25 || kl == 49);
+    if (!r.grouped) return r;
+    r.ride = op_mode(n) && n->Wp != nullptr;                  // the bin-major copy for the next step's chain: same taps, same launch
+    // Fused update (operator form, plain gradients): no update launch.  The spectra launch reads every tap THROUGH the pending
+    // update (w - clip_step(g, D): TapUpd) and carries the bias half as a trailing workgroup per pair; the taps and their momentum
+    // are stored in place by trailing workgroups of the tail launch (tail_kernel) -- nothing in between reads them.
+    r.fused_upd = r.ride && !sym && !maxdiff && !flag(AEFFT_F_NOFUSEUPD) && !ctx->prof;
+    const Pair& qi = n->pr[n->L - 1];
+    const bool inner_on_record = qi.P == n->pack.Pc && qi.dD <= CH_VMAX && qi.dM <= CH_VMAX;
+    // Operator form with the chain launch: NO planar spectra are written.  The next step's chain reads the bin-major record Wp
+    // and the compact planes Cc_l (C_l where the next pair's grid lands); the post-update MSE reads G'_l = F'_l.C'_l/(dM dD) --
+    // dD*dD planes per pair, the spectrum of the (2Nk-1)^2 kernel f' (*) c' whose taps the transforming workgroups form
+    // themselves (gspec_gbody) -- and the innermost pair from Wp.  Planar C|F are formed when something else asks (ensure_spectra).
+    r.gp_route = r.ride && n->pr[0].Cc != nullptr && 2 * (n->L - 1) <= 8 && chain_switches_ok() && n->compact && inner_on_record;
+    // Without the compact planes: the innermost pair's PLANAR spectra are not written (the chain, the post-update MSE and the
+    // DC-bin gradient terms take that pair from the bin-major record)
+    r.skip_inner = !r.gp_route && r.ride && inner_on_record && !flag(AEFFT_F_NOCHAIN) && !flag(AEFFT_F_NOFUSEUPD) && !ctx->prof;
+    return r;
+}
+
+// multiobjective terms (fft_backproplib.cu:709-753) of every pair in one grouped launch; their outputs and the chunk partial sums
+// live in per-net buffers (allocated the first time maxdiff is asked for)
+static int gdiff_grouped(aefft_net* n, GdiffGroup& gd)
 {
     aefft_ctx* ctx = n->ctx;
-    for (auto& q : n->pr) q.G_valid = false;          // the weights are about to change
-    n->packed_valid = false; n->chain_valid = false;
-    const bool nogroup1 = flag(AEFFT_F_NOGROUP);
-    bool fused_upd = false;                                                // the tap half of the update rides in the tail launch (below)
-    bool gp_route = false;                                                 // the spectra launch wrote G' = F'.C'/(dM dD) for every pair but the innermost
-    UpdateGroup wupd{};
-    bool grouped_w = n->L > 1 && n->L <= 8 && !nogroup1;
-    for (int l = 0; l < n->L && grouped_w; ++l) {
-        const Pair& q = n->pr[l];
-        grouped_w = q.Nk == n->pr[0].Nk && q.Nl == n->pr[0].Nl && pruned_supported(q.Nk, q.Nl, q.Nx, q.Ny);
+    const int kl = n->pr[0].Nk * n->pr[0].Nl;
+    if (!n->gd_out) {
+        size_t no = 0, np_ = 0;
+        for (const Pair& q : n->pr) { no += 2 * (size_t)q.dM * q.dD * kl + q.dM + q.dD; np_ += gradient_diff_ws_floats(q.dM, q.dD, q.Nk, q.Nl); }
+        RET_IF(net_alloc_t(n, &n->gd_out, no));
+        RET_IF(net_alloc_t(n, &n->gd_part, np_));
     }
-    // multiobjective terms (fft_backproplib.cu:709-753) of every pair in one grouped launch; their outputs and the chunk partial sums
-    // live in per-net buffers (allocated the first time maxdiff is asked for)
-    GdiffGroup gd{};
-    if (grouped_w && maxdiff) {
-        const int kl = n->pr[0].Nk * n->pr[0].Nl;
-        grouped_w = kl == 9 || kl == 25 || kl == 49;
-        if (grouped_w && !n->gd_out) {
-            size_t no = 0, np_ = 0;
-            for (const Pair& q : n->pr) { no += 2 * (size_t)q.dM * q.dD * kl + q.dM + q.dD; np_ += gradient_diff_ws_floats(q.dM, q.dD, q.Nk, q.Nl); }
-            RET_IF(net_alloc_t(n, &n->gd_out, no));
-            RET_IF(net_alloc_t(n, &n->gd_part, np_));
-        }
-        if (grouped_w) {
-            float *o = n->gd_out, *pw = n->gd_part;
-            double gbytes = 0;
-            for (int l = 0; l < n->L; ++l) {
-                Pair& q = n->pr[l];
-                const size_t nk = (size_t)q.dM * q.dD * kl;
-                gd.q[l] = GdiffProb{q.c, q.f, q.b, q.p, o, o + nk, o + 2 * nk, o + 2 * nk + q.dM, pw, q.dM, q.dD, 0, 0};
-                o += 2 * nk + q.dM + q.dD; pw += gradient_diff_ws_floats(q.dM, q.dD, q.Nk, q.Nl);
-                gbytes += (double)nk * 16.0;
-            }
-            gd.n = n->L;
-            Bracket br(ctx, KID_GDIFF, gbytes);
-            hipError_t e = launch_gradient_diff_group(gd, n->pr[0].Nk, n->pr[0].Nl, ctx->cur);
-            if (e != hipSuccess) return fail(ctx, AEFFT_EHIP, "gradient_diff(group)", e);
-        }
+    float *o = n->gd_out, *pw = n->gd_part;
+    double gbytes = 0;
+    for (int l = 0; l < n->L; ++l) {
+        Pair& q = n->pr[l];
+        const size_t nk = (size_t)q.dM * q.dD * kl;
+        gd.q[l] = GdiffProb{q.c, q.f, q.b, q.p, o, o + nk, o + 2 * nk, o + 2 * nk + q.dM, pw, q.dM, q.dD, 0, 0};
+        o += 2 * nk + q.dM + q.dD; pw += gradient_diff_ws_floats(q.dM, q.dD, q.Nk, q.Nl);
+        gbytes += (double)nk * 16.0;
     }
-    if (grouped_w) {
-        UpdateGroup ug{};
-        PrunedGroup pg{};
-        double ubytes = 0, kbytes = 0;
+    gd.n = n->L;
+    return launch_or_fail(ctx, KID_GDIFF, gbytes, "gradient_diff(group)", [&] { return launch_gradient_diff_group(gd, n->pr[0].Nk, n->pr[0].Nl, ctx->cur); });
+}
+
+// the grouped update of every pair (gd: with the multiobjective terms); returns its bytes
+static double fill_update(aefft_net* n, const GdiffGroup* gd, float del, int sym, float gscale, UpdateGroup& ug)
+{
+    double bytes = 0;
+    for (int l = 0; l < n->L; ++l) {
+        Pair& q = n->pr[l];
+        const GradSeg gs = q.grads(n->grad);
+        ug.a[l] = mk_update(q.c, q.f, q.b, q.p, gs.dck, gs.dfk, gs.db, gs.dp, Momentum{q.Dc, q.Df, q.Db, q.Dp},
+                            q.dM, q.dD, q.Nk, q.Nl, del, sym, gscale, n->mse_post + l);
+        if (gd) { ug.a[l].cd = gd->q[l].cd; ug.a[l].fd = gd->q[l].fd; ug.a[l].bd = gd->q[l].bd; ug.a[l].pd = gd->q[l].pd; }
+        bytes += (double)q.nk() * 4.0 * 8;
+    }
+    ug.n = n->L;
+    return bytes;
+}
+
+// problems of the grouped spectra launch: C'|F' of every pair (but the innermost with skip_inner), or on the G' route G'_l and
+// the compact planes Cc_l of every pair but the innermost; returns their bytes
+static double fill_spectra(aefft_net* n, const ApplyRoute& rt, const TapUpd* tu, PrunedGroup& pg)
+{
+    double kbytes = 0;
+    if (rt.gp_route) {
+        int k = 0;
+        for (int l = 0; l + 1 < n->L; ++l) {
+            Pair& q = n->pr[l];
+            pg.q[k] = PrunedProb{nullptr, q.G, (long)q.dD * q.dD, q.Nx, q.Ny, 1.0f, 0, 0};
+            pg.gsrc[k] = GtapSrc{q.c, q.f, q.dM, q.dD, 1.0f / ((float)q.dM * (float)q.dD)};
+            pg.upd[k] = tu[l];
+            kbytes += (double)q.dD * q.dD * q.P * 8.0 + 2.0 * q.dM * q.dD * q.Nk * q.Nl * 4.0;
+            ++k;
+        }
+        const int k0 = k;
+        pg.n = cc_problems(n, pg, k0, &kbytes);
+        for (int l = 0; l + 1 < n->L; ++l) pg.upd[k0 + l] = tu[l];
+        return kbytes;
+    }
+    for (int l = 0; l < n->L; ++l) {
+        Pair& q = n->pr[l];
+        pg.q[l] = PrunedProb{q.c, q.C, 2L * q.dM * q.dD, q.Nx, q.Ny, 1.0f};
+        pg.upd[l] = tu[l];
+        kbytes += 2.0 * q.dM * q.dD * (q.P * 8.0 + q.Nk * q.Nl * 4.0);
+    }
+    pg.n = n->L;
+    if (rt.skip_inner) {
+        const Pair& qi = n->pr[n->L - 1];
+        pg.n = n->L - 1;
+        kbytes -= 2.0 * qi.dM * qi.dD * (qi.P * 8.0 + qi.Nk * qi.Nl * 4.0);
+    }
+    return kbytes;
+}
+
+// the grouped update and the spectra launch of the new weights; a declined spectra launch falls back to the separate update
+// and the pair-by-pair transforms
+static int update_and_spectra(aefft_net* n, ApplyRoute& rt, UpdateGroup& ug, double ubytes)
+{
+    aefft_ctx* ctx = n->ctx;
+    BiasUpdGroup bu{};
+    TapUpd tu[8] = {};
+    if (rt.fused_upd) {
+        // the taps of every pair are read through TapUpd by the spectra launch, which also applies the bias half (BiasUpd)
         for (int l = 0; l < n->L; ++l) {
             Pair& q = n->pr[l];
-            float* g = n->grad + q.goff;
-            const size_t nk = (size_t)q.dM * q.dD * q.Nk * q.Nl;
-            ug.a[l] = mk_update(q.c, q.f, q.b, q.p, g, g + nk, g + 2 * nk, g + 2 * nk + q.dM, Momentum{q.Dc, q.Df, q.Db, q.Dp},
-                                q.dM, q.dD, q.Nk, q.Nl, del, sym, gscale, n->mse_post + l);
-            if (maxdiff) { ug.a[l].cd = gd.q[l].cd; ug.a[l].fd = gd.q[l].fd; ug.a[l].bd = gd.q[l].bd; ug.a[l].pd = gd.q[l].pd; }
-            ubytes += (double)nk * 4.0 * 8;
+            const GradSeg gs = q.grads(n->grad);
+            tu[l] = TapUpd{gs.dck, q.Dc, ug.a[l].del, ug.a[l].alpha, ug.a[l].gscale};        // (c|f, dck|dfk, Dc|Df: each pair contiguous)
+            bu.a[l] = BiasUpd{q.b, q.p, q.Db, q.Dp, gs.db, gs.dp, n->mse_post + l, q.dM, q.dD};
         }
-        ug.n = n->L;
-        const bool ride = op_mode(n) && n->Wp != nullptr;                  // the bin-major copy for the next step's chain: same taps, same launch
-        // Fused update (operator form, plain gradients): no update launch.  The spectra launch reads every tap THROUGH the pending
-        // update (w - clip_step(g, D): TapUpd) and carries the bias half as a trailing workgroup per pair; the taps and their momentum
-        // are stored in place by trailing workgroups of the tail launch (tail_kernel) -- nothing in between reads them.
-        fused_upd = ride && !sym && !maxdiff && !flag(AEFFT_F_NOFUSEUPD) && !ctx->prof;
-        // Operator form with the chain launch: NO planar spectra are written.  The next step's chain reads the bin-major record Wp
-        // and the compact planes Cc_l (C_l where the next pair's grid lands); the post-update MSE reads G'_l = F'_l.C'_l/(dM dD) --
-        // dD*dD planes per pair, the spectrum of the (2Nk-1)^2 kernel f' (*) c' whose taps the transforming workgroups form
-        // themselves (gspec_gbody) -- and the innermost pair from Wp.  Planar C|F are formed when something else asks (ensure_spectra).
-        gp_route = ride && n->pr[0].Cc != nullptr && 2 * (n->L - 1) <= 8 && chain_switches_ok() && n->compact &&
-                   n->pr[n->L - 1].P == n->pack.Pc && n->pr[n->L - 1].dD <= CH_VMAX && n->pr[n->L - 1].dM <= CH_VMAX;
-        BiasUpdGroup bu{};
-        TapUpd tu[8] = {};
-        if (fused_upd) {
-            for (int l = 0; l < n->L; ++l) {
-                Pair& q = n->pr[l];
-                float* g = n->grad + q.goff;
-                const size_t nk = (size_t)q.dM * q.dD * q.Nk * q.Nl;
-                tu[l] = TapUpd{g, q.Dc, ug.a[l].del, ug.a[l].alpha, ug.a[l].gscale};        // (c|f, dck|dfk, Dc|Df: each pair contiguous)
-                bu.a[l] = BiasUpd{q.b, q.p, q.Db, q.Dp, g + 2 * nk, g + 2 * nk + q.dM, n->mse_post + l, q.dM, q.dD};
-            }
-            bu.n = n->L; bu.del = ug.a[0].del; bu.alpha = ug.a[0].alpha; bu.gscale = ug.a[0].gscale;
-            n->pack.upd = 1; n->pack.upd_del = ug.a[0].del; n->pack.upd_alpha = ug.a[0].alpha; n->pack.upd_gscale = ug.a[0].gscale;
-            wupd = ug;
-        } else {
-            n->pack.upd = 0;
-            Bracket br(ctx, KID_UPDATE, ubytes);
-            hipError_t e = launch_update_group(ug, ctx->cur);
-            if (e != hipSuccess) return fail(ctx, AEFFT_EHIP, "update(group)", e);
-        }
-        bool skip_inner = false;
-        if (gp_route) {
-            int k = 0;
-            for (int l = 0; l + 1 < n->L; ++l) {
-                Pair& q = n->pr[l];
-                pg.q[k] = PrunedProb{nullptr, q.G, (long)q.dD * q.dD, q.Nx, q.Ny, 1.0f, 0, 0};
-                pg.gsrc[k] = GtapSrc{q.c, q.f, q.dM, q.dD, 1.0f / ((float)q.dM * (float)q.dD)};
-                pg.upd[k] = tu[l];
-                kbytes += (double)q.dD * q.dD * q.P * 8.0 + 2.0 * q.dM * q.dD * q.Nk * q.Nl * 4.0;
-                ++k;
-            }
-            const int k0 = k;
-            k = cc_problems(n, pg, k0, &kbytes);
-            for (int l = 0; l + 1 < n->L; ++l) pg.upd[k0 + l] = tu[l];
-            pg.n = k;
-        } else {
-            for (int l = 0; l < n->L; ++l) {
-                Pair& q = n->pr[l];
-                pg.q[l] = PrunedProb{q.c, q.C, 2L * q.dM * q.dD, q.Nx, q.Ny, 1.0f};
-                pg.upd[l] = tu[l];
-                kbytes += 2.0 * q.dM * q.dD * (q.P * 8.0 + q.Nk * q.Nl * 4.0);
-            }
-            pg.n = n->L;
-            // Without the compact planes: the innermost pair's PLANAR spectra are not written (the chain, the post-update MSE and the
-            // DC-bin gradient terms take that pair from the bin-major record)
-            skip_inner = ride && n->L > 1 && n->pr[n->L - 1].P == n->pack.Pc && n->pr[n->L - 1].dD <= CH_VMAX && n->pr[n->L - 1].dM <= CH_VMAX &&
-                         !flag(AEFFT_F_NOCHAIN) && !flag(AEFFT_F_NOFUSEUPD) && !ctx->prof;
-            if (skip_inner) {
-                const Pair& qi = n->pr[n->L - 1];
-                pg.n = n->L - 1;
-                kbytes -= 2.0 * qi.dM * qi.dD * (qi.P * 8.0 + qi.Nk * qi.Nl * 4.0);
-            }
-        }
-        hipError_t e;
-        {
-            Bracket br(ctx, KID_KSPEC, kbytes + ((op_mode(n) && n->Wp) ? (double)n->pack.Pc * n->pack.E * 8.0 : 0.0));
-            e = launch_kspec_group(pg, ctx->tw, n->pr[0].Nk, n->pr[0].Nl, ctx->cur, ride ? &n->pack : nullptr, fused_upd ? &bu : nullptr);
-            if (e == hipSuccess && ride) n->packed_valid = true;
-            if (e == hipSuccess && skip_inner) n->pr[n->L - 1].spectra_valid = false;
-            if (e == hipSuccess && gp_route) for (auto& q : n->pr) q.spectra_valid = false;
-            if (e == hipSuccess && !gp_route) for (int l = 0; l < pg.n; ++l) n->pr[l].spectra_valid = true;
-        }
+        bu.n = n->L; bu.del = ug.a[0].del; bu.alpha = ug.a[0].alpha; bu.gscale = ug.a[0].gscale;
+        n->pack.upd = 1; n->pack.upd_del = ug.a[0].del; n->pack.upd_alpha = ug.a[0].alpha; n->pack.upd_gscale = ug.a[0].gscale;
+    } else {
         n->pack.upd = 0;
-        if (e != hipSuccess) {
-            if (e != hipErrorInvalidValue) return fail(ctx, AEFFT_EHIP, "kspec(group)", e);
-            (void)hipGetLastError();
-            gp_route = false;
-            if (fused_upd) {                                               // declined before anything ran: the separate update after all
-                fused_upd = false;
-                hipError_t e2 = launch_update_group(ug, ctx->cur);
-                if (e2 != hipSuccess) return fail(ctx, AEFFT_EHIP, "update(group)", e2);
-            }
-            for (int l = 0; l < n->L; ++l) RET_IF(pair_spectra(n, n->pr[l]));
-            for (auto& q : n->pr) q.spectra_valid = true;
-        }
-    } else for (int l = 0; l < n->L; ++l) {
+        RET_IF(launch_or_fail(ctx, KID_UPDATE, ubytes, "update(group)", [&] { return launch_update_group(ug, ctx->cur); }));
+    }
+    PrunedGroup pg{};
+    const double kbytes = fill_spectra(n, rt, tu, pg);
+    const int rc = launch_or_decline(ctx, KID_KSPEC, kbytes + ((op_mode(n) && n->Wp) ? (double)n->pack.Pc * n->pack.E * 8.0 : 0.0), "kspec(group)", [&] {
+        return launch_kspec_group(pg, ctx->tw, n->pr[0].Nk, n->pr[0].Nl, ctx->cur, rt.ride ? &n->pack : nullptr, rt.fused_upd ? &bu : nullptr);
+    });
+    n->pack.upd = 0;
+    if (rc == AEFFT_OK) {
+        if (rt.ride) n->packed_valid = true;
+        if (rt.skip_inner) n->pr[n->L - 1].spectra_valid = false;
+        if (rt.gp_route) for (auto& q : n->pr) q.spectra_valid = false;
+        else for (int l = 0; l < pg.n; ++l) n->pr[l].spectra_valid = true;
+        return AEFFT_OK;
+    }
+    if (rc != DECLINED) return rc;
+    rt.gp_route = false;
+    if (rt.fused_upd) {                                               // declined before anything ran: the separate update after all
+        rt.fused_upd = false;
+        hipError_t e = launch_update_group(ug, ctx->cur);
+        if (e != hipSuccess) return fail(ctx, AEFFT_EHIP, "update(group)", e);
+    }
+    for (int l = 0; l < n->L; ++l) RET_IF(pair_spectra(n, n->pr[l]));
+    for (auto& q : n->pr) q.spectra_valid = true;
+    return AEFFT_OK;
+}
+
+static int update_per_pair(aefft_net* n, float del, int maxdiff, int sym, float gscale)
+{
+    for (int l = 0; l < n->L; ++l) {
         Pair& q = n->pr[l];
-        float* g = n->grad + q.goff;
-        const size_t nk = (size_t)q.dM * q.dD * q.Nk * q.Nl;
-        RET_IF(do_update(ctx, q.c, q.f, q.b, q.p, g, g + nk, g + 2 * nk, g + 2 * nk + q.dM, Momentum{q.Dc, q.Df, q.Db, q.Dp},
+        const GradSeg gs = q.grads(n->grad);
+        RET_IF(do_update(n->ctx, q.c, q.f, q.b, q.p, gs.dck, gs.dfk, gs.db, gs.dp, Momentum{q.Dc, q.Df, q.Db, q.Dp},
                          q.dM, q.dD, q.Nk, q.Nl, del, maxdiff, sym, gscale, n->mse_post + l));
         RET_IF(pair_spectra(n, q));
         q.spectra_valid = true;
     }
-    if (op_mode(n) && n->Wp) RET_IF(ensure_packed(n));     // the next step's chain reads the bin-major copy of the NEW weights
-    bool g_taps = false;                                   // G' of EVERY pair at hand (operator form without the chain launch, HBM-sized spectra)
-    if (op_mode(n) && !gp_route) {
-        // HBM-sized kernel spectra (no pooling): the post-update MSE would read all 2*dM*dD planes of C'|F' back (6 GB at cfg3-P1).  G' =
-        // F'.C'/(dM dD) as the spectrum of the (2Nk-1)^2-tap kernel f' (*) c' (weight_kernels.hip) is dD*dD planes written and read once.
-        double cf_bytes = 0;
-        for (int l = 0; l < n->L; ++l) cf_bytes += 2.0 * n->pr[l].dM * n->pr[l].dD * n->pr[l].P * 8.0;
-        const bool want = (cf_bytes > 256e6 || flag(AEFFT_F_GTAPS)) && !fused_upd /* the taps are stored */ && !flag(AEFFT_F_NOQPATH);
-        if (want) RET_IF(gprime_from_taps(n, &g_taps));
+    return AEFFT_OK;
+}
+
+// the operator-form MSE problem of every pair: from G'_l where the spectra launch (gp_route) or gprime_from_taps (g_taps) left it,
+// else from the updated spectra; the innermost pair from the bin-major copy when that is current
+static int fill_opmse(aefft_net* n, bool gp_route, bool g_taps, OpMseGroup& og, double* bytes)
+{
+    const bool inner_packed = n->Wp && n->packed_valid && n->pr[n->L - 1].P == n->pack.Pc;
+    for (int l = 0; l < n->L; ++l) {
+        Pair& q = n->pr[l];
+        const float scale = 1.0f / ((float)(2 * q.dM) * (float)q.Nx * (float)q.Ny * (float)n->B) / ((float)q.dD * q.Nx * q.Ny);   // as mk_gmse
+        OpMsePair o{};
+        o.A = op_view(n, l).A; o.C = q.C; o.F = q.F; o.b = q.b; o.p = q.p;
+        o.slots = mse_slot(n, l);
+        o.dD = q.dD; o.dM = q.dM; o.Nx = q.Nx; o.Ny = q.Ny; o.P = q.P; o.scale = scale;
+        if (gp_route && l + 1 < n->L) {
+            o.G = q.G; o.Fdc = n->Wp + n->pack.seg[2 * n->L - 1 - l].off; o.fdc_stride = 1;      // (F' at the DC bin: record 0 of the bin-major copy)
+            *bytes += ((double)q.dD * q.dD + (double)OPC * q.dD + (double)OPC * OPC) * q.P * 8.0;
+        } else if (g_taps && !(l == n->L - 1 && inner_packed)) {
+            RET_IF(ensure_spectra(n, q));
+            o.G = q.G; o.Fdc = q.F; o.fdc_stride = q.P;                                            // (the planar F', DC bin)
+            *bytes += ((double)q.dD * q.dD + (double)OPC * q.dD + (double)OPC * OPC) * q.P * 8.0;
+        } else {
+            if (!(l == n->L - 1 && inner_packed)) RET_IF(ensure_spectra(n, q));
+            *bytes += (2.0 * q.dM * q.dD + (double)OPC * q.dD + (double)OPC * OPC) * q.P * 8.0;
+        }
+        og.q[l] = o;
     }
-    if (op_mode(n)) {
-        // post-update MSE (fft_backproplib.cu:1460-1463) in operator form: R = A - F'(C' A / dM + b^) / dD - p^ per bin, then
-        // sum_a R[a] M^ R[a]^H; the updated spectra (or their product G') are read once, nothing is stored (opform_kernels.hip)
-        OpMseGroup og{};
-        double bytes = 0;
-        const bool inner_packed = n->Wp && n->packed_valid && n->pr[n->L - 1].P == n->pack.Pc;
-        for (int l = 0; l < n->L; ++l) {
-            Pair& q = n->pr[l];
-            const float scale = 1.0f / ((float)(2 * q.dM) * (float)q.Nx * (float)q.Ny * (float)n->B) / ((float)q.dD * q.Nx * q.Ny);   // as mk_gmse
-            OpMsePair o{};
-            o.A = op_view(n, l).A; o.C = q.C; o.F = q.F; o.b = q.b; o.p = q.p;
-            o.slots = n->mse_slots + (size_t)l * MSE_SLOTS * MSE_SLOT_STRIDE;
-            o.dD = q.dD; o.dM = q.dM; o.Nx = q.Nx; o.Ny = q.Ny; o.P = q.P; o.scale = scale;
-            if (gp_route && l + 1 < n->L) {
-                o.G = q.G; o.Fdc = n->Wp + n->pack.seg[2 * n->L - 1 - l].off; o.fdc_stride = 1;      // (F' at the DC bin: record 0 of the bin-major copy)
-                bytes += ((double)q.dD * q.dD + (double)OPC * q.dD + (double)OPC * OPC) * q.P * 8.0;
-            } else if (g_taps && !(l == n->L - 1 && inner_packed)) {
-                RET_IF(ensure_spectra(n, q));
-                o.G = q.G; o.Fdc = q.F; o.fdc_stride = q.P;                                            // (the planar F', DC bin)
-                bytes += ((double)q.dD * q.dD + (double)OPC * q.dD + (double)OPC * OPC) * q.P * 8.0;
-            } else {
-                if (!(l == n->L - 1 && inner_packed)) RET_IF(ensure_spectra(n, q));
-                bytes += (2.0 * q.dM * q.dD + (double)OPC * q.dD + (double)OPC * OPC) * q.P * 8.0;
-            }
-            og.q[l] = o;
-        }
-        og.n = n->L; og.Mhat = n->Mhat; og.Nx0 = n->pr[0].Nx; og.Ny0 = n->pr[0].Ny; og.P0 = n->pr[0].P;
-        if (inner_packed) {      // the innermost pair reads the bin-major copy the kspec launch just refreshed
-            og.Wp = n->Wp; og.E = n->pack.E;
-            og.offC = n->pack.seg[n->L - 1].off; og.offF = n->pack.seg[n->L].off;
-        }
-        // The NEXT step's operator chain depends on the updated weights only (the record Wp and the planes Cc the spectra launch has just
-        // written): it shares this launch, writing the other set of operator buffers, and the next aefft_net_step_grad starts from it.
-        const bool ahead = n->op_chain && n->Wp && n->packed_valid && chain_switches_ok() && (n->compact || n->L == 1) && !flag(AEFFT_F_NOAHEAD);
-        ChainArgs ca{};
-        if (ahead) fill_chain(n, ca, n->op_set ^ 1, &bytes);
-        {
-            Bracket br(ctx, KID_OPMSE, bytes);
-            hipError_t e = launch_opmse_group(og, ctx->cur, ahead ? &ca : nullptr, fused_upd ? &wupd : nullptr);
-            if (e != hipSuccess) return fail(ctx, AEFFT_EHIP, "opmse", e);
-        }
-        if (ahead) { n->op_set ^= 1; n->chain_valid = true; }
-        if (!mse_d && !ctx->prof && !flag(AEFFT_F_NOLAZYMSE)) {
-            // nobody asked for the sums now: they are formed by one more workgroup of the next step's gradient launch (before its
-            // all-reduce), by aefft_net_last_mse, or by whatever needs the slots next -- not by a launch of their own
-            n->mse_pending = true; n->mse_pending_scale = gscale;
-            return AEFFT_OK;
-        }
-        Bracket br(ctx, KID_DIFFMSE, 4.0 * n->L * MSE_SLOTS);
-        hipError_t e = launch_mse_finish(n->mse_slots, n->mse_post, mse_d, n->L, ctx->cur, nullptr, n->grad + n->grad_n, gscale);
-        if (e != hipSuccess) return fail(ctx, AEFFT_EHIP, "mse_finish", e);
-        return AEFFT_OK;
-    }
-    if (fused_upd) return fail(ctx, AEFFT_ESTATE, "apply: fused update without the operator-form tail");      // (cannot happen: fused_upd implies op_state)
-    // post-update MSE (fft_backproplib.cu:1460-1463): G = F.C of every eligible pair in one launch, then every pair's pass
-    // over X with the MSE epilogue in one launch; pairs the fused form does not serve (dD == 1, B == 1) go pair by pair
-    std::vector<char> g_in_S(n->L, 0);       // pair l: S holds G of the updated weights after this call
-    {
-        const bool nofuse = flag(AEFFT_F_NOFUSEMSE), nogroup = flag(AEFFT_F_NOGROUP);
-        Contract gq[8], mq[8];
-        int m = 0;
-        std::vector<int> rest;
-        for (int l = 0; l < n->L; ++l) {
-            Pair& q = n->pr[l];
-            if (!nofuse && !nogroup && q.dD >= 2 && n->B >= 2 && m < 8) {
-                gq[m] = mk_G(q.F, q.C, q.G, q.dM, q.dD, q.P);
-                mq[m] = mk_gmse(q.G, q.X, q.F, q.b, q.p, n->mse_slots + (size_t)l * MSE_SLOTS * MSE_SLOT_STRIDE, n->B, q.dM, q.dD, q.Nx, q.Ny);
-                ++m;
-            } else rest.push_back(l);
-        }
-        bool grouped = false;
-        if (m > 1) {
-            // G = F.C/(dM dD).  HBM-sized kernel spectra (no pooling): as the spectrum of the (2Nk-1)^2-tap kernel f (*) c
-            // (weight_kernels.hip), which reads the kernels and writes dD*dD planes instead of reading all 2*dM*dD planes of C|F;
-            // cache-sized ones: as a per-bin contraction of the spectra (measured faster there).
-            const bool noq = flag(AEFFT_F_NOQPATH);
-            double cf_bytes = 0;
-            for (int l = 0; l < n->L; ++l) cf_bytes += 2.0 * n->pr[l].dM * n->pr[l].dD * n->pr[l].P * 8.0;
-            bool gtaps = false;
-            if (!noq && (cf_bytes > 256e6 || flag(AEFFT_F_GTAPS)) && m == n->L) RET_IF(gprime_from_taps(n, &gtaps));
-            if (!gtaps) RET_IF(do_contract_group(ctx, gq, m, m, 0));
-            ContractN g{};
-            double bytes = 0;
-            for (int i = 0; i < m; ++i) { g.q[i] = mq[i]; bytes += contract_bytes(mq[i]); }
-            g.n = m;
-            hipError_t e;
-            {
-                Bracket br(ctx, KID_CONTRACT, bytes);
-                e = launch_contract_mfma(g, ctx->cur);
-            }
-            if (e == hipSuccess) grouped = true;
-            else if (e != hipErrorInvalidValue) return fail(ctx, AEFFT_EHIP, "contract(mse group)", e);
-            else (void)hipGetLastError();
-        }
-        for (int l = 0; l < n->L; ++l) {
-            const bool in_group = grouped && std::find(rest.begin(), rest.end(), l) == rest.end();
-            bool left = in_group;
-            if (!in_group) RET_IF(reforward_mse(n, n->pr[l], n->mse_slots + (size_t)l * MSE_SLOTS * MSE_SLOT_STRIDE, &left));
-            g_in_S[l] = left;
-        }
-    }
-    {
-        Bracket br(ctx, KID_DIFFMSE, 4.0 * n->L * MSE_SLOTS);
-        Pair& ql = n->pr[n->L - 1];
-        BetaArgs ba{ql.beta, ql.F, ql.b, ql.p, ql.dM, ql.dD, ql.P};
-        const bool want_beta = g_in_S[n->L - 1] && ql.beta && ql.dD <= 256;
-        hipError_t e = launch_mse_finish(n->mse_slots, n->mse_post, mse_d, n->L, ctx->cur, want_beta ? &ba : nullptr, n->grad + n->grad_n, gscale);     // also the copy-out to mse_d and to the packed buffer's tail
-        ql.G_valid = want_beta && e == hipSuccess;
-        if (e != hipSuccess) return fail(ctx, AEFFT_EHIP, "mse_finish", e);
+    og.n = n->L; og.Mhat = n->Mhat; og.Nx0 = n->pr[0].Nx; og.Ny0 = n->pr[0].Ny; og.P0 = n->pr[0].P;
+    if (inner_packed) {      // the innermost pair reads the bin-major copy the kspec launch just refreshed
+        og.Wp = n->Wp; og.E = n->pack.E;
+        og.offC = n->pack.seg[n->L - 1].off; og.offF = n->pack.seg[n->L].off;
     }
     return AEFFT_OK;
+}
+
+// post-update MSE (fft_backproplib.cu:1460-1463) in operator form: R = A - F'(C' A / dM + b^) / dD - p^ per bin, then
+// sum_a R[a] M^ R[a]^H; the updated spectra (or their product G') are read once, nothing is stored (opform_kernels.hip).
+// wupd: the fused update's tap half, stored by this launch.
+static int opform_mse(aefft_net* n, const ApplyRoute& rt, const UpdateGroup* wupd, float gscale, float* mse_d)
+{
+    aefft_ctx* ctx = n->ctx;
+    bool g_taps = false;                                   // G' of EVERY pair at hand (operator form without the chain launch, HBM-sized spectra)
+    if (!rt.gp_route && !rt.fused_upd /* the taps are stored */ && gprime_taps_pay(n)) RET_IF(gprime_from_taps(n, &g_taps));
+    OpMseGroup og{};
+    double bytes = 0;
+    RET_IF(fill_opmse(n, rt.gp_route, g_taps, og, &bytes));
+    // The NEXT step's operator chain depends on the updated weights only (the record Wp and the planes Cc the spectra launch has just
+    // written): it shares this launch, writing the other set of operator buffers, and the next aefft_net_step_grad starts from it.
+    const bool ahead = n->op_chain && n->Wp && n->packed_valid && chain_switches_ok() && (n->compact || n->L == 1) && !flag(AEFFT_F_NOAHEAD);
+    ChainArgs ca{};
+    if (ahead) fill_chain(n, ca, n->op_set ^ 1, &bytes);
+    RET_IF(launch_or_fail(ctx, KID_OPMSE, bytes, "opmse", [&] { return launch_opmse_group(og, ctx->cur, ahead ? &ca : nullptr, wupd); }));
+    if (ahead) { n->op_set ^= 1; n->chain_valid = true; }
+    if (!mse_d && !ctx->prof && !flag(AEFFT_F_NOLAZYMSE)) {
+        // nobody asked for the sums now: they are formed by one more workgroup of the next step's gradient launch (before its
+        // all-reduce), by aefft_net_last_mse, or by whatever needs the slots next -- not by a launch of their own
+        n->mse_pending = true; n->mse_pending_scale = gscale;
+        return AEFFT_OK;
+    }
+    return launch_or_fail(ctx, KID_DIFFMSE, 4.0 * n->L * MSE_SLOTS, "mse_finish",
+                          [&] { return launch_mse_finish(n->mse_slots, n->mse_post, mse_d, n->L, ctx->cur, nullptr, n->grad + n->grad_n, gscale); });
+}
+
+// the re-forward MSE of every pair into its slots: G = F.C of the first 8 pairs the fused form serves in one launch (or from the
+// taps), their passes over X in one launch, the other pairs (all of them if that launch declines) through reforward_mse.
+// *inner_g: the innermost pair's G belongs to the updated weights.
+static int reforward_mse_all(aefft_net* n, bool* inner_g)
+{
+    aefft_ctx* ctx = n->ctx;
+    const bool nofuse = flag(AEFFT_F_NOFUSEMSE), nogroup = flag(AEFFT_F_NOGROUP);
+    auto fusable = [&](const Pair& q) { return !nofuse && !nogroup && q.dD >= 2 && n->B >= 2; };
+    Contract gq[8], mq[8];
+    int m = 0;
+    for (int l = 0; l < n->L && m < 8; ++l) {
+        Pair& q = n->pr[l];
+        if (!fusable(q)) continue;
+        gq[m] = mk_G(q.F, q.C, q.G, q.dM, q.dD, q.P);
+        mq[m] = mk_gmse(q.G, q.X, q.F, q.b, q.p, mse_slot(n, l), n->B, q.dM, q.dD, q.Nx, q.Ny);
+        ++m;
+    }
+    bool grouped = false;
+    if (m > 1) {
+        bool gtaps = false;
+        if (m == n->L && gprime_taps_pay(n)) RET_IF(gprime_from_taps(n, &gtaps));
+        if (!gtaps) RET_IF(do_contract_group(ctx, gq, m, m, 0));
+        ContractN g{};
+        double bytes = 0;
+        for (int i = 0; i < m; ++i) { g.q[i] = mq[i]; bytes += contract_bytes(mq[i]); }
+        g.n = m;
+        const int rc = launch_or_decline(ctx, KID_CONTRACT, bytes, "contract(mse group)", [&] { return launch_contract_mfma(g, ctx->cur); });
+        if (rc != AEFFT_OK && rc != DECLINED) return rc;
+        grouped = rc == AEFFT_OK;
+    }
+    int k = 0;                                 // fusable pairs so far: the first 8 are in the group
+    for (int l = 0; l < n->L; ++l) {
+        Pair& q = n->pr[l];
+        const bool in_group = grouped && fusable(q) && k++ < 8;
+        bool left = in_group;
+        if (!in_group) RET_IF(reforward_mse(n, q, mse_slot(n, l), &left));
+        if (l == n->L - 1) *inner_g = left;
+    }
+    return AEFFT_OK;
+}
+
+// post-update MSE (fft_backproplib.cu:1460-1463): G = F.C of every eligible pair in one launch, then every pair's pass
+// over X with the MSE epilogue in one launch; pairs the fused form does not serve (dD == 1, B == 1) go pair by pair
+static int frame_mse(aefft_net* n, float gscale, float* mse_d)
+{
+    aefft_ctx* ctx = n->ctx;
+    bool inner_g = false;
+    RET_IF(reforward_mse_all(n, &inner_g));
+    Bracket br(ctx, KID_DIFFMSE, 4.0 * n->L * MSE_SLOTS);
+    Pair& ql = n->pr[n->L - 1];
+    BetaArgs ba{ql.beta, ql.F, ql.b, ql.p, ql.dM, ql.dD, ql.P};
+    const bool want_beta = inner_g && ql.beta && ql.dD <= 256;
+    hipError_t e = launch_mse_finish(n->mse_slots, n->mse_post, mse_d, n->L, ctx->cur, want_beta ? &ba : nullptr, n->grad + n->grad_n, gscale);     // also the copy-out to mse_d and to the packed buffer's tail
+    ql.G_valid = want_beta && e == hipSuccess;
+    if (e != hipSuccess) return fail(ctx, AEFFT_EHIP, "mse_finish", e);
+    return AEFFT_OK;
+}
+
+static int apply_grouped(aefft_net* n, float del, int maxdiff, int sym, float gscale, float* mse_d)
+{
+    for (auto& q : n->pr) q.G_valid = false;          // the weights are about to change
+    n->packed_valid = false; n->chain_valid = false;
+    ApplyRoute rt = apply_route(n, maxdiff, sym);
+    UpdateGroup ug{};
+    if (rt.grouped) {
+        GdiffGroup gd{};
+        if (maxdiff) RET_IF(gdiff_grouped(n, gd));
+        const double ubytes = fill_update(n, maxdiff ? &gd : nullptr, del, sym, gscale, ug);
+        RET_IF(update_and_spectra(n, rt, ug, ubytes));
+    } else RET_IF(update_per_pair(n, del, maxdiff, sym, gscale));
+    if (op_mode(n) && n->Wp) RET_IF(ensure_packed(n));     // the next step's chain reads the bin-major copy of the NEW weights
+    if (op_mode(n)) return opform_mse(n, rt, rt.fused_upd ? &ug : nullptr, gscale, mse_d);
+    if (rt.fused_upd) return fail(n->ctx, AEFFT_ESTATE, "apply: fused update without the operator-form tail");      // (cannot happen: fused_upd implies op_state)
+    return frame_mse(n, gscale, mse_d);
 }
 
 // input prefetch bookkeeping: everything of step k that reads this step's input-spectra buffer has been enqueued
@@ -1016,12 +1120,11 @@ extern "C" int aefft_net_set_input_ready(aefft_net* n, int enable)
     return AEFFT_OK;
 }
 
-extern "C" int aefft_net_step_grad(aefft_net* n, const float* frames_d, float* recon_d)
+static int step_grad(aefft_net* n, const float* frames_d, bool u8, float* recon_d)
 {
-    if (!n) return AEFFT_EINVAL;
     aefft_ctx* ctx = n->ctx;
     ++n->step_no;
-    RET_IF(net_forward(n, frames_d, recon_d, true, op_eligible(n)));
+    RET_IF(net_forward(n, frames_d, u8, recon_d, true, op_eligible(n)));
     {
         int rcg = grads_grouped(n);
         if (rcg == AEFFT_OK) rcg = mse_flush(n);      // (a gradient route without the wgrad launch: the deferred MSE sums as their own launch after all)
@@ -1035,10 +1138,10 @@ extern "C" int aefft_net_step_grad(aefft_net* n, const float* frames_d, float* r
         n->recon_deferred = nullptr;
         HIPCHK(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
         HIPCHK(ctx, hipStreamWaitEvent(ctx->aux[0], ctx->ev_fork, 0));
-        ctx->cur = ctx->aux[0];
-        const int rc = launch_recon(n, recon, WS_MID3);
-        ctx->cur = ctx->stream;
-        RET_IF(rc);
+        {
+            OnStream on(ctx, ctx->aux[0]);
+            RET_IF(launch_recon(n, recon, WS_MID3));
+        }
         HIPCHK(ctx, hipEventRecord(ctx->ev_join[0], ctx->aux[0]));
         ctx->recon_join = true;
     }
@@ -1054,22 +1157,12 @@ extern "C" int aefft_net_step_grad(aefft_net* n, const float* frames_d, float* r
     return mark_step_point(n);
 }
 
-// 8-bit frames: the same calls with the input transform converting on load (fft_kernels.hip r2c_rows_kernel<N, true>); nothing else reads the frames
+extern "C" int aefft_net_step_grad(aefft_net* n, const float* frames_d, float* recon_d) { return n ? step_grad(n, frames_d, false, recon_d) : AEFFT_EINVAL; }
+
+// 8-bit frames: the input transform converts on load (fft_kernels.hip r2c_rows_kernel<N, true>); nothing else reads the frames
 extern "C" int aefft_net_step_grad_u8(aefft_net* n, const unsigned char* frames_d, float* recon_d)
 {
-    if (!n) return AEFFT_EINVAL;
-    n->ctx->in_u8 = true;
-    const int rc = aefft_net_step_grad(n, reinterpret_cast<const float*>(frames_d), recon_d);
-    n->ctx->in_u8 = false;
-    return rc;
-}
-extern "C" int aefft_net_forward_u8(aefft_net* n, const unsigned char* frames_d, float* recon_d)
-{
-    if (!n) return AEFFT_EINVAL;
-    n->ctx->in_u8 = true;
-    const int rc = aefft_net_forward(n, reinterpret_cast<const float*>(frames_d), recon_d);
-    n->ctx->in_u8 = false;
-    return rc;
+    return n ? step_grad(n, reinterpret_cast<const float*>(frames_d), true, recon_d) : AEFFT_EINVAL;
 }
 
 extern "C" int aefft_net_step_form(aefft_net* n)

@@ -272,21 +272,15 @@ int aefft::do_contract_group(aefft_ctx* ctx, const Contract* qs, int n, int nA, 
         double bytes = 0;
         for (int i = 0; i < n; ++i) { g.q[i] = bc(ctx, qs[i]); bytes += contract_bytes(qs[i]); }
         g.n = n; g.nA = nA;
-        hipError_t e;
-        {
-            Bracket br(ctx, KID_CONTRACT, bytes);
-            e = launch_contract_group(g, cls, ctx->cur);
-        }
-        if (e == hipSuccess) return AEFFT_OK;
-        if (e != hipErrorInvalidValue) return fail(ctx, AEFFT_EHIP, "contract(group)", e);
-        (void)hipGetLastError();
+        const int rc = launch_or_decline(ctx, KID_CONTRACT, bytes, "contract(group)", [&] { return launch_contract_group(g, cls, ctx->cur); });
+        if (rc != DECLINED) return rc;
     }
     for (int i = 0; i < n; ++i) RET_IF(do_contract(ctx, qs[i]));
     return AEFFT_OK;
 }
 
 // pool_fft(conv_k(X)) without the full-resolution conv output (fft_backproplib.cu:1346-1348 when only the pooled
-// layer is consumed): Xs[b][r] on the [Nxs][Nys/2+1] grid.  Returns AEFFT_EUNSUPPORTED-like -1 when the kernel declines.
+// layer is consumed): Xs[b][r] on the [Nxs][Nys/2+1] grid.  *done = false: the kernel declined the shapes.
 int aefft::do_conv_pooled(aefft_ctx* ctx, const float2* X, const float2* W, const float* bias, float2* Xs, int B, int R, int K,
                           int Nx, int Ny, int Nxs, int Nys, bool* done)
 {
@@ -301,15 +295,10 @@ int aefft::do_conv_pooled(aefft_ctx* ctx, const float2* X, const float2* W, cons
     q.bias = bias; q.biasScale = (float)Nx * (float)Ny; q.biasAfterFirst = true;
     q.gdNx = Nx; q.gdNy = Ny; q.gdNxs = Nxs; q.gdNys = Nys; q.gdMask = 3;
     q = bc(ctx, q);
-    hipError_t e;
-    {
-        Bracket br(ctx, KID_CONTRACT, ((double)R * K + (double)K * B + (double)R * B) * Ps * 8.0);
-        e = launch_contract(q, ctx->cur);
-    }
-    if (e == hipSuccess) { *done = true; return AEFFT_OK; }
-    if (e != hipErrorInvalidValue) return fail(ctx, AEFFT_EHIP, "contract(pooled)", e);
-    (void)hipGetLastError();
-    return AEFFT_OK;
+    const int rc = launch_or_decline(ctx, KID_CONTRACT, ((double)R * K + (double)K * B + (double)R * B) * Ps * 8.0, "contract(pooled)",
+                                     [&] { return launch_contract(q, ctx->cur); });
+    *done = rc == AEFFT_OK;
+    return rc == DECLINED ? AEFFT_OK : rc;
 }
 
 // conv_k over a batch: O[b][r] = sum_k (X[b][k]/R) * W[r][k] (+ bias[r]*Nx*Ny at DC)
