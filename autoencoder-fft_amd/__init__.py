@@ -26,6 +26,7 @@ FLAGS = {n: 1 << i for i, n in enumerate(
      "NOPREFETCH", "NODEFER", "NOTILEDSPATIAL", "NOFAST", "NOSPLITK", "POISON", "NOOPFORM", "NOCHAIN", "NOFUSEUPD", "NOAHEAD", "NORCORR", "NOLAZYMSE", "SMALLOVERLAP", "CHAINMSE",
      "CHIRPZ"])}
 NET_SMOOTH_SIZES = 1 << 0   # include/aefft.h AEFFT_NET_SMOOTH_SIZES (aefft_net_create_ex)
+NET_SPATIAL = 1 << 1        # include/aefft.h AEFFT_NET_SPATIAL: the coordinate-space training mode as a resident net
 
 
 class AefftError(RuntimeError):
@@ -93,6 +94,7 @@ SIGNATURES = {
     "aefft_net_last_mse": (_i, [_vp, _vp]),
     "aefft_net_step_apply": (_i, [_vp, _f, _i, _i, _f, _fp]),
     "aefft_net_reset_momentum": (_i, [_vp]),
+    "aefft_net_set_inertia": (_i, [_vp, _f]),
     "aefft_prof_enable": (_i, [_vp, _i]),
     "aefft_prof_count": (_i, []),
     "aefft_prof_name": (C.c_char_p, [_i]),
@@ -410,9 +412,11 @@ class Context:
 class Net:
     """aefft_net: resident batched autoencoder (autoenc_fft / backprop_fft semantics)."""
 
-    def __init__(self, ctx, D, Nx, Ny, maps, Nk, scale, batch, Nl=None, smooth_sizes=False):
+    def __init__(self, ctx, D, Nx, Ny, maps, Nk, scale, batch, Nl=None, smooth_sizes=False, spatial=False):
         """smooth_sizes: also take Nx, Ny with prime factors 3 and 5 (640 x 480, ...; aefft_net_create_ex with
-        AEFFT_NET_SMOOTH_SIZES) -- such a net trains in the per-frame form."""
+        AEFFT_NET_SMOOTH_SIZES) -- such a net trains in the per-frame form.
+        spatial: the coordinate-space mode (Pool / Conv_gpu / backprop_gpu; aefft_net_create_ex with AEFFT_NET_SPATIAL): any frame size,
+        every scale dividing its input grid exactly; step_apply's del0 is backprop_gpu's delmax and the MSE tail is this step's."""
         self.ctx, self.L = ctx, ctx.L
         self.D, self.Nx, self.Ny, self.B = D, Nx, Ny, batch
         self.maps = list(maps); self.npairs = len(self.maps)
@@ -423,8 +427,9 @@ class Net:
         self._keep = [arr(self.maps), arr(self.Nk), arr(self.Nl), arr(self.scale)]
         d = NetDesc(D, Nx, Ny, self.npairs, *self._keep, batch)
         h = C.c_void_p()
-        if smooth_sizes:
-            ctx.check(self.L.aefft_net_create_ex(ctx.h, C.byref(d), NET_SMOOTH_SIZES, C.byref(h)))
+        if smooth_sizes or spatial:
+            opts = (NET_SMOOTH_SIZES if smooth_sizes else 0) | (NET_SPATIAL if spatial else 0)
+            ctx.check(self.L.aefft_net_create_ex(ctx.h, C.byref(d), opts, C.byref(h)))
         else:
             ctx.check(self.L.aefft_net_create(ctx.h, C.byref(d), C.byref(h)))
         self.h = h
@@ -539,8 +544,9 @@ class Net:
         return self._prevview[1]
 
     def step_form(self):
-        """which form the next training step runs in: "per_frame", "operator" or "operator_chain" (aefft_net_step_form)"""
-        return ("per_frame", "operator", "operator_chain")[self.L.aefft_net_step_form(self.h)]
+        """which form the next training step runs in: "per_frame", "operator", "operator_chain" or, on a spatial net, "spatial"
+        (aefft_net_step_form)"""
+        return ("per_frame", "operator", "operator_chain", "spatial")[self.L.aefft_net_step_form(self.h)]
 
     def step_apply(self, del0, maxdiff=0, sym=0, grad_scale=1.0, mse=None):
         self.ctx.check(self.L.aefft_net_step_apply(self.h, del0, maxdiff, sym, grad_scale, _ptr(mse)))
@@ -554,3 +560,7 @@ class Net:
 
     def reset_momentum(self):
         self.ctx.check(self.L.aefft_net_reset_momentum(self.h))
+
+    def set_inertia(self, alpha):
+        """inertia weight of backprop_gpu's update on a spatial net (default 0.9; aefft_net_set_inertia)"""
+        self.ctx.check(self.L.aefft_net_set_inertia(self.h, alpha))

@@ -268,7 +268,9 @@ hipError_t launch_gradient_diff_group(GdiffGroup& g, int Nk, int Nl, hipStream_t
 // ---- spatial_kernels.hip ---------------------------------------------------------------
 hipError_t launch_conv_spatial(const float* in, float* out, const float* c, const float* b, int B, int dD, int dM,
                                int Nx, int Ny, int Nk, int Nl, int ak, int al, float in_scale_div, int lo, hipStream_t st,
-                               int pool = 0 /* fused Pool(scale) in front: `in` is [B][dD][Nx*pool][Ny*pool] */, float* pooled_out = nullptr);
+                               int pool = 0 /* fused Pool(scale) in front: `in` is [B][dD][Nx*pool][Ny*pool] */, float* pooled_out = nullptr,
+                               int up = 0 /* fused Pool(-up) in front: `in` is [B][dD][Nx/up][Ny/up] */,
+                               float* out_up = nullptr, int out_up_s = 0 /* also the output up-sampled by out_up_s: [B][dM][Nx*s][Ny*s] */);
 struct SpatialGradArgs {
     const float *in, *out, *hin, *f;      // [dD][Nx][Ny], [dD][Nx][Ny], [dM][Nx][Ny], [dD][dM][Nk][Nl]
     float *gc, *gf, *gb, *gp;             // [dM][dD][Nk][Nl], [dD][dM][Nk][Nl], [dM], [dD]
@@ -283,6 +285,8 @@ struct SpatialGradArgs {
     // (dF[d][m][t] = sum_{d2,t2} c1[m][d2][t2]/div1 R_t[d][d2][t+t2] + b1[m] S_t[d]) and the hidden layer is not read by the gradient
     const float *c1 = nullptr, *b1 = nullptr;
     float div1 = 1.f;
+    // nullable: on the region route (spatial_regions_ok) also sum (out - in)^2 / Norm / B into *mse, from the error tile the route stages anyway
+    float* mse = nullptr;
 };
 hipError_t launch_spatial_grad(const SpatialGradArgs& a, hipStream_t st);
 bool spatial_regions_ok(const SpatialGradArgs& a);   // the gradient goes through the error-input region sums (what the fused step needs)
@@ -290,5 +294,13 @@ hipError_t launch_spatial_compat(const SpatialGradArgs& a, hipStream_t st);   //
 size_t spatial_partial_floats(int B, int dD, int dM, int Nx, int Ny, int Nk, int Nl);
 size_t spatial_rq_floats(int dD, int Nk, int Nl);
 hipError_t launch_pool_spatial(const float* in, float* out, long planes, int Nxi, int Nyi, int Nxo, int Nyo, int scale, hipStream_t st);   // netlib.cpp:114   // 0: shape not served by the tiled kernels
+// the spatial net's per-pair MSE: dst[k] = scale[k] * sum (a[k] - b[k])^2 over n[k] floats, for up to SQD_MAX pairs in two launches (fixed-order
+// partial sums: the same inputs give the same bits); part: SQD_MAX * SQD_BLOCKS floats
+constexpr int SQD_MAX = 8, SQD_BLOCKS = 128;
+struct SqdiffGroup { const float* a[SQD_MAX]; const float* b[SQD_MAX]; long n[SQD_MAX]; float scale[SQD_MAX]; float* dst[SQD_MAX]; int count; };
+hipError_t launch_sqdiff_group(const SqdiffGroup& g, float* part, hipStream_t st);
+// the spatial net's MSE tail at aefft_net_step_apply: tail[l] <- tail[l] * scale, the same into save[l] and mse[l] (nullable).  The tail then
+// holds the global mean on every rank, so a further all-reduce of it times 1/world (dp.py flush_mse) gives the mean back
+hipError_t launch_scale_tail(float* tail, float* save, float* mse, int L, float scale, hipStream_t st);
 
 }  // namespace aefft

@@ -31,6 +31,7 @@ struct Pair {
     float* es;               // [2*dD] DC bins of the error summed over the batch (inside the net scratch)
     float2 *S, *dc, *df;     // per-pair gradient workspaces (pairs run concurrently on side streams); df == dc + W
     float* part;             // kgrad partial sums
+    float *Lin = nullptr, *Lhid = nullptr, *Lout = nullptr;   // spatial net: layers 2l+1, 2l+2 and 4L-1-2l, [B][dD|dM|dD][Nx][Ny]
     size_t nk() const { return (size_t)dM * dD * Nk * Nl; }     // taps of each of the two kernels
     GradSeg grads(float* buf) const { float* g = buf + goff; return GradSeg{g, g + nk(), g + 2 * nk(), g + 2 * nk() + dM}; }   // its segment of buf (aefft_net::grad)
 };
@@ -92,6 +93,14 @@ struct aefft_net {
     bool fuse_crop = true;     // encoder convs also write the next pair's cropped input (no resize launches)
     bool pruned = true;        // every pair's kernel support has a pruned transform -> no shared FFT workspace in the backward
     float* real;
+    // spatial net (AEFFT_NET_SPATIAL, spatial_net.hip): coordinate-space layers per pair, no spectra
+    bool spatial = false;
+    float alpha = 0.9f;        // inertia weight of backprop_gpu (autoencoder.cpp:89), aefft_net_set_inertia
+    float* sp_ws = nullptr;    // back-convolved error of the largest pair (launch_spatial_grad's fallback routes)
+    float* sp_part = nullptr;  // tiled weight-gradient partial sums (spatial_partial_floats of the largest pair)
+    float* sp_rq = nullptr;    // error-input region sums (spatial_rq_floats)
+    float* sp_up = nullptr;    // an up-sampled decoder input, for kernel shapes the tiled convolutions do not serve
+    float* sp_sqd = nullptr;   // MSE partial sums (SQD_MAX * SQD_BLOCKS)
 };
 
 namespace aefft {
@@ -105,6 +114,15 @@ int net_alloc(aefft_net* n, void** p, size_t bytes);
 template <typename T> int net_alloc_t(aefft_net* n, T** p, size_t count) { return net_alloc(n, reinterpret_cast<void**>(p), count * sizeof(T)); }
 int pair_spectra(aefft_net* n, Pair& q);
 int ensure_spectra(aefft_net* n, Pair& q);
+
+// ---- spatial_net.hip (a net created with AEFFT_NET_SPATIAL: the entry points hand over to these) ------------------------
+int sp_create(aefft_ctx* ctx, const aefft_net_desc* d, aefft_net** out);
+int sp_forward(aefft_net* n, const float* frames_d, float* recon_d);
+int sp_step_grad(aefft_net* n, const float* frames_d, float* recon_d);
+int sp_step_apply(aefft_net* n, float del0, int maxdiff, int sym, float grad_scale, float* mse_d);
+int sp_get_layer(aefft_net* n, int layer, float* out_d, int* ch, int* nx, int* ny);
+int sp_last_mse(aefft_net* n, float* mse_d);
+int sp_refuse(aefft_net* n, const char* entry);     // AEFFT_EINVAL: `entry` does not apply to a spatial net
 
 // ---- net_step.hip ----------------------------------------------------------------------
 int ensure_frames(aefft_net* n);

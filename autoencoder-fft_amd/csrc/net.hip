@@ -205,7 +205,13 @@ static int net_create(aefft_ctx* ctx, const aefft_net_desc* d, unsigned opts, ae
 extern "C" int aefft_net_create(aefft_ctx* ctx, const aefft_net_desc* d, aefft_net** out) { return net_create(ctx, d, 0, out); }
 extern "C" int aefft_net_create_ex(aefft_ctx* ctx, const aefft_net_desc* d, unsigned opts, aefft_net** out)
 {
-    if (opts & ~(unsigned)AEFFT_NET_SMOOTH_SIZES) return fail(ctx, AEFFT_EINVAL, "aefft_net_create_ex: unknown option bits");
+    if (opts & ~(unsigned)(AEFFT_NET_SMOOTH_SIZES | AEFFT_NET_SPATIAL)) return fail(ctx, AEFFT_EINVAL, "aefft_net_create_ex: unknown option bits");
+    if (opts & AEFFT_NET_SPATIAL) {       // (AEFFT_NET_SMOOTH_SIZES has no effect: the spatial mode takes any frame size)
+        if (!ctx || !d || !out || d->npairs <= 0 || d->batch <= 0 || d->D <= 0 || !d->maps || !d->Nk || !d->Nl || !d->scale)
+            return fail(ctx, AEFFT_EINVAL, "aefft_net_create_ex: bad descriptor");
+        *out = nullptr;
+        return sp_create(ctx, d, out);
+    }
     return net_create(ctx, d, opts, out);
 }
 
@@ -286,6 +292,7 @@ int aefft::ensure_spectra(aefft_net* n, Pair& q)
 extern "C" int aefft_net_pair_spectra(aefft_net* n, int l, float** C_d, float** F_d)
 {
     if (!n || l < 0 || l >= n->L) return fail(n ? n->ctx : nullptr, AEFFT_EINVAL, "aefft_net_pair_spectra: bad argument");
+    if (n->spatial) return sp_refuse(n, "aefft_net_pair_spectra");
     RET_IF(ensure_spectra(n, n->pr[l]));
     if (C_d) *C_d = reinterpret_cast<float*>(n->pr[l].C);
     if (F_d) *F_d = reinterpret_cast<float*>(n->pr[l].F);
@@ -295,6 +302,7 @@ extern "C" int aefft_net_pair_spectra(aefft_net* n, int l, float** C_d, float** 
 extern "C" int aefft_net_store_spectra(aefft_net* n, int l, float* C_h, float* F_h)
 {
     if (!n || l < 0 || l >= n->L) return fail(n ? n->ctx : nullptr, AEFFT_EINVAL, "aefft_net_store_spectra: bad argument");
+    if (n->spatial) return sp_refuse(n, "aefft_net_store_spectra");
     aefft_ctx* ctx = n->ctx;
     Pair& q = n->pr[l];
     RET_IF(ensure_spectra(n, q));
@@ -310,6 +318,7 @@ extern "C" int aefft_net_store_spectra(aefft_net* n, int l, float* C_h, float* F
 extern "C" int aefft_net_load_spectra(aefft_net* n, int l, const float* C_h, const float* b_h, const float* F_h, const float* p_h)
 {
     if (!n || l < 0 || l >= n->L || !C_h || !b_h || !F_h || !p_h) return fail(n ? n->ctx : nullptr, AEFFT_EINVAL, "aefft_net_load_spectra: bad argument");
+    if (n->spatial) return sp_refuse(n, "aefft_net_load_spectra");
     n->upd_after_fwd = false;
     aefft_ctx* ctx = n->ctx;
     Pair& q = n->pr[l];
@@ -329,6 +338,7 @@ extern "C" int aefft_net_load_spectra(aefft_net* n, int l, const float* C_h, con
 extern "C" int aefft_net_get_layer(aefft_net* n, int layer, float* out_d, int* ch, int* nx, int* ny)
 {
     if (!n || layer < 0 || layer > 4 * n->L) return fail(n ? n->ctx : nullptr, AEFFT_EINVAL, "aefft_net_get_layer: bad layer index");
+    if (n->spatial) return sp_get_layer(n, layer, out_d, ch, nx, ny);
     aefft_ctx* ctx = n->ctx;
     RET_IF(join_recon(ctx));
     if (out_d && n->have_forward) RET_IF(ensure_frames(n));

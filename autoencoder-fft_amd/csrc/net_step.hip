@@ -479,6 +479,7 @@ int aefft::ensure_frames(aefft_net* n)
 
 extern "C" int aefft_net_forward(aefft_net* n, const float* frames_d, float* recon_d)
 {
+    if (n && n->spatial) return sp_forward(n, frames_d, recon_d);
     RET_IF(net_forward(n, frames_d, false, recon_d, false));
     return mark_step_point(n);
 }
@@ -487,6 +488,7 @@ extern "C" int aefft_net_forward(aefft_net* n, const float* frames_d, float* rec
 extern "C" int aefft_net_forward_u8(aefft_net* n, const unsigned char* frames_d, float* recon_d)
 {
     if (!n) return AEFFT_EINVAL;
+    if (n->spatial) return sp_refuse(n, "aefft_net_forward_u8");
     RET_IF(net_forward(n, reinterpret_cast<const float*>(frames_d), true, recon_d, false));
     return mark_step_point(n);
 }
@@ -551,6 +553,7 @@ static int pair_apply(aefft_net* n, Pair& q, float del, int maxdiff, int sym, fl
 extern "C" int aefft_net_train_pair(aefft_net* n, int l, int n_iter, float del0, int maxdiff, int sym, float* mse_h)
 {
     if (!n || l < 0 || l >= n->L || n_iter < 0) return fail(n ? n->ctx : nullptr, AEFFT_EINVAL, "aefft_net_train_pair: bad argument");
+    if (n->spatial) return sp_refuse(n, "aefft_net_train_pair");
     n->upd_after_fwd = false;
     aefft_ctx* ctx = n->ctx;
     if (!n->have_forward) return fail(ctx, AEFFT_ESTATE, "aefft_net_train_pair: run aefft_net_forward first (the burst trains on its layers)");
@@ -1108,6 +1111,7 @@ int aefft::mark_step_point(aefft_net* n)
 extern "C" int aefft_net_set_input_ready(aefft_net* n, int enable)
 {
     if (!n) return AEFFT_EINVAL;
+    if (n->spatial) return enable ? sp_refuse(n, "aefft_net_set_input_ready(1)") : AEFFT_OK;
     aefft_ctx* ctx = n->ctx;
     if (enable && !n->X0alt) {
         const Pair& q = n->pr[0];
@@ -1157,17 +1161,23 @@ static int step_grad(aefft_net* n, const float* frames_d, bool u8, float* recon_
     return mark_step_point(n);
 }
 
-extern "C" int aefft_net_step_grad(aefft_net* n, const float* frames_d, float* recon_d) { return n ? step_grad(n, frames_d, false, recon_d) : AEFFT_EINVAL; }
+extern "C" int aefft_net_step_grad(aefft_net* n, const float* frames_d, float* recon_d)
+{
+    if (n && n->spatial) return sp_step_grad(n, frames_d, recon_d);
+    return n ? step_grad(n, frames_d, false, recon_d) : AEFFT_EINVAL;
+}
 
 // 8-bit frames: the input transform converts on load (fft_kernels.hip r2c_rows_kernel<N, true>); nothing else reads the frames
 extern "C" int aefft_net_step_grad_u8(aefft_net* n, const unsigned char* frames_d, float* recon_d)
 {
+    if (n && n->spatial) return sp_refuse(n, "aefft_net_step_grad_u8");
     return n ? step_grad(n, reinterpret_cast<const float*>(frames_d), true, recon_d) : AEFFT_EINVAL;
 }
 
 extern "C" int aefft_net_step_form(aefft_net* n)
 {
     if (!n) return -1;
+    if (n->spatial) return AEFFT_FORM_SPATIAL;
     if (!op_eligible(n)) return AEFFT_FORM_PER_FRAME;
     const bool chain = n->Wp && (n->compact || n->L == 1) && chain_switches_ok();
     return chain ? AEFFT_FORM_OPERATOR_CHAIN : AEFFT_FORM_OPERATOR;
@@ -1184,6 +1194,7 @@ extern "C" int aefft_net_grad_buffer(aefft_net* n, float** buf_d, size_t* nfloat
 extern "C" int aefft_net_last_mse(aefft_net* n, float* mse_d)
 {
     if (!n || !mse_d) return AEFFT_EINVAL;
+    if (n->spatial) return sp_last_mse(n, mse_d);
     aefft_ctx* ctx = n->ctx;
     RET_IF(mse_flush(n));
     HIPCHK(ctx, hipMemcpyAsync(mse_d, n->mse_post, sizeof(float) * n->L, hipMemcpyDeviceToDevice, ctx->stream));
@@ -1193,6 +1204,7 @@ extern "C" int aefft_net_last_mse(aefft_net* n, float* mse_d)
 extern "C" int aefft_net_step_apply(aefft_net* n, float del0, int maxdiff, int sym, float grad_scale, float* mse_d)
 {
     if (!n) return AEFFT_EINVAL;
+    if (n->spatial) return sp_step_apply(n, del0, maxdiff, sym, grad_scale, mse_d);
     aefft_ctx* ctx = n->ctx;
     if (!n->have_grad) return fail(ctx, AEFFT_ESTATE, "aefft_net_step_apply: call aefft_net_step_grad first");
     RET_IF(mse_flush(n));

@@ -88,6 +88,12 @@ struct DConvArgs {
     // and every staged input pixel is max(0, trunc(max of its pool x pool window)); pooled_out (nullable) also receives the pooled
     // layer [B][Din][Nx][Ny] (the training step needs it as the pair's input).  pool == 0: off.
     int pool; float* pooled_out;
+    // the mirror case, nearest-neighbour up-sampling (netlib.cpp:141-162, scale < 0) in front of the convolution: `in` is the COARSE
+    // plane [Din][Nx/up][Ny/up] and the staged pixel (r, c) of the up-sampled grid reads in[r/up][c/up] (tap offsets and range tests on
+    // the up-sampled grid).  Nx, Ny are multiples of up.  up == 0: off.
+    int up;
+    // up-sampled publication: out_up (nullable) also receives the output replicated out_up_s x out_up_s, [B][M][Nx*s][Ny*s]
+    float* out_up; int out_up_s;
     int nt_out;                 // (set by launch_dconv) the output is larger than the Infinity Cache: streaming stores
 };
 
@@ -198,6 +204,9 @@ __global__ __launch_bounds__(256) void dconv4_kernel(const DConvArgs a)
     const int r0 = a.sgn < 0 ? ti * TR - a.ik0 - (NK - 1) : ti * TR + a.ik0;
     const int c0 = a.sgn < 0 ? tj * TC - a.il0 - (NK - 1) : tj * TC + a.il0;
     const long plane = (long)a.Nx * a.Ny;
+    const int su = a.up ? a.up : 1;                        // up-sampling on load: the input plane is the coarse one
+    const long plane_in = plane / ((long)su * su);
+    const int ny_in = a.Ny / su;
     // this thread's staged elements: offset inside a stage's DC planes (the same for every stage) and whether the element exists
     static_assert(NLD <= 64, "one mask bit per staged element");
     int off[NLD]; unsigned long long okm = 0;
@@ -207,7 +216,7 @@ __global__ __launch_bounds__(256) void dconv4_kernel(const DConvArgs a)
         const int dl = min(t / TSZ, DC - 1), q = t % TSZ;
         const int r = r0 + q / TWX, cc = c0 + q % TWX;
         const bool ok = t < DC * TSZ && r >= a.lo_in && r < a.Nx && cc >= a.lo_in && cc < a.Ny;
-        off[u] = ok ? dl * (int)plane + r * a.Ny + cc : 0;
+        off[u] = !ok ? 0 : a.up ? dl * (int)plane_in + (r / su) * ny_in + cc / su : dl * (int)plane + r * a.Ny + cc;
         okm |= (ok ? 1ull : 0ull) << u;
     }
     float acc[RW][TM][PX];
@@ -220,7 +229,7 @@ __global__ __launch_bounds__(256) void dconv4_kernel(const DConvArgs a)
     float v[NLD], v2[SUB ? NLD : 1];
     auto prefetch = [&](int d0) {                          // the next stage's inputs: in flight while this stage computes
         const int nd = min(DC, a.Din - d0);
-        const float* base = a.in + (bb * a.Din + d0) * plane;
+        const float* base = a.in + (bb * a.Din + d0) * plane_in;
         const float* base2 = SUB ? a.in2 + (bb * a.Din + d0) * plane : nullptr;
 #pragma unroll
         for (int u = 0; u < NLD; ++u) {
@@ -294,6 +303,16 @@ __global__ __launch_bounds__(256) void dconv4_kernel(const DConvArgs a)
 #pragma unroll
                 for (int p = 0; p < PX; ++p) if (j0 + p < a.Ny) dst[p] = o[p];
             }
+            if (a.out_up) {                                // the s x s replicated output from the same registers
+                const int s = a.out_up_s;
+                const long nyu = (long)a.Ny * s;
+                float* du = a.out_up + (bb * a.M + m) * plane * s * s + (long)ir * s * nyu + (long)j0 * s;
+                for (int u = 0; u < s; ++u)
+#pragma unroll
+                    for (int p = 0; p < PX; ++p)
+                        if (j0 + p < a.Ny)
+                            for (int v = 0; v < s; ++v) du[u * nyu + p * s + v] = o[p];
+            }
         }
     }
 }
@@ -364,6 +383,27 @@ __global__ __launch_bounds__(256) void mconv_kernel(const DConvArgs a)
                     if (r < a.lo_in || cc < a.lo_in) x = 0.f;                 // the convolution's own range test ('>0' of netlib.cpp:344)
                 }
                 tile[dl][q] = a.div != 1.f ? x / a.div : x;
+            }
+        } else if (a.up) {
+            // nearest-neighbour up-sampling on load: the staged pixel (r, cc) of the up-sampled grid is in[r/s][cc/s] of the coarse plane
+            const int s = a.up, Nxi = a.Nx / s, Nyi = a.Ny / s;
+            for (int t0 = 0; t0 < nd * TSZ; t0 += 256 * 8) {
+                float v[8];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                    const int t = t0 + u * 256 + threadIdx.x;
+                    const int dl = min(t / TSZ, nd - 1), q = t % TSZ;
+                    const int r = r0 + q / TWX, cc = c0 + q % TWX;
+                    const bool ok = t < nd * TSZ && r >= a.lo_in && r < a.Nx && cc >= a.lo_in && cc < a.Ny;
+                    const long idx = ok ? ((bb * a.Din + d0 + dl) * (long)Nxi + r / s) * Nyi + cc / s : 0;
+                    v[u] = ok ? a.in[idx] : 0.f;
+                }
+#pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                    const int t = t0 + u * 256 + threadIdx.x;
+                    if (t >= nd * TSZ) break;
+                    tile[t / TSZ][t % TSZ] = a.div != 1.f ? v[u] / a.div : v[u];
+                }
             }
         } else {
             for (int t0 = 0; t0 < nd * TSZ; t0 += 256 * 8) {
@@ -439,6 +479,13 @@ __global__ __launch_bounds__(256) void mconv_kernel(const DConvArgs a)
                 float* dst = &a.out[(bb * a.M + m0 + ml) * plane + (long)i * a.Ny + j];
                 if (a.nt_out) __builtin_nontemporal_store(o, dst);      // (uniform) a layer larger than the caches: do not displace its own input
                 else *dst = o;
+                if (a.out_up) {                                         // the s x s replicated output from the same registers
+                    const int s = a.out_up_s;
+                    const long nyu = (long)a.Ny * s;
+                    float* du = a.out_up + (bb * a.M + m0 + ml) * plane * s * s + (long)i * s * nyu + (long)j * s;
+                    for (int u = 0; u < s; ++u)
+                        for (int v = 0; v < s; ++v) du[u * nyu + v] = o;
+                }
             }
     }
 }
@@ -451,9 +498,15 @@ template <int NK> static hipError_t run_mconv(const DConvArgs& a, int B, hipStre
     return hipGetLastError();
 }
 
+// run_dconv takes the register-blocked few-map form (dconv4_kernel): few maps, wide planes.  The ONE place of this rule: launch_dconv sends
+// up-sampling launches that it does not take to the matrix-core kernel (dconv_kernel has no up-sampling)
+static bool dconv4_taken(const DConvArgs& a, int Nk)
+{
+    return a.M <= 4 && a.Ny >= 64 && (long)a.Nx * a.Ny * 4 < (1L << 31) && (size_t)a.Din * Nk * ((Nk * 4 + 3) & ~3) * 4 <= 32 * 1024 && !flag(AEFFT_F_NOFAST);
+}
 template <int NK> static hipError_t run_dconv(const DConvArgs& a, int B, hipStream_t st)
 {
-    if (a.M <= 4 && a.Ny >= 64 && (long)a.Nx * a.Ny * 4 < (1L << 31) && (size_t)a.Din * NK * ((NK * 4 + 3) & ~3) * 4 <= 32 * 1024 && !flag(AEFFT_F_NOFAST)) {        // few maps, wide planes: the register-blocked form
+    if (dconv4_taken(a, NK)) {
         const int tiles4 = ((a.Nx + 16 * DCONV4_RW - 1) / (16 * DCONV4_RW)) * ((a.Ny + 63) / 64);      // (dconv4_kernel: 16 * DCONV4_RW rows x 64 columns per workgroup)
 #define AEFFT_D4(TMV) { const size_t wb = sizeof(float) * (size_t)a.Din * NK * ((NK * TMV + 3) & ~3);                            \
             if (a.in2) dconv4_kernel<TMV, NK, true><<<dim3(tiles4, 1, B), 256, wb, st>>>(a);                                      \
@@ -476,9 +529,11 @@ static hipError_t launch_dconv(const DConvArgs& a0, int Nk, int B, hipStream_t s
 {
     DConvArgs a = a0;
     a.nt_out = (double)B * a.M * a.Nx * a.Ny * 4.0 > 192e6;
-    // matrix cores whenever there is a GEMM to speak of (>= 8 maps); AEFFT_F_NOMFMA keeps the VALU tile kernel (and the fused
-    // Pool exists only in the matrix-core kernel)
-    if ((a.M >= 8 && !flag(AEFFT_F_NOMFMA)) || a.pool) {
+    // matrix cores whenever there is a GEMM to speak of (>= 8 maps); AEFFT_F_NOMFMA keeps the VALU tile kernel -- except for the fused
+    // Pool, which exists only in the matrix-core kernel, and for up-sampling on load / the up-sampled publication, which exist in the
+    // matrix-core kernel and the few-map one: a launch with them that dconv4_kernel does not take runs on the matrix cores even under
+    // AEFFT_F_NOMFMA
+    if ((a.M >= 8 && !flag(AEFFT_F_NOMFMA)) || a.pool || ((a.up || a.out_up) && !dconv4_taken(a, Nk))) {
         if (Nk == 3) return run_mconv<3>(a, B, st);
         if (Nk == 5) return run_mconv<5>(a, B, st);
         return run_mconv<7>(a, B, st);
@@ -903,7 +958,7 @@ size_t spatial_partial_floats(int B, int dD, int dM, int Nx, int Ny, int Nk, int
     if (Nk == 3) x = std::max(wcorr_part_floats<3>(dM, dD, Nx, B), wcorr_part_floats<3>(dD, dM, Nx, B));
     else if (Nk == 5) x = std::max(wcorr_part_floats<5>(dM, dD, Nx, B), wcorr_part_floats<5>(dD, dM, Nx, B));
     else x = std::max(wcorr_part_floats<7>(dM, dD, Nx, B), wcorr_part_floats<7>(dD, dM, Nx, B));
-    x = std::max(x, (size_t)B * ((Nx + 7) / 8) * ((Ny + 255) / 256) * (16 * (9 * 25 + 3)));      // rcorr_kernel's workgroup partials (rc_pw<3>)
+    x = std::max(x, (size_t)B * ((Nx + 7) / 8) * ((Ny + 255) / 256) * (16 * (9 * 25 + 3) + 1));      // rcorr_kernel's workgroup partials (rc_pw<3>)
     return std::max(x, mcorr_part_floats(Nx, B));
 }
 template <int NK> static hipError_t launch_wcorr(const WCorrArgs& a, int B, float* out, float* osum, float scale, hipStream_t st)
@@ -913,19 +968,23 @@ template <int NK> static hipError_t launch_wcorr(const WCorrArgs& a, int B, floa
 
 hipError_t launch_conv_spatial(const float* in, float* out, const float* c, const float* b, int B, int dD, int dM,
                                int Nx, int Ny, int Nk, int Nl, int ak, int al, float in_scale_div, int lo, hipStream_t st,
-                               int pool, float* pooled_out)
+                               int pool, float* pooled_out, int up, float* out_up, int out_up_s)
 {
     const long total = (long)B * dM * Nx * Ny;
     if (total <= 0) return hipSuccess;
+    if (pool && up) return hipErrorInvalidValue;
+    if (up && (Nx % up || Ny % up)) return hipErrorInvalidValue;
     if (dconv_ok(Nk, Nl, B) && !flag(AEFFT_F_NOTILEDSPATIAL)) {
         DConvArgs a{};
         a.in = in; a.w = c; a.bias = b; a.out = out;
         a.Din = dD; a.M = dM; a.Nx = Nx; a.Ny = Ny; a.w_m = dD * Nk * Nl; a.w_d = Nk * Nl;
         a.ik0 = -2 * ak - 1; a.il0 = -2 * al - 1; a.sgn = -1; a.lo_in = lo; a.hi_lo = 0; a.div = in_scale_div;
         a.pool = pool; a.pooled_out = pooled_out;
+        a.up = up > 1 ? up : 0;
+        a.out_up = out_up_s >= 1 ? out_up : nullptr; a.out_up_s = out_up_s;
         return launch_dconv(a, Nk, B, st);
     }
-    if (pool) return hipErrorInvalidValue;                             // (callers pool separately for shapes the tiled kernels do not serve)
+    if (pool || up > 1 || out_up) return hipErrorInvalidValue;        // (callers pool / up-sample separately for shapes the tiled kernels do not serve)
     conv_spatial_kernel<<<dim3((unsigned)((total + 255) / 256)), 256, 0, st>>>(in, out, c, b, B, dD, dM, Nx, Ny, Nk, Nl, ak, al, in_scale_div, lo);
     return hipGetLastError();
 }
@@ -1047,6 +1106,58 @@ hipError_t launch_pool_spatial(const float* in, float* out, long planes, int Nxi
     return hipGetLastError();
 }
 
+// Per-pair sum of squared differences for the spatial net's MSE tail, without float atomics: SQD_BLOCKS workgroups per pair each sum a
+// fixed grid-stride slice (4 independent accumulators per thread), then one workgroup per pair adds the SQD_BLOCKS partials in index order.
+__global__ __launch_bounds__(256) void sqdiff_part_kernel(const SqdiffGroup g, float* __restrict__ part)
+{
+    const int k = blockIdx.y;
+    const float* __restrict__ a = g.a[k];
+    const float* __restrict__ b = g.b[k];
+    const long n = g.n[k], stride = (long)SQD_BLOCKS * 256;
+    float s[4] = {0.f, 0.f, 0.f, 0.f};
+    long i = (long)blockIdx.x * 256 + threadIdx.x;
+    for (; i + 3 * stride < n; i += 4 * stride)
+#pragma unroll
+        for (int u = 0; u < 4; ++u) { const float d = a[i + u * stride] - b[i + u * stride]; s[u] = fmaf(d, d, s[u]); }
+    for (; i < n; i += stride) { const float d = a[i] - b[i]; s[0] = fmaf(d, d, s[0]); }
+    const float t = block_sum((s[0] + s[1]) + (s[2] + s[3]));
+    if (threadIdx.x == 0) part[k * SQD_BLOCKS + blockIdx.x] = t;
+}
+
+__global__ __launch_bounds__(256) void sqdiff_sum_kernel(const SqdiffGroup g, const float* __restrict__ part)
+{
+    const int k = blockIdx.x;
+    const float v = threadIdx.x < SQD_BLOCKS ? part[k * SQD_BLOCKS + threadIdx.x] : 0.f;
+    const float t = block_sum(v);
+    if (threadIdx.x == 0) *g.dst[k] = t * g.scale[k];
+}
+
+hipError_t launch_sqdiff_group(const SqdiffGroup& g, float* part, hipStream_t st)
+{
+    if (g.count < 1 || g.count > SQD_MAX) return hipErrorInvalidValue;
+    sqdiff_part_kernel<<<dim3(SQD_BLOCKS, g.count), 256, 0, st>>>(g, part);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    sqdiff_sum_kernel<<<dim3(g.count), 256, 0, st>>>(g, part);
+    return hipGetLastError();
+}
+
+__global__ __launch_bounds__(64) void scale_tail_kernel(float* __restrict__ tail, float* __restrict__ save, float* __restrict__ mse, int L, float scale)
+{
+    for (int l = threadIdx.x; l < L; l += 64) {
+        const float v = tail[l] * scale;
+        tail[l] = v;
+        save[l] = v;
+        if (mse) mse[l] = v;
+    }
+}
+
+hipError_t launch_scale_tail(float* tail, float* save, float* mse, int L, float scale, hipStream_t st)
+{
+    scale_tail_kernel<<<dim3(1), 64, 0, st>>>(tail, save, mse, L, scale);
+    return hipGetLastError();
+}
+
 // ------------------------------------------------------------------------------------------
 // SURVEY Appendix B-11 compat mode: the decoder-kernel and encoder-bias gradients exactly as the reference's CUDA source
 // computes them (the literal per-element restatement the parity tests check against), overwriting what the kernels above produced:
@@ -1140,7 +1251,8 @@ hipError_t launch_spatial_compat(const SpatialGradArgs& a, hipStream_t st)
 static bool rcorr_ok(const SpatialGradArgs& a);
 struct RCorrArgs { const float *out, *in; float* part; int B, Nx, Ny, ik0, il0, lo; };
 constexpr int RC_TR = 8, RC_CW = 256, RC_T = 5, RC_NSEG = 16;
-template <int D> constexpr int rc_pw() { return 16 * (D * D * RC_T * RC_T + D); }      // floats of one workgroup's partial: [rc 4][cs 4][d1][d][a][b] | [rc][cs][d1]
+// floats of one workgroup's partial: [rc 4][cs 4][d1][d][a][b] | [rc][cs][d1] | sum of s0^2 over the workgroup's pixels (the MSE, SpatialGradArgs::mse)
+template <int D> constexpr int rc_pw() { return 16 * (D * D * RC_T * RC_T + D) + 1; }
 
 template <int D>
 __global__ __launch_bounds__(256) void rcorr_kernel(const RCorrArgs g)
@@ -1151,6 +1263,7 @@ __global__ __launch_bounds__(256) void rcorr_kernel(const RCorrArgs g)
     float* xt = rc_sh + D * TR * CW;                      // [D][XR][XC]
     const int i0 = blockIdx.x * TR, j0 = blockIdx.y * CW;
     const long bb = blockIdx.z, plane = (long)g.Nx * g.Ny;
+    float sq = 0.f;                                       // sum of s0^2 over this thread's quads (each image pixel is staged by one workgroup, once)
     // stage: s0 = out - in (zero outside the image), in shifted: tile (r, c) <-> image (i0 - 2 ik0 - 4 + r, j0 - 2 il0 - 4 + c), zero outside [lo, N).
     // Every global load of the workgroup is issued before the first LDS store (clamped addresses, masks applied on the way to LDS): a
     // rolled load -> store loop is one memory round trip per iteration.
@@ -1160,6 +1273,7 @@ __global__ __launch_bounds__(256) void rcorr_kernel(const RCorrArgs g)
         constexpr int NX = (D * XR * XC + 255) / 256;                    // elements of the input tile per thread (37 for D = 3)
         float4 vo[NQ], vi[NQ];
         float vx[NX];
+
 #pragma unroll
         for (int u = 0; u < NQ; ++u) {
             const int t = u * 256 + threadIdx.x;
@@ -1184,6 +1298,7 @@ __global__ __launch_bounds__(256) void rcorr_kernel(const RCorrArgs g)
             const bool ok = i0 + r < g.Nx && j0 + c < g.Ny;               // (Ny is a multiple of 4: a quad is inside or outside as a whole)
             const float4 v = ok ? make_float4(vo[u].x - vi[u].x, vo[u].y - vi[u].y, vo[u].z - vi[u].z, vo[u].w - vi[u].w) : make_float4(0.f, 0.f, 0.f, 0.f);
             *reinterpret_cast<float4*>(s0t + (d * TR + r) * CW + c) = v;
+            sq = fmaf(v.x, v.x, fmaf(v.y, v.y, fmaf(v.z, v.z, fmaf(v.w, v.w, sq))));
         }
 #pragma unroll
         for (int u = 0; u < NX; ++u) {
@@ -1209,6 +1324,7 @@ __global__ __launch_bounds__(256) void rcorr_kernel(const RCorrArgs g)
 #pragma unroll
             for (int b = 0; b < T; ++b) acc[cs][d1][b] = 0.f;
         }
+    const float sq_wg = block_sum(sq);                    // (fixed shuffle tree: the same inputs give the same bits)
     const bool active = seg < RC_NSEG && i0 + r < g.Nx;
     if (active) {
         // x at image (i - u_i, j - u_j), u = 2 ik0 + (a, b): tile row r + (T-1-a), tile column jj + (T-1-b)
@@ -1273,6 +1389,7 @@ __global__ __launch_bounds__(256) void rcorr_kernel(const RCorrArgs g)
     constexpr int NR = D * D * T * T, PW = rc_pw<D>();
     float* dst = g.part + ((bb * gridDim.x + blockIdx.x) * gridDim.y + blockIdx.y) * (long)PW;
     for (int e = threadIdx.x; e < PW; e += 256) {
+        if (e == PW - 1) { dst[e] = sq_wg; continue; }
         int rc, cs, d1, cmb, off;
         if (e < 16 * NR) {
             rc = e / (4 * NR); int rem = e - rc * 4 * NR;
@@ -1329,7 +1446,7 @@ template <int D>
 __global__ __launch_bounds__(256) void dc_from_regions_kernel(const float* __restrict__ f, const float* __restrict__ tmp, float* __restrict__ gc,
                                                               float* __restrict__ gb, int dM, int Nx, int Ny, int ik0, int il0, int lo, float scale,
                                                               const float* __restrict__ c1, const float* __restrict__ b1, float inv_div1,
-                                                              float* __restrict__ gf, float* __restrict__ gp)
+                                                              float* __restrict__ gf, float* __restrict__ gp, float* __restrict__ mse)
 {
     constexpr int NK = 3, KK = 9, T = RC_T, NR = D * D * T * T, PW = rc_pw<D>();
     __shared__ float reg[PW];
@@ -1367,6 +1484,7 @@ __global__ __launch_bounds__(256) void dc_from_regions_kernel(const float* __res
         Rt[e] = R;
     }
     __syncthreads();
+    if (mse && blockIdx.x == 0 && threadIdx.x == 0) *mse = reg[PW - 1];     // sum s0^2 * scale = sum (in - out)^2 / Norm / B (backproplib.cu:346-356)
     const int idx = blockIdx.x * 256 + threadIdx.x;
     const int nw = dM * D * KK;
     if (idx >= nw + dM) {
@@ -1412,7 +1530,7 @@ __global__ __launch_bounds__(256) void dc_from_regions_kernel(const float* __res
 }
 
 // floats of SpatialGradArgs::rq (the region sums)
-size_t spatial_rq_floats(int dD, int Nk, int Nl) { (void)Nk; (void)Nl; return (size_t)RC_NCH * 16 * ((size_t)dD * dD * RC_T * RC_T + dD); }
+size_t spatial_rq_floats(int dD, int Nk, int Nl) { (void)Nk; (void)Nl; return (size_t)RC_NCH * (16 * ((size_t)dD * dD * RC_T * RC_T + dD) + 1); }
 
 bool spatial_regions_ok(const SpatialGradArgs& a) { return a.part && dconv_ok(a.Nk, a.Nl, a.B) && !flag(AEFFT_F_NOTILEDSPATIAL) && rcorr_ok(a); }
 static bool rcorr_ok(const SpatialGradArgs& a)
@@ -1441,7 +1559,7 @@ template <int D> static hipError_t run_rcorr(const SpatialGradArgs& a, float sca
     if (e != hipSuccess) return e;
     const int total = a.dM * D * 9 + a.dM + (a.c1 ? a.dM * D * 9 + D : 0);
     dc_from_regions_kernel<D><<<dim3((total + 255) / 256), 256, 0, st>>>(a.f, a.rq, a.gc, a.gb, a.dM, a.Nx, a.Ny, ik0, il0, a.lo, scale,
-                                                                         a.c1, a.b1, 1.0f / a.div1, a.gf, a.gp);
+                                                                         a.c1, a.b1, 1.0f / a.div1, a.gf, a.gp, a.mse);
     return hipGetLastError();
 }
 

@@ -11,7 +11,11 @@ float32 update to the same all-reduced buffer.
 The MSE rides in the same message (SURVEY 8e "+ 1 float MSE"): the packed buffer ends in L floats, the post-update MSE per pair of
 this rank's shard as the PREVIOUS step left it (aefft_net_step_apply writes them there; the post-update MSE of a step needs that
 step's reduced gradients, so it cannot travel with them).  After the all-reduce that tail holds the sum over ranks; mse_tail() turns
-it into the global-batch mean (one step behind), and flush_mse() reduces the last step's values with one more small collective."""
+it into the global-batch mean (one step behind), and flush_mse() reduces the last step's values with one more small collective.
+
+A spatial net (Net(..., spatial=True), AEFFT_NET_SPATIAL) runs through both classes unchanged, but its tail is CURRENT-step: step_grad
+writes each pair's pre-update MSE of this rank's frames there (backprop_gpu forms it before its update), so after the all-reduce the
+saved tail -- mse_tail(), last_mse(), the `mse` output of step_apply -- is the global-batch pre-update MSE of the step just taken."""
 import numpy as np
 
 
@@ -108,7 +112,8 @@ class DataParallelStep:
 
     def mse_tail(self):
         """global-batch post-update MSE per pair of the step BEFORE the last one (it travelled in the last gradient all-reduce and was saved
-        behind the packed buffer by the last aefft_net_step_apply): a stream-ordered view, valid until the next step; zeros after the first step"""
+        behind the packed buffer by the last aefft_net_step_apply): a stream-ordered view, valid until the next step; zeros after the first step.
+        On a spatial net: the global-batch PRE-update MSE of the LAST step (its tail is current-step)."""
         return self._mse_prev
 
     def flush_mse(self):

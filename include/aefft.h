@@ -213,7 +213,34 @@ int aefft_net_create(aefft_ctx* ctx, const aefft_net_desc* desc, aefft_net** out
  * returns AEFFT_FORM_PER_FRAME (the operator forms need the pruned kernel transforms, which take power-of-two grids); a power-of-two net
  * created with the option runs exactly as one from aefft_net_create.  Every aefft_net_* entry
  * point works on it, and the net sizes all its workspaces here. */
-enum { AEFFT_NET_SMOOTH_SIZES = 1u << 0 };
+enum { AEFFT_NET_SMOOTH_SIZES = 1u << 0, AEFFT_NET_SPATIAL = 1u << 1 };
+/* AEFFT_NET_SPATIAL: the reference's coordinate-space training mode (autoencoder.cpp:135-150,171-201: Pool -> Conv_gpu per encoder,
+ * Conv_gpu -> Pool(-s) per decoder, backprop_gpu / backprop_gpu_cc per pair) as a resident, batched net, with GPU semantics throughout
+ * (cpu_semantics = 0 of the spatial ops above).  Same descriptor.  Any Nx, Ny; every pair's scale is an integer >= 1 that divides its
+ * input grid EXACTLY (Pool(-s) with a remainder reads past its input in the reference, netlib.cpp:141-162) and every pooled grid is at
+ * least the pair's kernel support -- AEFFT_EINVAL naming the rule and the pair otherwise (66 x 66 over two pairs of scale 2: pair 1 has
+ * 33 x 33).  Kernel supports: whatever aefft_step_spatial takes.  AEFFT_NET_SMOOTH_SIZES together with it is accepted and has no effect.
+ * Layers, pair l on the grid G_l = G_{l-1} / s_l: 2l+1 = Pool(2l, s_l), 2l+2 = Conv_gpu(2l+1; c_l, b_l), 4L-1-2l = Conv_gpu(4L-2-2l; f_l, p_l),
+ * 4L-2l = Pool(4L-1-2l, -s_l); layer 4L is the reconstruction.  On such a net:
+ *   aefft_net_forward       the forward (recon_d nullable).
+ *   aefft_net_step_grad     the forward, then for EVERY pair backprop_gpu's gradients as the batch mean with in = layer 2l+1, out = layer
+ *                           4L-1-2l (the whole network's decoder output at that grid, autoencoder.cpp:161-169,174 with q = 1), hin = layer
+ *                           2l+2, normalised with the untied Norm = dD*dM*Nk*Nl*Nx*Ny, into the packed buffer in the FFT nets' layout;
+ *                           its tail slot l holds sum (in - out)^2 / Norm, the mean over this rank's frames, BEFORE the update
+ *                           (backproplib.cu:346-356).  The same inputs give the same buffer bit for bit.
+ *   aefft_net_step_apply    backprop_gpu's update of every pair with its own momentum, d <- (1-alpha)*del0*g/max(10,|g|) + alpha*d,
+ *                           w <- w - d, g = buffer * grad_scale: del0 IS delmax (autoencoder.cpp:87,178 pass `del` straight through, no
+ *                           0.1 factor as in FFT mode); alpha: aefft_net_set_inertia.  sym = 1 is backprop_gpu_cc (backproplib.cu:521-644):
+ *                           gradients and MSE halved (Norm x 2, :533), g = gc + gf^T, f = c^T exactly afterwards.  maxdiff != 0:
+ *                           AEFFT_EINVAL (no multiobjective term).  The tail x grad_scale (x 1/2 with sym) replaces the tail and goes to
+ *                           mse_d (nullable) and behind the buffer, and aefft_net_last_mse returns it: after the all-reduce it is the
+ *                           global-batch PRE-update MSE of THIS step -- not one step behind as in FFT mode -- and, as on an FFT net, a
+ *                           further all-reduce of the tail times 1/world gives that mean again.
+ *   aefft_net_get_layer(s), aefft_net_layers_layout: every layer 0..4L of the last forward / step_grad (the pre-update weights); the
+ *                           up-sampled decoder layers 4L-2l are not kept and are formed on request (Pool(-s)).
+ *   npairs, pair_shape, set_pair, get_pair, reset_momentum, grad_buffer, last_mse, step_form (AEFFT_FORM_SPATIAL): as on any net.
+ *   pair_spectra, store_spectra, load_spectra (no spectra), train_pair, step_grad_u8, forward_u8, set_input_ready(1): AEFFT_EINVAL.
+ * The development switches AEFFT_F_NOTILEDSPATIAL and AEFFT_F_NORCORR select the fallback routes, as at op level. */
 int aefft_net_create_ex(aefft_ctx* ctx, const aefft_net_desc* desc, unsigned opts, aefft_net** out);
 void aefft_net_destroy(aefft_net* net);
 /* the descriptor back: number of pairs (negative for a null net); channels / maps / kernel support of pair l (any pointer nullable) */
@@ -304,7 +331,8 @@ int aefft_net_set_input_ready(aefft_net* net, int enable);
  * the post-update MSE of a step needs that step's reduced gradients, so it travels one step behind).  aefft_net_step_apply reads the
  * gradient part only and overwrites the tail; what it finds there it first saves, times its grad_scale, in the L floats BEHIND the
  * buffer (buf_d[nfloats .. nfloats + L), not part of the message): after step_apply of step t+1 they hold the global-batch MSE of step t
- * (with mse_d = NULL, see aefft_net_last_mse: once the sums of step t+1 have been formed, i.e. after the next aefft_net_step_grad). */
+ * (with mse_d = NULL, see aefft_net_last_mse: once the sums of step t+1 have been formed, i.e. after the next aefft_net_step_grad).
+ * A spatial net (AEFFT_NET_SPATIAL) puts the PRE-update MSE of THIS step in the tail: see aefft_net_create_ex. */
 int aefft_net_grad_buffer(aefft_net* net, float** buf_d, size_t* nfloats);
 /* Which form the NEXT aefft_net_step_grad / _apply of this net runs in (decided by the net's shapes and the development switches; the
  * arithmetic is the reference's in every form, re-associated -- DESIGN.md section 4):
@@ -316,7 +344,7 @@ int aefft_net_grad_buffer(aefft_net* net, float** buf_d, size_t* nfloats);
  *   AEFFT_FORM_OPERATOR_CHAIN  ... with the whole operator chain in one launch out of a bin-major copy of the kernel spectra (coarsest grid
  *                              of at most 16384 bins); the next step's chain rides in the last launch of this step.
  * Returns -1 for a null net. */
-enum { AEFFT_FORM_PER_FRAME = 0, AEFFT_FORM_OPERATOR = 1, AEFFT_FORM_OPERATOR_CHAIN = 2 };
+enum { AEFFT_FORM_PER_FRAME = 0, AEFFT_FORM_OPERATOR = 1, AEFFT_FORM_OPERATOR_CHAIN = 2, AEFFT_FORM_SPATIAL = 3 /* AEFFT_NET_SPATIAL */ };
 int aefft_net_step_form(aefft_net* net);
 int aefft_net_step_apply(aefft_net* net, float del0, int maxdiff, int sym, float grad_scale, float* mse_d);
 /* The per-pair post-update MSEs of the LAST aefft_net_step_apply (fft_backproplib.cu:1463), to mse_d[L] (device), in stream order.
@@ -325,6 +353,9 @@ int aefft_net_step_apply(aefft_net* net, float del0, int maxdiff, int sym, float
  * step's all-reduce -- or by this call, whichever comes first.  A loop that logs the MSE every K steps calls this every K steps. */
 int aefft_net_last_mse(aefft_net* net, float* mse_d);
 int aefft_net_reset_momentum(aefft_net* net);
+/* The inertia weight alpha of backprop_gpu's update (backproplib.cu:392-396) on a spatial net; default 0.9 (autoencoder.cpp:89; the
+ * application changes it with keys 6 / 7).  AEFFT_EINVAL for alpha outside [0, 1] or for an FFT net (its update has no alpha). */
+int aefft_net_set_inertia(aefft_net* net, float alpha);
 
 /* ---- measurement ----------------------------------------------------------------------------- */
 /* Per-kernel HIP event timing on the context stream (bench.py's roofline figure).  With
