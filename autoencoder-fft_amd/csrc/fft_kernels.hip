@@ -26,6 +26,7 @@
 #include <hip/hip_ext.h>
 #include <math.h>
 #include <map>
+#include <mutex>
 #include <vector>
 
 namespace aefft {
@@ -520,15 +521,6 @@ __global__ __launch_bounds__(CW* N / 8) void inv_cols_kernel(const float2* __res
 // transform).  One kernel transforms ROWS (contiguous); the 2-D transforms go rows -> transpose -> rows -> transpose.  Even n in 8..1024.
 // MODE 0: complex rows -> complex rows;  1: real rows -> half spectra (n/2+1);  2: half spectra -> real rows (Hermitian extension on load,
 // imaginary parts of the self-conjugate bins ignored -- pocketfft / numpy.irfft semantics, as the power-of-two path).
-__device__ __forceinline__ float2 chirp(int j, int n, int dir)
-{
-    // exp(dir * i * pi * j^2 / n), the phase reduced exactly in integers: j^2 mod 2n
-    const unsigned q = ((unsigned)j * (unsigned)j) % (2u * (unsigned)n);
-    float sn, cs;
-    sincospif((float)q / (float)n, &sn, &cs);
-    return make_float2(cs, dir < 0 ? -sn : sn);
-}
-
 template <int M> struct BluCfg {
     static constexpr int T = M / 8;
     static constexpr int NT = T > 256 ? T : 256;
@@ -536,29 +528,9 @@ template <int M> struct BluCfg {
     static constexpr int PL = pad_len(M);
 };
 
-// spectrum of the chirp filter b[j] = conj(w[j]) (|j| < n, wrapped into M points), once per (n, M, DIR): bhat[M]
-template <int M>
-__global__ __launch_bounds__(BluCfg<M>::T) void bluestein_setup_kernel(float2* __restrict__ bhat, int n, int dir)
-{
-    constexpr int T = BluCfg<M>::T;
-    extern __shared__ float2 s[];
-    const int t = threadIdx.x;
-    FftTw<M, -1> tws;
-    tws.load(t);
-    for (int j = t; j < M; j += T) {
-        const int jj = j < n ? j : (M - j < n ? M - j : -1);
-        float2 v = make_float2(0.f, 0.f);
-        if (jj >= 0) { v = chirp(jj, n, dir); v.y = -v.y; }
-        s[pad_idx(j)] = v;
-    }
-    __syncthreads();
-    fft_lds<M, -1>(s, t, tws);
-    for (int j = t; j < M; j += T) bhat[j] = s[pad_idx(j)];
-}
-
 template <int M, int MODE>
-__global__ __launch_bounds__(BluCfg<M>::NT) void bluestein_rows_kernel(const void* __restrict__ in_, void* __restrict__ out_, const float2* __restrict__ bhat,
-                                                                        long nrows, int n, int dir, float scale)
+__global__ __launch_bounds__(BluCfg<M>::NT) void bluestein_rows_kernel(const void* __restrict__ in_, void* __restrict__ out_, const float2* __restrict__ tab,
+                                                                        long nrows, int n, float scale)
 {
     using Cfg = BluCfg<M>;
     constexpr int T = Cfg::T, NT = Cfg::NT, G = Cfg::G, PL = Cfg::PL;
@@ -570,6 +542,8 @@ __global__ __launch_bounds__(BluCfg<M>::NT) void bluestein_rows_kernel(const voi
     FftTw<M, +1> twi;
     twf.load(t); twi.load(t);
     float2* z = s + g * PL;
+    const float2* const bhat = tab;                 // (blu_table: the filter's spectrum [M], then the chirp [n])
+    const float2* const w = tab + M;
     const int nh = n / 2 + 1;
     for (int j = t; j < M; j += T) {
         float2 v = make_float2(0.f, 0.f);
@@ -581,7 +555,7 @@ __global__ __launch_bounds__(BluCfg<M>::NT) void bluestein_rows_kernel(const voi
                 if (j < nh) { v = X[j]; if (j == 0 || 2 * j == n) v.y = 0.f; }
                 else { v = X[n - j]; v.y = -v.y; }
             }
-            v = cmul(v, chirp(j, n, dir));
+            v = cmul(v, w[j]);
         }
         z[pad_idx(j)] = v;
     }
@@ -594,7 +568,7 @@ __global__ __launch_bounds__(BluCfg<M>::NT) void bluestein_rows_kernel(const voi
     const float sc = scale / (float)M;
     const int nout = MODE == 1 ? nh : n;
     for (int k = t; k < nout; k += T) {
-        float2 v = cmul(z[pad_idx(k)], chirp(k, n, dir));
+        float2 v = cmul(z[pad_idx(k)], w[k]);
         if (MODE == 2) reinterpret_cast<float*>(out_)[row * n + k] = v.x * sc;
         else reinterpret_cast<float2*>(out_)[row * nout + k] = make_float2(v.x * sc, v.y * sc);
     }
@@ -707,7 +681,8 @@ template <int N, bool FWD> static hipError_t cols_dispatch(const float2* a, floa
 // ---- any even size in 8..1024 (Bluestein) ----
 bool fft_size_supported_any(int n) { return fft_size_supported(n) || (n >= 8 && n <= 1024 && (n & 1) == 0); }
 static int blu_m(int n) { int m = 16; while (m < 2 * n - 1) m *= 2; return m; }
-// the chirp spectra, once per (device, n, DIR); they live for the life of the process (a few KB each)
+// the chirp tables, once per (device, n, DIR) under g_blu_mu (contexts on several threads share them); they live for the life of the
+// process (at most 24 KB each)
 struct BluKey { int dev, n, dir; bool operator<(const BluKey& o) const { return dev != o.dev ? dev < o.dev : (n != o.n ? n < o.n : dir < o.dir); } };
 #define AEFFT_M_SWITCH(m, CALL)                      \
     switch (m) {                                      \
@@ -721,33 +696,57 @@ struct BluKey { int dev, n, dir; bool operator<(const BluKey& o) const { return 
     case 2048: { constexpr int MM = 2048; CALL; }     \
     default: e = hipErrorInvalidValue;                \
     }
-template <int M> static hipError_t run_blu_setup(float2* bhat, int n, int dir, hipStream_t st)
+static std::mutex g_blu_mu;
+// [M] the spectrum of the chirp filter b[j] = conj(w[j]) (|j| < n, wrapped into M points), then [n] the chirp w[j] = exp(DIR i pi j^2 / n) itself,
+// both in double precision on the host (the phase reduced exactly in integers, j^2 mod 2n; a direct M-point DFT of the 2n - 1 non-zero taps)
+// and rounded once: a chirp evaluated in float carries ~4e-7 rad of phase error into each of its three products per axis, several times
+// the float32 transform's own error
+static std::vector<float2> blu_host_table(int n, int dir)
 {
-    bluestein_setup_kernel<M><<<1, BluCfg<M>::T, sizeof(float2) * pad_len(M), st>>>(bhat, n, dir);
-    return hipGetLastError();
+    const int M = blu_m(n);
+    std::vector<double> wr(n), wi(n), cr(M), ci(M);
+    for (int j = 0; j < n; ++j) {
+        const long q = ((long)j * j) % (2L * n);
+        wr[j] = cos(M_PI * (double)q / n); wi[j] = dir * sin(M_PI * (double)q / n);
+    }
+    for (int m = 0; m < M; ++m) { cr[m] = cos(2.0 * M_PI * m / M); ci[m] = -sin(2.0 * M_PI * m / M); }
+    std::vector<float2> t(M + n);
+    for (int k = 0; k < M; ++k) {
+        double ar = 0.0, ai = 0.0;
+        for (int j = 0; j < M; ++j) {
+            const int jj = j < n ? j : (M - j < n ? M - j : -1);
+            if (jj < 0) continue;
+            const double br = wr[jj], bi = -wi[jj];
+            const int m = (int)(((long)j * k) % M);
+            ar += br * cr[m] - bi * ci[m]; ai += br * ci[m] + bi * cr[m];
+        }
+        t[k] = make_float2((float)ar, (float)ai);
+    }
+    for (int j = 0; j < n; ++j) t[M + j] = make_float2((float)wr[j], (float)wi[j]);
+    return t;
 }
-static hipError_t blu_table(int n, int dir, hipStream_t st, const float2** out)
+static hipError_t blu_table(int n, int dir, const float2** out)
 {
     static std::map<BluKey, float2*> cache;
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;
     const BluKey key{dev, n, dir};
+    std::lock_guard<std::mutex> lock(g_blu_mu);
     auto it = cache.find(key);
     if (it == cache.end()) {
-        const int M = blu_m(n);
+        const std::vector<float2> host = blu_host_table(n, dir);
         float2* p = nullptr;
-        e = hipMalloc(&p, sizeof(float2) * M);
+        e = hipMalloc(&p, sizeof(float2) * host.size());
         if (e != hipSuccess) return e;
-        AEFFT_M_SWITCH(M, e = run_blu_setup<MM>(p, n, dir, st); break)
-        if (e == hipSuccess) e = hipStreamSynchronize(st);      // (once per size: the table must be complete before another stream uses it)
+        e = hipMemcpy(p, host.data(), sizeof(float2) * host.size(), hipMemcpyHostToDevice);      // (once per size, blocking: complete for every stream)
         if (e != hipSuccess) { (void)hipFree(p); return e; }
         it = cache.emplace(key, p).first;
     }
     *out = it->second;
     return hipSuccess;
 }
-template <int M, int MODE> static hipError_t run_blu_rows(const void* in, void* out, const float2* bhat, long nrows, int n, int dir, float scale, hipStream_t st)
+template <int M, int MODE> static hipError_t run_blu_rows(const void* in, void* out, const float2* tab, long nrows, int n, float scale, hipStream_t st)
 {
     using Cfg = BluCfg<M>;
     const size_t lds = sizeof(float2) * (size_t)Cfg::G * Cfg::PL;
@@ -755,25 +754,32 @@ template <int M, int MODE> static hipError_t run_blu_rows(const void* in, void* 
     if (e != hipSuccess) return e;
     const long blocks = (nrows + Cfg::G - 1) / Cfg::G;
     if (blocks >= (1L << 31)) return hipErrorInvalidValue;
-    bluestein_rows_kernel<M, MODE><<<dim3((unsigned)blocks), dim3(Cfg::NT), lds, st>>>(in, out, bhat, nrows, n, dir, scale);
+    bluestein_rows_kernel<M, MODE><<<dim3((unsigned)blocks), dim3(Cfg::NT), lds, st>>>(in, out, tab, nrows, n, scale);
     return hipGetLastError();
 }
 static hipError_t blu_rows(int mode, const void* in, void* out, long nrows, int n, int dir, float scale, hipStream_t st)
 {
-    const float2* bhat = nullptr;
-    hipError_t e = blu_table(n, dir, st, &bhat);
+    const float2* tab = nullptr;
+    hipError_t e = blu_table(n, dir, &tab);
     if (e != hipSuccess) return e;
     const int M = blu_m(n);
-    if (mode == 0) { AEFFT_M_SWITCH(M, e = (run_blu_rows<MM, 0>(in, out, bhat, nrows, n, dir, scale, st)); break) }
-    else if (mode == 1) { AEFFT_M_SWITCH(M, e = (run_blu_rows<MM, 1>(in, out, bhat, nrows, n, dir, scale, st)); break) }
-    else { AEFFT_M_SWITCH(M, e = (run_blu_rows<MM, 2>(in, out, bhat, nrows, n, dir, scale, st)); break) }
+    if (mode == 0) { AEFFT_M_SWITCH(M, e = (run_blu_rows<MM, 0>(in, out, tab, nrows, n, scale, st)); break) }
+    else if (mode == 1) { AEFFT_M_SWITCH(M, e = (run_blu_rows<MM, 1>(in, out, tab, nrows, n, scale, st)); break) }
+    else { AEFFT_M_SWITCH(M, e = (run_blu_rows<MM, 2>(in, out, tab, nrows, n, scale, st)); break) }
     return e;
 }
 static hipError_t transpose_c(const float2* in, float2* out, long planes, int R, int C, hipStream_t st)
 {
-    if (planes > 65535) return hipErrorInvalidValue;
-    transpose_c_kernel<<<dim3((C + 31) / 32, (R + 31) / 32, (unsigned)planes), 256, 0, st>>>(in, out, R, C);
-    return hipGetLastError();
+    // the plane index rides in grid.z (at most 65535): larger batches go as several launches
+    constexpr long ZMAX = 65535;
+    for (long p0 = 0; p0 < planes; p0 += ZMAX) {
+        const long np = planes - p0 < ZMAX ? planes - p0 : ZMAX;
+        const long off = p0 * R * (long)C;
+        transpose_c_kernel<<<dim3((C + 31) / 32, (R + 31) / 32, (unsigned)np), 256, 0, st>>>(in + off, out + off, R, C);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 // complex elements each of the two workspaces of the any-size transforms needs
 size_t fft_any_ws_elems(long planes, int Nx, int Ny) { return (size_t)planes * Nx * (Ny / 2 + 1); }

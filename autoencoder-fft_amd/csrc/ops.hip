@@ -82,6 +82,7 @@ int aefft::do_r2c(aefft_ctx* ctx, const float* x, float2* X, long planes, int Nx
     if ((!pow2_sizes(Nx, Ny) || !pow2_sizes(Nxs, Nys)) && !mixed_route(Nx, Ny)) {
         if (u8) return fail(ctx, AEFFT_EINVAL, "r2c: 8-bit frames need power-of-two sizes");
         RET_IF(chk_size_any(ctx, Nx, Ny));
+        if (Nx > 1024 || Ny > 1024) return fail(ctx, AEFFT_EINVAL, "r2c: a crop to a size that is not a power of two needs a grid of at most 1024 x 1024");
         if (!aligned16(x) || !aligned16(X)) return fail(ctx, AEFFT_EINVAL, "r2c: pointers must be 16-byte aligned");
         return do_r2c_any(ctx, x, X, planes, Nx, Ny, Nxs, Nys);
     }
@@ -111,6 +112,7 @@ int aefft::do_c2r(aefft_ctx* ctx, const float2* X, float* x, long planes, int Nx
 {
     if (!opin && (!pow2_sizes(Nx, Ny) || !pow2_sizes(Nxi, Nyi)) && !mixed_route(Nx, Ny)) {
         RET_IF(chk_size_any(ctx, Nx, Ny));
+        if (Nx > 1024 || Ny > 1024) return fail(ctx, AEFFT_EINVAL, "c2r: a zero-pad from a size that is not a power of two needs a grid of at most 1024 x 1024");
         if (!aligned16(x) || !aligned16(X)) return fail(ctx, AEFFT_EINVAL, "c2r: pointers must be 16-byte aligned");
         return do_c2r_any(ctx, X, x, planes, Nxi, Nyi, Nx, Ny, scale);
     }
