@@ -24,7 +24,7 @@ OK, EINVAL, EHIP, ENOMEM, ESTATE = 0, 1, 2, 3, 4
 FLAGS = {n: 1 << i for i, n in enumerate(
     ["NOLAZY", "NOCOMPACT", "NOQPATH", "NOFUSEMSE", "NOGROUP", "NOMFMA", "NOGFWD", "NOOVERLAP", "NOFUSECROP", "GTAPS",
      "NOPREFETCH", "NODEFER", "NOTILEDSPATIAL", "NOFAST", "NOSPLITK", "POISON", "NOOPFORM", "NOCHAIN", "NOFUSEUPD", "NOAHEAD", "NORCORR", "NOLAZYMSE", "SMALLOVERLAP", "CHAINMSE",
-     "CHIRPZ"])}
+     "CHIRPZ", "NOPRUNESMOOTH"])}
 NET_SMOOTH_SIZES = 1 << 0   # include/aefft.h AEFFT_NET_SMOOTH_SIZES (aefft_net_create_ex)
 NET_SPATIAL = 1 << 1        # include/aefft.h AEFFT_NET_SPATIAL: the coordinate-space training mode as a resident net
 

@@ -125,7 +125,14 @@ hipError_t launch_bias_grad_group(BiasGradGroup& g, hipStream_t st);
 // ---- pruned_kernels.hip ----------------------------------------------------------------
 // Kernel-support-pruned transforms: only Nk x Nl taps are non-zero going forward / needed coming back,
 // so pad+R2C and C2R+shrink become direct DFT evaluations (fft.cu:1219-1226 and :1274-1282 fused).
+// Grids: both axes powers of two (the TW_N-point twiddle table) or smooth (even, 10..2048, no prime factor above 5: an N-point phase table
+// per (device, axis size), built on first use or by pruned_prepare), Ny/2+1 <= 320.  pruned_supported: the route is taken (false on a grid
+// with a smooth axis under AEFFT_F_NOPRUNESMOOTH); pruned_geometry: the grid has the route at all -- what buffers are sized by, the switch
+// may change on a live net; pruned_pow2: neither axis needs a table of its own (the operator form's kernels take nothing else).
 bool pruned_supported(int Nk, int Nl, int Nx, int Ny);
+bool pruned_geometry(int Nk, int Nl, int Nx, int Ny);
+bool pruned_pow2(int Nx, int Ny);
+hipError_t pruned_prepare(int Nx, int Ny);     // the phase tables of the current device for this grid: built here instead of inside a step
 hipError_t launch_kspec(const float* k, float2* K, const float2* tw, long planes, int Nx, int Ny, int Nk, int Nl, hipStream_t st);
 hipError_t launch_kgrad(const float2* D, float* g, float* part /*workspace: kgrad_partial_floats()*/, const float2* tw, long planes, int Nx, int Ny, int Nk, int Nl, float scale, hipStream_t st);
 size_t kgrad_partial_floats(long planes, int Nx, int Ny, int Nk, int Nl);

@@ -128,8 +128,10 @@ static int net_create(aefft_ctx* ctx, const aefft_net_desc* d, unsigned opts, ae
         if ((rc = net_alloc_t(n, &q.S, (size_t)q.dD * q.dD * q.P)) || (rc = net_alloc_t(n, &q.G, (size_t)q.dD * q.dD * q.P)) || (rc = net_alloc_t(n, &q.dc, 2 * W))) break;
         q.df = q.dc + W;
         q.part = nullptr;
-        if (pruned_supported(q.Nk, q.Nl, q.Nx, q.Ny)) { if ((rc = net_alloc_t(n, &q.part, kgrad_partial_floats(2L * q.dM * q.dD, q.Nx, q.Ny, q.Nk, q.Nl)))) break; }
-        else n->pruned = false;
+        // (sized by what the grid HAS, not by what AEFFT_F_NOPRUNESMOOTH selects at this moment: the switch may change on a live net, so a grid
+        // with a smooth axis owns both the row chunks' partial sums and the full route's real planes)
+        if (pruned_geometry(q.Nk, q.Nl, q.Nx, q.Ny)) { if ((rc = net_alloc_t(n, &q.part, kgrad_partial_floats(2L * q.dM * q.dD, q.Nx, q.Ny, q.Nk, q.Nl)))) break; }
+        if (!pruned_geometry(q.Nk, q.Nl, q.Nx, q.Ny) || !pruned_pow2(q.Nx, q.Ny)) n->pruned = false;
         maxS = std::max(maxS, (size_t)q.dD * q.dD * q.P); maxBDP = std::max(maxBDP, BDP); maxW = std::max(maxW, W);
         esoff[l] = soff; soff += 2 * (size_t)q.dD;
         maxReal = std::max(maxReal, (size_t)q.dM * q.dD * q.Nx * q.Ny);
@@ -196,6 +198,9 @@ static int net_create(aefft_ctx* ctx, const aefft_net_desc* d, unsigned opts, ae
         for (const Pair& q : n->pr) { sizes.push_back(q.Nx); sizes.push_back(q.Ny); }
         for (int m : sizes) if (fft_size_mixed(m) && (e = fft_mixed_prepare(m)) != hipSuccess) break;
         if (e != hipSuccess) { aefft_net_destroy(n); return fail(ctx, AEFFT_EHIP, "mixed-radix twiddle tables", e); }
+        // ... and the phase tables of the pruned kernel transforms on those grids
+        for (const Pair& q : n->pr) if (pruned_geometry(q.Nk, q.Nl, q.Nx, q.Ny) && (e = pruned_prepare(q.Nx, q.Ny)) != hipSuccess) break;
+        if (e != hipSuccess) { aefft_net_destroy(n); return fail(ctx, AEFFT_EHIP, "pruned transforms' phase tables", e); }
     }
     if (ensure_aux(ctx) != AEFFT_OK) { aefft_net_destroy(n); return AEFFT_EHIP; }
     *out = n;

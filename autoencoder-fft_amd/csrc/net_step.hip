@@ -120,7 +120,9 @@ static bool op_eligible(const aefft_net* n)
     if (flag(AEFFT_F_NOOPFORM) || flag(AEFFT_F_NOQPATH) || !n->A0hat || n->L > 8) return false;
     const Pair& q0 = n->pr[0];
     if (q0.Nk != q0.Nl || (q0.Nk != 3 && q0.Nk != 5)) return false;
-    for (const Pair& q : n->pr) if (q.Nk != q0.Nk || q.Nl != q0.Nl || !q.Q || !pruned_supported(q.Nk, q.Nl, q.Nx, q.Ny)) return false;
+    // (power-of-two grids only: the operator form's own kernels index the TW_N-point table, phase_tw / map_up_*; a smooth net has the
+    // pruned transforms in its per-frame step)
+    for (const Pair& q : n->pr) if (q.Nk != q0.Nk || q.Nl != q0.Nl || !q.Q || !pruned_pow2(q.Nx, q.Ny) || !pruned_supported(q.Nk, q.Nl, q.Nx, q.Ny)) return false;
     // channel counts the operator-form kernels' LDS tiles take (msgrad_kernel: 2*OPC*dD*8 complex; opmse: OPC*(dD+dM)*4 complex): a
     // launch declined in the middle of step_apply would leave a fused update half applied, so the step form is decided here
     for (const Pair& q : n->pr) if (q.dD > 256 || q.dM > 512 || q.dD + q.dM > 1024) return false;
@@ -521,7 +523,7 @@ static int shrink_dcdf(aefft_net* n, const Pair& q)
     aefft_ctx* ctx = n->ctx;
     const GradSeg gs = q.grads(n->grad);
     const long planes = (long)q.dM * q.dD;
-    if (q.part) return do_c2r_shrink(ctx, q.dc, gs.dck, nullptr, q.part, 2 * planes, q.Nx, q.Ny, q.Nk, q.Nl);   // dc|df -> dck|dfk, one launch
+    if (q.part && pruned_supported(q.Nk, q.Nl, q.Nx, q.Ny)) return do_c2r_shrink(ctx, q.dc, gs.dck, nullptr, q.part, 2 * planes, q.Nx, q.Ny, q.Nk, q.Nl);   // dc|df -> dck|dfk, one launch
     RET_IF(do_c2r_shrink(ctx, q.dc, gs.dck, n->real, nullptr, planes, q.Nx, q.Ny, q.Nk, q.Nl));
     return do_c2r_shrink(ctx, q.df, gs.dfk, n->real, nullptr, planes, q.Nx, q.Ny, q.Nk, q.Nl);
 }

@@ -15,13 +15,64 @@
 //
 // Row and column phase tables (Nx*Nk and Nyr*Nl complex) are built per workgroup in LDS from the
 // global twiddle table, so each bin costs one 8-byte global access plus LDS reads.
+#include "../../include/aefft.h"
 #include "internal.h"
 #include "device_util.h"
 #include "opform_device.h"
 #include "update_device.h"
 #include <algorithm>
+#include <map>
+#include <math.h>
+#include <mutex>
+#include <vector>
 
 namespace aefft {
+
+// Where a phase e^{-2 pi i pos*off / N} comes from.  The pruned transforms exist on power-of-two and on smooth axes (even, no prime
+// factor above 5: 640, 480, 360 ...), and the two kinds index different tables:
+//   PhasePow2 : the TW_N-point table of the FFT passes, entry ((pos*off) & (N-1)) * (TW_N/N) -- N divides TW_N;
+//   PhaseMod  : one N-point table per axis (phase_table below), entry (pos*off) mod N.  |off| <= 4 (the T = 9 taps of the Q path) and
+//               pos < N, so the residue is a bounded compare-and-subtract -- no '%' (hundreds of cycles, see `phase`); every phase is
+//               gathered once per workgroup or thread (rowph / colph in LDS, kspec_col_phases), never inside a row or column loop.
+// The kernels are templates on the source: the power-of-two instantiations keep their parameter list and their instruction stream,
+// and no run-time select between two table pointers exists anywhere (such a select compiles to flat loads).
+__device__ __forceinline__ float2 phase(const float2* tw, int pos, int off, int N, float sign);
+__device__ __forceinline__ int mod4(int v, int N)        // v mod N for 0 <= v < 4N
+{
+    if (v >= 2 * N) v -= 2 * N;
+    if (v >= N) v -= N;
+    return v;
+}
+struct PhasePow2 {
+    const float2* tw;
+    __device__ __forceinline__ float2 row(int pos, int off, int N) const { return phase_tw(tw, pos, off, N); }     // off > 0
+    __device__ __forceinline__ float2 col(int pos, int off, int N) const { return phase_tw(tw, pos, off, N); }
+    __device__ __forceinline__ float2 rowc(int pos, int off, int N) const { return phase(tw, pos, off, N, -1.f); }   // conjugate; off of either sign
+    __device__ __forceinline__ float2 colc(int pos, int off, int N) const { return phase(tw, pos, off, N, -1.f); }
+    static __device__ __forceinline__ int wrap(int pos, int N) { return pos & (N - 1); }                             // rows past a short last chunk: any valid row
+    static constexpr bool mod = false;
+};
+struct PhaseMod {
+    const float2* tx; const float2* ty;       // exp(-2 pi i r / Nx), r < Nx | exp(-2 pi i r / Ny), r < Ny
+    static __device__ __forceinline__ float2 conj_of(const float2* t, int pos, int off, int N)
+    {
+        float2 w = t[mod4(pos * (off < 0 ? -off : off), N)];
+        if (off >= 0) w.y = -w.y;                          // e^{+2 pi i pos*off/N}: the conjugate of the entry for off > 0, the entry of |off| for off < 0
+        return w;
+    }
+    __device__ __forceinline__ float2 row(int pos, int off, int N) const { return tx[mod4(pos * off, N)]; }
+    __device__ __forceinline__ float2 col(int pos, int off, int N) const { return ty[mod4(pos * off, N)]; }
+    __device__ __forceinline__ float2 rowc(int pos, int off, int N) const { return conj_of(tx, pos, off, N); }
+    __device__ __forceinline__ float2 colc(int pos, int off, int N) const { return conj_of(ty, pos, off, N); }
+    static __device__ __forceinline__ int wrap(int pos, int N) { return min(pos, N - 1); }
+    static constexpr bool mod = true;
+};
+// what a launch carries: the one table pointer as before, or the per-problem tables of a launch with a smooth axis (by value: kernel argument)
+struct ModTabs { const float2* x[8]; const float2* y[8]; };
+__device__ __forceinline__ PhasePow2 phase_src(const float2* tw, int) { return PhasePow2{tw}; }
+__device__ __forceinline__ PhaseMod phase_src(const ModTabs& t, int p) { return PhaseMod{t.x[p], t.y[p]}; }
+template <bool MOD> struct TwArg { typedef const float2* __restrict__ type; };
+template <> struct TwArg<true> { typedef ModTabs type; };
 
 __device__ __forceinline__ float2 phase(const float2* tw, int pos, int off, int N, float sign)
 {
@@ -42,12 +93,12 @@ __device__ __forceinline__ float2 phase(const float2* tw, int pos, int off, int 
 // grid lands: the chain's planar tiles read nothing else); NxB == Nx: the plane's own grid.
 // the column phases of thread column j (offsets 1 .. NL/2): gathers from the global twiddle table -- a memory round trip, so the callers ask for
 // them BEFORE they stage the taps (the G' workgroups had it behind their tap products: 1.5-2 us of every such workgroup)
-template <int NL>
-__device__ __forceinline__ void kspec_col_phases(const float2* __restrict__ tw, int j, int Ny, int NyB, float2 (&cp)[NL / 2 > 0 ? NL / 2 : 1])
+template <int NL, class PS>
+__device__ __forceinline__ void kspec_col_phases(const PS& ps, int j, int Ny, int NyB, float2 (&cp)[NL / 2 > 0 ? NL / 2 : 1])
 {
     const int jB = map_up_col(j, Ny, NyB);
 #pragma unroll
-    for (int l = 0; l < NL / 2; ++l) cp[l] = phase_tw(tw, jB, l + 1, NyB);
+    for (int l = 0; l < NL / 2; ++l) cp[l] = ps.col(jB, l + 1, NyB);
 }
 template <int NK, int NL>
 __device__ __forceinline__ void kspec_rows(const float* __restrict__ c, float2* __restrict__ dst, const float2 (&cp)[NL / 2 > 0 ? NL / 2 : 1], const float2* __restrict__ rowph,
@@ -188,9 +239,9 @@ __device__ __forceinline__ void gtaps_stage(const GtapSrc& gs, const TapUpd& upd
     }
 }
 
-template <int NK, int NL>
+template <int NK, int NL, class PS>
 __device__ __forceinline__ void kspec_body(const float* __restrict__ kern, float2* __restrict__ K,
-                                                    const float2* __restrict__ tw, long planes, int Nx, int Ny,
+                                                    const PS& ps, long planes, int Nx, int Ny,
                                                     int rows_per_chunk, int ppb, int bx, int by, float2* lds, const TapUpd& upd = TapUpd{},
                                                     int NxB = 0, int NyB = 0)
 {
@@ -208,11 +259,11 @@ __device__ __forceinline__ void kspec_body(const float* __restrict__ kern, float
     const int nrows = min(rows_per_chunk, Nx - i0);
     const int pl = threadIdx.x / Nyr, j = threadIdx.x - pl * Nyr;
     float2 cp[NL / 2 > 0 ? NL / 2 : 1];
-    kspec_col_phases<NL>(tw, j, Ny, NyB, cp);
+    kspec_col_phases<NL>(ps, j, Ny, NyB, cp);
     const bool one_trip = nrows * H <= (int)blockDim.x;          // (the row phases: requested here, stored behind the taps' loads -- one round trip for both)
     float2 rp0 = make_float2(0.f, 0.f);
-    if (one_trip) { if ((int)threadIdx.x < nrows * H) rp0 = phase_tw(tw, map_up_row(i0 + threadIdx.x / H, Nx, NxB), threadIdx.x % H + 1, NxB); }
-    else for (int t = threadIdx.x; t < nrows * H; t += blockDim.x) rowph[t] = phase_tw(tw, map_up_row(i0 + t / H, Nx, NxB), t % H + 1, NxB);
+    if (one_trip) { if ((int)threadIdx.x < nrows * H) rp0 = ps.row(map_up_row(i0 + threadIdx.x / H, Nx, NxB), threadIdx.x % H + 1, NxB); }
+    else for (int t = threadIdx.x; t < nrows * H; t += blockDim.x) rowph[t] = ps.row(map_up_row(i0 + t / H, Nx, NxB), t % H + 1, NxB);
     {
         // (through the pending update when there is one -- uniform --: w - clip_step(g, D), TapUpd)
         const long e0 = (long)bx * ppb * (NK * NL);
@@ -242,8 +293,8 @@ __device__ __forceinline__ void kspec_body(const float* __restrict__ kern, float
 }
 
 // the G' form of kspec_body: workgroup = (d', tile of ppb d's) x row chunk; the taps come from gtaps_stage
-template <int NK, int MU>
-__device__ __forceinline__ void gspec_gbody(const GtapSrc& gs, float2* __restrict__ G, const float2* __restrict__ tw, int Nx, int Ny,
+template <int NK, int MU, class PS>
+__device__ __forceinline__ void gspec_gbody(const GtapSrc& gs, float2* __restrict__ G, const PS& ps, int Nx, int Ny,
                                             int rows_per_chunk, int ppb, int bx, int by, float2* lds, const TapUpd& upd)
 {
     constexpr int T = 2 * NK - 1, TT = T * T, H = T / 2;
@@ -255,13 +306,13 @@ __device__ __forceinline__ void gspec_gbody(const GtapSrc& gs, float2* __restric
     const int nrows = min(rows_per_chunk, Nx - i0);
     const int pl = threadIdx.x / Nyr, j = threadIdx.x - pl * Nyr;
     float2 cp[H];
-    kspec_col_phases<T>(tw, j, Ny, Ny, cp);
+    kspec_col_phases<T>(ps, j, Ny, Ny, cp);
     // the row phases: requested here, stored BEHIND the tap stage's loads (a load -> LDS store in front of them is a round trip of its own:
     // the first barrier of these workgroups came at 5.8-7 us against 3.8 for the plain transform's)
     const bool one_trip = nrows * H <= (int)blockDim.x;
     float2 rp0 = make_float2(0.f, 0.f);
-    if (one_trip) { if ((int)threadIdx.x < nrows * H) rp0 = phase_tw(tw, i0 + threadIdx.x / H, threadIdx.x % H + 1, Nx); }
-    else for (int t = threadIdx.x; t < nrows * H; t += blockDim.x) rowph[t] = phase_tw(tw, i0 + t / H, t % H + 1, Nx);
+    if (one_trip) { if ((int)threadIdx.x < nrows * H) rp0 = ps.row(i0 + threadIdx.x / H, threadIdx.x % H + 1, Nx); }
+    else for (int t = threadIdx.x; t < nrows * H; t += blockDim.x) rowph[t] = ps.row(i0 + t / H, t % H + 1, Nx);
     const int tiles = (gs.dD + ppb - 1) / ppb;
     const int dp = bx / tiles, d0 = (bx - dp * tiles) * ppb;
     const int np = min(ppb, gs.dD - d0);
@@ -274,21 +325,21 @@ __device__ __forceinline__ void gspec_gbody(const GtapSrc& gs, float2* __restric
     kspec_rows<T, T>(taps_s + pl * TT, G + (plane * Nx + i0) * (long)Nyr + j, cp, rowph, Nyr, nrows);
 }
 
-template <int NK, int NL>
+template <int NK, int NL, bool MOD>
 __global__ __launch_bounds__(320) void kspec_kernel(const float* __restrict__ kern, float2* __restrict__ K,
-                                                    const float2* __restrict__ tw, long planes, int Nx, int Ny,
+                                                    const typename TwArg<MOD>::type tw, long planes, int Nx, int Ny,
                                                     int rows_per_chunk, int ppb)
 {
     extern __shared__ float2 lds[];
-    kspec_body<NK, NL>(kern, K, tw, planes, Nx, Ny, rows_per_chunk, ppb, blockIdx.x, blockIdx.y, lds);
+    kspec_body<NK, NL>(kern, K, phase_src(tw, 0), planes, Nx, Ny, rows_per_chunk, ppb, blockIdx.x, blockIdx.y, lds);
 }
 
 // all pairs' kernel spectra in one launch: problem p owns workgroups [start[p], start[p+1]), plane groups fastest
 #ifndef AEFFT_X_KSPEC_W
 #define AEFFT_X_KSPEC_W 1
 #endif
-template <int NK, int NL, int MU>
-__global__ __launch_bounds__(320, AEFFT_X_KSPEC_W) void kspec_group_kernel(const PrunedGroup g, const float2* __restrict__ tw, const PackArgs pk, const BiasUpdGroup bu, const int nbias_start)
+template <int NK, int NL, int MU, bool MOD>
+__global__ __launch_bounds__(320, AEFFT_X_KSPEC_W) void kspec_group_kernel(const PrunedGroup g, const typename TwArg<MOD>::type tw, const PackArgs pk, const BiasUpdGroup bu, const int nbias_start)
 {
     AEFFT_WGTIME(3);
     extern __shared__ float2 lds[];
@@ -302,7 +353,8 @@ __global__ __launch_bounds__(320, AEFFT_X_KSPEC_W) void kspec_group_kernel(const
     }
     if ((int)blockIdx.x >= g.start[g.n]) {
         // trailing workgroups: the bin-major copy of the spectra for the operator chain (opform_device.h), from the same taps
-        if constexpr (NK == NL && (NK == 3 || NK == 5)) {
+        // (the operator form's record: power-of-two grids only, the launcher sends none with MOD)
+        if constexpr (!MOD && NK == NL && (NK == 3 || NK == 5)) {
             const int lin = blockIdx.x - g.start[g.n];
             kspec_packed_body<NK>(pk, lin % pk.nblk, lin / pk.nblk, lds);
         }
@@ -315,11 +367,11 @@ __global__ __launch_bounds__(320, AEFFT_X_KSPEC_W) void kspec_group_kernel(const
     const PrunedProb& q = g.q[p];
     if constexpr (NK == NL && (NK == 3 || NK == 5)) {
         if (g.gsrc[p].f) {                                // (uniform) a G' problem: the (2NK-1)^2 taps are formed in the workgroup
-            gspec_gbody<NK, MU>(g.gsrc[p], static_cast<float2*>(q.dst), tw, q.Nx, q.Ny, g.rows[p], g.ppb[p], lin % g.pblocks[p], lin / g.pblocks[p], lds, g.upd[p]);
+            gspec_gbody<NK, MU>(g.gsrc[p], static_cast<float2*>(q.dst), phase_src(tw, p), q.Nx, q.Ny, g.rows[p], g.ppb[p], lin % g.pblocks[p], lin / g.pblocks[p], lds, g.upd[p]);
             return;
         }
     }
-    kspec_body<NK, NL>(static_cast<const float*>(q.src), static_cast<float2*>(q.dst), tw, q.planes, q.Nx, q.Ny, g.rows[p], g.ppb[p],
+    kspec_body<NK, NL>(static_cast<const float*>(q.src), static_cast<float2*>(q.dst), phase_src(tw, p), q.planes, q.Nx, q.Ny, g.rows[p], g.ppb[p],
                        lin % g.pblocks[p], lin / g.pblocks[p], lds, g.upd[p], q.NxB, q.NyB);
 }
 
@@ -327,17 +379,20 @@ __global__ __launch_bounds__(320, AEFFT_X_KSPEC_W) void kspec_group_kernel(const
 //   t_k[j]   = sum_i D[i][j] * e^{+2 pi i i*kap_k/Nx}                  (row phases: LDS broadcast reads; D read once, coalesced)
 //   g[k][l] += w_j * Re( t_k[j] * e^{+2 pi i j*lam_l/Ny} )              (summed over the plane's columns through LDS, fixed order)
 // Output: part[plane][chunk][NK*NL] (summed over chunks by ksum_kernel when chunks > 1).  Deterministic.
-template <int NK, int NL>
+template <int NK, int NL, class PS>
 __device__ __forceinline__ void kgrad_body(const float2* __restrict__ D, float* __restrict__ part,
-                                                    const float2* __restrict__ tw, long planes, int Nx, int Ny, int RB, int ppb, float scale,
+                                                    const PS& ps, long planes, int Nx, int Ny, int RBc, int ppb, float scale,
                                                     int bx, int chunk, int nchunks, float2* lds)
 {
     const int Nyr = Ny / 2 + 1;
     const int nthr = blockDim.x;
-    float2* rowph = lds;                                            // [RB][NK]
-    float* contrib = reinterpret_cast<float*>(rowph + RB * NK);     // [NK*NL][nthr]
-    const int i0 = chunk * RB;
-    for (int t = threadIdx.x; t < RB * NK; t += nthr) rowph[t] = phase(tw, i0 + t / NK, t % NK - NK / 2, Nx, -1.f);
+    float2* rowph = lds;                                            // [RBc][NK]
+    float* contrib = reinterpret_cast<float*>(rowph + RBc * NK);    // [NK*NL][nthr]
+    const int i0 = chunk * RBc;
+    // rows of this chunk: RBc = ceil(Nx / chunks), so on an Nx that the chunk count does not divide (90 rows in 4 chunks of 23) the last
+    // chunk is short; a power of two always divides
+    const int RB = PS::mod ? min(RBc, Nx - i0) : RBc;
+    for (int t = threadIdx.x; t < RB * NK; t += nthr) rowph[t] = ps.rowc(i0 + t / NK, t % NK - NK / 2, Nx);
     __syncthreads();
     const int pl = threadIdx.x / Nyr, j = threadIdx.x - pl * Nyr;
     const long plane = (long)bx * ppb + pl;
@@ -388,7 +443,7 @@ __device__ __forceinline__ void kgrad_body(const float2* __restrict__ D, float* 
         const float wj = (j == 0 || j == Ny / 2) ? 1.f : 2.f;
 #pragma unroll
         for (int l = 0; l < NL; ++l) {
-            const float2 cp = phase(tw, j, l - NL / 2, Ny, -1.f);
+            const float2 cp = ps.colc(j, l - NL / 2, Ny);
 #pragma unroll
             for (int k = 0; k < NK; ++k) contrib[(k * NL + l) * nthr + threadIdx.x] = wj * (t[k].x * cp.x - t[k].y * cp.y);
         }
@@ -404,12 +459,12 @@ __device__ __forceinline__ void kgrad_body(const float2* __restrict__ D, float* 
     }
 }
 
-template <int NK, int NL>
+template <int NK, int NL, bool MOD>
 __global__ __launch_bounds__(320) void kgrad_kernel(const float2* __restrict__ D, float* __restrict__ part,
-                                                    const float2* __restrict__ tw, long planes, int Nx, int Ny, int RB, int ppb, float scale)
+                                                    const typename TwArg<MOD>::type tw, long planes, int Nx, int Ny, int RB, int ppb, float scale)
 {
     extern __shared__ float2 lds[];
-    kgrad_body<NK, NL>(D, part, tw, planes, Nx, Ny, RB, ppb, scale, blockIdx.x, blockIdx.y, gridDim.y, lds);
+    kgrad_body<NK, NL>(D, part, phase_src(tw, 0), planes, Nx, Ny, RB, ppb, scale, blockIdx.x, blockIdx.y, gridDim.y, lds);
 }
 
 // Grouped form: all pairs' pruned inverse transforms in ONE launch.  A workgroup of NT threads owns ppb planes x one chunk of
@@ -418,8 +473,8 @@ __global__ __launch_bounds__(320) void kgrad_kernel(const float2* __restrict__ D
 // the NEXT kernel adds them in chunk order while staging (an in-launch combine by the last workgroup to arrive was measured at
 // 3.6x the whole kernel: its agent-scope release writes back the XCD's L2, which is full of freshly written S).
 // The global loads of the first batch are issued BEFORE the phase tables are built: the table gathers ride in their shadow.
-template <int NK, int NL, int NT>
-__device__ __forceinline__ void kgrad_sliced_body(const float2* __restrict__ D, float* __restrict__ g, const float2* __restrict__ tw,
+template <int NK, int NL, int NT, class PS>
+__device__ __forceinline__ void kgrad_sliced_body(const float2* __restrict__ D, float* __restrict__ g, const PS& ps,
                                                   long planes, int Nx, int Ny, int ppb, int S, int RB, int nchunks, float scale,
                                                   int bx, int chunk, float2* lds)
 {
@@ -450,7 +505,7 @@ __device__ __forceinline__ void kgrad_sliced_body(const float2* __restrict__ D, 
     for (int t0 = 0; t0 < CR * H; t0 += NT * 4) {
         float2 v[4];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) { const int t = min(t0 + u * NT + (int)threadIdx.x, CR * H - 1); v[u] = phase(tw, (r0 + t / H) & (Nx - 1), t % H + 1, Nx, -1.f); }
+        for (int u = 0; u < 4; ++u) { const int t = min(t0 + u * NT + (int)threadIdx.x, CR * H - 1); v[u] = ps.rowc(PS::wrap(r0 + t / H, Nx), t % H + 1, Nx); }
 #pragma unroll
         for (int u = 0; u < 4; ++u) { const int t = t0 + u * NT + threadIdx.x; if (t < CR * H) rowph[t] = v[u]; }
     }
@@ -459,7 +514,7 @@ __device__ __forceinline__ void kgrad_sliced_body(const float2* __restrict__ D, 
     for (int t0 = 0; t0 < Nyr * NLc; t0 += NT * 3) {
         float2 v[3];
 #pragma unroll
-        for (int u = 0; u < 3; ++u) { const int t = min(t0 + u * NT + (int)threadIdx.x, Nyr * NLc - 1); v[u] = phase(tw, t / NLc, t % NLc, Ny, -1.f); }
+        for (int u = 0; u < 3; ++u) { const int t = min(t0 + u * NT + (int)threadIdx.x, Nyr * NLc - 1); v[u] = ps.colc(t / NLc, t % NLc, Ny); }
 #pragma unroll
         for (int u = 0; u < 3; ++u) { const int t = t0 + u * NT + threadIdx.x; if (t < Nyr * NLc) colph[(t / NLc) * NL + HLc + t % NLc] = v[u]; }
     }
@@ -591,11 +646,11 @@ __device__ __forceinline__ void kgrad_sliced_body(const float2* __restrict__ D, 
     }
 }
 
-template <int NK, int NL, int NT>
+template <int NK, int NL, int NT, bool MOD>
 #ifndef AEFFT_X_KGRAD_W
 #define AEFFT_X_KGRAD_W 1
 #endif
-__global__ __launch_bounds__(NT, AEFFT_X_KGRAD_W) void kgrad_group_kernel(const PrunedGroup g, const float2* __restrict__ tw, const BiasGradGroup bg)
+__global__ __launch_bounds__(NT, AEFFT_X_KGRAD_W) void kgrad_group_kernel(const PrunedGroup g, const typename TwArg<MOD>::type tw, const BiasGradGroup bg)
 {
     AEFFT_WGTIME(1);
     extern __shared__ float2 lds[];
@@ -614,7 +669,7 @@ __global__ __launch_bounds__(NT, AEFFT_X_KGRAD_W) void kgrad_group_kernel(const 
     for (int i = 1; i < 8; ++i) if (i < g.n && (int)blockIdx.x >= g.start[i]) p = i;
     const PrunedProb& q = g.q[p];
     const int lin = blockIdx.x - g.start[p];
-    kgrad_sliced_body<NK, NL, NT>(static_cast<const float2*>(q.src), static_cast<float*>(q.dst), tw, q.planes, q.Nx, q.Ny, g.ppb[p], g.rows[p],
+    kgrad_sliced_body<NK, NL, NT>(static_cast<const float2*>(q.src), static_cast<float*>(q.dst), phase_src(tw, p), q.planes, q.Nx, q.Ny, g.ppb[p], g.rows[p],
                                   g.rb[p], g.chunks[p], q.scale, lin % g.pblocks[p], lin / g.pblocks[p], lds);
 }
 
@@ -640,8 +695,9 @@ static void kgrad_geom(long planes, int Nx, int Ny, int* RB, int* ppb, int* thre
     const long pblocks = (planes + *ppb - 1) / *ppb;
     int chunks = 1;       // row chunks cost a second (ksum) launch: only when one workgroup per plane group would starve the chip
     if (pblocks < 96) while (pblocks * chunks < 256 && Nx / (chunks * 2) >= 16) chunks *= 2;
-    *RB = Nx / chunks;
+    *RB = (Nx + chunks - 1) / chunks;       // by ceiling: the last chunk is short where `chunks` does not divide Nx (kgrad_chunks counts them)
 }
+static int kgrad_chunks(int Nx, int RB) { return (Nx + RB - 1) / RB; }
 static size_t kgrad_lds(long planes, int Nx, int Ny, int Nk, int Nl)
 {
     int RB, ppb, thr;
@@ -652,19 +708,89 @@ size_t kgrad_partial_floats(long planes, int Nx, int Ny, int Nk, int Nl)
 {
     int RB, ppb, thr;
     kgrad_geom(planes, Nx, Ny, &RB, &ppb, &thr);
-    return (size_t)planes * (Nx / RB) * Nk * Nl;
+    return (size_t)planes * kgrad_chunks(Nx, RB) * Nk * Nl;
 }
 
-bool pruned_supported(int Nk, int Nl, int Nx, int Ny)
+// ---- the N-point phase tables of smooth axes ------------------------------------------------------------------------------------
+static bool axis_pow2(int n) { return n > 0 && n <= TW_N && (TW_N % n) == 0; }
+// an axis the pruned transforms take: a power of two (the TW_N-point table) or a smooth size (its own table)
+static bool axis_ok(int n) { return axis_pow2(n) || fft_size_smooth(n); }
+static bool grid_mod(int Nx, int Ny) { return !axis_pow2(Nx) || !axis_pow2(Ny); }
+
+struct PhKey { int dev, n; bool operator<(const PhKey& o) const { return dev != o.dev ? dev < o.dev : n < o.n; } };
+static std::mutex g_ph_mu;
+static std::map<PhKey, float2*> g_ph_tab;     // per (device, n) for the life of the process: exp(-2 pi i r / n), r < n
+// the table of the current device, built on first use (double precision on the host, blocking upload); lookup and insert under one lock
+static hipError_t phase_table(int n, const float2** out)
+{
+    if (n < 1 || n > TW_N) return hipErrorInvalidValue;
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    std::lock_guard<std::mutex> lock(g_ph_mu);
+    auto it = g_ph_tab.find(PhKey{dev, n});
+    if (it == g_ph_tab.end()) {
+        std::vector<float2> host(n);
+        for (int r = 0; r < n; ++r) {
+            const double a = -2.0 * M_PI * (double)r / (double)n;
+            host[r] = make_float2((float)cos(a), (float)sin(a));
+        }
+        float2* d = nullptr;
+        e = hipMalloc(&d, sizeof(float2) * host.size());
+        if (e != hipSuccess) return e;
+        e = hipMemcpy(d, host.data(), sizeof(float2) * host.size(), hipMemcpyHostToDevice);
+        if (e != hipSuccess) { (void)hipFree(d); return e; }
+        it = g_ph_tab.emplace(PhKey{dev, n}, d).first;
+    }
+    *out = it->second;
+    return hipSuccess;
+}
+// the tables of problem p of a launch with a smooth axis: BOTH axes take N-point tables there (640 x 512: the 512 columns too)
+static hipError_t mod_tabs(ModTabs& t, int p, int Nx, int Ny)
+{
+    const hipError_t e = phase_table(Nx, &t.x[p]);
+    return e == hipSuccess ? phase_table(Ny, &t.y[p]) : e;
+}
+hipError_t pruned_prepare(int Nx, int Ny)
+{
+    if (!grid_mod(Nx, Ny)) return hipSuccess;
+    ModTabs t{};
+    return mod_tabs(t, 0, Nx, Ny);
+}
+static bool group_mod(const PrunedGroup& g)
+{
+    for (int p = 0; p < g.n; ++p) if (grid_mod(g.q[p].NxB ? g.q[p].NxB : g.q[p].Nx, g.q[p].NyB ? g.q[p].NyB : g.q[p].Ny)) return true;
+    return false;
+}
+static hipError_t group_tabs(const PrunedGroup& g, ModTabs& t)
+{
+    for (int p = 0; p < g.n; ++p) {
+        const hipError_t e = mod_tabs(t, p, g.q[p].NxB ? g.q[p].NxB : g.q[p].Nx, g.q[p].NyB ? g.q[p].NyB : g.q[p].Ny);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+// the grid has pruned transforms at all (what a net sizes its buffers by: AEFFT_F_NOPRUNESMOOTH may change on a live net)
+bool pruned_geometry(int Nk, int Nl, int Nx, int Ny)
 {
     if (!((Nk == 3 && Nl == 3) || (Nk == 5 && Nl == 5) || (Nk == 7 && Nl == 7))) return false;
-    if (Nx > TW_N || Ny > TW_N || (TW_N % Nx) || (TW_N % Ny) || Ny / 2 + 1 > 320) return false;
+    if (!axis_ok(Nx) || !axis_ok(Ny) || Ny / 2 + 1 > 320) return false;      // (a smooth axis ends at 2048 by fft_size_smooth, a power of two at TW_N as before)
     return kgrad_lds(1, Nx, Ny, Nk, Nl) <= 150 * 1024 && kgrad_lds(1L << 20, Nx, Ny, Nk, Nl) <= 150 * 1024;
+}
+bool pruned_pow2(int Nx, int Ny) { return !grid_mod(Nx, Ny); }
+bool pruned_supported(int Nk, int Nl, int Nx, int Ny)
+{
+    if (grid_mod(Nx, Ny) && flag(AEFFT_F_NOPRUNESMOOTH)) return false;     // the full pad + R2C / C2R + shrink route, for comparison
+    return pruned_geometry(Nk, Nl, Nx, Ny);
 }
 
 template <int NK, int NL>
 static hipError_t run_kspec(const float* k, float2* K, const float2* tw, long planes, int Nx, int Ny, hipStream_t st)
 {
+    const bool mod = grid_mod(Nx, Ny);
+    ModTabs mt{};
+    if (mod) { const hipError_t e = mod_tabs(mt, 0, Nx, Ny); if (e != hipSuccess) return e; }
     const int Nyr = Ny / 2 + 1;
     if (Nyr > 320) return hipErrorInvalidValue;          // one thread per column (callers fall back to pad + R2C above 512)
     const int ppb = std::max(1, 256 / Nyr);              // planes per workgroup
@@ -673,7 +799,9 @@ static hipError_t run_kspec(const float* k, float2* K, const float2* tw, long pl
     int chunks = 1;                                       // split the rows until the chip has ~1024 workgroups (>= 8 rows each)
     while (pblocks * chunks < 1024 && Nx / (chunks * 2) >= 8) chunks *= 2;
     const int rows = (Nx + chunks - 1) / chunks;
-    kspec_kernel<NK, NL><<<dim3((unsigned)pblocks, chunks), threads, kspec_lds(rows, NK, ppb), st>>>(k, K, tw, planes, Nx, Ny, rows, ppb);
+    chunks = (Nx + rows - 1) / rows;                      // (360 rows: 32 chunks of 12 would leave two workgroups per plane group without a row)
+    if (mod) kspec_kernel<NK, NL, true><<<dim3((unsigned)pblocks, chunks), threads, kspec_lds(rows, NK, ppb), st>>>(k, K, mt, planes, Nx, Ny, rows, ppb);
+    else kspec_kernel<NK, NL, false><<<dim3((unsigned)pblocks, chunks), threads, kspec_lds(rows, NK, ppb), st>>>(k, K, tw, planes, Nx, Ny, rows, ppb);
     return hipGetLastError();
 }
 
@@ -682,14 +810,19 @@ static hipError_t run_kgrad(const float2* D, float* g, float* part, const float2
 {
     int RB, ppb, thr;
     kgrad_geom(planes, Nx, Ny, &RB, &ppb, &thr);
-    const int chunks = Nx / RB;
+    const int chunks = kgrad_chunks(Nx, RB);
     const size_t lds = kgrad_lds(planes, Nx, Ny, NK, NL);
+    const bool mod = grid_mod(Nx, Ny);
+    ModTabs mt{};
+    if (mod) { const hipError_t e = mod_tabs(mt, 0, Nx, Ny); if (e != hipSuccess) return e; }
     if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kgrad_kernel<NK, NL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipError_t e = mod ? hipFuncSetAttribute(reinterpret_cast<const void*>(kgrad_kernel<NK, NL, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)
+                           : hipFuncSetAttribute(reinterpret_cast<const void*>(kgrad_kernel<NK, NL, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
     float* dst = chunks == 1 ? g : part;
-    kgrad_kernel<NK, NL><<<dim3((unsigned)((planes + ppb - 1) / ppb), chunks), thr, lds, st>>>(D, dst, tw, planes, Nx, Ny, RB, ppb, scale);
+    if (mod) kgrad_kernel<NK, NL, true><<<dim3((unsigned)((planes + ppb - 1) / ppb), chunks), thr, lds, st>>>(D, dst, mt, planes, Nx, Ny, RB, ppb, scale);
+    else kgrad_kernel<NK, NL, false><<<dim3((unsigned)((planes + ppb - 1) / ppb), chunks), thr, lds, st>>>(D, dst, tw, planes, Nx, Ny, RB, ppb, scale);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || chunks == 1) return e;
     const long n = planes * NK * NL;
@@ -760,8 +893,9 @@ template <int NK, int NL> static hipError_t run_kspec_group(PrunedGroup& g, cons
         // shorter, but twice as many for the launch's resident slots: 18.8-19.1 vs 18.7-18.9 us at cfg3, step +2 us.  So: 64 rows, and 16 in a launch
         // that leaves most of the chip idle anyway (cfg2: 22 such workgroups): grows)
         const int rmax = g.gsrc[p].f ? grows : 64;
-        const int chunks = (q.Nx + rmax - 1) / rmax;
+        int chunks = (q.Nx + rmax - 1) / rmax;
         g.rows[p] = (q.Nx + chunks - 1) / chunks;
+        chunks = (q.Nx + g.rows[p] - 1) / g.rows[p];      // (no workgroup without a row; the same count on every power of two)
         if (g.gsrc[p].f) {
             // G' problem (gspec_gbody): plane groups (d', tile of ppb d's); LDS = row phases | taps | f' | c' tile | slice partials
             if (!(NK == NL && (NK == 3 || NK == 5))) return hipErrorInvalidValue;
@@ -794,9 +928,17 @@ template <int NK, int NL> static hipError_t run_kspec_group(PrunedGroup& g, cons
     }
     bool has_g = false;                                   // (which instantiation: see gtaps_stage)
     for (int p = 0; p < g.n; ++p) has_g = has_g || g.gsrc[p].f != nullptr;
+    const bool mod = group_mod(g);                        // some problem has a smooth axis: every problem of the launch takes N-point tables
+    ModTabs mt{};
+    if (mod) {
+        if (extra) return hipErrorInvalidValue;           // (the operator form's record: power-of-two grids only)
+        const hipError_t e = group_tabs(g, mt);
+        if (e != hipSuccess) return e;
+    }
     if (lds > 64 * 1024) {
-        const hipError_t e = has_g ? hipFuncSetAttribute(reinterpret_cast<const void*>(kspec_group_kernel<NK, NL, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)
-                                   : hipFuncSetAttribute(reinterpret_cast<const void*>(kspec_group_kernel<NK, NL, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        const void* fn = mod ? (has_g ? reinterpret_cast<const void*>(kspec_group_kernel<NK, NL, 1, true>) : reinterpret_cast<const void*>(kspec_group_kernel<NK, NL, 2, true>))
+                             : (has_g ? reinterpret_cast<const void*>(kspec_group_kernel<NK, NL, 1, false>) : reinterpret_cast<const void*>(kspec_group_kernel<NK, NL, 2, false>));
+        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
     int threads = 256;                                    // one thread per (plane in group, column)
@@ -804,8 +946,12 @@ template <int NK, int NL> static hipError_t run_kspec_group(PrunedGroup& g, cons
     if (threads > 320) return hipErrorInvalidValue;
     if (extra) lds = std::max(lds, kspec_packed_lds(NK));
     const int nb = bu ? bu->n : 0;
-    if (has_g) kspec_group_kernel<NK, NL, 1><<<dim3(total + extra + nb), threads, lds, st>>>(g, tw, extra ? *pk : g_pack_none, nb ? *bu : g_bu_none, total + extra);
-    else kspec_group_kernel<NK, NL, 2><<<dim3(total + extra + nb), threads, lds, st>>>(g, tw, extra ? *pk : g_pack_none, nb ? *bu : g_bu_none, total + extra);
+    if (mod) {
+        if (has_g) kspec_group_kernel<NK, NL, 1, true><<<dim3(total + nb), threads, lds, st>>>(g, mt, g_pack_none, nb ? *bu : g_bu_none, total);
+        else kspec_group_kernel<NK, NL, 2, true><<<dim3(total + nb), threads, lds, st>>>(g, mt, g_pack_none, nb ? *bu : g_bu_none, total);
+    }
+    else if (has_g) kspec_group_kernel<NK, NL, 1, false><<<dim3(total + extra + nb), threads, lds, st>>>(g, tw, extra ? *pk : g_pack_none, nb ? *bu : g_bu_none, total + extra);
+    else kspec_group_kernel<NK, NL, 2, false><<<dim3(total + extra + nb), threads, lds, st>>>(g, tw, extra ? *pk : g_pack_none, nb ? *bu : g_bu_none, total + extra);
     return hipGetLastError();
 }
 
@@ -862,8 +1008,12 @@ template <int NK, int NL, int NT> static hipError_t run_kgrad_group(PrunedGroup&
     }
     g.start[g.n] = total;
     if (lds > 150 * 1024) return hipErrorInvalidValue;
+    const bool mod = group_mod(g);
+    ModTabs mt{};
+    if (mod) { const hipError_t e = group_tabs(g, mt); if (e != hipSuccess) return e; }
     if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kgrad_group_kernel<NK, NL, NT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipError_t e = mod ? hipFuncSetAttribute(reinterpret_cast<const void*>(kgrad_group_kernel<NK, NL, NT, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)
+                           : hipFuncSetAttribute(reinterpret_cast<const void*>(kgrad_group_kernel<NK, NL, NT, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
     BiasGradGroup bg{};
@@ -878,7 +1028,8 @@ template <int NK, int NL, int NT> static hipError_t run_kgrad_group(PrunedGroup&
         bgp->start[bgp->n] = extra;
         bg = *bgp;
     }
-    kgrad_group_kernel<NK, NL, NT><<<dim3(total + extra), NT, lds, st>>>(g, tw, bg);
+    if (mod) kgrad_group_kernel<NK, NL, NT, true><<<dim3(total + extra), NT, lds, st>>>(g, mt, bg);
+    else kgrad_group_kernel<NK, NL, NT, false><<<dim3(total + extra), NT, lds, st>>>(g, tw, bg);
     return hipGetLastError();
 }
 
@@ -892,12 +1043,18 @@ static bool pruned_group_ok(const PrunedGroup& g, const float2* tw, int Nk, int 
     return true;
 }
 
+// the axes alone (the T x T-tap launches: any support the instantiation has): powers of two up to TW_N or smooth sizes (up to 2048), one thread per column
+static bool axes_served(int Nx, int Ny)
+{
+    if (!axis_ok(Nx) || !axis_ok(Ny) || Ny / 2 + 1 > 320) return false;
+    return !(grid_mod(Nx, Ny) && flag(AEFFT_F_NOPRUNESMOOTH));
+}
 static bool taps_group_ok(const PrunedGroup& g, const float2* tw)
 {
     if (g.n < 1 || g.n > 8 || !tw) return false;
     for (int p = 0; p < g.n; ++p) {
         const PrunedProb& q = g.q[p];
-        if (q.planes <= 0 || q.Nx > TW_N || q.Ny > TW_N || (TW_N % q.Nx) || (TW_N % q.Ny) || q.Ny / 2 + 1 > 320) return false;
+        if (q.planes <= 0 || !axes_served(q.Nx, q.Ny)) return false;
     }
     return true;
 }
@@ -922,7 +1079,7 @@ hipError_t launch_kspec_group_taps(PrunedGroup& g, const float2* tw, int T, hipS
     if (g.n < 1 || g.n > 8 || !tw || (T != 5 && T != 9)) return hipErrorInvalidValue;
     for (int p = 0; p < g.n; ++p) {
         const PrunedProb& q = g.q[p];
-        if (q.planes <= 0 || g.gsrc[p].f || q.Nx > TW_N || q.Ny > TW_N || (TW_N % q.Nx) || (TW_N % q.Ny) || q.Ny / 2 + 1 > 320 || T > q.Nx || T > q.Ny) return hipErrorInvalidValue;
+        if (q.planes <= 0 || g.gsrc[p].f || !axes_served(q.Nx, q.Ny) || T > q.Nx || T > q.Ny) return hipErrorInvalidValue;
     }
     return T == 5 ? run_kspec_group<5, 5>(g, tw, st) : run_kspec_group<9, 9>(g, tw, st);
 }

@@ -93,8 +93,10 @@ enum {
     AEFFT_F_SMALLOVERLAP = 1 << 22, /* reconstructions below 8 MB take the side stream as well (the test suite's small nets then run the two-stream path of the large ones) */
     AEFFT_F_CHAINMSE = 1 << 23,    /* operator form with the chain: the innermost pair's post-update MSE inside the chain's per-bin items whatever the launch's size
                                    * (by default only in launches of more than ~6 000 workgroups, which are bound by their resident slots) */
-    AEFFT_F_CHIRPZ = 1 << 24       /* grids with a smooth axis, both axes up to 1024, through Bluestein's chirp-z transforms instead of the mixed-radix ones (the two
+    AEFFT_F_CHIRPZ = 1 << 24,      /* grids with a smooth axis, both axes up to 1024, through Bluestein's chirp-z transforms instead of the mixed-radix ones (the two
                                    * paths compared; power-of-two grids never take the mixed-radix passes) */
+    AEFFT_F_NOPRUNESMOOTH = 1 << 25 /* grids with a smooth axis: kernel spectra and weight gradients by pad + full R2C / full C2R + shrink instead of the
+                                   * support-pruned transforms (the two routes compared; power-of-two grids are not affected) */
 };
 int aefft_ctx_set_flags(aefft_ctx* ctx, unsigned flags);
 unsigned aefft_ctx_get_flags(const aefft_ctx* ctx);
@@ -117,9 +119,16 @@ int aefft_r2c_pool(aefft_ctx* ctx, const float* x_d, float* Xs_d, long planes, i
 int aefft_unpool_c2r(aefft_ctx* ctx, const float* Xs_d, float* x_d, long planes, int Nxs, int Nys, int scale, float out_scale);
 
 /* fft_backproplib.cu:1018-1064 `kernel_pad` + :869-916 `kfft` (first pass of StoreLoad_cfreq,
- * :1146-1158): k_d [nA][nB][Nk][Nl] -> K_d [nA][nB][Nx][Nyr]. */
+ * :1146-1158): k_d [nA][nB][Nk][Nl] -> K_d [nA][nB][Nx][Nyr].
+ * 3x3 / 5x5 / 7x7 supports are evaluated directly (the DFT of the support, no padded plane) on grids whose axes are powers of two or
+ * smooth sizes (even, no prime factor above 5) with Ny/2+1 <= 320; other shapes, and grids with a smooth axis under
+ * AEFFT_F_NOPRUNESMOOTH, take pad + R2C.
+ * The first pruned call of a process on a smooth axis size builds that size's phase table on the device in use (one allocation and a
+ * blocking upload per (device, axis size), kept for the life of the process): a one-time synchronisation inside the call, which must
+ * therefore not be the first one made while the stream is being captured.  A net builds its tables in aefft_net_create_ex. */
 int aefft_kernel_spectrum(aefft_ctx* ctx, const float* k_d, float* K_d, int nA, int nB, int Nk, int Nl, int Nx, int Ny);
-/* fft_backproplib.cu:1166-1172 `export_cfreq` (= `kfft_inv` :921-970 + `kernel_invpad` :1069-1112). */
+/* fft_backproplib.cu:1166-1172 `export_cfreq` (= `kfft_inv` :921-970 + `kernel_invpad` :1069-1112).  The same shapes as
+ * aefft_kernel_spectrum take the pruned adjoint (the inverse transform sampled on the support) instead of C2R + shrink, smooth grids included. */
 int aefft_kernel_export(aefft_ctx* ctx, const float* K_d, float* k_d, int nA, int nB, int Nk, int Nl, int Nx, int Ny);
 
 /* fft_backproplib.cu:1007-1013 `conv_fft` / :162-189 `conv_k`:
@@ -141,7 +150,8 @@ int aefft_mse(aefft_ctx* ctx, const float* T_d, const float* O_d, float* mse_d, 
 /* fft_backproplib.cu:1197-1291 host `backprop`: unnormalised C2R of dc/df, shrink_k (:535),
  * backprop_d (:605) or gradient_diff + backprop_double (:709,:657) when maxdiff, pad_k (:570),
  * R2C -> new C, F.  c,f,b,p and the momentum buffers Dc,Df,Db,Dp are updated in place.
- * `del` is the step actually applied (the reference passes 0.1*del0, :1445). */
+ * `del` is the step actually applied (the reference passes 0.1*del0, :1445).
+ * Both transforms take the pruned routes of aefft_kernel_export / aefft_kernel_spectrum where those do, on power-of-two and smooth grids. */
 int aefft_update(aefft_ctx* ctx, float* c_d, float* f_d, float* b_d, float* p_d, float* C_d, float* F_d,
                  const float* dc_d, const float* df_d, const float* db_d, const float* dp_d,
                  float* Dc_d, float* Df_d, float* Db_d, float* Dp_d,

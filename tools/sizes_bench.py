@@ -4,11 +4,13 @@
              Bluestein route (AEFFT_F_CHIRPZ) on the same buffers, alternated: time per call, algorithmic bytes/s (read + write once),
              the share of HBM peak -- the per-kernel split comes from a separate `rocprofv3 --kernel-trace --stats` run of this script
   training : cfg3-P2's net (D=3, maps 8/16/32/64, 5x5, s=2, B=32) at 640 x 480 (smooth sizes, per-frame form) and at 512^2 under NOOPFORM
-             (the same per-frame form on powers of two: the yardstick), alternated: ms/step and frames/s
+             (the same per-frame form on powers of two: the yardstick), alternated: ms/step and frames/s; vga_640x480_full is the 640 x 480
+             net with the weight side on the full pad + R2C / C2R + shrink route (AEFFT_F_NOPRUNESMOOTH), the A/B of the pruned transforms
 
     python tools/sizes_bench.py [--reps 20] [--steps 20] [--warmup 5]
     rocprofv3 --kernel-trace --stats -d DIR -o run -- python tools/sizes_bench.py --no-train --rounds 1     (per-kernel split, op level)
     rocprofv3 --kernel-trace --stats -d DIR -o run -- python tools/sizes_bench.py --train-only vga_640x480   (per-kernel split of one step kind)
+    python tools/sizes_bench.py --train --flags NOGROUP     (training only; development switches added to every net's own)
 """
 import argparse
 import importlib
@@ -68,10 +70,11 @@ def op_level(ctx, planes, Nx, Ny, reps, rounds):
     return out
 
 
-NETS = (("vga_640x480", 640, 480, True), ("p2_512x512_noopform", 512, 512, False))
+NETS = (("vga_640x480", 640, 480, True), ("vga_640x480_full", 640, 480, True), ("p2_512x512_noopform", 512, 512, False), ("p2_512x512", 512, 512, False))
+FLAGS_OF = {"vga_640x480": [], "vga_640x480_full": ["NOPRUNESMOOTH"], "p2_512x512_noopform": ["NOOPFORM"], "p2_512x512": []}
 
 
-def training(ctx, steps, warmup, rounds, only=None):
+def training(ctx, steps, warmup, rounds, only=None, extra=()):
     D, maps, Nk, s, B = 3, [8, 16, 32, 64], 5, 2, 32
     rng = np.random.default_rng(3)
     nets = {}
@@ -93,7 +96,7 @@ def training(ctx, steps, warmup, rounds, only=None):
         net.step_grad(frames, recon)
         net.step_apply(0.2)
 
-    flags_of = {"vga_640x480": [], "p2_512x512_noopform": ["NOOPFORM"]}
+    flags_of = {k: v + [f for f in extra if f not in v] for k, v in FLAGS_OF.items()}
     for tag in nets:
         ctx.set_flags(*flags_of[tag])
         for _ in range(warmup):
@@ -108,7 +111,9 @@ def training(ctx, steps, warmup, rounds, only=None):
     out = {}
     for tag, v in res.items():
         ms = float(np.median(v))
-        out[tag] = {"ms_per_step": round(ms, 4), "frames_per_s": round(B / ms * 1e3, 1), "form": nets[tag][0].step_form() if tag.startswith("vga") else "per_frame"}
+        ctx.set_flags(*flags_of[tag])
+        out[tag] = {"ms_per_step": round(ms, 4), "rounds_ms": [round(x, 4) for x in v], "frames_per_s": round(B / ms * 1e3, 1), "form": nets[tag][0].step_form()}
+    ctx.set_flags()
     if not only:
         out["step_ratio_vga_over_512"] = round(out["vga_640x480"]["ms_per_step"] / out["p2_512x512_noopform"]["ms_per_step"], 3)
         out["pixel_ratio"] = round(640 * 480 / 512 / 512, 3)
@@ -125,15 +130,18 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--no-train", action="store_true", help="op level only (the profiler run)")
     ap.add_argument("--train-only", choices=[n[0] for n in NETS], default=None, help="the training steps of one net only (the profiler run)")
+    ap.add_argument("--train", action="store_true", help="training only, every net, alternated")
+    ap.add_argument("--flags", default="", help="comma-separated development switches (without AEFFT_F_) added to every net's own")
     a = ap.parse_args()
+    extra = [f for f in a.flags.split(",") if f]
     ctx = aefft.Context(0)
-    if a.train_only:
-        print(json.dumps({"train": training(ctx, a.steps, a.warmup, a.rounds, a.train_only)}))
+    if a.train_only or a.train:
+        print(json.dumps({"train": training(ctx, a.steps, a.warmup, a.rounds, a.train_only, extra)}))
         ctx.close()
         return
     out = {"op": [op_level(ctx, 96, 640, 480, a.reps, a.rounds), op_level(ctx, 32, 1280, 720, a.reps, a.rounds)]}
     if not a.no_train:
-        out["train"] = training(ctx, a.steps, a.warmup, a.rounds)
+        out["train"] = training(ctx, a.steps, a.warmup, a.rounds, None, extra)
     print(json.dumps(out))
     ctx.close()
 
