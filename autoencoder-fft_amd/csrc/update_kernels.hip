@@ -173,11 +173,18 @@ __device__ __forceinline__ void gdiff_part_body(const float* __restrict__ c, con
     // FMA, ONE reciprocal, KP/2 packed FMAs for the weighted partner sum -- two thirds of the instructions of the difference form below.  The partner
     // norms are formed once per chunk and kept in the last padding slot of each LDS row (this thread's padding taps are zero, so the slot drops out
     // of the dot product; the padding lanes of the sums are not stored).  A thread owns GD_KPT kernels (rows i, i + 256, ...: gd_kpt).  Rounding: the squared distance is exact
-    // to a few ulp of |a|^2 + |b|^2 instead of of itself; identical kernels still give 1/0 and NaN sums like the reference's 0/0 (the norm and the dot
-    // product are the same FMA chain).
+    // to a few ulp of |a|^2 + |b|^2 instead of of itself, i.e. to ~k * 6e-8 * (|a|^2 + |b|^2) / den relative -- nothing on far-apart kernels, every digit
+    // once two kernels are closer than ~3e-4 of their size (the regime the repulsion term exists for).  So a partner with
+    //     den < GD_CLOSE * (|a|^2 + |b|^2),   GD_CLOSE = 1/16
+    // takes the reference's difference form instead: den' = sum (a - b)^2 and w' (a - b) goes straight into the partner sum (acc -= w' (a - b), nothing into
+    // sum_j w_j), so neither the distance nor a sum_j w_j - sum_j w_j b_j cancels for it.  Above the threshold the expanded distance is good to
+    // ~3 * 6e-8 * 16 = 3e-6 relative, and |a - b| >= |a| / 2.9 bounds what a w - w b loses to a bit and a half.  The branch depends on the data only
+    // (replicas stay bit-identical) and is not taken on U(-1, 1) weights.  Identical kernels take it too and give 0 * (1/0) = NaN like the reference's 0/0
+    // (their expanded distance is exactly 0: the norm and the dot product are the same FMA chain).
     {
         static_assert(KP > KL, "a padding slot for the norm");
         constexpr int KH = KP / 2, GD_KPT = gd_kpt(KL);
+        constexpr float GD_CLOSE = 1.f / 16.f;
         const int nj = j1 - j0;
         __syncthreads();
         for (int t = threadIdx.x; t < nj; t += 256) {
@@ -221,13 +228,30 @@ __device__ __forceinline__ void gdiff_part_body(const float* __restrict__ c, con
                 float2 dot2 = make_float2(0.f, 0.f);
 #pragma unroll
                 for (int h = 0; h < KH; ++h) dot2 = dot2 + ca2[u][h] * b2[h];
-                const float den = fmaf(-2.f, dot2.x + dot2.y, ni[u] + nb);
+                const float nab = ni[u] + nb;
+                const float den = fmaf(-2.f, dot2.x + dot2.y, nab);
                 // pairs need m1 != m AND d1 != d (:724)
-                const float wgt = (jf != i_f[u] && js != i_s[u]) ? __builtin_amdgcn_rcpf(den) : 0.f;
+                const bool pair = jf != i_f[u] && js != i_s[u];
+                const bool close = pair && den < GD_CLOSE * nab;
+                const float wgt = (pair && !close) ? __builtin_amdgcn_rcpf(den) : 0.f;
                 const float2 w2 = make_float2(wgt, wgt);
                 sw[u] += wgt;
 #pragma unroll
                 for (int h = 0; h < KH; ++h) acc2[u][h] = acc2[u][h] + b2[h] * w2;
+                if (__builtin_expect(close, 0)) {
+                    // the difference form for this partner; the row's last slot holds |b|^2, not a tap
+                    float2 dd2 = make_float2(0.f, 0.f);
+#pragma unroll
+                    for (int h = 0; h < KH; ++h) {
+                        float2 d = ca2[u][h] - b2[h];
+                        if (h == KH - 1) d.y = 0.f;
+                        dd2 = dd2 + d * d;
+                    }
+                    const float wd = __builtin_amdgcn_rcpf(dd2.x + dd2.y);
+                    const float2 wd2 = make_float2(wd, wd);
+#pragma unroll
+                    for (int h = 0; h < KH; ++h) acc2[u][h] = acc2[u][h] + (b2[h] - ca2[u][h]) * wd2;     // (the last slot's lane is not stored)
+                }
             }
             if (++jf == fast_n) { jf = 0; ++js; }
         }
