@@ -27,6 +27,7 @@ FLAGS = {n: 1 << i for i, n in enumerate(
      "CHIRPZ", "NOPRUNESMOOTH"])}
 NET_SMOOTH_SIZES = 1 << 0   # include/aefft.h AEFFT_NET_SMOOTH_SIZES (aefft_net_create_ex)
 NET_SPATIAL = 1 << 1        # include/aefft.h AEFFT_NET_SPATIAL: the coordinate-space training mode as a resident net
+NET_SMOOTH_OPFORM = 1 << 2  # include/aefft.h AEFFT_NET_SMOOTH_OPFORM: the operator-form training step on grids with a smooth axis
 
 
 class AefftError(RuntimeError):
@@ -412,9 +413,11 @@ class Context:
 class Net:
     """aefft_net: resident batched autoencoder (autoenc_fft / backprop_fft semantics)."""
 
-    def __init__(self, ctx, D, Nx, Ny, maps, Nk, scale, batch, Nl=None, smooth_sizes=False, spatial=False):
+    def __init__(self, ctx, D, Nx, Ny, maps, Nk, scale, batch, Nl=None, smooth_sizes=False, spatial=False, operator_form=False):
         """smooth_sizes: also take Nx, Ny with prime factors 3 and 5 (640 x 480, ...; aefft_net_create_ex with
-        AEFFT_NET_SMOOTH_SIZES) -- such a net trains in the per-frame form.
+        AEFFT_NET_SMOOTH_SIZES) -- such a net trains in the per-frame form, unless
+        operator_form (AEFFT_NET_SMOOTH_OPFORM, with smooth_sizes): it trains in the operator form where it meets that form's rules
+        (step_form() reports the form it runs in); no effect on a power-of-two net, on a spatial net or without smooth_sizes.
         spatial: the coordinate-space mode (Pool / Conv_gpu / backprop_gpu; aefft_net_create_ex with AEFFT_NET_SPATIAL): any frame size,
         every scale dividing its input grid exactly; step_apply's del0 is backprop_gpu's delmax and the MSE tail is this step's."""
         self.ctx, self.L = ctx, ctx.L
@@ -427,8 +430,8 @@ class Net:
         self._keep = [arr(self.maps), arr(self.Nk), arr(self.Nl), arr(self.scale)]
         d = NetDesc(D, Nx, Ny, self.npairs, *self._keep, batch)
         h = C.c_void_p()
-        if smooth_sizes or spatial:
-            opts = (NET_SMOOTH_SIZES if smooth_sizes else 0) | (NET_SPATIAL if spatial else 0)
+        if smooth_sizes or spatial or operator_form:
+            opts = (NET_SMOOTH_SIZES if smooth_sizes else 0) | (NET_SPATIAL if spatial else 0) | (NET_SMOOTH_OPFORM if operator_form else 0)
             ctx.check(self.L.aefft_net_create_ex(ctx.h, C.byref(d), opts, C.byref(h)))
         else:
             ctx.check(self.L.aefft_net_create(ctx.h, C.byref(d), C.byref(h)))

@@ -417,26 +417,7 @@ __global__ __launch_bounds__(CW* N / 8) void fwd_cols_kernel(const float2* __res
     }
 }
 
-// Operator-form input of the reconstruction's inverse transform (opform_kernels.hip): the spectrum of plane (b, d) is not
-// stored but evaluated where it is read, O_b[d][t] = A[OPC-1][d][t] + sum_j A[j][d][t] x_b[j][u(t)] (u: the bin of the input grid
-// that bin t of this grid maps to) -- 4 loads and 3 complex FMAs per element instead of a launch that writes the planes out.
-__device__ __forceinline__ float2 opin_load(const OpIn& o, long plane, int t, int Nxi, int Nyi)
-{
-    const int b = (int)(plane / o.D0), d = (int)(plane - (long)b * o.D0);
-    const long Pc = (long)Nxi * (Nyi / 2 + 1), P0 = (long)o.Nx0 * (o.Ny0 / 2 + 1);
-    const unsigned nyr = Nyi / 2 + 1, NyrB = o.Ny0 / 2 + 1;
-    const unsigned i = (unsigned)t / nyr, j = (unsigned)t - i * nyr;
-    const unsigned bi = i < (unsigned)Nxi / 2 ? i : (i == (unsigned)Nxi / 2 ? (unsigned)o.Nx0 / 2 : i + o.Nx0 - Nxi);
-    const unsigned bj = j < nyr - 1 ? j : NyrB - 1;
-    const long u = (long)bi * NyrB + bj;
-    float2 acc = o.A[((long)(OPIN_COLS - 1) * o.D0 + d) * Pc + t];
-    for (int jj = 0; jj < o.D0; ++jj) {
-        const float2 a = o.A[((long)jj * o.D0 + d) * Pc + t], x = o.Xf[((long)b * o.D0 + jj) * P0 + u];
-        acc.x += a.x * x.x - a.y * x.y; acc.y += a.x * x.y + a.y * x.x;
-    }
-    return acc;
-}
-
+// (opin_load, the operator-form input of the reconstruction: fft_common.h)
 // inverse: in [planes][Nxi][Wc+1] (rows zero-padded to N) -> mid [planes][N][Wc], inverse FFT along x
 template <int N, int CW>
 __global__ __launch_bounds__(CW* N / 8) void inv_cols_kernel(const float2* __restrict__ in, float2* __restrict__ mid,
@@ -855,15 +836,15 @@ hipError_t launch_c2r(const float2* in, float* out, float2* mid, long planes, in
     const OpIn op = opin ? *opin : g_opin_none;
     if ((Nxi == Nx) != (Nyi == Ny)) return hipErrorInvalidValue;   // pad both axes or none
     if (!fft_size_supported(Nx) || !fft_size_supported(Ny) || Nxi > Nx || Nyi > Ny || Nyi < 8 || Nxi < 2 || (Nyi & 1) || (Nxi & 1)) {
-        // sizes with factors 3 and 5 (stored spectra only: the operator-form input is a power-of-two path)
-        if (!axis_ok(Nx) || !axis_ok(Ny) || Nxi > Nx || Nyi > Ny || Nxi < 2 || Nyi < 2 || (Nxi & 1) || (Nyi & 1) || op.A) return hipErrorInvalidValue;
+        // sizes with factors 3 and 5 (the operator-form input rides in either column pass)
+        if (!axis_ok(Nx) || !axis_ok(Ny) || Nxi > Nx || Nyi > Ny || Nxi < 2 || Nyi < 2 || (Nxi & 1) || (Nyi & 1)) return hipErrorInvalidValue;
         if (planes <= 0) return hipSuccess;
         const int Wc = Nyi / 2;
         const long npairs = planes * Nx / 2;
         hipError_t e = hipSuccess;
-        if (in) {
-            if (cols_pow2(Nx, Wc)) { AEFFT_N_SWITCH(Nx, e = (cols_dispatch<NN, false>(in, mid, planes, Wc, Nxi, st)); break) }
-            else e = launch_mix_inv_cols(in, mid, planes, Nx, Wc, Nxi, st);
+        if (in || op.A) {
+            if (cols_pow2(Nx, Wc)) { AEFFT_N_SWITCH(Nx, e = (cols_dispatch<NN, false>(in, mid, planes, Wc, Nxi, st, op)); break) }
+            else e = launch_mix_inv_cols(in, mid, planes, Nx, Wc, Nxi, st, op.A ? &op : nullptr);
             if (e != hipSuccess) return e;
         }
         if (out) {

@@ -280,9 +280,14 @@ __global__ __launch_bounds__(1024) void mix_fwd_cols_kernel(const float2* __rest
 }
 
 // inverse: in [planes][Nxi][Wc+1] (rows zero-padded to n) -> mid [planes][n][Wc]
-template <int T>
+// OPIN: the input spectra are not stored but evaluated on load from the reconstruction's operator (opin_load, fft_common.h), as in the
+// power-of-two inv_cols_kernel; `in` is not read.  Its own instantiation: the stored-spectra kernel keeps its load loop.
+struct MixNoOp {};
+template <bool OPIN> struct MixOpArg { typedef MixNoOp type; };
+template <> struct MixOpArg<true> { typedef OpIn type; };
+template <int T, bool OPIN>
 __global__ __launch_bounds__(1024) void mix_inv_cols_kernel(const float2* __restrict__ in, float2* __restrict__ mid, int Wc, int Nxi, int CW,
-                                                             const MixPlan pl)
+                                                             const MixPlan pl, const typename MixOpArg<OPIN>::type op)
 {
     extern __shared__ float2 s[];
     const int N = pl.n, PL = pad_len(N), NT = blockDim.x;
@@ -299,8 +304,15 @@ __global__ __launch_bounds__(1024) void mix_inv_cols_kernel(const float2* __rest
     }
     for (int it = tid; it < Nxi * cw; it += NT) {
         const int sr = it / cw, c = it - sr * cw;
-        const float2 v = src[(long)sr * Nyri + c0 + c];
-        if (c0 + c == 0) { dcs[sr] = v; nys[sr] = src[(long)sr * Nyri + Wc]; }
+        float2 v, vn = make_float2(0.f, 0.f);
+        if constexpr (OPIN) {
+            v = opin_load(op, plane, sr * Nyri + c0 + c, Nxi, 2 * Wc);
+            if (c0 + c == 0) vn = opin_load(op, plane, sr * Nyri + Wc, Nxi, 2 * Wc);
+        } else {
+            v = src[(long)sr * Nyri + c0 + c];
+            if (c0 + c == 0) vn = src[(long)sr * Nyri + Wc];
+        }
+        if (c0 + c == 0) { dcs[sr] = v; nys[sr] = vn; }
         else {
             const int r = Nxi == N ? sr : (sr < Nxi / 2 ? sr : (sr == Nxi / 2 ? N / 2 : sr + N - Nxi));    // inverse of padsrc_row
             s[c * PL + pad_idx(r)] = v;
@@ -450,14 +462,16 @@ template <int T> static hipError_t run_mix_fwd_cols(const float2* mid, float2* o
     else mix_fwd_cols_kernel<T><<<grid, dim3(cw * T), lds, st>>>(mid, out, Wc, Nxs, cw, pl);
     return hipGetLastError();
 }
-template <int T> static hipError_t run_mix_inv_cols(const float2* in, float2* mid, long planes, int Wc, int Nxi, const MixPlan& pl, hipStream_t st)
+template <int T> static hipError_t run_mix_inv_cols(const float2* in, float2* mid, long planes, int Wc, int Nxi, const MixPlan& pl, hipStream_t st, const OpIn* op)
 {
     const size_t extra = sizeof(float2) * 2 * (size_t)Nxi;
     const int cw = mix_cw(pl.n, T, Wc, extra);
     const size_t lds = sizeof(float2) * ((size_t)cw * pad_len(pl.n)) + extra;
-    hipError_t e = mix_allow_lds(mix_inv_cols_kernel<T>, lds);
+    hipError_t e = op ? mix_allow_lds(mix_inv_cols_kernel<T, true>, lds) : mix_allow_lds(mix_inv_cols_kernel<T, false>, lds);
     if (e != hipSuccess) return e;
-    mix_inv_cols_kernel<T><<<dim3((unsigned)planes, (unsigned)((Wc + cw - 1) / cw)), dim3(cw * T), lds, st>>>(in, mid, Wc, Nxi, cw, pl);
+    const dim3 grid((unsigned)planes, (unsigned)((Wc + cw - 1) / cw));
+    if (op) mix_inv_cols_kernel<T, true><<<grid, dim3(cw * T), lds, st>>>(in, mid, Wc, Nxi, cw, pl, *op);
+    else mix_inv_cols_kernel<T, false><<<grid, dim3(cw * T), lds, st>>>(in, mid, Wc, Nxi, cw, pl, MixNoOp{});
     return hipGetLastError();
 }
 
@@ -488,13 +502,16 @@ hipError_t launch_mix_fwd_cols(const float2* mid, float2* out, long planes, int 
     AEFFT_T_SWITCH(mix_threads(Nx), e = run_mix_fwd_cols<TT>(mid, out, planes, Wc, Nxs, pl, st, done); break)
     return e;
 }
-hipError_t launch_mix_inv_cols(const float2* in, float2* mid, long planes, int Nx, int Wc, int Nxi, hipStream_t st)
+hipError_t launch_mix_inv_cols(const float2* in, float2* mid, long planes, int Nx, int Wc, int Nxi, hipStream_t st, const OpIn* opin)
 {
     MixPlan pl;
     hipError_t e = mix_plan(Nx, &pl);
     if (e != hipSuccess) return e;
     if (Wc < 1 || Nxi < 2 || Nxi > Nx || (Nxi & 1) || planes >= (1L << 31)) return hipErrorInvalidValue;
-    AEFFT_T_SWITCH(mix_threads(Nx), e = run_mix_inv_cols<TT>(in, mid, planes, Wc, Nxi, pl, st); break)
+    if ((opin != nullptr) == (in != nullptr)) return hipErrorInvalidValue;      // stored spectra or the operator, not both
+    // (the operator's bin index and plane products in 32 bits, as opin_load forms them)
+    if (opin && (opin->D0 < 1 || opin->D0 > OPIN_COLS - 1 || (long)Nxi * (Wc + 1) >= (1L << 31))) return hipErrorInvalidValue;
+    AEFFT_T_SWITCH(mix_threads(Nx), e = run_mix_inv_cols<TT>(in, mid, planes, Wc, Nxi, pl, st, opin); break)
     return e;
 }
 

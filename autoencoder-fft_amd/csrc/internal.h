@@ -26,7 +26,7 @@ hipError_t launch_r2c(const void* in, float2* out, float2* mid, long planes, int
                       int Nxs, int Nys, hipStream_t st, hipEvent_t done = nullptr /* recorded by the column pass's own completion signal */, bool in_u8 = false);
 // Batched 2-D C2R with optional fused spectral zero-pad (== `resize` up-sampling from
 // Nxi x Nyi, then cufftExecC2R, then * scale).  in [planes][Nxi][Nyi/2+1] -> out [planes][Nx][Ny].
-// opin (nullable): the input spectra are not stored but evaluated from an operator (see inv_cols_kernel): plane (b, d) at bin t is
+// opin (nullable): the input spectra are not stored but evaluated from an operator (inv_cols_kernel, mix_inv_cols_kernel): plane (b, d) at bin t is
 // A[OPIN_COLS-1][d][t] + sum_{j<D0} A[j][d][t] * Xf[b][j][u(t)], A [OPIN_COLS][D0][Nxi*(Nyi/2+1)], Xf [B][D0][Nx0*(Ny0/2+1)]
 constexpr int OPIN_COLS = 4;
 constexpr int OPMSE_PACKED_STEPS = 16;  // steps of the innermost pair's two stages in the post-update MSE (opmse_packed)
@@ -51,7 +51,8 @@ bool fft_size_smooth(int n);   // ... in 10..2048 and not a power of two: the si
 hipError_t fft_mixed_prepare(int n);     // builds the n-point twiddle table of the current device (done on first use otherwise)
 hipError_t launch_mix_r2c_rows(const void* in, float2* mid, long npairs, int Ny, int Wc, hipStream_t st, bool in_u8);
 hipError_t launch_mix_fwd_cols(const float2* mid, float2* out, long planes, int Nx, int Wc, int Nxs, hipStream_t st, hipEvent_t done);
-hipError_t launch_mix_inv_cols(const float2* in, float2* mid, long planes, int Nx, int Wc, int Nxi, hipStream_t st);
+hipError_t launch_mix_inv_cols(const float2* in, float2* mid, long planes, int Nx, int Wc, int Nxi, hipStream_t st,
+                               const OpIn* opin = nullptr /* the spectra evaluated on load from an operator (launch_c2r); then in == null */);
 hipError_t launch_mix_c2r_rows(const float2* mid, float* out, long npairs, int Ny, int Wc, float scale, hipStream_t st);
 
 // ---- spectral_kernels.hip --------------------------------------------------------------
@@ -128,7 +129,7 @@ hipError_t launch_bias_grad_group(BiasGradGroup& g, hipStream_t st);
 // Grids: both axes powers of two (the TW_N-point twiddle table) or smooth (even, 10..2048, no prime factor above 5: an N-point phase table
 // per (device, axis size), built on first use or by pruned_prepare), Ny/2+1 <= 320.  pruned_supported: the route is taken (false on a grid
 // with a smooth axis under AEFFT_F_NOPRUNESMOOTH); pruned_geometry: the grid has the route at all -- what buffers are sized by, the switch
-// may change on a live net; pruned_pow2: neither axis needs a table of its own (the operator form's kernels take nothing else).
+// may change on a live net; pruned_pow2: neither axis needs a table of its own.
 bool pruned_supported(int Nk, int Nl, int Nx, int Ny);
 bool pruned_geometry(int Nk, int Nl, int Nx, int Ny);
 bool pruned_pow2(int Nx, int Ny);
@@ -243,6 +244,11 @@ struct PackArgs { PackSeg seg[16]; int nseg, L, E, Nk; int Nx[8], Ny[8]; int NxC
                   int upd; float upd_del, upd_alpha, upd_gscale; /* upd != 0: taps read through the pending update (TapUpd) */ };
 void pack_blocks(PackArgs& g);
 hipError_t launch_kspec_packed(PackArgs& g, hipStream_t st);
+// (pruned_kernels.hip) some level of the record's net has a smooth axis: its phases then come from N-point tables per level and axis
+// (PackTabs, opform_device.h: the cached tables of pruned_prepare), by value in the kernel arguments
+struct PackTabs;
+bool pack_mod(const PackArgs& g);
+hipError_t pack_tabs(const PackArgs& g, PackTabs& t);
 
 // ---- update_kernels.hip ----------------------------------------------------------------
 hipError_t launch_pad(const float* ck, float* cpad, long planes, int Nx, int Ny, int Nk, int Nl, hipStream_t st);   // fft.cu:570 (zero-fills)

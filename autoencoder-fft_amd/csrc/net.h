@@ -46,6 +46,7 @@ struct aefft_net {
     float2* Xf = nullptr;      // [B][D][P0] input spectra of the frames (pair 0's X in the per-frame form)
     float2* A0hat = nullptr;   // [OPC][D][P0] basis frames (pair 0's X in the operator form); null: D > OPC-1
     float2* Mhat = nullptr;    // [OPC][OPC][P0] second moments of the batch
+    bool smooth_opform = false; // created with AEFFT_NET_SMOOTH_OPFORM on a grid with a smooth axis: the operator form also where a pair's grid is not a power of two
     bool op_state = false;     // the activation buffers hold OPERATORS (basis-frame responses) of the last step_grad, not frames
     // chain mode (the step's forward is chain_kernel): the operators live in their OWN buffers (Pair::opA / opO), two sets, because the
     // tail launch of a step already runs the NEXT step's chain on the updated weights (it depends on the weights only) while the

@@ -90,6 +90,7 @@ static int net_create(aefft_ctx* ctx, const aefft_net_desc* d, unsigned opts, ae
     aefft_net* n = new aefft_net();
     n->ctx = ctx; n->D = d->D; n->Nx = d->Nx; n->Ny = d->Ny; n->L = d->npairs; n->B = d->batch;
     n->Bc = std::max(n->B, (int)OPC);
+    n->smooth_opform = smooth && (opts & AEFFT_NET_SMOOTH_OPFORM) && (fft_size_smooth(d->Nx) || fft_size_smooth(d->Ny));
     n->pr.resize(n->L);
     int dD = d->D, nx = d->Nx, ny = d->Ny;
     size_t maxS = 0, maxBDP = 0, maxW = 0, maxReal = 0, goff = 0, maxMid = 0, maxDen = 0, maxSmall = 0, soff = 2 * (size_t)d->npairs;
@@ -210,8 +211,8 @@ static int net_create(aefft_ctx* ctx, const aefft_net_desc* d, unsigned opts, ae
 extern "C" int aefft_net_create(aefft_ctx* ctx, const aefft_net_desc* d, aefft_net** out) { return net_create(ctx, d, 0, out); }
 extern "C" int aefft_net_create_ex(aefft_ctx* ctx, const aefft_net_desc* d, unsigned opts, aefft_net** out)
 {
-    if (opts & ~(unsigned)(AEFFT_NET_SMOOTH_SIZES | AEFFT_NET_SPATIAL)) return fail(ctx, AEFFT_EINVAL, "aefft_net_create_ex: unknown option bits");
-    if (opts & AEFFT_NET_SPATIAL) {       // (AEFFT_NET_SMOOTH_SIZES has no effect: the spatial mode takes any frame size)
+    if (opts & ~(unsigned)(AEFFT_NET_SMOOTH_SIZES | AEFFT_NET_SPATIAL | AEFFT_NET_SMOOTH_OPFORM)) return fail(ctx, AEFFT_EINVAL, "aefft_net_create_ex: unknown option bits");
+    if (opts & AEFFT_NET_SPATIAL) {       // (AEFFT_NET_SMOOTH_SIZES and AEFFT_NET_SMOOTH_OPFORM have no effect: the spatial mode takes any frame size)
         if (!ctx || !d || !out || d->npairs <= 0 || d->batch <= 0 || d->D <= 0 || !d->maps || !d->Nk || !d->Nl || !d->scale)
             return fail(ctx, AEFFT_EINVAL, "aefft_net_create_ex: bad descriptor");
         *out = nullptr;

@@ -120,9 +120,10 @@ static bool op_eligible(const aefft_net* n)
     if (flag(AEFFT_F_NOOPFORM) || flag(AEFFT_F_NOQPATH) || !n->A0hat || n->L > 8) return false;
     const Pair& q0 = n->pr[0];
     if (q0.Nk != q0.Nl || (q0.Nk != 3 && q0.Nk != 5)) return false;
-    // (power-of-two grids only: the operator form's own kernels index the TW_N-point table, phase_tw / map_up_*; a smooth net has the
-    // pruned transforms in its per-frame step)
-    for (const Pair& q : n->pr) if (q.Nk != q0.Nk || q.Nl != q0.Nl || !q.Q || !pruned_pow2(q.Nx, q.Ny) || !pruned_supported(q.Nk, q.Nl, q.Nx, q.Ny)) return false;
+    // (grids with a smooth axis: only on a net created with AEFFT_NET_SMOOTH_OPFORM -- the record and the reconstruction then take N-point
+    // phase tables and the mixed-radix column pass -- and, by pruned_supported, not under AEFFT_F_NOPRUNESMOOTH)
+    for (const Pair& q : n->pr)
+        if (q.Nk != q0.Nk || q.Nl != q0.Nl || !q.Q || !(pruned_pow2(q.Nx, q.Ny) || n->smooth_opform) || !pruned_supported(q.Nk, q.Nl, q.Nx, q.Ny)) return false;
     // channel counts the operator-form kernels' LDS tiles take (msgrad_kernel: 2*OPC*dD*8 complex; opmse: OPC*(dD+dM)*4 complex): a
     // launch declined in the middle of step_apply would leave a fused update half applied, so the step form is decided here
     for (const Pair& q : n->pr) if (q.dD > 256 || q.dM > 512 || q.dD + q.dM > 1024) return false;
@@ -163,7 +164,10 @@ static int launch_recon(aefft_net* n, float* recon_d, int wsid)
     if (op_mode(n)) {
         static_assert(OPIN_COLS == OPC, "operator width");
         const long PO = bins(nxo, nyo);
-        if ((double)n->B * q.dD * PO * 8.0 > 16e6) {
+#ifndef AEFFT_X_RECON_EXPAND_BYTES
+#define AEFFT_X_RECON_EXPAND_BYTES 16e6      // (experiment builds, tools/mkx.sh: 0 sends every reconstruction through the stored planes)
+#endif
+        if ((double)n->B * q.dD * PO * 8.0 > AEFFT_X_RECON_EXPAND_BYTES) {
             // large supports (no pooling: the decoder output lives on the whole grid): the per-frame spectra O_0,b = O^_0 [x_b; 1] are
             // written out once by a coalesced pass (7 plane-ordered loads per output) and the inverse transform reads them back.  Evaluated
             // inside the column pass instead, the same 7 loads are strided 128-byte pieces: 1.1 ms against 0.2 ms at cfg3-P1.

@@ -36,6 +36,13 @@ __device__ __forceinline__ float2 phase_tw(const float2* tw, int pos, int off, i
     return tw[((pos * off) & (N - 1)) * (TW_N / N)];
 }
 
+__device__ __forceinline__ int mod4(int v, int N)        // v mod N for 0 <= v < 4N
+{
+    if (v >= 2 * N) v -= 2 * N;
+    if (v >= N) v -= N;
+    return v;
+}
+
 // the two halves of map_up: row i / column j of the small grid -> row / column of the big grid
 __device__ __forceinline__ int map_up_row(int i, int Nx, int NxB) { return i < Nx / 2 ? i : (i == Nx / 2 ? NxB / 2 : i + NxB - Nx); }
 __device__ __forceinline__ int map_up_col(int j, int Ny, int NyB) { return j < Ny / 2 ? j : NyB / 2; }
@@ -57,8 +64,19 @@ static inline int pack_yblocks(const PackArgs& g) { return (g.NyC / 2 + 1) * ((g
 // (LDS: `smem`, kspec_packed_lds(NK) bytes of the hosting kernel's dynamic region -- a static allocation would ADD to the dynamic size the
 // host launch asks for on behalf of its other workgroups: 52 KB instead of 26 KB per workgroup at cfg3)
 constexpr size_t kspec_packed_lds(int NK) { return sizeof(float2) * (size_t)(PACK_RG + 1) * (NK / 2 > 0 ? NK / 2 : 1) + sizeof(float) * 256 * (size_t)(NK * NK); }
-template <int NK>
-__device__ __forceinline__ void kspec_packed_body(const PackArgs& g, int bx, int by, void* smem)
+// Where the record's phases come from (the PhasePow2 / PhaseMod of pruned_kernels.hip, per LEVEL of the net instead of per problem): the
+// TW_N-point table of PackArgs, or -- a net with a smooth axis -- one N-point table exp(-2 pi i r / N) per level and axis, by value in the
+// kernel arguments (PackTabs).  The offsets are 1 .. NK/2 <= 2 and pos < N, so the residue is mod4's compare-and-subtract.
+struct PackTabs { const float2* x[8]; const float2* y[8]; };
+struct PackPhasePow2 { static constexpr bool mod = false; };      // phase_tw on PackArgs::tw, where the body always took it
+struct PackPhaseMod {
+    const PackTabs& t;
+    static constexpr bool mod = true;
+    __device__ __forceinline__ float2 row(int lev, int pos, int off, int N) const { return t.x[lev][mod4(pos * off, N)]; }
+    __device__ __forceinline__ float2 col(int lev, int pos, int off, int N) const { return t.y[lev][mod4(pos * off, N)]; }
+};
+template <int NK, class PS>
+__device__ __forceinline__ void kspec_packed_body(const PackArgs& g, const PS& ps, int bx, int by, void* smem)
 {
     constexpr int RG = PACK_RG, KK = NK * NK, H = NK / 2;
     static_assert(NK % 2 == 1, "symmetric tap offsets");
@@ -90,8 +108,12 @@ __device__ __forceinline__ void kspec_packed_body(const PackArgs& g, int bx, int
         if (threadIdx.x < (RG + 1) * H) {
             const int k = threadIdx.x % H, r = threadIdx.x / H;
             const int NxB = g.Nx[sd.lev], NyB = g.Ny[sd.lev];
-            pv = r < RG ? phase_tw(g.tw, map_up_row(min(i0 + r, g.NxC - 1), g.NxC, NxB), k + 1, NxB)
-                        : phase_tw(g.tw, map_up_col(j, g.NyC, NyB), k + 1, NyB);
+            if constexpr (PS::mod)
+                pv = r < RG ? ps.row(sd.lev, map_up_row(min(i0 + r, g.NxC - 1), g.NxC, NxB), k + 1, NxB)
+                            : ps.col(sd.lev, map_up_col(j, g.NyC, NyB), k + 1, NyB);
+            else      // (the power-of-two instantiations keep this statement, and with it their instruction stream)
+                pv = r < RG ? phase_tw(g.tw, map_up_row(min(i0 + r, g.NxC - 1), g.NxC, NxB), k + 1, NxB)
+                            : phase_tw(g.tw, map_up_col(j, g.NyC, NyB), k + 1, NyB);
         }
 #pragma unroll
         for (int w = 0; w < KK; ++w) { const int f = w * 256 + threadIdx.x; if (f < nf) taps[f] = v[w]; }

@@ -1090,7 +1090,13 @@ namespace aefft {
 template <int NK> __global__ __launch_bounds__(256) void kspec_packed_kernel(const PackArgs g)
 {
     extern __shared__ float2 pk_lds[];
-    kspec_packed_body<NK>(g, blockIdx.x, blockIdx.y, pk_lds);
+    kspec_packed_body<NK>(g, PackPhasePow2{}, blockIdx.x, blockIdx.y, pk_lds);
+}
+// ... of a net with a smooth axis: the phases from the per-level N-point tables
+template <int NK> __global__ __launch_bounds__(256) void kspec_packed_mod_kernel(const PackArgs g, const PackTabs t)
+{
+    extern __shared__ float2 pk_lds[];
+    kspec_packed_body<NK>(g, PackPhaseMod{t}, blockIdx.x, blockIdx.y, pk_lds);
 }
 
 void pack_blocks(PackArgs& g)
@@ -1106,6 +1112,14 @@ hipError_t launch_kspec_packed(PackArgs& g, hipStream_t st)
     if (g.nseg < 1 || g.nseg > 16 || g.L < 1 || g.L > 8 || g.E < 1 || (g.Nk != 3 && g.Nk != 5)) return hipErrorInvalidValue;
     pack_blocks(g);
     const dim3 grid((unsigned)g.nblk, (unsigned)pack_yblocks(g));
+    if (pack_mod(g)) {
+        PackTabs t{};
+        const hipError_t e = pack_tabs(g, t);
+        if (e != hipSuccess) return e;
+        if (g.Nk == 3) kspec_packed_mod_kernel<3><<<grid, 256, kspec_packed_lds(3), st>>>(g, t);
+        else kspec_packed_mod_kernel<5><<<grid, 256, kspec_packed_lds(5), st>>>(g, t);
+        return hipGetLastError();
+    }
     if (g.Nk == 3) kspec_packed_kernel<3><<<grid, 256, kspec_packed_lds(3), st>>>(g);
     else kspec_packed_kernel<5><<<grid, 256, kspec_packed_lds(5), st>>>(g);
     return hipGetLastError();

@@ -37,12 +37,7 @@ namespace aefft {
 // The kernels are templates on the source: the power-of-two instantiations keep their parameter list and their instruction stream,
 // and no run-time select between two table pointers exists anywhere (such a select compiles to flat loads).
 __device__ __forceinline__ float2 phase(const float2* tw, int pos, int off, int N, float sign);
-__device__ __forceinline__ int mod4(int v, int N)        // v mod N for 0 <= v < 4N
-{
-    if (v >= 2 * N) v -= 2 * N;
-    if (v >= N) v -= N;
-    return v;
-}
+// (mod4, the residue of 0 <= v < 4N: opform_device.h)
 struct PhasePow2 {
     const float2* tw;
     __device__ __forceinline__ float2 row(int pos, int off, int N) const { return phase_tw(tw, pos, off, N); }     // off > 0
@@ -73,6 +68,13 @@ __device__ __forceinline__ PhasePow2 phase_src(const float2* tw, int) { return P
 __device__ __forceinline__ PhaseMod phase_src(const ModTabs& t, int p) { return PhaseMod{t.x[p], t.y[p]}; }
 template <bool MOD> struct TwArg { typedef const float2* __restrict__ type; };
 template <> struct TwArg<true> { typedef ModTabs type; };
+// the grouped spectra launch hosts the operator form's record (kspec_packed_body) as well: with a smooth axis its per-level tables ride
+// behind the per-problem ones
+struct ModTabsPk : ModTabs { PackTabs pk; };
+template <bool MOD> struct TwArgPk { typedef const float2* __restrict__ type; };
+template <> struct TwArgPk<true> { typedef ModTabsPk type; };
+__device__ __forceinline__ PackPhasePow2 pack_phase_src(const float2*) { return PackPhasePow2{}; }
+__device__ __forceinline__ PackPhaseMod pack_phase_src(const ModTabsPk& t) { return PackPhaseMod{t.pk}; }
 
 __device__ __forceinline__ float2 phase(const float2* tw, int pos, int off, int N, float sign)
 {
@@ -339,7 +341,7 @@ __global__ __launch_bounds__(320) void kspec_kernel(const float* __restrict__ ke
 #define AEFFT_X_KSPEC_W 1
 #endif
 template <int NK, int NL, int MU, bool MOD>
-__global__ __launch_bounds__(320, AEFFT_X_KSPEC_W) void kspec_group_kernel(const PrunedGroup g, const typename TwArg<MOD>::type tw, const PackArgs pk, const BiasUpdGroup bu, const int nbias_start)
+__global__ __launch_bounds__(320, AEFFT_X_KSPEC_W) void kspec_group_kernel(const PrunedGroup g, const typename TwArgPk<MOD>::type tw, const PackArgs pk, const BiasUpdGroup bu, const int nbias_start)
 {
     AEFFT_WGTIME(3);
     extern __shared__ float2 lds[];
@@ -353,10 +355,9 @@ __global__ __launch_bounds__(320, AEFFT_X_KSPEC_W) void kspec_group_kernel(const
     }
     if ((int)blockIdx.x >= g.start[g.n]) {
         // trailing workgroups: the bin-major copy of the spectra for the operator chain (opform_device.h), from the same taps
-        // (the operator form's record: power-of-two grids only, the launcher sends none with MOD)
-        if constexpr (!MOD && NK == NL && (NK == 3 || NK == 5)) {
+        if constexpr (NK == NL && (NK == 3 || NK == 5)) {
             const int lin = blockIdx.x - g.start[g.n];
-            kspec_packed_body<NK>(pk, lin % pk.nblk, lin / pk.nblk, lds);
+            kspec_packed_body<NK>(pk, pack_phase_src(tw), lin % pk.nblk, lin / pk.nblk, lds);
         }
         return;
     }
@@ -771,6 +772,24 @@ static hipError_t group_tabs(const PrunedGroup& g, ModTabs& t)
     return hipSuccess;
 }
 
+// the record's phase tables (PackTabs): a net with a smooth axis on ANY level takes N-point tables on every level and axis
+bool pack_mod(const PackArgs& g)
+{
+    for (int l = 0; l < g.L; ++l) if (grid_mod(g.Nx[l], g.Ny[l])) return true;
+    return false;
+}
+hipError_t pack_tabs(const PackArgs& g, PackTabs& t)
+{
+    if (g.L < 1 || g.L > 8) return hipErrorInvalidValue;
+    for (int l = 0; l < 8; ++l) {
+        const int k = l < g.L ? l : 0;                     // (unused levels: a valid pointer all the same)
+        hipError_t e = phase_table(g.Nx[k], &t.x[l]);
+        if (e == hipSuccess) e = phase_table(g.Ny[k], &t.y[l]);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
 // the grid has pruned transforms at all (what a net sizes its buffers by: AEFFT_F_NOPRUNESMOOTH may change on a live net)
 bool pruned_geometry(int Nk, int Nl, int Nx, int Ny)
 {
@@ -928,11 +947,12 @@ template <int NK, int NL> static hipError_t run_kspec_group(PrunedGroup& g, cons
     }
     bool has_g = false;                                   // (which instantiation: see gtaps_stage)
     for (int p = 0; p < g.n; ++p) has_g = has_g || g.gsrc[p].f != nullptr;
-    const bool mod = group_mod(g);                        // some problem has a smooth axis: every problem of the launch takes N-point tables
-    ModTabs mt{};
+    // some problem, or a level of the record, has a smooth axis: every problem of the launch and every level of the record takes N-point tables
+    const bool mod = group_mod(g) || (extra && pack_mod(*pk));
+    ModTabsPk mt{};
     if (mod) {
-        if (extra) return hipErrorInvalidValue;           // (the operator form's record: power-of-two grids only)
-        const hipError_t e = group_tabs(g, mt);
+        hipError_t e = group_tabs(g, mt);
+        if (e == hipSuccess && extra) e = pack_tabs(*pk, mt.pk);
         if (e != hipSuccess) return e;
     }
     if (lds > 64 * 1024) {
@@ -947,8 +967,8 @@ template <int NK, int NL> static hipError_t run_kspec_group(PrunedGroup& g, cons
     if (extra) lds = std::max(lds, kspec_packed_lds(NK));
     const int nb = bu ? bu->n : 0;
     if (mod) {
-        if (has_g) kspec_group_kernel<NK, NL, 1, true><<<dim3(total + nb), threads, lds, st>>>(g, mt, g_pack_none, nb ? *bu : g_bu_none, total);
-        else kspec_group_kernel<NK, NL, 2, true><<<dim3(total + nb), threads, lds, st>>>(g, mt, g_pack_none, nb ? *bu : g_bu_none, total);
+        if (has_g) kspec_group_kernel<NK, NL, 1, true><<<dim3(total + extra + nb), threads, lds, st>>>(g, mt, extra ? *pk : g_pack_none, nb ? *bu : g_bu_none, total + extra);
+        else kspec_group_kernel<NK, NL, 2, true><<<dim3(total + extra + nb), threads, lds, st>>>(g, mt, extra ? *pk : g_pack_none, nb ? *bu : g_bu_none, total + extra);
     }
     else if (has_g) kspec_group_kernel<NK, NL, 1, false><<<dim3(total + extra + nb), threads, lds, st>>>(g, tw, extra ? *pk : g_pack_none, nb ? *bu : g_bu_none, total + extra);
     else kspec_group_kernel<NK, NL, 2, false><<<dim3(total + extra + nb), threads, lds, st>>>(g, tw, extra ? *pk : g_pack_none, nb ? *bu : g_bu_none, total + extra);

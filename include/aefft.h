@@ -219,11 +219,19 @@ int aefft_net_create(aefft_ctx* ctx, const aefft_net_desc* desc, aefft_net** out
 /* aefft_net_create with options.  opts = 0 is exactly aefft_net_create.  AEFFT_NET_SMOOTH_SIZES: Nx, Ny may also be smooth sizes
  * (even, 10..2048, no prime factor above 5: 640 x 480, 1280 x 720, ...), mixed freely with power-of-two axes; every pair's pooled grid
  * must be even and >= 8 (pooling scales powers of two, kernels no larger than the grid as always) -- AEFFT_EINVAL names the rule otherwise
- * (480 over 5 pairs of scale 2: the 5th grid is 15).  A net with a smooth axis runs every step in the per-frame form: aefft_net_step_form
- * returns AEFFT_FORM_PER_FRAME (the operator forms need the pruned kernel transforms, which take power-of-two grids); a power-of-two net
+ * (480 over 5 pairs of scale 2: the 5th grid is 15).  A net with a smooth axis runs every step in the per-frame form unless it was also
+ * created with AEFFT_NET_SMOOTH_OPFORM: aefft_net_step_form returns AEFFT_FORM_PER_FRAME; a power-of-two net
  * created with the option runs exactly as one from aefft_net_create.  Every aefft_net_* entry
- * point works on it, and the net sizes all its workspaces here. */
-enum { AEFFT_NET_SMOOTH_SIZES = 1u << 0, AEFFT_NET_SPATIAL = 1u << 1 };
+ * point works on it, and the net sizes all its workspaces here.
+ * AEFFT_NET_SMOOTH_OPFORM (with AEFFT_NET_SMOOTH_SIZES): a net with a smooth axis runs aefft_net_step_grad / _apply in the operator form
+ * when it meets that form's other rules -- at most 3 input channels, every pair the same square 3x3 or 5x5 support, dD <= 256, dM <= 512,
+ * dD + dM <= 1024, Ny/2+1 <= 320 on every pair's grid -- and in AEFFT_FORM_OPERATOR_CHAIN when in addition the coarsest grid has at most
+ * 16384 bins and every dD, dM <= 128 (AEFFT_FORM_OPERATOR otherwise, and under AEFFT_F_NOCHAIN and its companions); aefft_net_step_form
+ * reports the form the net runs in.  A net that does not meet the rules (7x7 or 5x3 kernels, 4 input channels) runs in the per-frame form
+ * exactly as without the option.  AEFFT_F_NOOPFORM, AEFFT_F_NOQPATH and AEFFT_F_NOPRUNESMOOTH (the operator form needs the pruned kernel
+ * transforms) force the per-frame form, also on a live net.  The option has no effect on a power-of-two net, on a spatial net, or
+ * without AEFFT_NET_SMOOTH_SIZES (a smooth size then stays AEFFT_EINVAL). */
+enum { AEFFT_NET_SMOOTH_SIZES = 1u << 0, AEFFT_NET_SPATIAL = 1u << 1, AEFFT_NET_SMOOTH_OPFORM = 1u << 2 };
 /* AEFFT_NET_SPATIAL: the reference's coordinate-space training mode (autoencoder.cpp:135-150,171-201: Pool -> Conv_gpu per encoder,
  * Conv_gpu -> Pool(-s) per decoder, backprop_gpu / backprop_gpu_cc per pair) as a resident, batched net, with GPU semantics throughout
  * (cpu_semantics = 0 of the spatial ops above).  Same descriptor.  Any Nx, Ny; every pair's scale is an integer >= 1 that divides its

@@ -5,7 +5,9 @@
              the share of HBM peak -- the per-kernel split comes from a separate `rocprofv3 --kernel-trace --stats` run of this script
   training : cfg3-P2's net (D=3, maps 8/16/32/64, 5x5, s=2, B=32) at 640 x 480 (smooth sizes, per-frame form) and at 512^2 under NOOPFORM
              (the same per-frame form on powers of two: the yardstick), alternated: ms/step and frames/s; vga_640x480_full is the 640 x 480
-             net with the weight side on the full pad + R2C / C2R + shrink route (AEFFT_F_NOPRUNESMOOTH), the A/B of the pruned transforms
+             net with the weight side on the full pad + R2C / C2R + shrink route (AEFFT_F_NOPRUNESMOOTH), the A/B of the pruned transforms;
+             vga_640x480_opform is the 640 x 480 net created with AEFFT_NET_SMOOTH_OPFORM (operator form; left out, with a note in the
+             result, when AEFFT_LIB names a library from before the option)
 
     python tools/sizes_bench.py [--reps 20] [--steps 20] [--warmup 5]
     rocprofv3 --kernel-trace --stats -d DIR -o run -- python tools/sizes_bench.py --no-train --rounds 1     (per-kernel split, op level)
@@ -70,18 +72,26 @@ def op_level(ctx, planes, Nx, Ny, reps, rounds):
     return out
 
 
-NETS = (("vga_640x480", 640, 480, True), ("vga_640x480_full", 640, 480, True), ("p2_512x512_noopform", 512, 512, False), ("p2_512x512", 512, 512, False))
-FLAGS_OF = {"vga_640x480": [], "vga_640x480_full": ["NOPRUNESMOOTH"], "p2_512x512_noopform": ["NOOPFORM"], "p2_512x512": []}
+NETS = (("vga_640x480", 640, 480, True), ("vga_640x480_full", 640, 480, True), ("p2_512x512_noopform", 512, 512, False), ("p2_512x512", 512, 512, False),
+        ("vga_640x480_opform", 640, 480, True))
+FLAGS_OF = {"vga_640x480": [], "vga_640x480_full": ["NOPRUNESMOOTH"], "p2_512x512_noopform": ["NOOPFORM"], "p2_512x512": [], "vga_640x480_opform": []}
 
 
 def training(ctx, steps, warmup, rounds, only=None, extra=()):
     D, maps, Nk, s, B = 3, [8, 16, 32, 64], 5, 2, 32
     rng = np.random.default_rng(3)
     nets = {}
+    skipped = []
     for tag, Nx, Ny, smooth in NETS:
         if only and tag != only:
             continue
-        net = aefft.Net(ctx, D, Nx, Ny, maps, Nk, s, batch=B, smooth_sizes=smooth)
+        try:
+            net = aefft.Net(ctx, D, Nx, Ny, maps, Nk, s, batch=B, smooth_sizes=smooth, operator_form=tag.endswith("_opform"))
+        except RuntimeError:
+            if not tag.endswith("_opform"):
+                raise
+            skipped.append(tag)          # a library from before AEFFT_NET_SMOOTH_OPFORM refuses the option bit
+            continue
         dD = D
         for l, dM in enumerate(maps):
             net.set_pair(l, rng.uniform(-1, 1, (dM, dD, Nk, Nk)) * 0.05, rng.uniform(-1, 1, dM), rng.uniform(-1, 1, (dD, dM, Nk, Nk)) * 0.05,
@@ -114,7 +124,12 @@ def training(ctx, steps, warmup, rounds, only=None, extra=()):
         ctx.set_flags(*flags_of[tag])
         out[tag] = {"ms_per_step": round(ms, 4), "rounds_ms": [round(x, 4) for x in v], "frames_per_s": round(B / ms * 1e3, 1), "form": nets[tag][0].step_form()}
     ctx.set_flags()
+    if skipped:
+        out["skipped"] = skipped
     if not only:
+        if "vga_640x480_opform" in out:
+            out["step_ratio_opform_over_per_frame"] = round(out["vga_640x480_opform"]["ms_per_step"] / out["vga_640x480"]["ms_per_step"], 3)
+            out["step_ratio_opform_over_512_default"] = round(out["vga_640x480_opform"]["ms_per_step"] / out["p2_512x512"]["ms_per_step"], 3)
         out["step_ratio_vga_over_512"] = round(out["vga_640x480"]["ms_per_step"] / out["p2_512x512_noopform"]["ms_per_step"], 3)
         out["pixel_ratio"] = round(640 * 480 / 512 / 512, 3)
     for net, *_ in nets.values():
