@@ -90,6 +90,7 @@ SIGNATURES = {
     "aefft_net_step_grad_u8": (_i, [_vp, _vp, _fp]),
     "aefft_net_forward_u8": (_i, [_vp, _vp, _fp]),
     "aefft_net_infer": (_i, [_vp, _vp, _i, _vp, _i, _i, _fp]),
+    "aefft_net_decode": (_i, [_vp, _i, _fp, _vp, _i]),
     "aefft_net_set_input_ready": (_i, [_vp, _i]),
     "aefft_net_grad_buffer": (_i, [_vp, C.POINTER(_vp), C.POINTER(C.c_size_t)]),
     "aefft_net_step_form": (_i, [_vp]),
@@ -499,6 +500,14 @@ class Net:
         hp = -1 if hidden_pair is None else int(hidden_pair)
         self.ctx.check(self.L.aefft_net_infer(self.h, _ptr(frames), int(_is_u8(frames)), _ptr(recon), int(_is_u8(recon)), hp, _ptr(hidden)))
         return recon, hidden
+
+    def decode(self, code, hidden_pair, recon):
+        """The reconstruction from a stored hidden layer (aefft_net_decode): `code` is float32 [B][dM][Nx_l][Ny_l] of pair `hidden_pair`, as
+        Net.infer writes `hidden`; a uint8 `recon` receives clamp(round(v), 0, 255) (SpinToImage_C).  Operator-form nets (step_form) form the
+        decoding operator once per weight set and pair.  No frame stands behind the call: get_layer(s) raise until the next forward.
+        Returns recon."""
+        self.ctx.check(self.L.aefft_net_decode(self.h, int(hidden_pair), _ptr(code), _ptr(recon), int(_is_u8(recon))))
+        return recon
 
     def get_layer(self, layer):
         ch, nx, ny = C.c_int(), C.c_int(), C.c_int()

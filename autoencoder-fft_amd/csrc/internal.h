@@ -210,6 +210,19 @@ hipError_t launch_op_expand(const float2* A, const float2* Xf, float2* out, int 
 // H^_l = C_l A_l / dM (+ b_l Nx Ny on the affine column's DC bin): pair l's hidden layer as an operator [OPC][dM][P], from its input
 // operator A [OPC][dD][P] and the encoder spectrum C [dM][dD][P] (what conv_k gives on the basis frames); launch_op_expand then gives the frames' planes
 hipError_t launch_hidden_op(const float2* C, const float2* A, const float* b, float2* H, int dM, int dD, int Nx, int Ny, hipStream_t st);
+// Decode (decode_kernels.hip, aefft_net_decode): the remainder of the network from pair l's hidden layer as one affine operator per bin of
+// the coarsest grid, T [D][dM_l + 1][Pc] (last column: every bias below).  One stage per conv_k on the way, in the order the ROW vector
+// e_d^T F_0 F_1 .. F_{L-1} C_{L-1} .. C_{l+1} meets them: W [K][M][P] row-major over (in, out) -- F_j [dD][dM], C_j [dM][dD] as stored --
+// on the grid Nx x Ny, inv = 1 / (the conv's output channels), bias [K] of the conv, nn = Nx * Ny.
+constexpr int DEC_MAX_STAGES = 16;       // 2 L - 1 stages of a net of L <= 8 pairs (the operator forms' limit)
+constexpr int DEC_MAX_THREADS = 16384;   // bins in flight: sizes the row workspace ws [2][D][maxW][NT]
+constexpr double DEC_WS_BYTES = 16e6;     // ... which stays within this: wide rows take fewer bins in flight (the kernel's threads stride over the bins)
+struct DecodeStage { const float2* W; const float* bias; int K, M, Nx, Ny; long P; float inv, nn; };
+// maxW, NT: the column stride and thread count ws was ALLOCATED for; Tw: the rows T was allocated for (T [D][Tw][Pc] at least)
+struct DecodeOpArgs { DecodeStage st[DEC_MAX_STAGES]; int nst; float2* T; float2* ws; int D, NxC, NyC; long Pc; int NT, maxW, Tw; };
+hipError_t launch_decode_op(const DecodeOpArgs& g, hipStream_t st);
+// out[b][d][t] = sum_m T[d][m][t] h[b][m][t] + T[d][K][t]: h [B][K][Pc], out [B][D][Pc], D <= 3
+hipError_t launch_decode_apply(const float2* T, const float2* h, float2* out, int B, int D, int K, long Pc, hipStream_t st);
 struct OpMsePair {
     const float2 *A, *C, *F;   // A_l [OPC][dD][P]; the UPDATED kernel spectra C [dM][dD][P], F [dD][dM][P]
     const float2* G;           // nullable: G' = F.C/(dM dD) [dD][dD][P] of the updated weights -- then C and F are not read (opmse_gbody) ...

@@ -62,6 +62,12 @@ struct aefft_net {
     float2* Hhat = nullptr;    // [OPC][dM][P] of the largest pair: one pair's hidden layer as an operator, H^_l = C_l A_l / dM + bias
     int hid_pair = -1;         // ... of this pair
     bool hid_valid = false;    // ... and of the CURRENT weights
+    // decode (aefft_net_decode): the remainder of the network from one pair's hidden layer as an operator on the coarsest grid's bins
+    float2* That = nullptr;    // [D][dM_l + 1][Pc], sized for the widest pair: T^_l (decode_kernels.hip); null: D > OPC-1
+    float2* dec_ws = nullptr;  // [2][D][dec_w][dec_nt] rows in flight while decode_op_kernel forms it
+    int dec_nt = 0, dec_w = 0; // threads (bins in flight) and column stride (max dM + 1: the longest row with its affine element) it was allocated for
+    int dec_pair = -1;         // ... of this pair
+    bool dec_valid = false;    // ... and of the CURRENT weights
     float2* Wp = nullptr;      // [Pc][packE] bin-major copy of the kernel spectra the coarsest-grid chain items read (kspec_packed_kernel)
     aefft::PackArgs pack{};    // its description (static per net)
     bool packed_valid = false; // Wp belongs to the current weights
@@ -125,6 +131,7 @@ int ensure_spectra(aefft_net* n, Pair& q);
 // ---- spatial_net.hip (a net created with AEFFT_NET_SPATIAL: the entry points hand over to these) ------------------------
 int sp_create(aefft_ctx* ctx, const aefft_net_desc* d, aefft_net** out);
 int sp_forward(aefft_net* n, const float* frames_d, float* recon_d);
+int sp_decode(aefft_net* n, int l, const float* code_d, float* recon_d);
 int sp_step_grad(aefft_net* n, const float* frames_d, float* recon_d);
 int sp_step_apply(aefft_net* n, float del0, int maxdiff, int sym, float grad_scale, float* mse_d);
 int sp_get_layer(aefft_net* n, int layer, float* out_d, int* ch, int* nx, int* ny);

@@ -93,7 +93,7 @@ static int net_create(aefft_ctx* ctx, const aefft_net_desc* d, unsigned opts, ae
     n->smooth_opform = smooth && (opts & AEFFT_NET_SMOOTH_OPFORM) && (fft_size_smooth(d->Nx) || fft_size_smooth(d->Ny));
     n->pr.resize(n->L);
     int dD = d->D, nx = d->Nx, ny = d->Ny;
-    size_t maxS = 0, maxBDP = 0, maxW = 0, maxReal = 0, goff = 0, maxMid = 0, maxDen = 0, maxSmall = 0, maxHid = 0, soff = 2 * (size_t)d->npairs;
+    size_t maxS = 0, maxBDP = 0, maxW = 0, maxReal = 0, goff = 0, maxMid = 0, maxDen = 0, maxSmall = 0, maxHid = 0, maxDM = 0, soff = 2 * (size_t)d->npairs;
     std::vector<size_t> esoff(d->npairs);
     int rc = AEFFT_OK;
     for (int l = 0; l < n->L && rc == AEFFT_OK; ++l) {
@@ -139,6 +139,7 @@ static int net_create(aefft_ctx* ctx, const aefft_net_desc* d, unsigned opts, ae
         maxMid = std::max(maxMid, (size_t)q.dM * q.dD * q.Nx * (q.Ny / 2));
         maxMid = std::max(maxMid, (size_t)n->B * q.dM * q.Nx * (q.Ny / 2));      // (a hidden layer of the whole batch: aefft_net_infer)
         maxHid = std::max(maxHid, (size_t)OPC * q.dM * q.P);
+        maxDM = std::max(maxDM, (size_t)q.dM);
         maxDen = std::max(maxDen, gradient_diff_ws_floats(q.dM, q.dD, q.Nk, q.Nl));
         maxSmall = std::max(maxSmall, 2 * nk + q.dM + q.dD + 64);
         dD = q.dM; nx = q.Nx; ny = q.Ny;
@@ -169,6 +170,20 @@ static int net_create(aefft_ctx* ctx, const aefft_net_desc* d, unsigned opts, ae
                 // frozen-weight inference sizes what it needs here: the hidden-layer operator, and the reconstruction's per-frame spectra where
                 // launch_recon writes them out (its 16 MB rule)
                 if (rc == AEFFT_OK) rc = net_alloc_t(n, &n->Hhat, maxHid);
+                // ... and decode (aefft_net_decode) its operator T^_l on the coarsest grid's bins, for the widest pair, with the rows in flight
+                // while it is formed -- on nets whose shapes can take an operator form at all (the part of op_eligible no switch moves).  A row
+                // is a stage's OUTPUT with its affine element, at most max dM + 1 long (stage 0 reads row d of F_0 directly: D is no row
+                // length); the bins in flight are cut down so that the workspace stays within DEC_WS_BYTES.
+                bool dec_shapes = n->L <= 8 && q0.Nk == q0.Nl && (q0.Nk == 3 || q0.Nk == 5);
+                for (const Pair& q : n->pr) if (q.Nk != q0.Nk || q.Nl != q0.Nl || q.dD > 256 || q.dM > 512 || q.dD + q.dM > 1024) dec_shapes = false;
+                if (dec_shapes) {
+                    const long PcD = n->pr[n->L - 1].P;
+                    n->dec_w = (int)maxDM + 1;
+                    const long fit = (long)(DEC_WS_BYTES / (2.0 * n->D * n->dec_w * sizeof(float2))) / 64 * 64;
+                    n->dec_nt = (int)std::max<long>(64, std::min<long>({(PcD + 63) / 64 * 64, (long)DEC_MAX_THREADS, fit}));
+                    if (rc == AEFFT_OK) rc = net_alloc_t(n, &n->That, (size_t)n->D * n->dec_w * PcD);
+                    if (rc == AEFFT_OK) rc = net_alloc_t(n, &n->dec_ws, 2 * (size_t)n->D * n->dec_w * n->dec_nt);
+                }
                 // (launch_recon's own test: O^_0 lives on the coarsest pair's grid -- of a one-pair net, pair 0's)
                 const Pair& qc0 = n->pr[n->L - 1];
                 if (rc == AEFFT_OK && (double)n->B * q0.dD * qc0.P * 8.0 > 16e6) {
@@ -271,7 +286,7 @@ extern "C" int aefft_net_set_pair(aefft_net* n, int l, const float* c_h, const f
     HIPCHK(ctx, hipMemcpyAsync(q.b, b_h, q.dM * 4, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(q.p, p_h, q.dD * 4, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // host buffers may be pageable / reused by the caller
-    q.spectra_valid = false; q.G_valid = false; n->packed_valid = false; n->chain_valid = false; n->ops_valid = false; n->hid_valid = false;
+    q.spectra_valid = false; q.G_valid = false; n->packed_valid = false; n->chain_valid = false; n->ops_valid = false; n->hid_valid = false; n->dec_valid = false;
     return AEFFT_OK;
 }
 
@@ -345,7 +360,7 @@ extern "C" int aefft_net_load_spectra(aefft_net* n, int l, const float* C_h, con
     HIPCHK(ctx, hipMemcpyAsync(q.b, b_h, q.dM * 4, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(q.p, p_h, q.dD * 4, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    q.spectra_valid = true; q.G_valid = false; n->packed_valid = false; n->chain_valid = false; n->ops_valid = false; n->hid_valid = false;
+    q.spectra_valid = true; q.G_valid = false; n->packed_valid = false; n->chain_valid = false; n->ops_valid = false; n->hid_valid = false; n->dec_valid = false;
     RET_IF(aefft_kernel_export(ctx, reinterpret_cast<const float*>(q.C), q.c, q.dM, q.dD, q.Nk, q.Nl, q.Nx, q.Ny));
     RET_IF(aefft_kernel_export(ctx, reinterpret_cast<const float*>(q.F), q.f, q.dD, q.dM, q.Nk, q.Nl, q.Nx, q.Ny));
     return AEFFT_OK;

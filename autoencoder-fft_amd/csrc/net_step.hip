@@ -276,16 +276,18 @@ static int forward_chain(aefft_net* n, const FwdPlan& plan, bool* forked)
 }
 
 // pool -> conv per pair; B columns of the activation buffers
-static int forward_encoder(aefft_net* n, int B, bool lazy, bool op)
+// first: the pair to start at, its input X already in place (aefft_net_decode: no frame stands behind the call, so the innermost pair
+// does not take the collapsed operator's route either -- that launch also forms gradient terms of EVERY pair's input)
+static int forward_encoder(aefft_net* n, int B, bool lazy, bool op, int first = 0)
 {
     aefft_ctx* ctx = n->ctx;
     const int L = n->L;
-    for (int l = 0; l < L; ++l) {
+    for (int l = first; l < L; ++l) {
         Pair& q = n->pr[l];
         // the next pair's spectral down-sampling (pool_fft, :1346) is written by this conv's epilogue: no resize launch
         const bool fuse = (l + 1 < L) && n->pr[l + 1].s != 1 && n->fuse_crop && !flag(AEFFT_F_NOFUSECROP);
         q.H_stale = false;
-        if (lazy && !op && l == L - 1 && q.G_valid && !flag(AEFFT_F_NOGFWD)) {
+        if (lazy && !op && first == 0 && l == L - 1 && q.G_valid && !flag(AEFFT_F_NOGFWD)) {
             // innermost pair of a training step: its hidden layer feeds only its own decoder conv, and the previous step left
             // the collapsed operator of the CURRENT weights behind (G = F.C/(dM dD) in S, DC bias in beta): O = G X + beta below,
             // a quarter of the arithmetic and bytes of conv_k o conv_k, no H.
@@ -567,6 +569,101 @@ extern "C" int aefft_net_infer(aefft_net* n, const void* frames_d, int frames_u8
     return mark_step_point(n);
 }
 
+// ------------------------------------------------------------------------------------------
+// decode (include/aefft.h aefft_net_decode): layer 4L from a stored layer 2l+2
+// ------------------------------------------------------------------------------------------
+// T^_l of the CURRENT weights (decode_kernels.hip), cached until the weights or the pair change
+static int ensure_decode_op(aefft_net* n, int l)
+{
+    if (n->dec_valid && n->dec_pair == l) return AEFFT_OK;
+    aefft_ctx* ctx = n->ctx;
+    const int L = n->L;
+    if (!n->That || !n->dec_ws) return fail(ctx, AEFFT_ESTATE, "aefft_net_decode: operator form on a net created without the decode buffers");      // (cannot happen: net_create sizes them by op_eligible's shape rules)
+    // the planar spectra: where the step keeps them stale (spectra_valid false) the buffers are free, and stay marked stale -- the step's own
+    // choice between the planar spectra and the bin-major record is not touched (as infer_hidden_op)
+    for (int j = 0; j < L; ++j) if (!n->pr[j].spectra_valid) RET_IF(pair_spectra(n, n->pr[j]));
+    DecodeOpArgs g{};
+    double bytes = 0;
+    for (int j = 0; j < L; ++j) {            // e_d^T F_0 F_1 .. F_{L-1}
+        const Pair& q = n->pr[j];
+        g.st[g.nst++] = DecodeStage{q.F, q.p, q.dD, q.dM, q.Nx, q.Ny, q.P, 1.0f / (float)q.dD, (float)q.Nx * (float)q.Ny};
+    }
+    for (int j = L - 1; j > l; --j) {        // .. C_{L-1} .. C_{l+1}
+        const Pair& q = n->pr[j];
+        g.st[g.nst++] = DecodeStage{q.C, q.b, q.dM, q.dD, q.Nx, q.Ny, q.P, 1.0f / (float)q.dM, (float)q.Nx * (float)q.Ny};
+    }
+    for (int s = 0; s < g.nst; ++s) bytes += (double)g.st[s].K * g.st[s].M * n->Pc * 8.0;
+    // (stride, thread count and rows of T as net_create allocated them: launch_decode_op holds every stage's row against these)
+    g.T = n->That; g.ws = n->dec_ws; g.D = n->D; g.NxC = n->NxC; g.NyC = n->NyC; g.Pc = n->Pc; g.NT = n->dec_nt; g.maxW = n->dec_w; g.Tw = n->dec_w;
+    n->dec_valid = false;
+    RET_IF(launch_or_fail(ctx, KID_OPFORM, bytes + (double)n->D * (n->pr[l].dM + 1) * n->Pc * 8.0, "decode_op", [&] { return launch_decode_op(g, ctx->cur); }));
+    n->dec_pair = l; n->dec_valid = true;
+    return AEFFT_OK;
+}
+
+// OPERATOR / OPERATOR_CHAIN: R2C of the code cropped to the coarsest grid (into the pair's own hidden buffer), T^_l applied per bin into
+// pair 0's compact decoder output, the reconstruction's sparse inverse transform: five launches
+static int decode_operator(aefft_net* n, int l, const float* code_d, void* recon_d, bool out_u8)
+{
+    aefft_ctx* ctx = n->ctx;
+    Pair& q = n->pr[l];
+    Pair& q0 = n->pr[0];
+    RET_IF(ensure_decode_op(n, l));
+    RET_IF(do_r2c(ctx, code_d, q.H, (long)n->B * q.dM, q.Nx, q.Ny, n->NxC, n->NyC));
+    RET_IF(launch_or_fail(ctx, KID_OPFORM, ((double)n->D * (q.dM + 1) + (double)n->B * (q.dM + n->D)) * n->Pc * 8.0, "decode_apply",
+                          [&] { return launch_decode_apply(n->That, q.H, q0.Oc, n->B, n->D, q.dM, n->Pc, ctx->cur); }));
+    // (the two activation buffers written: in the operator form without the chain launch they held operators of the current weights;
+    // the chain form's operator sets are buffers of their own)
+    n->ops_valid = false;
+    return do_c2r(ctx, q0.Oc, recon_d, (long)n->B * n->D, n->NxC, n->NyC, n->Nx, n->Ny, 1.0f / ((float)n->Nx * (float)n->Ny), WS_MID, nullptr, out_u8);
+}
+
+// PER_FRAME: R2C of the code straight onto the next pair's grid (its pooling is the transform's fused crop), the lazy per-frame forward
+// from there, the reconstruction
+static int decode_per_frame(aefft_net* n, int l, const float* code_d, void* recon_d, bool out_u8)
+{
+    aefft_ctx* ctx = n->ctx;
+    const int L = n->L;
+    Pair& q = n->pr[l];
+    BiasColGuard bias_col(ctx, 0);
+    n->xx_done = false; n->ox_done = 0;
+    n->op_state = false; n->op_chain = false; n->act_stale = false; n->ops_valid = false;
+    for (int j = 0; j < L; ++j) RET_IF(ensure_spectra(n, n->pr[j]));
+    if (l + 1 < L) {
+        const Pair& nx = n->pr[l + 1];       // (scale 1: nx.X is q.H and the grids are equal)
+        RET_IF(do_r2c(ctx, code_d, nx.X, (long)n->B * q.dM, q.Nx, q.Ny, nx.Nx, nx.Ny));
+        q.H_stale = nx.X != q.H;
+        RET_IF(forward_encoder(n, n->B, true, false, l + 1));
+    } else {
+        RET_IF(do_r2c(ctx, code_d, q.H, (long)n->B * q.dM, q.Nx, q.Ny, q.Nx, q.Ny));
+        q.H_stale = false;
+    }
+    RET_IF(forward_decoder(n, n->B, true, false));
+    return launch_recon(n, recon_d, WS_MID, out_u8);
+}
+
+extern "C" int aefft_net_decode(aefft_net* n, int hidden_pair, const float* code_d, void* recon_d, int recon_u8)
+{
+    if (!n) return AEFFT_EINVAL;
+    aefft_ctx* ctx = n->ctx;
+    if (!code_d || !recon_d) return fail(ctx, AEFFT_EINVAL, "aefft_net_decode: null code or reconstruction");
+    if (hidden_pair < 0 || hidden_pair >= n->L) return fail(ctx, AEFFT_EINVAL, "aefft_net_decode: hidden_pair outside 0..L-1");
+    if (!aligned16p(code_d) || !aligned16p(recon_d)) return fail(ctx, AEFFT_EINVAL, "aefft_net_decode: pointers must be 16-byte aligned");
+    if (n->spatial) {
+        if (recon_u8) return sp_refuse(n, "aefft_net_decode with 8-bit pixels");
+        return sp_decode(n, hidden_pair, code_d, static_cast<float*>(recon_d));
+    }
+    RET_IF(join_recon(ctx));
+    // no frame stands behind the call: a pending step_grad ends, and the layer exports wait for the next forward
+    n->have_grad = false; n->have_forward = false;
+    n->recon_deferred = nullptr;
+    if (op_eligible(n)) RET_IF(decode_operator(n, hidden_pair, code_d, recon_d, recon_u8 != 0));
+    else RET_IF(decode_per_frame(n, hidden_pair, code_d, recon_d, recon_u8 != 0));
+    // (the call reads no input spectra; the end-of-step event is recorded behind it all the same, as aefft_net_infer does, so that a
+    // decode that one day does cannot race the prefetched input transform)
+    return mark_step_point(n);
+}
+
 // expand a decoder output that the training-step forward kept on its support only
 static int ensure_O(aefft_net* n, Pair& q)
 {
@@ -665,7 +762,7 @@ extern "C" int aefft_net_train_pair(aefft_net* n, int l, int n_iter, float del0,
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     }
     q.G_valid = false; n->packed_valid = false; n->chain_valid = false;         // the burst changed this pair's weights (and used S)
-    n->ops_valid = false; n->hid_valid = false;
+    n->ops_valid = false; n->hid_valid = false; n->dec_valid = false;
     return mark_step_point(n);
 }
 
@@ -1159,7 +1256,7 @@ static int frame_mse(aefft_net* n, float gscale, float* mse_d)
 static int apply_grouped(aefft_net* n, float del, int maxdiff, int sym, float gscale, float* mse_d)
 {
     for (auto& q : n->pr) q.G_valid = false;          // the weights are about to change
-    n->packed_valid = false; n->chain_valid = false; n->ops_valid = false; n->hid_valid = false;
+    n->packed_valid = false; n->chain_valid = false; n->ops_valid = false; n->hid_valid = false; n->dec_valid = false;
     ApplyRoute rt = apply_route(n, maxdiff, sym);
     UpdateGroup ug{};
     if (rt.grouped) {

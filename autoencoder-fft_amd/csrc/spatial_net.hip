@@ -94,13 +94,14 @@ int aefft::sp_create(aefft_ctx* ctx, const aefft_net_desc* d, aefft_net** out)
 // The forward: per encoder ONE launch (Pool on load, the pooled layer published), per decoder ONE launch (the inner decoder's output
 // up-sampled on load; pair 0's also writes the reconstruction).  Shapes the tiled convolutions do not serve decline the fused launch and
 // run Pool / Pool(-s) as launches of their own around the plain convolution.
-static int sp_run_forward(aefft_net* n, const float* frames_d, float* recon_d)
+// first > 0 (aefft_net_decode): the encoders from pair `first` on, reading the stored layer 2*first (pair first-1's hidden layer); no frames.
+static int sp_run_forward(aefft_net* n, const float* frames_d, float* recon_d, int first = 0)
 {
     aefft_ctx* ctx = n->ctx;
     const int L = n->L, B = n->B;
-    if (!frames_d) return fail(ctx, AEFFT_EINVAL, "aefft_net_forward / step_grad: null frames");
-    const float* x = frames_d;
-    for (int l = 0; l < L; ++l) {
+    if (!frames_d && first == 0) return fail(ctx, AEFFT_EINVAL, "aefft_net_forward / step_grad: null frames");
+    const float* x = first ? n->pr[first - 1].Lhid : frames_d;
+    for (int l = first; l < L; ++l) {
         Pair& q = n->pr[l];
         int ak, al;
         sp_geom(q, &ak, &al);
@@ -149,11 +150,22 @@ static int sp_run_forward(aefft_net* n, const float* frames_d, float* recon_d)
     }
     n->last_frames = frames_d;
     n->last_frames_u8 = false;
-    n->have_forward = true;
+    n->have_forward = first == 0;
     return AEFFT_OK;
 }
 
 int aefft::sp_forward(aefft_net* n, const float* frames_d, float* recon_d) { return sp_run_forward(n, frames_d, recon_d); }
+
+// aefft_net_decode: the code becomes the stored layer 2l+2 and the coordinate-space sequence runs from there.  No frame stands behind the
+// call: a pending step_grad ends and the layer exports wait for the next forward.
+int aefft::sp_decode(aefft_net* n, int l, const float* code_d, float* recon_d)
+{
+    aefft_ctx* ctx = n->ctx;
+    const Pair& q = n->pr[l];
+    HIPCHK(ctx, hipMemcpyAsync(q.Lhid, code_d, sizeof(float) * n->B * q.dM * q.Nx * q.Ny, hipMemcpyDeviceToDevice, ctx->cur));
+    n->have_grad = false;
+    return sp_run_forward(n, nullptr, recon_d, l + 1);
+}
 
 // forward, then per pair backprop_gpu's batch-mean gradients (in = layer 2l+1, out = layer 4L-1-2l, hin = layer 2l+2) straight into the
 // pair's slice of the packed buffer, then the per-pair MSE into the buffer's tail

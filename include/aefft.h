@@ -356,6 +356,28 @@ int aefft_net_forward_u8(aefft_net* net, const unsigned char* frames_d, float* r
  * Spatial net: float frames and float outputs only (sp_forward; hidden_d from the stored layer); any 8-bit argument is AEFFT_EINVAL.
  * AEFFT_EINVAL: null net or frames, both outputs null, hidden_d with hidden_pair outside 0..L-1, a pointer not 16-byte aligned. */
 int aefft_net_infer(aefft_net* net, const void* frames_d, int frames_u8, void* recon_d, int recon_u8, int hidden_pair, float* hidden_d);
+/* Decode: the reconstruction from a STORED hidden layer -- the other half of aefft_net_infer(hidden_pair = l, hidden_d).  code_d
+ * [B][dM_l][Nx_l][Ny_l] float, l = hidden_pair: layer 2l+2 in coordinate space, shape and layout as aefft_net_infer writes hidden_d (stored,
+ * transmitted or edited since: it need not be an encoder output).  recon_d [B][D][Nx][Ny] float, or unsigned char when recon_u8 under
+ * SpinToImage_C's rule as in aefft_net_infer.  Both pointers 16-byte aligned; B is the net's batch.
+ * The result is layer 4L of autoenc_fft (fft_backproplib.cu:1331-1376) run from its loop index n = l+1 with freq = fft(code), on the
+ * CURRENT weights: pool then conv_k with c_n for the pairs below l, conv_k with f_n then pool(-s) for every decoder down to pair 0.
+ * The call runs in the form aefft_net_step_form reports.  OPERATOR / OPERATOR_CHAIN: every pooling crop below the code discards the bins
+ * outside the coarsest grid, so the remainder of the network is one affine operator T^_l [D][dM_l + 1] per bin of that grid (the last
+ * column carries every bias below).  It is formed by one launch from the kernel spectra and cached until aefft_net_set_pair,
+ * aefft_net_load_spectra, aefft_net_step_apply or aefft_net_train_pair change the weights, or hidden_pair changes; any other call is
+ * five launches: the code's transform with the crop to the coarsest grid fused (2), the per-bin product (1), the reconstruction's
+ * sparse inverse transform (2).  PER_FRAME: the code's transform, then the lazy per-frame forward from pair l+1's pooling onward and the
+ * reconstruction, with the contraction kernels of the step.
+ * State: the call ends a pending aefft_net_step_grad (aefft_net_step_apply then fails with AEFFT_ESTATE).  No frame stands behind a
+ * decode: aefft_net_get_layer(s) return AEFFT_ESTATE until the next aefft_net_forward, aefft_net_infer or aefft_net_step_grad.  Training
+ * is not disturbed: operator sets, the chain carried ahead, the double-buffered input spectra, the cached hidden-layer operator of
+ * aefft_net_infer and the deferred MSE sums are left so that the next aefft_net_step_grad / _apply give bit for bit what they would have
+ * given without the call.  Everything is ordered on the context stream, whatever the pipelining switches and aefft_net_set_input_ready
+ * say.  No host synchronisation, no allocation (sized by aefft_net_create*).
+ * Spatial net: the coordinate-space sequence from layer 2l+2 (float only; recon_u8 is AEFFT_EINVAL).
+ * AEFFT_EINVAL: null net, code or reconstruction, hidden_pair outside 0..L-1, a pointer not 16-byte aligned. */
+int aefft_net_decode(aefft_net* net, int hidden_pair, const float* code_d, void* recon_d, int recon_u8);
 /* Opt-in input prefetch for pipelined training loops.  enable = 1 asserts that the frames handed to
  * aefft_net_step_grad are COMPLETE in device memory when the call is made (not merely ordered on the
  * context stream, e.g. a loader that synchronises its own copy stream): their R2C then runs on an
