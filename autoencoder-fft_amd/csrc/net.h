@@ -1,5 +1,6 @@
-// The resident network (aefft_net) and its pairs, shared by net.hip (lifetime, weights and spectra, chain set-up, layer exports)
-// and net_step.hip (forward, bursts, training step), with the helpers one of the two defines for the other.  Nothing here is exported.
+// The resident network (aefft_net) and its pairs, shared by net.hip (lifetime, weights and spectra, chain set-up, layer exports),
+// net_forward.hip (forward, inference, decode) and net_step.hip (bursts, training step): the rules more than one of them applies, each
+// stated once, and the helpers one unit defines for another.  Nothing here is exported.
 #pragma once
 #include "host.h"
 
@@ -17,7 +18,7 @@ struct Pair {
     bool spectra_valid;
     bool H_stale = false;    // the last (lazy) forward produced only the pooled part of H: recompute before reading H
     float2* G = nullptr;     // [dD][dD][P] collapsed pair operator F.C/(dM dD) (post-update MSE; innermost pair's forward)
-    bool G_valid = false;    // G and beta (its DC bias) belong to the CURRENT weights (left by aefft_net_step_apply)
+    bool G_valid = false;    // G and beta (its DC bias) belong to the CURRENT weights (left by aefft_net_step_apply; dropped by weights_changed)
     float* beta = nullptr;   // [dD]
     float* Q = nullptr;      // [dD][dD][Qn][T*T], T = 2Nk-1: pruned inverse transform of S (weight_kernels.hip), Qn row-chunk partial sums
     int Qn = 1;
@@ -55,22 +56,22 @@ struct aefft_net {
     bool act_stale = false;    // the activation buffers do not hold the last forward's frames (ensure_frames expands them from the operators)
     bool upd_after_fwd = false; // aefft_net_step_apply has changed the weights since the step's forward: a layer export forms a skipped hidden layer with
                                // the encoder of THAT forward, recovered as w + D (the momentum buffer holds the step that was applied)
-    bool chain_valid = false;  // set op_set holds the operators of the CURRENT weights
+    bool chain_valid = false;  // set op_set holds the operators of the CURRENT weights (weights_changed)
     int op_set = 0, op_fwd = 0;
     // frozen-weight inference (aefft_net_infer): what it caches beside the operator sets
-    bool ops_valid = false;    // operator form without the chain launch: the activation buffers hold the operators of the CURRENT weights
+    bool ops_valid = false;    // operator form without the chain launch: the activation buffers hold the operators of the CURRENT weights (weights_changed)
     float2* Hhat = nullptr;    // [OPC][dM][P] of the largest pair: one pair's hidden layer as an operator, H^_l = C_l A_l / dM + bias
     int hid_pair = -1;         // ... of this pair
-    bool hid_valid = false;    // ... and of the CURRENT weights
+    bool hid_valid = false;    // ... and of the CURRENT weights (weights_changed)
     // decode (aefft_net_decode): the remainder of the network from one pair's hidden layer as an operator on the coarsest grid's bins
     float2* That = nullptr;    // [D][dM_l + 1][Pc], sized for the widest pair: T^_l (decode_kernels.hip); null: D > OPC-1
     float2* dec_ws = nullptr;  // [2][D][dec_w][dec_nt] rows in flight while decode_op_kernel forms it
     int dec_nt = 0, dec_w = 0; // threads (bins in flight) and column stride (max dM + 1: the longest row with its affine element) it was allocated for
     int dec_pair = -1;         // ... of this pair
-    bool dec_valid = false;    // ... and of the CURRENT weights
+    bool dec_valid = false;    // ... and of the CURRENT weights (weights_changed)
     float2* Wp = nullptr;      // [Pc][packE] bin-major copy of the kernel spectra the coarsest-grid chain items read (kspec_packed_kernel)
     aefft::PackArgs pack{};    // its description (static per net)
-    bool packed_valid = false; // Wp belongs to the current weights
+    bool packed_valid = false; // Wp belongs to the CURRENT weights (weights_changed)
     float* grad = nullptr; size_t grad_n = 0;
     float* scratch = nullptr;  // [mse_pre[L] | mse_post[L] | es of pair 0 (2*dD) | es of pair 1 | ...], zeroed once per step
     size_t scratch_n = 0;
@@ -139,7 +140,53 @@ int sp_last_mse(aefft_net* n, float* mse_d);
 int sp_refuse(aefft_net* n, const char* entry);     // AEFFT_EINVAL: `entry` does not apply to a spatial net
 
 // ---- net_step.hip ----------------------------------------------------------------------
-int ensure_frames(aefft_net* n);
 int mark_step_point(aefft_net* n);
+
+// ---- net_forward.hip -------------------------------------------------------------------
+int ensure_frames(aefft_net* n);
+
+// What follows was local to one file while that held the forward and the step: it stays out of the library's symbol table (an inline function
+// the compiler does not inline would be a weak symbol of it)
+#pragma GCC visibility push(hidden)
+// ---- rules that more than one unit applies, each stated once ---------------------------
+// The weights of pair `only` (nullptr: of every pair) change: A NEW CACHE OF THE WEIGHTS IS CLEARED HERE, and nowhere else.  Not in the list:
+// Pair::spectra_valid (the caller knows whether it wrote taps or spectra) and upd_after_fwd (which is about the last forward).
+inline void weights_changed(aefft_net* n, Pair* only)
+{
+    for (Pair& q : n->pr) if (!only || only == &q) q.G_valid = false;
+    n->packed_valid = n->chain_valid = n->ops_valid = n->hid_valid = n->dec_valid = false;
+}
+// kernel supports of the Q-path gradient and the operator form: square 3x3 or 5x5; every pair has pair 0's support
+inline bool qpath_support(int Nk, int Nl) { return Nk == Nl && (Nk == 3 || Nk == 5); }
+inline bool same_supports(const aefft_net* n) { for (const Pair& q : n->pr) if (q.Nk != n->pr[0].Nk || q.Nl != n->pr[0].Nl) return false; return true; }
+// shapes that can take an operator form at all (the part of op_eligible no switch moves; net_create sizes the decode buffers by it): the
+// channel counts the operator-form kernels' LDS tiles take (msgrad_kernel: 2*OPC*dD*8 complex; opmse: OPC*(dD+dM)*4), 8 pairs, one Q-path support
+inline bool op_shapes(const aefft_net* n)
+{
+    for (const Pair& q : n->pr) if (q.dD > 256 || q.dM > 512 || q.dD + q.dM > 1024) return false;
+    return n->L <= 8 && qpath_support(n->pr[0].Nk, n->pr[0].Nl) && same_supports(n);
+}
+// an operator-form reconstruction above this size writes its per-frame spectra out (launch_recon; net_create sizes their buffer by it)
+#ifndef AEFFT_X_RECON_EXPAND_BYTES
+#define AEFFT_X_RECON_EXPAND_BYTES 16e6      // (experiment builds, tools/mkx.sh: 0 sends every reconstruction through the stored planes)
+#endif
+// where pair q's decoder output of the last forward lies: O on its own grid, or Oc on the coarsest grid's support (O_stale); its support term
+struct OutView { const float2* O; int nx, ny; long P; };
+inline OutView out_view(const aefft_net* n, const Pair& q) { return q.O_stale ? OutView{q.Oc, n->NxC, n->NyC, n->Pc} : OutView{q.O, q.Nx, q.Ny, q.P}; }
+inline Contract mk_OX(const aefft_net* n, const Pair& q, int B) { const OutView v = out_view(n, q); return mk_OX(v.O, q.X, q.S, B, q.dD, q.P, v.P, q.Nx, q.Ny, v.nx, v.ny); }
+// operator form: where pair l's operators of the step in progress are (A_l [OPC][dD][P], O^_l [OPC][dD][PO] on the grid nxo x nyo): op_view
+struct OpView { const float2 *A, *O; int nxo, nyo; long PO; };
+inline bool op_mode(const aefft_net* n) { return n->op_state || n->op_chain; }
+
+// ---- net_forward.hip, for net_step.hip -------------------------------------------------
+bool chain_form(const aefft_net* n);       // the step's forward is one chain launch: Wp && (compact || L == 1) && the switches allow it
+bool op_eligible(const aefft_net* n);      // the step runs in operator form
+OpView op_view(const aefft_net* n, int l);
+int cc_problems(aefft_net* n, PrunedGroup& pg, int first, double* bytes);
+int ensure_packed(aefft_net* n);
+void fill_chain(aefft_net* n, ChainArgs& ca, int set, double* bytes);
+int launch_recon(aefft_net* n, void* recon_d, int wsid, bool out_u8 = false);
+int net_forward(aefft_net* n, const float* frames_d, bool u8, float* recon_d, bool lazy, bool op = false, bool infer = false);
+#pragma GCC visibility pop
 
 }  // namespace aefft

@@ -1,6 +1,6 @@
 // C-ABI layer (include/aefft.h), resident network: create / destroy, the weight and spectra accessors, the operator chain's set-up
-// (build_chain_items) and the layer exports (aefft_net_get_layer*, aefft_net_layers_layout, aefft_magnitude).  The forward, the bursts
-// and the training step are in net_step.hip.
+// (build_chain_items) and the layer exports (aefft_net_get_layer*, aefft_net_layers_layout, aefft_magnitude).  The forward, inference
+// and decode are in net_forward.hip, the bursts and the training step in net_step.hip.
 #include "net.h"
 
 #include <algorithm>
@@ -34,8 +34,8 @@ static int build_chain_items(aefft_net* n)
     for (int l = 0; l + 1 < L; ++l) dims_ok = dims_ok && 2 * n->pr[l].dM * (int)OPC * 8 <= 6144;
     if (!dims_ok || n->pr[L - 1].P > 16384) return AEFFT_OK;
     // the bin-major copy for the coarsest-grid items: C_0 .. C_{L-1}, F_{L-1} .. F_0 in chain order, segments padded to even sizes
-    bool pk = n->pr[0].Nk == n->pr[0].Nl && (n->pr[0].Nk == 3 || n->pr[0].Nk == 5) && 2 * L <= 16;
-    for (const Pair& q : n->pr) pk = pk && q.Nk == n->pr[0].Nk && q.Nl == n->pr[0].Nk && (((q.dM * q.dD + 1) & ~1) <= CH_VMAX * CH_VMAX);      // (matrices are read from the record in place: only the row counts are bounded)
+    bool pk = qpath_support(n->pr[0].Nk, n->pr[0].Nl) && same_supports(n) && 2 * L <= 16;
+    for (const Pair& q : n->pr) pk = pk && (((q.dM * q.dD + 1) & ~1) <= CH_VMAX * CH_VMAX);      // (matrices are read from the record in place: only the row counts are bounded)
     if (pk) {
         PackArgs& pa = n->pack;
         int off = 0, ns = 0;
@@ -168,15 +168,13 @@ static int net_create(aefft_ctx* ctx, const aefft_net_desc* d, unsigned opts, ae
                 if (rc == AEFFT_OK && launch_basis_fill(n->A0hat, q0.dD, q0.P, ctx->stream) != hipSuccess) rc = fail(ctx, AEFFT_EHIP, "basis_fill");
                 if (rc == AEFFT_OK) rc = build_chain_items(n);
                 // frozen-weight inference sizes what it needs here: the hidden-layer operator, and the reconstruction's per-frame spectra where
-                // launch_recon writes them out (its 16 MB rule)
+                // launch_recon writes them out (AEFFT_X_RECON_EXPAND_BYTES)
                 if (rc == AEFFT_OK) rc = net_alloc_t(n, &n->Hhat, maxHid);
                 // ... and decode (aefft_net_decode) its operator T^_l on the coarsest grid's bins, for the widest pair, with the rows in flight
-                // while it is formed -- on nets whose shapes can take an operator form at all (the part of op_eligible no switch moves).  A row
+                // while it is formed -- on nets whose shapes can take an operator form at all (op_shapes).  A row
                 // is a stage's OUTPUT with its affine element, at most max dM + 1 long (stage 0 reads row d of F_0 directly: D is no row
                 // length); the bins in flight are cut down so that the workspace stays within DEC_WS_BYTES.
-                bool dec_shapes = n->L <= 8 && q0.Nk == q0.Nl && (q0.Nk == 3 || q0.Nk == 5);
-                for (const Pair& q : n->pr) if (q.Nk != q0.Nk || q.Nl != q0.Nl || q.dD > 256 || q.dM > 512 || q.dD + q.dM > 1024) dec_shapes = false;
-                if (dec_shapes) {
+                if (op_shapes(n)) {
                     const long PcD = n->pr[n->L - 1].P;
                     n->dec_w = (int)maxDM + 1;
                     const long fit = (long)(DEC_WS_BYTES / (2.0 * n->D * n->dec_w * sizeof(float2))) / 64 * 64;
@@ -186,7 +184,7 @@ static int net_create(aefft_ctx* ctx, const aefft_net_desc* d, unsigned opts, ae
                 }
                 // (launch_recon's own test: O^_0 lives on the coarsest pair's grid -- of a one-pair net, pair 0's)
                 const Pair& qc0 = n->pr[n->L - 1];
-                if (rc == AEFFT_OK && (double)n->B * q0.dD * qc0.P * 8.0 > 16e6) {
+                if (rc == AEFFT_OK && (double)n->B * q0.dD * qc0.P * 8.0 > AEFFT_X_RECON_EXPAND_BYTES) {
                     n->recon_exp_n = (size_t)n->B * q0.dD * qc0.P;
                     rc = net_alloc_t(n, &n->recon_exp, n->recon_exp_n);
                 }
@@ -199,7 +197,7 @@ static int net_create(aefft_ctx* ctx, const aefft_net_desc* d, unsigned opts, ae
                 if (rc == AEFFT_OK) rc = net_alloc_t(n, &q.beta, (size_t)q.dD);
                 if (q.P == n->Pc) q.Oc = q.O;            // already on the coarsest grid: nothing to compact
                 else rc = net_alloc_t(n, &q.Oc, (size_t)n->Bc * q.dD * n->Pc);
-                if (rc == AEFFT_OK && q.Nk == q.Nl && (q.Nk == 3 || q.Nk == 5)) {
+                if (rc == AEFFT_OK && qpath_support(q.Nk, q.Nl)) {
                     const size_t tt = (size_t)(2 * q.Nk - 1) * (2 * q.Nk - 1);
                     q.Qn = kgrad_group_chunks((long)q.dD * q.dD, q.Nx, q.Ny);       // room for the row chunks' partial sums
                     rc = net_alloc_t(n, &q.Q, (size_t)q.dD * q.dD * tt * q.Qn);
@@ -286,7 +284,7 @@ extern "C" int aefft_net_set_pair(aefft_net* n, int l, const float* c_h, const f
     HIPCHK(ctx, hipMemcpyAsync(q.b, b_h, q.dM * 4, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(q.p, p_h, q.dD * 4, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // host buffers may be pageable / reused by the caller
-    q.spectra_valid = false; q.G_valid = false; n->packed_valid = false; n->chain_valid = false; n->ops_valid = false; n->hid_valid = false; n->dec_valid = false;
+    q.spectra_valid = false; weights_changed(n, &q);
     return AEFFT_OK;
 }
 
@@ -360,7 +358,7 @@ extern "C" int aefft_net_load_spectra(aefft_net* n, int l, const float* C_h, con
     HIPCHK(ctx, hipMemcpyAsync(q.b, b_h, q.dM * 4, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(q.p, p_h, q.dD * 4, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    q.spectra_valid = true; q.G_valid = false; n->packed_valid = false; n->chain_valid = false; n->ops_valid = false; n->hid_valid = false; n->dec_valid = false;
+    q.spectra_valid = true; weights_changed(n, &q);
     RET_IF(aefft_kernel_export(ctx, reinterpret_cast<const float*>(q.C), q.c, q.dM, q.dD, q.Nk, q.Nl, q.Nx, q.Ny));
     RET_IF(aefft_kernel_export(ctx, reinterpret_cast<const float*>(q.F), q.f, q.dD, q.dM, q.Nk, q.Nl, q.Nx, q.Ny));
     return AEFFT_OK;
@@ -412,8 +410,8 @@ extern "C" int aefft_net_get_layer(aefft_net* n, int layer, float* out_d, int* c
     } else {
         const int nn = (layer - 1) / 2;           // decoder conv index L..2L-1
         const Pair& q = n->pr[2 * L - 1 - nn];
-        c = q.dD; S = q.O; xi = q.Nx; yi = q.Ny;
-        if (q.O_stale) { S = q.Oc; xi = n->NxC; yi = n->NyC; }      // training-step forward: the layer is stored on its support only
+        const OutView v = out_view(n, q);                            // (training-step forward: the layer is stored on its support only)
+        c = q.dD; S = v.O; xi = v.nx; yi = v.ny;
         if (layer & 1) { x = q.Nx; y = q.Ny; } else { x = q.Nxin; y = q.Nyin; }   // odd: conv output; even: up-sampled
     }
     if (ch) *ch = c;
