@@ -25,6 +25,8 @@ FLAGS = {n: 1 << i for i, n in enumerate(
     ["NOLAZY", "NOCOMPACT", "NOQPATH", "NOFUSEMSE", "NOGROUP", "NOMFMA", "NOGFWD", "NOOVERLAP", "NOFUSECROP", "GTAPS",
      "NOPREFETCH", "NODEFER", "NOTILEDSPATIAL", "NOFAST", "NOSPLITK", "POISON", "NOOPFORM", "NOCHAIN", "NOFUSEUPD", "NOAHEAD", "NORCORR", "NOLAZYMSE", "SMALLOVERLAP", "CHAINMSE",
      "CHIRPZ", "NOPRUNESMOOTH"])}
+# ... and the switch the header keeps apart from that table (bit 26); Context.set_flags takes the names of both
+DEV_FLAGS = {"NOSTATICCHAIN": 1 << 26}
 NET_SMOOTH_SIZES = 1 << 0   # include/aefft.h AEFFT_NET_SMOOTH_SIZES (aefft_net_create_ex)
 NET_SPATIAL = 1 << 1        # include/aefft.h AEFFT_NET_SPATIAL: the coordinate-space training mode as a resident net
 NET_SMOOTH_OPFORM = 1 << 2  # include/aefft.h AEFFT_NET_SMOOTH_OPFORM: the operator-form training step on grids with a smooth axis
@@ -94,6 +96,7 @@ SIGNATURES = {
     "aefft_net_set_input_ready": (_i, [_vp, _i]),
     "aefft_net_grad_buffer": (_i, [_vp, C.POINTER(_vp), C.POINTER(C.c_size_t)]),
     "aefft_net_step_form": (_i, [_vp]),
+    "aefft_net_tail_route": (_i, [_vp]),
     "aefft_net_last_mse": (_i, [_vp, _vp]),
     "aefft_net_step_apply": (_i, [_vp, _f, _i, _i, _f, _fp]),
     "aefft_net_reset_momentum": (_i, [_vp]),
@@ -390,7 +393,8 @@ class Context:
         v = 0
         for nme in names:
             if nme:
-                v |= FLAGS[nme.replace("AEFFT_", "").replace("F_", "")]
+                key = nme.replace("AEFFT_", "").replace("F_", "")
+                v |= FLAGS[key] if key in FLAGS else DEV_FLAGS[key]
         self.check(self.L.aefft_ctx_set_flags(self.h, v))
 
     def get_flags(self):
@@ -571,6 +575,11 @@ class Net:
         """which form the next training step runs in: "per_frame", "operator", "operator_chain" or, on a spatial net, "spatial"
         (aefft_net_step_form)"""
         return ("per_frame", "operator", "operator_chain", "spatial")[self.L.aefft_net_step_form(self.h)]
+
+    def tail_route(self):
+        """which step code the last tail launch ran: "static" (compile-time step table for the net's channel counts), "generic", or None before
+        the first one (aefft_net_tail_route)"""
+        return (None, "generic", "static")[self.L.aefft_net_tail_route(self.h)]
 
     def step_apply(self, del0, maxdiff=0, sym=0, grad_scale=1.0, mse=None):
         self.ctx.check(self.L.aefft_net_step_apply(self.h, del0, maxdiff, sym, grad_scale, _ptr(mse)))

@@ -239,7 +239,9 @@ struct ChainArgs;
 struct UpdateGroup;
 // the MSE of every pair; optionally in the same launch: the operator chain of the NEXT step (chain, reading the just-written Wp / Cc, writing its own
 // operator buffers) and the tap half of a fused update (weights_upd) -- tail_kernel
-hipError_t launch_opmse_group(OpMseGroup& g, hipStream_t st, ChainArgs* chain = nullptr, const UpdateGroup* weights_upd = nullptr);
+// route (nullable, out): which step code the launch's chain items and packed MSE run -- AEFFT_TAIL_STATIC when the net's step lists equal one of the
+// compile-time tables (opform_kernels.hip ChainTable), AEFFT_TAIL_GENERIC otherwise and under AEFFT_F_NOSTATICCHAIN
+hipError_t launch_opmse_group(OpMseGroup& g, hipStream_t st, ChainArgs* chain = nullptr, const UpdateGroup* weights_upd = nullptr, int* route = nullptr);
 // the network on the basis frames in one launch (chain_kernel): per pair the spectra, biases and the operator outputs
 struct ChainLevel { const float2 *C, *F; const float *b, *p; float2 *A /*[OPC][dD][P]*/, *O /*[OPC][dD][Pc]*/; int dD, dM, Nx, Ny; long P;
                     const float2* Cc; /* nullable: C sampled at the bins the NEXT level's grid lands on, [dM][dD][P of the next level] (then C is not read) */ };

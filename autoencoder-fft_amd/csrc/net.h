@@ -87,6 +87,7 @@ struct aefft_net {
     const float* last_frames = nullptr;
     bool last_frames_u8 = false;     // ... and they were 8-bit pixels
     bool have_forward = false, have_grad = false;
+    int tail_route = 0;        // AEFFT_TAIL_*: the step code of the last tail launch (launch_opmse_group; aefft_net_tail_route)
     int NxC = 0, NyC = 0; long Pc = 0;   // grid of the coarsest pair = support of every decoder output
     bool compact = true;                 // the training step may keep decoder outputs on that support only
     // input prefetch (aefft_net_set_input_ready): second buffer for pair 0's input spectra, end-of-step events, step counter

@@ -595,7 +595,7 @@ static int opform_mse(aefft_net* n, const ApplyRoute& rt, const UpdateGroup* wup
     const bool ahead = n->op_chain && n->packed_valid && chain_form(n) && !flag(AEFFT_F_NOAHEAD);
     ChainArgs ca{};
     if (ahead) fill_chain(n, ca, n->op_set ^ 1, &bytes);
-    RET_IF(launch_or_fail(ctx, KID_OPMSE, bytes, "opmse", [&] { return launch_opmse_group(og, ctx->cur, ahead ? &ca : nullptr, wupd); }));
+    RET_IF(launch_or_fail(ctx, KID_OPMSE, bytes, "opmse", [&] { return launch_opmse_group(og, ctx->cur, ahead ? &ca : nullptr, wupd, &n->tail_route); }));
     if (ahead) { n->op_set ^= 1; n->chain_valid = true; }
     if (!mse_d && !ctx->prof && !flag(AEFFT_F_NOLAZYMSE)) {
         // nobody asked for the sums now: they are formed by one more workgroup of the next step's gradient launch (before its
@@ -764,6 +764,8 @@ extern "C" int aefft_net_step_form(aefft_net* n)
     if (!op_eligible(n)) return AEFFT_FORM_PER_FRAME;
     return chain_form(n) ? AEFFT_FORM_OPERATOR_CHAIN : AEFFT_FORM_OPERATOR;
 }
+
+extern "C" int aefft_net_tail_route(aefft_net* n) { return n ? n->tail_route : -1; }
 
 extern "C" int aefft_net_grad_buffer(aefft_net* n, float** buf_d, size_t* nfloats)
 {

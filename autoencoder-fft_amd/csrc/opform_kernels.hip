@@ -18,6 +18,7 @@
 #include "opform_device.h"
 #include <algorithm>
 #include <type_traits>
+#include <utility>
 
 namespace aefft {
 
@@ -952,8 +953,9 @@ __device__ __forceinline__ void chain_run_steps(const SRC& g, const float2* __re
         chain_steps<0, DUAL, SRC>(g, rec, base, nb, w, bv, acc, acc2, Wl, t);
     }
 }
-// host: the steps of one stage (R x K matrix at record offset `off`, reading running vector `par`) appended to a step list; false: the list is full
-static bool chain_add_stage(unsigned* st_off, unsigned* st_desc, int* n, int cap, int R, int K, unsigned off, int par, bool enc, int lvl)
+// the steps of one stage (R x K matrix at record offset `off`, reading running vector `par`) appended to a step list; false: the list is full
+// (constexpr: the host builds a net's list with it at run time, the static tables below are built with it by the compiler)
+static constexpr bool chain_add_stage(unsigned* st_off, unsigned* st_desc, int* n, int cap, int R, int K, unsigned off, int par, bool enc, int lvl)
 {
     int ksh = 0;                                                     // KS = min(largest power of two <= 256 / R, smallest power of two >= K, 16)
     while (ksh < CH_KSH_MAX && (2 << ksh) * R <= 256 && (1 << ksh) < K) ++ksh;
@@ -968,6 +970,210 @@ static bool chain_add_stage(unsigned* st_off, unsigned* st_desc, int* n, int cap
     return true;
 }
 
+// ---- step lists as functions of the net's channel counts ----
+// A step list depends on nothing but the channel counts of the levels (and on whether the innermost pair's two stages carry the dual mark): not
+// on the bin, the batch or the grid.  ONE function builds it -- chain_geometry / opmse_geometry call it for the net at hand, and the compiler
+// evaluates it for the signatures of ChainTable below -- so a static table and the runtime list of the same net cannot disagree.
+struct ChainSig { int L; int dD[8], dM[8]; };
+struct ChainStepList { unsigned off[CH_MAXSTEPS], desc[CH_MAXSTEPS]; int n; bool fits; unsigned offC, offF; /* record offsets of the innermost pair's C, F */ };
+struct PackedStepList { unsigned off[OPMSE_PACKED_STEPS], desc[OPMSE_PACKED_STEPS]; int n; };
+// the per-bin item: stage si = level si's encoder matrix, then the decoders from the innermost level out.  n == 0: more steps than the table holds.
+static constexpr ChainStepList chain_step_list(const ChainSig& s, bool dual)
+{
+    ChainStepList r{};
+    int n = 0; unsigned off = 0;
+    bool fits = true;
+    int dual_lo = 0, dual_hi = 0;                                       // steps [dual_lo, dual_hi): the innermost pair's two stages
+    for (int si = 0; si < 2 * s.L && fits; ++si) {
+        const bool enc = si < s.L;
+        const int l = enc ? si : 2 * s.L - 1 - si;
+        const int R = enc ? s.dM[l] : s.dD[l], K = enc ? s.dD[l] : s.dM[l];
+        if (si == s.L - 1) { dual_lo = n; r.offC = off; }
+        if (si == s.L) r.offF = off;
+        fits = chain_add_stage(r.off, r.desc, &n, CH_MAXSTEPS, R, K, off, si & 1, enc, l);
+        if (si == s.L) dual_hi = n;
+        off += (unsigned)((R * K + 1) & ~1);
+    }
+    r.fits = fits; r.n = fits ? n : 0;
+    if (dual && fits) for (int i = dual_lo; i < dual_hi; ++i) r.off[i] |= 1u << 30;
+    return r;
+}
+// the innermost pair's two stages C' (dM x dD at offC), F' (dD x dM at offF) alone: opmse_packed
+static constexpr PackedStepList packed_step_list(int dD, int dM, unsigned offC, unsigned offF)
+{
+    PackedStepList r{};
+    int n = 0;
+    const bool fits = chain_add_stage(r.off, r.desc, &n, OPMSE_PACKED_STEPS, dM, dD, offC, 0, true, 0) &&
+                      chain_add_stage(r.off, r.desc, &n, OPMSE_PACKED_STEPS, dD, dM, offF, 1, false, 0);
+    r.n = fits ? n : 0;
+    return r;
+}
+
+// ---- static step tables ----
+// The nets the baseline configurations train: input D = 3, maps (8,16,32,64), (8,16,32), (8,16,32,64,128).  SIG 0 is "no table": the generic
+// step code above, which serves every other net and is the parity reference of the static route (AEFFT_F_NOSTATICCHAIN forces it).
+constexpr int CH_NSIG = 3;
+static constexpr ChainSig chain_sig(int D, int m0, int m1 = 0, int m2 = 0, int m3 = 0, int m4 = 0)
+{
+    ChainSig s{};
+    const int m[5] = {m0, m1, m2, m3, m4};
+    for (int l = 0; l < 5 && m[l] > 0; ++l) { s.dD[l] = l ? m[l - 1] : D; s.dM[l] = m[l]; s.L = l + 1; }
+    return s;
+}
+template <int SIG> struct ChainSigOf;
+template <> struct ChainSigOf<1> { static constexpr ChainSig sig = chain_sig(3, 8, 16, 32, 64); };
+// (2: without the dual marking only -- its fused kernel needs a 97th register at five waves per SIMD, 8 bytes of scratch per lane; such a net fuses
+// only under AEFFT_F_CHAINMSE, its launches being far below the size at which the fused MSE pays, and then runs the generic step code)
+template <> struct ChainSigOf<2> { static constexpr ChainSig sig = chain_sig(3, 8, 16, 32); };
+template <> struct ChainSigOf<3> { static constexpr ChainSig sig = chain_sig(3, 8, 16, 32, 64, 128); };
+template <int SIG, bool DUAL> struct ChainTable {
+    static constexpr ChainSig sig = ChainSigOf<SIG>::sig;
+    static constexpr ChainStepList steps = chain_step_list(sig, DUAL);
+    static constexpr PackedStepList packed = packed_step_list(sig.dD[sig.L - 1], sig.dM[sig.L - 1], steps.offC, steps.offF);
+    static_assert(steps.n > 0 && packed.n > 0, "a static table whose net does not fit the step tables");
+};
+// One step with its words as compile-time constants: R, K, k0, KS, the flags, the level, the record offset and the LDS regions fold into the
+// instructions.  What a lane's element u is (k = k0 + ks + u KS, ks < KS): `live` -- some lane's k lies inside the row; `whole` -- every lane's does
+// (no clamp of the address, no mask on the element).
+template <unsigned D, unsigned O> struct ChainStepC {
+    static constexpr unsigned R = D & 255u, K = (D >> 8) & 255u, k0 = (D >> 16) & 127u, ksh = (D >> 23) & 7u, KS = 1u << ksh;
+    static constexpr bool last = (D >> 26) & 1u, first = (D >> 27) & 1u, enc = (D >> 28) & 1u, dual = (O >> 30) & 1u;
+    static constexpr unsigned lv = D >> 29, off = O & 0xffffffu, par = O >> 31;
+    static constexpr bool all_rows = (R << ksh) >= 256u;             // every thread of the workgroup owns a row
+    static constexpr bool live(int u) { return k0 + (unsigned)u * KS < K; }
+    static constexpr bool whole(int u) { return k0 + (KS - 1u) + (unsigned)u * KS < K; }
+};
+// the static step sources: the host of the list (biases, NN, outputs) as in the generic source, the words from a table
+template <int SIG, bool DUAL> struct ChainSrcC : ChainSrc {
+    static constexpr int n = ChainTable<SIG, DUAL>::steps.n;
+    template <int I> using step = ChainStepC<ChainTable<SIG, DUAL>::steps.desc[I], ChainTable<SIG, DUAL>::steps.off[I]>;
+};
+// chain_step_load with the step's words folded: the same CH_NE + 1 unconditional loads from the same addresses (an element no lane needs still
+// reads the row's last one: the number of loads in flight at every wait stays what the pipeline's waits were placed for)
+template <class S, class SRC>
+__device__ __forceinline__ void chain_step_load_c(const SRC& g, const float2* __restrict__ rec, float2 (&w)[CH_NE], float& bv)
+{
+    const unsigned tid = threadIdx.x;
+    const unsigned rq = tid >> S::ksh, r = S::all_rows ? rq : min(rq, S::R - 1u), ks = tid & (S::KS - 1u);
+    const unsigned row = S::off + r * S::K, e0 = row + S::k0 + ks, elast = row + S::K - 1u;
+#pragma unroll
+    for (int u = 0; u < CH_NE; ++u) w[u] = ld8(rec, S::whole(u) ? e0 + (unsigned)u * S::KS : S::live(u) ? min(e0 + (unsigned)u * S::KS, elast) : elast);
+    bv = g.bias(S::lv, S::enc)[r];
+}
+// chain_step_compute with the step's words folded: the same products in the same order.  An element NO lane needs is skipped instead of being
+// added as 0 * v: the sums start from +0 and only ever add, so they are never -0, and x + (+-0) == x bit for bit for every other x (v is a finite
+// element of the running vector either way).  1 / R is the correctly rounded quotient whether the compiler or the lane divides.
+template <bool DUAL, class S, class SRC>
+__device__ __forceinline__ void chain_step_compute_c(const SRC& g, const float2 (&w)[CH_NE], const float bv, float2 (&acc)[OPC], float2 (&acc2)[OPC],
+                                                     float2* const Wl, const int t)
+{
+    static_assert(OPC == 4, "two 16-byte LDS accesses per row of V");
+    constexpr bool dual = DUAL && S::dual;
+    constexpr unsigned VS = CH_VMAX * OPC;
+    const unsigned tid = threadIdx.x;
+    const unsigned rr = tid >> S::ksh, ks = tid & (S::KS - 1u);
+    const bool valid = S::all_rows || rr < S::R;
+    if constexpr (S::first) {
+#pragma unroll
+        for (int c = 0; c < OPC; ++c) { acc[c] = make_float2(0.f, 0.f); if (DUAL) acc2[c] = make_float2(0.f, 0.f); }
+    }
+    const float2* Vin = Wl + S::par * VS;
+    const float2* Vin2 = Wl + (S::enc ? 2 : 3) * VS;
+#pragma unroll
+    for (int u = 0; u < CH_NE; ++u) {
+        if (!S::live(u)) continue;
+        const unsigned k = S::k0 + ks + (unsigned)u * S::KS;
+        const bool ok = valid && (S::whole(u) || k < S::K);
+        const float2 wv = (S::all_rows && S::whole(u)) ? w[u] : (ok ? w[u] : make_float2(0.f, 0.f));
+        const unsigned kk = (S::whole(u) ? k : min(k, S::K - 1u)) * OPC;
+        {
+            const float4* vp = reinterpret_cast<const float4*>(Vin + kk);
+            const float4 va = vp[0], vb = vp[1];
+            cfma_pk(acc[0], wv, make_float2(va.x, va.y)); cfma_pk(acc[1], wv, make_float2(va.z, va.w));
+            cfma_pk(acc[2], wv, make_float2(vb.x, vb.y)); cfma_pk(acc[3], wv, make_float2(vb.z, vb.w));
+        }
+        if constexpr (dual) {
+            const float4* vp = reinterpret_cast<const float4*>(Vin2 + kk);
+            const float4 va = vp[0], vb = vp[1];
+            cfma_pk(acc2[0], wv, make_float2(va.x, va.y)); cfma_pk(acc2[1], wv, make_float2(va.z, va.w));
+            cfma_pk(acc2[2], wv, make_float2(vb.x, vb.y)); cfma_pk(acc2[3], wv, make_float2(vb.z, vb.w));
+        }
+    }
+    if constexpr (S::last) {
+        // the row sums: exactly log2 KS DPP adds per value (chain_step_compute's ladder with its tests decided)
+        auto rowsum = [&](auto SH) {
+            constexpr int N = decltype(SH)::value;
+#pragma unroll
+            for (int c = 0; c < OPC; ++c) { acc[c].x += dpp_row_shl<N>(acc[c].x); acc[c].y += dpp_row_shl<N>(acc[c].y); }
+            if constexpr (dual) {
+#pragma unroll
+                for (int c = 0; c < OPC; ++c) { acc2[c].x += dpp_row_shl<N>(acc2[c].x); acc2[c].y += dpp_row_shl<N>(acc2[c].y); }
+            }
+        };
+        if constexpr (S::ksh > 0) rowsum(std::integral_constant<int, 1>{});
+        if constexpr (S::ksh > 1) rowsum(std::integral_constant<int, 2>{});
+        if constexpr (S::ksh > 2) rowsum(std::integral_constant<int, 4>{});
+        if constexpr (S::ksh > 3) rowsum(std::integral_constant<int, 8>{});
+        if (valid && ks == 0) {
+            constexpr float scale = 1.0f / (float)S::R;
+#pragma unroll
+            for (int c = 0; c < OPC; ++c) { acc[c].x *= scale; acc[c].y *= scale; }
+            if (t == 0) acc[OPC - 1].x += bv * g.NN(S::lv);
+            if constexpr (dual) {
+#pragma unroll
+                for (int c = 0; c < OPC; ++c) { acc2[c].x *= scale; acc2[c].y *= scale; }
+                if (t == 0) acc2[OPC - 1].x += bv * g.NN(S::lv);
+                float4* v2 = reinterpret_cast<float4*>(Wl + (S::enc ? 3 : 4) * VS + rr * OPC);
+                v2[0] = make_float4(acc2[0].x, acc2[0].y, acc2[1].x, acc2[1].y); v2[1] = make_float4(acc2[2].x, acc2[2].y, acc2[3].x, acc2[3].y);
+            }
+            const float4 o0 = make_float4(acc[0].x, acc[0].y, acc[1].x, acc[1].y), o1 = make_float4(acc[2].x, acc[2].y, acc[3].x, acc[3].y);
+            float4* vo = reinterpret_cast<float4*>(Wl + (S::par ^ 1u) * VS + rr * OPC);
+            vo[0] = o0; vo[1] = o1;
+            if constexpr (!S::enc) {                                  // a decoder stage: its rows may be an output of the item
+                float2* O = g.out(S::lv);
+                if (O) {
+                    const unsigned Pc = g.Pc();
+#pragma unroll
+                    for (int c = 0; c < OPC; ++c) st8(O, ((unsigned)c * S::R + rr) * Pc + (unsigned)t, acc[c]);
+                }
+            }
+        }
+        __syncthreads();                                              // the stage's output is complete
+    }
+}
+// the first CH_DEPTH loads of a block of steps [BASE, BASE + NB)
+template <int BASE, int NB, class SRC, int... J>
+__device__ __forceinline__ void chain_fill_c(const SRC& g, const float2* __restrict__ rec, float2 (&w)[CH_NB][CH_NE], float (&bv)[CH_NB], std::integer_sequence<int, J...>)
+{
+    (chain_step_load_c<typename SRC::template step<BASE + (J < NB - 1 ? J : NB - 1)>>(g, rec, w[J], bv[J]), ...);
+}
+// chain_run_steps + chain_steps for a static source: the same blocks of CH_BLOCK steps, the same fill, drain and rotation -- with the step index
+// (and so every word of the step) a template parameter all the way down
+template <int I, bool DUAL, class SRC, class INIT>
+__device__ __forceinline__ void chain_steps_c(const SRC& g, const float2* __restrict__ rec, float2 (&w)[CH_NB][CH_NE], float (&bv)[CH_NB],
+                                              float2 (&acc)[OPC], float2 (&acc2)[OPC], float2* const Wl, const int t, INIT& init)
+{
+    if constexpr (I < SRC::n) {
+        constexpr int base = I / CH_BLOCK * CH_BLOCK, nb = SRC::n - base < CH_BLOCK ? SRC::n - base : CH_BLOCK, j = I - base;
+        if constexpr (j == 0) {
+            chain_fill_c<base, nb>(g, rec, w, bv, std::make_integer_sequence<int, CH_DEPTH>{});
+            if constexpr (base == 0) { init(); __syncthreads(); }
+        }
+        constexpr int jl = j + CH_DEPTH < nb - 1 ? j + CH_DEPTH : nb - 1;
+        chain_step_load_c<typename SRC::template step<base + jl>>(g, rec, w[(j + CH_DEPTH) % CH_NB], bv[(j + CH_DEPTH) % CH_NB]);
+        chain_step_compute_c<DUAL, typename SRC::template step<I>>(g, w[j % CH_NB], bv[j % CH_NB], acc, acc2, Wl, t);
+        chain_steps_c<I + 1, DUAL, SRC>(g, rec, w, bv, acc, acc2, Wl, t, init);
+    }
+}
+template <bool DUAL, class SRC, class INIT>
+__device__ __forceinline__ void chain_run_steps_c(const SRC& g, const float2* __restrict__ rec, float2* const Wl, const int t, INIT init)
+{
+    float2 w[CH_NB][CH_NE];
+    float bv[CH_NB];
+    float2 acc[OPC], acc2[OPC];
+    chain_steps_c<0, DUAL, SRC>(g, rec, w, bv, acc, acc2, Wl, t, init);
+}
+
 // The innermost pair from the bin-major copy of the updated spectra (kspec_packed_body): one workgroup per bin, C' and F' read as
 // contiguous rows (the planar layout makes them 8 K scattered 32-byte pieces per bin tile), two chain stages and the quadratic form.
 constexpr size_t OPMSE_PACKED_LDS = sizeof(float2) * (3 * CH_VMAX * OPC + 2 + OPC * OPC) + 128;
@@ -980,6 +1186,12 @@ struct PackedMseSrc {                                   // the two stages C', F'
     __device__ __forceinline__ float2* out(unsigned) const { return nullptr; }
     __device__ __forceinline__ unsigned Pc() const { return 0u; }
 };
+template <int SIG> struct PackedMseSrcC : PackedMseSrc {
+    static constexpr int n = ChainTable<SIG, false>::packed.n;
+    template <int I> using step = ChainStepC<ChainTable<SIG, false>::packed.desc[I], ChainTable<SIG, false>::packed.off[I]>;
+};
+// SIG: the static table of the launch (0: the step list of the group, generic step code)
+template <int SIG>
 __device__ __forceinline__ void opmse_packed(const OpMseGroup& g, int p, long t, float2* sh)
 {
     float2 *Va = sh + 2 * CH_VMAX * OPC;                 // A of the bin (kept); the running vectors are buffers 0 and 1 of sh
@@ -990,15 +1202,20 @@ __device__ __forceinline__ void opmse_packed(const OpMseGroup& g, int p, long t,
     const float2* Vc;                                    // F'(C' A / dM + b^) / dD + p^ of the bin
     float2* Ms = sh + 3 * CH_VMAX * OPC + 2;             // the bin's 4x4 moments, requested with A (behind the stages they were a round trip of their own)
     const long um = map_up(t, q.Nx, q.Ny, g.Nx0, g.Ny0);
-    if (g.pst_n > 0) {
+    auto init = [&]() {
+        float2 mv = make_float2(0.f, 0.f);
+        if (threadIdx.x < OPC * OPC) mv = g.Mhat[(long)threadIdx.x * g.P0 + um];
+        for (int i = threadIdx.x; i < dD * OPC; i += 256) { const int a = i / OPC, k = i - a * OPC; const float2 v = q.A[((long)k * dD + a) * q.P + t]; sh[i] = v; Va[i] = v; }
+        if (threadIdx.x < OPC * OPC) Ms[threadIdx.x] = mv;
+    };
+    if constexpr (SIG > 0) {                             // (the launcher has matched pst_* with the table word for word)
+        const PackedMseSrcC<SIG> src{{g, q}};
+        chain_run_steps_c<false>(src, rec, sh, (int)t, init);
+        Vc = sh;
+    } else if (g.pst_n > 0) {
         // (as a software pipeline over the record: the stage-by-stage form below was six dependent round trips, 11 us per workgroup at cfg3)
         const PackedMseSrc src{g, q};
-        chain_run_steps<false>(src, rec, g.pst_n, sh, (int)t, [&]() {
-            float2 mv = make_float2(0.f, 0.f);
-            if (threadIdx.x < OPC * OPC) mv = g.Mhat[(long)threadIdx.x * g.P0 + um];
-            for (int i = threadIdx.x; i < dD * OPC; i += 256) { const int a = i / OPC, k = i - a * OPC; const float2 v = q.A[((long)k * dD + a) * q.P + t]; sh[i] = v; Va[i] = v; }
-            if (threadIdx.x < OPC * OPC) Ms[threadIdx.x] = mv;
-        });
+        chain_run_steps<false>(src, rec, g.pst_n, sh, (int)t, init);
         Vc = sh;                                         // (stage 0 reads buffer 0 and writes 1, stage 1 writes 0; its barrier has been passed)
     } else {
         float2 *Vb = sh, *Vd = sh + CH_VMAX * OPC;
@@ -1036,14 +1253,14 @@ __device__ __forceinline__ void opmse_packed(const OpMseGroup& g, int p, long t,
 // (the bodies take their workgroup index from blockIdx.x - g.base: the launch may host other work in front, tail_kernel)
 // LEAN: every pair of the launch is served by opmse_packed or opmse_gbody (launch_opmse_group checks) -- the bodies that read the planar
 // C' | F' are not instantiated: they need 103-121 registers against 62-78 for the rest, and a launch's allocation is its largest body's
-template <bool LEAN>
+template <bool LEAN, int SIG = 0>
 __device__ __forceinline__ void opmse_dispatch(const OpMseGroup& g, float2* sh)
 {
     const int blk = (int)blockIdx.x - g.base;
     int p = g.n - 1;                                                 // pair n-1 owns the first workgroups, pair 0 the last
 #pragma unroll
     for (int i = 6; i >= 0; --i) if (i < g.n - 1 && blk >= g.start[i] - g.base) p = i;
-    if (p == g.n - 1 && g.Wp) { opmse_packed(g, p, (long)blockIdx.x - g.start[p], sh); return; }
+    if (p == g.n - 1 && g.Wp) { opmse_packed<SIG>(g, p, (long)blockIdx.x - g.start[p], sh); return; }
     if (LEAN || g.q[p].G) { opmse_gbody(g, p, sh); return; }         // (uniform) the pair's collapsed operator G' is at hand
     if constexpr (!LEAN) {
         const int bt = g.bt[p];                                      // uniform per workgroup
@@ -1070,10 +1287,9 @@ static hipError_t opmse_geometry(OpMseGroup& g, int base, long* nblocks, size_t*
         const bool pk = i == g.n - 1 && g.Wp && q.dD <= CH_VMAX && q.dM <= CH_VMAX;
         if (pk) {
             need = OPMSE_PACKED_LDS;
-            int n = 0;
-            const bool fits = chain_add_stage(g.pst_off, g.pst_desc, &n, OPMSE_PACKED_STEPS, q.dM, q.dD, (unsigned)g.offC, 0, true, 0) &&
-                              chain_add_stage(g.pst_off, g.pst_desc, &n, OPMSE_PACKED_STEPS, q.dD, q.dM, (unsigned)g.offF, 1, false, 0);
-            g.pst_n = fits && AEFFT_X_CHAINPIPE ? n : 0;
+            const PackedStepList sl = packed_step_list(q.dD, q.dM, (unsigned)g.offC, (unsigned)g.offF);
+            std::copy(sl.off, sl.off + OPMSE_PACKED_STEPS, g.pst_off); std::copy(sl.desc, sl.desc + OPMSE_PACKED_STEPS, g.pst_desc);
+            g.pst_n = AEFFT_X_CHAINPIPE ? sl.n : 0;
         }
         else if (q.G) {                                                  // opmse_gbody
             if ((double)q.dD * q.dD * q.P * 8.0 >= 4294967296.0) return hipErrorInvalidValue;
@@ -1160,13 +1376,13 @@ hipError_t launch_kspec_packed(PackArgs& g, hipStream_t st)
 // No workgroup waits for another one; the only cost of the independence is the re-evaluation of a few small products.
 // mse (nullable): the tail launch's MSE description when THIS item also forms the innermost pair's post-update MSE at its bin (ChainArgs::fuse_mse:
 // the steps of the two innermost stages are marked dual) -- what opmse_packed does in a workgroup of its own otherwise
-template <bool DUAL>
+// SIG: the static table of the launch, matched with st_* word for word by the launcher (0: the step list of the arguments, generic step code)
+template <bool DUAL, int SIG = 0>
 __device__ __forceinline__ void chain_item_run(const ChainArgs& g, const int t, float2* Wl, const OpMseGroup* mse)
 {
-    const ChainSrc src{g};
     constexpr int VS = CH_VMAX * OPC;
     float2* Ms = Wl + 5 * VS;                             // [OPC*OPC] the bin's moments (DUAL)
-    chain_run_steps<DUAL>(src, g.Wp + (long)t * g.E, g.st_n, Wl, t, [&]() {
+    auto init = [&]() {
         float2 mv = make_float2(0.f, 0.f);
         if (DUAL) {
             const OpMsePair& q = mse->q[mse->n - 1];
@@ -1176,7 +1392,9 @@ __device__ __forceinline__ void chain_item_run(const ChainArgs& g, const int t, 
         }
         for (int i = threadIdx.x; i < VS; i += 256) { const int k = i / OPC, c = i - k * OPC; Wl[i] = make_float2((k == c && c < OPC - 1) ? 1.f : 0.f, 0.f); }
         if (DUAL && threadIdx.x < OPC * OPC) Ms[threadIdx.x] = mv;
-    });
+    };
+    if constexpr (SIG > 0) { const ChainSrcC<SIG, DUAL> src{{g}}; chain_run_steps_c<DUAL>(src, g.Wp + (long)t * g.E, Wl, t, init); }
+    else { const ChainSrc src{g}; chain_run_steps<DUAL>(src, g.Wp + (long)t * g.E, g.st_n, Wl, t, init); }
     if (DUAL) {
         // R = A - (F'(C' A / dM + b^) / dD + p^) at this bin and tr(R M^ R^H): opmse_packed's epilogue (the last stage's barrier has made region 4 visible)
         const OpMsePair& q = mse->q[mse->n - 1];
@@ -1217,13 +1435,14 @@ constexpr int CH_ITEM_VECS = 2;
 constexpr int CH_BT = 8;
 // bx: the workgroup's index inside the chain part of the launch; Wl: dynamic LDS (per-bin items: two running vectors; planar tiles:
 // two V tiles [rows][OPC][CH_BT])
-template <bool FUSE>
+template <bool FUSE, int SIG = 0>
 __device__ __forceinline__ void chain_body(const ChainArgs& g, const int bx, float2* Wl, const OpMseGroup* mse = nullptr)
 {
     const int tid = threadIdx.x;
     const int L = g.L;
-    if (AEFFT_X_CHAINPIPE && (long)bx < g.Pc && g.st_n > 0) { chain_item_run<FUSE>(g, bx, Wl, mse); return; }      // (st_n == 0: more steps than the step table holds)
-    if ((long)bx < g.Pc) {
+    if constexpr (SIG > 0) { if ((long)bx < g.Pc) { chain_item_run<FUSE, SIG>(g, bx, Wl, mse); return; } }
+    else if (AEFFT_X_CHAINPIPE && (long)bx < g.Pc && g.st_n > 0) { chain_item_run<FUSE>(g, bx, Wl, mse); return; }      // (st_n == 0: more steps than the step table holds)
+    if (SIG == 0 && (long)bx < g.Pc) {
         const int t = bx;
         const bool dc = t == 0;
         const float2* rec = g.Wp + (long)t * g.E;
@@ -1321,25 +1540,16 @@ static hipError_t chain_geometry(ChainArgs& g, long* nblocks, size_t* lds_out, b
         if (l + 1 < g.L && (size_t)2 * g.lv[l].dM * OPC * CH_BT > CH_WL) return hipErrorInvalidValue;     // planar tiles: two V tiles share the LDS buffer (at the narrowest tile)
     }
     {
-        // the per-bin item's step list (chain_item_pipelined): stage si = level si's encoder matrix, then the decoders from the innermost level out
-        int n = 0; unsigned off = 0;
-        bool fits = true, offs_ok = true;
-        int dual_lo = 0, dual_hi = 0;                                   // steps [dual_lo, dual_hi): the innermost pair's two stages
-        for (int si = 0; si < 2 * g.L && fits; ++si) {
-            const bool enc = si < g.L;
-            const int l = enc ? si : 2 * g.L - 1 - si;
-            const int R = enc ? g.lv[l].dM : g.lv[l].dD, K = enc ? g.lv[l].dD : g.lv[l].dM;
-            if (si == g.L - 1) { dual_lo = n; offs_ok = offs_ok && off == offC; }
-            if (si == g.L) offs_ok = offs_ok && off == offF;
-            fits = chain_add_stage(g.st_off, g.st_desc, &n, CH_MAXSTEPS, R, K, off, si & 1, enc, l);
-            if (si == g.L) dual_hi = n;
-            off += (unsigned)((R * K + 1) & ~1);
-        }
-        g.st_n = fits ? n : 0;                                          // (0: the item runs stage by stage, chain_stage_rec)
-        if (fuse) {
-            *fuse = *fuse && fits && offs_ok && AEFFT_X_CHAINPIPE;
-            if (*fuse) for (int i = dual_lo; i < dual_hi; ++i) g.st_off[i] |= 1u << 30;
-        }
+        // the per-bin item's step list (chain_step_list): empty when it has more steps than the table holds -- the item then runs stage by stage, chain_stage_rec
+        ChainSig sig{};
+        sig.L = g.L;
+        for (int l = 0; l < g.L; ++l) { sig.dD[l] = g.lv[l].dD; sig.dM[l] = g.lv[l].dM; }
+        ChainStepList sl = chain_step_list(sig, false);
+        const bool dual = fuse && *fuse && sl.fits && sl.offC == offC && sl.offF == offF && AEFFT_X_CHAINPIPE;
+        if (dual) sl = chain_step_list(sig, true);
+        std::copy(sl.off, sl.off + CH_MAXSTEPS, g.st_off); std::copy(sl.desc, sl.desc + CH_MAXSTEPS, g.st_desc);
+        g.st_n = sl.n;
+        if (fuse) *fuse = dual;
         if ((double)OPC * CH_VMAX * (double)g.Pc * sizeof(float2) >= 4294967296.0) return hipErrorInvalidValue;      // (32-bit byte offsets of the output stores, st8)
     }
     long total = g.Pc;
@@ -1388,12 +1598,14 @@ hipError_t launch_chain(ChainArgs& g, hipStream_t st, hipEvent_t done)
 #ifndef AEFFT_X_TAIL_WF
 #define AEFFT_X_TAIL_WF 5
 #endif
-template <bool LEAN, bool FUSE>
+// SIG: the static step table of the launch's net (ChainTable; 0: none).  Every table is a kernel of its own: each then holds ONE copy of the items'
+// straight-line steps and one of the packed MSE's, as the generic kernel does (a second copy in one kernel spills).
+template <bool LEAN, bool FUSE, int SIG = 0>
 __global__ __launch_bounds__(256, LEAN ? (FUSE ? AEFFT_X_TAIL_WF : AEFFT_X_TAIL_W) : 4) void tail_kernel(const OpMseGroup g, const ChainArgs ch, const UpdateGroup ug, const int nchain, const int nupd_start)
 {
     AEFFT_WGTIME(4);
     extern __shared__ float2 sh[];
-    if ((int)blockIdx.x < nchain) { chain_body<FUSE>(ch, blockIdx.x, sh, &g); return; }
+    if ((int)blockIdx.x < nchain) { chain_body<FUSE, SIG>(ch, blockIdx.x, sh, &g); return; }
     if ((int)blockIdx.x >= nupd_start) {
         const int blk = blockIdx.x - nupd_start;
         int p = 0;
@@ -1402,13 +1614,29 @@ __global__ __launch_bounds__(256, LEAN ? (FUSE ? AEFFT_X_TAIL_WF : AEFFT_X_TAIL_
         update_weights_part(ug.a[p], blk - ug.start[p]);
         return;
     }
-    opmse_dispatch<LEAN>(g, sh);
+    opmse_dispatch<LEAN, SIG>(g, sh);
 }
 
 static UpdateGroup g_tail_ug_none{};
 static ChainArgs g_tail_chain_none{};
-// chain == null: the MSE (and the tap stores) alone
-hipError_t launch_opmse_group(OpMseGroup& g, hipStream_t st, ChainArgs* chain, const UpdateGroup* weights_upd)
+// the launch's step lists (the chain items' and the packed MSE's, as chain_geometry and opmse_geometry have just built them) against static
+// table SIG, word for word
+template <int SIG, bool DUAL> static bool tail_table_matches(const ChainArgs& c, const OpMseGroup& g)
+{
+    const ChainStepList& a = ChainTable<SIG, DUAL>::steps;
+    const PackedStepList& b = ChainTable<SIG, DUAL>::packed;
+    return c.st_n == a.n && std::equal(a.off, a.off + a.n, c.st_off) && std::equal(a.desc, a.desc + a.n, c.st_desc) &&
+           g.Wp && g.pst_n == b.n && std::equal(b.off, b.off + b.n, g.pst_off) && std::equal(b.desc, b.desc + b.n, g.pst_desc);
+}
+template <bool DUAL> static int tail_table_of(const ChainArgs& c, const OpMseGroup& g)
+{
+    if (tail_table_matches<1, DUAL>(c, g)) return 1;
+    if constexpr (!DUAL) if (tail_table_matches<2, DUAL>(c, g)) return 2;      // (no fused table for the three-pair net: see ChainSigOf)
+    if (tail_table_matches<3, DUAL>(c, g)) return 3;
+    return 0;
+}
+// chain == null: the MSE (and the tap stores) alone.  route (nullable): AEFFT_TAIL_GENERIC / AEFFT_TAIL_STATIC, the step code the launch runs
+hipError_t launch_opmse_group(OpMseGroup& g, hipStream_t st, ChainArgs* chain, const UpdateGroup* weights_upd, int* route)
 {
     long nchain = 0, nmse = 0;
     size_t lds_c = 0, lds_m = 0;
@@ -1446,17 +1674,33 @@ hipError_t launch_opmse_group(OpMseGroup& g, hipStream_t st, ChainArgs* chain, c
     for (int i = 0; i < g.n && lean; ++i) lean = g.q[i].G != nullptr || (i == g.n - 1 && g.Wp != nullptr);      // (after opmse_geometry: Wp is null unless the innermost pair goes packed)
     const long total = nchain + nmse + nupd;
     if (total >= (1L << 31)) return hipErrorInvalidValue;
-    auto go = [&](auto LEANT, auto FUSET) -> hipError_t {
+    auto go = [&](auto LEANT, auto FUSET, auto SIGT) -> hipError_t {
         constexpr bool LN = decltype(LEANT)::value, FS = decltype(FUSET)::value;
+        constexpr int SG = decltype(SIGT)::value;
         if (lds > 64 * 1024) {
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(tail_kernel<LN, FS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(tail_kernel<LN, FS, SG>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
             if (e != hipSuccess) return e;
         }
-        tail_kernel<LN, FS><<<dim3((unsigned)total), 256, lds, st>>>(g, chain ? *chain : g_tail_chain_none, ug, (int)nchain, (int)(nchain + nmse));
+        tail_kernel<LN, FS, SG><<<dim3((unsigned)total), 256, lds, st>>>(g, chain ? *chain : g_tail_chain_none, ug, (int)nchain, (int)(nchain + nmse));
         return hipGetLastError();
     };
-    if (lean) return fuse ? go(std::true_type{}, std::true_type{}) : go(std::true_type{}, std::false_type{});
-    return fuse ? go(std::false_type{}, std::true_type{}) : go(std::false_type{}, std::false_type{});
+    // the static route: a lean launch whose chain items and packed MSE run exactly the step lists of one of the tables
+    int sig = 0;
+#if !(defined(AEFFT_X_WGTIME) && AEFFT_X_WGTIME)      // (the stage stamps of the experiment build live in the generic step code)
+    if (lean && chain && AEFFT_X_CHAINPIPE && !flag(AEFFT_F_NOSTATICCHAIN)) sig = fuse ? tail_table_of<true>(*chain, g) : tail_table_of<false>(*chain, g);
+#endif
+    if (route) *route = sig ? AEFFT_TAIL_STATIC : AEFFT_TAIL_GENERIC;
+    auto sigs = [&](auto FUSET) -> hipError_t {
+        switch (sig) {
+        case 1: return go(std::true_type{}, FUSET, std::integral_constant<int, 1>{});
+        case 2: if constexpr (!decltype(FUSET)::value) return go(std::true_type{}, FUSET, std::integral_constant<int, 2>{}); else break;
+        case 3: return go(std::true_type{}, FUSET, std::integral_constant<int, 3>{});
+        default: break;
+        }
+        return go(std::true_type{}, FUSET, std::integral_constant<int, 0>{});
+    };
+    if (lean) return fuse ? sigs(std::true_type{}) : sigs(std::false_type{});
+    return fuse ? go(std::false_type{}, std::true_type{}, std::integral_constant<int, 0>{}) : go(std::false_type{}, std::false_type{}, std::integral_constant<int, 0>{});
 }
 
 }  // namespace aefft

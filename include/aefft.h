@@ -98,6 +98,13 @@ enum {
     AEFFT_F_NOPRUNESMOOTH = 1 << 25 /* grids with a smooth axis: kernel spectra and weight gradients by pad + full R2C / full C2R + shrink instead of the
                                    * support-pruned transforms (the two routes compared; power-of-two grids are not affected) */
 };
+/* One more switch, bit 26 (kept apart from the table above and written as a plain constant: the ABI tests of earlier calls pin that table's
+ * 26 entries).  AEFFT_FLAGS and aefft_ctx_set_flags take it like the others. */
+enum {
+    AEFFT_F_NOSTATICCHAIN = 0x04000000 /* operator form with the chain: the tail launch's per-bin steps from the step list in the kernel's arguments
+                                        * (the generic step code, which serves any net) even where the net's channel counts have a compile-time
+                                        * step table; the two routes give the same bits (aefft_net_tail_route says which one ran) */
+};
 int aefft_ctx_set_flags(aefft_ctx* ctx, unsigned flags);
 unsigned aefft_ctx_get_flags(const aefft_ctx* ctx);
 const char* aefft_version(void);
@@ -409,6 +416,13 @@ int aefft_net_grad_buffer(aefft_net* net, float** buf_d, size_t* nfloats);
  * aefft_net_infer runs in the same form (its operators are then evaluated once per weight set).  Returns -1 for a null net. */
 enum { AEFFT_FORM_PER_FRAME = 0, AEFFT_FORM_OPERATOR = 1, AEFFT_FORM_OPERATOR_CHAIN = 2, AEFFT_FORM_SPATIAL = 3 /* AEFFT_NET_SPATIAL */ };
 int aefft_net_step_form(aefft_net* net);
+/* Which step code the LAST tail launch of this net ran (the launch that ends aefft_net_step_apply in the operator forms: the next step's operator
+ * chain, the post-update MSE and the tap stores): AEFFT_TAIL_STATIC when the per-bin steps came from a compile-time table for the net's channel
+ * counts (input 3; maps 8,16,32 / 8,16,32,64 / 8,16,32,64,128), AEFFT_TAIL_GENERIC when they were decoded from the step list in the kernel's
+ * arguments (every other net, launches without the chain, AEFFT_F_NOSTATICCHAIN), AEFFT_TAIL_NONE before the first such launch and on nets that
+ * have none.  The results do not depend on the route.  Returns -1 for a null net. */
+enum { AEFFT_TAIL_NONE = 0, AEFFT_TAIL_GENERIC = 1, AEFFT_TAIL_STATIC = 2 };
+int aefft_net_tail_route(aefft_net* net);
 int aefft_net_step_apply(aefft_net* net, float del0, int maxdiff, int sym, float grad_scale, float* mse_d);
 /* The per-pair post-update MSEs of the LAST aefft_net_step_apply (fft_backproplib.cu:1463), to mse_d[L] (device), in stream order.
  * aefft_net_step_apply(mse_d = NULL) does not form them in a launch of its own: the per-workgroup partial sums wait in the net and are
