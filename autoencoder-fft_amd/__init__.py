@@ -93,6 +93,7 @@ SIGNATURES = {
     "aefft_net_forward_u8": (_i, [_vp, _vp, _fp]),
     "aefft_net_infer": (_i, [_vp, _vp, _i, _vp, _i, _i, _fp]),
     "aefft_net_decode": (_i, [_vp, _i, _fp, _vp, _i]),
+    "aefft_net_score": (_i, [_vp, _vp, _i, _fp, _fp]),
     "aefft_net_set_input_ready": (_i, [_vp, _i]),
     "aefft_net_grad_buffer": (_i, [_vp, C.POINTER(_vp), C.POINTER(C.c_size_t)]),
     "aefft_net_step_form": (_i, [_vp]),
@@ -504,6 +505,16 @@ class Net:
         hp = -1 if hidden_pair is None else int(hidden_pair)
         self.ctx.check(self.L.aefft_net_infer(self.h, _ptr(frames), int(_is_u8(frames)), _ptr(recon), int(_is_u8(recon)), hp, _ptr(hidden)))
         return recon, hidden
+
+    def score(self, frames, score=None, recon=None):
+        """Per-frame reconstruction error under the current weights (aefft_net_score): score[b] = mean over the frame's D*Nx*Ny pixels of
+        (x - r)^2, r the float32 reconstruction Net.infer would write.  uint8 `frames` are read as 8-bit pixels.  `score` (float32 [B]) is
+        allocated when None; `recon` (float32 [B][D][Nx][Ny], optional) receives the reconstruction from the same launch -- the spatial net
+        and the chirp-z transforms need it.  Nothing waits for the device.  Returns (score, recon)."""
+        if score is None:
+            score = self.ctx.empty(self.B)
+        self.ctx.check(self.L.aefft_net_score(self.h, _ptr(frames), int(_is_u8(frames)), _ptr(score), _ptr(recon)))
+        return score, recon
 
     def decode(self, code, hidden_pair, recon):
         """The reconstruction from a stored hidden layer (aefft_net_decode): `code` is float32 [B][dM][Nx_l][Ny_l] of pair `hidden_pair`, as

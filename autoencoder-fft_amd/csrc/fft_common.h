@@ -124,4 +124,27 @@ __device__ __forceinline__ float2 opin_load(const OpIn& o, long plane, int t, in
     return acc;
 }
 
+// ------------------------------------------------------------------------------------------
+// the scoring epilogue of the inverse row passes (aefft_net_score: c2r_rows_kernel<.., SCORE>, mix_c2r_rows_kernel<.., SCORE>)
+// ------------------------------------------------------------------------------------------
+// SCORE 0: none; 1: float frames; 2: 8-bit frames.  Only a scoring instantiation carries the argument: the others take the empty ScoreNone,
+// so their argument loads and their code are what they were.
+struct ScoreNone {};
+struct ScoreDev { const void* frames; float* part; };
+template <int SCORE> struct ScoreParam { typedef ScoreDev type; };
+template <> struct ScoreParam<0> { typedef ScoreNone type; };
+// The reconstructed pixel is the ROUNDED product z * scale, the value the float row pass stores.  Passing it through an empty asm makes it a
+// value of its own: the back end cannot contract the product into the subtraction that follows (x - z * scale as one fma would make the score
+// a function of the unrounded product, and a trained net's small residual is where that shows).
+__device__ __forceinline__ float score_px(float z, float scale) { float r = z * scale; asm("" : "+v"(r)); return r; }
+__device__ __forceinline__ float score_sq(float x, float r) { const float d = x - r; return d * d; }
+// the sum over an aligned segment of W lanes of a wave (W a power of two), in every lane of it: a butterfly, whose two partners add the same
+// two numbers at every level -- one fixed order, the same bits in every lane
+template <int W> __device__ __forceinline__ float score_seg_sum(float v)
+{
+#pragma unroll
+    for (int o = W / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
 }  // namespace aefft

@@ -259,18 +259,46 @@ __global__ __launch_bounds__(RowCfg<N>::NT) void r2c_rows_kernel(const void* __r
 // through LDS, no first-pass LDS reads, a third of the first pass's arithmetic; the passes at strides 8 and 64 follow unchanged.
 // U8: the rows go out as 8-bit pixels by SpinToImage_C's rule (netlib.cpp:66-68, px_u8 in fft_common.h) -- four per lane as one 32-bit store, a
 // quarter of the launch's writes; `out_v` is then unsigned char [npairs*2][N].  Everything in front of the store is the float kernel.
-template <int N, bool SPARSE, bool U8 = false>
+// SCORE (1: float frames, 2: 8-bit frames; aefft_net_score): the lane also holds the FRAME's pixels for the elements it ends up with -- the float4
+// it would store to, or one word of four 8-bit pixels, per row -- requested right behind the spectrum's loads so that they arrive under the
+// LDS passes (read once: streaming loads).  It forms (x - r)^2 for both rows of its pair, r = the rounded product it would store (score_px), stores r as
+// well when out_v is non-null (a uniform branch), and the row pair's sum goes to sc.part[pair]: eight terms per position in the lane, a
+// butterfly over the pair's lanes of the wave, the pair's waves in order through LDS -- no atomics, one order.  U8 is false with SCORE.
+template <int N, bool SPARSE, bool U8 = false, int SCORE = 0>
 __global__ __launch_bounds__(RowCfg<N>::NT) void c2r_rows_kernel(const float2* __restrict__ mid, void* __restrict__ out_v,
-                                                                   long npairs, int Wc, float scale)
+                                                                   long npairs, int Wc, float scale, const typename ScoreParam<SCORE>::type sc)
 {
     using Cfg = RowCfg<N>;
     constexpr int T = Cfg::T, NT = Cfg::NT, G = Cfg::G, PL = Cfg::PL;
+    static_assert(!(U8 && SCORE), "the scoring epilogue has no 8-bit reconstruction");
     extern __shared__ float2 s[];
     const int tid = threadIdx.x;
     const int g = tid / T, t = tid % T;
     FftTw<N, +1> tws;
     tws.load(t);
     const long pair0 = (long)blockIdx.x * G;
+    constexpr int NQ = G * (N / 4) / NT;                        // epilogue positions per lane (= 2 when NT = G*N/8)
+    [[maybe_unused]] float4 fa[NQ], fb[NQ];
+    [[maybe_unused]] unsigned ua[NQ], ub[NQ];
+    [[maybe_unused]] auto load_frames = [&](int lv) {
+        if constexpr (SCORE != 0) {
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) {
+                const int idx = tid + q * NT;
+                const int gg = idx / (N / 4), n4 = idx % (N / 4);
+                const int off = (gg < lv ? gg * (2 * N / 4) : 0) + n4;         // (32-bit lane offsets; rows that do not exist re-read pair 0)
+                if constexpr (SCORE == 1) {
+                    const float4* src = reinterpret_cast<const float4*>(static_cast<const float*>(sc.frames) + pair0 * 2 * N);
+                    fa[q] = ld_stream(&src[off]);
+                    fb[q] = ld_stream(&src[off + N / 4]);
+                } else {
+                    const unsigned* src = reinterpret_cast<const unsigned*>(static_cast<const unsigned char*>(sc.frames) + pair0 * 2 * N);
+                    ua[q] = __builtin_nontemporal_load(&src[off]);
+                    ub[q] = __builtin_nontemporal_load(&src[off + N / 4]);
+                }
+            }
+        }
+    };
     if constexpr (SPARSE) {
         static_assert(N >= 128, "sparse head: three radix-8 passes or more");
         const int live = npairs - pair0 < G ? (int)(npairs - pair0) : G;
@@ -281,6 +309,7 @@ __global__ __launch_bounds__(RowCfg<N>::NT) void c2r_rows_kernel(const float2* _
         const bool ok = g < live && (lo || hi);
         const int off = ok ? g * 2 * Wc + k : 0;
         float2 A = ibase[off], B = ibase[off + Wc];
+        load_frames(live);
         if (!ok) { A = make_float2(0.f, 0.f); B = A; }
         const float2 zz = make_float2(0.f, 0.f);
         // t = 0: DC of both rows in .x, Nyquist in .y of the packed column (imaginary parts ignored)
@@ -322,6 +351,7 @@ __global__ __launch_bounds__(RowCfg<N>::NT) void c2r_rows_kernel(const float2* _
         bv[q] = ld_stream(reinterpret_cast<const float4*>(ibase + off + Wc));
         if (!ok) { av[q] = make_float4(0.f, 0.f, 0.f, 0.f); bv[q] = av[q]; }
     }
+    load_frames(live);
 #pragma unroll
     for (int q = 0; q < NIT; ++q) {
         const int it = tid + q * NT;
@@ -345,8 +375,69 @@ __global__ __launch_bounds__(RowCfg<N>::NT) void c2r_rows_kernel(const float2* _
 
     // four consecutive complex elements per lane (read once, adjacent in the padded layout): their real parts are 16 bytes of row A, their
     // imaginary parts 16 bytes of row B
-    constexpr int NQ = G * (N / 4) / NT;
     const int live = npairs - pair0 < G ? (int)(npairs - pair0) : G;
+    if constexpr (SCORE != 0) {
+        float* const orow = static_cast<float*>(out_v) + pair0 * 2 * N;      // (read under `store` only)
+        const bool store = out_v != nullptr;
+        float acc[NQ];
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+            const int idx = tid + q * NT;
+            const int gg = idx / (N / 4), n = (idx % (N / 4)) * 4;
+            acc[q] = 0.f;
+            if (gg < live) {
+                const float2* z = s + gg * PL + pad_idx(n);
+                const float2 z0 = z[0], z1 = z[1], z2 = z[2], z3 = z[3];
+                const float4 ra = make_float4(score_px(z0.x, scale), score_px(z1.x, scale), score_px(z2.x, scale), score_px(z3.x, scale));
+                const float4 rb = make_float4(score_px(z0.y, scale), score_px(z1.y, scale), score_px(z2.y, scale), score_px(z3.y, scale));
+                float4 xa, xb;
+                if constexpr (SCORE == 1) { xa = fa[q]; xb = fb[q]; }
+                else {
+                    xa = make_float4((float)(ua[q] & 255u), (float)((ua[q] >> 8) & 255u), (float)((ua[q] >> 16) & 255u), (float)(ua[q] >> 24));
+                    xb = make_float4((float)(ub[q] & 255u), (float)((ub[q] >> 8) & 255u), (float)((ub[q] >> 16) & 255u), (float)(ub[q] >> 24));
+                }
+                float a = score_sq(xa.x, ra.x);
+                a += score_sq(xa.y, ra.y); a += score_sq(xa.z, ra.z); a += score_sq(xa.w, ra.w);
+                a += score_sq(xb.x, rb.x); a += score_sq(xb.y, rb.y); a += score_sq(xb.z, rb.z); a += score_sq(xb.w, rb.w);
+                acc[q] = a;
+                if (store) {
+                    st_stream(reinterpret_cast<float4*>(orow + (gg * 2) * N + n), ra);
+                    st_stream(reinterpret_cast<float4*>(orow + (gg * 2 + 1) * N + n), rb);
+                }
+            }
+        }
+        // a row pair's N/4 positions lie in consecutive lanes of one q (N/4 <= NT), or are the whole workgroup's, both q (N = 2048)
+        constexpr int LPP = N / 4 < NT ? N / 4 : NT;        // lanes of one row pair
+        constexpr int NR = N / 4 <= NT ? NQ : 1;            // row pairs a lane contributes to
+        if constexpr (N / 4 > NT) acc[0] += acc[1];
+        if constexpr (LPP <= 64) {
+#pragma unroll
+            for (int q = 0; q < NR; ++q) {
+                const float v = score_seg_sum<LPP>(acc[q]);
+                const int gg = (tid + q * NT) / (N / 4);
+                if (tid % LPP == 0 && gg < live) sc.part[pair0 + gg] = v;
+            }
+        } else {
+            __shared__ float red[NR][NT / 64];
+#pragma unroll
+            for (int q = 0; q < NR; ++q) {
+                const float v = score_seg_sum<64>(acc[q]);
+                if ((tid & 63) == 0) red[q][tid >> 6] = v;
+            }
+            __syncthreads();
+#pragma unroll
+            for (int q = 0; q < NR; ++q) {
+                const int gg = N / 4 > NT ? 0 : (tid + q * NT) / (N / 4);
+                if (tid % LPP == 0 && gg < live) {
+                    float v = red[q][tid >> 6];
+#pragma unroll
+                    for (int w = 1; w < LPP / 64; ++w) v += red[q][(tid >> 6) + w];
+                    sc.part[pair0 + gg] = v;
+                }
+            }
+        }
+        return;
+    }
     if constexpr (U8) {
         unsigned* const orow = reinterpret_cast<unsigned*>(static_cast<unsigned char*>(out_v) + pair0 * 2 * N);      // four pixels per word
 #pragma unroll
@@ -608,23 +699,33 @@ template <int N> static hipError_t run_r2c_rows(const void* in, float2* mid, lon
     else r2c_rows_kernel<N, false><<<dim3((unsigned)blocks), dim3(Cfg::NT), lds, st>>>(in, mid, npairs, Wc);
     return hipGetLastError();
 }
-template <int N, bool SPARSE, bool U8> static hipError_t run_c2r_rows_as(const float2* mid, void* out, long npairs, int Wc, float scale, hipStream_t st)
+template <int N, bool SPARSE, bool U8, int SCORE = 0>
+static hipError_t run_c2r_rows_as(const float2* mid, void* out, long npairs, int Wc, float scale, hipStream_t st, const typename ScoreParam<SCORE>::type sc = {})
 {
     using Cfg = RowCfg<N>;
     const size_t lds = sizeof(float2) * (Cfg::G * Cfg::PL);
     const long blocks = (npairs + Cfg::G - 1) / Cfg::G;
-    hipError_t e = allow_lds(c2r_rows_kernel<N, SPARSE, U8>, lds);
+    hipError_t e = allow_lds(c2r_rows_kernel<N, SPARSE, U8, SCORE>, lds);
     if (e != hipSuccess) return e;
-    c2r_rows_kernel<N, SPARSE, U8><<<dim3((unsigned)blocks), dim3(Cfg::NT), lds, st>>>(mid, out, npairs, Wc, scale);
+    c2r_rows_kernel<N, SPARSE, U8, SCORE><<<dim3((unsigned)blocks), dim3(Cfg::NT), lds, st>>>(mid, out, npairs, Wc, scale, sc);
     return hipGetLastError();
 }
-template <int N> static hipError_t run_c2r_rows(const float2* mid, void* out, long npairs, int Wc, float scale, hipStream_t st, bool out_u8)
+template <int N, bool SPARSE> static hipError_t run_c2r_rows_sp(const float2* mid, void* out, long npairs, int Wc, float scale, hipStream_t st, bool out_u8, const ScoreArg* score)
+{
+    if (score) {
+        if (out_u8 || !score->frames || !score->part) return hipErrorInvalidValue;
+        const ScoreDev sc{score->frames, score->part};
+        return score->u8 ? run_c2r_rows_as<N, SPARSE, false, 2>(mid, out, npairs, Wc, scale, st, sc) : run_c2r_rows_as<N, SPARSE, false, 1>(mid, out, npairs, Wc, scale, st, sc);
+    }
+    return out_u8 ? run_c2r_rows_as<N, SPARSE, true>(mid, out, npairs, Wc, scale, st) : run_c2r_rows_as<N, SPARSE, false>(mid, out, npairs, Wc, scale, st);
+}
+template <int N> static hipError_t run_c2r_rows(const float2* mid, void* out, long npairs, int Wc, float scale, hipStream_t st, bool out_u8, const ScoreArg* score)
 {
     if constexpr (N >= 128) {
         if (Wc <= N / 16)                            // few non-zero columns (the reconstruction of a pooled network): sparse first pass
-            return out_u8 ? run_c2r_rows_as<N, true, true>(mid, out, npairs, Wc, scale, st) : run_c2r_rows_as<N, true, false>(mid, out, npairs, Wc, scale, st);
+            return run_c2r_rows_sp<N, true>(mid, out, npairs, Wc, scale, st, out_u8, score);
     }
-    return out_u8 ? run_c2r_rows_as<N, false, true>(mid, out, npairs, Wc, scale, st) : run_c2r_rows_as<N, false, false>(mid, out, npairs, Wc, scale, st);
+    return run_c2r_rows_sp<N, false>(mid, out, npairs, Wc, scale, st, out_u8, score);
 }
 template <int N, int CW> static hipError_t run_fwd_cols(const float2* mid, float2* out, long planes, int Wc, int Nxs, hipStream_t st, hipEvent_t done)
 {
@@ -851,8 +952,9 @@ hipError_t launch_r2c(const void* in, float2* out, float2* mid, long planes, int
 
 // `in` non-null: run the column pass (in -> mid); `out` non-null: run the row pass (mid -> out).
 // out_u8: `out` is unsigned char [planes][Nx][Ny], written by the row pass with SpinToImage_C's rule (c2r_rows_kernel<N, SPARSE, true>).
+// score: the row pass runs its scoring epilogue (internal.h ScoreArg); `out` may then be null
 hipError_t launch_c2r(const float2* in, void* out, float2* mid, long planes, int Nxi, int Nyi, int Nx, int Ny, float scale, hipStream_t st, const OpIn* opin,
-                      bool out_u8)
+                      bool out_u8, const ScoreArg* score)
 {
     const OpIn op = opin ? *opin : g_opin_none;
     if ((Nxi == Nx) != (Nyi == Ny)) return hipErrorInvalidValue;   // pad both axes or none
@@ -868,9 +970,9 @@ hipError_t launch_c2r(const float2* in, void* out, float2* mid, long planes, int
             else e = launch_mix_inv_cols(in, mid, planes, Nx, Wc, Nxi, st, op.A ? &op : nullptr);
             if (e != hipSuccess) return e;
         }
-        if (out) {
-            if (rows_pow2(Ny, Wc)) { AEFFT_N_SWITCH(Ny, e = run_c2r_rows<NN>(mid, out, npairs, Wc, scale, st, out_u8); break) }
-            else e = launch_mix_c2r_rows(mid, out, npairs, Ny, Wc, scale, st, out_u8);
+        if (out || score) {
+            if (rows_pow2(Ny, Wc)) { AEFFT_N_SWITCH(Ny, e = run_c2r_rows<NN>(mid, out, npairs, Wc, scale, st, out_u8, score); break) }
+            else e = launch_mix_c2r_rows(mid, out, npairs, Ny, Wc, scale, st, out_u8, score);
         }
         return e;
     }
@@ -882,8 +984,8 @@ hipError_t launch_c2r(const float2* in, void* out, float2* mid, long planes, int
         AEFFT_N_SWITCH(Nx, e = (cols_dispatch<NN, false>(in, mid, planes, Wc, Nxi, st, op)); break)
         if (e != hipSuccess) return e;
     }
-    if (out) {
-        AEFFT_N_SWITCH(Ny, e = run_c2r_rows<NN>(mid, out, npairs, Wc, scale, st, out_u8); break)
+    if (out || score) {
+        AEFFT_N_SWITCH(Ny, e = run_c2r_rows<NN>(mid, out, npairs, Wc, scale, st, out_u8, score); break)
     }
     return e;
 }

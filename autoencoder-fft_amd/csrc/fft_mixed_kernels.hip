@@ -201,10 +201,15 @@ __global__ __launch_bounds__(MixRowCfg<T>::NT) void mix_r2c_rows_kernel(const vo
 // inverse: mid [npairs*2][Wc] packed half spectra (the columns from Wc to n/2 are zero) -> out [npairs*2][n] real, times scale
 // U8: ... -> unsigned char [npairs*2][n] by SpinToImage_C's rule (px_u8, fft_common.h), two pixels per 16-bit store (n is even: every row
 // starts on a 2-byte boundary whatever n % 4 is, as on the forward pass's load)
-template <int T, bool U8 = false>
+// SCORE (1: float frames, 2: 8-bit frames; aefft_net_score, as c2r_rows_kernel's): thread t of row pair g takes the element pairs t, t + T, ..
+// of ITS pair (at most four: n <= 8 T) -- the frame's two pixels of both rows requested behind the spectrum's loads, (x - r)^2 against the
+// rounded product, r stored as well when `out` is non-null -- and the pair's sum is reduced across its T threads: the lane's terms in order, a
+// butterfly over the pair's lanes of the wave, the pair's waves in order through LDS.  One float per row pair to sc.part.
+template <int T, bool U8 = false, int SCORE = 0>
 __global__ __launch_bounds__(MixRowCfg<T>::NT) void mix_c2r_rows_kernel(const float2* __restrict__ mid, void* __restrict__ out, long npairs,
-                                                                         int Wc, float scale, const MixPlan pl)
+                                                                         int Wc, float scale, const MixPlan pl, const typename ScoreParam<SCORE>::type sc)
 {
+    static_assert(!(U8 && SCORE), "the scoring epilogue has no 8-bit reconstruction");
     constexpr int NT = MixRowCfg<T>::NT, G = MixRowCfg<T>::G;
     extern __shared__ float2 s[];
     const int N = pl.n, H = N / 2, PL = pad_len(N);
@@ -228,9 +233,67 @@ __global__ __launch_bounds__(MixRowCfg<T>::NT) void mix_c2r_rows_kernel(const fl
             z[pad_idx(N - k)] = make_float2(A.x + B.y, -A.y + B.x);     // conj(A) + i conj(B)
         }
     }
+    constexpr int NJ = 4;                                           // element pairs of a row per thread: H <= 4 T
+    [[maybe_unused]] float2 fa[NJ], fb[NJ];
+    [[maybe_unused]] unsigned ua[NJ], ub[NJ];
+    if constexpr (SCORE != 0) {
+        const long r0 = (pair0 + (g < live ? g : 0)) * 2 * H;     // (a row pair that does not exist re-reads pair 0; an element pair beyond the row, pair 0 of it)
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            const int c = t + j * T < H ? t + j * T : 0;
+            if constexpr (SCORE == 1) {
+                const float2* src = static_cast<const float2*>(sc.frames);
+                fa[j] = ld_stream(&src[r0 + c]);                    // (frames are read once)
+                fb[j] = ld_stream(&src[r0 + H + c]);
+            } else {
+                const unsigned short* src = static_cast<const unsigned short*>(sc.frames);
+                ua[j] = __builtin_nontemporal_load(&src[r0 + c]);
+                ub[j] = __builtin_nontemporal_load(&src[r0 + H + c]);
+            }
+        }
+    }
     __syncthreads();
     mix_fft<T, +1>(s + g * PL, t, pl);
 
+    if constexpr (SCORE != 0) {
+        float2* const o = static_cast<float2*>(out);
+        const bool store = out != nullptr;
+        const float2* z = s + g * PL;
+        float acc = 0.f;
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            const int c = t + j * T;
+            if (g < live && c < H) {
+                const float2 z0 = z[pad_idx(2 * c)], z1 = z[pad_idx(2 * c + 1)];
+                const float2 ra = make_float2(score_px(z0.x, scale), score_px(z1.x, scale)), rb = make_float2(score_px(z0.y, scale), score_px(z1.y, scale));
+                float2 xa, xb;
+                if constexpr (SCORE == 1) { xa = fa[j]; xb = fb[j]; }
+                else { xa = make_float2((float)(ua[j] & 255u), (float)(ua[j] >> 8)); xb = make_float2((float)(ub[j] & 255u), (float)(ub[j] >> 8)); }
+                acc += score_sq(xa.x, ra.x); acc += score_sq(xa.y, ra.y); acc += score_sq(xb.x, rb.x); acc += score_sq(xb.y, rb.y);
+                if (store) {
+                    const long ra_i = (pair0 + g) * 2 * H + c;
+                    st_stream(&o[ra_i], ra);
+                    st_stream(&o[ra_i + H], rb);
+                }
+            }
+        }
+        if constexpr (T <= 64) {
+            const float v = score_seg_sum<T>(acc);
+            if (t == 0 && g < live) sc.part[pair0 + g] = v;
+        } else {
+            __shared__ float red[NT / 64];
+            const float v = score_seg_sum<64>(acc);
+            if ((tid & 63) == 0) red[tid >> 6] = v;
+            __syncthreads();
+            if (t == 0 && g < live) {
+                float w = red[tid >> 6];
+#pragma unroll
+                for (int k = 1; k < T / 64; ++k) w += red[(tid >> 6) + k];
+                sc.part[pair0 + g] = w;
+            }
+        }
+        return;
+    }
     if constexpr (U8) {
         unsigned short* const o8 = static_cast<unsigned short*>(out);
         for (int it = tid; it < live * H; it += NT) {
@@ -448,14 +511,21 @@ template <int T> static hipError_t run_mix_r2c_rows(const void* in, float2* mid,
     else mix_r2c_rows_kernel<T, false><<<dim3((unsigned)blocks), dim3(Cfg::NT), lds, st>>>(in, mid, npairs, Wc, pl);
     return hipGetLastError();
 }
-template <int T> static hipError_t run_mix_c2r_rows(const float2* mid, void* out, long npairs, int Wc, float scale, const MixPlan& pl, hipStream_t st, bool u8)
+template <int T> static hipError_t run_mix_c2r_rows(const float2* mid, void* out, long npairs, int Wc, float scale, const MixPlan& pl, hipStream_t st, bool u8,
+                                                    const ScoreArg* score)
 {
     using Cfg = MixRowCfg<T>;
     const size_t lds = sizeof(float2) * (size_t)Cfg::G * pad_len(pl.n);
     const long blocks = (npairs + Cfg::G - 1) / Cfg::G;
     if (blocks >= (1L << 31)) return hipErrorInvalidValue;
-    if (u8) mix_c2r_rows_kernel<T, true><<<dim3((unsigned)blocks), dim3(Cfg::NT), lds, st>>>(mid, out, npairs, Wc, scale, pl);
-    else mix_c2r_rows_kernel<T, false><<<dim3((unsigned)blocks), dim3(Cfg::NT), lds, st>>>(mid, out, npairs, Wc, scale, pl);
+    if (score) {
+        if (u8 || !score->frames || !score->part) return hipErrorInvalidValue;
+        const ScoreDev sc{score->frames, score->part};
+        if (score->u8) mix_c2r_rows_kernel<T, false, 2><<<dim3((unsigned)blocks), dim3(Cfg::NT), lds, st>>>(mid, out, npairs, Wc, scale, pl, sc);
+        else mix_c2r_rows_kernel<T, false, 1><<<dim3((unsigned)blocks), dim3(Cfg::NT), lds, st>>>(mid, out, npairs, Wc, scale, pl, sc);
+    }
+    else if (u8) mix_c2r_rows_kernel<T, true><<<dim3((unsigned)blocks), dim3(Cfg::NT), lds, st>>>(mid, out, npairs, Wc, scale, pl, ScoreNone{});
+    else mix_c2r_rows_kernel<T, false><<<dim3((unsigned)blocks), dim3(Cfg::NT), lds, st>>>(mid, out, npairs, Wc, scale, pl, ScoreNone{});
     return hipGetLastError();
 }
 
@@ -499,13 +569,13 @@ hipError_t launch_mix_r2c_rows(const void* in, float2* mid, long npairs, int Ny,
     AEFFT_T_SWITCH(mix_threads(Ny), e = run_mix_r2c_rows<TT>(in, mid, npairs, Wc, pl, st, in_u8); break)
     return e;
 }
-hipError_t launch_mix_c2r_rows(const float2* mid, void* out, long npairs, int Ny, int Wc, float scale, hipStream_t st, bool out_u8)
+hipError_t launch_mix_c2r_rows(const float2* mid, void* out, long npairs, int Ny, int Wc, float scale, hipStream_t st, bool out_u8, const ScoreArg* score)
 {
     MixPlan pl;
     hipError_t e = mix_plan(Ny, &pl);
     if (e != hipSuccess) return e;
     if (Wc < 1 || 2 * Wc > Ny) return hipErrorInvalidValue;
-    AEFFT_T_SWITCH(mix_threads(Ny), e = run_mix_c2r_rows<TT>(mid, out, npairs, Wc, scale, pl, st, out_u8); break)
+    AEFFT_T_SWITCH(mix_threads(Ny), e = run_mix_c2r_rows<TT>(mid, out, npairs, Wc, scale, pl, st, out_u8, score); break)
     return e;
 }
 hipError_t launch_mix_fwd_cols(const float2* mid, float2* out, long planes, int Nx, int Wc, int Nxs, hipStream_t st, hipEvent_t done)

@@ -13,7 +13,7 @@ enum { WS_MID = 0, WS_REAL = 1, WS_S = 2, WS_ES = 3, WS_E = 4, WS_DC = 5, WS_DF 
 // fine-grained kernel ids for profiling; the public classes (aefft.h) aggregate them
 enum {
     KID_R2C_ROWS = 0, KID_R2C_COLS, KID_C2R_COLS, KID_C2R_ROWS, KID_CONTRACT, KID_RESIZE, KID_DIFFMSE, KID_BIASGRAD,
-    KID_PAD, KID_SHRINK, KID_UPDATE, KID_GDIFF, KID_SPATIAL, KID_KSPEC, KID_KGRAD, KID_WGRAD, KID_OPFORM, KID_CHAIN, KID_SGRAD, KID_OPMSE, KID_COUNT
+    KID_PAD, KID_SHRINK, KID_UPDATE, KID_GDIFF, KID_SPATIAL, KID_KSPEC, KID_KGRAD, KID_WGRAD, KID_OPFORM, KID_CHAIN, KID_SGRAD, KID_OPMSE, KID_SCORE, KID_COUNT
 };
 
 struct ProfEvent { hipEvent_t a, b; int kid; double bytes; };
@@ -100,8 +100,12 @@ bool net_size(int n);
 int do_r2c(aefft_ctx* ctx, const float* x, float2* X, long planes, int Nx, int Ny, int Nxs, int Nys, int ws_id = WS_MID, hipEvent_t done = nullptr,
            bool u8 = false);
 // out_u8: x is unsigned char [planes][Nx][Ny] (8-bit pixels, SpinToImage_C's rule; the power-of-two and mixed-radix routes only)
+// score (nullable, aefft_net_score): the row-pair partial sums of the squared difference between score->frames and the rows this transform
+// produces, into score->part -- by the row pass's scoring epilogue (x may then be null: nothing is stored), or, on the any-size route, by
+// score_diff_kernel from the stored x (which it needs: c2r_scores_in_rows says which)
 int do_c2r(aefft_ctx* ctx, const float2* X, void* x, long planes, int Nxi, int Nyi, int Nx, int Ny, float scale, int ws_id = WS_MID,
-           const OpIn* opin = nullptr, bool out_u8 = false);
+           const OpIn* opin = nullptr, bool out_u8 = false, const ScoreArg* score = nullptr);
+bool c2r_scores_in_rows(int Nx, int Ny);     // a net's reconstruction on this frame grid comes out of one of the two row kernels (under the current switches)
 double contract_bytes(const Contract& q);
 Contract bc(const aefft_ctx* ctx, Contract q);
 int do_contract(aefft_ctx* ctx, const Contract& q0);

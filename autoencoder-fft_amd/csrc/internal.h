@@ -34,8 +34,17 @@ constexpr int CH_MAXSTEPS = 40;       // most steps of a per-bin chain item (cha
 constexpr int CH_VMAX = 128;          // most rows of a matrix the packed-record kernels (chain, innermost-pair MSE) take
 struct OpIn { const float2* A; const float2* Xf; int D0, Nx0, Ny0; };
 // out_u8: `out` is unsigned char [planes][Nx][Ny]: the row pass writes 8-bit pixels by SpinToImage_C's rule (netlib.cpp:66-68)
+// score (nullable; aefft_net_score): the row pass compares the rows it holds with the frames instead of only storing them -- frames [planes][Nx][Ny]
+// float, or unsigned char when u8; part [planes*Nx/2] receives one float per ROW PAIR, the sum of (x - r)^2 over the pair's 2 Ny pixels with r the
+// rounded product the float row pass stores.  `out` (float, not out_u8) is then optional: non-null, it receives r as without `score`.
+struct ScoreArg { const void* frames; bool u8; float* part; };
 hipError_t launch_c2r(const float2* in, void* out, float2* mid, long planes, int Nxi, int Nyi,
-                      int Nx, int Ny, float scale, hipStream_t st, const OpIn* opin = nullptr, bool out_u8 = false);
+                      int Nx, int Ny, float scale, hipStream_t st, const OpIn* opin = nullptr, bool out_u8 = false, const ScoreArg* score = nullptr);
+// The same partials from a STORED float reconstruction (routes whose reconstruction does not come out of one of the two row kernels): a frame's
+// `rows` rows of n floats are taken two at a time (an odd last row alone), part [B][(rows+1)/2]
+hipError_t launch_score_diff(const void* frames, bool u8, const float* recon, float* part, int B, long rows, int n, hipStream_t st);
+// score[b] = scale * (part[b][0] + part[b][1] + ...), npf partials per frame, summed in double in a fixed order
+hipError_t launch_score_finish(const float* part, float* score, int B, long npf, double scale, hipStream_t st);
 size_t fft_mid_elems(long planes, int Nx, int Wc);   // complex elements needed in `mid`
 // sizes that are not powers of two (cufftPlanMany takes any size, fft.cu:773-779): even n in 8..1024 through Bluestein's chirp-z form on the
 // power-of-two LDS passes; rows -> transpose -> rows -> transpose.  w1, w2: workspaces of fft_any_ws_elems complex each.
@@ -54,7 +63,8 @@ hipError_t launch_mix_r2c_rows(const void* in, float2* mid, long npairs, int Ny,
 hipError_t launch_mix_fwd_cols(const float2* mid, float2* out, long planes, int Nx, int Wc, int Nxs, hipStream_t st, hipEvent_t done);
 hipError_t launch_mix_inv_cols(const float2* in, float2* mid, long planes, int Nx, int Wc, int Nxi, hipStream_t st,
                                const OpIn* opin = nullptr /* the spectra evaluated on load from an operator (launch_c2r); then in == null */);
-hipError_t launch_mix_c2r_rows(const float2* mid, void* out, long npairs, int Ny, int Wc, float scale, hipStream_t st, bool out_u8 = false);
+hipError_t launch_mix_c2r_rows(const float2* mid, void* out, long npairs, int Ny, int Wc, float scale, hipStream_t st, bool out_u8 = false,
+                               const ScoreArg* score = nullptr);
 
 // ---- spectral_kernels.hip --------------------------------------------------------------
 // Per-bin complex contraction  Out[r][c][bin] = alpha * sum_k opA(A[r][k][bin]) * opB(B[k][c][bin])

@@ -69,6 +69,8 @@ struct aefft_net {
     int dec_nt = 0, dec_w = 0; // threads (bins in flight) and column stride (max dM + 1: the longest row with its affine element) it was allocated for
     int dec_pair = -1;         // ... of this pair
     bool dec_valid = false;    // ... and of the CURRENT weights (weights_changed)
+    // per-frame reconstruction error (aefft_net_score)
+    float* score_part = nullptr; // [B][(D*Nx + 1)/2] one partial sum of squared differences per ROW PAIR of a frame (the row passes' scoring epilogue, score_diff_kernel)
     float2* Wp = nullptr;      // [Pc][packE] bin-major copy of the kernel spectra the coarsest-grid chain items read (kspec_packed_kernel)
     aefft::PackArgs pack{};    // its description (static per net)
     bool packed_valid = false; // Wp belongs to the CURRENT weights (weights_changed)
@@ -186,7 +188,9 @@ OpView op_view(const aefft_net* n, int l);
 int cc_problems(aefft_net* n, PrunedGroup& pg, int first, double* bytes);
 int ensure_packed(aefft_net* n);
 void fill_chain(aefft_net* n, ChainArgs& ca, int set, double* bytes);
-int launch_recon(aefft_net* n, void* recon_d, int wsid, bool out_u8 = false);
+// score (nullable, aefft_net_score): handed to the inverse transform's row pass (do_c2r); recon_d may then be null where c2r_scores_in_rows
+int launch_recon(aefft_net* n, void* recon_d, int wsid, bool out_u8 = false, const ScoreArg* score = nullptr);
+inline long score_pairs_per_frame(const aefft_net* n) { return ((long)n->D * n->Nx + 1) / 2; }
 int net_forward(aefft_net* n, const float* frames_d, bool u8, float* recon_d, bool lazy, bool op = false, bool infer = false);
 #pragma GCC visibility pop
 

@@ -1,6 +1,6 @@
 // C-ABI layer (include/aefft.h), the resident network's forward: net_forward and its stages, the operator chain and the bin-major record it
 // reads (ensure_packed, fill_chain), the reconstruction (launch_recon), the per-frame expansion of an operator-form step (ensure_frames), and
-// the entry points that only run forward: aefft_net_forward*, aefft_net_infer, aefft_net_decode.  Bursts and the training step: net_step.hip.
+// the entry points that only run forward: aefft_net_forward*, aefft_net_infer, aefft_net_score, aefft_net_decode.  Bursts and the training step: net_step.hip.
 #include "net.h"
 
 #include <algorithm>
@@ -78,7 +78,8 @@ void aefft::fill_chain(aefft_net* n, ChainArgs& ca, int set, double* bytes)
 
 // the reconstruction's inverse FFT (fft_backproplib.cu:1373) on ctx->cur; operator form: the per-frame spectra are expanded first
 // out_u8: recon_d is unsigned char, written as 8-bit pixels by the row pass
-int aefft::launch_recon(aefft_net* n, void* recon_d, int wsid, bool out_u8)
+// score: the row pass (or, behind the any-size transforms, score_diff_kernel) leaves the row-pair sums of the squared difference to score->frames
+int aefft::launch_recon(aefft_net* n, void* recon_d, int wsid, bool out_u8, const ScoreArg* score)
 {
     aefft_ctx* ctx = n->ctx;
     Pair& q = n->pr[0];
@@ -99,13 +100,13 @@ int aefft::launch_recon(aefft_net* n, void* recon_d, int wsid, bool out_u8)
             if (need > n->recon_exp_n) { RET_IF(net_alloc_t(n, &n->recon_exp, need)); n->recon_exp_n = need; }
             RET_IF(launch_or_fail(ctx, KID_OPFORM, ((double)OPC * q.dD * PO + (double)n->B * q.dD * PO + (double)n->B * q.dD * q.P) * 8.0, "recon_expand",
                                   [&] { return launch_recon_expand(src, n->Xf, n->recon_exp, n->B, q.dD, q.Nx, q.Ny, nxo, nyo, ctx->cur); }));
-            return do_c2r(ctx, n->recon_exp, recon_d, (long)n->B * q.dD, nxo, nyo, n->Nx, n->Ny, 1.0f / ((float)n->Nx * (float)n->Ny), wsid, nullptr, out_u8);
+            return do_c2r(ctx, n->recon_exp, recon_d, (long)n->B * q.dD, nxo, nyo, n->Nx, n->Ny, 1.0f / ((float)n->Nx * (float)n->Ny), wsid, nullptr, out_u8, score);
         }
         // small supports: O_0,b = O^_0 [x_b; 1] is evaluated inside the column pass of the inverse transform (no stored planes)
         const OpIn op{src, n->Xf, q.dD, q.Nx, q.Ny};
-        return do_c2r(ctx, nullptr, recon_d, (long)n->B * q.dD, nxo, nyo, n->Nx, n->Ny, 1.0f / ((float)n->Nx * (float)n->Ny), wsid, &op, out_u8);
+        return do_c2r(ctx, nullptr, recon_d, (long)n->B * q.dD, nxo, nyo, n->Nx, n->Ny, 1.0f / ((float)n->Nx * (float)n->Ny), wsid, &op, out_u8, score);
     }
-    return do_c2r(ctx, src, recon_d, (long)n->B * q.dD, nxo, nyo, n->Nx, n->Ny, 1.0f / ((float)n->Nx * (float)n->Ny), wsid, nullptr, out_u8);
+    return do_c2r(ctx, src, recon_d, (long)n->B * q.dD, nxo, nyo, n->Nx, n->Ny, 1.0f / ((float)n->Nx * (float)n->Ny), wsid, nullptr, out_u8, score);
 }
 
 // How net_forward runs, decided in front of its first launch.
@@ -486,6 +487,45 @@ extern "C" int aefft_net_infer(aefft_net* n, const void* frames_d, int frames_u8
         if (op) RET_IF(infer_hidden_op(n, hidden_pair, hidden_d));
         else RET_IF(aefft_net_get_layer(n, 2 * hidden_pair + 2, hidden_d, nullptr, nullptr, nullptr));      // formed on request from the pair's input
     }
+    return mark_step_point(n);
+}
+
+// ------------------------------------------------------------------------------------------
+// per-frame reconstruction error (include/aefft.h aefft_net_score)
+// ------------------------------------------------------------------------------------------
+// a frame's row-pair partials added up (score_finish_kernel): score_d[b] = sum / (D Nx Ny)
+static int score_finish(aefft_net* n, float* score_d)
+{
+    aefft_ctx* ctx = n->ctx;
+    const long npf = score_pairs_per_frame(n);
+    return launch_or_fail(ctx, KID_SCORE, (double)n->B * (npf + 1) * 4.0, "score_finish",
+                          [&] { return launch_score_finish(n->score_part, score_d, n->B, npf, 1.0 / ((double)n->D * n->Nx * n->Ny), ctx->cur); });
+}
+
+// aefft_net_infer's body with the score argument handed to the reconstruction, then the finish launch
+extern "C" int aefft_net_score(aefft_net* n, const void* frames_d, int frames_u8, float* score_d, float* recon_d)
+{
+    if (!n) return AEFFT_EINVAL;
+    aefft_ctx* ctx = n->ctx;
+    if (!frames_d || !score_d) return fail(ctx, AEFFT_EINVAL, "aefft_net_score: null frames or score");
+    if (!aligned16p(frames_d) || !aligned16p(score_d) || !aligned16p(recon_d)) return fail(ctx, AEFFT_EINVAL, "aefft_net_score: pointers must be 16-byte aligned");
+    if (n->spatial) {
+        if (frames_u8) return sp_refuse(n, "aefft_net_score with 8-bit frames");
+        if (!recon_d) return fail(ctx, AEFFT_EINVAL, "aefft_net_score: a spatial net's reconstruction is written by its last convolution, not by an inverse transform's row pass -- the score is formed from the stored reconstruction, so recon_d must be given");
+        RET_IF(sp_forward(n, static_cast<const float*>(frames_d), recon_d));
+        RET_IF(launch_or_fail(ctx, KID_SCORE, (double)n->B * n->D * n->Nx * n->Ny * 8.0, "score_diff", [&] {
+            return launch_score_diff(frames_d, false, recon_d, n->score_part, n->B, (long)n->D * n->Nx, n->Ny, ctx->cur);
+        }));
+        RET_IF(score_finish(n, score_d));
+        return mark_step_point(n);
+    }
+    if (!recon_d && !c2r_scores_in_rows(n->Nx, n->Ny))
+        return fail(ctx, AEFFT_EINVAL, "aefft_net_score: under AEFFT_F_CHIRPZ this grid's reconstruction comes out of the chirp-z transforms, not of an inverse row pass -- the score is formed from the stored reconstruction, so recon_d must be given");
+    const bool op = op_eligible(n);
+    RET_IF(net_forward(n, static_cast<const float*>(frames_d), frames_u8 != 0, nullptr, true, op, true));
+    const ScoreArg sc{frames_d, frames_u8 != 0, n->score_part};
+    RET_IF(launch_recon(n, recon_d, WS_MID, false, &sc));
+    RET_IF(score_finish(n, score_d));
     return mark_step_point(n);
 }
 

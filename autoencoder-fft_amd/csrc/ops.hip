@@ -108,21 +108,32 @@ int aefft::do_r2c(aefft_ctx* ctx, const float* x, float2* X, long planes, int Nx
     return AEFFT_OK;
 }
 
+// (every pair's grid of a net on a power-of-two frame grid is a power of two: the frame grid decides)
+bool aefft::c2r_scores_in_rows(int Nx, int Ny) { return pow2_sizes(Nx, Ny) || mixed_route(Nx, Ny); }
+
 int aefft::do_c2r(aefft_ctx* ctx, const float2* X, void* x, long planes, int Nxi, int Nyi, int Nx, int Ny, float scale, int ws_id, const OpIn* opin,
-                  bool out_u8)
+                  bool out_u8, const ScoreArg* score)
 {
+    if (score && out_u8) return fail(ctx, AEFFT_EINVAL, "c2r: the scoring row pass writes no 8-bit pixels");
     if (!opin && (!pow2_sizes(Nx, Ny) || !pow2_sizes(Nxi, Nyi)) && !mixed_route(Nx, Ny)) {
         if (out_u8) return fail(ctx, AEFFT_EINVAL, "c2r: 8-bit output needs a power-of-two or smooth grid");
+        if (score && !x) return fail(ctx, AEFFT_EINVAL, "c2r: on the any-size route the score is formed from the stored reconstruction, which was not asked for");
         RET_IF(chk_size_any(ctx, Nx, Ny));
         if (Nx > 1024 || Ny > 1024) return fail(ctx, AEFFT_EINVAL, "c2r: a zero-pad from a size that is not a power of two needs a grid of at most 1024 x 1024");
         if (!aligned16(x) || !aligned16(X)) return fail(ctx, AEFFT_EINVAL, "c2r: pointers must be 16-byte aligned");
-        return do_c2r_any(ctx, X, static_cast<float*>(x), planes, Nxi, Nyi, Nx, Ny, scale);
+        RET_IF(do_c2r_any(ctx, X, static_cast<float*>(x), planes, Nxi, Nyi, Nx, Ny, scale));
+        if (!score) return AEFFT_OK;
+        // (planes * Nx rows taken two at a time: Nx is even, so the pairs are the row pass's)
+        return launch_or_fail(ctx, KID_SCORE, (double)planes * Nx * Ny * (score->u8 ? 5.0 : 8.0), "score_diff",
+                              [&] { return launch_score_diff(score->frames, score->u8, static_cast<const float*>(x), score->part, 1, planes * Nx, Ny, ctx->cur); });
     }
     if (!aligned16(x) || (!opin && !aligned16(X))) return fail(ctx, AEFFT_EINVAL, "c2r: pointers must be 16-byte aligned");
     if (Nxi > Nx || Nyi > Ny || Nxi < 2 || Nyi < 2 || (Nxi & 1) || (Nyi & 1)) return fail(ctx, AEFFT_EINVAL, "c2r: padded-from size must be even and inside the grid");
     void* mid;
     RET_IF(ws_get(ctx, ws_id, sizeof(float2) * fft_mid_elems(planes, Nx, Nyi / 2), &mid));
-    const double b_in = (double)planes * bins(Nxi, Nyi) * 8, b_mid = (double)planes * Nx * (Nyi / 2) * 8, b_out = (double)planes * Nx * Ny * (out_u8 ? 1 : 4);
+    const double b_in = (double)planes * bins(Nxi, Nyi) * 8, b_mid = (double)planes * Nx * (Nyi / 2) * 8;
+    // (the scoring row pass reads the frames, writes one float per row pair, and the rows only when they were asked for)
+    const double b_out = (double)planes * Nx * Ny * (out_u8 ? 1 : (x ? 4 : 0)) + (score ? (double)planes * Nx * Ny * (score->u8 ? 1 : 4) + (double)planes * Nx * 2 : 0.0);
     hipError_t e;
     {
         Bracket br(ctx, KID_C2R_COLS, b_in + b_mid);
@@ -131,7 +142,7 @@ int aefft::do_c2r(aefft_ctx* ctx, const float2* X, void* x, long planes, int Nxi
     if (e != hipSuccess) return fail(ctx, AEFFT_EHIP, "c2r cols", e);
     {
         Bracket br(ctx, KID_C2R_ROWS, b_mid + b_out);
-        e = launch_c2r(nullptr, x, (float2*)mid, planes, Nxi, Nyi, Nx, Ny, scale, ctx->cur, nullptr, out_u8);
+        e = launch_c2r(nullptr, x, (float2*)mid, planes, Nxi, Nyi, Nx, Ny, scale, ctx->cur, nullptr, out_u8, score);
     }
     if (e != hipSuccess) return fail(ctx, AEFFT_EHIP, "c2r rows", e);
     return AEFFT_OK;

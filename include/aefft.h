@@ -363,6 +363,33 @@ int aefft_net_forward_u8(aefft_net* net, const unsigned char* frames_d, float* r
  * Spatial net: float frames and float outputs only (sp_forward; hidden_d from the stored layer); any 8-bit argument is AEFFT_EINVAL.
  * AEFFT_EINVAL: null net or frames, both outputs null, hidden_d with hidden_pair outside 0..L-1, a pointer not 16-byte aligned. */
 int aefft_net_infer(aefft_net* net, const void* frames_d, int frames_u8, void* recon_d, int recon_u8, int hidden_pair, float* hidden_d);
+/* Per-frame reconstruction error under the CURRENT (frozen) weights -- a validation curve on held-out frames, an anomaly score:
+ *     score_d[b] = sum over d, i, j of (x_b[d][i][j] - r_b[d][i][j])^2 / (D Nx Ny)
+ * x the frame as floats (8-bit pixels converted as everywhere else), r the float32 reconstruction aefft_net_infer would write for the same
+ * frames and weights (layer 4L of autoenc_fft, fft_backproplib.cu:1331-1376).  frames_d [B][D][Nx][Ny] float, or unsigned char when
+ * frames_u8; score_d [B] float; recon_d (nullable) float [B][D][Nx][Ny].  All pointers 16-byte aligned.
+ * By Parseval this is mse_fft's sum (fft_backproplib.cu:480-498, :1178-1192) between layer 0 and layer 4L, times 2*dM -- for the whole
+ * network instead of one pair, per frame instead of a batch mean, and with no weight update behind it.
+ * The inverse transform's row pass holds every reconstructed pixel in registers just before it would store it: it loads the frame's pixels
+ * for the same elements and forms the squared difference there, so the reconstruction need not reach memory.  The difference is formed from
+ * the ROUNDED product z*scale, the value the row pass stores (the compiler is kept from contracting the product into the subtraction):
+ * score_d is exactly a function of the float reconstruction, whether or not recon_d is given, and a trained net's small residual does not
+ * depend on which variant ran.  recon_d, when given, receives the float reconstruction, bit for bit what aefft_net_infer writes, from the
+ * same launch.  There is no 8-bit reconstruction here: callers that want pixels use aefft_net_infer.
+ * Every frame's score is reduced in a fixed order, with no atomics: one float per pair of rows (the lane's terms in order, a butterfly
+ * over the wave, the pair's waves in order), then the frame's D*Nx/2 row-pair sums in double.  The same inputs give the same bits, and a
+ * frame's score does not depend on the other frames of the batch.
+ * Form, caches, state and ordering are exactly those of aefft_net_infer (DESIGN.md sections 13 and 15): the call runs in the form
+ * aefft_net_step_form reports and reuses the operators of the current weights where they are at hand (in the chain form five launches:
+ * the input transform's two, the inverse column pass with the operator on load, the scoring row pass, the finish; one more above 16 MB of
+ * output spectra); it ends a pending aefft_net_step_grad (aefft_net_step_apply then fails with AEFFT_ESTATE) and aefft_net_get_layer(s)
+ * afterwards export the layers of this call; it leaves training bit for bit undisturbed; it runs on the context stream only, with no host
+ * synchronisation and no allocation (sized by aefft_net_create*).
+ * Routes whose reconstruction does not come out of one of the two row kernels -- the spatial net (float frames only), and smooth grids up to
+ * 1024 x 1024 under AEFFT_F_CHIRPZ -- form the same row-pair sums from the STORED reconstruction in a launch of their own: they need recon_d.
+ * AEFFT_EINVAL: null net, frames or score_d; a pointer not 16-byte aligned; frames_u8 on a spatial net; recon_d == NULL on one of the routes
+ * just named (the message says why).  The outputs are then untouched. */
+int aefft_net_score(aefft_net* net, const void* frames_d, int frames_u8, float* score_d, float* recon_d /* nullable */);
 /* Decode: the reconstruction from a STORED hidden layer -- the other half of aefft_net_infer(hidden_pair = l, hidden_d).  code_d
  * [B][dM_l][Nx_l][Ny_l] float, l = hidden_pair: layer 2l+2 in coordinate space, shape and layout as aefft_net_infer writes hidden_d (stored,
  * transmitted or edited since: it need not be an encoder output).  recon_d [B][D][Nx][Ny] float, or unsigned char when recon_u8 under
