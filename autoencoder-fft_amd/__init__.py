@@ -94,6 +94,7 @@ SIGNATURES = {
     "aefft_net_infer": (_i, [_vp, _vp, _i, _vp, _i, _i, _fp]),
     "aefft_net_decode": (_i, [_vp, _i, _fp, _vp, _i]),
     "aefft_net_score": (_i, [_vp, _vp, _i, _fp, _fp]),
+    "aefft_net_score_map": (_i, [_vp, _vp, _i, _i, _fp, _fp, _fp]),
     "aefft_net_set_input_ready": (_i, [_vp, _i]),
     "aefft_net_grad_buffer": (_i, [_vp, C.POINTER(_vp), C.POINTER(C.c_size_t)]),
     "aefft_net_step_form": (_i, [_vp]),
@@ -515,6 +516,21 @@ class Net:
             score = self.ctx.empty(self.B)
         self.ctx.check(self.L.aefft_net_score(self.h, _ptr(frames), int(_is_u8(frames)), _ptr(score), _ptr(recon)))
         return score, recon
+
+    def score_map(self, frames, tile, map=None, score=None, recon=None):
+        """Per-tile reconstruction error under the current weights (aefft_net_score_map): map[b][I][J] = mean over the D channels and the
+        tile x tile pixels of tile (I, J) of (x - r)^2, r the float32 reconstruction Net.infer would write.  `tile` is 8, 16, 32 or 64 and divides
+        Nx and Ny.  uint8 `frames` are read as 8-bit pixels.  `map` (float32 [B][Nx/tile][Ny/tile]) and `score` (float32 [B], the mean of the
+        frame's map entries) are allocated when None; `recon` (float32 [B][D][Nx][Ny], optional) receives the reconstruction from the same
+        launch -- the spatial net and the chirp-z transforms need it.  Nothing waits for the device.  Returns (map, score, recon)."""
+        tile = int(tile)
+        if map is None:
+            t = max(tile, 1)                  # (a tile the library refuses still gets a buffer: the error is the library's)
+            map = self.ctx.empty(self.B, max(self.Nx // t, 1), max(self.Ny // t, 1))
+        if score is None:
+            score = self.ctx.empty(self.B)
+        self.ctx.check(self.L.aefft_net_score_map(self.h, _ptr(frames), int(_is_u8(frames)), tile, _ptr(map), _ptr(score), _ptr(recon)))
+        return map, score, recon
 
     def decode(self, code, hidden_pair, recon):
         """The reconstruction from a stored hidden layer (aefft_net_decode): `code` is float32 [B][dM][Nx_l][Ny_l] of pair `hidden_pair`, as

@@ -147,4 +147,20 @@ template <int W> __device__ __forceinline__ float score_seg_sum(float v)
     return v;
 }
 
+// SCORE 3: float frames; 4: 8-bit frames (aefft_net_score_map).  The epilogue of SCORE 1 / 2 up to the lane's (x - r)^2 terms; the butterfly
+// then stops at a STRIP -- two rows x `tile` columns of one channel, tile = 1 << lt in 8..64 -- and one float per strip goes to
+// part [npairs][n >> lt].  The tile is a run-time value (no template axis over it): the butterfly is a loop with a uniform bound.
+struct ScoreMapDev { const void* frames; float* part; int lt; };
+template <> struct ScoreParam<3> { typedef ScoreMapDev type; };
+template <> struct ScoreParam<4> { typedef ScoreMapDev type; };
+// the sum over an aligned segment of 1 << lw lanes of a wave (lw uniform, at most LMAX), in every lane of it: score_seg_sum's butterfly from the
+// nearest partner outwards, as many levels as the segment has
+template <int LMAX> __device__ __forceinline__ float score_seg_sum_rt(float v, int lw)
+{
+#pragma unroll
+    for (int l = 0; l < LMAX; ++l)
+        if (l < lw) v += __shfl_xor(v, 1 << l, 64);
+    return v;
+}
+
 }  // namespace aefft

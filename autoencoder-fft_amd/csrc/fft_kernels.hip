@@ -264,6 +264,8 @@ __global__ __launch_bounds__(RowCfg<N>::NT) void r2c_rows_kernel(const void* __r
 // LDS passes (read once: streaming loads).  It forms (x - r)^2 for both rows of its pair, r = the rounded product it would store (score_px), stores r as
 // well when out_v is non-null (a uniform branch), and the row pair's sum goes to sc.part[pair]: eight terms per position in the lane, a
 // butterfly over the pair's lanes of the wave, the pair's waves in order through LDS -- no atomics, one order.  U8 is false with SCORE.
+// SCORE (3: float frames, 4: 8-bit frames; aefft_net_score_map): the same up to the lane's eight terms; the butterfly stops at a strip of
+// sc's tile (fft_common.h ScoreMapDev) and the first lane of each strip writes sc.part[pair][strip].
 template <int N, bool SPARSE, bool U8 = false, int SCORE = 0>
 __global__ __launch_bounds__(RowCfg<N>::NT) void c2r_rows_kernel(const float2* __restrict__ mid, void* __restrict__ out_v,
                                                                    long npairs, int Wc, float scale, const typename ScoreParam<SCORE>::type sc)
@@ -278,6 +280,7 @@ __global__ __launch_bounds__(RowCfg<N>::NT) void c2r_rows_kernel(const float2* _
     tws.load(t);
     const long pair0 = (long)blockIdx.x * G;
     constexpr int NQ = G * (N / 4) / NT;                        // epilogue positions per lane (= 2 when NT = G*N/8)
+    constexpr bool SF32 = SCORE == 1 || SCORE == 3;             // the frames are floats (SCORE 2, 4: 8-bit pixels)
     [[maybe_unused]] float4 fa[NQ], fb[NQ];
     [[maybe_unused]] unsigned ua[NQ], ub[NQ];
     [[maybe_unused]] auto load_frames = [&](int lv) {
@@ -287,7 +290,7 @@ __global__ __launch_bounds__(RowCfg<N>::NT) void c2r_rows_kernel(const float2* _
                 const int idx = tid + q * NT;
                 const int gg = idx / (N / 4), n4 = idx % (N / 4);
                 const int off = (gg < lv ? gg * (2 * N / 4) : 0) + n4;         // (32-bit lane offsets; rows that do not exist re-read pair 0)
-                if constexpr (SCORE == 1) {
+                if constexpr (SF32) {
                     const float4* src = reinterpret_cast<const float4*>(static_cast<const float*>(sc.frames) + pair0 * 2 * N);
                     fa[q] = ld_stream(&src[off]);
                     fb[q] = ld_stream(&src[off + N / 4]);
@@ -391,7 +394,7 @@ __global__ __launch_bounds__(RowCfg<N>::NT) void c2r_rows_kernel(const float2* _
                 const float4 ra = make_float4(score_px(z0.x, scale), score_px(z1.x, scale), score_px(z2.x, scale), score_px(z3.x, scale));
                 const float4 rb = make_float4(score_px(z0.y, scale), score_px(z1.y, scale), score_px(z2.y, scale), score_px(z3.y, scale));
                 float4 xa, xb;
-                if constexpr (SCORE == 1) { xa = fa[q]; xb = fb[q]; }
+                if constexpr (SF32) { xa = fa[q]; xb = fb[q]; }
                 else {
                     xa = make_float4((float)(ua[q] & 255u), (float)((ua[q] >> 8) & 255u), (float)((ua[q] >> 16) & 255u), (float)(ua[q] >> 24));
                     xb = make_float4((float)(ub[q] & 255u), (float)((ub[q] >> 8) & 255u), (float)((ub[q] >> 16) & 255u), (float)(ub[q] >> 24));
@@ -405,6 +408,19 @@ __global__ __launch_bounds__(RowCfg<N>::NT) void c2r_rows_kernel(const float2* _
                     st_stream(reinterpret_cast<float4*>(orow + (gg * 2 + 1) * N + n), rb);
                 }
             }
+        }
+        if constexpr (SCORE >= 3) {
+            // a strip's tile/4 positions lie in consecutive lanes of one q, aligned (tile | N), never across waves; at N = 2048 the lane's
+            // two positions belong to different strips of the one row pair, at N = 8 the strip is the pair's two lanes
+            const int lw = sc.lt - 2, ns = N >> sc.lt;        // log2 of a strip's lanes; strips of a row pair
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) {
+                const float v = score_seg_sum_rt<4>(acc[q], lw);
+                const int idx = tid + q * NT;
+                const int gg = idx / (N / 4), n4 = idx % (N / 4);
+                if ((n4 & ((1 << lw) - 1)) == 0 && gg < live) sc.part[(pair0 + gg) * ns + (n4 >> lw)] = v;
+            }
+            return;
         }
         // a row pair's N/4 positions lie in consecutive lanes of one q (N/4 <= NT), or are the whole workgroup's, both q (N = 2048)
         constexpr int LPP = N / 4 < NT ? N / 4 : NT;        // lanes of one row pair
@@ -713,6 +729,12 @@ static hipError_t run_c2r_rows_as(const float2* mid, void* out, long npairs, int
 template <int N, bool SPARSE> static hipError_t run_c2r_rows_sp(const float2* mid, void* out, long npairs, int Wc, float scale, hipStream_t st, bool out_u8, const ScoreArg* score)
 {
     if (score) {
+        if (score->tile) {
+            const int lt = score_tile_log2(score->tile);
+            if (out_u8 || !score->frames || !score->strips || lt < 0 || N % score->tile) return hipErrorInvalidValue;
+            const ScoreMapDev sm{score->frames, score->strips, lt};
+            return score->u8 ? run_c2r_rows_as<N, SPARSE, false, 4>(mid, out, npairs, Wc, scale, st, sm) : run_c2r_rows_as<N, SPARSE, false, 3>(mid, out, npairs, Wc, scale, st, sm);
+        }
         if (out_u8 || !score->frames || !score->part) return hipErrorInvalidValue;
         const ScoreDev sc{score->frames, score->part};
         return score->u8 ? run_c2r_rows_as<N, SPARSE, false, 2>(mid, out, npairs, Wc, scale, st, sc) : run_c2r_rows_as<N, SPARSE, false, 1>(mid, out, npairs, Wc, scale, st, sc);

@@ -205,6 +205,7 @@ __global__ __launch_bounds__(MixRowCfg<T>::NT) void mix_r2c_rows_kernel(const vo
 // of ITS pair (at most four: n <= 8 T) -- the frame's two pixels of both rows requested behind the spectrum's loads, (x - r)^2 against the
 // rounded product, r stored as well when `out` is non-null -- and the pair's sum is reduced across its T threads: the lane's terms in order, a
 // butterfly over the pair's lanes of the wave, the pair's waves in order through LDS.  One float per row pair to sc.part.
+// SCORE (3: float frames, 4: 8-bit frames; aefft_net_score_map): one float per STRIP of sc's tile (fft_common.h ScoreMapDev) instead.
 template <int T, bool U8 = false, int SCORE = 0>
 __global__ __launch_bounds__(MixRowCfg<T>::NT) void mix_c2r_rows_kernel(const float2* __restrict__ mid, void* __restrict__ out, long npairs,
                                                                          int Wc, float scale, const MixPlan pl, const typename ScoreParam<SCORE>::type sc)
@@ -234,6 +235,7 @@ __global__ __launch_bounds__(MixRowCfg<T>::NT) void mix_c2r_rows_kernel(const fl
         }
     }
     constexpr int NJ = 4;                                           // element pairs of a row per thread: H <= 4 T
+    constexpr bool SF32 = SCORE == 1 || SCORE == 3;                 // the frames are floats (SCORE 2, 4: 8-bit pixels)
     [[maybe_unused]] float2 fa[NJ], fb[NJ];
     [[maybe_unused]] unsigned ua[NJ], ub[NJ];
     if constexpr (SCORE != 0) {
@@ -241,7 +243,7 @@ __global__ __launch_bounds__(MixRowCfg<T>::NT) void mix_c2r_rows_kernel(const fl
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
             const int c = t + j * T < H ? t + j * T : 0;
-            if constexpr (SCORE == 1) {
+            if constexpr (SF32) {
                 const float2* src = static_cast<const float2*>(sc.frames);
                 fa[j] = ld_stream(&src[r0 + c]);                    // (frames are read once)
                 fb[j] = ld_stream(&src[r0 + H + c]);
@@ -255,6 +257,37 @@ __global__ __launch_bounds__(MixRowCfg<T>::NT) void mix_c2r_rows_kernel(const fl
     __syncthreads();
     mix_fft<T, +1>(s + g * PL, t, pl);
 
+    if constexpr (SCORE >= 3) {
+        // the map: element pair e = t + j T is two columns of both rows; a strip is tile/2 consecutive element pairs, i.e. for a FIXED j an aligned
+        // segment of tile/2 lanes (T is a power of two, and T >= tile/2 for every smooth n a tile divides; the launcher checks) -- a butterfly
+        // per j, never a sum over j.  Lanes with e >= H add 0; they lie in whole segments (tile | n) and write nothing.
+        float2* const o = static_cast<float2*>(out);
+        const bool store = out != nullptr;
+        const float2* z = s + g * PL;
+        const int lw = sc.lt - 1, ns = N >> sc.lt;                  // log2 of a strip's lanes; strips of a row pair
+        float* const prow = sc.part + (pair0 + g) * ns;
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            const int c = t + j * T;
+            float a = 0.f;
+            if (g < live && c < H) {
+                const float2 z0 = z[pad_idx(2 * c)], z1 = z[pad_idx(2 * c + 1)];
+                const float2 ra = make_float2(score_px(z0.x, scale), score_px(z1.x, scale)), rb = make_float2(score_px(z0.y, scale), score_px(z1.y, scale));
+                float2 xa, xb;
+                if constexpr (SF32) { xa = fa[j]; xb = fb[j]; }
+                else { xa = make_float2((float)(ua[j] & 255u), (float)(ua[j] >> 8)); xb = make_float2((float)(ub[j] & 255u), (float)(ub[j] >> 8)); }
+                a += score_sq(xa.x, ra.x); a += score_sq(xa.y, ra.y); a += score_sq(xb.x, rb.x); a += score_sq(xb.y, rb.y);
+                if (store) {
+                    const long ra_i = (pair0 + g) * 2 * H + c;
+                    st_stream(&o[ra_i], ra);
+                    st_stream(&o[ra_i + H], rb);
+                }
+            }
+            const float v = score_seg_sum_rt<5>(a, lw);
+            if ((t & ((1 << lw) - 1)) == 0 && g < live && c < H) prow[c >> lw] = v;
+        }
+        return;
+    }
     if constexpr (SCORE != 0) {
         float2* const o = static_cast<float2*>(out);
         const bool store = out != nullptr;
@@ -267,7 +300,7 @@ __global__ __launch_bounds__(MixRowCfg<T>::NT) void mix_c2r_rows_kernel(const fl
                 const float2 z0 = z[pad_idx(2 * c)], z1 = z[pad_idx(2 * c + 1)];
                 const float2 ra = make_float2(score_px(z0.x, scale), score_px(z1.x, scale)), rb = make_float2(score_px(z0.y, scale), score_px(z1.y, scale));
                 float2 xa, xb;
-                if constexpr (SCORE == 1) { xa = fa[j]; xb = fb[j]; }
+                if constexpr (SF32) { xa = fa[j]; xb = fb[j]; }
                 else { xa = make_float2((float)(ua[j] & 255u), (float)(ua[j] >> 8)); xb = make_float2((float)(ub[j] & 255u), (float)(ub[j] >> 8)); }
                 acc += score_sq(xa.x, ra.x); acc += score_sq(xa.y, ra.y); acc += score_sq(xb.x, rb.x); acc += score_sq(xb.y, rb.y);
                 if (store) {
@@ -519,6 +552,16 @@ template <int T> static hipError_t run_mix_c2r_rows(const float2* mid, void* out
     const long blocks = (npairs + Cfg::G - 1) / Cfg::G;
     if (blocks >= (1L << 31)) return hipErrorInvalidValue;
     if (score) {
+        if (score->tile) {
+            const int lt = score_tile_log2(score->tile);
+            // (T >= tile/2: a strip's element pairs are lanes of ONE row pair.  Every smooth n a tile divides has it; n = 64, 128 with tile 64 would
+            // not, and reaches the power-of-two pass instead: a net's pooled grids are >= 8, so its packed width is a power of two >= 4)
+            if (u8 || !score->frames || !score->strips || lt < 0 || pl.n % score->tile || score->tile / 2 > T) return hipErrorInvalidValue;
+            const ScoreMapDev sm{score->frames, score->strips, lt};
+            if (score->u8) mix_c2r_rows_kernel<T, false, 4><<<dim3((unsigned)blocks), dim3(Cfg::NT), lds, st>>>(mid, out, npairs, Wc, scale, pl, sm);
+            else mix_c2r_rows_kernel<T, false, 3><<<dim3((unsigned)blocks), dim3(Cfg::NT), lds, st>>>(mid, out, npairs, Wc, scale, pl, sm);
+            return hipGetLastError();
+        }
         if (u8 || !score->frames || !score->part) return hipErrorInvalidValue;
         const ScoreDev sc{score->frames, score->part};
         if (score->u8) mix_c2r_rows_kernel<T, false, 2><<<dim3((unsigned)blocks), dim3(Cfg::NT), lds, st>>>(mid, out, npairs, Wc, scale, pl, sc);

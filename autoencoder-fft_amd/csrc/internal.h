@@ -37,7 +37,10 @@ struct OpIn { const float2* A; const float2* Xf; int D0, Nx0, Ny0; };
 // score (nullable; aefft_net_score): the row pass compares the rows it holds with the frames instead of only storing them -- frames [planes][Nx][Ny]
 // float, or unsigned char when u8; part [planes*Nx/2] receives one float per ROW PAIR, the sum of (x - r)^2 over the pair's 2 Ny pixels with r the
 // rounded product the float row pass stores.  `out` (float, not out_u8) is then optional: non-null, it receives r as without `score`.
-struct ScoreArg { const void* frames; bool u8; float* part; };
+// tile (0: none; 8, 16, 32 or 64, dividing Nx and Ny; aefft_net_score_map): the row pass stops its reduction at a STRIP -- two rows x tile
+// columns of one channel -- and strips [planes*Nx/2][Ny/tile] receives one float per strip; `part` is then not written.
+struct ScoreArg { const void* frames; bool u8; float* part; int tile = 0; float* strips = nullptr; };
+inline int score_tile_log2(int tile) { return tile == 8 ? 3 : tile == 16 ? 4 : tile == 32 ? 5 : tile == 64 ? 6 : -1; }
 hipError_t launch_c2r(const float2* in, void* out, float2* mid, long planes, int Nxi, int Nyi,
                       int Nx, int Ny, float scale, hipStream_t st, const OpIn* opin = nullptr, bool out_u8 = false, const ScoreArg* score = nullptr);
 // The same partials from a STORED float reconstruction (routes whose reconstruction does not come out of one of the two row kernels): a frame's
@@ -45,6 +48,11 @@ hipError_t launch_c2r(const float2* in, void* out, float2* mid, long planes, int
 hipError_t launch_score_diff(const void* frames, bool u8, const float* recon, float* part, int B, long rows, int n, hipStream_t st);
 // score[b] = scale * (part[b][0] + part[b][1] + ...), npf partials per frame, summed in double in a fixed order
 hipError_t launch_score_finish(const float* part, float* score, int B, long npf, double scale, hipStream_t st);
+// ---- score_map_kernels.hip (aefft_net_score_map) ----
+// The strips of launch_c2r's ScoreArg from a STORED float reconstruction: npairs row pairs of 2 x n floats, strips [npairs][n/tile]
+hipError_t launch_score_map_diff(const void* frames, bool u8, const float* recon, float* strips, long npairs, int n, int tile, hipStream_t st);
+// map[b][I][J] = sum over d < D and the tile/2 row pairs of tile row I of strips[((b D + d) Nx/2 + I tile/2 + p)][J], in double, / (D tile tile)
+hipError_t launch_score_map_finish(const float* strips, float* map, int B, int D, int Nx, int Ny, int tile, hipStream_t st);
 size_t fft_mid_elems(long planes, int Nx, int Wc);   // complex elements needed in `mid`
 // sizes that are not powers of two (cufftPlanMany takes any size, fft.cu:773-779): even n in 8..1024 through Bluestein's chirp-z form on the
 // power-of-two LDS passes; rows -> transpose -> rows -> transpose.  w1, w2: workspaces of fft_any_ws_elems complex each.

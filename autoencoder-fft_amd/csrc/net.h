@@ -71,6 +71,7 @@ struct aefft_net {
     bool dec_valid = false;    // ... and of the CURRENT weights (weights_changed)
     // per-frame reconstruction error (aefft_net_score)
     float* score_part = nullptr; // [B][(D*Nx + 1)/2] one partial sum of squared differences per ROW PAIR of a frame (the row passes' scoring epilogue, score_diff_kernel)
+    float* map_part = nullptr;   // [B*D*Nx/2][Ny/tile] one float per STRIP (two rows x tile columns of a channel; aefft_net_score_map), sized for tile 8
     float2* Wp = nullptr;      // [Pc][packE] bin-major copy of the kernel spectra the coarsest-grid chain items read (kspec_packed_kernel)
     aefft::PackArgs pack{};    // its description (static per net)
     bool packed_valid = false; // Wp belongs to the CURRENT weights (weights_changed)
@@ -191,6 +192,7 @@ void fill_chain(aefft_net* n, ChainArgs& ca, int set, double* bytes);
 // score (nullable, aefft_net_score): handed to the inverse transform's row pass (do_c2r); recon_d may then be null where c2r_scores_in_rows
 int launch_recon(aefft_net* n, void* recon_d, int wsid, bool out_u8 = false, const ScoreArg* score = nullptr);
 inline long score_pairs_per_frame(const aefft_net* n) { return ((long)n->D * n->Nx + 1) / 2; }
+inline size_t score_map_strips(const aefft_net* n) { return ((size_t)n->B * n->D * n->Nx * n->Ny + 15) / 16; }     // the most strips: tile 8
 int net_forward(aefft_net* n, const float* frames_d, bool u8, float* recon_d, bool lazy, bool op = false, bool infer = false);
 #pragma GCC visibility pop
 

@@ -157,6 +157,7 @@ static int net_create(aefft_ctx* ctx, const aefft_net_desc* d, unsigned opts, ae
             (rc = net_alloc_t(n, &n->real, n->pruned ? 64 : maxReal)) == AEFFT_OK &&
             (rc = net_alloc_t(n, &n->mse_slots, n->L * MSE_PAIR_FLOATS)) == AEFFT_OK &&
             (rc = net_alloc_t(n, &n->score_part, (size_t)n->B * score_pairs_per_frame(n))) == AEFFT_OK &&
+            (rc = net_alloc_t(n, &n->map_part, score_map_strips(n))) == AEFFT_OK &&
             (rc = net_alloc_t(n, &n->grad, goff + 2 * (size_t)n->L)) == AEFFT_OK && (rc = net_alloc_t(n, &n->scratch, soff)) == AEFFT_OK) {
             n->scratch_n = soff; n->mse_pre = n->scratch; n->mse_post = n->scratch + n->L;
             for (int l = 0; l < n->L; ++l) n->pr[l].es = n->scratch + esoff[l];

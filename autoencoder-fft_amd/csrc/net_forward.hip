@@ -1,6 +1,6 @@
 // C-ABI layer (include/aefft.h), the resident network's forward: net_forward and its stages, the operator chain and the bin-major record it
 // reads (ensure_packed, fill_chain), the reconstruction (launch_recon), the per-frame expansion of an operator-form step (ensure_frames), and
-// the entry points that only run forward: aefft_net_forward*, aefft_net_infer, aefft_net_score, aefft_net_decode.  Bursts and the training step: net_step.hip.
+// the entry points that only run forward: aefft_net_forward*, aefft_net_infer, aefft_net_score, aefft_net_score_map, aefft_net_decode.  Bursts and the training step: net_step.hip.
 #include "net.h"
 
 #include <algorithm>
@@ -526,6 +526,52 @@ extern "C" int aefft_net_score(aefft_net* n, const void* frames_d, int frames_u8
     const ScoreArg sc{frames_d, frames_u8 != 0, n->score_part};
     RET_IF(launch_recon(n, recon_d, WS_MID, false, &sc));
     RET_IF(score_finish(n, score_d));
+    return mark_step_point(n);
+}
+
+// ------------------------------------------------------------------------------------------
+// per-tile reconstruction error (include/aefft.h aefft_net_score_map)
+// ------------------------------------------------------------------------------------------
+// the strips added up per map entry (score_map_finish_kernel), then, when asked for, a frame's map entries averaged (score_finish_kernel with
+// the map as the partials)
+static int score_map_finish(aefft_net* n, int tile, float* map_d, float* score_d)
+{
+    aefft_ctx* ctx = n->ctx;
+    const long epf = (long)(n->Nx / tile) * (n->Ny / tile);        // map entries per frame
+    RET_IF(launch_or_fail(ctx, KID_SCORE_MAP, ((double)n->B * n->D * n->Nx / 2 * (n->Ny / tile) + (double)n->B * epf) * 4.0, "score_map_finish",
+                          [&] { return launch_score_map_finish(n->map_part, map_d, n->B, n->D, n->Nx, n->Ny, tile, ctx->cur); }));
+    if (!score_d) return AEFFT_OK;
+    return launch_or_fail(ctx, KID_SCORE, (double)n->B * (epf + 1) * 4.0, "score_finish",
+                          [&] { return launch_score_finish(map_d, score_d, n->B, epf, 1.0 / (double)epf, ctx->cur); });
+}
+
+// aefft_net_score's body with the tile in the score argument: the row pass leaves strips, the finish makes the map of them
+extern "C" int aefft_net_score_map(aefft_net* n, const void* frames_d, int frames_u8, int tile, float* map_d, float* score_d, float* recon_d)
+{
+    if (!n) return AEFFT_EINVAL;
+    aefft_ctx* ctx = n->ctx;
+    if (!frames_d || !map_d) return fail(ctx, AEFFT_EINVAL, "aefft_net_score_map: null frames or map");
+    if (!aligned16p(frames_d) || !aligned16p(map_d) || !aligned16p(score_d) || !aligned16p(recon_d))
+        return fail(ctx, AEFFT_EINVAL, "aefft_net_score_map: pointers must be 16-byte aligned");
+    if (score_tile_log2(tile) < 0 || n->Nx % tile || n->Ny % tile)
+        return fail(ctx, AEFFT_EINVAL, "aefft_net_score_map: tile must be 8, 16, 32 or 64 and divide both Nx and Ny");
+    if (n->spatial) {
+        if (frames_u8) return sp_refuse(n, "aefft_net_score_map with 8-bit frames");
+        if (!recon_d) return fail(ctx, AEFFT_EINVAL, "aefft_net_score_map: a spatial net's reconstruction is written by its last convolution, not by an inverse transform's row pass -- the map is formed from the stored reconstruction, so recon_d must be given");
+        RET_IF(sp_forward(n, static_cast<const float*>(frames_d), recon_d));
+        RET_IF(launch_or_fail(ctx, KID_SCORE_MAP, (double)n->B * n->D * n->Nx * n->Ny * 8.0, "score_map_diff", [&] {
+            return launch_score_map_diff(frames_d, false, recon_d, n->map_part, (long)n->B * n->D * n->Nx / 2, n->Ny, tile, ctx->cur);
+        }));
+        RET_IF(score_map_finish(n, tile, map_d, score_d));
+        return mark_step_point(n);
+    }
+    if (!recon_d && !c2r_scores_in_rows(n->Nx, n->Ny))
+        return fail(ctx, AEFFT_EINVAL, "aefft_net_score_map: under AEFFT_F_CHIRPZ this grid's reconstruction comes out of the chirp-z transforms, not of an inverse row pass -- the map is formed from the stored reconstruction, so recon_d must be given");
+    const bool op = op_eligible(n);
+    RET_IF(net_forward(n, static_cast<const float*>(frames_d), frames_u8 != 0, nullptr, true, op, true));
+    const ScoreArg sc{frames_d, frames_u8 != 0, nullptr, tile, n->map_part};
+    RET_IF(launch_recon(n, recon_d, WS_MID, false, &sc));
+    RET_IF(score_map_finish(n, tile, map_d, score_d));
     return mark_step_point(n);
 }
 

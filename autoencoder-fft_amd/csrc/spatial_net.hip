@@ -76,7 +76,7 @@ int aefft::sp_create(aefft_ctx* ctx, const aefft_net_desc* d, aefft_net** out)
     }
     if (rc == AEFFT_OK && (rc = net_alloc_t(n, &n->grad, goff + 2 * (size_t)n->L)) == AEFFT_OK && (rc = net_alloc_t(n, &n->sp_ws, maxWs)) == AEFFT_OK &&
         (rc = net_alloc_t(n, &n->sp_rq, maxRq)) == AEFFT_OK && (rc = net_alloc_t(n, &n->sp_sqd, (size_t)SQD_MAX * SQD_BLOCKS)) == AEFFT_OK &&
-        (rc = net_alloc_t(n, &n->score_part, B * score_pairs_per_frame(n))) == AEFFT_OK &&
+        (rc = net_alloc_t(n, &n->score_part, B * score_pairs_per_frame(n))) == AEFFT_OK && (rc = net_alloc_t(n, &n->map_part, score_map_strips(n))) == AEFFT_OK &&
         (maxPart == 0 || (rc = net_alloc_t(n, &n->sp_part, maxPart)) == AEFFT_OK) && (maxUp == 0 || (rc = net_alloc_t(n, &n->sp_up, maxUp)) == AEFFT_OK))
         n->grad_n = goff;
     if (rc != AEFFT_OK) { aefft_net_destroy(n); return rc; }

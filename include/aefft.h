@@ -390,6 +390,32 @@ int aefft_net_infer(aefft_net* net, const void* frames_d, int frames_u8, void* r
  * AEFFT_EINVAL: null net, frames or score_d; a pointer not 16-byte aligned; frames_u8 on a spatial net; recon_d == NULL on one of the routes
  * just named (the message says why).  The outputs are then untouched. */
 int aefft_net_score(aefft_net* net, const void* frames_d, int frames_u8, float* score_d, float* recon_d /* nullable */);
+/* Per-tile reconstruction error under the CURRENT (frozen) weights -- WHERE in the frame the error is: one heat map over the image plane
+ * per frame, channels summed.  With t = tile and map_d float [B][Nx/t][Ny/t]:
+ *     map_d[b][I][J] = sum over d < D, i in [I t, I t + t), j in [J t, J t + t) of (x_b[d][i][j] - r_b[d][i][j])^2 / (D t t)
+ * x and r are exactly those of aefft_net_score: 8-bit pixels converted exactly, r the ROUNDED product z*scale the float row pass stores, so
+ * the map is a function of the float reconstruction whether or not recon_d is given.  tile is one of 8, 16, 32, 64 and must divide both Nx
+ * and Ny (640 x 480 takes 8, 16, 32; 1280 x 720 takes 8, 16; a power-of-two grid every tile up to its shorter side).
+ * score_d (nullable) [B] float: the mean of the frame's Nx/t * Ny/t map entries, taken from the float entries as stored, added in double
+ * and rounded once -- a function of the map.  It agrees with aefft_net_score to rounding, NOT bit for bit: the two add the same terms in
+ * different orders and round at different places.
+ * recon_d (nullable) float [B][D][Nx][Ny] receives the float reconstruction, bit for bit what aefft_net_infer writes, from the same launch.
+ * All pointers 16-byte aligned.
+ * The inverse row pass's scoring epilogue with its reduction stopped early: one float per STRIP (two rows x t columns of one channel; the
+ * lane's terms in order, then a butterfly over the strip's lanes of the wave), then score_map_finish_kernel adds an entry's D * t/2 strips
+ * in double, channel outer, row pair inner, and rounds once.  There are no atomics: the same inputs give the same bits, and a frame's map
+ * does not depend on the other frames of the batch.
+ * Form, operator caches, state and ordering are exactly those of aefft_net_score: the form aefft_net_step_form reports; in the chain form
+ * with the operators at hand five launches (the input transform's two, the inverse column pass with the operator on load, the mapping row
+ * pass, the map finish), six with score_d; a pending aefft_net_step_grad is ended (aefft_net_step_apply then fails with AEFFT_ESTATE);
+ * aefft_net_get_layer(s) afterwards export the layers of this call; training is left bit for bit undisturbed; the context stream only, no
+ * host synchronisation and no allocation (the strip buffer, B*D*Nx*Ny/16 floats, is sized by aefft_net_create*).
+ * The spatial net (float frames only) and smooth grids under AEFFT_F_CHIRPZ form the same strips from the STORED reconstruction in a
+ * launch of their own: they need recon_d.
+ * AEFFT_EINVAL: null net, frames or map_d; a pointer not 16-byte aligned; a tile that is not 8, 16, 32 or 64 or does not divide Nx and Ny;
+ * frames_u8 on a spatial net; recon_d == NULL on one of the routes just named (the message says why).  The outputs are then untouched. */
+int aefft_net_score_map(aefft_net* net, const void* frames_d, int frames_u8, int tile, float* map_d, float* score_d /* nullable */,
+                        float* recon_d /* nullable */);
 /* Decode: the reconstruction from a STORED hidden layer -- the other half of aefft_net_infer(hidden_pair = l, hidden_d).  code_d
  * [B][dM_l][Nx_l][Ny_l] float, l = hidden_pair: layer 2l+2 in coordinate space, shape and layout as aefft_net_infer writes hidden_d (stored,
  * transmitted or edited since: it need not be an encoder output).  recon_d [B][D][Nx][Ny] float, or unsigned char when recon_u8 under

@@ -8,10 +8,18 @@ Three nets -- cfg3-P2's (D=3, maps 8/16/32/64, 5x5, s=2) at 512^2 with B = 32, t
   score_recon      aefft_net_score with recon_d
   score_u8         aefft_net_score, 8-bit frames, without recon_d
   score_u8_recon   aefft_net_score, 8-bit frames, with recon_d
+--group map measures the per-tile map instead, with --tile (default 16, which divides every net's grid):
+  score_pool       (a) aefft_net_score(.., recon_d) followed by torch's avg_pool2d of ((x - r)**2).sum(1) / D: what a caller does without
+                       aefft_net_score_map
+  map              (b) aefft_net_score_map without score_d and without recon_d (the C entry: Net.score_map always hands a score buffer over)
+  map_score        (b') ... with score_d (one launch more)
+  map_recon        (c) ... without score_d, with recon_d
+  map_u8           (d) ... 8-bit frames, without score_d and recon_d
+  score            (e) aefft_net_score without recon_d: the base
 The variants are alternated in the process: --rounds rounds of --calls calls each between events on the library's stream (torch's current
 stream: the torch expression is ordered on it), after --warmup calls of each.
 
-    python tools/score_bench.py [--calls 40] [--warmup 15] [--rounds 3] [--only NAME] [--variant NAME]
+    python tools/score_bench.py [--calls 40] [--warmup 15] [--rounds 3] [--only NAME] [--variant NAME] [--group score|map] [--tile T]
 """
 import argparse
 import importlib
@@ -28,7 +36,7 @@ from tools.infer_bench import NETS  # noqa: E402
 from tools.sizes_bench import timed  # noqa: E402
 
 
-def bench_net(ctx, name, calls, warmup, rounds, variants):
+def bench_net(ctx, name, calls, warmup, rounds, variants, group="score", tile=16):
     D, Nx, Ny, maps, Nk, s, B, smooth = NETS[name]
     t = ctx.torch
     rng = np.random.default_rng(len(name))
@@ -48,6 +56,20 @@ def bench_net(ctx, name, calls, warmup, rounds, variants):
     fns = {"infer": lambda: net.infer(f32, o32), "infer_torch": infer_torch,
            "score": lambda: net.score(f32, sc), "score_recon": lambda: net.score(f32, sc, o32),
            "score_u8": lambda: net.score(u8, sc), "score_u8_recon": lambda: net.score(u8, sc, o32)}
+    if group == "map":
+        mp = ctx.empty(B, Nx // tile, Ny // tile)
+
+        def score_pool():
+            net.score(f32, sc, o32)
+            return t.nn.functional.avg_pool2d(((f32 - o32) ** 2).sum(1, keepdim=True), tile) / D
+
+        P = aefft._ptr
+
+        def c_map(frames, is_u8, recon):
+            return lambda: ctx.check(net.L.aefft_net_score_map(net.h, P(frames), is_u8, tile, P(mp), None, P(recon)))
+
+        fns = {"score_pool": score_pool, "map": c_map(f32, 0, None), "map_score": lambda: net.score_map(f32, tile, mp, sc), "map_recon": c_map(f32, 0, o32),
+               "map_u8": c_map(u8, 1, None), "score": lambda: net.score(f32, sc)}
     fns = {k: v for k, v in fns.items() if not variants or k in variants}
     res = {k: [] for k in fns}
     for fn in fns.values():
@@ -69,13 +91,17 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--only", default="")
     ap.add_argument("--variant", default="")
+    ap.add_argument("--group", default="score", choices=["score", "map"])
+    ap.add_argument("--tile", type=int, default=16)
     a = ap.parse_args()
     ctx = aefft.Context(0)
-    out = {"lib": aefft.LIB_PATH, "calls": a.calls, "warmup": a.warmup}
+    out = {"lib": aefft.LIB_PATH, "calls": a.calls, "warmup": a.warmup, "group": a.group}
+    if a.group == "map":
+        out["tile"] = a.tile
     for name in NETS:
         if a.only and name != a.only:
             continue
-        out[name] = bench_net(ctx, name, a.calls, a.warmup, a.rounds, [a.variant] if a.variant else [])
+        out[name] = bench_net(ctx, name, a.calls, a.warmup, a.rounds, [a.variant] if a.variant else [], a.group, a.tile)
     ctx.close()
     print(json.dumps(out))
 
