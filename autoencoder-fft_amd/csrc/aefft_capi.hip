@@ -138,7 +138,7 @@ static int device_cus(int device)
     return n;
 }
 
-// side streams (0: reconstruction inverse FFT, 1: input prefetch) and their events; all-or-nothing
+// side streams (0: reconstruction inverse FFT, 1: input prefetch) and their events (device scope: host.h AEFFT_X_QUEUE_EVENT_FLAGS); all-or-nothing
 int aefft::ensure_aux(aefft_ctx* ctx)
 {
     if (ctx->aux[0]) return AEFFT_OK;
@@ -149,9 +149,9 @@ int aefft::ensure_aux(aefft_ctx* ctx)
         if (ctx->side_cus > 0) e = masked_stream(&ctx->aux[i], device_cus(ctx->device), 0, ctx->side_cus);
         else
         e = hipStreamCreateWithPriority(&ctx->aux[i], hipStreamNonBlocking, pr_least);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->ev_join[i], hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->ev_join[i], AEFFT_X_QUEUE_EVENT_FLAGS);
     }
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->ev_fork, AEFFT_X_QUEUE_EVENT_FLAGS);
     if (e == hipSuccess) return AEFFT_OK;
     for (int i = 0; i < aefft_ctx::NAUX; ++i) {
         if (ctx->aux[i]) (void)hipStreamDestroy(ctx->aux[i]);

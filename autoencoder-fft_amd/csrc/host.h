@@ -18,6 +18,18 @@ enum {
 
 struct ProfEvent { hipEvent_t a, b; int kid; double bytes; };
 
+// Flags of the events that order the library's OWN queues against each other: the fork and the join of the reconstruction's side stream
+// (ev_fork, ev_join[]) and the three of the pipelined mode (ev_r2c, ev_mid, ev_end[]).  Device scope is enough for them: whoever waits for one
+// is a kernel of this library on the same device in another queue (hipStreamWaitEvent), and the kernel packets' own agent-scope release and
+// acquire order such kernels; no host thread waits for these events (aefft_sync synchronises the context stream itself) and no other device
+// sees them.  Without the flag the record behind fwd_cols -- its dispatch's own completion signal -- is a system-scope release: a cache
+// write-back and invalidation right behind the 25 MB of Xf that msgrad reads next.
+// NEVER with this flag: the profiling pool's events (the host reads their times), the events of dp_rccl.cpp (another device's queue, or the
+// host, waits for them), and any event a caller of include/aefft.h is given.
+#ifndef AEFFT_X_QUEUE_EVENT_FLAGS
+#define AEFFT_X_QUEUE_EVENT_FLAGS (hipEventDisableTiming | hipEventDisableSystemFence)
+#endif
+
 struct aefft_ctx {
     int device = 0;
     hipStream_t stream = nullptr;    // the caller-visible stream: every public call is ordered on it

@@ -699,9 +699,10 @@ extern "C" int aefft_net_set_input_ready(aefft_net* n, int enable)
     if (enable && !n->X0alt) {
         const Pair& q = n->pr[0];
         RET_IF(net_alloc_t(n, &n->X0alt, (size_t)n->B * q.dD * q.P));
-        for (int i = 0; i < 2; ++i) HIPCHK(ctx, hipEventCreateWithFlags(&n->ev_end[i], hipEventDisableTiming));
-        HIPCHK(ctx, hipEventCreateWithFlags(&n->ev_r2c, hipEventDisableTiming));
-        HIPCHK(ctx, hipEventCreateWithFlags(&n->ev_mid, hipEventDisableTiming));
+        // (queue-to-queue events of this library only: device scope, host.h AEFFT_X_QUEUE_EVENT_FLAGS)
+        for (int i = 0; i < 2; ++i) HIPCHK(ctx, hipEventCreateWithFlags(&n->ev_end[i], AEFFT_X_QUEUE_EVENT_FLAGS));
+        HIPCHK(ctx, hipEventCreateWithFlags(&n->ev_r2c, AEFFT_X_QUEUE_EVENT_FLAGS));
+        HIPCHK(ctx, hipEventCreateWithFlags(&n->ev_mid, AEFFT_X_QUEUE_EVENT_FLAGS));
     }
     n->input_ready = enable != 0;
     return AEFFT_OK;
