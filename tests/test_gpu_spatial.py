@@ -190,15 +190,11 @@ def test_backprop_gpu_many_bands(ctx, dD, dM, N, Nk, B, tied):
         assert np.abs(host(g) - r).max() < 2e-5 * max(np.abs(r).max(), 1e-30), k
 
 
-@pytest.mark.parametrize("dD,dM,N,Nk", [(2, 2, 8, 3), (2, 3, 12, 5), (1, 2, 10, 3)])
-def test_b11_compat_switch_reproduces_the_cuda_source(ctx, dD, dM, N, Nk):
-    """SURVEY Appendix B-11: semantics="cuda_compat" gives the decoder-kernel / encoder-bias gradients of the CUDA source as
-    written (hidden layer read at (i-ik)*Nx + (j-ik), stale per-pixel buffer, `dDdB2 =`), i.e. the literal restatement
-    oracle/np_spatial_literal.py with compat=True; the other two gradients are untouched."""
+def _b11_compat(ctx, dD, dM, Nx, Ny, Nk):
     import np_spatial_literal as SL
-    rng = np.random.default_rng(dD + dM + N + Nk)
-    x = rng.uniform(0, 16, (1, dD, N, N)).astype(np.float32); out = (x + rng.uniform(-2, 2, x.shape)).astype(np.float32)
-    hin = rng.uniform(-4, 4, (1, dM, N, N)).astype(np.float32); f = rng.uniform(-1, 1, (dD, dM, Nk, Nk)).astype(np.float32)
+    rng = np.random.default_rng(dD + dM + Nx + Nk)
+    x = rng.uniform(0, 16, (1, dD, Nx, Ny)).astype(np.float32); out = (x + rng.uniform(-2, 2, x.shape)).astype(np.float32)
+    hin = rng.uniform(-4, 4, (1, dM, Nx, Ny)).astype(np.float32); f = rng.uniform(-1, 1, (dD, dM, Nk, Nk)).astype(np.float32)
     z = np.zeros((dM, dD, Nk, Nk), np.float32)
     res = {}
     for sem in ("gpu", "cuda_compat"):
@@ -212,6 +208,20 @@ def test_b11_compat_switch_reproduces_the_cuda_source(ctx, dD, dM, N, Nk):
         for got, ref, k in zip(res[sem], (gc, gb, gf, gp), ("gc", "gb", "gf", "gp")):
             assert np.abs(got - ref).max() < 2e-5 * max(np.abs(ref).max(), 1e-30), (sem, k)
     assert not np.allclose(res["gpu"][2], res["cuda_compat"][2])
+
+
+@pytest.mark.parametrize("dD,dM,N,Nk", [(2, 2, 8, 3), (2, 3, 12, 5), (1, 2, 10, 3)])
+def test_b11_compat_switch_reproduces_the_cuda_source(ctx, dD, dM, N, Nk):
+    """SURVEY Appendix B-11: semantics="cuda_compat" gives the decoder-kernel / encoder-bias gradients of the CUDA source as
+    written (hidden layer read at (i-ik)*Nx + (j-ik), stale per-pixel buffer, `dDdB2 =`), i.e. the literal restatement
+    oracle/np_spatial_literal.py with compat=True; the other two gradients are untouched."""
+    _b11_compat(ctx, dD, dM, N, N, Nk)
+
+
+@pytest.mark.parametrize("dD,dM,Nx,Ny,Nk", [(2, 3, 8, 12, 5)])
+def test_b11_compat_switch_on_a_non_square_grid(ctx, dD, dM, Nx, Ny, Nk):
+    """the same with Nx != Ny, where the source's row stride Nx (instead of Ny) reads another row of the hidden layer"""
+    _b11_compat(ctx, dD, dM, Nx, Ny, Nk)
 
 
 @pytest.mark.parametrize("dD,dM,N,B,tied,sem", [(3, 8, 24, 2, False, "gpu"), (1, 9, 40, 1, False, "gpu"), (3, 50, 16, 3, True, "gpu"),

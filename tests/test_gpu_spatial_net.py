@@ -105,13 +105,9 @@ def _grad_segments(buf, dims):
     return [dict(zip(("dck", "dfk", "db", "dp"), t)) for t in dp.unpack_grads(buf, dims)], buf[n:n + len(dims)]
 
 
-@pytest.mark.parametrize("sym", [0, 1])
-def test_steps_against_backprop_gpu(ctx, sym):
-    """three step_grad / step_apply rounds against backprop_gpu[_cc] per pair on the GPU's own layers: the packed gradients, the MSE
-    tail, the weights (momentum carried across steps); set_inertia reaches the update"""
-    D, Nx, Ny, maps, Nk, s, B = 3, 64, 48, [8, 12], 3, 2, 2
+def _steps_against_backprop_gpu(ctx, sym, D, Nx, Ny, maps, Nk, Nl, s, B, steps):
     L, del0 = len(maps), 0.2
-    net = make_net(ctx, D, Nx, Ny, maps, Nk, Nk, s, B, seed=3)
+    net = make_net(ctx, D, Nx, Ny, maps, Nk, Nl, s, B, seed=3)
     if sym:
         for l in range(L):
             c, b, f, p = net.get_pair(l)
@@ -120,9 +116,9 @@ def test_steps_against_backprop_gpu(ctx, sym):
     if sym:
         net.set_inertia(alpha)
     x = ctx.dev(frames(np.random.default_rng(5), B, D, Nx, Ny))
-    mom = [[np.zeros((g["dM"], g["dD"], Nk, Nk)), np.zeros(g["dM"]), np.zeros((g["dD"], g["dM"], Nk, Nk)), np.zeros(g["dD"])] for g in net.dims]
+    mom = [[np.zeros((g["dM"], g["dD"], Nk, Nl)), np.zeros(g["dM"]), np.zeros((g["dD"], g["dM"], Nk, Nl)), np.zeros(g["dD"])] for g in net.dims]
     mse = ctx.empty(L)
-    for step in range(3):
+    for step in range(steps):
         w = [net.get_pair(l) for l in range(L)]
         net.step_grad(x)
         lay = [host(t) for t in net.get_layers()]
@@ -135,7 +131,7 @@ def test_steps_against_backprop_gpu(ctx, sym):
             gc, gf, gb, gp = (sum(t) / B for t in zip(*gs))
             for name, ref in (("dck", gc), ("dfk", gf), ("db", gb), ("dp", gp)):
                 assert np.abs(segs[l][name] - ref).max() <= 5e-5 * np.abs(ref).max(), (step, l, name)
-            norm = g["dD"] * g["dM"] * Nk * Nk * g["Nx"] * g["Ny"]
+            norm = g["dD"] * g["dM"] * Nk * Nl * g["Nx"] * g["Ny"]
             ref_mse = ((xin.astype(np.float64) - out) ** 2).sum() / norm / B
             assert abs(tail[l] - ref_mse) <= 1e-4 * ref_mse, (step, l)
             assert abs(got_mse[l] - ref_mse * (0.5 if sym else 1.0)) <= 1e-4 * ref_mse, (step, l)
@@ -148,6 +144,62 @@ def test_steps_against_backprop_gpu(ctx, sym):
                 assert np.array_equal(now[2], np.ascontiguousarray(now[0].transpose(1, 0, 2, 3)))
         assert np.array_equal(host(net.last_mse()), got_mse)
     net.close()
+
+
+# (D, Nx, Ny, maps, Nk, Nl, scale, B, steps) and the weight-gradient route of each pair (launch_spatial_grad)
+STEP_SHAPES = [
+    (3, 64, 48, [8, 12], 3, 3, 2, 2, 3),      # pair 0 on 32x24: region sums (rcorr<3>); pair 1 on 16x12, dD = 8: mcorr<3>
+    (3, 40, 24, [8, 10], 5, 5, 2, 2, 2),      # pair 0 on 20x12: mcorr<5>; pair 1 on 10x6, Ny % 4 != 0: wcorr<5>
+    (1, 28, 32, [9], 7, 7, 2, 1, 2),          # 14x16: mcorr<7>
+    (3, 36, 60, [4, 3], 5, 3, 2, 2, 2),       # Nk != Nl: the naive kernels; Pool and up-sampling run as launches of their own
+]
+
+
+@pytest.mark.parametrize("sym", [0, 1])
+def test_steps_against_backprop_gpu(ctx, sym):
+    """three step_grad / step_apply rounds against backprop_gpu[_cc] per pair on the GPU's own layers: the packed gradients, the MSE
+    tail, the weights (momentum carried across steps); set_inertia reaches the update"""
+    _steps_against_backprop_gpu(ctx, sym, *STEP_SHAPES[0])
+
+
+@pytest.mark.parametrize("D,Nx,Ny,maps,Nk,Nl,s,B,steps,sym", [STEP_SHAPES[1] + (0,), STEP_SHAPES[1] + (1,), STEP_SHAPES[2] + (0,), STEP_SHAPES[3] + (0,)])
+def test_steps_against_backprop_gpu_other_supports_and_routes(ctx, D, Nx, Ny, maps, Nk, Nl, s, B, steps, sym):
+    """the same checks, two steps each, where the pairs' gradients take the other routes: 5x5 supports on the matrix cores and through
+    the VALU correlation (untied and tied), 7x7 on the matrix cores, and a 5x3 support, which only the naive kernels serve"""
+    _steps_against_backprop_gpu(ctx, sym, D, Nx, Ny, maps, Nk, Nl, s, B, steps)
+
+
+def test_reset_momentum_on_a_spatial_net(ctx):
+    """after two steps and reset_momentum, the next step gives the weights -- to the bit -- that a fresh net gives when it starts
+    from the same weights: the momentum buffers are zero again and nothing else of the two steps is carried over"""
+    D, Nx, Ny, maps, Nk, s, B = 3, 40, 24, [8, 10], 5, 2, 2
+    L = len(maps)
+    x = ctx.dev(frames(np.random.default_rng(71), B, D, Nx, Ny))
+    net = make_net(ctx, D, Nx, Ny, maps, Nk, Nk, s, B, seed=70)
+    w0 = [net.get_pair(l) for l in range(L)]
+    for _ in range(2):
+        net.step_grad(x); net.step_apply(0.2, 0, 0, 1.0)
+    w2 = [net.get_pair(l) for l in range(L)]
+    assert all(not np.array_equal(a[0], b[0]) for a, b in zip(w0, w2))
+    net.reset_momentum()
+    net.step_grad(x); net.step_apply(0.2, 0, 0, 1.0)
+    got = [net.get_pair(l) for l in range(L)]
+    net.close()
+    fresh = make_net(ctx, D, Nx, Ny, maps, Nk, Nk, s, B, seed=1)
+    for l in range(L):
+        fresh.set_pair(l, *w2[l])
+    fresh.step_grad(x); fresh.step_apply(0.2, 0, 0, 1.0)
+    want = [fresh.get_pair(l) for l in range(L)]
+    fresh.close()
+    for a, o in zip(got, want):
+        for u, v in zip(a, o):
+            assert np.array_equal(u, v)
+    # the momentum mattered: without the reset the third step differs
+    cont = make_net(ctx, D, Nx, Ny, maps, Nk, Nk, s, B, seed=70)
+    for _ in range(3):
+        cont.step_grad(x); cont.step_apply(0.2, 0, 0, 1.0)
+    assert not np.array_equal(cont.get_pair(0)[0], got[0][0])
+    cont.close()
 
 
 def _train(ctx, flags, fl, steps=2, shape=(3, 64, 48, [8, 12], 3, 2, 2)):

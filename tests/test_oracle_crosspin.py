@@ -191,8 +191,10 @@ import np_spatial as S
 def test_spatial_conv_cpu_semantics_equals_compiled_conv():
     L = _ref_or_port()
     rng = np.random.default_rng(11)
-    for (dD, dM, N, Nk) in ((2, 3, 12, 3), (3, 2, 14, 5), (1, 2, 16, 7)):
-        x = np.floor(rng.uniform(0, 256, (dD, N, N))); c = rng.uniform(-1, 1, (dM, dD, Nk, Nk)); b = rng.uniform(-1, 1, dM)
+    # (dD, dM, Nx, Ny, Nk, Nl): square grids and supports, then Nx != Ny and Nk != Nl (taps -3..1 for 5, -5..1 for 7 in each axis)
+    for (dD, dM, Nx, Ny, Nk, Nl) in ((2, 3, 12, 12, 3, 3), (3, 2, 14, 14, 5, 5), (1, 2, 16, 16, 7, 7),
+                                     (2, 3, 10, 14, 3, 3), (2, 2, 12, 9, 5, 5), (1, 2, 11, 16, 7, 7), (2, 2, 12, 10, 5, 3), (1, 2, 10, 13, 3, 7)):
+        x = np.floor(rng.uniform(0, 256, (dD, Nx, Ny))); c = rng.uniform(-1, 1, (dM, dD, Nk, Nl)); b = rng.uniform(-1, 1, dM)
         ref = L.conv(x, c, b)
         got = S.conv(x.astype(np.float32), c.astype(np.float32), b.astype(np.float32), cpu_semantics=True)
         assert np.abs(got - ref).max() < 1e-5 * np.abs(ref).max()
@@ -203,12 +205,14 @@ def test_spatial_gradients_cpu_semantics_equal_compiled_backprop():
     (read back from a tiny step on zero weights; f untouched so no in-loop update effect)."""
     L = _ref_or_port()
     rng = np.random.default_rng(12)
-    for (dD, dM, N, Nk) in ((2, 3, 10, 3), (2, 2, 12, 5)):
-        x = rng.uniform(0, 16, (dD, N, N)).astype(np.float32); out = (x + rng.uniform(-2, 2, x.shape)).astype(np.float32)
-        hin = rng.uniform(-4, 4, (dM, N, N)).astype(np.float32)
-        f = rng.uniform(-1, 1, (dD, dM, Nk, Nk)).astype(np.float32)
+    # (dD, dM, Nx, Ny, Nk, Nl): as in test_spatial_conv_cpu_semantics_equals_compiled_conv
+    for (dD, dM, Nx, Ny, Nk, Nl) in ((2, 3, 10, 10, 3, 3), (2, 2, 12, 12, 5, 5),
+                                     (2, 3, 10, 14, 3, 3), (2, 2, 12, 9, 5, 5), (1, 2, 11, 16, 7, 7), (2, 2, 12, 10, 5, 3), (1, 2, 10, 13, 3, 7)):
+        x = rng.uniform(0, 16, (dD, Nx, Ny)).astype(np.float32); out = (x + rng.uniform(-2, 2, x.shape)).astype(np.float32)
+        hin = rng.uniform(-4, 4, (dM, Nx, Ny)).astype(np.float32)
+        f = rng.uniform(-1, 1, (dD, dM, Nk, Nl)).astype(np.float32)
         dele = 1e-12
-        z = np.zeros((dM, dD, Nk, Nk), np.float32)
+        z = np.zeros((dM, dD, Nk, Nl), np.float32)
         c2, b2, f2, p2 = L.backprop(x, out, hin, z, np.zeros(dM, np.float32), f, np.zeros(dD, np.float32), dele)
         assert np.array_equal(f2, f)
         c3, b3, f3, p3 = L.backprop(x, out, hin, z, np.zeros(dM, np.float32), np.zeros_like(f), np.zeros(dD, np.float32), dele)
@@ -234,13 +238,18 @@ def test_spatial_gpu_conv_matches_fft_mode_interior_3x3():
 import np_spatial_literal as SL
 
 
-@pytest.mark.parametrize("dD,dM,Nx,Ny,Nk", [(2, 3, 10, 10, 3), (2, 2, 12, 9, 5), (1, 2, 9, 14, 7), (3, 2, 8, 8, 5)])
-def test_spatial_reassociated_gradients_equal_literal_per_element_loops(dD, dM, Nx, Ny, Nk):
+# (the square supports keep the ids they had when the support was one parameter)
+_LITERAL_SHAPES = [(2, 3, 10, 10, 3, 3), (2, 2, 12, 9, 5, 5), (1, 2, 9, 14, 7, 7), (3, 2, 8, 8, 5, 5), (2, 2, 9, 12, 5, 3), (1, 2, 10, 8, 3, 7)]
+
+
+@pytest.mark.parametrize("dD,dM,Nx,Ny,Nk,Nl", _LITERAL_SHAPES,
+                         ids=["-".join(str(v) for v in (t[:5] if t[4] == t[5] else t)) for t in _LITERAL_SHAPES])
+def test_spatial_reassociated_gradients_equal_literal_per_element_loops(dD, dM, Nx, Ny, Nk, Nl):
     """np_spatial.gradients (back-conv + correlation, the association the HIP kernels share) == the CUDA source followed loop
     by loop, GPU geometry (ak = ((Nk-1)/2-1)/2, range test '>= 0'), B-11 terms with CPU semantics."""
     rng = np.random.default_rng(dD + dM + Nx + Nk)
     x = rng.uniform(0, 16, (dD, Nx, Ny)); out = x + rng.uniform(-2, 2, x.shape)
-    hin = rng.uniform(-4, 4, (dM, Nx, Ny)); f = rng.uniform(-1, 1, (dD, dM, Nk, Nk))
+    hin = rng.uniform(-4, 4, (dM, Nx, Ny)); f = rng.uniform(-1, 1, (dD, dM, Nk, Nl))
     a = S.gradients(x, out, hin, f, lo=0, cpu_geom=False)
     b = SL.gradients_literal(x, out, hin, f, compat=False)
     for u, v, name in zip(a, b, ("gc", "gf", "gb", "gp")):
