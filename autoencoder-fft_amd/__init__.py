@@ -12,6 +12,7 @@ import ctypes as C
 import os
 
 import numpy as np
+import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # (AEFFT_LIB: development only -- tools/x*.sh point the binding at an experiment build under build_x/ instead of copying it over the product)
@@ -72,6 +73,8 @@ SIGNATURES = {
     "aefft_pool_conv_spatial": (_i, [_vp, _fp, _fp, _fp, _fp, _fp] + [_i] * 9),
     "aefft_backprop_spatial": (_i, [_vp] + [_fp] * 15 + [_i] * 7 + [_f, _f, _i, _i]),
     "aefft_step_spatial": (_i, [_vp] + [_fp] * 15 + [_i] * 7 + [_f, _f, _i, _i]),
+    "aefft_image_to_frames": (_i, [_vp, _vp, C.c_size_t, _vp, _i, _i, _i, _i, _i]),
+    "aefft_frames_to_image": (_i, [_vp, _vp, _i, _vp, C.c_size_t, _i, _i, _i, _i]),
     "aefft_net_create": (_i, [_vp, C.POINTER(NetDesc), C.POINTER(_vp)]),
     "aefft_net_create_ex": (_i, [_vp, C.POINTER(NetDesc), C.c_uint, C.POINTER(_vp)]),
     "aefft_net_destroy": (None, [_vp]),
@@ -183,6 +186,21 @@ def _is_u8(t):
 
 def _hptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def _image_layout(image, what):
+    """(the image as [B][Ny][Nx][D], pitch in bytes) of a uint8 tensor [B][Ny][Nx][D] or [Ny][Nx][D] of interleaved image rows: contiguous, or a
+    row-padded view -- stride(-1) == 1, stride(-2) == D, stride(-3) = pitch >= Nx * D and, for a batch, stride(0) == Ny * pitch"""
+    if image.dtype != torch.uint8 or image.dim() not in (3, 4):
+        raise ValueError(f"{what}: the image must be a uint8 tensor [B][Ny][Nx][D] or [Ny][Nx][D]")
+    img = image if image.dim() == 4 else image.unsqueeze(0)
+    B, Ny, Nx, D = img.shape
+    sb, sj, si, sd = img.stride()
+    pitch = sj if Ny > 1 else (sb if B > 1 else Nx * D)
+    if min(B, Ny, Nx, D) < 1 or (D > 1 and sd != 1) or (Nx > 1 and si != D) or pitch < Nx * D or (B > 1 and sb != Ny * pitch):
+        raise ValueError(f"{what}: the image must be contiguous or a row-padded view (stride(-1) == 1, stride(-2) == D, stride(-3) = pitch >= Nx * D, "
+                         f"stride(0) == Ny * pitch); got shape {tuple(image.shape)} with strides {tuple(image.stride())}")
+    return img, int(pitch)
 
 
 class Context:
@@ -389,6 +407,38 @@ class Context:
                                              _ptr(dc), _ptr(db), _ptr(df), _ptr(dp), _ptr(ddc), _ptr(ddb), _ptr(ddf), _ptr(ddp),
                                              B, dD, dM, Nx, Ny, Nk, Nl, delmax, alpha, 1 if tied else 0, {"gpu": 0, "cpu": 1}[semantics]))
         return hin, out
+
+    # ---- image boundary ----
+    def image_to_frames(self, image, out=None, dtype=torch.uint8):
+        """ImageToSpin_C on the device (aefft_image_to_frames): `image` is a uint8 device tensor [B][Ny][Nx][D] of interleaved image rows (or
+        [Ny][Nx][D] for one image), contiguous or a row-padded view (stride(-3) = pitch >= Nx * D; ValueError otherwise).  Returns, or fills
+        `out` with, the planar frames [B][D][Nx][Ny] of `dtype` uint8 or float32: frames[b][d][i][j] = image[b][j][i][d].  One launch, nothing
+        waits for the device."""
+        img, pitch = _image_layout(image, "Context.image_to_frames")
+        B, Ny, Nx, D = img.shape
+        if out is None:
+            if dtype not in (torch.uint8, torch.float32):
+                raise ValueError("Context.image_to_frames: dtype must be torch.uint8 or torch.float32")
+            out = self.empty(B, D, Nx, Ny, dtype=dtype)
+        elif out.dtype not in (torch.uint8, torch.float32) or tuple(out.shape) != (B, D, Nx, Ny) or not out.is_contiguous():
+            raise ValueError(f"Context.image_to_frames: out must be a contiguous uint8 or float32 tensor of shape {(B, D, Nx, Ny)}")
+        self.check(self.L.aefft_image_to_frames(self.h, _ptr(img), pitch, _ptr(out), int(_is_u8(out)), B, D, Nx, Ny))
+        return out
+
+    def frames_to_image(self, frames, out=None):
+        """SpinToImage_C on the device (aefft_frames_to_image): `frames` is uint8 or float32 [B][D][Nx][Ny]; float values become
+        clamp(round(v), 0, 255) as Net.infer's uint8 reconstruction does.  Returns, or fills `out` with, the uint8 image rows [B][Ny][Nx][D];
+        `out` may be a row-padded view as for image_to_frames (its pad bytes are not written).  One launch, nothing waits for the device."""
+        if frames.dtype not in (torch.uint8, torch.float32) or frames.dim() != 4 or not frames.is_contiguous():
+            raise ValueError("Context.frames_to_image: frames must be a contiguous uint8 or float32 tensor [B][D][Nx][Ny]")
+        B, D, Nx, Ny = frames.shape
+        if out is None:
+            out = self.empty(B, Ny, Nx, D, dtype=torch.uint8)
+        img, pitch = _image_layout(out, "Context.frames_to_image")
+        if tuple(img.shape) != (B, Ny, Nx, D):
+            raise ValueError(f"Context.frames_to_image: out must have shape {(B, Ny, Nx, D)}")
+        self.check(self.L.aefft_frames_to_image(self.h, _ptr(frames), int(_is_u8(frames)), _ptr(img), pitch, B, D, Nx, Ny))
+        return out
 
     def set_flags(self, *names):
         """Development switches (include/aefft.h AEFFT_F_*), by name without the prefix; no names = defaults."""

@@ -53,6 +53,12 @@ hipError_t launch_score_finish(const float* part, float* score, int B, long npf,
 hipError_t launch_score_map_diff(const void* frames, bool u8, const float* recon, float* strips, long npairs, int n, int tile, hipStream_t st);
 // map[b][I][J] = sum over d < D and the tile/2 row pairs of tile row I of strips[((b D + d) Nx/2 + I tile/2 + p)][J], in double, / (D tile tile)
 hipError_t launch_score_map_finish(const float* strips, float* map, int B, int D, int Nx, int Ny, int tile, hipStream_t st);
+// ---- image_kernels.hip (aefft_image_to_frames / aefft_frames_to_image) ----
+// ImageToSpin_C / SpinToImage_C for a batch: image = B images of Ny rows of `pitch` bytes, pixel (row j, column i) channel d at j pitch + i D + d;
+// frames [B][D][Nx][Ny], float when f32, unsigned char otherwise: frames[b][d][i][j] = image[b][j][i][d] (float frames -> pixels by px_u8).
+// D in 1..4, Nx, Ny in 1..8192, pitch >= Nx D (hipErrorInvalidValue otherwise); any alignment of image and pitch, frames 16-byte aligned.
+hipError_t launch_image_unpack(const unsigned char* image, size_t pitch, void* frames, bool f32, int B, int D, int Nx, int Ny, hipStream_t st);
+hipError_t launch_image_pack(const void* frames, bool f32, unsigned char* image, size_t pitch, int B, int D, int Nx, int Ny, hipStream_t st);
 size_t fft_mid_elems(long planes, int Nx, int Wc);   // complex elements needed in `mid`
 // sizes that are not powers of two (cufftPlanMany takes any size, fft.cu:773-779): even n in 8..1024 through Bluestein's chirp-z form on the
 // power-of-two LDS passes; rows -> transpose -> rows -> transpose.  w1, w2: workspaces of fft_any_ws_elems complex each.

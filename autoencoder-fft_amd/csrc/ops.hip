@@ -1,6 +1,6 @@
 // C-ABI layer (include/aefft.h), op level: the internal op helpers -- transform routes and size checks, contractions and their
 // descriptors, the gradient, the kernel-support transforms, the update -- which the network units (net.hip, net_step.hip) build on,
-// and the op-level and spatial entry points.
+// and the op-level, spatial and image-boundary entry points.
 #include "host.h"
 
 #include <algorithm>
@@ -740,4 +740,39 @@ extern "C" int aefft_step_spatial(aefft_ctx* ctx, const float* in_d, float* hin_
     RET_IF(aefft_conv_spatial(ctx, hin_d, out_d, f_d, p_d, B, dM, dD, Nx, Ny, Nk, Nl, cpu_semantics));
     return backprop_spatial_impl(ctx, in_d, out_d, hin_d, c_d, b_d, f_d, p_d, dc_d, db_d, df_d, dp_d, ddc_d, ddb_d, ddf_d, ddp_d,
                                  B, dD, dM, Nx, Ny, Nk, Nl, delmax, alpha, tied, cpu_semantics, true);
+}
+
+// image boundary ------------------------------------------------------------------------------
+// the rules both directions share (include/aefft.h "image boundary"); nothing is enqueued when one fails
+static int chk_image(aefft_ctx* ctx, const char* fn, const void* image_d, size_t pitch, const void* frames_d, int frames_u8, int B, int D, int Nx, int Ny)
+{
+    const auto bad = [&](const char* rule) { return fail(ctx, AEFFT_EINVAL, (std::string(fn) + ": " + rule).c_str()); };
+    if (!ctx || !image_d || !frames_d) return bad("null context, image or frames");
+    if (D < 1 || D > 4) return bad("D must be 1..4 (grey, BGR, BGRA)");
+    if (B < 1 || Nx < 1 || Ny < 1 || Nx > 8192 || Ny > 8192) return bad("B must be >= 1 and Nx, Ny in 1..8192");
+    if (pitch < (size_t)Nx * D) return bad("pitch must be at least Nx * D bytes");
+    const size_t rows = (size_t)B * Ny;
+    if (pitch > (~size_t(0) >> 1) / rows) return bad("B * Ny * pitch does not fit the address space");
+    if (!aligned16(frames_d)) return bad("frames_d must be 16-byte aligned");
+    // the bytes either side touches: the frames whole, the image up to the last row's Nx * D
+    const uintptr_t f0 = reinterpret_cast<uintptr_t>(frames_d), f1 = f0 + (size_t)B * D * Nx * Ny * (frames_u8 ? 1 : 4);
+    const uintptr_t i0 = reinterpret_cast<uintptr_t>(image_d), i1 = i0 + (rows - 1) * pitch + (size_t)Nx * D;
+    if (f0 < i1 && i0 < f1) return bad("the frame and image ranges overlap (the op is out-of-place)");
+    return AEFFT_OK;
+}
+
+extern "C" int aefft_image_to_frames(aefft_ctx* ctx, const unsigned char* image_d, size_t pitch, void* frames_d, int frames_u8, int B, int D, int Nx, int Ny)
+{
+    RET_IF(chk_image(ctx, "aefft_image_to_frames", image_d, pitch, frames_d, frames_u8, B, D, Nx, Ny));
+    RET_IF(join_recon(ctx));                          // (frames_d may be a buffer a deferred reconstruction is still writing)
+    return launch_or_fail(ctx, KID_IMAGE, (double)B * D * Nx * Ny * (frames_u8 ? 2.0 : 5.0), "image_unpack",
+                          [&] { return launch_image_unpack(image_d, pitch, frames_d, !frames_u8, B, D, Nx, Ny, ctx->cur); });
+}
+
+extern "C" int aefft_frames_to_image(aefft_ctx* ctx, const void* frames_d, int frames_u8, unsigned char* image_d, size_t pitch, int B, int D, int Nx, int Ny)
+{
+    RET_IF(chk_image(ctx, "aefft_frames_to_image", image_d, pitch, frames_d, frames_u8, B, D, Nx, Ny));
+    RET_IF(join_recon(ctx));                          // (frames_d may be the reconstruction of a step whose inverse transform is still on the side stream)
+    return launch_or_fail(ctx, KID_IMAGE, (double)B * D * Nx * Ny * (frames_u8 ? 2.0 : 5.0), "image_pack",
+                          [&] { return launch_image_pack(frames_d, !frames_u8, image_d, pitch, B, D, Nx, Ny, ctx->cur); });
 }

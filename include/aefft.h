@@ -211,6 +211,30 @@ int aefft_step_spatial(aefft_ctx* ctx, const float* in_d, float* hin_d, float* o
                        int B, int dD, int dM, int Nx, int Ny, int Nk, int Nl,
                        float delmax, float alpha, int tied, int cpu_semantics);
 
+/* ---- image boundary: camera images as delivered <-> the library's planar frames --------------- */
+/* netlib.cpp:37-51 `ImageToSpin_C` and :54-77 `SpinToImage_C` on the device, for a batch, one launch each.  Every 8-bit entry point of the
+ * network level takes PLANAR pixels; a camera, a cv::Mat, a V4L2 buffer or an image file delivers rows of interleaved pixels.  These two
+ * calls convert between the two on the device, so that no host loop touches the pixels.
+ * Image layout: B images, each Ny rows of `pitch` bytes; image b starts at b * Ny * pitch; pixel (row j, column i), channel d, is the byte at
+ *   j * pitch + i * D + d,     pitch >= Nx * D   (cv::Mat::step, a V4L2 bytesperline, the pitch of a 2-D copy).
+ * Bytes of a row beyond Nx * D are never read by aefft_image_to_frames and never written by aefft_frames_to_image.  The channel order is the
+ * image's own (d is d: BGR stays BGR, as in the reference).
+ * Frame layout: the library's [B][D][Nx][Ny], unsigned char when frames_u8 != 0, float otherwise:
+ *   frames[b][d][i][j] = image[b][j][i][d]        i < Nx = image columns,  j < Ny = image rows.
+ * The transposition is the reference's: ImageToSpin_C fills spin[c][i][j] = img.at<Vec3b>(j, i)[c] with Nx = img.cols, Ny = img.rows.
+ * Values: to frames (float)pixel, exact; from float frames SpinToImage_C's rule exactly as the inverse row pass applies it for
+ * aefft_net_infer(recon_u8 = 1) -- clamp((int)round(v), 0, 255), halves away from zero, NaN -> 0, -inf -> 0, +inf -> 255; from 8-bit frames
+ * the bytes themselves.
+ * Shapes: D in 1..4 (grey, BGR, BGRA); Nx, Ny in 1..8192, odd sizes included -- the calls are not tied to what a net accepts; B >= 1.
+ * Alignment: frames_d is 16-byte aligned (the library's rule); image_d and pitch may have ANY alignment.  With image_d and pitch multiples of 4
+ * the image side moves dwords, with Ny a multiple of 4 the frame side does; otherwise that side moves single bytes.  Every accepted argument
+ * gives the same bytes.
+ * One launch on the context's stream; no host synchronisation, no allocation, no workspace; safe under stream capture.  Out-of-place.
+ * AEFFT_EINVAL, with aefft_last_error naming the rule and nothing enqueued: a null context or pointer, D outside 1..4, a size outside its
+ * range, pitch < Nx * D, frames_d not 16-byte aligned, frame and image ranges that overlap. */
+int aefft_image_to_frames(aefft_ctx* ctx, const unsigned char* image_d, size_t pitch, void* frames_d, int frames_u8, int B, int D, int Nx, int Ny);
+int aefft_frames_to_image(aefft_ctx* ctx, const void* frames_d, int frames_u8, unsigned char* image_d, size_t pitch, int B, int D, int Nx, int Ny);
+
 /* ---- network level: the resident, batched form of autoenc_fft / backprop_fft ------------------ */
 typedef struct {
     int D, Nx, Ny;        /* input frames [B][D][Nx][Ny] */
