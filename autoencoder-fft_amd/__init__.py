@@ -93,6 +93,7 @@ SIGNATURES = {
     "aefft_net_train_pair": (_i, [_vp, _i, _i, _f, _i, _i, _vp]),
     "aefft_net_step_grad": (_i, [_vp, _fp, _fp]),
     "aefft_net_step_grad_u8": (_i, [_vp, _vp, _fp]),
+    "aefft_net_step_grad_target": (_i, [_vp, _vp, _i, _vp, _i, _fp]),
     "aefft_net_forward_u8": (_i, [_vp, _vp, _fp]),
     "aefft_net_infer": (_i, [_vp, _vp, _i, _vp, _i, _i, _fp]),
     "aefft_net_decode": (_i, [_vp, _i, _fp, _vp, _i]),
@@ -624,6 +625,13 @@ class Net:
         """frames: float32 [B][D][Nx][Ny], or uint8 of the same shape (8-bit pixels: aefft_net_step_grad_u8, converted by the input transform)."""
         fn = self.L.aefft_net_step_grad_u8 if _is_u8(frames) else self.L.aefft_net_step_grad
         self.ctx.check(fn(self.h, _ptr(frames), _ptr(recon)))
+
+    def step_grad_target(self, frames, targets, recon=None):
+        """step_grad toward a target (aefft_net_step_grad_target): pair 0's expected output is the spectrum of `targets` instead of the frames'
+        own -- denoising, deblurring, restoration.  frames, targets: float32 or uint8 [B][D][Nx][Ny], each on its own (8-bit pixels convert on
+        load).  The following step_apply is the usual one; pair 0's post-update MSE is then taken against the target.  The first call of a
+        net allocates the target's workspaces."""
+        self.ctx.check(self.L.aefft_net_step_grad_target(self.h, _ptr(frames), int(_is_u8(frames)), _ptr(targets), int(_is_u8(targets)), _ptr(recon)))
 
     def grad_buffer(self):
         """torch view of the packed gradient buffer (for torch.distributed.all_reduce)."""

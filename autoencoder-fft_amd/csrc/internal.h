@@ -293,6 +293,16 @@ struct PackTabs;
 bool pack_mod(const PackArgs& g);
 hipError_t pack_tabs(const PackArgs& g, PackTabs& t);
 
+// ---- target_kernels.hip (aefft_net_step_grad_target) -----------------------------------
+// With N_b = Xf_b - Tf_b (both [B][D][P0], D <= 4):  S [D][D][P0] += sum_b N_b Xf_b^H (mk_S layout),  es[2 a + {0, 1}] += sum_b N_b[a](0,0) (nullable),
+// K [D][D+1][P0] = sum_b N_b [Xf_b; 1]^H,  n2 [P0] = sum_b |N_b|^2.  The batch is summed in a fixed order, no atomics.
+hipError_t launch_target_terms(const float2* Xf, const float2* Tf, float2* S, float* es, float2* K, float* n2, int B, int D, long P0, hipStream_t st);
+// slots += scale * sum over the bins, with calc_mse's weights, of -2 Re tr(R K^H) + n2, R = [I - G' | -beta^] of pair 0's UPDATED weights:
+// G [D][D][P] = F'.C'/(dM D), or null and the planar C [dM][D][P], F [D][dM][P]; F' at the DC bin: element (a, m) at Fdc[(a*dM + m) * fdc_stride]
+struct TargetMseArgs { const float2 *G, *C, *F, *Fdc; long fdc_stride; const float *b, *p; const float2* K; const float* n2; float* slots;
+                       int dM, Nx, Ny; long P; float scale; };
+hipError_t launch_target_mse(const TargetMseArgs& q, int D, hipStream_t st);
+
 // ---- update_kernels.hip ----------------------------------------------------------------
 hipError_t launch_pad(const float* ck, float* cpad, long planes, int Nx, int Ny, int Nk, int Nl, hipStream_t st);   // fft.cu:570 (zero-fills)
 hipError_t launch_shrink(const float* cpad, float* ck, long planes, int Nx, int Ny, int Nk, int Nl, float scale, hipStream_t st); // fft.cu:535

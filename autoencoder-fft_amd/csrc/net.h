@@ -81,6 +81,11 @@ struct aefft_net {
     float* mse_pre = nullptr;  // = scratch
     float* mse_post = nullptr; // = scratch + L
     float* gtaps = nullptr;      // G' from the stored taps on HBM-sized grids: the (2Nk-1)^2 taps of every plane of every pair (gprime_from_taps)
+    // training toward a target (aefft_net_step_grad_target, target_kernels.hip): allocated by the net's first target call
+    float2* Tf = nullptr;        // [B][D][P0] the targets' spectra on pair 0's grid
+    float2* tgtK = nullptr;      // [D][D+1][P0] K = sum_b N_b [X_0,b; 1]^H, N_b = X_0,b - T_b (the post-update MSE's cross term)
+    float* tgtN2 = nullptr;      // [P0] sum_b |N_b|^2
+    bool target_step = false;    // the pending step (have_grad) has a target: from aefft_net_step_grad_target to its aefft_net_step_apply
     float *gd_out = nullptr, *gd_part = nullptr;   // multiobjective mode: [cd | fd | bd | pd] per pair, and the chunk partial sums (gradient_diff_ws_floats)
     bool mse_pending = false;   // the slots hold the unsummed post-update MSE of the last aefft_net_step_apply (mse_d == NULL): summed by the next step's wgrad launch or mse_flush
     float mse_pending_scale = 1.f;

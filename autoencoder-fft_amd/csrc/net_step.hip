@@ -178,6 +178,45 @@ extern "C" int aefft_net_train_pair(aefft_net* n, int l, int n_iter, float del0,
     return mark_step_point(n);
 }
 
+// The spectra that stand in gradient_k_io's EXPECTED-OUTPUT role for pair q in the per-frame form: the pair's input (expout = in,
+// autoencoder.cpp:194), or for pair 0 of a target step the targets' spectra (aefft_net_step_grad_target)
+static const float2* expected_out(const aefft_net* n, const Pair& q) { return (n->target_step && &q == n->pr.data()) ? n->Tf : q.X; }
+
+// Target step: the targets' spectra on pair 0's grid (the input transform with the crop fused, on the context stream: never prefetched),
+// then S_0 += sum_b N_b X_b^H with N_b = X_0,b - T_b -- behind the launch that completes S_0 (opform_moments / support_terms), in front of
+// its first consumer -- and, for the post-update MSE, K and n2 (target_kernels.hip).  es_0 takes its correction here in the operator
+// form only: the per-frame DC-bin workgroups form O - T themselves from expected_out().
+static int target_terms(aefft_net* n, const void* targets_d, bool u8)
+{
+    aefft_ctx* ctx = n->ctx;
+    Pair& q = n->pr[0];
+    RET_IF(do_r2c(ctx, static_cast<const float*>(targets_d), n->Tf, (long)n->B * n->D, n->Nx, n->Ny, q.Nx, q.Ny, WS_MID, nullptr, u8));
+    const double bytes = (2.0 * n->B * n->D + 2.0 * n->D * n->D + (double)n->D * (n->D + 1)) * q.P * 8.0 + q.P * 4.0;
+    return launch_or_fail(ctx, KID_TARGET, bytes, "target_terms", [&] {
+        return launch_target_terms(n->Xf, n->Tf, q.S, op_mode(n) ? q.es : nullptr, n->tgtK, n->tgtN2, n->B, n->D, q.P, ctx->cur);
+    });
+}
+
+// Target step: pair 0's post-update MSE is mse_fft(T, O') = |E|^2 - 2 Re(E^H N) + |N|^2 with E = X - O' the residual the step's own
+// launches sum; the other two terms go into the pair's slots here, in front of whichever launch sums them.  G (nullable): G'_0 of the
+// UPDATED weights where a route left it, else it is formed from the pair's planar spectra; Fdc: F' at the DC bin.
+static int target_mse(aefft_net* n, const float2* G, const float2* Fdc, long fdc_stride)
+{
+    aefft_ctx* ctx = n->ctx;
+    Pair& q = n->pr[0];
+    TargetMseArgs a{};
+    a.G = G; a.Fdc = Fdc; a.fdc_stride = fdc_stride;
+    if (!G) {
+        RET_IF(ensure_spectra(n, q));
+        a.C = q.C; a.F = q.F; a.Fdc = q.F; a.fdc_stride = q.P;
+    }
+    a.b = q.b; a.p = q.p; a.K = n->tgtK; a.n2 = n->tgtN2; a.slots = mse_slot(n, 0);
+    a.dM = q.dM; a.Nx = q.Nx; a.Ny = q.Ny; a.P = q.P;
+    a.scale = 1.0f / ((float)(2 * q.dM) * (float)q.Nx * (float)q.Ny * (float)n->B) / ((float)q.dD * q.Nx * q.Ny);   // as mk_gmse
+    const double bytes = ((G ? (double)q.dD * q.dD : 2.0 * q.dM * q.dD) + (double)q.dD * (q.dD + 1)) * q.P * 8.0 + q.P * 4.0;
+    return launch_or_fail(ctx, KID_TARGET, bytes, "target_mse", [&] { return launch_target_mse(a, q.dD, ctx->cur); });
+}
+
 // Step mode runs the same per-pair sequences as pair_grad / pair_apply, phase by phase over ALL pairs, so that
 // the independent contractions of a phase (4 x S, 4 x dc + 4 x df, 4 + 4 re-forward convs) go out as one launch each.
 static int bias_and_kgrad(aefft_net* n, Pair& q)
@@ -187,7 +226,7 @@ static int bias_and_kgrad(aefft_net* n, Pair& q)
     const GradSeg gs = q.grads(n->grad);
     const float norm = (float)q.Nx * (float)q.Ny, Norm = grad_norm(q.dM, q.dD, q.Nx, q.Ny);
     RET_IF(launch_or_fail(ctx, KID_BIASGRAD, ((double)(q.dM * q.dD + q.dM + q.dD) + 2.0 * n->B * q.dD) * 8.0, "bias_grad",
-                          [&] { return launch_bias_grad(q.O, q.X, q.F, q.b, q.df, gs.db, gs.dp, n->B, q.dM, q.dD, q.P, norm, Norm, ctx->cur); }));
+                          [&] { return launch_bias_grad(q.O, expected_out(n, q), q.F, q.b, q.df, gs.db, gs.dp, n->B, q.dM, q.dD, q.P, norm, Norm, ctx->cur); }));
     return shrink_dcdf(n, q);
 }
 
@@ -264,7 +303,7 @@ static int fill_bias_grads(aefft_net* n, bool op, bool qpath, BiasGradGroup& bg,
         const GradSeg gs = q.grads(n->grad);
         const float Norm = grad_norm(q.dM, q.dD, q.Nx, q.Ny);
         const OutView v = out_view(n, q);
-        bg.a[l] = BiasGradArgs{v.O, q.X, q.F, q.b, qpath ? nullptr : q.df, gs.db, gs.dp, n->B, q.dM, q.dD, q.P,
+        bg.a[l] = BiasGradArgs{v.O, expected_out(n, q), q.F, q.b, qpath ? nullptr : q.df, gs.db, gs.dp, n->B, q.dM, q.dD, q.P,
                                (float)q.Nx * (float)q.Ny, Norm, v.P, qpath ? q.es : nullptr, op ? q.es : nullptr};
         if (!q.spectra_valid) {
             // (operator form: the step left the planar spectra stale; F at the DC bin is record 0 of the
@@ -336,11 +375,12 @@ static int wgrads_dcdf(aefft_net* n, bool op)
     return AEFFT_OK;
 }
 
-static int grads_grouped(aefft_net* n)
+static int grads_grouped(aefft_net* n, const void* targets_d, bool targets_u8)
 {
     const bool op = op_mode(n);
     RET_IF(op ? opform_moments(n) : support_terms(n));
     n->xx_done = false; n->ox_done = 0;
+    if (targets_d) RET_IF(target_terms(n, targets_d, targets_u8));
     // DC-bin terms and the pruned inverse transforms of all pairs: one launch each when the pairs share (Nk, Nl)
     const bool same = (op || (n->L > 1 && n->L <= 8 && !flag(AEFFT_F_NOGROUP))) && shared_supports(n);
     if (!same) {
@@ -358,6 +398,8 @@ static int grads_grouped(aefft_net* n)
 // re-forward's H and O again (the next forward overwrites them), so they are not materialised: G = F.C per bin
 // (into the dead S workspace), then one pass over X with the MSE epilogue.  Falls back to conv, conv, diff_mse
 // for shapes the lean kernel does not serve (dD == 1 or B == 1).
+// With a target, pair 0's fused pass still sums |X - O'|^2 (the caller adds the target's terms: target_mse); the conv, conv, diff_mse
+// route compares O' with the target's spectra directly.
 static int reforward_mse(aefft_net* n, Pair& q, float* mse_slots, bool* g_left_in_S = nullptr)
 {
     if (g_left_in_S) *g_left_in_S = false;
@@ -373,7 +415,7 @@ static int reforward_mse(aefft_net* n, Pair& q, float* mse_slots, bool* g_left_i
     RET_IF(join_recon(ctx));                                                  // a deferred reconstruction may still be reading q.O (== Oc when P == Pc)
     RET_IF(do_conv(ctx, q.X, q.C, q.b, q.H, n->B, q.dM, q.dD, q.Nx, q.Ny));   // :1460
     RET_IF(do_conv(ctx, q.H, q.F, q.p, q.O, n->B, q.dD, q.dM, q.Nx, q.Ny));   // :1461
-    return do_diff_mse(ctx, q.X, q.O, nullptr, n->mse_post + (&q - n->pr.data()), nullptr, n->B, q.dM, q.dD, q.Nx, q.Ny);   // :1463
+    return do_diff_mse(ctx, expected_out(n, q), q.O, nullptr, n->mse_post + (&q - n->pr.data()), nullptr, n->B, q.dM, q.dD, q.Nx, q.Ny);   // :1463
 }
 
 // The routes of one aefft_net_step_apply, decided in front of its first launch.  A declined spectra launch drops fused_upd and gp_route.
@@ -597,6 +639,9 @@ static int opform_mse(aefft_net* n, const ApplyRoute& rt, const UpdateGroup* wup
     if (ahead) fill_chain(n, ca, n->op_set ^ 1, &bytes);
     RET_IF(launch_or_fail(ctx, KID_OPMSE, bytes, "opmse", [&] { return launch_opmse_group(og, ctx->cur, ahead ? &ca : nullptr, wupd, &n->tail_route); }));
     if (ahead) { n->op_set ^= 1; n->chain_valid = true; }
+    // (target step: behind the tail launch -- a fused update stores the taps there, and planar spectra formed on request read them -- and
+    // in front of whatever sums the slots)
+    if (n->target_step) RET_IF(target_mse(n, og.q[0].G, og.q[0].Fdc, og.q[0].fdc_stride));
     if (!mse_d && !ctx->prof && !flag(AEFFT_F_NOLAZYMSE)) {
         // nobody asked for the sums now: they are formed by one more workgroup of the next step's gradient launch (before its
         // all-reduce), by aefft_net_last_mse, or by whatever needs the slots next -- not by a launch of their own
@@ -644,6 +689,8 @@ static int reforward_mse_all(aefft_net* n, bool* inner_g)
         bool left = in_group;
         if (!in_group) RET_IF(reforward_mse(n, q, mse_slot(n, l), &left));
         if (l == n->L - 1) *inner_g = left;
+        // (target step: pair 0 went through G'_0 = q.G and summed |X - O'|^2; the cross term and |N|^2 into the same slots)
+        if (l == 0 && left && n->target_step) RET_IF(target_mse(n, q.G, q.F, q.P));
     }
     return AEFFT_OK;
 }
@@ -708,13 +755,16 @@ extern "C" int aefft_net_set_input_ready(aefft_net* n, int enable)
     return AEFFT_OK;
 }
 
-static int step_grad(aefft_net* n, const float* frames_d, bool u8, float* recon_d)
+// targets_d (nullable): the step trains pair 0 toward these frames (aefft_net_step_grad_target)
+static int step_grad(aefft_net* n, const float* frames_d, bool u8, float* recon_d, const void* targets_d = nullptr, bool targets_u8 = false)
 {
     aefft_ctx* ctx = n->ctx;
     ++n->step_no;
+    n->target_step = false;
     RET_IF(net_forward(n, frames_d, u8, recon_d, true, op_eligible(n)));
+    n->target_step = targets_d != nullptr;
     {
-        int rcg = grads_grouped(n);
+        int rcg = grads_grouped(n, targets_d, targets_u8);
         if (rcg == AEFFT_OK) rcg = mse_flush(n);      // (a gradient route without the wgrad launch: the deferred MSE sums as their own launch after all)
         if (rcg != AEFFT_OK) { n->recon_deferred = nullptr; return rcg; }
     }
@@ -758,6 +808,28 @@ extern "C" int aefft_net_step_grad_u8(aefft_net* n, const unsigned char* frames_
     return n ? step_grad(n, reinterpret_cast<const float*>(frames_d), true, recon_d) : AEFFT_EINVAL;
 }
 
+static bool aligned16p(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+extern "C" int aefft_net_step_grad_target(aefft_net* n, const void* frames_d, int frames_u8, const void* targets_d, int targets_u8, float* recon_d)
+{
+    if (!n) return AEFFT_EINVAL;
+    aefft_ctx* ctx = n->ctx;
+    if (!frames_d || !targets_d) return fail(ctx, AEFFT_EINVAL, "aefft_net_step_grad_target: null frames or targets");
+    if (!aligned16p(frames_d) || !aligned16p(targets_d) || !aligned16p(recon_d)) return fail(ctx, AEFFT_EINVAL, "aefft_net_step_grad_target: pointers must be 16-byte aligned");
+    if (n->spatial) return sp_refuse(n, "aefft_net_step_grad_target");
+    if (n->D > 4) return fail(ctx, AEFFT_EINVAL, "aefft_net_step_grad_target: frames are images of 1 to 4 channels (grey, BGR, BGRA): D must be at most 4");
+    if (!n->Tf) {
+        // (the first target call of a net: not under stream capture, include/aefft.h)
+        const Pair& q = n->pr[0];
+        float2 *tf = nullptr, *k = nullptr;
+        RET_IF(net_alloc_t(n, &tf, (size_t)n->B * n->D * q.P));
+        RET_IF(net_alloc_t(n, &k, (size_t)n->D * (n->D + 1) * q.P));
+        RET_IF(net_alloc_t(n, &n->tgtN2, (size_t)q.P));
+        n->tgtK = k; n->Tf = tf;
+    }
+    return step_grad(n, static_cast<const float*>(frames_d), frames_u8 != 0, recon_d, targets_d, targets_u8 != 0);
+}
+
 extern "C" int aefft_net_step_form(aefft_net* n)
 {
     if (!n) return -1;
@@ -796,6 +868,7 @@ extern "C" int aefft_net_step_apply(aefft_net* n, float del0, int maxdiff, int s
     const float del = 0.1f * del0;
     RET_IF(apply_grouped(n, del, maxdiff, sym, grad_scale, mse_d));
     n->have_grad = false;
+    n->target_step = false;
     n->upd_after_fwd = true;
     RET_IF(join_recon(ctx));
     return mark_step_point(n);

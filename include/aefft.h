@@ -365,6 +365,32 @@ int aefft_net_step_grad(aefft_net* net, const float* frames_d, float* recon_d);
  * 16-byte aligned.  aefft_net_get_layer(0) returns the pixels as floats. */
 int aefft_net_step_grad_u8(aefft_net* net, const unsigned char* frames_d, float* recon_d);
 int aefft_net_forward_u8(aefft_net* net, const unsigned char* frames_d, float* recon_d);
+/* Training toward a TARGET frame -- supervised image-to-image training: denoising, deblurring, restoration.  The reference's entry point takes
+ * three tensors, backprop_fft(in, expout, out, ..) (fft_backproplib.cu:1381-1463), and gradient_k_io (:395-475) reads the expected output only in
+ * the error `ofreq - freqout`; the application passes expout = in, and its commented-out lines (autoencoder.cpp:126-127,192-193) show the
+ * intended use: a second image as expout for the first pair, `if(n_l!=0) expout1=in_s` for the deeper ones.
+ * The call is aefft_net_step_grad with one change: for PAIR 0 the expected output is T_b = pool_fft(fft(target_b), s_0), the target's spectrum
+ * on pair 0's grid, instead of the pair's input X_0,b; the input role (freqin) stays X_0,b.  Pairs l >= 1 keep expout = in.  frames_d and
+ * targets_d are [B][D][Nx][Ny], each float, or unsigned char when its _u8 flag is set (8-bit pixels convert on load as everywhere else; the
+ * two may differ in type).  All pointers 16-byte aligned.  The forward pass, recon_d (nullable), the layers exported afterwards and the packed
+ * buffer's layout are those of aefft_net_step_grad; a data-parallel caller all-reduces the same buffer.
+ * The following aefft_net_step_apply is the existing call.  After a target step pair 0's post-update MSE is mse_fft(T, O') (:1463 with
+ * freqo_d = the target) wherever it is reported: mse_d, the packed buffer's tail, aefft_net_last_mse, the deferred sums under mse_d = NULL.
+ * The net remembers that the pending step has a target from this call until that step's aefft_net_step_apply, or any call that ends a pending
+ * step; a plain aefft_net_step_grad clears it.
+ * Every term of gradient_k_io is linear in the error, so with N_b = X_0,b - T_b (exactly zero when the target is the frame) the target enters
+ * as S_0 += sum_b N_b X_b^H and es_0 += sum_b N_b(0,0) behind the launch that forms them, and as -2 Re(E^H N) + |N|^2 in pair 0's MSE sums
+ * (DESIGN.md section 18): the target's input transform (never prefetched) and two short launches on top of the plain step, batch sums in a
+ * fixed order with no atomics -- replicas of a data-parallel run keep bit-identical gradients.  With target == frames the gradients and the
+ * updated weights are those of the plain step by value.
+ * The call runs in whatever form aefft_net_step_form reports and under every development switch; everything it adds is ordered on the
+ * context stream, also under aefft_net_set_input_ready(1).  The FIRST target call of a net allocates the target's workspaces (as
+ * aefft_net_set_input_ready and the multiobjective buffers are allocated on first use): it must not be made under stream capture.  Later
+ * calls allocate nothing and do not synchronise.
+ * AEFFT_EINVAL, with nothing enqueued: a null net, null frames or null targets; a pointer not 16-byte aligned; a spatial net; D > 4 (frames
+ * are images: grey, BGR, BGRA).  Not offered: targets for aefft_net_train_pair bursts (backprop_fft of the vector API takes expout), for
+ * aefft_net_score / _score_map, and for pairs l >= 1. */
+int aefft_net_step_grad_target(aefft_net* net, const void* frames_d, int frames_u8, const void* targets_d, int targets_u8, float* recon_d /* nullable */);
 /* Frozen-weight inference over a batch -- the application's display loop (ImageToSpin_C, autoenc_fft, SpinToImage_C on every camera frame,
  * netlib.cpp:37-77, autoencoder.cpp:218-227): the reconstruction (layers.back() of autoenc_fft) and optionally ONE hidden layer, from the
  * CURRENT weights.  frames_d [B][D][Nx][Ny] float, or unsigned char when frames_u8; recon_d (nullable) [B][D][Nx][Ny] float, or
