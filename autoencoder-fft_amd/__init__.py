@@ -99,6 +99,9 @@ SIGNATURES = {
     "aefft_net_decode": (_i, [_vp, _i, _fp, _vp, _i]),
     "aefft_net_score": (_i, [_vp, _vp, _i, _fp, _fp]),
     "aefft_net_score_map": (_i, [_vp, _vp, _i, _i, _fp, _fp, _fp]),
+    "aefft_net_score_target": (_i, [_vp, _vp, _i, _vp, _i, _fp, _fp]),
+    "aefft_net_score_map_target": (_i, [_vp, _vp, _i, _vp, _i, _i, _fp, _fp, _fp]),
+    "aefft_net_ssim_map": (_i, [_vp, _vp, _i, _vp, _i, _i, _f, _fp, _fp, _fp]),
     "aefft_net_set_input_ready": (_i, [_vp, _i]),
     "aefft_net_grad_buffer": (_i, [_vp, C.POINTER(_vp), C.POINTER(C.c_size_t)]),
     "aefft_net_step_form": (_i, [_vp]),
@@ -581,6 +584,45 @@ class Net:
         if score is None:
             score = self.ctx.empty(self.B)
         self.ctx.check(self.L.aefft_net_score_map(self.h, _ptr(frames), int(_is_u8(frames)), tile, _ptr(map), _ptr(score), _ptr(recon)))
+        return map, score, recon
+
+    def score_target(self, frames, targets, score=None, recon=None):
+        """Net.score against a target (aefft_net_score_target): the net reads `frames`, score[b] = mean of (t - r)^2 with t the pixels of
+        `targets` (float32 or uint8 [B][D][Nx][Ny], on its own) -- the validation number of a net trained by step_grad_target.
+        Returns (score, recon)."""
+        if score is None:
+            score = self.ctx.empty(self.B)
+        self.ctx.check(self.L.aefft_net_score_target(self.h, _ptr(frames), int(_is_u8(frames)), _ptr(targets), int(_is_u8(targets)), _ptr(score), _ptr(recon)))
+        return score, recon
+
+    def score_map_target(self, frames, targets, tile, map=None, score=None, recon=None):
+        """Net.score_map against a target (aefft_net_score_map_target): the net reads `frames`, the map holds the block means of (t - r)^2 with
+        t the pixels of `targets` (float32 or uint8 [B][D][Nx][Ny], on its own).  Returns (map, score, recon)."""
+        tile = int(tile)
+        if map is None:
+            t = max(tile, 1)
+            map = self.ctx.empty(self.B, max(self.Nx // t, 1), max(self.Ny // t, 1))
+        if score is None:
+            score = self.ctx.empty(self.B)
+        self.ctx.check(self.L.aefft_net_score_map_target(self.h, _ptr(frames), int(_is_u8(frames)), _ptr(targets), int(_is_u8(targets)), tile,
+                                                         _ptr(map), _ptr(score), _ptr(recon)))
+        return map, score, recon
+
+    def ssim_map(self, frames, tile, targets=None, data_range=255.0, map=None, score=None, recon=None):
+        """Block SSIM of the reconstruction under the current weights (aefft_net_ssim_map): map[b][I][J] = mean over the D channels of the SSIM
+        of window (I, J) -- tile x tile pixels, uniform weights, population statistics, C1 = (0.01 L)^2, C2 = (0.03 L)^2, L = data_range --
+        between the reference (`targets`, or the frames when None) and r, the float32 reconstruction Net.infer would write.  `tile` is 8, 16, 32
+        or 64 and divides Nx and Ny.  `map` (float32 [B][Nx/tile][Ny/tile]) and `score` (float32 [B], the mean of the frame's map entries) are
+        allocated when None; `recon` (optional) receives the reconstruction from the same launch -- the spatial net and the chirp-z transforms
+        need it.  The first call of a net allocates the strip buffer.  Returns (map, score, recon)."""
+        tile = int(tile)
+        if map is None:
+            t = max(tile, 1)
+            map = self.ctx.empty(self.B, max(self.Nx // t, 1), max(self.Ny // t, 1))
+        if score is None:
+            score = self.ctx.empty(self.B)
+        self.ctx.check(self.L.aefft_net_ssim_map(self.h, _ptr(frames), int(_is_u8(frames)), _ptr(targets), int(_is_u8(targets)), tile, float(data_range),
+                                                 _ptr(map), _ptr(score), _ptr(recon)))
         return map, score, recon
 
     def decode(self, code, hidden_pair, recon):

@@ -228,7 +228,7 @@ extern "C" int aefft_prof_reset(aefft_ctx* ctx)
 }
 
 static const char* kid_names[KID_COUNT] = {"r2c_rows", "r2c_cols", "c2r_cols", "c2r_rows", "contract", "resize", "diff_mse",
-                                           "bias_grad", "pad", "shrink", "update", "gradient_diff", "spatial", "kspec", "kgrad", "weight_taps", "moment", "chain", "sgrad", "opmse", "score", "score_map", "image", "target"};
+                                           "bias_grad", "pad", "shrink", "update", "gradient_diff", "spatial", "kspec", "kgrad", "weight_taps", "moment", "chain", "sgrad", "opmse", "score", "score_map", "image", "target", "ssim"};
 
 extern "C" int aefft_prof_read(aefft_ctx* ctx, int kid, long* launches, double* total_ms, double* algo_bytes)
 {

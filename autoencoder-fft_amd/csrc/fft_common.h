@@ -163,4 +163,18 @@ template <int LMAX> __device__ __forceinline__ float score_seg_sum_rt(float v, i
     return v;
 }
 
+// SCORE 5: float reference; 6: 8-bit reference (aefft_net_ssim_map).  The epilogue of SCORE 3 / 4 with FIVE sums per strip instead of one:
+// sum x', r', x'^2, r'^2, x'r' with x' = x - pivot, r' = r - pivot (x the reference pixel `frames` holds, r the rounded reconstruction).
+// The pivot (half the data range) keeps the float sums of squares small where the window is flat; variances and the covariance do not
+// depend on it, the finish adds it back to the means.  part [5][npairs][n >> lt]: one plane per moment, each laid out as ScoreMapDev's.
+struct ScoreSsimDev { const void* frames; float* part; int lt; float pivot; };
+template <> struct ScoreParam<5> { typedef ScoreSsimDev type; };
+template <> struct ScoreParam<6> { typedef ScoreSsimDev type; };
+// one pixel's five terms, in this order
+__device__ __forceinline__ void ssim_acc(float (&m)[SSIM_MOMENTS], float x, float r, float pivot)
+{
+    const float a = x - pivot, b = r - pivot;
+    m[0] += a; m[1] += b; m[2] += a * a; m[3] += b * b; m[4] += a * b;
+}
+
 }  // namespace aefft

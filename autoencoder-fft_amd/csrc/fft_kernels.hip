@@ -266,6 +266,8 @@ __global__ __launch_bounds__(RowCfg<N>::NT) void r2c_rows_kernel(const void* __r
 // butterfly over the pair's lanes of the wave, the pair's waves in order through LDS -- no atomics, one order.  U8 is false with SCORE.
 // SCORE (3: float frames, 4: 8-bit frames; aefft_net_score_map): the same up to the lane's eight terms; the butterfly stops at a strip of
 // sc's tile (fft_common.h ScoreMapDev) and the first lane of each strip writes sc.part[pair][strip].
+// SCORE (5: float reference, 6: 8-bit reference; aefft_net_ssim_map): the mapping epilogue with five sums per strip (fft_common.h ScoreSsimDev) --
+// the same lanes, loads and segments, the butterfly run on each of the five, one plane of sc.part per moment.
 template <int N, bool SPARSE, bool U8 = false, int SCORE = 0>
 __global__ __launch_bounds__(RowCfg<N>::NT) void c2r_rows_kernel(const float2* __restrict__ mid, void* __restrict__ out_v,
                                                                    long npairs, int Wc, float scale, const typename ScoreParam<SCORE>::type sc)
@@ -280,7 +282,7 @@ __global__ __launch_bounds__(RowCfg<N>::NT) void c2r_rows_kernel(const float2* _
     tws.load(t);
     const long pair0 = (long)blockIdx.x * G;
     constexpr int NQ = G * (N / 4) / NT;                        // epilogue positions per lane (= 2 when NT = G*N/8)
-    constexpr bool SF32 = SCORE == 1 || SCORE == 3;             // the frames are floats (SCORE 2, 4: 8-bit pixels)
+    constexpr bool SF32 = SCORE == 1 || SCORE == 3 || SCORE == 5;      // the frames are floats (SCORE 2, 4, 6: 8-bit pixels)
     [[maybe_unused]] float4 fa[NQ], fb[NQ];
     [[maybe_unused]] unsigned ua[NQ], ub[NQ];
     [[maybe_unused]] auto load_frames = [&](int lv) {
@@ -379,6 +381,45 @@ __global__ __launch_bounds__(RowCfg<N>::NT) void c2r_rows_kernel(const float2* _
     // four consecutive complex elements per lane (read once, adjacent in the padded layout): their real parts are 16 bytes of row A, their
     // imaginary parts 16 bytes of row B
     const int live = npairs - pair0 < G ? (int)(npairs - pair0) : G;
+    if constexpr (SCORE >= 5) {
+        float* const orow = static_cast<float*>(out_v) + pair0 * 2 * N;      // (read under `store` only)
+        const bool store = out_v != nullptr;
+        const int lw = sc.lt - 2, ns = N >> sc.lt;            // log2 of a strip's lanes; strips of a row pair
+        const long ms = npairs * ns;                          // floats of one moment's plane
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+            const int idx = tid + q * NT;
+            const int gg = idx / (N / 4), n4 = idx % (N / 4), n = n4 * 4;
+            float m[SSIM_MOMENTS] = {0.f, 0.f, 0.f, 0.f, 0.f};
+            if (gg < live) {
+                const float2* z = s + gg * PL + pad_idx(n);
+                const float2 z0 = z[0], z1 = z[1], z2 = z[2], z3 = z[3];
+                const float4 ra = make_float4(score_px(z0.x, scale), score_px(z1.x, scale), score_px(z2.x, scale), score_px(z3.x, scale));
+                const float4 rb = make_float4(score_px(z0.y, scale), score_px(z1.y, scale), score_px(z2.y, scale), score_px(z3.y, scale));
+                float4 xa, xb;
+                if constexpr (SF32) { xa = fa[q]; xb = fb[q]; }
+                else {
+                    xa = make_float4((float)(ua[q] & 255u), (float)((ua[q] >> 8) & 255u), (float)((ua[q] >> 16) & 255u), (float)(ua[q] >> 24));
+                    xb = make_float4((float)(ub[q] & 255u), (float)((ub[q] >> 8) & 255u), (float)((ub[q] >> 16) & 255u), (float)(ub[q] >> 24));
+                }
+                ssim_acc(m, xa.x, ra.x, sc.pivot); ssim_acc(m, xa.y, ra.y, sc.pivot); ssim_acc(m, xa.z, ra.z, sc.pivot); ssim_acc(m, xa.w, ra.w, sc.pivot);
+                ssim_acc(m, xb.x, rb.x, sc.pivot); ssim_acc(m, xb.y, rb.y, sc.pivot); ssim_acc(m, xb.z, rb.z, sc.pivot); ssim_acc(m, xb.w, rb.w, sc.pivot);
+                if (store) {
+                    st_stream(reinterpret_cast<float4*>(orow + (gg * 2) * N + n), ra);
+                    st_stream(reinterpret_cast<float4*>(orow + (gg * 2 + 1) * N + n), rb);
+                }
+            }
+            // (the segments are those of SCORE 3 / 4: a strip's tile/4 positions in consecutive lanes of one q)
+            const bool first = (n4 & ((1 << lw) - 1)) == 0 && gg < live;
+            float* const dst = sc.part + (pair0 + gg) * ns + (n4 >> lw);
+#pragma unroll
+            for (int k = 0; k < SSIM_MOMENTS; ++k) {
+                const float v = score_seg_sum_rt<4>(m[k], lw);
+                if (first) dst[k * ms] = v;
+            }
+        }
+        return;
+    }
     if constexpr (SCORE != 0) {
         float* const orow = static_cast<float*>(out_v) + pair0 * 2 * N;      // (read under `store` only)
         const bool store = out_v != nullptr;
@@ -732,6 +773,10 @@ template <int N, bool SPARSE> static hipError_t run_c2r_rows_sp(const float2* mi
         if (score->tile) {
             const int lt = score_tile_log2(score->tile);
             if (out_u8 || !score->frames || !score->strips || lt < 0 || N % score->tile) return hipErrorInvalidValue;
+            if (score->ssim) {
+                const ScoreSsimDev ss{score->frames, score->strips, lt, score->pivot};
+                return score->u8 ? run_c2r_rows_as<N, SPARSE, false, 6>(mid, out, npairs, Wc, scale, st, ss) : run_c2r_rows_as<N, SPARSE, false, 5>(mid, out, npairs, Wc, scale, st, ss);
+            }
             const ScoreMapDev sm{score->frames, score->strips, lt};
             return score->u8 ? run_c2r_rows_as<N, SPARSE, false, 4>(mid, out, npairs, Wc, scale, st, sm) : run_c2r_rows_as<N, SPARSE, false, 3>(mid, out, npairs, Wc, scale, st, sm);
         }

@@ -206,6 +206,7 @@ __global__ __launch_bounds__(MixRowCfg<T>::NT) void mix_r2c_rows_kernel(const vo
 // rounded product, r stored as well when `out` is non-null -- and the pair's sum is reduced across its T threads: the lane's terms in order, a
 // butterfly over the pair's lanes of the wave, the pair's waves in order through LDS.  One float per row pair to sc.part.
 // SCORE (3: float frames, 4: 8-bit frames; aefft_net_score_map): one float per STRIP of sc's tile (fft_common.h ScoreMapDev) instead.
+// SCORE (5: float reference, 6: 8-bit reference; aefft_net_ssim_map): five sums per strip (fft_common.h ScoreSsimDev), one plane of sc.part each.
 template <int T, bool U8 = false, int SCORE = 0>
 __global__ __launch_bounds__(MixRowCfg<T>::NT) void mix_c2r_rows_kernel(const float2* __restrict__ mid, void* __restrict__ out, long npairs,
                                                                          int Wc, float scale, const MixPlan pl, const typename ScoreParam<SCORE>::type sc)
@@ -235,7 +236,7 @@ __global__ __launch_bounds__(MixRowCfg<T>::NT) void mix_c2r_rows_kernel(const fl
         }
     }
     constexpr int NJ = 4;                                           // element pairs of a row per thread: H <= 4 T
-    constexpr bool SF32 = SCORE == 1 || SCORE == 3;                 // the frames are floats (SCORE 2, 4: 8-bit pixels)
+    constexpr bool SF32 = SCORE == 1 || SCORE == 3 || SCORE == 5;   // the frames are floats (SCORE 2, 4, 6: 8-bit pixels)
     [[maybe_unused]] float2 fa[NJ], fb[NJ];
     [[maybe_unused]] unsigned ua[NJ], ub[NJ];
     if constexpr (SCORE != 0) {
@@ -257,6 +258,40 @@ __global__ __launch_bounds__(MixRowCfg<T>::NT) void mix_c2r_rows_kernel(const fl
     __syncthreads();
     mix_fft<T, +1>(s + g * PL, t, pl);
 
+    if constexpr (SCORE >= 5) {
+        // SCORE 3 / 4's segments (below) with five sums per strip
+        float2* const o = static_cast<float2*>(out);
+        const bool store = out != nullptr;
+        const float2* z = s + g * PL;
+        const int lw = sc.lt - 1, ns = N >> sc.lt;                  // log2 of a strip's lanes; strips of a row pair
+        const long ms = npairs * ns;                                // floats of one moment's plane
+        float* const prow = sc.part + (pair0 + g) * ns;
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            const int c = t + j * T;
+            float m[SSIM_MOMENTS] = {0.f, 0.f, 0.f, 0.f, 0.f};
+            if (g < live && c < H) {
+                const float2 z0 = z[pad_idx(2 * c)], z1 = z[pad_idx(2 * c + 1)];
+                const float2 ra = make_float2(score_px(z0.x, scale), score_px(z1.x, scale)), rb = make_float2(score_px(z0.y, scale), score_px(z1.y, scale));
+                float2 xa, xb;
+                if constexpr (SF32) { xa = fa[j]; xb = fb[j]; }
+                else { xa = make_float2((float)(ua[j] & 255u), (float)(ua[j] >> 8)); xb = make_float2((float)(ub[j] & 255u), (float)(ub[j] >> 8)); }
+                ssim_acc(m, xa.x, ra.x, sc.pivot); ssim_acc(m, xa.y, ra.y, sc.pivot); ssim_acc(m, xb.x, rb.x, sc.pivot); ssim_acc(m, xb.y, rb.y, sc.pivot);
+                if (store) {
+                    const long ra_i = (pair0 + g) * 2 * H + c;
+                    st_stream(&o[ra_i], ra);
+                    st_stream(&o[ra_i + H], rb);
+                }
+            }
+            const bool first = (t & ((1 << lw) - 1)) == 0 && g < live && c < H;
+#pragma unroll
+            for (int k = 0; k < SSIM_MOMENTS; ++k) {
+                const float v = score_seg_sum_rt<5>(m[k], lw);
+                if (first) prow[k * ms + (c >> lw)] = v;
+            }
+        }
+        return;
+    }
     if constexpr (SCORE >= 3) {
         // the map: element pair e = t + j T is two columns of both rows; a strip is tile/2 consecutive element pairs, i.e. for a FIXED j an aligned
         // segment of tile/2 lanes (T is a power of two, and T >= tile/2 for every smooth n a tile divides; the launcher checks) -- a butterfly
@@ -557,6 +592,12 @@ template <int T> static hipError_t run_mix_c2r_rows(const float2* mid, void* out
             // (T >= tile/2: a strip's element pairs are lanes of ONE row pair.  Every smooth n a tile divides has it; n = 64, 128 with tile 64 would
             // not, and reaches the power-of-two pass instead: a net's pooled grids are >= 8, so its packed width is a power of two >= 4)
             if (u8 || !score->frames || !score->strips || lt < 0 || pl.n % score->tile || score->tile / 2 > T) return hipErrorInvalidValue;
+            if (score->ssim) {
+                const ScoreSsimDev ss{score->frames, score->strips, lt, score->pivot};
+                if (score->u8) mix_c2r_rows_kernel<T, false, 6><<<dim3((unsigned)blocks), dim3(Cfg::NT), lds, st>>>(mid, out, npairs, Wc, scale, pl, ss);
+                else mix_c2r_rows_kernel<T, false, 5><<<dim3((unsigned)blocks), dim3(Cfg::NT), lds, st>>>(mid, out, npairs, Wc, scale, pl, ss);
+                return hipGetLastError();
+            }
             const ScoreMapDev sm{score->frames, score->strips, lt};
             if (score->u8) mix_c2r_rows_kernel<T, false, 4><<<dim3((unsigned)blocks), dim3(Cfg::NT), lds, st>>>(mid, out, npairs, Wc, scale, pl, sm);
             else mix_c2r_rows_kernel<T, false, 3><<<dim3((unsigned)blocks), dim3(Cfg::NT), lds, st>>>(mid, out, npairs, Wc, scale, pl, sm);

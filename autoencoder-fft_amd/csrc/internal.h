@@ -39,7 +39,11 @@ struct OpIn { const float2* A; const float2* Xf; int D0, Nx0, Ny0; };
 // rounded product the float row pass stores.  `out` (float, not out_u8) is then optional: non-null, it receives r as without `score`.
 // tile (0: none; 8, 16, 32 or 64, dividing Nx and Ny; aefft_net_score_map): the row pass stops its reduction at a STRIP -- two rows x tile
 // columns of one channel -- and strips [planes*Nx/2][Ny/tile] receives one float per strip; `part` is then not written.
-struct ScoreArg { const void* frames; bool u8; float* part; int tile = 0; float* strips = nullptr; };
+// ssim (with a tile; aefft_net_ssim_map): FIVE floats per strip instead of one -- the sums of x', r', x'^2, r'^2, x'r' over the strip, x' = x - pivot,
+// r' = r - pivot -- and strips is [SSIM_MOMENTS][planes*Nx/2][Ny/tile], one plane per moment.
+// `frames` is whatever the reconstruction is compared with: the frames the net read, or a target of the same shape (the _target calls).
+struct ScoreArg { const void* frames; bool u8; float* part; int tile = 0; float* strips = nullptr; bool ssim = false; float pivot = 0.f; };
+constexpr int SSIM_MOMENTS = 5;
 inline int score_tile_log2(int tile) { return tile == 8 ? 3 : tile == 16 ? 4 : tile == 32 ? 5 : tile == 64 ? 6 : -1; }
 hipError_t launch_c2r(const float2* in, void* out, float2* mid, long planes, int Nxi, int Nyi,
                       int Nx, int Ny, float scale, hipStream_t st, const OpIn* opin = nullptr, bool out_u8 = false, const ScoreArg* score = nullptr);
@@ -53,6 +57,11 @@ hipError_t launch_score_finish(const float* part, float* score, int B, long npf,
 hipError_t launch_score_map_diff(const void* frames, bool u8, const float* recon, float* strips, long npairs, int n, int tile, hipStream_t st);
 // map[b][I][J] = sum over d < D and the tile/2 row pairs of tile row I of strips[((b D + d) Nx/2 + I tile/2 + p)][J], in double, / (D tile tile)
 hipError_t launch_score_map_finish(const float* strips, float* map, int B, int D, int Nx, int Ny, int tile, hipStream_t st);
+// ---- ssim_kernels.hip (aefft_net_ssim_map) ----
+// The five strip sums of launch_c2r's ScoreArg (ssim) from a STORED float reconstruction: strips [SSIM_MOMENTS][npairs][n/tile]
+hipError_t launch_ssim_diff(const void* ref, bool u8, const float* recon, float* strips, long npairs, int n, int tile, float pivot, hipStream_t st);
+// map[b][I][J] = mean over d < D of the window's SSIM, from its tile/2 strips of each moment added in double (ssim_kernels.hip ssim_finish_kernel)
+hipError_t launch_ssim_finish(const float* strips, float* map, int B, int D, int Nx, int Ny, int tile, float data_range, float pivot, hipStream_t st);
 // ---- image_kernels.hip (aefft_image_to_frames / aefft_frames_to_image) ----
 // ImageToSpin_C / SpinToImage_C for a batch: image = B images of Ny rows of `pitch` bytes, pixel (row j, column i) channel d at j pitch + i D + d;
 // frames [B][D][Nx][Ny], float when f32, unsigned char otherwise: frames[b][d][i][j] = image[b][j][i][d] (float frames -> pixels by px_u8).

@@ -72,6 +72,7 @@ struct aefft_net {
     // per-frame reconstruction error (aefft_net_score)
     float* score_part = nullptr; // [B][(D*Nx + 1)/2] one partial sum of squared differences per ROW PAIR of a frame (the row passes' scoring epilogue, score_diff_kernel)
     float* map_part = nullptr;   // [B*D*Nx/2][Ny/tile] one float per STRIP (two rows x tile columns of a channel; aefft_net_score_map), sized for tile 8
+    float* ssim_part = nullptr;  // [5][B*D*Nx/2][Ny/tile] five floats per strip (aefft_net_ssim_map), sized for tile 8: allocated by the net's first SSIM call
     float2* Wp = nullptr;      // [Pc][packE] bin-major copy of the kernel spectra the coarsest-grid chain items read (kspec_packed_kernel)
     aefft::PackArgs pack{};    // its description (static per net)
     bool packed_valid = false; // Wp belongs to the CURRENT weights (weights_changed)

@@ -124,6 +124,10 @@ int aefft::do_c2r(aefft_ctx* ctx, const float2* X, void* x, long planes, int Nxi
         RET_IF(do_c2r_any(ctx, X, static_cast<float*>(x), planes, Nxi, Nyi, Nx, Ny, scale));
         if (!score) return AEFFT_OK;
         // (planes * Nx rows taken two at a time: Nx is even, so the pairs are the row pass's)
+        if (score->tile && score->ssim)
+            return launch_or_fail(ctx, KID_SSIM, (double)planes * Nx * Ny * (score->u8 ? 5.0 : 8.0), "ssim_diff", [&] {
+                return launch_ssim_diff(score->frames, score->u8, static_cast<const float*>(x), score->strips, planes * Nx / 2, Ny, score->tile, score->pivot, ctx->cur);
+            });
         if (score->tile)
             return launch_or_fail(ctx, KID_SCORE_MAP, (double)planes * Nx * Ny * (score->u8 ? 5.0 : 8.0), "score_map_diff", [&] {
                 return launch_score_map_diff(score->frames, score->u8, static_cast<const float*>(x), score->strips, planes * Nx / 2, Ny, score->tile, ctx->cur);
@@ -137,7 +141,7 @@ int aefft::do_c2r(aefft_ctx* ctx, const float2* X, void* x, long planes, int Nxi
     RET_IF(ws_get(ctx, ws_id, sizeof(float2) * fft_mid_elems(planes, Nx, Nyi / 2), &mid));
     const double b_in = (double)planes * bins(Nxi, Nyi) * 8, b_mid = (double)planes * Nx * (Nyi / 2) * 8;
     // (the scoring row pass reads the frames, writes one float per row pair, and the rows only when they were asked for)
-    const double b_out = (double)planes * Nx * Ny * (out_u8 ? 1 : (x ? 4 : 0)) + (score ? (double)planes * Nx * Ny * (score->u8 ? 1 : 4) + (double)planes * Nx * 2 * (score->tile ? Ny / score->tile : 1) : 0.0);
+    const double b_out = (double)planes * Nx * Ny * (out_u8 ? 1 : (x ? 4 : 0)) + (score ? (double)planes * Nx * Ny * (score->u8 ? 1 : 4) + (double)planes * Nx * 2 * (score->tile ? Ny / score->tile : 1) * (score->ssim ? SSIM_MOMENTS : 1) : 0.0);
     hipError_t e;
     {
         Bracket br(ctx, KID_C2R_COLS, b_in + b_mid);

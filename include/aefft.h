@@ -388,8 +388,8 @@ int aefft_net_forward_u8(aefft_net* net, const unsigned char* frames_d, float* r
  * aefft_net_set_input_ready and the multiobjective buffers are allocated on first use): it must not be made under stream capture.  Later
  * calls allocate nothing and do not synchronise.
  * AEFFT_EINVAL, with nothing enqueued: a null net, null frames or null targets; a pointer not 16-byte aligned; a spatial net; D > 4 (frames
- * are images: grey, BGR, BGRA).  Not offered: targets for aefft_net_train_pair bursts (backprop_fft of the vector API takes expout), for
- * aefft_net_score / _score_map, and for pairs l >= 1. */
+ * are images: grey, BGR, BGRA).  Not offered: targets for aefft_net_train_pair bursts (backprop_fft of the vector API takes expout) and for
+ * pairs l >= 1.  (Judging such a net: aefft_net_score_target, aefft_net_score_map_target, aefft_net_ssim_map.) */
 int aefft_net_step_grad_target(aefft_net* net, const void* frames_d, int frames_u8, const void* targets_d, int targets_u8, float* recon_d /* nullable */);
 /* Frozen-weight inference over a batch -- the application's display loop (ImageToSpin_C, autoenc_fft, SpinToImage_C on every camera frame,
  * netlib.cpp:37-77, autoencoder.cpp:218-227): the reconstruction (layers.back() of autoenc_fft) and optionally ONE hidden layer, from the
@@ -466,6 +466,53 @@ int aefft_net_score(aefft_net* net, const void* frames_d, int frames_u8, float* 
  * frames_u8 on a spatial net; recon_d == NULL on one of the routes just named (the message says why).  The outputs are then untouched. */
 int aefft_net_score_map(aefft_net* net, const void* frames_d, int frames_u8, int tile, float* map_d, float* score_d /* nullable */,
                         float* recon_d /* nullable */);
+/* aefft_net_score and aefft_net_score_map against a TARGET -- the validation numbers of a net trained by aefft_net_step_grad_target (a
+ * denoiser is judged against the clean frame, not against its noisy input).  They are exactly the two calls above with x replaced by the
+ * target's pixels t_b[d][i][j] in (x - r)^2: the net still reads frames_d, the inverse row pass loads targets_d for the comparison.  frames_d
+ * and targets_d are [B][D][Nx][Ny], each float, or unsigned char when its _u8 flag is set -- each on its own, as in
+ * aefft_net_step_grad_target.  With targets_d == frames_d (and equal flags) they give the bits of the plain calls.
+ * Everything else is that of the plain calls: form, operator caches, state, launch counts (no new kernel, no further launch), ordering,
+ * determinism, training left bit for bit undisturbed, no allocation, and the routes that need recon_d.  A spatial net takes float frames and
+ * float targets only.  The PSNR follows from score_d: 10 log10(L^2 / score_d[b]) with L the data range (255 for 8-bit images).
+ * AEFFT_EINVAL, with the outputs untouched: what the plain calls refuse, and a null or misaligned targets_d. */
+int aefft_net_score_target(aefft_net* net, const void* frames_d, int frames_u8, const void* targets_d, int targets_u8, float* score_d,
+                           float* recon_d /* nullable */);
+int aefft_net_score_map_target(aefft_net* net, const void* frames_d, int frames_u8, const void* targets_d, int targets_u8, int tile, float* map_d,
+                               float* score_d /* nullable */, float* recon_d /* nullable */);
+/* Block SSIM of the reconstruction under the CURRENT (frozen) weights -- the structural similarity index over non-overlapping windows, the
+ * second number restoration quality is quoted in.  With
+ *   x the reference pixels: the target, or the frame when targets_d == NULL (8-bit pixels converted exactly);
+ *   r the ROUNDED float reconstruction, exactly the r of aefft_net_score;
+ *   t = tile, one of 8, 16, 32, 64, which must divide both Nx and Ny, and n = t*t;
+ *   L = data_range > 0 (255 for 8-bit images);
+ * for every channel d and window (I, J) -- rows [I t, I t + t), columns [J t, J t + t) -- with uniform weights and population statistics:
+ *     mx = sum x / n,  mr = sum r / n,  vx = max(sum x^2 / n - mx^2, 0),  vr = max(sum r^2 / n - mr^2, 0),  c = sum x r / n - mx mr
+ *     C1 = (0.01 L)^2,  C2 = (0.03 L)^2
+ *     ssim = (2 mx mr + C1)(2 c + C2) / ((mx^2 + mr^2 + C1)(vx + vr + C2))
+ * map_d[b][I][J], float [B][Nx/t][Ny/t], is the mean over d < D of ssim.  score_d (nullable) [B] float is the mean of the frame's map entries,
+ * taken from the floats as stored, added in double and rounded once -- a function of the map.  recon_d (nullable) float [B][D][Nx][Ny]
+ * receives the float reconstruction, bit for bit what aefft_net_infer writes, from the same launch.  frames_d and targets_d are
+ * [B][D][Nx][Ny], each float, or unsigned char when its _u8 flag is set (targets_u8 is ignored with targets_d == NULL).  All pointers 16-byte
+ * aligned.
+ * The mapping epilogue of the inverse row pass with five sums per STRIP (two rows x t columns of one channel) where the error map keeps one:
+ * sum x', r', x'^2, r'^2, x'r' with x' = x - L/2, r' = r - L/2 -- the pivot keeps the float sums of squares small where a window is flat;
+ * variances and the covariance do not depend on it, the finish adds it back to the means.  Each sum: the lane's terms in order, then a
+ * butterfly over the strip's lanes of the wave.  ssim_finish_kernel then adds, per channel, the window's t/2 strips of each moment in double,
+ * evaluates the formula in double, adds the channels in order, scales by 1/D and rounds once.  There are no atomics: the same inputs give
+ * the same bits, and a frame's map does not depend on the other frames of the batch.
+ * Form, operator caches, state and ordering are exactly those of aefft_net_score_map: the form aefft_net_step_form reports; in the chain form
+ * with the operators at hand five launches (the input transform's two, the inverse column pass with the operator on load, the SSIM row
+ * pass, the finish), six with score_d; a pending aefft_net_step_grad is ended (aefft_net_step_apply then fails with AEFFT_ESTATE);
+ * aefft_net_get_layer(s) afterwards export the layers of this call; training is left bit for bit undisturbed; the context stream only, no
+ * host synchronisation.  The FIRST SSIM call of a net allocates its strip buffer (5 B*D*Nx*Ny/16 floats, as the first target step allocates
+ * its workspaces): it must not be made under stream capture.  Later calls allocate nothing and do not synchronise.
+ * The spatial net (float frames and float targets only) and smooth grids under AEFFT_F_CHIRPZ form the same strips from the STORED
+ * reconstruction in a launch of their own: they need recon_d.
+ * AEFFT_EINVAL: null net, frames or map_d; a pointer not 16-byte aligned; a tile that is not 8, 16, 32 or 64 or does not divide Nx and Ny;
+ * a data_range that is not finite or not greater than 0; an 8-bit argument on a spatial net; recon_d == NULL on one of the routes just named
+ * (the message says why).  The outputs are then untouched. */
+int aefft_net_ssim_map(aefft_net* net, const void* frames_d, int frames_u8, const void* targets_d /* nullable: the frames */, int targets_u8,
+                       int tile, float data_range, float* map_d, float* score_d /* nullable */, float* recon_d /* nullable */);
 /* Decode: the reconstruction from a STORED hidden layer -- the other half of aefft_net_infer(hidden_pair = l, hidden_d).  code_d
  * [B][dM_l][Nx_l][Ny_l] float, l = hidden_pair: layer 2l+2 in coordinate space, shape and layout as aefft_net_infer writes hidden_d (stored,
  * transmitted or edited since: it need not be an encoder output).  recon_d [B][D][Nx][Ny] float, or unsigned char when recon_u8 under
