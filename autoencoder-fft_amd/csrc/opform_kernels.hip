@@ -1421,8 +1421,9 @@ __device__ __forceinline__ void chain_item_run(const ChainArgs& g, const int t, 
         }
     }
 #if defined(AEFFT_X_WGTIME) && AEFFT_X_WGTIME
+    // (the static steps take no stage stamps: their items leave the start and end stamps of the workgroup alone, and 0 = "not taken" here)
     if (threadIdx.x == 0 && g_wgtime && blockIdx.x < WGT_MAX)
-        for (int k = 0; k < 8; ++k) g_wgtime[(size_t)5 * WGT_MAX * 2 + ((size_t)4 * WGT_MAX + blockIdx.x) * 8 + k] = reinterpret_cast<unsigned long long*>(Wl + 5 * CH_VMAX * OPC + 4 + OPC * OPC)[k];
+        for (int k = 0; k < 8; ++k) g_wgtime[(size_t)5 * WGT_MAX * 2 + ((size_t)4 * WGT_MAX + blockIdx.x) * 8 + k] = SIG > 0 ? 0ull : reinterpret_cast<unsigned long long*>(Wl + 5 * CH_VMAX * OPC + 4 + OPC * OPC)[k];
 #endif
 }
 // (ONE instantiation per kernel: two inlined copies of the straight-line steps in one kernel spill)
@@ -1594,14 +1595,22 @@ hipError_t launch_chain(ChainArgs& g, hipStream_t st, hipEvent_t done)
 #ifndef AEFFT_X_TAIL_W
 #define AEFFT_X_TAIL_W 6
 #endif
-// (with the fused MSE the items carry a second set of sums: 5 waves per SIMD, 96 registers -- at 6 the back end spills 20 bytes; cfg5 82.6-84 vs 82 us)
-#ifndef AEFFT_X_TAIL_WF
-#define AEFFT_X_TAIL_WF 5
+// (with the fused MSE the items carry a second set of sums.  The GENERIC fused kernel stays at 5 waves per SIMD: 90 registers, and at 6 the back end
+// spills 20 bytes; cfg5 82.6-84 vs 82 us.  The fused kernels of the static tables fit 6 without scratch -- 78 registers for the four-pair table, 80 for
+// the five-pair one, against 87 at 5 -- and their items' 20.9 KB of LDS fit six times into a CU.  The four-pair table takes 6: cfg3-P2's fused tail
+// 20.2 -> 19.2 us under the kernel trace.  The five-pair table stays at 5: at 6 cfg5's tail read 66.7 against 65.7 us and its step 0.802 against
+// 0.800 ms, three interleaved runs each -- 20 % more slots bought nothing there.  AEFFT_X_TAIL_WF, where given, holds for all of them.)
+#ifdef AEFFT_X_TAIL_WF
+constexpr int TAIL_WF = AEFFT_X_TAIL_WF, TAIL_WF_STATIC4 = AEFFT_X_TAIL_WF;
+#else
+constexpr int TAIL_WF = 5, TAIL_WF_STATIC4 = 6;
 #endif
+// workgroups per CU that tail_kernel<LEAN, FUSE, SIG> is compiled for (its second launch bound)
+constexpr int tail_residency(bool lean, bool fuse, int sig) { return !lean ? 4 : !fuse ? AEFFT_X_TAIL_W : sig == 1 ? TAIL_WF_STATIC4 : TAIL_WF; }
 // SIG: the static step table of the launch's net (ChainTable; 0: none).  Every table is a kernel of its own: each then holds ONE copy of the items'
 // straight-line steps and one of the packed MSE's, as the generic kernel does (a second copy in one kernel spills).
 template <bool LEAN, bool FUSE, int SIG = 0>
-__global__ __launch_bounds__(256, LEAN ? (FUSE ? AEFFT_X_TAIL_WF : AEFFT_X_TAIL_W) : 4) void tail_kernel(const OpMseGroup g, const ChainArgs ch, const UpdateGroup ug, const int nchain, const int nupd_start)
+__global__ __launch_bounds__(256, tail_residency(LEAN, FUSE, SIG)) void tail_kernel(const OpMseGroup g, const ChainArgs ch, const UpdateGroup ug, const int nchain, const int nupd_start)
 {
     AEFFT_WGTIME(4);
     extern __shared__ float2 sh[];
@@ -1648,9 +1657,24 @@ hipError_t launch_opmse_group(OpMseGroup& g, hipStream_t st, ChainArgs* chain, c
                 g.q[g.n - 1].dD <= CH_VMAX && g.q[g.n - 1].dM <= CH_VMAX && g.q[g.n - 1].dD <= 256;
     if (chain) { const hipError_t e = chain_geometry(*chain, &nchain, &lds_c, &fuse, (unsigned)g.offC, (unsigned)g.offF); if (e != hipSuccess) return e; }
     { const hipError_t e = opmse_geometry(g, (int)nchain, &nmse, &lds_m, false); if (e != hipSuccess) return e; }
-    // ... where the launch is bound by its resident slots (cfg5: 11 000 workgroups, tail 89 -> 82 us).  Where the items themselves are the launch's
-    // long pole (cfg3-P2: 3 634 workgroups) the two wider stages lengthen it: 23.9 -> 26.1 us.
-    if (fuse && nchain + nmse < 4 * 1536 && !flag(AEFFT_F_CHAINMSE)) {
+#ifndef AEFFT_X_LEANTAIL
+#define AEFFT_X_LEANTAIL 1
+#endif
+    bool lean = AEFFT_X_LEANTAIL != 0;
+    for (int i = 0; i < g.n && lean; ++i) lean = g.q[i].G != nullptr || (i == g.n - 1 && g.Wp != nullptr);      // (after opmse_geometry: Wp is null unless the innermost pair goes packed)
+    // From which size on the fused MSE pays depends on the kernel the launch will run.
+    //  * The generic fused kernel (90 registers, 5 waves per SIMD): where the launch is bound by its resident slots (cfg5: 11 000 workgroups, tail
+    //    89 -> 82 us).  Where the items themselves are the launch's long pole (cfg3-P2: 3 634 workgroups) the two wider stages lengthen it: 23.9 ->
+    //    26.1 us.  Hence four rounds of the 1 536 slots.
+    //  * A fused STATIC table (the four-pair net's: 78 registers, 6 waves per SIMD, as many slots as the unfused kernel has): as soon as the unfused launch needs a
+    //    second round of slots.  Measured at cfg3-P2 (2 456 + 266 workgroups unfused, 1 912 + 266 fused; one MI355X, interleaved): tail 20.6 -> 18.7 us
+    //    under the kernel trace, step 142.3 (141.9-143.3) -> 139.6 (139.0-140.3) us over five plain bench runs each; the fused item runs 14-15 us
+    //    against 9-10 and the launch still starts its last workgroups at 14 of 18.4 us.  Within ONE round the fused items would
+    //    only lengthen the pole, so such launches stay unfused -- by that arithmetic, not by a measurement.  cfg5 fuses under either rule; cfg2's net has
+    //    no fused table.
+    const bool fused_table = fuse && lean && AEFFT_X_CHAINPIPE && !flag(AEFFT_F_NOSTATICCHAIN) && tail_table_of<true>(*chain, g) != 0;
+    const long fuse_from = fused_table ? 1536 + 1 : 4 * 1536;
+    if (fuse && nchain + nmse < fuse_from && !flag(AEFFT_F_CHAINMSE)) {
         fuse = false;
         for (int i = 0; i < chain->st_n; ++i) chain->st_off[i] &= ~(1u << 30);
         const hipError_t e = chain_geometry(*chain, &nchain, &lds_c); if (e != hipSuccess) return e;      // (the items' LDS without the MSE's vectors)
@@ -1667,11 +1691,6 @@ hipError_t launch_opmse_group(OpMseGroup& g, hipStream_t st, ChainArgs* chain, c
         ug.start[ug.n] = nupd;
     }
     const size_t lds = std::max(lds_c, lds_m);
-#ifndef AEFFT_X_LEANTAIL
-#define AEFFT_X_LEANTAIL 1
-#endif
-    bool lean = AEFFT_X_LEANTAIL != 0;
-    for (int i = 0; i < g.n && lean; ++i) lean = g.q[i].G != nullptr || (i == g.n - 1 && g.Wp != nullptr);      // (after opmse_geometry: Wp is null unless the innermost pair goes packed)
     const long total = nchain + nmse + nupd;
     if (total >= (1L << 31)) return hipErrorInvalidValue;
     auto go = [&](auto LEANT, auto FUSET, auto SIGT) -> hipError_t {
@@ -1686,9 +1705,8 @@ hipError_t launch_opmse_group(OpMseGroup& g, hipStream_t st, ChainArgs* chain, c
     };
     // the static route: a lean launch whose chain items and packed MSE run exactly the step lists of one of the tables
     int sig = 0;
-#if !(defined(AEFFT_X_WGTIME) && AEFFT_X_WGTIME)      // (the stage stamps of the experiment build live in the generic step code)
+    // (the experiment build with the workgroup clocks runs it too, with the start and end stamps only: the stage stamps live in the generic step code)
     if (lean && chain && AEFFT_X_CHAINPIPE && !flag(AEFFT_F_NOSTATICCHAIN)) sig = fuse ? tail_table_of<true>(*chain, g) : tail_table_of<false>(*chain, g);
-#endif
     if (route) *route = sig ? AEFFT_TAIL_STATIC : AEFFT_TAIL_GENERIC;
     auto sigs = [&](auto FUSET) -> hipError_t {
         switch (sig) {

@@ -92,7 +92,8 @@ enum {
     AEFFT_F_NOLAZYMSE = 1 << 21,   /* aefft_net_step_apply(mse_d = NULL) still sums the MSE slots in a launch of its own instead of leaving them to the next step's gradient launch */
     AEFFT_F_SMALLOVERLAP = 1 << 22, /* reconstructions below 8 MB take the side stream as well (the test suite's small nets then run the two-stream path of the large ones) */
     AEFFT_F_CHAINMSE = 1 << 23,    /* operator form with the chain: the innermost pair's post-update MSE inside the chain's per-bin items whatever the launch's size
-                                   * (by default only in launches of more than ~6 000 workgroups, which are bound by their resident slots) */
+                                   * (by default only in launches of more than ~6 000 workgroups, which are bound by their resident slots -- and, for the
+                                   * net 3 -> 8,16,32,64 with its fused kernel compiled from a static table, in launches of more than one round of 1 536) */
     AEFFT_F_CHIRPZ = 1 << 24,      /* grids with a smooth axis, both axes up to 1024, through Bluestein's chirp-z transforms instead of the mixed-radix ones (the two
                                    * paths compared; power-of-two grids never take the mixed-radix passes) */
     AEFFT_F_NOPRUNESMOOTH = 1 << 25 /* grids with a smooth axis: kernel spectra and weight gradients by pad + full R2C / full C2R + shrink instead of the

@@ -28,11 +28,17 @@ ctx.sync()
 raw = buf.cpu().numpy().astype(np.float64) / 100.0                                  # microseconds (100 MHz)
 t = raw[:NS * WMAX * 2].reshape(NS, WMAX, 2)
 st = raw[NS * WMAX * 2:].reshape(NS, WMAX, 8)                                        # stage stamps (0 = not taken)
+if os.environ.get("WGT_DUMP"): np.save(os.environ["WGT_DUMP"], t)                    # (the start / end stamps as they are, for a closer look)
 for k, name in enumerate(("msgrad", "kgrad", "wgrad_taps", "kspec", "tail")):
     a = t[k]; live = a[:, 1] > 0; n = int(live.sum())
     if not n: print(name, "no data"); continue
     a = a[:n]; t0 = a[:, 0].min(); span = a[:, 1].max() - t0
     print(f"{name}: {n} workgroups recorded (of the launch's first {WMAX}), span {span:.1f} us; first start -> bucket [start median, duration median / max, last end]")
+    # pole or round: the longest workgroup against the span, and how late the last workgroup starts (a launch that ends on a slot round starts
+    # workgroups until shortly before its end; one that ends on a pole has started them all long before)
+    dur = a[:, 1] - a[:, 0]; lp = int(dur.argmax()); ls = int(a[:, 0].argmax()); le = int(a[:, 1].argmax())
+    print(f"   longest workgroup: wg {lp}, {dur[lp]:.1f} us, start {a[lp,0]-t0:.1f} end {a[lp,1]-t0:.1f};  last to start: wg {ls} at {a[ls,0]-t0:.1f} (runs {dur[ls]:.1f});  "
+          f"last to end: wg {le}, start {a[le,0]-t0:.1f} dur {dur[le]:.1f};  workgroups starting after the first {span/2:.1f} us: {int((a[:,0]-t0 > span/2).sum())}")
     nb = 16
     for b in range(nb):
         sl = a[b * n // nb:(b + 1) * n // nb]
