@@ -75,6 +75,7 @@ SIGNATURES = {
     "aefft_step_spatial": (_i, [_vp] + [_fp] * 15 + [_i] * 7 + [_f, _f, _i, _i]),
     "aefft_image_to_frames": (_i, [_vp, _vp, C.c_size_t, _vp, _i, _i, _i, _i, _i]),
     "aefft_frames_to_image": (_i, [_vp, _vp, _i, _vp, C.c_size_t, _i, _i, _i, _i]),
+    "aefft_image_resize_to_frames": (_i, [_vp, _vp, C.c_size_t, C.c_size_t, _i, _i, _i, _vp, _i, _i, _i, _i, _i]),
     "aefft_net_create": (_i, [_vp, C.POINTER(NetDesc), C.POINTER(_vp)]),
     "aefft_net_create_ex": (_i, [_vp, C.POINTER(NetDesc), C.c_uint, C.POINTER(_vp)]),
     "aefft_net_destroy": (None, [_vp]),
@@ -205,6 +206,28 @@ def _image_layout(image, what):
         raise ValueError(f"{what}: the image must be contiguous or a row-padded view (stride(-1) == 1, stride(-2) == D, stride(-3) = pitch >= Nx * D, "
                          f"stride(0) == Ny * pitch); got shape {tuple(image.shape)} with strides {tuple(image.stride())}")
     return img, int(pitch)
+
+
+RESIZE_MODES = {"linear": 0, "area": 1}      # AEFFT_RESIZE_LINEAR, AEFFT_RESIZE_AREA
+
+
+def _resize_layout(image, what):
+    """(the image as [B][H][W][D], pitch, image stride in bytes) of a uint8 tensor [B][H][W][D] or [H][W][D] of interleaved image rows as
+    aefft_image_resize_to_frames takes them: stride(-1) == 1, stride(-2) == D, stride(-3) = pitch >= W * D and ANY batch stride of at least
+    (H - 1) * pitch + W * D -- contiguous, row-padded, or a region of interest big[:, y0:y1, x0:x1] of a larger batch"""
+    if image.dtype != torch.uint8 or image.dim() not in (3, 4):
+        raise ValueError(f"{what}: the image must be a uint8 tensor [B][H][W][D] or [H][W][D]")
+    img = image if image.dim() == 4 else image.unsqueeze(0)
+    B, H, W, D = img.shape
+    sb, sy, sx, sd = img.stride()
+    if min(B, H, W, D) < 1:
+        raise ValueError(f"{what}: empty image of shape {tuple(image.shape)}")
+    pitch = sy if H > 1 else W * D
+    extent = (H - 1) * pitch + W * D
+    if (D > 1 and sd != 1) or (W > 1 and sx != D) or pitch < W * D or (B > 1 and sb < extent):
+        raise ValueError(f"{what}: the image must have stride(-1) == 1, stride(-2) == D, stride(-3) = pitch >= W * D and a batch stride of at least "
+                         f"(H - 1) * pitch + W * D; got shape {tuple(image.shape)} with strides {tuple(image.stride())}")
+    return img, int(pitch), int(sb if B > 1 else extent)
 
 
 class Context:
@@ -442,6 +465,33 @@ class Context:
         if tuple(img.shape) != (B, Ny, Nx, D):
             raise ValueError(f"Context.frames_to_image: out must have shape {(B, Ny, Nx, D)}")
         self.check(self.L.aefft_frames_to_image(self.h, _ptr(frames), int(_is_u8(frames)), _ptr(img), pitch, B, D, Nx, Ny))
+        return out
+
+    def image_resize_to_frames(self, image, size, mode="linear", out=None, dtype=torch.uint8):
+        """resize + ImageToSpin_C on the device (aefft_image_resize_to_frames): `image` is a uint8 device tensor [B][H][W][D] of interleaved image
+        rows (or [H][W][D]) of ANY size -- contiguous, row-padded, or a region of interest big[:, y0:y1, x0:x1] of a larger batch (stride(-1) == 1,
+        stride(-2) == D, stride(-3) >= W * D, any sufficient batch stride; ValueError otherwise).  size = (Nx, Ny), the frames' columns and rows.
+        mode "linear" (cv::resize's default geometry, any size to any size) or "area" (the exact box average; Nx <= W, Ny <= H).  Returns, or
+        fills `out` with, the planar frames [B][D][Nx][Ny] of `dtype` uint8 or float32.  All-integer arithmetic (include/aefft.h).  One launch,
+        nothing waits for the device."""
+        what = "Context.image_resize_to_frames"
+        img, pitch, stride = _resize_layout(image, what)
+        B, H, W, D = img.shape
+        if mode not in RESIZE_MODES:
+            raise ValueError(f"{what}: mode must be one of {sorted(RESIZE_MODES)}")
+        try:
+            Nx, Ny = (int(v) for v in size)
+        except (TypeError, ValueError):
+            raise ValueError(f"{what}: size must be (Nx, Ny)") from None
+        if out is None:
+            if dtype not in (torch.uint8, torch.float32):
+                raise ValueError(f"{what}: dtype must be torch.uint8 or torch.float32")
+            if Nx < 1 or Ny < 1:
+                raise ValueError(f"{what}: size must be positive")
+            out = self.empty(B, D, Nx, Ny, dtype=dtype)
+        elif out.dtype not in (torch.uint8, torch.float32) or tuple(out.shape) != (B, D, Nx, Ny) or not out.is_contiguous():
+            raise ValueError(f"{what}: out must be a contiguous uint8 or float32 tensor of shape {(B, D, Nx, Ny)}")
+        self.check(self.L.aefft_image_resize_to_frames(self.h, _ptr(img), pitch, stride, W, H, RESIZE_MODES[mode], _ptr(out), int(_is_u8(out)), B, D, Nx, Ny))
         return out
 
     def set_flags(self, *names):

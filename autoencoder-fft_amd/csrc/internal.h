@@ -68,6 +68,12 @@ hipError_t launch_ssim_finish(const float* strips, float* map, int B, int D, int
 // D in 1..4, Nx, Ny in 1..8192, pitch >= Nx D (hipErrorInvalidValue otherwise); any alignment of image and pitch, frames 16-byte aligned.
 hipError_t launch_image_unpack(const unsigned char* image, size_t pitch, void* frames, bool f32, int B, int D, int Nx, int Ny, hipStream_t st);
 hipError_t launch_image_pack(const void* frames, bool f32, unsigned char* image, size_t pitch, int B, int D, int Nx, int Ny, hipStream_t st);
+// ---- resize_kernels.hip (aefft_image_resize_to_frames) ----
+// B images of H rows of `pitch` bytes, image b at b * stride, W x H interleaved pixels of D channels -> frames [B][D][Nx][Ny] (float when f32): the bilinear
+// (mode 0) or box-average (mode 1, Nx <= W and Ny <= H) resize and ImageToSpin_C's transposition in one launch, all-integer (include/aefft.h).
+// D in 1..4, W, H, Nx, Ny in 1..8192, pitch >= W D (hipErrorInvalidValue otherwise); any alignment of image, pitch and stride, frames 16-byte aligned.
+hipError_t launch_image_resize(const unsigned char* image, size_t pitch, size_t stride, int W, int H, int mode, void* frames, bool f32,
+                               int B, int D, int Nx, int Ny, hipStream_t st);
 size_t fft_mid_elems(long planes, int Nx, int Wc);   // complex elements needed in `mid`
 // sizes that are not powers of two (cufftPlanMany takes any size, fft.cu:773-779): even n in 8..1024 through Bluestein's chirp-z form on the
 // power-of-two LDS passes; rows -> transpose -> rows -> transpose.  w1, w2: workspaces of fft_any_ws_elems complex each.

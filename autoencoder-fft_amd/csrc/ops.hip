@@ -780,3 +780,36 @@ extern "C" int aefft_frames_to_image(aefft_ctx* ctx, const void* frames_d, int f
     return launch_or_fail(ctx, KID_IMAGE, (double)B * D * Nx * Ny * (frames_u8 ? 2.0 : 5.0), "image_pack",
                           [&] { return launch_image_pack(frames_d, !frames_u8, image_d, pitch, B, D, Nx, Ny, ctx->cur); });
 }
+
+// the rules of aefft_image_resize_to_frames (include/aefft.h "image boundary"); nothing is enqueued when one fails
+static int chk_resize(aefft_ctx* ctx, const unsigned char* image_d, size_t pitch, size_t image_stride, int W, int H, int mode, const void* frames_d,
+                      int frames_u8, int B, int D, int Nx, int Ny)
+{
+    const auto bad = [&](const char* rule) { return fail(ctx, AEFFT_EINVAL, (std::string("aefft_image_resize_to_frames: ") + rule).c_str()); };
+    const auto in = [](int v) { return v >= 1 && v <= 8192; };
+    if (!ctx || !image_d || !frames_d) return bad("null context, image or frames");
+    if (D < 1 || D > 4) return bad("D must be 1..4 (grey, BGR, BGRA)");
+    if (B < 1 || !in(W) || !in(H) || !in(Nx) || !in(Ny)) return bad("B must be >= 1 and W, H, Nx, Ny in 1..8192");
+    if (mode != AEFFT_RESIZE_LINEAR && mode != AEFFT_RESIZE_AREA) return bad("mode must be AEFFT_RESIZE_LINEAR or AEFFT_RESIZE_AREA");
+    if (mode == AEFFT_RESIZE_AREA && (Nx > W || Ny > H)) return bad("AEFFT_RESIZE_AREA does not enlarge: it needs Nx <= W and Ny <= H");
+    if (pitch < (size_t)W * D) return bad("pitch must be at least W * D bytes");
+    const size_t half = ~size_t(0) >> 1;
+    if (pitch > half / (size_t)H) return bad("H * pitch does not fit the address space");
+    const size_t extent = (size_t)(H - 1) * pitch + (size_t)W * D;             // the bytes of one image, up to its last row's W * D
+    if (B > 1 && image_stride < extent) return bad("image_stride must be at least (H - 1) * pitch + W * D bytes for B > 1");
+    if (B > 1 && image_stride > (half - extent) / (size_t)(B - 1)) return bad("B * image_stride does not fit the address space");
+    if (!aligned16(frames_d)) return bad("frames_d must be 16-byte aligned");
+    const uintptr_t f0 = reinterpret_cast<uintptr_t>(frames_d), f1 = f0 + (size_t)B * D * Nx * Ny * (frames_u8 ? 1 : 4);
+    const uintptr_t i0 = reinterpret_cast<uintptr_t>(image_d), i1 = i0 + (B > 1 ? (size_t)(B - 1) * image_stride : 0) + extent;
+    if (f0 < i1 && i0 < f1) return bad("the frame and image ranges overlap (the op is out-of-place)");
+    return AEFFT_OK;
+}
+
+extern "C" int aefft_image_resize_to_frames(aefft_ctx* ctx, const unsigned char* image_d, size_t pitch, size_t image_stride, int W, int H, int mode,
+                                            void* frames_d, int frames_u8, int B, int D, int Nx, int Ny)
+{
+    RET_IF(chk_resize(ctx, image_d, pitch, image_stride, W, H, mode, frames_d, frames_u8, B, D, Nx, Ny));
+    RET_IF(join_recon(ctx));                          // (frames_d may be a buffer a deferred reconstruction is still writing)
+    return launch_or_fail(ctx, KID_IMAGE, (double)B * D * ((double)W * H + (double)Nx * Ny * (frames_u8 ? 1.0 : 4.0)), "image_resize",
+                          [&] { return launch_image_resize(image_d, pitch, image_stride, W, H, mode, frames_d, !frames_u8, B, D, Nx, Ny, ctx->cur); });
+}

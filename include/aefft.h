@@ -236,6 +236,38 @@ int aefft_step_spatial(aefft_ctx* ctx, const float* in_d, float* hin_d, float* o
 int aefft_image_to_frames(aefft_ctx* ctx, const unsigned char* image_d, size_t pitch, void* frames_d, int frames_u8, int B, int D, int Nx, int Ny);
 int aefft_frames_to_image(aefft_ctx* ctx, const void* frames_d, int frames_u8, unsigned char* image_d, size_t pitch, int B, int D, int Nx, int Ny);
 
+/* aefft_image_resize_to_frames: camera images of ANY size to frames -- the reference loop's `resize(rgb, imgC, Size(Nx, Ny))` followed by
+ * ImageToSpin_C (autoencoder.cpp:124-125) in one launch, so that a 640 x 480 or 1920 x 1080 stream feeds a 256^2 / 512^2 / 1024^2 net without a
+ * host resize and without a float, planar copy of the camera image.
+ * Source: B images; image b starts at b * image_stride (ignored when B == 1); each image is H rows of `pitch` bytes; pixel (row y, column x),
+ * channel d, is the byte at  y * pitch + x * D + d.  pitch >= W * D; for B > 1, image_stride >= (H - 1) * pitch + W * D.  image_d, pitch and
+ * image_stride may have ANY alignment (all three multiples of 4: the image side loads dwords, bytes otherwise; the same bytes come out).  A region
+ * of interest of a larger image is image_d + y0 * pitch + x0 * D with the parent's pitch and stride.  Bytes beyond W * D of a row are never read.
+ * Destination: the library's [B][D][Nx][Ny] frames, unsigned char when frames_u8 != 0, float otherwise, 16-byte aligned; frames[b][d][i][j] is
+ * destination column i, destination row j: the transposition of aefft_image_to_frames.
+ * Shapes: D in 1..4; W, H, Nx, Ny in 1..8192, odd sizes included; B >= 1.
+ * Arithmetic: all-integer, so every route and a numpy restatement give the same bits.  Per axis, source size S, destination size N:
+ *   AEFFT_RESIZE_LINEAR  cv::resize's default geometry -- half-pixel centres, edges replicated, weights quantised to 1/2048.  For destination
+ *     index i:  n = (2i+1) S - N, den = 2N, s = floor(n / den), r = n - s den,  w = floor((4096 r + den) / (2 den))  = round(2048 r / den),
+ *     halves up;  s < 0: s = 0, w = 0;  s >= S-1: s = S-1, w = 0;  the second tap is min(s+1, S-1).  With column taps (x0, x1, wx) and row taps
+ *     (y0, y1, wy):  v = (2048-wy) ((2048-wx) p[y0][x0] + wx p[y0][x1]) + wy ((2048-wx) p[y1][x0] + wx p[y1][x1])  < 2^30.
+ *     8-bit frame: (v + 2^21) >> 22.  Float frame: q * 2^-16 with q = (v + 32) >> 6  (q < 2^24: the float is exact).  Any size to any size.
+ *   AEFFT_RESIZE_AREA    the exact box average, the anti-aliased choice for decimation (1080p -> 256^2); requires Nx <= W and Ny <= H.
+ *     Overlap of destination cell i with source pixel k:  o(i,k) = max(0, min((i+1) S, (k+1) N) - max(i S, k N))  (sum over k: S).
+ *     num = sum_y oy(j,y) sum_x ox(i,x) p[y][x]  (64 bits).  8-bit frame: floor((2 num + W H) / (2 W H)).  Float frame: q * 2^-16 with
+ *     q = floor((65536 num + floor(W H / 2)) / (W H)), exact in float.
+ * Consequences: with W == Nx and H == Ny both modes give exactly aefft_image_to_frames' output; with integer ratios AREA is the rounded block mean.
+ * Relation to OpenCV: LINEAR has cv::resize's geometry and 11-bit weights but is NOT promised byte-identical to it -- OpenCV derives its weights
+ * in float and truncates in its vertical pass, and it silently switches to INTER_AREA at exact 2x reduction, which this call never does (it never
+ * switches modes).  Differences of one grey level are to be expected; the difference is unmeasured (OpenCV was not available to the build).
+ * One launch on the context's stream; no host synchronisation, no allocation, no workspace; safe under stream capture.  Out-of-place.
+ * AEFFT_EINVAL, with aefft_last_error naming the rule, nothing enqueued and the outputs untouched: a null context or pointer, D or a size out of
+ * range, an unknown mode, AREA with an enlarging axis, pitch < W * D, image_stride too small for B > 1, frames_d not 16-byte aligned, source and
+ * destination byte ranges that overlap. */
+enum { AEFFT_RESIZE_LINEAR = 0, AEFFT_RESIZE_AREA = 1 };
+int aefft_image_resize_to_frames(aefft_ctx* ctx, const unsigned char* image_d, size_t pitch, size_t image_stride,
+                                 int W, int H, int mode, void* frames_d, int frames_u8, int B, int D, int Nx, int Ny);
+
 /* ---- network level: the resident, batched form of autoenc_fft / backprop_fft ------------------ */
 typedef struct {
     int D, Nx, Ny;        /* input frames [B][D][Nx][Ny] */

@@ -1,0 +1,180 @@
+// aefft_image_resize_to_frames without a device: the kernel source itself -- autoencoder-fft_amd/csrc/resize_kernels.hip,
+// body and launch geometry -- compiled for the HOST, 256 threads as the lanes of a workgroup and a barrier for __syncthreads, under the
+// sanitizers, with the source, frame and LDS buffers allocated at exactly their live extent, against a C restatement of include/aefft.h's
+// formulas in 64-bit integers (which shares nothing with the kernel's taps).
+//
+//   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -pthread -Wno-unknown-pragmas
+//       -o resize_hostcheck tools/resize_hostcheck.cpp   (one line),   then   ./resize_hostcheck
+//
+// A stand-alone program: it is not loaded into Python and does not touch a GPU.  Exit status 0 and "all N runs exact" when every run is
+// byte-exact (float frames compared as bits) and every byte/element of the frames was written.
+#include <pthread.h>
+#include <stddef.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <thread>
+#include <vector>
+
+struct Dim3 { unsigned x, y, z; };
+static thread_local Dim3 threadIdx, blockIdx;
+static Dim3 gridDim;
+static pthread_barrier_t wg_barrier;
+static void __syncthreads() { pthread_barrier_wait(&wg_barrier); }
+struct float4 { float x, y, z, w; } __attribute__((aligned(16)));
+static inline float4 make_float4(float x, float y, float z, float w) { return float4{x, y, z, w}; }
+#define __device__
+#define __forceinline__ inline
+#define RZ_HD static inline
+#define RZ_UNIFORM(x) (x)
+#define AEFFT_RESIZE_HOSTCHECK
+#include "../autoencoder-fft_amd/csrc/resize_kernels.hip"
+
+using namespace aefft;
+
+// ---- the formulas of include/aefft.h, restated -------------------------------------------------
+typedef long long i64;
+static i64 fdiv(i64 a, i64 b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
+static void linear_axis(int i, int S, int N, int* s0, int* s1, int* w)
+{
+    const i64 n = (2LL * i + 1) * S - N, den = 2LL * N;
+    i64 s = fdiv(n, den), r = n - s * den, ww = (4096 * r + den) / (2 * den);
+    if (s < 0) { s = 0; ww = 0; }
+    if (s >= S - 1) { s = S - 1; ww = 0; }
+    *s0 = (int)s; *s1 = (int)(s + 1 < S - 1 ? s + 1 : S - 1); *w = (int)ww;
+}
+static i64 overlap(int i, int k, int S, int N)
+{
+    const i64 hi = (i + 1LL) * S < (k + 1LL) * N ? (i + 1LL) * S : (k + 1LL) * N, lo = (i64)i * S > (i64)k * N ? (i64)i * S : (i64)k * N;
+    return hi > lo ? hi - lo : 0;
+}
+// want: [B][D][Nx][Ny] as the 8-bit pixel or, float frames, q (value = q * 2^-16)
+static void reference(const unsigned char* img, size_t pitch, size_t stride, int W, int H, int mode, bool f32, int B, int D, int Nx, int Ny, std::vector<unsigned>& want)
+{
+    want.assign((size_t)B * D * Nx * Ny, 0);
+    std::vector<std::vector<i64>> ox(Nx, std::vector<i64>(W, 0)), oy(Ny, std::vector<i64>(H, 0));
+    if (mode == 1) {
+        for (int i = 0; i < Nx; ++i) for (int k = 0; k < W; ++k) ox[i][k] = overlap(i, k, W, Nx);
+        for (int j = 0; j < Ny; ++j) for (int k = 0; k < H; ++k) oy[j][k] = overlap(j, k, H, Ny);
+    }
+    for (int b = 0; b < B; ++b)
+        for (int d = 0; d < D; ++d)
+            for (int i = 0; i < Nx; ++i)
+                for (int j = 0; j < Ny; ++j) {
+                    const unsigned char* p = img + b * stride + d;
+                    unsigned out;
+                    if (mode == 0) {
+                        int x0, x1, wx, y0, y1, wy;
+                        linear_axis(i, W, Nx, &x0, &x1, &wx);
+                        linear_axis(j, H, Ny, &y0, &y1, &wy);
+                        const i64 v = (2048LL - wy) * ((2048LL - wx) * p[y0 * pitch + x0 * D] + (i64)wx * p[y0 * pitch + x1 * D]) +
+                                      (i64)wy * ((2048LL - wx) * p[y1 * pitch + x0 * D] + (i64)wx * p[y1 * pitch + x1 * D]);
+                        out = f32 ? (unsigned)((v + 32) >> 6) : (unsigned)((v + (1LL << 21)) >> 22);
+                    } else {
+                        i64 num = 0;
+                        for (int y = 0; y < H; ++y) {
+                            if (!oy[j][y]) continue;
+                            i64 row = 0;
+                            for (int x = 0; x < W; ++x)
+                                if (ox[i][x]) row += ox[i][x] * p[y * pitch + x * D];
+                            num += oy[j][y] * row;
+                        }
+                        const i64 wh = (i64)W * H;
+                        out = f32 ? (unsigned)((65536 * num + wh / 2) / wh) : (unsigned)((2 * num + wh) / (2 * wh));
+                    }
+                    want[(((size_t)b * D + d) * Nx + i) * Ny + j] = out;
+                }
+}
+
+// ---- the launch: every workgroup of the grid, one after the other, its 256 lanes as threads -----
+typedef void (*body_fn)(const RzArgs&, unsigned*);
+template <int D, bool F32, int MODE> static void body(const RzArgs& a, unsigned* lds) { resize_body<D, F32, MODE>(a, lds); }
+#define ROW(D) {{body<D, false, 0>, body<D, false, 1>}, {body<D, true, 0>, body<D, true, 1>}}
+static const body_fn BODIES[4][2][2] = {ROW(1), ROW(2), ROW(3), ROW(4)};
+
+static void launch(const RzArgs& g, int D, bool f32, int mode, unsigned grid_y)
+{
+    const size_t words = (size_t)rz_lds_words(D, g.P, g.RB);
+    unsigned* lds = (unsigned*)malloc(4 * words);                                // exactly what the launcher asks for: LDS overruns show
+    gridDim = Dim3{(unsigned)(g.tx * g.ty), grid_y, 1};
+    pthread_barrier_init(&wg_barrier, nullptr, 256);
+    std::vector<std::thread> th;
+    for (unsigned t = 0; t < 256; ++t)
+        th.emplace_back([&, t] {
+            for (unsigned by = 0; by < gridDim.y; ++by)
+                for (unsigned bx = 0; bx < gridDim.x; ++bx) {
+                    threadIdx = Dim3{t, 0, 0};
+                    blockIdx = Dim3{bx, by, 0};
+                    BODIES[D - 1][f32][mode](g, lds);
+                    __syncthreads();                                             // (the next workgroup reuses this one's LDS)
+                }
+        });
+    for (auto& x : th) x.join();
+    pthread_barrier_destroy(&wg_barrier);
+    free(lds);
+}
+
+struct Shape { int B, D, W, H, Nx, Ny; };
+static unsigned rnd_state = 12345;
+static unsigned rnd() { rnd_state = rnd_state * 1664525u + 1013904223u; return rnd_state >> 24; }
+
+static int runs = 0, failures = 0;
+// kind 0 tight, 1 pitch rounded up to 64, 2 pitch W D + 5 from a base off by one byte, 3 a region of interest at (3, 5) of a larger batch
+static void run(const Shape& s, int kind, int mode, bool f32, unsigned grid_y = 0)
+{
+    const int B = s.B, D = s.D, W = s.W, H = s.H, Nx = s.Nx, Ny = s.Ny;
+    size_t pitch = (size_t)W * D, stride, off = 0;
+    if (kind == 1) pitch = (pitch + 63) / 64 * 64;
+    if (kind == 2) { pitch += 5; off = 1; }
+    stride = (size_t)H * pitch;
+    if (kind == 3) { pitch = (size_t)(W + 9) * D; stride = (size_t)(H + 7) * pitch; off = 3 * pitch + 5 * D; }
+    const size_t extent = (size_t)(B - 1) * stride + (size_t)(H - 1) * pitch + (size_t)W * D;   // the LAST byte the call may read is at off + extent - 1
+    unsigned char* alloc = (unsigned char*)malloc(off + extent);
+    for (size_t k = 0; k < off + extent; ++k) alloc[k] = (unsigned char)rnd();
+    const unsigned char* img = alloc + off;
+    const size_t n = (size_t)B * D * Nx * Ny, es = f32 ? 4 : 1;
+    void* fp = nullptr;
+    if (posix_memalign(&fp, 16, n * es)) abort();                                // 16-byte aligned, exactly n elements
+    unsigned char* frames = (unsigned char*)fp;
+    memset(frames, 0xEE, n * es);
+    const RzArgs g = rz_geometry(img, pitch, stride, W, H, mode, frames, B, D, Nx, Ny);
+    launch(g, D, f32, mode, grid_y ? grid_y : (unsigned)B);
+    std::vector<unsigned> want;
+    reference(img, pitch, stride, W, H, mode, f32, B, D, Nx, Ny, want);
+    size_t bad = 0;
+    for (size_t k = 0; k < n; ++k) {
+        if (f32) {
+            const float w = (float)want[k] * (1.0f / 65536.0f);
+            bad += memcmp(&w, frames + 4 * k, 4) != 0;
+        } else bad += frames[k] != (unsigned char)want[k];
+    }
+    ++runs;
+    if (bad) {
+        ++failures;
+        printf("MISMATCH B=%d D=%d %dx%d -> %dx%d kind=%d mode=%d f32=%d: %zu of %zu differ (words img=%d frm=%d P=%d RB=%d)\n", B, D, W, H, Nx, Ny, kind, mode, (int)f32, bad, n,
+               (int)g.img_words, (int)g.frm_words, g.P, g.RB);
+    }
+    free(frames);
+    free(alloc);
+}
+
+int main()
+{
+    const Shape shapes[] = {{1, 1, 8, 8, 8, 8}, {2, 3, 11, 9, 8, 8}, {1, 3, 7, 5, 16, 8}, {2, 4, 64, 64, 32, 32}, {1, 3, 130, 70, 66, 34},
+                            {1, 2, 200, 150, 10, 12}, {2, 3, 640, 480, 256, 256}, {1, 3, 1920, 1080, 64, 64},
+                            // beyond the device tests: one destination pixel, one source pixel, wide rows that need several bands (down to one row per band), 3 -> 2
+                            {1, 1, 37, 29, 1, 1}, {1, 4, 1, 1, 5, 3}, {1, 4, 2500, 40, 16, 4}, {3, 2, 3, 3, 2, 2}, {1, 1, 8192, 3, 2, 3}, {1, 4, 8192, 2, 1, 1}};
+    for (const Shape& s : shapes)
+        for (int kind = 0; kind < 4; ++kind)
+            for (int mode = 0; mode < 2; ++mode) {
+                if (mode == 1 && (s.Nx > s.W || s.Ny > s.H)) continue;
+                for (int f32 = 0; f32 < 2; ++f32) run(s, kind, mode, f32 != 0);
+            }
+    // a folded grid: five images on two rows of workgroups
+    for (int mode = 0; mode < 2; ++mode) run(Shape{5, 3, 11, 9, 8, 8}, 2, mode, false, 2);
+    if (failures) printf("%d of %d runs FAILED\n", failures, runs);
+    else printf("all %d runs exact\n", runs);
+    return failures ? 1 : 0;
+}
