@@ -124,57 +124,4 @@ __device__ __forceinline__ float2 opin_load(const OpIn& o, long plane, int t, in
     return acc;
 }
 
-// ------------------------------------------------------------------------------------------
-// the scoring epilogue of the inverse row passes (aefft_net_score: c2r_rows_kernel<.., SCORE>, mix_c2r_rows_kernel<.., SCORE>)
-// ------------------------------------------------------------------------------------------
-// SCORE 0: none; 1: float frames; 2: 8-bit frames.  Only a scoring instantiation carries the argument: the others take the empty ScoreNone,
-// so their argument loads and their code are what they were.
-struct ScoreNone {};
-struct ScoreDev { const void* frames; float* part; };
-template <int SCORE> struct ScoreParam { typedef ScoreDev type; };
-template <> struct ScoreParam<0> { typedef ScoreNone type; };
-// The reconstructed pixel is the ROUNDED product z * scale, the value the float row pass stores.  Passing it through an empty asm makes it a
-// value of its own: the back end cannot contract the product into the subtraction that follows (x - z * scale as one fma would make the score
-// a function of the unrounded product, and a trained net's small residual is where that shows).
-__device__ __forceinline__ float score_px(float z, float scale) { float r = z * scale; asm("" : "+v"(r)); return r; }
-__device__ __forceinline__ float score_sq(float x, float r) { const float d = x - r; return d * d; }
-// the sum over an aligned segment of W lanes of a wave (W a power of two), in every lane of it: a butterfly, whose two partners add the same
-// two numbers at every level -- one fixed order, the same bits in every lane
-template <int W> __device__ __forceinline__ float score_seg_sum(float v)
-{
-#pragma unroll
-    for (int o = W / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// SCORE 3: float frames; 4: 8-bit frames (aefft_net_score_map).  The epilogue of SCORE 1 / 2 up to the lane's (x - r)^2 terms; the butterfly
-// then stops at a STRIP -- two rows x `tile` columns of one channel, tile = 1 << lt in 8..64 -- and one float per strip goes to
-// part [npairs][n >> lt].  The tile is a run-time value (no template axis over it): the butterfly is a loop with a uniform bound.
-struct ScoreMapDev { const void* frames; float* part; int lt; };
-template <> struct ScoreParam<3> { typedef ScoreMapDev type; };
-template <> struct ScoreParam<4> { typedef ScoreMapDev type; };
-// the sum over an aligned segment of 1 << lw lanes of a wave (lw uniform, at most LMAX), in every lane of it: score_seg_sum's butterfly from the
-// nearest partner outwards, as many levels as the segment has
-template <int LMAX> __device__ __forceinline__ float score_seg_sum_rt(float v, int lw)
-{
-#pragma unroll
-    for (int l = 0; l < LMAX; ++l)
-        if (l < lw) v += __shfl_xor(v, 1 << l, 64);
-    return v;
-}
-
-// SCORE 5: float reference; 6: 8-bit reference (aefft_net_ssim_map).  The epilogue of SCORE 3 / 4 with FIVE sums per strip instead of one:
-// sum x', r', x'^2, r'^2, x'r' with x' = x - pivot, r' = r - pivot (x the reference pixel `frames` holds, r the rounded reconstruction).
-// The pivot (half the data range) keeps the float sums of squares small where the window is flat; variances and the covariance do not
-// depend on it, the finish adds it back to the means.  part [5][npairs][n >> lt]: one plane per moment, each laid out as ScoreMapDev's.
-struct ScoreSsimDev { const void* frames; float* part; int lt; float pivot; };
-template <> struct ScoreParam<5> { typedef ScoreSsimDev type; };
-template <> struct ScoreParam<6> { typedef ScoreSsimDev type; };
-// one pixel's five terms, in this order
-__device__ __forceinline__ void ssim_acc(float (&m)[SSIM_MOMENTS], float x, float r, float pivot)
-{
-    const float a = x - pivot, b = r - pivot;
-    m[0] += a; m[1] += b; m[2] += a * a; m[3] += b * b; m[4] += a * b;
-}
-
 }  // namespace aefft

@@ -23,6 +23,7 @@
 #include "internal.h"
 #include "device_util.h"
 #include "fft_common.h"
+#include "score_device.h"
 #include <hip/hip_ext.h>
 #include <math.h>
 #include <map>
@@ -259,15 +260,10 @@ __global__ __launch_bounds__(RowCfg<N>::NT) void r2c_rows_kernel(const void* __r
 // through LDS, no first-pass LDS reads, a third of the first pass's arithmetic; the passes at strides 8 and 64 follow unchanged.
 // U8: the rows go out as 8-bit pixels by SpinToImage_C's rule (netlib.cpp:66-68, px_u8 in fft_common.h) -- four per lane as one 32-bit store, a
 // quarter of the launch's writes; `out_v` is then unsigned char [npairs*2][N].  Everything in front of the store is the float kernel.
-// SCORE (1: float frames, 2: 8-bit frames; aefft_net_score): the lane also holds the FRAME's pixels for the elements it ends up with -- the float4
-// it would store to, or one word of four 8-bit pixels, per row -- requested right behind the spectrum's loads so that they arrive under the
-// LDS passes (read once: streaming loads).  It forms (x - r)^2 for both rows of its pair, r = the rounded product it would store (score_px), stores r as
-// well when out_v is non-null (a uniform branch), and the row pair's sum goes to sc.part[pair]: eight terms per position in the lane, a
-// butterfly over the pair's lanes of the wave, the pair's waves in order through LDS -- no atomics, one order.  U8 is false with SCORE.
-// SCORE (3: float frames, 4: 8-bit frames; aefft_net_score_map): the same up to the lane's eight terms; the butterfly stops at a strip of
-// sc's tile (fft_common.h ScoreMapDev) and the first lane of each strip writes sc.part[pair][strip].
-// SCORE (5: float reference, 6: 8-bit reference; aefft_net_ssim_map): the mapping epilogue with five sums per strip (fft_common.h ScoreSsimDev) --
-// the same lanes, loads and segments, the butterfly run on each of the five, one plane of sc.part per moment.
+// SCORE (1..6, score_device.h; U8 is false with it): the lane also holds the REFERENCE pixels for the elements it ends up with -- the float4 it
+// would store to, or one word of four 8-bit pixels, per row -- requested right behind the spectrum's loads so that they arrive under the LDS
+// passes.  One block behind the passes forms the rounded rows r (stored as well when out_v is non-null), feeds the lane's sums per position and
+// reduces them over a strip or over the row pair into sc.part -- no atomics, one order.
 template <int N, bool SPARSE, bool U8 = false, int SCORE = 0>
 __global__ __launch_bounds__(RowCfg<N>::NT) void c2r_rows_kernel(const float2* __restrict__ mid, void* __restrict__ out_v,
                                                                    long npairs, int Wc, float scale, const typename ScoreParam<SCORE>::type sc)
@@ -282,9 +278,8 @@ __global__ __launch_bounds__(RowCfg<N>::NT) void c2r_rows_kernel(const float2* _
     tws.load(t);
     const long pair0 = (long)blockIdx.x * G;
     constexpr int NQ = G * (N / 4) / NT;                        // epilogue positions per lane (= 2 when NT = G*N/8)
-    constexpr bool SF32 = SCORE == 1 || SCORE == 3 || SCORE == 5;      // the frames are floats (SCORE 2, 4, 6: 8-bit pixels)
-    [[maybe_unused]] float4 fa[NQ], fb[NQ];
-    [[maybe_unused]] unsigned ua[NQ], ub[NQ];
+    using Tr = ScoreTraits<SCORE>;
+    [[maybe_unused]] ScoreRef<4, Tr::F32> ref[NQ];
     [[maybe_unused]] auto load_frames = [&](int lv) {
         if constexpr (SCORE != 0) {
 #pragma unroll
@@ -292,15 +287,7 @@ __global__ __launch_bounds__(RowCfg<N>::NT) void c2r_rows_kernel(const float2* _
                 const int idx = tid + q * NT;
                 const int gg = idx / (N / 4), n4 = idx % (N / 4);
                 const int off = (gg < lv ? gg * (2 * N / 4) : 0) + n4;         // (32-bit lane offsets; rows that do not exist re-read pair 0)
-                if constexpr (SF32) {
-                    const float4* src = reinterpret_cast<const float4*>(static_cast<const float*>(sc.frames) + pair0 * 2 * N);
-                    fa[q] = ld_stream(&src[off]);
-                    fb[q] = ld_stream(&src[off + N / 4]);
-                } else {
-                    const unsigned* src = reinterpret_cast<const unsigned*>(static_cast<const unsigned char*>(sc.frames) + pair0 * 2 * N);
-                    ua[q] = __builtin_nontemporal_load(&src[off]);
-                    ub[q] = __builtin_nontemporal_load(&src[off + N / 4]);
-                }
+                ref[q].load(score_rows<Tr::F32>(sc.frames, pair0 * 2 * N), off, off + N / 4);
             }
         }
     };
@@ -381,96 +368,39 @@ __global__ __launch_bounds__(RowCfg<N>::NT) void c2r_rows_kernel(const float2* _
     // four consecutive complex elements per lane (read once, adjacent in the padded layout): their real parts are 16 bytes of row A, their
     // imaginary parts 16 bytes of row B
     const int live = npairs - pair0 < G ? (int)(npairs - pair0) : G;
-    if constexpr (SCORE >= 5) {
-        float* const orow = static_cast<float*>(out_v) + pair0 * 2 * N;      // (read under `store` only)
-        const bool store = out_v != nullptr;
-        const int lw = sc.lt - 2, ns = N >> sc.lt;            // log2 of a strip's lanes; strips of a row pair
-        const long ms = npairs * ns;                          // floats of one moment's plane
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) {
-            const int idx = tid + q * NT;
-            const int gg = idx / (N / 4), n4 = idx % (N / 4), n = n4 * 4;
-            float m[SSIM_MOMENTS] = {0.f, 0.f, 0.f, 0.f, 0.f};
-            if (gg < live) {
-                const float2* z = s + gg * PL + pad_idx(n);
-                const float2 z0 = z[0], z1 = z[1], z2 = z[2], z3 = z[3];
-                const float4 ra = make_float4(score_px(z0.x, scale), score_px(z1.x, scale), score_px(z2.x, scale), score_px(z3.x, scale));
-                const float4 rb = make_float4(score_px(z0.y, scale), score_px(z1.y, scale), score_px(z2.y, scale), score_px(z3.y, scale));
-                float4 xa, xb;
-                if constexpr (SF32) { xa = fa[q]; xb = fb[q]; }
-                else {
-                    xa = make_float4((float)(ua[q] & 255u), (float)((ua[q] >> 8) & 255u), (float)((ua[q] >> 16) & 255u), (float)(ua[q] >> 24));
-                    xb = make_float4((float)(ub[q] & 255u), (float)((ub[q] >> 8) & 255u), (float)((ub[q] >> 16) & 255u), (float)(ub[q] >> 24));
-                }
-                ssim_acc(m, xa.x, ra.x, sc.pivot); ssim_acc(m, xa.y, ra.y, sc.pivot); ssim_acc(m, xa.z, ra.z, sc.pivot); ssim_acc(m, xa.w, ra.w, sc.pivot);
-                ssim_acc(m, xb.x, rb.x, sc.pivot); ssim_acc(m, xb.y, rb.y, sc.pivot); ssim_acc(m, xb.z, rb.z, sc.pivot); ssim_acc(m, xb.w, rb.w, sc.pivot);
-                if (store) {
-                    st_stream(reinterpret_cast<float4*>(orow + (gg * 2) * N + n), ra);
-                    st_stream(reinterpret_cast<float4*>(orow + (gg * 2 + 1) * N + n), rb);
-                }
-            }
-            // (the segments are those of SCORE 3 / 4: a strip's tile/4 positions in consecutive lanes of one q)
-            const bool first = (n4 & ((1 << lw) - 1)) == 0 && gg < live;
-            float* const dst = sc.part + (pair0 + gg) * ns + (n4 >> lw);
-#pragma unroll
-            for (int k = 0; k < SSIM_MOMENTS; ++k) {
-                const float v = score_seg_sum_rt<4>(m[k], lw);
-                if (first) dst[k * ms] = v;
-            }
-        }
-        return;
-    }
     if constexpr (SCORE != 0) {
         float* const orow = static_cast<float*>(out_v) + pair0 * 2 * N;      // (read under `store` only)
         const bool store = out_v != nullptr;
-        float acc[NQ];
+        ScoreAcc<Tr::NS> acc[NQ];
 #pragma unroll
         for (int q = 0; q < NQ; ++q) {
             const int idx = tid + q * NT;
             const int gg = idx / (N / 4), n = (idx % (N / 4)) * 4;
-            acc[q] = 0.f;
-            if (gg < live) {
-                const float2* z = s + gg * PL + pad_idx(n);
-                const float2 z0 = z[0], z1 = z[1], z2 = z[2], z3 = z[3];
-                const float4 ra = make_float4(score_px(z0.x, scale), score_px(z1.x, scale), score_px(z2.x, scale), score_px(z3.x, scale));
-                const float4 rb = make_float4(score_px(z0.y, scale), score_px(z1.y, scale), score_px(z2.y, scale), score_px(z3.y, scale));
-                float4 xa, xb;
-                if constexpr (SF32) { xa = fa[q]; xb = fb[q]; }
-                else {
-                    xa = make_float4((float)(ua[q] & 255u), (float)((ua[q] >> 8) & 255u), (float)((ua[q] >> 16) & 255u), (float)(ua[q] >> 24));
-                    xb = make_float4((float)(ub[q] & 255u), (float)((ub[q] >> 8) & 255u), (float)((ub[q] >> 16) & 255u), (float)(ub[q] >> 24));
-                }
-                float a = score_sq(xa.x, ra.x);
-                a += score_sq(xa.y, ra.y); a += score_sq(xa.z, ra.z); a += score_sq(xa.w, ra.w);
-                a += score_sq(xb.x, rb.x); a += score_sq(xb.y, rb.y); a += score_sq(xb.z, rb.z); a += score_sq(xb.w, rb.w);
-                acc[q] = a;
-                if (store) {
-                    st_stream(reinterpret_cast<float4*>(orow + (gg * 2) * N + n), ra);
-                    st_stream(reinterpret_cast<float4*>(orow + (gg * 2 + 1) * N + n), rb);
-                }
-            }
+            acc[q].clear();
+            if (gg < live)
+                score_position(s + gg * PL + pad_idx(n), scale, ref[q], score_pivot(sc), store, orow + (gg * 2) * N + n, orow + (gg * 2 + 1) * N + n, acc[q]);
         }
-        if constexpr (SCORE >= 3) {
+        if constexpr (Tr::STRIP) {
             // a strip's tile/4 positions lie in consecutive lanes of one q, aligned (tile | N), never across waves; at N = 2048 the lane's
             // two positions belong to different strips of the one row pair, at N = 8 the strip is the pair's two lanes
             const int lw = sc.lt - 2, ns = N >> sc.lt;        // log2 of a strip's lanes; strips of a row pair
+            const long ms = npairs * ns;                      // floats of one moment's plane
 #pragma unroll
             for (int q = 0; q < NQ; ++q) {
-                const float v = score_seg_sum_rt<4>(acc[q], lw);
                 const int idx = tid + q * NT;
                 const int gg = idx / (N / 4), n4 = idx % (N / 4);
-                if ((n4 & ((1 << lw) - 1)) == 0 && gg < live) sc.part[(pair0 + gg) * ns + (n4 >> lw)] = v;
+                score_strip_reduce<4>(acc[q], lw, (n4 & ((1 << lw) - 1)) == 0 && gg < live, sc.part + (pair0 + gg) * ns + (n4 >> lw), ms);
             }
             return;
         }
         // a row pair's N/4 positions lie in consecutive lanes of one q (N/4 <= NT), or are the whole workgroup's, both q (N = 2048)
         constexpr int LPP = N / 4 < NT ? N / 4 : NT;        // lanes of one row pair
         constexpr int NR = N / 4 <= NT ? NQ : 1;            // row pairs a lane contributes to
-        if constexpr (N / 4 > NT) acc[0] += acc[1];
+        if constexpr (N / 4 > NT) acc[0].m[0] += acc[1].m[0];
         if constexpr (LPP <= 64) {
 #pragma unroll
             for (int q = 0; q < NR; ++q) {
-                const float v = score_seg_sum<LPP>(acc[q]);
+                const float v = score_seg_sum<LPP>(acc[q].m[0]);
                 const int gg = (tid + q * NT) / (N / 4);
                 if (tid % LPP == 0 && gg < live) sc.part[pair0 + gg] = v;
             }
@@ -478,7 +408,7 @@ __global__ __launch_bounds__(RowCfg<N>::NT) void c2r_rows_kernel(const float2* _
             __shared__ float red[NR][NT / 64];
 #pragma unroll
             for (int q = 0; q < NR; ++q) {
-                const float v = score_seg_sum<64>(acc[q]);
+                const float v = score_seg_sum<64>(acc[q].m[0]);
                 if ((tid & 63) == 0) red[q][tid >> 6] = v;
             }
             __syncthreads();
@@ -769,21 +699,10 @@ static hipError_t run_c2r_rows_as(const float2* mid, void* out, long npairs, int
 }
 template <int N, bool SPARSE> static hipError_t run_c2r_rows_sp(const float2* mid, void* out, long npairs, int Wc, float scale, hipStream_t st, bool out_u8, const ScoreArg* score)
 {
-    if (score) {
-        if (score->tile) {
-            const int lt = score_tile_log2(score->tile);
-            if (out_u8 || !score->frames || !score->strips || lt < 0 || N % score->tile) return hipErrorInvalidValue;
-            if (score->ssim) {
-                const ScoreSsimDev ss{score->frames, score->strips, lt, score->pivot};
-                return score->u8 ? run_c2r_rows_as<N, SPARSE, false, 6>(mid, out, npairs, Wc, scale, st, ss) : run_c2r_rows_as<N, SPARSE, false, 5>(mid, out, npairs, Wc, scale, st, ss);
-            }
-            const ScoreMapDev sm{score->frames, score->strips, lt};
-            return score->u8 ? run_c2r_rows_as<N, SPARSE, false, 4>(mid, out, npairs, Wc, scale, st, sm) : run_c2r_rows_as<N, SPARSE, false, 3>(mid, out, npairs, Wc, scale, st, sm);
-        }
-        if (out_u8 || !score->frames || !score->part) return hipErrorInvalidValue;
-        const ScoreDev sc{score->frames, score->part};
-        return score->u8 ? run_c2r_rows_as<N, SPARSE, false, 2>(mid, out, npairs, Wc, scale, st, sc) : run_c2r_rows_as<N, SPARSE, false, 1>(mid, out, npairs, Wc, scale, st, sc);
-    }
+    if (score)
+        return score_dispatch(*score, N, out_u8, [&](auto S, const auto& dev) {
+            return run_c2r_rows_as<N, SPARSE, false, decltype(S)::value>(mid, out, npairs, Wc, scale, st, dev);
+        });
     return out_u8 ? run_c2r_rows_as<N, SPARSE, true>(mid, out, npairs, Wc, scale, st) : run_c2r_rows_as<N, SPARSE, false>(mid, out, npairs, Wc, scale, st);
 }
 template <int N> static hipError_t run_c2r_rows(const float2* mid, void* out, long npairs, int Wc, float scale, hipStream_t st, bool out_u8, const ScoreArg* score)

@@ -18,6 +18,7 @@
 #include "internal.h"
 #include "device_util.h"
 #include "fft_common.h"
+#include "score_device.h"
 #include <hip/hip_ext.h>
 #include <math.h>
 #include <map>
@@ -201,12 +202,9 @@ __global__ __launch_bounds__(MixRowCfg<T>::NT) void mix_r2c_rows_kernel(const vo
 // inverse: mid [npairs*2][Wc] packed half spectra (the columns from Wc to n/2 are zero) -> out [npairs*2][n] real, times scale
 // U8: ... -> unsigned char [npairs*2][n] by SpinToImage_C's rule (px_u8, fft_common.h), two pixels per 16-bit store (n is even: every row
 // starts on a 2-byte boundary whatever n % 4 is, as on the forward pass's load)
-// SCORE (1: float frames, 2: 8-bit frames; aefft_net_score, as c2r_rows_kernel's): thread t of row pair g takes the element pairs t, t + T, ..
-// of ITS pair (at most four: n <= 8 T) -- the frame's two pixels of both rows requested behind the spectrum's loads, (x - r)^2 against the
-// rounded product, r stored as well when `out` is non-null -- and the pair's sum is reduced across its T threads: the lane's terms in order, a
-// butterfly over the pair's lanes of the wave, the pair's waves in order through LDS.  One float per row pair to sc.part.
-// SCORE (3: float frames, 4: 8-bit frames; aefft_net_score_map): one float per STRIP of sc's tile (fft_common.h ScoreMapDev) instead.
-// SCORE (5: float reference, 6: 8-bit reference; aefft_net_ssim_map): five sums per strip (fft_common.h ScoreSsimDev), one plane of sc.part each.
+// SCORE (1..6, score_device.h; as c2r_rows_kernel's): thread t of row pair g takes the element pairs t, t + T, .. of ITS pair (at most four:
+// n <= 8 T) -- the reference's two pixels of both rows requested behind the spectrum's loads -- and one block behind the passes forms the
+// rounded rows (stored as well when `out` is non-null), the lane's sums, and their reduction over a strip or over the pair's T threads.
 template <int T, bool U8 = false, int SCORE = 0>
 __global__ __launch_bounds__(MixRowCfg<T>::NT) void mix_c2r_rows_kernel(const float2* __restrict__ mid, void* __restrict__ out, long npairs,
                                                                          int Wc, float scale, const MixPlan pl, const typename ScoreParam<SCORE>::type sc)
@@ -236,121 +234,56 @@ __global__ __launch_bounds__(MixRowCfg<T>::NT) void mix_c2r_rows_kernel(const fl
         }
     }
     constexpr int NJ = 4;                                           // element pairs of a row per thread: H <= 4 T
-    constexpr bool SF32 = SCORE == 1 || SCORE == 3 || SCORE == 5;   // the frames are floats (SCORE 2, 4, 6: 8-bit pixels)
-    [[maybe_unused]] float2 fa[NJ], fb[NJ];
-    [[maybe_unused]] unsigned ua[NJ], ub[NJ];
+    using Tr = ScoreTraits<SCORE>;
+    [[maybe_unused]] ScoreRef<2, Tr::F32> ref[NJ];
     if constexpr (SCORE != 0) {
         const long r0 = (pair0 + (g < live ? g : 0)) * 2 * H;     // (a row pair that does not exist re-reads pair 0; an element pair beyond the row, pair 0 of it)
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
             const int c = t + j * T < H ? t + j * T : 0;
-            if constexpr (SF32) {
-                const float2* src = static_cast<const float2*>(sc.frames);
-                fa[j] = ld_stream(&src[r0 + c]);                    // (frames are read once)
-                fb[j] = ld_stream(&src[r0 + H + c]);
-            } else {
-                const unsigned short* src = static_cast<const unsigned short*>(sc.frames);
-                ua[j] = __builtin_nontemporal_load(&src[r0 + c]);
-                ub[j] = __builtin_nontemporal_load(&src[r0 + H + c]);
-            }
+            ref[j].load(sc.frames, r0 + c, r0 + H + c);
         }
     }
     __syncthreads();
     mix_fft<T, +1>(s + g * PL, t, pl);
 
-    if constexpr (SCORE >= 5) {
-        // SCORE 3 / 4's segments (below) with five sums per strip
-        float2* const o = static_cast<float2*>(out);
-        const bool store = out != nullptr;
-        const float2* z = s + g * PL;
-        const int lw = sc.lt - 1, ns = N >> sc.lt;                  // log2 of a strip's lanes; strips of a row pair
-        const long ms = npairs * ns;                                // floats of one moment's plane
-        float* const prow = sc.part + (pair0 + g) * ns;
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-            const int c = t + j * T;
-            float m[SSIM_MOMENTS] = {0.f, 0.f, 0.f, 0.f, 0.f};
-            if (g < live && c < H) {
-                const float2 z0 = z[pad_idx(2 * c)], z1 = z[pad_idx(2 * c + 1)];
-                const float2 ra = make_float2(score_px(z0.x, scale), score_px(z1.x, scale)), rb = make_float2(score_px(z0.y, scale), score_px(z1.y, scale));
-                float2 xa, xb;
-                if constexpr (SF32) { xa = fa[j]; xb = fb[j]; }
-                else { xa = make_float2((float)(ua[j] & 255u), (float)(ua[j] >> 8)); xb = make_float2((float)(ub[j] & 255u), (float)(ub[j] >> 8)); }
-                ssim_acc(m, xa.x, ra.x, sc.pivot); ssim_acc(m, xa.y, ra.y, sc.pivot); ssim_acc(m, xb.x, rb.x, sc.pivot); ssim_acc(m, xb.y, rb.y, sc.pivot);
-                if (store) {
-                    const long ra_i = (pair0 + g) * 2 * H + c;
-                    st_stream(&o[ra_i], ra);
-                    st_stream(&o[ra_i + H], rb);
-                }
-            }
-            const bool first = (t & ((1 << lw) - 1)) == 0 && g < live && c < H;
-#pragma unroll
-            for (int k = 0; k < SSIM_MOMENTS; ++k) {
-                const float v = score_seg_sum_rt<5>(m[k], lw);
-                if (first) prow[k * ms + (c >> lw)] = v;
-            }
-        }
-        return;
-    }
-    if constexpr (SCORE >= 3) {
-        // the map: element pair e = t + j T is two columns of both rows; a strip is tile/2 consecutive element pairs, i.e. for a FIXED j an aligned
-        // segment of tile/2 lanes (T is a power of two, and T >= tile/2 for every smooth n a tile divides; the launcher checks) -- a butterfly
-        // per j, never a sum over j.  Lanes with e >= H add 0; they lie in whole segments (tile | n) and write nothing.
-        float2* const o = static_cast<float2*>(out);
-        const bool store = out != nullptr;
-        const float2* z = s + g * PL;
-        const int lw = sc.lt - 1, ns = N >> sc.lt;                  // log2 of a strip's lanes; strips of a row pair
-        float* const prow = sc.part + (pair0 + g) * ns;
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-            const int c = t + j * T;
-            float a = 0.f;
-            if (g < live && c < H) {
-                const float2 z0 = z[pad_idx(2 * c)], z1 = z[pad_idx(2 * c + 1)];
-                const float2 ra = make_float2(score_px(z0.x, scale), score_px(z1.x, scale)), rb = make_float2(score_px(z0.y, scale), score_px(z1.y, scale));
-                float2 xa, xb;
-                if constexpr (SF32) { xa = fa[j]; xb = fb[j]; }
-                else { xa = make_float2((float)(ua[j] & 255u), (float)(ua[j] >> 8)); xb = make_float2((float)(ub[j] & 255u), (float)(ub[j] >> 8)); }
-                a += score_sq(xa.x, ra.x); a += score_sq(xa.y, ra.y); a += score_sq(xb.x, rb.x); a += score_sq(xb.y, rb.y);
-                if (store) {
-                    const long ra_i = (pair0 + g) * 2 * H + c;
-                    st_stream(&o[ra_i], ra);
-                    st_stream(&o[ra_i + H], rb);
-                }
-            }
-            const float v = score_seg_sum_rt<5>(a, lw);
-            if ((t & ((1 << lw) - 1)) == 0 && g < live && c < H) prow[c >> lw] = v;
-        }
-        return;
-    }
     if constexpr (SCORE != 0) {
-        float2* const o = static_cast<float2*>(out);
+        float* const orow = static_cast<float*>(out) + (pair0 + g) * 2 * N;      // (read under `store` only)
         const bool store = out != nullptr;
         const float2* z = s + g * PL;
-        float acc = 0.f;
+        // a strip's sums are one position's; a row pair's run over the lane's positions, its terms in order
+        constexpr int NA = Tr::STRIP ? NJ : 1;
+        ScoreAcc<Tr::NS> acc[NA];
+        if constexpr (!Tr::STRIP) acc[0].clear();
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
             const int c = t + j * T;
-            if (g < live && c < H) {
-                const float2 z0 = z[pad_idx(2 * c)], z1 = z[pad_idx(2 * c + 1)];
-                const float2 ra = make_float2(score_px(z0.x, scale), score_px(z1.x, scale)), rb = make_float2(score_px(z0.y, scale), score_px(z1.y, scale));
-                float2 xa, xb;
-                if constexpr (SF32) { xa = fa[j]; xb = fb[j]; }
-                else { xa = make_float2((float)(ua[j] & 255u), (float)(ua[j] >> 8)); xb = make_float2((float)(ub[j] & 255u), (float)(ub[j] >> 8)); }
-                acc += score_sq(xa.x, ra.x); acc += score_sq(xa.y, ra.y); acc += score_sq(xb.x, rb.x); acc += score_sq(xb.y, rb.y);
-                if (store) {
-                    const long ra_i = (pair0 + g) * 2 * H + c;
-                    st_stream(&o[ra_i], ra);
-                    st_stream(&o[ra_i + H], rb);
-                }
-            }
+            ScoreAcc<Tr::NS>& a = acc[Tr::STRIP ? j : 0];
+            if constexpr (Tr::STRIP) a.clear();
+            if (g < live && c < H)
+                score_position(z + pad_idx(2 * c), scale, ref[j], score_pivot(sc), store, orow + 2 * c, orow + N + 2 * c, a);
         }
+        if constexpr (Tr::STRIP) {
+            // the map: element pair e = t + j T is two columns of both rows; a strip is tile/2 consecutive element pairs, i.e. for a FIXED j an aligned
+            // segment of tile/2 lanes (T is a power of two, and T >= tile/2 for every smooth n a tile divides; the launcher checks) -- a butterfly
+            // per j, never a sum over j.  Lanes with e >= H add 0; they lie in whole segments (tile | n) and write nothing.
+            const int lw = sc.lt - 1, ns = N >> sc.lt;                  // log2 of a strip's lanes; strips of a row pair
+            const long ms = npairs * ns;                                // floats of one moment's plane
+            float* const prow = sc.part + (pair0 + g) * ns;
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) {
+                const int c = t + j * T;
+                score_strip_reduce<5>(acc[j], lw, (t & ((1 << lw) - 1)) == 0 && g < live && c < H, prow + (c >> lw), ms);
+            }
+            return;
+        }
+        const float sum = acc[0].m[0];
         if constexpr (T <= 64) {
-            const float v = score_seg_sum<T>(acc);
+            const float v = score_seg_sum<T>(sum);
             if (t == 0 && g < live) sc.part[pair0 + g] = v;
         } else {
             __shared__ float red[NT / 64];
-            const float v = score_seg_sum<64>(acc);
+            const float v = score_seg_sum<64>(sum);
             if ((tid & 63) == 0) red[tid >> 6] = v;
             __syncthreads();
             if (t == 0 && g < live) {
@@ -587,28 +520,15 @@ template <int T> static hipError_t run_mix_c2r_rows(const float2* mid, void* out
     const long blocks = (npairs + Cfg::G - 1) / Cfg::G;
     if (blocks >= (1L << 31)) return hipErrorInvalidValue;
     if (score) {
-        if (score->tile) {
-            const int lt = score_tile_log2(score->tile);
-            // (T >= tile/2: a strip's element pairs are lanes of ONE row pair.  Every smooth n a tile divides has it; n = 64, 128 with tile 64 would
-            // not, and reaches the power-of-two pass instead: a net's pooled grids are >= 8, so its packed width is a power of two >= 4)
-            if (u8 || !score->frames || !score->strips || lt < 0 || pl.n % score->tile || score->tile / 2 > T) return hipErrorInvalidValue;
-            if (score->ssim) {
-                const ScoreSsimDev ss{score->frames, score->strips, lt, score->pivot};
-                if (score->u8) mix_c2r_rows_kernel<T, false, 6><<<dim3((unsigned)blocks), dim3(Cfg::NT), lds, st>>>(mid, out, npairs, Wc, scale, pl, ss);
-                else mix_c2r_rows_kernel<T, false, 5><<<dim3((unsigned)blocks), dim3(Cfg::NT), lds, st>>>(mid, out, npairs, Wc, scale, pl, ss);
-                return hipGetLastError();
-            }
-            const ScoreMapDev sm{score->frames, score->strips, lt};
-            if (score->u8) mix_c2r_rows_kernel<T, false, 4><<<dim3((unsigned)blocks), dim3(Cfg::NT), lds, st>>>(mid, out, npairs, Wc, scale, pl, sm);
-            else mix_c2r_rows_kernel<T, false, 3><<<dim3((unsigned)blocks), dim3(Cfg::NT), lds, st>>>(mid, out, npairs, Wc, scale, pl, sm);
+        // (T >= tile/2: a strip's element pairs are lanes of ONE row pair.  Every smooth n a tile divides has it; n = 64, 128 with tile 64 would
+        // not, and reaches the power-of-two pass instead: a net's pooled grids are >= 8, so its packed width is a power of two >= 4)
+        if (score->tile / 2 > T) return hipErrorInvalidValue;
+        return score_dispatch(*score, pl.n, u8, [&](auto S, const auto& dev) {
+            mix_c2r_rows_kernel<T, false, decltype(S)::value><<<dim3((unsigned)blocks), dim3(Cfg::NT), lds, st>>>(mid, out, npairs, Wc, scale, pl, dev);
             return hipGetLastError();
-        }
-        if (u8 || !score->frames || !score->part) return hipErrorInvalidValue;
-        const ScoreDev sc{score->frames, score->part};
-        if (score->u8) mix_c2r_rows_kernel<T, false, 2><<<dim3((unsigned)blocks), dim3(Cfg::NT), lds, st>>>(mid, out, npairs, Wc, scale, pl, sc);
-        else mix_c2r_rows_kernel<T, false, 1><<<dim3((unsigned)blocks), dim3(Cfg::NT), lds, st>>>(mid, out, npairs, Wc, scale, pl, sc);
+        });
     }
-    else if (u8) mix_c2r_rows_kernel<T, true><<<dim3((unsigned)blocks), dim3(Cfg::NT), lds, st>>>(mid, out, npairs, Wc, scale, pl, ScoreNone{});
+    if (u8) mix_c2r_rows_kernel<T, true><<<dim3((unsigned)blocks), dim3(Cfg::NT), lds, st>>>(mid, out, npairs, Wc, scale, pl, ScoreNone{});
     else mix_c2r_rows_kernel<T, false><<<dim3((unsigned)blocks), dim3(Cfg::NT), lds, st>>>(mid, out, npairs, Wc, scale, pl, ScoreNone{});
     return hipGetLastError();
 }

@@ -1,5 +1,5 @@
 // The resident network (aefft_net) and its pairs, shared by net.hip (lifetime, weights and spectra, chain set-up, layer exports),
-// net_forward.hip (forward, inference, decode) and net_step.hip (bursts, training step): the rules more than one of them applies, each
+// net_forward.hip (forward, inference, decode), net_score.hip (read-outs of the reconstruction) and net_step.hip (bursts, training step): the rules more than one of them applies, each
 // stated once, and the helpers one unit defines for another.  Nothing here is exported.
 #pragma once
 #include "host.h"
@@ -188,7 +188,7 @@ inline Contract mk_OX(const aefft_net* n, const Pair& q, int B) { const OutView 
 struct OpView { const float2 *A, *O; int nxo, nyo; long PO; };
 inline bool op_mode(const aefft_net* n) { return n->op_state || n->op_chain; }
 
-// ---- net_forward.hip, for net_step.hip -------------------------------------------------
+// ---- net_forward.hip, for net_step.hip and net_score.hip -------------------------------
 bool chain_form(const aefft_net* n);       // the step's forward is one chain launch: Wp && (compact || L == 1) && the switches allow it
 bool op_eligible(const aefft_net* n);      // the step runs in operator form
 OpView op_view(const aefft_net* n, int l);
@@ -197,6 +197,7 @@ int ensure_packed(aefft_net* n);
 void fill_chain(aefft_net* n, ChainArgs& ca, int set, double* bytes);
 // score (nullable, aefft_net_score): handed to the inverse transform's row pass (do_c2r); recon_d may then be null where c2r_scores_in_rows
 int launch_recon(aefft_net* n, void* recon_d, int wsid, bool out_u8 = false, const ScoreArg* score = nullptr);
+inline bool aligned16p(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }      // (null passes: optional pointers)
 inline long score_pairs_per_frame(const aefft_net* n) { return ((long)n->D * n->Nx + 1) / 2; }
 inline size_t score_map_strips(const aefft_net* n) { return ((size_t)n->B * n->D * n->Nx * n->Ny + 15) / 16; }     // the most strips: tile 8
 int net_forward(aefft_net* n, const float* frames_d, bool u8, float* recon_d, bool lazy, bool op = false, bool infer = false);

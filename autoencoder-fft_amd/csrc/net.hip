@@ -1,6 +1,6 @@
 // C-ABI layer (include/aefft.h), resident network: create / destroy, the weight and spectra accessors, the operator chain's set-up
 // (build_chain_items) and the layer exports (aefft_net_get_layer*, aefft_net_layers_layout, aefft_magnitude).  The forward, inference
-// and decode are in net_forward.hip, the bursts and the training step in net_step.hip.
+// and decode are in net_forward.hip, the read-outs of the reconstruction in net_score.hip, the bursts and the training step in net_step.hip.
 #include "net.h"
 
 #include <algorithm>

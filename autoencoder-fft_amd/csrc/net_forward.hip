@@ -1,11 +1,10 @@
 // C-ABI layer (include/aefft.h), the resident network's forward: net_forward and its stages, the operator chain and the bin-major record it
 // reads (ensure_packed, fill_chain), the reconstruction (launch_recon), the per-frame expansion of an operator-form step (ensure_frames), and
-// the entry points that only run forward: aefft_net_forward*, aefft_net_infer, aefft_net_score, aefft_net_score_map, aefft_net_decode.  Bursts and the training step: net_step.hip.
+// the entry points that only run forward: aefft_net_forward*, aefft_net_infer, aefft_net_decode.  The read-outs of the reconstruction
+// (aefft_net_score and its kin): net_score.hip.  Bursts and the training step: net_step.hip.
 #include "net.h"
 
 #include <algorithm>
-#include <cmath>
-#include <string>
 
 using namespace aefft;
 
@@ -462,8 +461,6 @@ static int infer_hidden_op(aefft_net* n, int l, float* hidden_d)
     return do_c2r(ctx, q.H, hidden_d, (long)n->B * q.dM, q.Nx, q.Ny, q.Nx, q.Ny, 1.0f / ((float)q.Nx * (float)q.Ny));
 }
 
-static bool aligned16p(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 extern "C" int aefft_net_infer(aefft_net* n, const void* frames_d, int frames_u8, void* recon_d, int recon_u8, int hidden_pair, float* hidden_d)
 {
     if (!n) return AEFFT_EINVAL;
@@ -490,173 +487,6 @@ extern "C" int aefft_net_infer(aefft_net* n, const void* frames_d, int frames_u8
         else RET_IF(aefft_net_get_layer(n, 2 * hidden_pair + 2, hidden_d, nullptr, nullptr, nullptr));      // formed on request from the pair's input
     }
     return mark_step_point(n);
-}
-
-// ------------------------------------------------------------------------------------------
-// per-frame reconstruction error (include/aefft.h aefft_net_score)
-// ------------------------------------------------------------------------------------------
-// a frame's row-pair partials added up (score_finish_kernel): score_d[b] = sum / (D Nx Ny)
-static int score_finish(aefft_net* n, float* score_d)
-{
-    aefft_ctx* ctx = n->ctx;
-    const long npf = score_pairs_per_frame(n);
-    return launch_or_fail(ctx, KID_SCORE, (double)n->B * (npf + 1) * 4.0, "score_finish",
-                          [&] { return launch_score_finish(n->score_part, score_d, n->B, npf, 1.0 / ((double)n->D * n->Nx * n->Ny), ctx->cur); });
-}
-
-// aefft_net_infer's body with the score argument handed to the reconstruction, then the finish launch.  ref: the pixels the reconstruction is
-// compared with -- the frames themselves (aefft_net_score) or a target of the same shape (aefft_net_score_target); the net reads frames_d.
-static int score_body(aefft_net* n, const char* who, const void* frames_d, bool frames_u8, const void* ref_d, bool ref_u8, float* score_d, float* recon_d)
-{
-    aefft_ctx* ctx = n->ctx;
-    const std::string w(who);
-    if (n->spatial) {
-        if (frames_u8 || ref_u8) return sp_refuse(n, (w + " with 8-bit frames").c_str());
-        if (!recon_d) return fail(ctx, AEFFT_EINVAL, (w + ": a spatial net's reconstruction is written by its last convolution, not by an inverse transform's row pass -- the score is formed from the stored reconstruction, so recon_d must be given").c_str());
-        RET_IF(sp_forward(n, static_cast<const float*>(frames_d), recon_d));
-        RET_IF(launch_or_fail(ctx, KID_SCORE, (double)n->B * n->D * n->Nx * n->Ny * 8.0, "score_diff", [&] {
-            return launch_score_diff(ref_d, false, recon_d, n->score_part, n->B, (long)n->D * n->Nx, n->Ny, ctx->cur);
-        }));
-        RET_IF(score_finish(n, score_d));
-        return mark_step_point(n);
-    }
-    if (!recon_d && !c2r_scores_in_rows(n->Nx, n->Ny))
-        return fail(ctx, AEFFT_EINVAL, (w + ": under AEFFT_F_CHIRPZ this grid's reconstruction comes out of the chirp-z transforms, not of an inverse row pass -- the score is formed from the stored reconstruction, so recon_d must be given").c_str());
-    const bool op = op_eligible(n);
-    RET_IF(net_forward(n, static_cast<const float*>(frames_d), frames_u8, nullptr, true, op, true));
-    const ScoreArg sc{ref_d, ref_u8, n->score_part};
-    RET_IF(launch_recon(n, recon_d, WS_MID, false, &sc));
-    RET_IF(score_finish(n, score_d));
-    return mark_step_point(n);
-}
-
-extern "C" int aefft_net_score(aefft_net* n, const void* frames_d, int frames_u8, float* score_d, float* recon_d)
-{
-    if (!n) return AEFFT_EINVAL;
-    aefft_ctx* ctx = n->ctx;
-    if (!frames_d || !score_d) return fail(ctx, AEFFT_EINVAL, "aefft_net_score: null frames or score");
-    if (!aligned16p(frames_d) || !aligned16p(score_d) || !aligned16p(recon_d)) return fail(ctx, AEFFT_EINVAL, "aefft_net_score: pointers must be 16-byte aligned");
-    return score_body(n, "aefft_net_score", frames_d, frames_u8 != 0, frames_d, frames_u8 != 0, score_d, recon_d);
-}
-
-extern "C" int aefft_net_score_target(aefft_net* n, const void* frames_d, int frames_u8, const void* targets_d, int targets_u8, float* score_d, float* recon_d)
-{
-    if (!n) return AEFFT_EINVAL;
-    aefft_ctx* ctx = n->ctx;
-    if (!frames_d || !targets_d || !score_d) return fail(ctx, AEFFT_EINVAL, "aefft_net_score_target: null frames, targets or score");
-    if (!aligned16p(frames_d) || !aligned16p(targets_d) || !aligned16p(score_d) || !aligned16p(recon_d))
-        return fail(ctx, AEFFT_EINVAL, "aefft_net_score_target: pointers must be 16-byte aligned");
-    return score_body(n, "aefft_net_score_target", frames_d, frames_u8 != 0, targets_d, targets_u8 != 0, score_d, recon_d);
-}
-
-// ------------------------------------------------------------------------------------------
-// per-tile reconstruction error (include/aefft.h aefft_net_score_map)
-// ------------------------------------------------------------------------------------------
-// the strips added up per map entry (score_map_finish_kernel), then, when asked for, a frame's map entries averaged (score_finish_kernel with
-// the map as the partials)
-static int score_map_finish(aefft_net* n, int tile, float* map_d, float* score_d)
-{
-    aefft_ctx* ctx = n->ctx;
-    const long epf = (long)(n->Nx / tile) * (n->Ny / tile);        // map entries per frame
-    RET_IF(launch_or_fail(ctx, KID_SCORE_MAP, ((double)n->B * n->D * n->Nx / 2 * (n->Ny / tile) + (double)n->B * epf) * 4.0, "score_map_finish",
-                          [&] { return launch_score_map_finish(n->map_part, map_d, n->B, n->D, n->Nx, n->Ny, tile, ctx->cur); }));
-    if (!score_d) return AEFFT_OK;
-    return launch_or_fail(ctx, KID_SCORE, (double)n->B * (epf + 1) * 4.0, "score_finish",
-                          [&] { return launch_score_finish(map_d, score_d, n->B, epf, 1.0 / (double)epf, ctx->cur); });
-}
-
-// aefft_net_score's body with the tile in the score argument: the row pass leaves strips, the finish makes the map of them.
-// ssim (aefft_net_ssim_map): five sums per strip into ssim_part, and the SSIM finish; L = data_range.  ref as in score_body.
-static int map_body(aefft_net* n, const char* who, const void* frames_d, bool frames_u8, const void* ref_d, bool ref_u8, int tile, bool ssim, float L,
-                    float* map_d, float* score_d, float* recon_d)
-{
-    aefft_ctx* ctx = n->ctx;
-    const std::string w(who);
-    const float pivot = 0.5f * L;
-    const int kid = ssim ? KID_SSIM : KID_SCORE_MAP;
-    float* strips = n->map_part;
-    // (the first SSIM call of a net allocates its strip buffer, behind the refusals: not under stream capture, include/aefft.h)
-    auto ssim_strips = [&]() -> int {
-        if (!ssim) return AEFFT_OK;
-        if (!n->ssim_part) RET_IF(net_alloc_t(n, &n->ssim_part, (size_t)SSIM_MOMENTS * score_map_strips(n)));
-        strips = n->ssim_part;
-        return AEFFT_OK;
-    };
-    const double px = (double)n->B * n->D * n->Nx * n->Ny;
-    auto finish = [&]() -> int {
-        if (!ssim) return score_map_finish(n, tile, map_d, score_d);
-        const long epf = (long)(n->Nx / tile) * (n->Ny / tile);        // map entries per frame
-        RET_IF(launch_or_fail(ctx, KID_SSIM, (SSIM_MOMENTS * px / 2 / tile + (double)n->B * epf) * 4.0, "ssim_finish",
-                              [&] { return launch_ssim_finish(strips, map_d, n->B, n->D, n->Nx, n->Ny, tile, L, pivot, ctx->cur); }));
-        if (!score_d) return AEFFT_OK;
-        return launch_or_fail(ctx, KID_SCORE, (double)n->B * (epf + 1) * 4.0, "score_finish",
-                              [&] { return launch_score_finish(map_d, score_d, n->B, epf, 1.0 / (double)epf, ctx->cur); });
-    };
-    if (n->spatial) {
-        if (frames_u8 || ref_u8) return sp_refuse(n, (w + " with 8-bit frames").c_str());
-        if (!recon_d) return fail(ctx, AEFFT_EINVAL, (w + ": a spatial net's reconstruction is written by its last convolution, not by an inverse transform's row pass -- the map is formed from the stored reconstruction, so recon_d must be given").c_str());
-        RET_IF(ssim_strips());
-        RET_IF(sp_forward(n, static_cast<const float*>(frames_d), recon_d));
-        RET_IF(launch_or_fail(ctx, kid, px * 8.0, ssim ? "ssim_diff" : "score_map_diff", [&] {
-            const long npairs = (long)n->B * n->D * n->Nx / 2;
-            return ssim ? launch_ssim_diff(ref_d, false, recon_d, strips, npairs, n->Ny, tile, pivot, ctx->cur)
-                        : launch_score_map_diff(ref_d, false, recon_d, strips, npairs, n->Ny, tile, ctx->cur);
-        }));
-        RET_IF(finish());
-        return mark_step_point(n);
-    }
-    if (!recon_d && !c2r_scores_in_rows(n->Nx, n->Ny))
-        return fail(ctx, AEFFT_EINVAL, (w + ": under AEFFT_F_CHIRPZ this grid's reconstruction comes out of the chirp-z transforms, not of an inverse row pass -- the map is formed from the stored reconstruction, so recon_d must be given").c_str());
-    RET_IF(ssim_strips());
-    const bool op = op_eligible(n);
-    RET_IF(net_forward(n, static_cast<const float*>(frames_d), frames_u8, nullptr, true, op, true));
-    const ScoreArg sc{ref_d, ref_u8, nullptr, tile, strips, ssim, pivot};
-    RET_IF(launch_recon(n, recon_d, WS_MID, false, &sc));
-    RET_IF(finish());
-    return mark_step_point(n);
-}
-
-static bool map_tile_ok(const aefft_net* n, int tile) { return score_tile_log2(tile) >= 0 && n->Nx % tile == 0 && n->Ny % tile == 0; }
-
-extern "C" int aefft_net_score_map(aefft_net* n, const void* frames_d, int frames_u8, int tile, float* map_d, float* score_d, float* recon_d)
-{
-    if (!n) return AEFFT_EINVAL;
-    aefft_ctx* ctx = n->ctx;
-    if (!frames_d || !map_d) return fail(ctx, AEFFT_EINVAL, "aefft_net_score_map: null frames or map");
-    if (!aligned16p(frames_d) || !aligned16p(map_d) || !aligned16p(score_d) || !aligned16p(recon_d))
-        return fail(ctx, AEFFT_EINVAL, "aefft_net_score_map: pointers must be 16-byte aligned");
-    if (!map_tile_ok(n, tile)) return fail(ctx, AEFFT_EINVAL, "aefft_net_score_map: tile must be 8, 16, 32 or 64 and divide both Nx and Ny");
-    return map_body(n, "aefft_net_score_map", frames_d, frames_u8 != 0, frames_d, frames_u8 != 0, tile, false, 0.f, map_d, score_d, recon_d);
-}
-
-extern "C" int aefft_net_score_map_target(aefft_net* n, const void* frames_d, int frames_u8, const void* targets_d, int targets_u8, int tile, float* map_d,
-                                          float* score_d, float* recon_d)
-{
-    if (!n) return AEFFT_EINVAL;
-    aefft_ctx* ctx = n->ctx;
-    if (!frames_d || !targets_d || !map_d) return fail(ctx, AEFFT_EINVAL, "aefft_net_score_map_target: null frames, targets or map");
-    if (!aligned16p(frames_d) || !aligned16p(targets_d) || !aligned16p(map_d) || !aligned16p(score_d) || !aligned16p(recon_d))
-        return fail(ctx, AEFFT_EINVAL, "aefft_net_score_map_target: pointers must be 16-byte aligned");
-    if (!map_tile_ok(n, tile)) return fail(ctx, AEFFT_EINVAL, "aefft_net_score_map_target: tile must be 8, 16, 32 or 64 and divide both Nx and Ny");
-    return map_body(n, "aefft_net_score_map_target", frames_d, frames_u8 != 0, targets_d, targets_u8 != 0, tile, false, 0.f, map_d, score_d, recon_d);
-}
-
-// ------------------------------------------------------------------------------------------
-// block SSIM of the reconstruction (include/aefft.h aefft_net_ssim_map)
-// ------------------------------------------------------------------------------------------
-extern "C" int aefft_net_ssim_map(aefft_net* n, const void* frames_d, int frames_u8, const void* targets_d, int targets_u8, int tile, float data_range,
-                                  float* map_d, float* score_d, float* recon_d)
-{
-    if (!n) return AEFFT_EINVAL;
-    aefft_ctx* ctx = n->ctx;
-    if (!frames_d || !map_d) return fail(ctx, AEFFT_EINVAL, "aefft_net_ssim_map: null frames or map");
-    if (!aligned16p(frames_d) || !aligned16p(targets_d) || !aligned16p(map_d) || !aligned16p(score_d) || !aligned16p(recon_d))
-        return fail(ctx, AEFFT_EINVAL, "aefft_net_ssim_map: pointers must be 16-byte aligned");
-    if (!map_tile_ok(n, tile)) return fail(ctx, AEFFT_EINVAL, "aefft_net_ssim_map: tile must be 8, 16, 32 or 64 and divide both Nx and Ny");
-    if (!std::isfinite(data_range) || !(data_range > 0.f)) return fail(ctx, AEFFT_EINVAL, "aefft_net_ssim_map: data_range must be finite and greater than 0 (255 for 8-bit images)");
-    const void* ref = targets_d ? targets_d : frames_d;
-    const bool ref_u8 = targets_d ? targets_u8 != 0 : frames_u8 != 0;
-    return map_body(n, "aefft_net_ssim_map", frames_d, frames_u8 != 0, ref, ref_u8, tile, true, data_range, map_d, score_d, recon_d);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -808,8 +808,6 @@ extern "C" int aefft_net_step_grad_u8(aefft_net* n, const unsigned char* frames_
     return n ? step_grad(n, reinterpret_cast<const float*>(frames_d), true, recon_d) : AEFFT_EINVAL;
 }
 
-static bool aligned16p(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 extern "C" int aefft_net_step_grad_target(aefft_net* n, const void* frames_d, int frames_u8, const void* targets_d, int targets_u8, float* recon_d)
 {
     if (!n) return AEFFT_EINVAL;

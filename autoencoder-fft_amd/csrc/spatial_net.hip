@@ -1,7 +1,7 @@
 // C-ABI layer (include/aefft.h), the spatial net: an aefft_net created with AEFFT_NET_SPATIAL trains the reference's coordinate-space
 // mode (autoencoder.cpp:135-150 Pool -> Conv_gpu per encoder, Conv_gpu -> Pool(-s) per decoder, then backprop_gpu[_cc] per pair,
 // :161-178) over a batch, every pair per step, split into step_grad / all-reduce / step_apply like the FFT nets.  The public entry
-// points in net.hip, net_forward.hip and net_step.hip hand a spatial net over to the functions here.  DESIGN.md section 12.
+// points in net.hip, net_forward.hip, net_score.hip and net_step.hip hand a spatial net over to the functions here.  DESIGN.md section 12.
 //
 // Layers (autoencoder.cpp:109-120 ordering), pair l on the grid G_l = G_{l-1} / s_l:
 //   2l+1     Pool(layer 2l, s_l)         q.Lin   written by the encoder's convolution (Pool on load, pooled_out)
