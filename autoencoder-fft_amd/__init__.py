@@ -76,6 +76,8 @@ SIGNATURES = {
     "aefft_image_to_frames": (_i, [_vp, _vp, C.c_size_t, _vp, _i, _i, _i, _i, _i]),
     "aefft_frames_to_image": (_i, [_vp, _vp, _i, _vp, C.c_size_t, _i, _i, _i, _i]),
     "aefft_image_resize_to_frames": (_i, [_vp, _vp, C.c_size_t, C.c_size_t, _i, _i, _i, _vp, _i, _i, _i, _i, _i]),
+    "aefft_frames_resize_to_image": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, C.c_size_t, C.c_size_t, _i, _i, _i, _i]),
+    "aefft_map_overlay_image": (_i, [_vp, _fp, _i, _i, _f, _f, _i, _vp, _i, _vp, C.c_size_t, C.c_size_t, _i, _i, _i, _i]),
     "aefft_net_create": (_i, [_vp, C.POINTER(NetDesc), C.POINTER(_vp)]),
     "aefft_net_create_ex": (_i, [_vp, C.POINTER(NetDesc), C.c_uint, C.POINTER(_vp)]),
     "aefft_net_destroy": (None, [_vp]),
@@ -228,6 +230,61 @@ def _resize_layout(image, what):
         raise ValueError(f"{what}: the image must have stride(-1) == 1, stride(-2) == D, stride(-3) = pitch >= W * D and a batch stride of at least "
                          f"(H - 1) * pitch + W * D; got shape {tuple(image.shape)} with strides {tuple(image.stride())}")
     return img, int(pitch), int(sb if B > 1 else extent)
+
+
+def heat_lut(D=3):
+    """A default colour table for Context.map_overlay as a numpy uint8 [256][D], from integer formulas: entry k runs from blue (k = 0) through
+    green to red (k = 255) in the image's own BGR order -- B = 255 - k, G = 255 - |2 k - 255|, R = k; D == 1 a grey ramp k; D == 2 (k, 255);
+    D == 4 BGR with the fourth channel 255."""
+    if D not in (1, 2, 3, 4):
+        raise ValueError("heat_lut: D must be 1..4")
+    k = np.arange(256, dtype=np.int64)
+    if D == 1:
+        cols = [k]
+    elif D == 2:
+        cols = [k, np.full(256, 255)]
+    else:
+        cols = [255 - k, 255 - np.abs(2 * k - 255), k] + ([np.full(256, 255)] if D == 4 else [])
+    return np.ascontiguousarray(np.stack(cols, axis=1).astype(np.uint8))
+
+
+def _frames_resize_args(frames, size, mode, out):
+    """the checks of Context.frames_resize_to_image that need no device: (frames, (W, H), mode value); `out`, when given, is checked by the caller
+    through _resize_layout"""
+    what = "Context.frames_resize_to_image"
+    if frames.dtype not in (torch.uint8, torch.float32) or frames.dim() != 4 or not frames.is_contiguous() or min(frames.shape) < 1:
+        raise ValueError(f"{what}: frames must be a contiguous, non-empty uint8 or float32 tensor [B][D][Nx][Ny]")
+    if mode not in RESIZE_MODES:
+        raise ValueError(f"{what}: mode must be one of {sorted(RESIZE_MODES)}")
+    try:
+        W, H = (int(v) for v in size)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: size must be (W, H)") from None
+    if W < 1 or H < 1:
+        raise ValueError(f"{what}: size must be positive")
+    B, D = frames.shape[:2]
+    if out is not None and (out.dim() != 4 or tuple(out.shape) != (B, H, W, D)):
+        raise ValueError(f"{what}: out must be a uint8 tensor of shape {(B, H, W, D)}")
+    return W, H, RESIZE_MODES[mode]
+
+
+def _overlay_args(map, image, lut, lo, hi, alpha):
+    """the checks of Context.map_overlay that need no device: (map as [B][Mx][My], image as [B][H][W][D], pitch, image stride)"""
+    what = "Context.map_overlay"
+    img, pitch, stride = _resize_layout(image, what)
+    B, H, W, D = img.shape
+    if map.dtype != torch.float32 or map.dim() not in (2, 3) or not map.is_contiguous() or min(map.shape) < 1:
+        raise ValueError(f"{what}: map must be a contiguous, non-empty float32 tensor [B][Mx][My] or [Mx][My]")
+    m = map if map.dim() == 3 else map.unsqueeze(0)
+    if m.shape[0] != B:
+        raise ValueError(f"{what}: map has {m.shape[0]} entries along the batch, the image {B}")
+    if lut.dtype != torch.uint8 or tuple(lut.shape) != (256, D) or not lut.is_contiguous():
+        raise ValueError(f"{what}: lut must be a contiguous uint8 tensor of shape {(256, D)}")
+    if not (np.isfinite(lo) and np.isfinite(hi)) or lo == hi:
+        raise ValueError(f"{what}: lo and hi must be finite and different")
+    if int(alpha) != alpha or not 0 <= alpha <= 256:
+        raise ValueError(f"{what}: alpha must be an integer in 0..256")
+    return m, img, pitch, stride
 
 
 class Context:
@@ -493,6 +550,32 @@ class Context:
             raise ValueError(f"{what}: out must be a contiguous uint8 or float32 tensor of shape {(B, D, Nx, Ny)}")
         self.check(self.L.aefft_image_resize_to_frames(self.h, _ptr(img), pitch, stride, W, H, RESIZE_MODES[mode], _ptr(out), int(_is_u8(out)), B, D, Nx, Ny))
         return out
+
+    def frames_resize_to_image(self, frames, size, mode="linear", out=None):
+        """SpinToImage_C + resize on the device (aefft_frames_resize_to_image), the mirror of image_resize_to_frames: `frames` is uint8 or float32
+        [B][D][Nx][Ny] (float values become pixels first, as in frames_to_image); size = (W, H), the image's columns and rows; mode "linear" (any
+        size to any size) or "area" (the exact box average; W <= Nx, H <= Ny).  Returns, or fills `out` with, the uint8 image rows [B][H][W][D];
+        `out` may be a row-padded view or a region of interest big[:, y0:y1, x0:x1] of a larger batch (bytes outside it are not written;
+        ValueError for layouts the C call cannot describe).  All-integer arithmetic (include/aefft.h).  One launch, nothing waits for the device."""
+        W, H, m = _frames_resize_args(frames, size, mode, out)
+        B, D, Nx, Ny = frames.shape
+        if out is None:
+            out = self.empty(B, H, W, D, dtype=torch.uint8)
+        img, pitch, stride = _resize_layout(out, "Context.frames_resize_to_image")
+        self.check(self.L.aefft_frames_resize_to_image(self.h, _ptr(frames), int(_is_u8(frames)), Nx, Ny, m, _ptr(img), pitch, stride, W, H, B, D))
+        return out
+
+    def map_overlay(self, map, image, lut, lo, hi, alpha=128, smooth=True):
+        """A heat map onto images, IN PLACE (aefft_map_overlay_image): `map` is float32 [B][Mx][My] or [Mx][My] as Net.score_map / Net.ssim_map
+        return it; `image` uint8 [B][H][W][D] or [H][W][D], contiguous, row-padded or a region of interest; `lut` a uint8 device tensor [256][D]
+        (heat_lut gives a default).  k = clamp(round((m - lo) * 255 / (hi - lo)), 0, 255) per map entry (hi < lo inverts the scale), carried to
+        the pixels bilinearly (smooth) or per tile, then image = (alpha * lut[k] + (256 - alpha) * image + 128) >> 8 with alpha in 0..256.
+        Returns `image`.  One launch, nothing waits for the device."""
+        m, img, pitch, stride = _overlay_args(map, image, lut, lo, hi, alpha)
+        B, H, W, D = img.shape
+        self.check(self.L.aefft_map_overlay_image(self.h, _ptr(m), m.shape[1], m.shape[2], float(lo), float(hi), 1 if smooth else 0, _ptr(lut), int(alpha),
+                                                  _ptr(img), pitch, stride, W, H, B, D))
+        return image
 
     def set_flags(self, *names):
         """Development switches (include/aefft.h AEFFT_F_*), by name without the prefix; no names = defaults."""

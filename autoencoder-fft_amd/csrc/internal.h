@@ -74,6 +74,15 @@ hipError_t launch_image_pack(const void* frames, bool f32, unsigned char* image,
 // D in 1..4, W, H, Nx, Ny in 1..8192, pitch >= W D (hipErrorInvalidValue otherwise); any alignment of image, pitch and stride, frames 16-byte aligned.
 hipError_t launch_image_resize(const unsigned char* image, size_t pitch, size_t stride, int W, int H, int mode, void* frames, bool f32,
                                int B, int D, int Nx, int Ny, hipStream_t st);
+// ---- present_kernels.hip (aefft_frames_resize_to_image, aefft_map_overlay_image) ----
+// frames [B][D][Nx][Ny] (float when f32, through px_u8) -> B images of H rows of `pitch` bytes, image b at b * stride, W x H interleaved pixels: the same
+// two resizes with the roles swapped (mode 1: W <= Nx and H <= Ny) and SpinToImage_C's transposition in one launch.  Shape rules as above.
+hipError_t launch_frames_resize(const void* frames, bool f32, int Nx, int Ny, int mode, unsigned char* image, size_t pitch, size_t stride,
+                                int W, int H, int B, int D, hipStream_t st);
+// map [B][Mx][My] (Mx, My in 1..1024) -> k0 = px_u8((m - lo) * inv) -> bilinear (smooth) or per-tile index k -> lut[k][d] blended IN PLACE onto the
+// images with weight alpha / 256 (alpha in 0..256); lut: 256 * D bytes of any alignment.
+hipError_t launch_map_overlay(const float* map, int Mx, int My, float lo, float inv, int smooth, const unsigned char* lut, int alpha,
+                              unsigned char* image, size_t pitch, size_t stride, int W, int H, int B, int D, hipStream_t st);
 size_t fft_mid_elems(long planes, int Nx, int Wc);   // complex elements needed in `mid`
 // sizes that are not powers of two (cufftPlanMany takes any size, fft.cu:773-779): even n in 8..1024 through Bluestein's chirp-z form on the
 // power-of-two LDS passes; rows -> transpose -> rows -> transpose.  w1, w2: workspaces of fft_any_ws_elems complex each.

@@ -4,6 +4,7 @@
 #include "host.h"
 
 #include <algorithm>
+#include <cmath>
 
 using namespace aefft;
 
@@ -812,4 +813,67 @@ extern "C" int aefft_image_resize_to_frames(aefft_ctx* ctx, const unsigned char*
     RET_IF(join_recon(ctx));                          // (frames_d may be a buffer a deferred reconstruction is still writing)
     return launch_or_fail(ctx, KID_IMAGE, (double)B * D * ((double)W * H + (double)Nx * Ny * (frames_u8 ? 1.0 : 4.0)), "image_resize",
                           [&] { return launch_image_resize(image_d, pitch, image_stride, W, H, mode, frames_d, !frames_u8, B, D, Nx, Ny, ctx->cur); });
+}
+
+// the image rules aefft_frames_resize_to_image and aefft_map_overlay_image share (include/aefft.h "image boundary"): `extent` receives the bytes of
+// the B images, first byte to last
+template <class Bad>
+static int chk_present_image(const Bad& bad, size_t pitch, size_t image_stride, int W, int H, int B, int D, size_t* extent)
+{
+    const auto in = [](int v) { return v >= 1 && v <= 8192; };
+    if (D < 1 || D > 4) return bad("D must be 1..4 (grey, BGR, BGRA)");
+    if (B < 1 || !in(W) || !in(H)) return bad("B must be >= 1 and W, H in 1..8192");
+    if (pitch < (size_t)W * D) return bad("pitch must be at least W * D bytes");
+    const size_t half = ~size_t(0) >> 1;
+    if (pitch > half / (size_t)H) return bad("H * pitch does not fit the address space");
+    const size_t one = (size_t)(H - 1) * pitch + (size_t)W * D;                // the bytes of one image, up to its last row's W * D
+    if (B > 1 && image_stride < one) return bad("image_stride must be at least (H - 1) * pitch + W * D bytes for B > 1");
+    if (B > 1 && image_stride > (half - one) / (size_t)(B - 1)) return bad("B * image_stride does not fit the address space");
+    *extent = (B > 1 ? (size_t)(B - 1) * image_stride : 0) + one;
+    return AEFFT_OK;
+}
+static bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb)
+{
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+    return a0 < b0 + nb && b0 < a0 + na;
+}
+
+extern "C" int aefft_frames_resize_to_image(aefft_ctx* ctx, const void* frames_d, int frames_u8, int Nx, int Ny, int mode,
+                                            unsigned char* image_d, size_t pitch, size_t image_stride, int W, int H, int B, int D)
+{
+    const auto bad = [&](const char* rule) { return fail(ctx, AEFFT_EINVAL, (std::string("aefft_frames_resize_to_image: ") + rule).c_str()); };
+    if (!ctx || !image_d || !frames_d) return bad("null context, image or frames");
+    if (Nx < 1 || Ny < 1 || Nx > 8192 || Ny > 8192) return bad("Nx, Ny must be in 1..8192");
+    size_t extent = 0;
+    RET_IF(chk_present_image(bad, pitch, image_stride, W, H, B, D, &extent));
+    if (mode != AEFFT_RESIZE_LINEAR && mode != AEFFT_RESIZE_AREA) return bad("mode must be AEFFT_RESIZE_LINEAR or AEFFT_RESIZE_AREA");
+    if (mode == AEFFT_RESIZE_AREA && (W > Nx || H > Ny)) return bad("AEFFT_RESIZE_AREA does not enlarge: it needs W <= Nx and H <= Ny");
+    if (!aligned16(frames_d)) return bad("frames_d must be 16-byte aligned");
+    const size_t per = (size_t)D * Nx * Ny * (frames_u8 ? 1 : 4);              // (at most 2^30 bytes of one image's frames)
+    if ((size_t)B > (~size_t(0) >> 1) / per) return bad("B * D * Nx * Ny does not fit the address space");
+    if (ranges_overlap(frames_d, (size_t)B * per, image_d, extent)) return bad("the frame and image ranges overlap (the op is out-of-place)");
+    RET_IF(join_recon(ctx));                          // (frames_d may be the reconstruction of a step whose inverse transform is still on the side stream)
+    return launch_or_fail(ctx, KID_IMAGE, (double)B * D * ((double)Nx * Ny * (frames_u8 ? 1.0 : 4.0) + (double)W * H), "frames_resize",
+                          [&] { return launch_frames_resize(frames_d, !frames_u8, Nx, Ny, mode, image_d, pitch, image_stride, W, H, B, D, ctx->cur); });
+}
+
+extern "C" int aefft_map_overlay_image(aefft_ctx* ctx, const float* map_d, int Mx, int My, float lo, float hi, int smooth,
+                                       const unsigned char* lut_d, int alpha,
+                                       unsigned char* image_d, size_t pitch, size_t image_stride, int W, int H, int B, int D)
+{
+    const auto bad = [&](const char* rule) { return fail(ctx, AEFFT_EINVAL, (std::string("aefft_map_overlay_image: ") + rule).c_str()); };
+    if (!ctx || !map_d || !lut_d || !image_d) return bad("null context, map, lut or image");
+    if (Mx < 1 || My < 1 || Mx > 1024 || My > 1024) return bad("Mx, My must be in 1..1024");
+    size_t extent = 0;
+    RET_IF(chk_present_image(bad, pitch, image_stride, W, H, B, D, &extent));
+    if (alpha < 0 || alpha > 256) return bad("alpha must be 0..256");
+    const float inv = 255.0f / (hi - lo);
+    if (!std::isfinite(lo) || !std::isfinite(hi) || lo == hi || !std::isfinite(inv)) return bad("lo and hi must be finite and different (255 / (hi - lo) finite)");
+    if (!aligned16(map_d)) return bad("map_d must be 16-byte aligned");
+    if ((size_t)B > (~size_t(0) >> 1) / ((size_t)4 * Mx * My)) return bad("B * Mx * My does not fit the address space");
+    if (ranges_overlap(map_d, (size_t)B * Mx * My * 4, image_d, extent)) return bad("the map and image ranges overlap");
+    if (ranges_overlap(lut_d, (size_t)256 * D, image_d, extent)) return bad("the lut and image ranges overlap");
+    RET_IF(join_recon(ctx));                          // (image_d may hold a reconstruction that is still on the side stream)
+    return launch_or_fail(ctx, KID_IMAGE, (double)B * (4.0 * Mx * My + 2.0 * D * W * H) + 256.0 * D, "map_overlay",
+                          [&] { return launch_map_overlay(map_d, Mx, My, lo, inv, smooth, lut_d, alpha, image_d, pitch, image_stride, W, H, B, D, ctx->cur); });
 }

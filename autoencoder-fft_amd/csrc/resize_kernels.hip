@@ -24,43 +24,14 @@
 #define RZ_HD __host__ __device__ __forceinline__
 #define RZ_UNIFORM(x) __builtin_amdgcn_readfirstlane(x)
 #endif
+#include "resize_taps.h"                         // RzTap, rz_tap, rz_weight: the tap formulas, shared with present_kernels.hip
 
 namespace aefft {
 
-constexpr int RZ_LINEAR = 0, RZ_AREA = 1;        // == AEFFT_RESIZE_LINEAR / AEFFT_RESIZE_AREA
 constexpr int RZ_TJ = 16;                        // destination rows of a tile: 4 blocks of 4, so TI D * 4 <= 256 blocks, one per lane
 constexpr int RZ_MLP = 8;                        // source rows a wave has in flight while staging
 constexpr int RZ_BAND_WORDS = 8704;              // dwords of staged source rows a workgroup holds (34 KiB: a row of 8192 x 4 bytes + its slack fits)
 RZ_HD int rz_ti(int D) { return 64 / D; }        // destination columns of a tile: 64, 32, 21, 16
-RZ_HD int rz_min(int a, int b) { return a < b ? a : b; }
-RZ_HD int rz_max(int a, int b) { return a > b ? a : b; }
-
-struct RzTap { int lo, cnt, wf, wl; };
-// the taps of destination index i on an axis of S source and N destination samples (all products below 2^28: S, N <= 8192)
-RZ_HD RzTap rz_tap(int mode, int i, int S, int N)
-{
-    RzTap t;
-    if (mode == RZ_LINEAR) {
-        const int n = (2 * i + 1) * S - N, den = 2 * N;
-        int s = n >= 0 ? n / den : -((-n + den - 1) / den);                      // floor
-        int w = (4096 * (n - s * den) + den) / (2 * den);                       // round(2048 r / den), halves up
-        if (s < 0) { s = 0; w = 0; }
-        if (s >= S - 1) { s = S - 1; w = 0; }
-        t.lo = s; t.cnt = rz_min(s + 1, S - 1) - s + 1; t.wf = 2048 - w; t.wl = w;
-    } else {
-        const int a = i * S, b = a + S;                                          // the cell [i S, (i + 1) S) in units of 1 / N source pixels
-        const int lo = a / N, hi = (b - 1) / N;
-        t.lo = lo; t.cnt = hi - lo + 1; t.wf = rz_min(b, (lo + 1) * N) - a; t.wl = b - hi * N;
-    }
-    return t;
-}
-// weight of source index k for a tap (0 outside it); mid = the destination size of the axis
-RZ_HD int rz_weight(const RzTap& t, int k, int mid)
-{
-    const int r = k - t.lo;
-    if (r < 0 || r >= t.cnt) return 0;
-    return r == 0 ? t.wf : (r == t.cnt - 1 ? t.wl : mid);
-}
 
 struct RzArgs {
     const unsigned char* image; size_t pitch, stride; void* frames;

@@ -268,6 +268,54 @@ enum { AEFFT_RESIZE_LINEAR = 0, AEFFT_RESIZE_AREA = 1 };
 int aefft_image_resize_to_frames(aefft_ctx* ctx, const unsigned char* image_d, size_t pitch, size_t image_stride,
                                  int W, int H, int mode, void* frames_d, int frames_u8, int B, int D, int Nx, int Ny);
 
+/* aefft_frames_resize_to_image: the mirror of aefft_image_resize_to_frames -- frames of ANY size back to camera-sized images, SpinToImage_C
+ * (autoencoder.cpp:217-223) and the resize in one launch, so that a 512^2 reconstruction is written into the 640 x 480 video it came from.
+ * Source: the library's [B][D][Nx][Ny] frames, 16-byte aligned, unsigned char when frames_u8 != 0, float otherwise.  The source sample at column
+ * x, row y, channel d is  p[y][x] = frames[b][d][x][y]  for 8-bit frames and  px_u8(frames[b][d][x][y])  for float frames -- px_u8 is SpinToImage_C's
+ * rule exactly as aefft_frames_to_image applies it: clamp((int)round(v), 0, 255), halves away from zero, NaN -> 0, -inf -> 0, +inf -> 255.  So
+ * float frames are first turned into pixels, then resized.
+ * Destination: B images of H rows of `pitch` bytes; image b starts at b * image_stride (ignored when B == 1); pixel (row y, column x), channel d,
+ * is the byte at  y * pitch + x * D + d.  pitch >= W * D; for B > 1, image_stride >= (H - 1) * pitch + W * D.  image_d, pitch and image_stride may
+ * have ANY alignment (all three multiples of 4: the image side stores dwords, bytes otherwise; the same bytes come out).  Bytes of a row beyond
+ * W * D are never written.  A region of interest of a larger image is image_d + y0 * pitch + x0 * D with the parent's pitch and stride.
+ * Shapes: D in 1..4; Nx, Ny, W, H in 1..8192, odd sizes included; B >= 1.
+ * Arithmetic: all-integer, the per-axis formulas of AEFFT_RESIZE_LINEAR and AEFFT_RESIZE_AREA above with the roles swapped -- source sizes
+ * (Nx, Ny), destination sizes (W, H).  The output is always 8-bit: LINEAR (v + 2^21) >> 22; AREA floor((2 num + Nx Ny) / (2 Nx Ny)), which requires
+ * W <= Nx and H <= Ny.
+ * Consequences: with W == Nx and H == Ny both modes give exactly aefft_frames_to_image's bytes.  For every accepted argument the result equals the
+ * composition of three existing calls, bit for bit: aefft_frames_to_image(F) -> aefft_image_resize_to_frames(.., (W, H), mode, 8-bit) ->
+ * aefft_frames_to_image; this call does it in one launch, with no intermediate image.  The relation to OpenCV's own resize is that of
+ * aefft_image_resize_to_frames, and as unmeasured.
+ * One launch on the context's stream; no host synchronisation, no allocation, no workspace; safe under stream capture.  Out-of-place.
+ * AEFFT_EINVAL, with aefft_last_error starting "aefft_frames_resize_to_image: " and naming the rule, nothing enqueued and the outputs untouched: a
+ * null context or pointer, D or a size out of range, an unknown mode, AREA with an enlarging axis, pitch < W * D, image_stride too small for
+ * B > 1, frames_d not 16-byte aligned, source and destination byte ranges that overlap, sizes that overflow the address space. */
+int aefft_frames_resize_to_image(aefft_ctx* ctx, const void* frames_d, int frames_u8, int Nx, int Ny, int mode,
+                                 unsigned char* image_d, size_t pitch, size_t image_stride, int W, int H, int B, int D);
+
+/* aefft_map_overlay_image: a heat map onto an image, in place -- the [B][Nx/t][Ny/t] maps of aefft_net_score_map / aefft_net_ssim_map coloured
+ * and blended onto the camera-sized images on the device.
+ * map_d: float [B][Mx][My], 16-byte aligned, the layout those calls write: Mx along image columns, My along image rows, My contiguous; Mx, My in
+ * 1..1024.  lut_d: a colour table of 256 * D bytes on the device, entry k, channel d, at k * D + d; any alignment; supplied by the caller (the
+ * library ships no colour map).  The image layout and shape rules are those of aefft_frames_resize_to_image.  alpha in 0..256.  lo, hi finite and
+ * lo != hi (255 / (hi - lo) must be finite in float); hi < lo inverts the scale, which is what an SSIM map wants.
+ * Definition (every step can be restated exactly in numpy):
+ *   1. inv = 255.0f / (hi - lo), computed once on the host in float.
+ *   2. k0[I][J] = px_u8((map[b][I][J] - lo) * inv): the subtraction and the product each rounded to float32; px_u8 as above (NaN -> 0, clamped
+ *      to 0..255, halves away from zero).
+ *   3. smooth == 0:  k(x, y) = k0[floor(x Mx / W)][floor(y My / H)], the tile the pixel lies in.
+ *   4. smooth != 0:  the AEFFT_RESIZE_LINEAR taps on the axes (Mx -> W) and (My -> H) applied to k0, k = (v + 2^21) >> 22.
+ *   5. image[y][x][d] = (alpha * lut[k][d] + (256 - alpha) * image[y][x][d] + 128) >> 8.
+ * alpha = 0 leaves every byte as it was; alpha = 256 writes the table's colour exactly.  Bytes beyond W * D of a row are neither read nor written.
+ * One launch on the context's stream; no host synchronisation, no allocation, no workspace; safe under stream capture.  Accounted under the
+ * profile id `image` with B (4 Mx My + 2 W H D) + 256 D bytes.
+ * AEFFT_EINVAL, with aefft_last_error starting "aefft_map_overlay_image: " and naming the rule, nothing enqueued and the image untouched: a null
+ * context or pointer, a size, D or alpha out of range, non-finite or equal lo / hi, map_d not 16-byte aligned, pitch or image_stride too small,
+ * map_d or lut_d overlapping the image range. */
+int aefft_map_overlay_image(aefft_ctx* ctx, const float* map_d, int Mx, int My, float lo, float hi, int smooth,
+                            const unsigned char* lut_d, int alpha,
+                            unsigned char* image_d, size_t pitch, size_t image_stride, int W, int H, int B, int D);
+
 /* ---- network level: the resident, batched form of autoenc_fft / backprop_fft ------------------ */
 typedef struct {
     int D, Nx, Ny;        /* input frames [B][D][Nx][Ny] */
