@@ -78,6 +78,7 @@ SIGNATURES = {
     "aefft_image_resize_to_frames": (_i, [_vp, _vp, C.c_size_t, C.c_size_t, _i, _i, _i, _vp, _i, _i, _i, _i, _i]),
     "aefft_frames_resize_to_image": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, C.c_size_t, C.c_size_t, _i, _i, _i, _i]),
     "aefft_map_overlay_image": (_i, [_vp, _fp, _i, _i, _f, _f, _i, _vp, _i, _vp, C.c_size_t, C.c_size_t, _i, _i, _i, _i]),
+    "aefft_frames_degrade": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _f, _f, C.c_ulonglong, C.c_ulonglong]),
     "aefft_net_create": (_i, [_vp, C.POINTER(NetDesc), C.POINTER(_vp)]),
     "aefft_net_create_ex": (_i, [_vp, C.POINTER(NetDesc), C.c_uint, C.POINTER(_vp)]),
     "aefft_net_destroy": (None, [_vp]),
@@ -285,6 +286,40 @@ def _overlay_args(map, image, lut, lo, hi, alpha):
     if int(alpha) != alpha or not 0 <= alpha <= 256:
         raise ValueError(f"{what}: alpha must be an integer in 0..256")
     return m, img, pitch, stride
+
+
+def _frames_degrade_args(frames, blur, sigma, impulse, seed, first_frame, out, dtype):
+    """the checks of Context.frames_degrade that need no device: (blur, sigma, impulse, seed, first_frame, the result's dtype) as the C call takes
+    them; `out`, when given, has the frames' shape and is `frames` itself only in the element-wise case (blur == 0, the same dtype)"""
+    what = "Context.frames_degrade"
+    if frames.dtype not in (torch.uint8, torch.float32) or frames.dim() != 4 or not frames.is_contiguous() or min(frames.shape) < 1:
+        raise ValueError(f"{what}: frames must be a contiguous, non-empty uint8 or float32 tensor [B][D][Nx][Ny]")
+    B, D, Nx, Ny = frames.shape
+    if not 1 <= D <= 4 or Nx > 8192 or Ny > 8192:
+        raise ValueError(f"{what}: D must be 1..4 and Nx, Ny in 1..8192; got shape {tuple(frames.shape)}")
+    if isinstance(blur, bool) or int(blur) != blur or not 0 <= blur <= 4:
+        raise ValueError(f"{what}: blur must be an integer in 0..4")
+    if not np.isfinite(sigma) or not 0 <= sigma <= 255:
+        raise ValueError(f"{what}: sigma must be finite and in 0..255")
+    if not np.isfinite(impulse) or not 0 <= impulse <= 1:
+        raise ValueError(f"{what}: impulse must be finite and in 0..1")
+    for name, v in (("seed", seed), ("first_frame", first_frame)):
+        if isinstance(v, bool) or int(v) != v or not 0 <= v < 2 ** 64:
+            raise ValueError(f"{what}: {name} must be an integer in 0..2^64 - 1")
+    if out is not None:
+        if dtype is not None and dtype != out.dtype:
+            raise ValueError(f"{what}: dtype and out.dtype differ")
+        dtype = out.dtype
+    elif dtype is None:
+        dtype = frames.dtype
+    if dtype not in (torch.uint8, torch.float32):
+        raise ValueError(f"{what}: the result must be uint8 or float32")
+    if out is not None:
+        if tuple(out.shape) != tuple(frames.shape) or not out.is_contiguous():
+            raise ValueError(f"{what}: out must be a contiguous tensor of shape {tuple(frames.shape)}")
+        if out.data_ptr() == frames.data_ptr() and (blur != 0 or out.dtype != frames.dtype):
+            raise ValueError(f"{what}: in place (out=frames) needs blur == 0 and the frames' own dtype")
+    return int(blur), float(sigma), float(impulse), int(seed), int(first_frame), dtype
 
 
 class Context:
@@ -576,6 +611,23 @@ class Context:
         self.check(self.L.aefft_map_overlay_image(self.h, _ptr(m), m.shape[1], m.shape[2], float(lo), float(hi), 1 if smooth else 0, _ptr(lut), int(alpha),
                                                   _ptr(img), pitch, stride, W, H, B, D))
         return image
+
+    def frames_degrade(self, frames, blur=0, sigma=0.0, impulse=0.0, seed=0, first_frame=0, out=None, dtype=None):
+        """The degraded input of target training from the clean frames (aefft_frames_degrade), one launch: `frames` uint8 or float32
+        [B][D][Nx][Ny] (float values become pixels first) -> the binomial blur of radius `blur` in 0..4 (2 blur + 1 taps per axis, edges
+        replicated), additive noise of standard deviation `sigma` grey levels (an Irwin-Hall sum of six bytes: approximately normal, bounded at
+        +-4.23 sigma) and salt-and-pepper impulses of probability `impulse` per element, from Philox4x32-10 keyed by `seed` and counted by
+        (first_frame + b, the element's index): frame b's result depends on nothing else, so a data-parallel rank passes
+        first_frame = step * global_batch + rank * B.  Returns, or fills `out` with, frames of `dtype` uint8 (rounded and clipped) or float32
+        (not clipped); dtype defaults to the source's; out=frames is the in-place form (blur == 0 and the same dtype only).  All-integer
+        arithmetic (include/aefft.h): the same arguments always give the same bytes.  Nothing waits for the device."""
+        blur, sigma, impulse, seed, first_frame, dtype = _frames_degrade_args(frames, blur, sigma, impulse, seed, first_frame, out, dtype)
+        B, D, Nx, Ny = frames.shape
+        if out is None:
+            out = self.empty(B, D, Nx, Ny, dtype=dtype)
+        self.check(self.L.aefft_frames_degrade(self.h, _ptr(frames), int(_is_u8(frames)), _ptr(out), int(_is_u8(out)), B, D, Nx, Ny,
+                                               blur, sigma, impulse, seed, first_frame))
+        return out
 
     def set_flags(self, *names):
         """Development switches (include/aefft.h AEFFT_F_*), by name without the prefix; no names = defaults."""

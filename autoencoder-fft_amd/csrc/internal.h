@@ -83,6 +83,13 @@ hipError_t launch_frames_resize(const void* frames, bool f32, int Nx, int Ny, in
 // images with weight alpha / 256 (alpha in 0..256); lut: 256 * D bytes of any alignment.
 hipError_t launch_map_overlay(const float* map, int Mx, int My, float lo, float inv, int smooth, const unsigned char* lut, int alpha,
                               unsigned char* image, size_t pitch, size_t stride, int W, int H, int B, int D, hipStream_t st);
+// ---- degrade_kernels.hip (aefft_frames_degrade) ----
+// frames [B][D][Nx][Ny] -> frames of the same shape (float when the side's f32 is set; a float source through px_u8): the binomial blur of radius
+// `blur` in 0..4, the Irwin-Hall noise of standard deviation sigma and the impulses of probability `impulse`, keyed by (seed, first_frame + b),
+// all-integer behind the two quantisations of dg_quantise (include/aefft.h).  D in 1..4, Nx, Ny in 1..8192, sigma in 0..255, impulse in 0..1
+// (hipErrorInvalidValue otherwise); both sides 16-byte aligned; dst == src only with blur == 0 and the same element type.
+hipError_t launch_degrade(const void* src, bool src_f32, void* dst, bool dst_f32, int B, int D, int Nx, int Ny, int blur, float sigma, float impulse,
+                          unsigned long long seed, unsigned long long first_frame, hipStream_t st);
 size_t fft_mid_elems(long planes, int Nx, int Wc);   // complex elements needed in `mid`
 // sizes that are not powers of two (cufftPlanMany takes any size, fft.cu:773-779): even n in 8..1024 through Bluestein's chirp-z form on the
 // power-of-two LDS passes; rows -> transpose -> rows -> transpose.  w1, w2: workspaces of fft_any_ws_elems complex each.

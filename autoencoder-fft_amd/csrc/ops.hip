@@ -877,3 +877,24 @@ extern "C" int aefft_map_overlay_image(aefft_ctx* ctx, const float* map_d, int M
     return launch_or_fail(ctx, KID_IMAGE, (double)B * (4.0 * Mx * My + 2.0 * D * W * H) + 256.0 * D, "map_overlay",
                           [&] { return launch_map_overlay(map_d, Mx, My, lo, inv, smooth, lut_d, alpha, image_d, pitch, image_stride, W, H, B, D, ctx->cur); });
 }
+
+extern "C" int aefft_frames_degrade(aefft_ctx* ctx, const void* src_d, int src_u8, void* dst_d, int dst_u8, int B, int D, int Nx, int Ny,
+                                    int blur, float sigma, float impulse, unsigned long long seed, unsigned long long first_frame)
+{
+    const auto bad = [&](const char* rule) { return fail(ctx, AEFFT_EINVAL, (std::string("aefft_frames_degrade: ") + rule).c_str()); };
+    if (!ctx || !src_d || !dst_d) return bad("null context, source or destination");
+    if (D < 1 || D > 4) return bad("D must be 1..4 (grey, BGR, BGRA)");
+    if (B < 1 || Nx < 1 || Ny < 1 || Nx > 8192 || Ny > 8192) return bad("B must be >= 1 and Nx, Ny in 1..8192");
+    if (blur < 0 || blur > 4) return bad("blur must be 0..4");
+    if (!std::isfinite(sigma) || sigma < 0.f || sigma > 255.f) return bad("sigma must be finite and in 0..255");
+    if (!std::isfinite(impulse) || impulse < 0.f || impulse > 1.f) return bad("impulse must be finite and in 0..1");
+    if (!aligned16(src_d) || !aligned16(dst_d)) return bad("src_d and dst_d must be 16-byte aligned");
+    const size_t per = (size_t)D * Nx * Ny, ss = src_u8 ? 1 : 4, ds = dst_u8 ? 1 : 4;   // (at most 2^28 elements of a frame)
+    if ((size_t)B > (~size_t(0) >> 1) / (4 * per)) return bad("B * D * Nx * Ny does not fit the address space");
+    const bool in_place = dst_d == src_d && blur == 0 && ss == ds;
+    if (!in_place && ranges_overlap(src_d, (size_t)B * per * ss, dst_d, (size_t)B * per * ds))
+        return bad("the source and destination ranges overlap (in place needs dst_d == src_d, blur == 0 and src_u8 == dst_u8)");
+    RET_IF(join_recon(ctx));                          // (src_d may be a reconstruction that is still on the side stream)
+    return launch_or_fail(ctx, KID_IMAGE, (double)B * per * (double)(ss + ds), "frames_degrade",
+                          [&] { return launch_degrade(src_d, !src_u8, dst_d, !dst_u8, B, D, Nx, Ny, blur, sigma, impulse, seed, first_frame, ctx->cur); });
+}

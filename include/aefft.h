@@ -316,6 +316,47 @@ int aefft_map_overlay_image(aefft_ctx* ctx, const float* map_d, int Mx, int My, 
                             const unsigned char* lut_d, int alpha,
                             unsigned char* image_d, size_t pitch, size_t image_stride, int W, int H, int B, int D);
 
+/* aefft_frames_degrade: the degraded input of target training from the clean frame -- blur, additive noise and impulses in one launch, so that
+ * aefft_net_step_grad_target(frames = degraded, targets = clean) needs no float copies of the frames and no generator outside the library.
+ * src_d, dst_d: the library's [B][D][Nx][Ny] frames, 16-byte aligned, each unsigned char when its _u8 flag != 0, float otherwise.
+ * Shapes: D in 1..4; Nx, Ny in 1..8192, odd sizes included; B >= 1.
+ * Definition: everything behind the host's two quantisations (m and t below) is integer arithmetic, so a numpy restatement gives the same bits.
+ *   1. Pixels.  p[b][d][i][j] is the source byte; for a float source px_u8(src[b][d][i][j]), SpinToImage_C's rule exactly as
+ *      aefft_frames_to_image applies it: NaN -> 0, clamp to 0..255, halves away from zero.  So float frames are first turned into pixels, as in
+ *      aefft_frames_resize_to_image.
+ *   2. Blur, blur = r in 0..4: the separable binomial filter of 2r+1 taps per axis, w_k = C(2r, k) (sum 4^r), indices clamped to the plane
+ *      (edges replicated):  h[i][j] = sum_k w_k p[clamp(i+k-r)][j],  v[i][j] = sum_l w_l h[i][clamp(j+l-r)]  <= 255 * 16^r < 2^24.  The working
+ *      value in Q16 is  u = v << (16 - 4r), exact: no rounding anywhere; r = 0 gives u = p << 16.
+ *   3. Random words.  Philox4x32-10 with the standard constants (multipliers 0xD2511F53, 0xCD9E8D57; key increments 0x9E3779B9, 0xBB67AE85);
+ *      key = (seed low word, seed high word).  For the element of linear index n = (d Nx + i) Ny + j of frame g = first_frame + b (64-bit,
+ *      wrapping) the counter is (n >> 1, 0, g low word, g high word): one call serves two elements.  An even n takes the output words
+ *      (a, c) = (x0, x1), an odd n (x2, x3).  T = (sum of the four bytes of a) + (sum of the two low bytes of c) - 765;  hsel = c >> 16.
+ *   4. Noise.  m = floor(((double)sigma * 65536.0) / sqrt(32767.5) + 0.5), once on the host;  u += T * m.  T is an Irwin-Hall sum of six
+ *      bytes: zero mean, standard deviation sqrt(32767.5) exactly, excess kurtosis -0.2, bounded at +-4.23 sigma.  The noise is APPROXIMATELY
+ *      normal, not normal: lighter tails and a hard bound.  The effective sigma is m sqrt(32767.5) / 65536: sigma quantised to about 1/362 of a
+ *      grey level.  With sigma <= 255, |u| < 2^27: everything fits 32 bits.
+ *   5. Impulses.  t = floor((double)impulse * 65536.0 + 0.5), once on the host.  If hsel < t the element is replaced:  u = 255 << 16 when
+ *      a & 1, else u = 0.  Resolution 1/65536; impulse = 1 replaces every element.  Each element (channel) is hit on its own.
+ *   6. Output.  8-bit: clamp((u + 32768) >> 16, 0, 255), arithmetic shift -- it clips as a sensor does.  Float: (float)u * 2^-16, the
+ *      int32 -> float conversion rounding to nearest even; not clamped: it models additive noise.
+ * Consequences: blur = 0, sigma = 0, impulse = 0 is a copy for 8-bit -> 8-bit, px_u8 for float -> 8-bit and the exact conversion for
+ * 8-bit -> float.  A frame's result depends only on (seed, first_frame + b) and its own pixels, so
+ *   degrade(B = 2, first_frame = f)[1] == degrade(B = 1, first_frame = f + 1)[0]:
+ * a data-parallel rank passes first_frame = step * global_batch + rank * B, and the union over the ranks is the single-process batch.  A constant
+ * frame stays constant under any blur.  The same arguments always give the same bytes, on every route (Ny % 4 == 0: the frame side moves dwords /
+ * float4; single elements otherwise).
+ * In place: dst_d == src_d is allowed exactly when blur == 0 and src_u8 == dst_u8 (the operation is then element-wise); any other overlap of the
+ * two byte ranges is an error.
+ * One launch on the context's stream; no host synchronisation, no allocation, no workspace; safe under stream capture.  Accounted under the
+ * profile id `image` with the bytes read plus the bytes written, B D Nx Ny (source element size + destination element size).
+ * AEFFT_EINVAL, with aefft_last_error starting "aefft_frames_degrade: " and naming the rule, nothing enqueued and the outputs untouched: a null
+ * context or pointer; D, a size or B out of range; blur outside 0..4; sigma not finite, negative or above 255; impulse not finite or outside
+ * 0..1; a pointer not 16-byte aligned; overlapping ranges other than the in-place case above; sizes that overflow the address space. */
+int aefft_frames_degrade(aefft_ctx* ctx, const void* src_d, int src_u8, void* dst_d, int dst_u8,
+                         int B, int D, int Nx, int Ny,
+                         int blur, float sigma, float impulse,
+                         unsigned long long seed, unsigned long long first_frame);
+
 /* ---- network level: the resident, batched form of autoenc_fft / backprop_fft ------------------ */
 typedef struct {
     int D, Nx, Ny;        /* input frames [B][D][Nx][Ny] */
