@@ -43,6 +43,12 @@ class NetDesc(C.Structure):
                 ("scale", C.POINTER(C.c_int)), ("batch", C.c_int)]
 
 
+class YuvDesc(C.Structure):
+    """include/aefft.h aefft_yuv_desc"""
+    _fields_ = [("format", C.c_int), ("matrix", C.c_int), ("W", C.c_int), ("H", C.c_int),
+                ("plane", C.c_void_p * 3), ("pitch", C.c_size_t * 3), ("stride", C.c_size_t * 3)]
+
+
 _lib = None
 _vp, _fp, _i, _l, _f = C.c_void_p, C.c_void_p, C.c_int, C.c_long, C.c_float   # device float* passed as void*
 
@@ -79,6 +85,8 @@ SIGNATURES = {
     "aefft_frames_resize_to_image": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, C.c_size_t, C.c_size_t, _i, _i, _i, _i]),
     "aefft_map_overlay_image": (_i, [_vp, _fp, _i, _i, _f, _f, _i, _vp, _i, _vp, C.c_size_t, C.c_size_t, _i, _i, _i, _i]),
     "aefft_frames_degrade": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _f, _f, C.c_ulonglong, C.c_ulonglong]),
+    "aefft_yuv_to_image": (_i, [_vp, C.POINTER(YuvDesc), _i, _vp, C.c_size_t, C.c_size_t, _i]),
+    "aefft_yuv_resize_to_frames": (_i, [_vp, C.POINTER(YuvDesc), _i, _i, _vp, _i, _i, _i, _i]),
     "aefft_net_create": (_i, [_vp, C.POINTER(NetDesc), C.POINTER(_vp)]),
     "aefft_net_create_ex": (_i, [_vp, C.POINTER(NetDesc), C.c_uint, C.POINTER(_vp)]),
     "aefft_net_destroy": (None, [_vp]),
@@ -212,6 +220,9 @@ def _image_layout(image, what):
 
 
 RESIZE_MODES = {"linear": 0, "area": 1}      # AEFFT_RESIZE_LINEAR, AEFFT_RESIZE_AREA
+YUV_FORMATS = {"nv12": 0, "i420": 1, "yuyv": 2}      # AEFFT_YUV_NV12, AEFFT_YUV_I420, AEFFT_YUV_YUYV
+YUV_MATRICES = {"bt601": 0, "bt709": 1, "jpeg": 2}   # AEFFT_YUV_BT601, AEFFT_YUV_BT709, AEFFT_YUV_JPEG
+YUV_ORDERS = {"bgr": 0, "rgb": 1, "gray": 2}         # AEFFT_YUV_BGR, AEFFT_YUV_RGB, AEFFT_YUV_GRAY: D = 3, 3, 1
 
 
 def _resize_layout(image, what):
@@ -231,6 +242,47 @@ def _resize_layout(image, what):
         raise ValueError(f"{what}: the image must have stride(-1) == 1, stride(-2) == D, stride(-3) = pitch >= W * D and a batch stride of at least "
                          f"(H - 1) * pitch + W * D; got shape {tuple(image.shape)} with strides {tuple(image.stride())}")
     return img, int(pitch), int(sb if B > 1 else extent)
+
+
+def _yuv_source(planes, fmt, matrix, order, what):
+    """the checks of the YUV calls that need no device: (the filled YuvDesc, B, W, H, D, the plane tensors the descriptor points into).  `planes`
+    is a tuple of uint8 tensors -- nv12 (y [B][H][W], uv [B][Hc][Wc][2]), i420 (y, u [B][Hc][Wc], v), yuyv (yuyv [B][H][W/2][4],), or the same
+    without the batch axis -- each contiguous or a view with stride(-1) == 1 (the interleaved axes whole), a row pitch and any sufficient batch
+    stride, checked like _resize_layout: two views into one decoder surface therefore work.  With order "gray" only the luma plane is looked at."""
+    if fmt not in YUV_FORMATS or matrix not in YUV_MATRICES or order not in YUV_ORDERS:
+        raise ValueError(f"{what}: fmt must be one of {sorted(YUV_FORMATS)}, matrix of {sorted(YUV_MATRICES)}, order of {sorted(YUV_ORDERS)}")
+    try:
+        planes = tuple(planes)
+    except TypeError:
+        raise ValueError(f"{what}: planes must be a tuple of uint8 tensors") from None
+    need = {"nv12": 2, "i420": 3, "yuyv": 1}[fmt]
+    used = 1 if order == "gray" else need
+    if len(planes) not in (need, used) or any(p is None for p in planes[:used]):
+        raise ValueError(f"{what}: {fmt} takes {need} plane(s)")
+    inner = {"nv12": (1, 2), "i420": (1, 1, 1), "yuyv": (4,)}[fmt]      # interleaved bytes per element of a plane's row
+    views, desc = [], YuvDesc()
+    desc.format, desc.matrix = YUV_FORMATS[fmt], YUV_MATRICES[matrix]
+    B = W = H = None
+    for k, p in enumerate(planes[:used]):
+        rank = 3 if inner[k] == 1 else 4
+        if not isinstance(p, torch.Tensor) or p.dtype != torch.uint8 or p.dim() not in (rank - 1, rank):
+            raise ValueError(f"{what}: plane {k} must be a uint8 tensor with {rank} axes (or {rank - 1}, unbatched)")
+        v = p if p.dim() == rank else p.unsqueeze(0)
+        v = v if rank == 4 else v.unsqueeze(-1)
+        img, pitch, stride = _resize_layout(v, f"{what}: plane {k}")
+        b, rows, cols, e = img.shape
+        if e != inner[k]:
+            raise ValueError(f"{what}: plane {k} must have {inner[k]} interleaved bytes per element, got {e}")
+        if k == 0:
+            B, H, W = b, rows, cols * (2 if fmt == "yuyv" else 1)
+        elif (b, rows, cols) != (B, (H + 1) // 2, (W + 1) // 2):
+            raise ValueError(f"{what}: plane {k} must be {(B, (H + 1) // 2, (W + 1) // 2)} chroma samples for a luma plane of {(B, H, W)}, got {(b, rows, cols)}")
+        views.append(img)
+        desc.plane[k], desc.pitch[k], desc.stride[k] = img.data_ptr(), pitch, stride
+    if W > 8192 or H > 8192:
+        raise ValueError(f"{what}: W, H must be in 1..8192")
+    desc.W, desc.H = W, H
+    return desc, B, W, H, 1 if order == "gray" else 3, views
 
 
 def heat_lut(D=3):
@@ -627,6 +679,47 @@ class Context:
             out = self.empty(B, D, Nx, Ny, dtype=dtype)
         self.check(self.L.aefft_frames_degrade(self.h, _ptr(frames), int(_is_u8(frames)), _ptr(out), int(_is_u8(out)), B, D, Nx, Ny,
                                                blur, sigma, impulse, seed, first_frame))
+        return out
+
+    def yuv_to_image(self, planes, fmt, matrix="bt601", order="bgr", out=None):
+        """Colour conversion on the device (aefft_yuv_to_image): `planes` is a tuple of uint8 device tensors -- fmt "nv12": (y [B][H][W],
+        uv [B][Hc][Wc][2]); "i420": (y, u [B][Hc][Wc], v); "yuyv": (yuyv [B][H][W/2][4],); unbatched tensors too -- each contiguous or a view with a
+        row pitch and any sufficient batch stride (two views into one decoder surface work; ValueError otherwise).  matrix "bt601", "bt709"
+        (limited range) or "jpeg" (601 full range); order "bgr", "rgb" (D = 3) or "gray" (D = 1, the chroma planes are not read).  Chroma is
+        replicated (nearest).  Returns, or fills `out` with, the uint8 image rows [B][H][W][D]; `out` may be a row-padded view or a region of
+        interest.  All-integer arithmetic (include/aefft.h).  One launch, nothing waits for the device."""
+        what = "Context.yuv_to_image"
+        desc, B, W, H, D, keep = _yuv_source(planes, fmt, matrix, order, what)      # (keep: the views the descriptor points into)
+        if out is None:
+            out = self.empty(B, H, W, D, dtype=torch.uint8)
+        img, pitch, stride = _resize_layout(out, what)
+        if tuple(img.shape) != (B, H, W, D):
+            raise ValueError(f"{what}: out must have shape {(B, H, W, D)}")
+        self.check(self.L.aefft_yuv_to_image(self.h, C.byref(desc), YUV_ORDERS[order], _ptr(img), pitch, stride, B))
+        return out
+
+    def yuv_resize_to_frames(self, planes, fmt, size, matrix="bt601", order="bgr", mode="linear", out=None, dtype=torch.uint8):
+        """Colour conversion + resize + ImageToSpin_C on the device in one launch (aefft_yuv_resize_to_frames): `planes`, `fmt`, `matrix` and
+        `order` as for yuv_to_image; size = (Nx, Ny) and mode as for image_resize_to_frames.  Returns, or fills `out` with, the planar frames
+        [B][D][Nx][Ny] of `dtype` uint8 or float32 -- bit for bit yuv_to_image followed by image_resize_to_frames, without the image in
+        between.  Nothing waits for the device."""
+        what = "Context.yuv_resize_to_frames"
+        desc, B, W, H, D, keep = _yuv_source(planes, fmt, matrix, order, what)      # (keep: the views the descriptor points into)
+        if mode not in RESIZE_MODES:
+            raise ValueError(f"{what}: mode must be one of {sorted(RESIZE_MODES)}")
+        try:
+            Nx, Ny = (int(v) for v in size)
+        except (TypeError, ValueError):
+            raise ValueError(f"{what}: size must be (Nx, Ny)") from None
+        if out is None:
+            if dtype not in (torch.uint8, torch.float32):
+                raise ValueError(f"{what}: dtype must be torch.uint8 or torch.float32")
+            if Nx < 1 or Ny < 1:
+                raise ValueError(f"{what}: size must be positive")
+            out = self.empty(B, D, Nx, Ny, dtype=dtype)
+        elif out.dtype not in (torch.uint8, torch.float32) or tuple(out.shape) != (B, D, Nx, Ny) or not out.is_contiguous():
+            raise ValueError(f"{what}: out must be a contiguous uint8 or float32 tensor of shape {(B, D, Nx, Ny)}")
+        self.check(self.L.aefft_yuv_resize_to_frames(self.h, C.byref(desc), YUV_ORDERS[order], RESIZE_MODES[mode], _ptr(out), int(_is_u8(out)), B, Nx, Ny))
         return out
 
     def set_flags(self, *names):

@@ -90,6 +90,16 @@ hipError_t launch_map_overlay(const float* map, int Mx, int My, float lo, float 
 // (hipErrorInvalidValue otherwise); both sides 16-byte aligned; dst == src only with blur == 0 and the same element type.
 hipError_t launch_degrade(const void* src, bool src_f32, void* dst, bool dst_f32, int B, int D, int Nx, int Ny, int blur, float sigma, float impulse,
                           unsigned long long seed, unsigned long long first_frame, hipStream_t st);
+// ---- yuv_kernels.hip (aefft_yuv_to_image, aefft_yuv_resize_to_frames) ----
+// B video images of W x H luma samples, format 0 NV12 / 1 I420 / 2 YUYV in up to three planes (plane k of image b at plane[k] + b * stride[k]) -> the
+// integer colour conversion of include/aefft.h (matrix 0 BT601 / 1 BT709 / 2 JPEG; order 0 BGR / 1 RGB / 2 GRAY, D = 3, 3, 1) -> B interleaved images
+// (launch_yuv_image: layout as launch_frames_resize's destination), or the resize of launch_image_resize applied to those pixels -> frames
+// [B][D][Nx][Ny] (launch_yuv_resize), one launch each, no intermediate image.  W, H, Nx, Ny in 1..8192, YUYV: W even; any alignment of planes,
+// pitches and strides, frames 16-byte aligned (hipErrorInvalidValue for what the kernels cannot serve; the C entry points check the rest).
+hipError_t launch_yuv_image(int fmt, const unsigned char* const* plane, const size_t* pitch, const size_t* stride, int W, int H, int matrix, int order,
+                            unsigned char* image, size_t ipitch, size_t istride, int B, hipStream_t st);
+hipError_t launch_yuv_resize(int fmt, const unsigned char* const* plane, const size_t* pitch, const size_t* stride, int W, int H, int matrix, int order,
+                             int mode, void* frames, bool f32, int B, int Nx, int Ny, hipStream_t st);
 size_t fft_mid_elems(long planes, int Nx, int Wc);   // complex elements needed in `mid`
 // sizes that are not powers of two (cufftPlanMany takes any size, fft.cu:773-779): even n in 8..1024 through Bluestein's chirp-z form on the
 // power-of-two LDS passes; rows -> transpose -> rows -> transpose.  w1, w2: workspaces of fft_any_ws_elems complex each.

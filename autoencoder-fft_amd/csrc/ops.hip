@@ -898,3 +898,78 @@ extern "C" int aefft_frames_degrade(aefft_ctx* ctx, const void* src_d, int src_u
     return launch_or_fail(ctx, KID_IMAGE, (double)B * per * (double)(ss + ds), "frames_degrade",
                           [&] { return launch_degrade(src_d, !src_u8, dst_d, !dst_u8, B, D, Nx, Ny, blur, sigma, impulse, seed, first_frame, ctx->cur); });
 }
+
+// the source bytes one image's conversion reads: the luma samples and, unless the order is GRAY, the chroma samples (YUYV: the rows whole)
+static double yuv_bytes(const aefft_yuv_desc& s, int order)
+{
+    const double W = s.W, H = s.H, Wc = (s.W + 1) / 2, Hc = (s.H + 1) / 2;
+    if (s.format == AEFFT_YUV_YUYV) return 2.0 * W * H;
+    return W * H + (order == AEFFT_YUV_GRAY ? 0.0 : 2.0 * Wc * Hc);
+}
+// the source rules aefft_yuv_to_image and aefft_yuv_resize_to_frames share (include/aefft.h "image boundary"): `used` receives the planes the call
+// reads and `extent[k]` the bytes of plane k over the B images, first byte to last
+template <class Bad>
+static int chk_yuv_source(const Bad& bad, const aefft_yuv_desc* src, int order, int B, int* used, size_t* extent)
+{
+    const auto in = [](int v) { return v >= 1 && v <= 8192; };
+    if (src->format != AEFFT_YUV_NV12 && src->format != AEFFT_YUV_I420 && src->format != AEFFT_YUV_YUYV) return bad("format must be AEFFT_YUV_NV12, AEFFT_YUV_I420 or AEFFT_YUV_YUYV");
+    if (src->matrix != AEFFT_YUV_BT601 && src->matrix != AEFFT_YUV_BT709 && src->matrix != AEFFT_YUV_JPEG) return bad("matrix must be AEFFT_YUV_BT601, AEFFT_YUV_BT709 or AEFFT_YUV_JPEG");
+    if (order != AEFFT_YUV_BGR && order != AEFFT_YUV_RGB && order != AEFFT_YUV_GRAY) return bad("order must be AEFFT_YUV_BGR, AEFFT_YUV_RGB or AEFFT_YUV_GRAY");
+    if (B < 1 || !in(src->W) || !in(src->H)) return bad("B must be >= 1 and W, H in 1..8192");
+    const bool yuyv = src->format == AEFFT_YUV_YUYV;
+    if (yuyv && (src->W & 1)) return bad("YUYV needs an even W");
+    const size_t W = (size_t)src->W, H = (size_t)src->H, Wc = (W + 1) / 2, Hc = (H + 1) / 2;
+    // live bytes of a row and rows of each plane
+    const size_t live[3] = {yuyv ? 2 * W : W, src->format == AEFFT_YUV_NV12 ? 2 * Wc : Wc, Wc}, rows[3] = {H, Hc, Hc};
+    *used = order == AEFFT_YUV_GRAY || yuyv ? 1 : (src->format == AEFFT_YUV_NV12 ? 2 : 3);
+    const size_t half = ~size_t(0) >> 1;
+    for (int k = 0; k < *used; ++k) {
+        if (!src->plane[k]) return bad("null plane (NV12 needs plane[0..1], I420 plane[0..2], YUYV and AEFFT_YUV_GRAY plane[0])");
+        if (src->pitch[k] < live[k]) return bad("pitch too small: pitch[0] >= W (YUYV 2 W), NV12 pitch[1] >= 2 ceil(W / 2), I420 pitch[1], pitch[2] >= ceil(W / 2)");
+        if (src->pitch[k] > half / rows[k]) return bad("rows * pitch does not fit the address space");
+        const size_t one = (rows[k] - 1) * src->pitch[k] + live[k];
+        if (B > 1 && src->stride[k] < one) return bad("stride too small: each used stride[k] must be at least (rows - 1) * pitch[k] + the live bytes of a row for B > 1");
+        if (B > 1 && src->stride[k] > (half - one) / (size_t)(B - 1)) return bad("B * stride does not fit the address space");
+        extent[k] = (B > 1 ? (size_t)(B - 1) * src->stride[k] : 0) + one;
+    }
+    return AEFFT_OK;
+}
+
+extern "C" int aefft_yuv_to_image(aefft_ctx* ctx, const aefft_yuv_desc* src, int order, unsigned char* image_d, size_t pitch, size_t image_stride, int B)
+{
+    const auto bad = [&](const char* rule) { return fail(ctx, AEFFT_EINVAL, (std::string("aefft_yuv_to_image: ") + rule).c_str()); };
+    if (!ctx || !src || !image_d) return bad("null context, descriptor or image");
+    int used = 0;
+    size_t sext[3] = {0, 0, 0}, extent = 0;
+    RET_IF(chk_yuv_source(bad, src, order, B, &used, sext));
+    const int D = order == AEFFT_YUV_GRAY ? 1 : 3;
+    RET_IF(chk_present_image(bad, pitch, image_stride, src->W, src->H, B, D, &extent));
+    for (int k = 0; k < used; ++k)
+        if (ranges_overlap(src->plane[k], sext[k], image_d, extent)) return bad("a source plane and the image range overlap (the op is out-of-place)");
+    RET_IF(join_recon(ctx));                          // (a plane may be a buffer the side stream is still writing)
+    return launch_or_fail(ctx, KID_IMAGE, (double)B * (yuv_bytes(*src, order) + (double)D * src->W * src->H), "yuv_to_image", [&] {
+        return launch_yuv_image(src->format, src->plane, src->pitch, src->stride, src->W, src->H, src->matrix, order, image_d, pitch, image_stride, B, ctx->cur);
+    });
+}
+
+extern "C" int aefft_yuv_resize_to_frames(aefft_ctx* ctx, const aefft_yuv_desc* src, int order, int mode, void* frames_d, int frames_u8, int B, int Nx, int Ny)
+{
+    const auto bad = [&](const char* rule) { return fail(ctx, AEFFT_EINVAL, (std::string("aefft_yuv_resize_to_frames: ") + rule).c_str()); };
+    if (!ctx || !src || !frames_d) return bad("null context, descriptor or frames");
+    int used = 0;
+    size_t sext[3] = {0, 0, 0};
+    RET_IF(chk_yuv_source(bad, src, order, B, &used, sext));
+    if (Nx < 1 || Ny < 1 || Nx > 8192 || Ny > 8192) return bad("Nx, Ny must be in 1..8192");
+    if (mode != AEFFT_RESIZE_LINEAR && mode != AEFFT_RESIZE_AREA) return bad("mode must be AEFFT_RESIZE_LINEAR or AEFFT_RESIZE_AREA");
+    if (mode == AEFFT_RESIZE_AREA && (Nx > src->W || Ny > src->H)) return bad("AEFFT_RESIZE_AREA does not enlarge: it needs Nx <= W and Ny <= H");
+    if (!aligned16(frames_d)) return bad("frames_d must be 16-byte aligned");
+    const int D = order == AEFFT_YUV_GRAY ? 1 : 3;
+    const size_t per = (size_t)D * Nx * Ny * (frames_u8 ? 1 : 4);              // (at most 2^30 bytes of one image's frames)
+    if ((size_t)B > (~size_t(0) >> 1) / per) return bad("B * D * Nx * Ny does not fit the address space");
+    for (int k = 0; k < used; ++k)
+        if (ranges_overlap(src->plane[k], sext[k], frames_d, (size_t)B * per)) return bad("a source plane and the frame range overlap (the op is out-of-place)");
+    RET_IF(join_recon(ctx));                          // (frames_d may be a buffer a deferred reconstruction is still writing)
+    return launch_or_fail(ctx, KID_IMAGE, (double)B * (yuv_bytes(*src, order) + (double)per), "yuv_resize", [&] {
+        return launch_yuv_resize(src->format, src->plane, src->pitch, src->stride, src->W, src->H, src->matrix, order, mode, frames_d, !frames_u8, B, Nx, Ny, ctx->cur);
+    });
+}

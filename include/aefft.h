@@ -357,6 +357,68 @@ int aefft_frames_degrade(aefft_ctx* ctx, const void* src_d, int src_u8, void* ds
                          int blur, float sigma, float impulse,
                          unsigned long long seed, unsigned long long first_frame);
 
+/* aefft_yuv_to_image, aefft_yuv_resize_to_frames: video as delivered -- the NV12 surface of a hardware decoder, the I420 planes of a software
+ * decoder, the YUYV buffer of a V4L2 webcam -- to interleaved 8-bit images, or straight to the planar frames every 8-bit net call takes.  The
+ * reference gets BGR because `cam >> rgb` (autoencoder.cpp:123) runs OpenCV's colour conversion on the host; these two calls are that conversion on
+ * the device, defined bit for bit, alone or fused with the resize + ImageToSpin_C of aefft_image_resize_to_frames in one launch.
+ * Source: the descriptor below, read on the host during the call (it need not outlive it).  W x H is the luma size, each in 1..8192; write
+ * Wc = ceil(W / 2), Hc = ceil(H / 2).  plane[k] are device pointers of ANY alignment, pitch[k] the bytes per row of plane k; for B > 1 image b's
+ * plane k starts at plane[k] + b * stride[k] (stride is ignored when B == 1).
+ *   AEFFT_YUV_NV12  plane[0] is Y: H rows, Y(x, y) at y * pitch[0] + x, pitch[0] >= W.  plane[1] is interleaved chroma: Hc rows, U at
+ *                   y' * pitch[1] + 2 x', V one byte behind, pitch[1] >= 2 Wc.  plane[2] is ignored.  A decoder surface that keeps both planes in
+ *                   one allocation is plane[1] = plane[0] + pitch * surface_height.
+ *   AEFFT_YUV_I420  plane[0] as NV12; plane[1] is U and plane[2] is V, each Hc rows of Wc bytes, pitch[k] >= Wc.  YV12 is the same call with the
+ *                   two pointers swapped.
+ *   AEFFT_YUV_YUYV  (YUY2) plane[0] only; W must be even.  Y(x, y) at y * pitch[0] + 2 x, U at y * pitch[0] + 4 (x >> 1) + 1, V two bytes further;
+ *                   pitch[0] >= 2 W.
+ * Chroma rule: NEAREST, i.e. replication -- the chroma of pixel (x, y) is the sample at (x >> 1, y >> 1) for NV12 and I420 and at (x >> 1, y) for
+ * YUYV; no interpolation and no siting offset.  Odd W and H are served for NV12 and I420 (the chroma planes have the ceil sizes: the last chroma
+ * column and row then serve one pixel).  For B > 1 each used stride[k] must be at least the plane's extent, (rows - 1) * pitch[k] + the live bytes
+ * of a row.  Bytes of a row beyond its live bytes are never read.  With order == AEFFT_YUV_GRAY no chroma plane is read, and plane[1] and plane[2]
+ * may be NULL.  A region of interest with even x0, y0 is pointer arithmetic on the caller's side, as for aefft_image_resize_to_frames.
+ * Arithmetic: all-integer, 32 bits suffice.  With c = Y - yoff, u = U - 128, v = V - 128:
+ *   p[y][x][ch] = clamp((ky c + a_ch u + b_ch v + 2^19) >> 20, 0, 255)          (>> 20: an arithmetic shift, i.e. the floor)
+ *   matrix            yoff  ky        R: (a, b)       G: (a, b)             B: (a, b)
+ *   AEFFT_YUV_BT601   16    1220945   (0, 1673555)    (-410793, -852458)    (2115221, 0)       BT.601, limited range
+ *   AEFFT_YUV_BT709   16    1220945   (0, 1879825)    (-223607, -558796)    (2215014, 0)       BT.709, limited range
+ *   AEFFT_YUV_JPEG    0     1048576   (0, 1470104)    (-360853, -748826)    (1858077, 0)       BT.601, full range (MJPEG)
+ * Each entry is round(k * 2^20) of the standards' constants in double: Kr = 0.299, Kb = 0.114 (601) or Kr = 0.2126, Kb = 0.0722 (709),
+ * Kg = 1 - Kr - Kb;  ky = s_y,  b_R = 2 (1 - Kr) s_c,  a_G = -2 (1 - Kb) (Kb / Kg) s_c,  b_G = -2 (1 - Kr) (Kr / Kg) s_c,  a_B = 2 (1 - Kb) s_c;
+ * s_y = 255 / 219 and s_c = 255 / 224 for the limited ranges, both 1 for JPEG.  c is NOT clamped below zero (Y < 16): the final clamp does that
+ * work.  The largest magnitude is below 2^30.  order AEFFT_YUV_BGR stores the rows (B, G, R) at d = 0, 1, 2 and AEFFT_YUV_RGB the reverse: D = 3.
+ * AEFFT_YUV_GRAY is clamp((ky c + 2^19) >> 20, 0, 255), D = 1; for AEFFT_YUV_JPEG that is Y itself.
+ * Relation to OpenCV: cv::cvtColor's YUV conversions have the same form (fixed-point, nearest chroma) but OpenCV's OWN constants and its own
+ * handling of Y < 16; they are not the ones above.  Differences of a grey level are to be expected; the difference is unmeasured (OpenCV was not
+ * available to the build).
+ * aefft_yuv_to_image writes p into B interleaved images of D channels with the destination layout and rules of aefft_frames_resize_to_image:
+ * pixel (row y, column x), channel d, at y * pitch + x * D + d; pitch >= W * D; image b at b * image_stride, image_stride >= (H - 1) * pitch + W * D for
+ * B > 1 (ignored when B == 1); any alignment; bytes beyond W * D of a row are never written.
+ * aefft_yuv_resize_to_frames is, for every accepted argument and bit for bit, aefft_yuv_to_image into a tight image followed by
+ * aefft_image_resize_to_frames(.., W, H, mode, frames_d, frames_u8, B, D, Nx, Ny): the AEFFT_RESIZE_LINEAR / AEFFT_RESIZE_AREA formulas above with p
+ * as the source pixels, to 8-bit or float frames [B][D][Nx][Ny], 16-byte aligned -- in one launch with no intermediate image.  With Nx == W and
+ * Ny == H both modes give aefft_yuv_to_image -> aefft_image_to_frames.  Nx, Ny in 1..8192; AEFFT_RESIZE_AREA requires Nx <= W and Ny <= H.
+ * Both calls: one launch on the context's stream; no host synchronisation, no allocation, no workspace; safe under stream capture.  Out-of-place.
+ * Accounted under the profile id `image` with the bytes read plus the bytes written: B times the source samples (W H luma and, unless the order is
+ * GRAY, 2 Wc Hc chroma; YUYV 2 W H) plus B W H D image bytes or the B D Nx Ny frame elements.
+ * AEFFT_EINVAL, with aefft_last_error starting with the call's name ("aefft_yuv_to_image: ", "aefft_yuv_resize_to_frames: ") and naming the rule,
+ * nothing enqueued and the outputs untouched: a null context, descriptor, output or needed plane; an unknown format, matrix, order or mode; a size
+ * or B out of range; YUYV with odd W; a pitch or stride too small; AREA with an enlarging axis; frames_d not 16-byte aligned; any source plane's
+ * byte range overlapping the destination's; sizes that overflow the address space. */
+enum { AEFFT_YUV_NV12 = 0, AEFFT_YUV_I420 = 1, AEFFT_YUV_YUYV = 2 };      /* format */
+enum { AEFFT_YUV_BT601 = 0, AEFFT_YUV_BT709 = 1, AEFFT_YUV_JPEG = 2 };    /* matrix: 601 limited, 709 limited, 601 full range (MJPEG) */
+enum { AEFFT_YUV_BGR = 0, AEFFT_YUV_RGB = 1, AEFFT_YUV_GRAY = 2 };        /* order of the produced channels: D = 3, 3, 1 */
+typedef struct {
+    int format, matrix;
+    int W, H;                          /* luma size; 1..8192 */
+    const unsigned char* plane[3];     /* device pointers, ANY alignment */
+    size_t pitch[3];                   /* bytes per row of each plane */
+    size_t stride[3];                  /* image b's plane k starts at plane[k] + b * stride[k]; ignored when B == 1 */
+} aefft_yuv_desc;
+int aefft_yuv_to_image(aefft_ctx* ctx, const aefft_yuv_desc* src, int order,
+                       unsigned char* image_d, size_t pitch, size_t image_stride, int B);
+int aefft_yuv_resize_to_frames(aefft_ctx* ctx, const aefft_yuv_desc* src, int order, int mode,
+                               void* frames_d, int frames_u8, int B, int Nx, int Ny);
+
 /* ---- network level: the resident, batched form of autoenc_fft / backprop_fft ------------------ */
 typedef struct {
     int D, Nx, Ny;        /* input frames [B][D][Nx][Ny] */
