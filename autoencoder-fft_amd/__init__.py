@@ -49,6 +49,18 @@ class YuvDesc(C.Structure):
                 ("plane", C.c_void_p * 3), ("pitch", C.c_size_t * 3), ("stride", C.c_size_t * 3)]
 
 
+class TileDesc(C.Structure):
+    """include/aefft.h aefft_tile_desc"""
+    _fields_ = [("W", C.c_int), ("H", C.c_int), ("Nx", C.c_int), ("Ny", C.c_int),
+                ("overlap_x", C.c_int), ("overlap_y", C.c_int), ("rim_x", C.c_int), ("rim_y", C.c_int)]
+
+
+class TilePlan(C.Structure):
+    """include/aefft.h aefft_tile_plan"""
+    _fields_ = [("ntx", C.c_int), ("nty", C.c_int), ("ox0", C.c_int), ("oy0", C.c_int),
+                ("step_x", C.c_int), ("step_y", C.c_int), ("ramp_x", C.c_int), ("ramp_y", C.c_int)]
+
+
 _lib = None
 _vp, _fp, _i, _l, _f = C.c_void_p, C.c_void_p, C.c_int, C.c_long, C.c_float   # device float* passed as void*
 
@@ -87,6 +99,9 @@ SIGNATURES = {
     "aefft_frames_degrade": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _f, _f, C.c_ulonglong, C.c_ulonglong]),
     "aefft_yuv_to_image": (_i, [_vp, C.POINTER(YuvDesc), _i, _vp, C.c_size_t, C.c_size_t, _i]),
     "aefft_yuv_resize_to_frames": (_i, [_vp, C.POINTER(YuvDesc), _i, _i, _vp, _i, _i, _i, _i]),
+    "aefft_tile_plan_make": (_i, [C.POINTER(TileDesc), C.POINTER(TilePlan)]),
+    "aefft_image_tiles_to_frames": (_i, [_vp, _vp, C.c_size_t, C.c_size_t, C.POINTER(TileDesc), _vp, _i, _i, _i]),
+    "aefft_frames_tiles_to_image": (_i, [_vp, _vp, _i, C.POINTER(TileDesc), _vp, C.c_size_t, C.c_size_t, _i, _i]),
     "aefft_net_create": (_i, [_vp, C.POINTER(NetDesc), C.POINTER(_vp)]),
     "aefft_net_create_ex": (_i, [_vp, C.POINTER(NetDesc), C.c_uint, C.POINTER(_vp)]),
     "aefft_net_destroy": (None, [_vp]),
@@ -372,6 +387,81 @@ def _frames_degrade_args(frames, blur, sigma, impulse, seed, first_frame, out, d
         if out.data_ptr() == frames.data_ptr() and (blur != 0 or out.dtype != frames.dtype):
             raise ValueError(f"{what}: in place (out=frames) needs blur == 0 and the frames' own dtype")
     return int(blur), float(sigma), float(impulse), int(seed), int(first_frame), dtype
+
+
+def _pair(v, what, name):
+    """an int, or an (x, y) pair of ints, as two ints"""
+    try:
+        x, y = (v, v) if isinstance(v, (int, np.integer)) and not isinstance(v, bool) else v
+        if any(isinstance(q, bool) or int(q) != q for q in (x, y)):
+            raise TypeError
+        return int(x), int(y)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: {name} must be an int or an (x, y) pair of ints") from None
+
+
+def tile_plan(W, H, Nx, Ny, overlap, rim=0):
+    """The tile grid of tiled inference (aefft_tile_plan_make; host arithmetic, no device): an image of W x H pixels cut into tiles of Nx x Ny
+    (Nx along the image's columns) that share `overlap` pixels with their neighbours, of which `rim` at each tile edge are never used.
+    `overlap` and `rim` are each an int or an (x, y) pair.  Returns (the filled TileDesc, the TilePlan: ntx, nty, ox0, oy0, step_x, step_y,
+    ramp_x, ramp_y); ValueError for what the library refuses (W, H in 1..8192; Nx, Ny in 2..2048; 0 <= 2 overlap <= N; 0 <= 2 rim <= overlap)."""
+    what = "tile_plan"
+    (vx, vy), (mx, my) = _pair(overlap, what, "overlap"), _pair(rim, what, "rim")
+    try:
+        desc = TileDesc(int(W), int(H), int(Nx), int(Ny), vx, vy, mx, my)
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError(f"{what}: W, H, Nx, Ny must be ints") from None
+    plan = TilePlan()
+    if lib().aefft_tile_plan_make(C.byref(desc), C.byref(plan)) != 0:
+        raise ValueError(f"{what}: W, H must be in 1..8192, Nx, Ny in 2..2048, 0 <= 2 overlap <= N and 0 <= 2 rim <= overlap per axis; got "
+                         f"W={W} H={H} Nx={Nx} Ny={Ny} overlap={(vx, vy)} rim={(mx, my)}")
+    return desc, plan
+
+
+def _image_tiles_args(image, tile, overlap, rim, out, dtype):
+    """the checks of Context.image_tiles_to_frames that need no device: (the image as [B][H][W][D], pitch, image stride, the TileDesc, the shape
+    (T, D, Nx, Ny) of the tile frames, their dtype)"""
+    what = "Context.image_tiles_to_frames"
+    img, pitch, stride = _resize_layout(image, what)
+    B, H, W, D = img.shape
+    if not 1 <= D <= 4:
+        raise ValueError(f"{what}: D must be 1..4")
+    try:
+        Nx, Ny = (int(v) for v in tile)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: tile must be (Nx, Ny)") from None
+    desc, plan = tile_plan(W, H, Nx, Ny, overlap, rim)
+    shape = (B * plan.ntx * plan.nty, D, Nx, Ny)
+    if out is not None:
+        if out.dtype not in (torch.uint8, torch.float32) or tuple(out.shape) != shape or not out.is_contiguous():
+            raise ValueError(f"{what}: out must be a contiguous uint8 or float32 tensor of shape {shape}")
+        dtype = out.dtype
+    elif dtype not in (torch.uint8, torch.float32):
+        raise ValueError(f"{what}: dtype must be torch.uint8 or torch.float32")
+    return img, pitch, stride, desc, shape, dtype
+
+
+def _frames_tiles_args(frames, size, overlap, rim, out):
+    """the checks of Context.frames_tiles_to_image that need no device: (the TileDesc, the shape (B, H, W, D) of the image); `out`, when given,
+    is checked for that shape here and for its layout by the caller through _resize_layout"""
+    what = "Context.frames_tiles_to_image"
+    if frames.dtype not in (torch.uint8, torch.float32) or frames.dim() != 4 or not frames.is_contiguous() or min(frames.shape) < 1:
+        raise ValueError(f"{what}: frames must be a contiguous, non-empty uint8 or float32 tensor [T][D][Nx][Ny]")
+    T, D, Nx, Ny = frames.shape
+    if not 1 <= D <= 4:
+        raise ValueError(f"{what}: D must be 1..4")
+    try:
+        W, H = (int(v) for v in size)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: size must be (W, H)") from None
+    desc, plan = tile_plan(W, H, Nx, Ny, overlap, rim)
+    per = plan.ntx * plan.nty
+    if T % per:
+        raise ValueError(f"{what}: {T} frames are not a whole number of images of {plan.ntx} x {plan.nty} tiles")
+    shape = (T // per, H, W, D)
+    if out is not None and (out.dim() != 4 or tuple(out.shape) != shape):
+        raise ValueError(f"{what}: out must be a uint8 tensor of shape {shape}")
+    return desc, shape
 
 
 class Context:
@@ -681,6 +771,31 @@ class Context:
                                                blur, sigma, impulse, seed, first_frame))
         return out
 
+    def image_tiles_to_frames(self, image, tile, overlap, rim=0, out=None, dtype=torch.uint8):
+        """Overlapping tiles of an image as frames (aefft_image_tiles_to_frames), one launch: `image` is a uint8 device tensor [B][H][W][D] (or
+        [H][W][D]) laid out as image_resize_to_frames takes it; tile = (Nx, Ny), the net's frame size; `overlap` the pixels two neighbouring
+        tiles share and `rim` the pixels at each tile edge that the blend never uses, each an int or an (x, y) pair (tile_plan gives the grid).
+        Beyond the image's edge the tiles hold reflected pixels (the edge pixel not repeated).  Returns, or fills `out` with, the frames
+        [B * ntx * nty][D][Nx][Ny] of `dtype` uint8 or float32, image-major, then tile row, then tile column.  Nothing waits for the device."""
+        img, pitch, stride, desc, shape, dtype = _image_tiles_args(image, tile, overlap, rim, out, dtype)
+        if out is None:
+            out = self.empty(*shape, dtype=dtype)
+        self.check(self.L.aefft_image_tiles_to_frames(self.h, _ptr(img), pitch, stride, C.byref(desc), _ptr(out), int(_is_u8(out)), img.shape[0], img.shape[3]))
+        return out
+
+    def frames_tiles_to_image(self, frames, size, overlap, rim=0, out=None):
+        """Tile frames blended back into images (aefft_frames_tiles_to_image), one launch, the inverse of image_tiles_to_frames: `frames` is
+        uint8 or float32 [B * ntx * nty][D][Nx][Ny] (float values become pixels first); size = (W, H); `overlap` and `rim` as given to the
+        gather.  Each pixel is the integer-weighted mean of the one, two or four tiles whose kept area covers it: linear ramps across the
+        overlap minus the rims, so unchanged tiles give back the image's bytes.  Returns, or fills `out` with, the uint8 image rows
+        [B][H][W][D]; `out` may be row-padded or a region of interest (bytes outside it are not written).  Nothing waits for the device."""
+        desc, shape = _frames_tiles_args(frames, size, overlap, rim, out)
+        if out is None:
+            out = self.empty(*shape, dtype=torch.uint8)
+        img, pitch, stride = _resize_layout(out, "Context.frames_tiles_to_image")
+        self.check(self.L.aefft_frames_tiles_to_image(self.h, _ptr(frames), int(_is_u8(frames)), C.byref(desc), _ptr(img), pitch, stride, shape[0], shape[3]))
+        return out
+
     def yuv_to_image(self, planes, fmt, matrix="bt601", order="bgr", out=None):
         """Colour conversion on the device (aefft_yuv_to_image): `planes` is a tuple of uint8 device tensors -- fmt "nv12": (y [B][H][W],
         uv [B][Hc][Wc][2]); "i420": (y, u [B][Hc][Wc], v); "yuyv": (yuyv [B][H][W/2][4],); unbatched tensors too -- each contiguous or a view with a
@@ -762,6 +877,7 @@ class Net:
         every scale dividing its input grid exactly; step_apply's del0 is backprop_gpu's delmax and the MSE tail is this step's."""
         self.ctx, self.L = ctx, ctx.L
         self.D, self.Nx, self.Ny, self.B = D, Nx, Ny, batch
+        self.spatial = bool(spatial)
         self.maps = list(maps); self.npairs = len(self.maps)
         self.Nk = [Nk] * self.npairs if isinstance(Nk, int) else list(Nk)
         self.Nl = list(self.Nk) if Nl is None else ([Nl] * self.npairs if isinstance(Nl, int) else list(Nl))
@@ -838,6 +954,33 @@ class Net:
         hp = -1 if hidden_pair is None else int(hidden_pair)
         self.ctx.check(self.L.aefft_net_infer(self.h, _ptr(frames), int(_is_u8(frames)), _ptr(recon), int(_is_u8(recon)), hp, _ptr(hidden)))
         return recon, hidden
+
+    def infer_tiled(self, image, overlap, rim=0, out=None):
+        """Frozen-weight inference at the image's own resolution: `image` is a uint8 device tensor [B][H][W][D] of any size, cut into overlapping
+        tiles of the net's (Nx, Ny) (Context.image_tiles_to_frames), reconstructed by aefft_net_infer in chunks of the net's batch (8-bit in,
+        8-bit out) and blended into `out`, uint8 [B][H][W][D] (Context.frames_tiles_to_image).  `rim` should cover the summed kernel reach of the
+        net, whose circular convolution contaminates that much of every tile's edge; `overlap` is 2 * rim plus the ramp the seam is blended
+        over.  The tile buffer is rounded up to a multiple of the batch; the padding frames are zero and ignored.  An FFT net only
+        (ValueError on a spatial net).  Nothing waits for the device.  Returns `out`."""
+        what = "Net.infer_tiled"
+        if self.spatial:
+            raise ValueError(f"{what}: tiled inference serves the FFT net (its circular convolution is what the rim is for), not a spatial net")
+        if image.dim() != 4:
+            raise ValueError(f"{what}: the image must be a uint8 tensor [B][H][W][D]")
+        img, pitch, stride, desc, shape, _ = _image_tiles_args(image, (self.Nx, self.Ny), overlap, rim, None, torch.uint8)
+        B, H, W, D = img.shape
+        if D != self.D:
+            raise ValueError(f"{what}: the image has {D} channels, the net {self.D}")
+        if out is not None and (out.dtype != torch.uint8 or tuple(out.shape) != (B, H, W, D)):
+            raise ValueError(f"{what}: out must be a uint8 tensor of shape {(B, H, W, D)}")
+        T = shape[0]
+        Tp = -(-T // self.B) * self.B
+        tiles = torch.zeros(Tp, D, self.Nx, self.Ny, dtype=torch.uint8, device=image.device)
+        recon = torch.empty_like(tiles)
+        self.ctx.image_tiles_to_frames(img, (self.Nx, self.Ny), overlap, rim, out=tiles[:T])
+        for k in range(0, Tp, self.B):
+            self.infer(tiles[k:k + self.B], recon[k:k + self.B])
+        return self.ctx.frames_tiles_to_image(recon[:T], (W, H), overlap, rim, out=out)
 
     def score(self, frames, score=None, recon=None):
         """Per-frame reconstruction error under the current weights (aefft_net_score): score[b] = mean over the frame's D*Nx*Ny pixels of

@@ -5,6 +5,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "../../include/aefft.h"
+
 namespace aefft {
 
 // Development switches (include/aefft.h AEFFT_F_*, aefft_ctx_set_flags): one process-wide word, written by the setter (and once
@@ -100,6 +102,17 @@ hipError_t launch_yuv_image(int fmt, const unsigned char* const* plane, const si
                             unsigned char* image, size_t ipitch, size_t istride, int B, hipStream_t st);
 hipError_t launch_yuv_resize(int fmt, const unsigned char* const* plane, const size_t* pitch, const size_t* stride, int W, int H, int matrix, int order,
                              int mode, void* frames, bool f32, int B, int Nx, int Ny, hipStream_t st);
+// ---- tile_kernels.hip (aefft_tile_plan_make, aefft_image_tiles_to_frames, aefft_frames_tiles_to_image) ----
+// the plan of include/aefft.h from a description: false, and nothing written, for a null pointer or a value out of range
+bool tile_plan(const aefft_tile_desc* desc, aefft_tile_plan* plan);
+// B images of H rows of `pitch` bytes, image b at b * stride, W x H interleaved pixels of D channels <-> the T = B ntx nty overlapping tiles of the plan as
+// frames [T][D][Nx][Ny] (float when f32): the gather reflects beyond the image's edge, the blend weighs the one, two or four tiles of a pixel with the
+// integer ramps (float frames through px_u8 first).  One launch each.  D in 1..4, pitch >= W D, a description tile_plan takes (hipErrorInvalidValue
+// otherwise); any alignment of image, pitch and stride, frames 16-byte aligned.
+hipError_t launch_tile_gather(const unsigned char* image, size_t pitch, size_t stride, const aefft_tile_desc* desc, void* frames, bool f32, int B, int D,
+                              hipStream_t st);
+hipError_t launch_tile_blend(const void* frames, bool f32, const aefft_tile_desc* desc, unsigned char* image, size_t pitch, size_t stride, int B, int D,
+                             hipStream_t st);
 size_t fft_mid_elems(long planes, int Nx, int Wc);   // complex elements needed in `mid`
 // sizes that are not powers of two (cufftPlanMany takes any size, fft.cu:773-779): even n in 8..1024 through Bluestein's chirp-z form on the
 // power-of-two LDS passes; rows -> transpose -> rows -> transpose.  w1, w2: workspaces of fft_any_ws_elems complex each.

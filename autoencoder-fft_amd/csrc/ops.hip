@@ -4,6 +4,7 @@
 #include "host.h"
 
 #include <algorithm>
+#include <climits>
 #include <cmath>
 
 using namespace aefft;
@@ -972,4 +973,50 @@ extern "C" int aefft_yuv_resize_to_frames(aefft_ctx* ctx, const aefft_yuv_desc* 
     return launch_or_fail(ctx, KID_IMAGE, (double)B * (yuv_bytes(*src, order) + (double)per), "yuv_resize", [&] {
         return launch_yuv_resize(src->format, src->plane, src->pitch, src->stride, src->W, src->H, src->matrix, order, mode, frames_d, !frames_u8, B, Nx, Ny, ctx->cur);
     });
+}
+
+// tiled inference (include/aefft.h "tiled inference"): the plan is host arithmetic only
+extern "C" int aefft_tile_plan_make(const aefft_tile_desc* desc, aefft_tile_plan* plan) { return tile_plan(desc, plan) ? AEFFT_OK : AEFFT_EINVAL; }
+
+// the rules aefft_image_tiles_to_frames and aefft_frames_tiles_to_image share; `frame_bytes` receives the bytes of the T tile frames
+template <class Bad>
+static int chk_tiles(const Bad& bad, aefft_ctx* ctx, const void* image_d, size_t pitch, size_t image_stride, const aefft_tile_desc* desc, const void* frames_d,
+                     int frames_u8, int B, int D, size_t* frame_bytes)
+{
+    if (!ctx || !image_d || !frames_d || !desc) return bad("null context, image, frames or description");
+    aefft_tile_plan plan;
+    if (!tile_plan(desc, &plan))
+        return bad("the description is not one aefft_tile_plan_make takes (W, H in 1..8192; Nx, Ny in 2..2048; 0 <= 2 overlap <= N; 0 <= 2 rim <= overlap)");
+    size_t extent = 0;
+    RET_IF(chk_present_image(bad, pitch, image_stride, desc->W, desc->H, B, D, &extent));
+    if (!aligned16(frames_d)) return bad("frames_d must be 16-byte aligned");
+    const size_t tiles = (size_t)plan.ntx * plan.nty;                            // (at most 2^26 of an image)
+    if ((size_t)B > (size_t)INT_MAX / tiles) return bad("B * ntx * nty tiles do not fit an int");
+    const size_t per = (size_t)D * desc->Nx * desc->Ny * (frames_u8 ? 1 : 4);    // (at most 2^26 bytes of a tile)
+    if ((size_t)B * tiles > (~size_t(0) >> 1) / per) return bad("T * D * Nx * Ny does not fit the address space");
+    *frame_bytes = (size_t)B * tiles * per;
+    if (ranges_overlap(frames_d, *frame_bytes, image_d, extent)) return bad("the frame and image ranges overlap (the op is out-of-place)");
+    return AEFFT_OK;
+}
+
+extern "C" int aefft_image_tiles_to_frames(aefft_ctx* ctx, const unsigned char* image_d, size_t pitch, size_t image_stride, const aefft_tile_desc* desc,
+                                           void* frames_d, int frames_u8, int B, int D)
+{
+    const auto bad = [&](const char* rule) { return fail(ctx, AEFFT_EINVAL, (std::string("aefft_image_tiles_to_frames: ") + rule).c_str()); };
+    size_t fb = 0;
+    RET_IF(chk_tiles(bad, ctx, image_d, pitch, image_stride, desc, frames_d, frames_u8, B, D, &fb));
+    RET_IF(join_recon(ctx));                          // (frames_d may be a buffer a deferred reconstruction is still writing)
+    return launch_or_fail(ctx, KID_IMAGE, (double)B * D * desc->W * desc->H + (double)fb, "tile_gather",
+                          [&] { return launch_tile_gather(image_d, pitch, image_stride, desc, frames_d, !frames_u8, B, D, ctx->cur); });
+}
+
+extern "C" int aefft_frames_tiles_to_image(aefft_ctx* ctx, const void* frames_d, int frames_u8, const aefft_tile_desc* desc, unsigned char* image_d,
+                                           size_t pitch, size_t image_stride, int B, int D)
+{
+    const auto bad = [&](const char* rule) { return fail(ctx, AEFFT_EINVAL, (std::string("aefft_frames_tiles_to_image: ") + rule).c_str()); };
+    size_t fb = 0;
+    RET_IF(chk_tiles(bad, ctx, image_d, pitch, image_stride, desc, frames_d, frames_u8, B, D, &fb));
+    RET_IF(join_recon(ctx));                          // (frames_d may be the reconstruction of a step whose inverse transform is still on the side stream)
+    return launch_or_fail(ctx, KID_IMAGE, (double)B * D * desc->W * desc->H + (double)fb, "tile_blend",
+                          [&] { return launch_tile_blend(frames_d, !frames_u8, desc, image_d, pitch, image_stride, B, D, ctx->cur); });
 }

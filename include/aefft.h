@@ -419,6 +419,66 @@ int aefft_yuv_to_image(aefft_ctx* ctx, const aefft_yuv_desc* src, int order,
 int aefft_yuv_resize_to_frames(aefft_ctx* ctx, const aefft_yuv_desc* src, int order, int mode,
                                void* frames_d, int frames_u8, int B, int Nx, int Ny);
 
+/* aefft_tile_plan_make, aefft_image_tiles_to_frames, aefft_frames_tiles_to_image: tiled inference.  A net takes frames of its own size; an image
+ * of the sensor's size is cut into overlapping tiles of that size (the gather), the net runs over the tiles, and the reconstructed tiles are
+ * blended back into an image of the sensor's size (the blend).  The FFT net's convolution is circular, so the rim of every tile is contaminated
+ * by wrap-around from the opposite edge: tiles overlap, the rim is never used, and across the rest of the overlap the two tiles are blended
+ * with integer ramp weights that sum to a constant, so that an unchanged image is restored exactly.
+ * The plan (host only: no device, no context).  Per axis, with image size W, tile N, overlap V and rim M, in integer arithmetic only:
+ *   S = N - V  (the step)   and   R = V - 2M  (the ramp);
+ *   n = max(1, ceil((W - N + 2M) / S) + 1), the smallest count whose kept areas [o_t + M, o_t + N - M) cover [0, W);
+ *   E = (n-1) S + N - 2M - W >= 0;   o_0 = -M - floor(E / 2), so the grid is centred;   o_t = o_0 + t S.
+ * Ranges: W, H in 1..8192; Nx, Ny in 2..2048 (Nx along image columns, Ny along rows); 0 <= 2 V <= N; 0 <= 2 M <= V.  The last two guarantee that
+ * at most two tiles per axis cover any pixel.  Examples (W, N, V, M): (1920, 512, 64, 8) gives n = 5, S = 448, R = 48, o_0 = -192;
+ * (13, 8, 4, 1) gives n = 3, S = 4, R = 2, o_0 = -1; (5, 8, 4, 1) gives n = 1, o_0 = -1; (9, 8, 4, 2) gives n = 3, R = 0, o_0 = -3.
+ * aefft_tile_plan_make returns AEFFT_EINVAL for a null pointer or any value outside the ranges above and writes nothing in that case.
+ * Tile order in the frame buffer is image-major, then tile row, then tile column: frame f = (b * nty + ty) * ntx + tx, and T = B * ntx * nty.
+ * aefft_image_tiles_to_frames (the gather).  Source: B interleaved images with the layout and rules of aefft_image_resize_to_frames -- pixel
+ * (row y, column x), channel d, at y * pitch + x * D + d; any alignment; pitch >= W * D; image b at image_d + b * image_stride,
+ * image_stride >= (H - 1) * pitch + W * D for B > 1 (ignored when B == 1); bytes beyond W * D of a row are never read.  Destination: frames
+ * [T][D][Nx][Ny], unsigned char when frames_u8 != 0, float with (float)pixel otherwise, 16-byte aligned:
+ *   frames[f][d][i][j] = image[b][ry(oy_ty + j)][rx(ox_tx + i)][d]
+ * r is reflection without repeating the edge pixel (OpenCV's BORDER_REFLECT_101), iterated so that it is defined for any reach: for W = 1 the
+ * result is 0; otherwise P = 2(W-1), m = x mod P taken non-negative, r = m when m < W, else P - m.  Every element of every tile is written.
+ * aefft_frames_tiles_to_image (the blend).  Source samples p are the bytes of 8-bit frames, or px_u8(v) for float frames: float frames are first
+ * turned into pixels, as in aefft_frames_resize_to_image and aefft_frames_degrade.  Destination: B images, layout as above.  The per-axis weight
+ * of tile t at image coordinate x, with k = x - o_t, is
+ *   0                      when k < M or k >= N - M;
+ *   2(k - M) + 1           when t > 0 and k < M + R                (left ramp);
+ *   2(N - M - 1 - k) + 1   when t < n-1 and k >= N - M - R        (right ramp);
+ *   den                    otherwise, with den = 2R for R > 0 and den = 1 for R = 0.
+ * In a seam the two weights add up to 2R, so the weights over all tiles sum to den at every x.  With R = 0 the kept areas abut and there is no
+ * blend.  The outermost tiles have no ramp on their outer side.  The output is
+ *   acc = sum over the (at most four) tiles of wx * wy * p;    image[y][x][d] = floor((2 acc + denx deny) / (2 denx deny)).
+ * With N <= 2048, acc < 255 * 2^22, so 32 bits are enough.  Every pixel of [0,W) x [0,H) is written once; bytes beyond W * D of a row are never
+ * written and the image is never read.
+ * Consequences: blend(gather(image)) returns the image's bytes for every valid description.  With W == Nx, H == Ny, V = 0 the two calls are
+ * aefft_image_to_frames / aefft_frames_to_image.  Constant tiles give a constant image.  The same arguments always give the same bytes, on every
+ * route (image pointer, pitch and stride multiples of 4: the image side moves dwords; Ny % 4 == 0: the frame side moves dwords / float4; single
+ * elements otherwise).
+ * Both calls: one launch on the context's stream; no host synchronisation, no allocation, no workspace; safe under stream capture.  Out-of-place.
+ * Accounted under the profile id `image` with the bytes read plus the bytes written: the B W H D image bytes plus the T D Nx Ny frame elements
+ * (1 or 4 bytes each).
+ * AEFFT_EINVAL, with aefft_last_error starting with the call's name ("aefft_image_tiles_to_frames: ", "aefft_frames_tiles_to_image: ") and naming
+ * the rule, nothing enqueued and the outputs untouched: a null context, pointer or description; anything aefft_tile_plan_make refuses; D outside
+ * 1..4; B < 1; a pitch or stride that is too small; frames_d not 16-byte aligned; overlapping source and destination ranges; sizes that overflow the
+ * address space or an int tile count. */
+typedef struct { int W, H;            /* image size, 1..8192 */
+                 int Nx, Ny;          /* tile = frame size, 2..2048 (Nx along image columns, Ny along rows) */
+                 int overlap_x, overlap_y;   /* V: pixels two neighbouring tiles share, 0 <= 2 V <= N */
+                 int rim_x, rim_y;           /* M: pixels at each tile edge that are never used, 0 <= 2 M <= V */
+} aefft_tile_desc;
+typedef struct { int ntx, nty;        /* tiles per image along columns / rows */
+                 int ox0, oy0;        /* origin of tile 0 in image coordinates (<= 0) */
+                 int step_x, step_y;  /* S = N - V */
+                 int ramp_x, ramp_y;  /* R = V - 2 M */
+} aefft_tile_plan;
+int aefft_tile_plan_make(const aefft_tile_desc* desc, aefft_tile_plan* plan);
+int aefft_image_tiles_to_frames(aefft_ctx* ctx, const unsigned char* image_d, size_t pitch, size_t image_stride,
+                                const aefft_tile_desc* desc, void* frames_d, int frames_u8, int B, int D);
+int aefft_frames_tiles_to_image(aefft_ctx* ctx, const void* frames_d, int frames_u8, const aefft_tile_desc* desc,
+                                unsigned char* image_d, size_t pitch, size_t image_stride, int B, int D);
+
 /* ---- network level: the resident, batched form of autoenc_fft / backprop_fft ------------------ */
 typedef struct {
     int D, Nx, Ny;        /* input frames [B][D][Nx][Ny] */
