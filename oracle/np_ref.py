@@ -478,9 +478,13 @@ def backprop_sym(c, f, b, p, dck, dfk, db, dp, Dc, Df, Db, Dp, dele, cd=None, fd
 # EVERY pair one backprop_fft loop-body iteration on the spectra of that forward (batch-mean gradients), momentum carried from
 # step to step (aefft_net_step_grad / _apply).  Used by the trajectory tests; one call = one step.
 # ----------------------------------------------------------------------------------------
-def net_step(xs, ws, moms, scale, del0, maxdiff=0, sym=0, dtype=np.float64, fast_diff=True):
+def net_step(xs, ws, moms, scale, del0, maxdiff=0, sym=0, dtype=np.float64, fast_diff=True, grad_scale=1.0, return_grads=False):
     """xs [B][D][Nx][Ny]; ws = [(c, b, f, p)] per pair; moms = [(Dc, Df, Db, Dp)] per pair (None: zeros).  Returns
-    (ws', moms', mse per pair [post-update, fft.cu:1463], recon [B][D][Nx][Ny])."""
+    (ws', moms', mse per pair [post-update, fft.cu:1463], recon [B][D][Nx][Ny]).
+    grad_scale: the batch-mean gradients times this enter the update (aefft_net_step_apply's grad_scale: 1/world after an all-reduce);
+    the multiobjective term is not scaled.  return_grads: a fifth result, per pair the UNSCALED batch-mean gradients (dck, dfk, db, dp)
+    of this step's forward -- what aefft_net_grad_buffer holds.  Both off by default.  fast_diff: the multiobjective term from
+    gradient_diff_fast (float64, tied and untied alike) instead of the literal loop nest."""
     L = len(ws)
     net_c = [np.asarray(w[0], dtype) for w in ws] + [np.asarray(w[2], dtype) for w in ws[::-1]]
     net_b = [np.asarray(w[1], dtype) for w in ws] + [np.asarray(w[3], dtype) for w in ws[::-1]]
@@ -491,24 +495,31 @@ def net_step(xs, ws, moms, scale, del0, maxdiff=0, sym=0, dtype=np.float64, fast
         sp.append((layers, spec))
     recon = np.stack([q[0][-1] for q in sp])
     dele = dtype(0.1) * dtype(del0)
-    out_w, out_m, mses = [], [], []
+    out_w, out_m, mses, out_g = [], [], [], []
     for l in range(L):
         c, b, f, p = (np.asarray(a, dtype) for a in ws[l])
         mom = moms[l] if moms is not None and moms[l] is not None else tuple(np.zeros_like(a) for a in (c, f, b, p))
         Xs = [q[1][2 * l + 1] for q in sp]; Os = [q[1][4 * L - 1 - 2 * l] for q in sp]
         dM, dD, Nk, Nl = c.shape
         Nx = Xs[0].shape[-2]; Ny = (Xs[0].shape[-1] - 1) * 2
-        if not sym:
+        if not sym and grad_scale == 1.0 and not return_grads and not (maxdiff and fast_diff):
             r = batch_train_iter(Xs, Xs, Os, cf[l], cf[2 * L - 1 - l], c, f, b, p, mom, dele, maxdiff, dtype)
             out_w.append((r["c"], r["b"], r["f"], r["p"])); out_m.append(r["mom"]); mses.append(r["mse"])
             continue
-        dck, dfk, db, dp = batch_grad(Xs, Xs, Os, cf[l], cf[2 * L - 1 - l], b, Nk, Nl, dtype)
+        grads = batch_grad(Xs, Xs, Os, cf[l], cf[2 * L - 1 - l], b, Nk, Nl, dtype)
+        out_g.append(tuple(grads))
+        dck, dfk, db, dp = grads if grad_scale == 1.0 else [(g * dtype(grad_scale)).astype(dtype) for g in grads]
         extra = ()
         if maxdiff:
             extra = tuple(np.asarray(a, dtype) for a in (gradient_diff_fast(c, f, b, p) if fast_diff else gradient_diff(c, f, b, p, dtype)))
-        c2, f2, b2, p2, Dc, Df, Db, Dp = backprop_sym(c, f, b, p, dck, dfk, db, dp, *mom, dele, *extra, dtype=dtype)
+        if sym:
+            c2, f2, b2, p2, Dc, Df, Db, Dp = backprop_sym(c, f, b, p, dck, dfk, db, dp, *mom, dele, *extra, dtype=dtype)
+        elif maxdiff:
+            c2, f2, b2, p2, Dc, Df, Db, Dp = backprop_double(c, f, b, p, dck, dfk, db, dp, *mom, *extra, dele, dtype)
+        else:
+            c2, f2, b2, p2, Dc, Df, Db, Dp = backprop_d(c, f, b, p, dck, dfk, db, dp, *mom, dele, dtype)
         C = fft(pad_k(c2, Nx, Ny), dtype); F = fft(pad_k(f2, Nx, Ny), dtype)
         Os2 = [conv_k(conv_k(X, C, b2, Nx, Ny, dtype), F, p2, Nx, Ny, dtype) for X in Xs]
         mses.append(dtype(np.mean([mse_fft(X, O, dM, dD, Nx, Ny, dtype) for X, O in zip(Xs, Os2)])))
         out_w.append((c2, b2, f2, p2)); out_m.append((Dc, Df, Db, Dp))
-    return out_w, out_m, mses, recon
+    return (out_w, out_m, mses, recon, out_g) if return_grads else (out_w, out_m, mses, recon)
