@@ -224,14 +224,14 @@ def _image_layout(image, what):
     row-padded view -- stride(-1) == 1, stride(-2) == D, stride(-3) = pitch >= Nx * D and, for a batch, stride(0) == Ny * pitch"""
     if image.dtype != torch.uint8 or image.dim() not in (3, 4):
         raise ValueError(f"{what}: the image must be a uint8 tensor [B][Ny][Nx][D] or [Ny][Nx][D]")
-    img = image if image.dim() == 4 else image.unsqueeze(0)
-    B, Ny, Nx, D = img.shape
-    sb, sj, si, sd = img.stride()
-    pitch = sj if Ny > 1 else (sb if B > 1 else Nx * D)
-    if min(B, Ny, Nx, D) < 1 or (D > 1 and sd != 1) or (Nx > 1 and si != D) or pitch < Nx * D or (B > 1 and sb != Ny * pitch):
+    try:
+        img, pitch, stride = _resize_layout(image, what)
+        if img.shape[0] > 1 and img.shape[1] > 1 and stride != img.shape[1] * pitch:
+            raise ValueError
+    except ValueError:
         raise ValueError(f"{what}: the image must be contiguous or a row-padded view (stride(-1) == 1, stride(-2) == D, stride(-3) = pitch >= Nx * D, "
-                         f"stride(0) == Ny * pitch); got shape {tuple(image.shape)} with strides {tuple(image.stride())}")
-    return img, int(pitch)
+                         f"stride(0) == Ny * pitch); got shape {tuple(image.shape)} with strides {tuple(image.stride())}") from None
+    return img, stride if img.shape[1] == 1 else pitch       # (one row an image: the batch stride is the pitch)
 
 
 RESIZE_MODES = {"linear": 0, "area": 1}      # AEFFT_RESIZE_LINEAR, AEFFT_RESIZE_AREA
@@ -316,21 +316,32 @@ def heat_lut(D=3):
     return np.ascontiguousarray(np.stack(cols, axis=1).astype(np.uint8))
 
 
+def _frames4(frames, what, axes="[B][D][Nx][Ny]"):
+    """the shape of frames as every boundary call takes them: contiguous, non-empty, uint8 or float32, four axes"""
+    if frames.dtype not in (torch.uint8, torch.float32) or frames.dim() != 4 or not frames.is_contiguous() or min(frames.shape) < 1:
+        raise ValueError(f"{what}: frames must be a contiguous, non-empty uint8 or float32 tensor {axes}")
+    return frames.shape
+
+
+def _two_ints(v, what, rule):
+    """a size such as (W, H) as two ints; `rule` is the sentence for anything else"""
+    try:
+        x, y = (int(q) for q in v)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: {rule}") from None
+    return x, y
+
+
 def _frames_resize_args(frames, size, mode, out):
     """the checks of Context.frames_resize_to_image that need no device: (frames, (W, H), mode value); `out`, when given, is checked by the caller
     through _resize_layout"""
     what = "Context.frames_resize_to_image"
-    if frames.dtype not in (torch.uint8, torch.float32) or frames.dim() != 4 or not frames.is_contiguous() or min(frames.shape) < 1:
-        raise ValueError(f"{what}: frames must be a contiguous, non-empty uint8 or float32 tensor [B][D][Nx][Ny]")
+    B, D = _frames4(frames, what)[:2]
     if mode not in RESIZE_MODES:
         raise ValueError(f"{what}: mode must be one of {sorted(RESIZE_MODES)}")
-    try:
-        W, H = (int(v) for v in size)
-    except (TypeError, ValueError):
-        raise ValueError(f"{what}: size must be (W, H)") from None
+    W, H = _two_ints(size, what, "size must be (W, H)")
     if W < 1 or H < 1:
         raise ValueError(f"{what}: size must be positive")
-    B, D = frames.shape[:2]
     if out is not None and (out.dim() != 4 or tuple(out.shape) != (B, H, W, D)):
         raise ValueError(f"{what}: out must be a uint8 tensor of shape {(B, H, W, D)}")
     return W, H, RESIZE_MODES[mode]
@@ -359,9 +370,7 @@ def _frames_degrade_args(frames, blur, sigma, impulse, seed, first_frame, out, d
     """the checks of Context.frames_degrade that need no device: (blur, sigma, impulse, seed, first_frame, the result's dtype) as the C call takes
     them; `out`, when given, has the frames' shape and is `frames` itself only in the element-wise case (blur == 0, the same dtype)"""
     what = "Context.frames_degrade"
-    if frames.dtype not in (torch.uint8, torch.float32) or frames.dim() != 4 or not frames.is_contiguous() or min(frames.shape) < 1:
-        raise ValueError(f"{what}: frames must be a contiguous, non-empty uint8 or float32 tensor [B][D][Nx][Ny]")
-    B, D, Nx, Ny = frames.shape
+    B, D, Nx, Ny = _frames4(frames, what)
     if not 1 <= D <= 4 or Nx > 8192 or Ny > 8192:
         raise ValueError(f"{what}: D must be 1..4 and Nx, Ny in 1..8192; got shape {tuple(frames.shape)}")
     if isinstance(blur, bool) or int(blur) != blur or not 0 <= blur <= 4:
@@ -426,10 +435,7 @@ def _image_tiles_args(image, tile, overlap, rim, out, dtype):
     B, H, W, D = img.shape
     if not 1 <= D <= 4:
         raise ValueError(f"{what}: D must be 1..4")
-    try:
-        Nx, Ny = (int(v) for v in tile)
-    except (TypeError, ValueError):
-        raise ValueError(f"{what}: tile must be (Nx, Ny)") from None
+    Nx, Ny = _two_ints(tile, what, "tile must be (Nx, Ny)")
     desc, plan = tile_plan(W, H, Nx, Ny, overlap, rim)
     shape = (B * plan.ntx * plan.nty, D, Nx, Ny)
     if out is not None:
@@ -445,15 +451,10 @@ def _frames_tiles_args(frames, size, overlap, rim, out):
     """the checks of Context.frames_tiles_to_image that need no device: (the TileDesc, the shape (B, H, W, D) of the image); `out`, when given,
     is checked for that shape here and for its layout by the caller through _resize_layout"""
     what = "Context.frames_tiles_to_image"
-    if frames.dtype not in (torch.uint8, torch.float32) or frames.dim() != 4 or not frames.is_contiguous() or min(frames.shape) < 1:
-        raise ValueError(f"{what}: frames must be a contiguous, non-empty uint8 or float32 tensor [T][D][Nx][Ny]")
-    T, D, Nx, Ny = frames.shape
+    T, D, Nx, Ny = _frames4(frames, what, "[T][D][Nx][Ny]")
     if not 1 <= D <= 4:
         raise ValueError(f"{what}: D must be 1..4")
-    try:
-        W, H = (int(v) for v in size)
-    except (TypeError, ValueError):
-        raise ValueError(f"{what}: size must be (W, H)") from None
+    W, H = _two_ints(size, what, "size must be (W, H)")
     desc, plan = tile_plan(W, H, Nx, Ny, overlap, rim)
     per = plan.ntx * plan.nty
     if T % per:
@@ -713,10 +714,7 @@ class Context:
         B, H, W, D = img.shape
         if mode not in RESIZE_MODES:
             raise ValueError(f"{what}: mode must be one of {sorted(RESIZE_MODES)}")
-        try:
-            Nx, Ny = (int(v) for v in size)
-        except (TypeError, ValueError):
-            raise ValueError(f"{what}: size must be (Nx, Ny)") from None
+        Nx, Ny = _two_ints(size, what, "size must be (Nx, Ny)")
         if out is None:
             if dtype not in (torch.uint8, torch.float32):
                 raise ValueError(f"{what}: dtype must be torch.uint8 or torch.float32")
@@ -822,10 +820,7 @@ class Context:
         desc, B, W, H, D, keep = _yuv_source(planes, fmt, matrix, order, what)      # (keep: the views the descriptor points into)
         if mode not in RESIZE_MODES:
             raise ValueError(f"{what}: mode must be one of {sorted(RESIZE_MODES)}")
-        try:
-            Nx, Ny = (int(v) for v in size)
-        except (TypeError, ValueError):
-            raise ValueError(f"{what}: size must be (Nx, Ny)") from None
+        Nx, Ny = _two_ints(size, what, "size must be (Nx, Ny)")
         if out is None:
             if dtype not in (torch.uint8, torch.float32):
                 raise ValueError(f"{what}: dtype must be torch.uint8 or torch.float32")

@@ -1,5 +1,5 @@
 // C-ABI layer (include/aefft.h), context part: aefft_ctx create / destroy, the development switches (AEFFT_FLAGS, aefft_ctx_set_flags),
-// workspaces, side streams and their CU partition, and the profiling API.  The op-level entry points are in ops.hip, the resident
+// workspaces, side streams and their CU partition, and the profiling API.  The op-level entry points are in ops.hip, the image-boundary ones in image_ops.hip, the resident
 // network in net.hip, net_forward.hip, net_score.hip and net_step.hip; host.h is what they share.  Host-side orchestration only -- all arithmetic lives in the
 // *_kernels.hip files.
 #include "host.h"

@@ -21,10 +21,10 @@
 // schedule and the counter's frame words are the same in the whole launch: scalar registers.  Each round's two products are one 32 x 32 -> 64-bit
 // multiply each.  When m == 0 and t == 0 (a blur alone, or the copy) the launch makes no Philox call at all.
 // No scratch, no atomics, no workspace.  The kernel bodies are plain C++ over (threadIdx, blockIdx, gridDim, __syncthreads) and an LDS pointer:
-// tools/degrade_hostcheck.cpp compiles this file for the host, threads as lanes, under the sanitizers (AEFFT_DEGRADE_HOSTCHECK: it supplies those
+// tools/degrade_hostcheck.cpp compiles this file for the host, threads as lanes, under the sanitizers (AEFFT_HOSTCHECK: tools/hostlanes.h and the program supply those
 // names, px_u8 and the byte sum, and leaves the launcher out).
 #include <math.h>
-#ifndef AEFFT_DEGRADE_HOSTCHECK
+#ifndef AEFFT_HOSTCHECK
 #include "internal.h"
 #include "fft_common.h"
 #define DG_HD __device__ __forceinline__
@@ -273,7 +273,7 @@ static inline DgArgs dg_geometry(const void* src, void* dst, int B, int D, int N
 // grid.x of a launch: 256 quads each for R == 0, D x the tiles of a plane otherwise (at most 2^18 and 2^17)
 static inline unsigned dg_grid_x(int R, const DgArgs& g) { return R == 0 ? (g.P / 4u + (g.P % 4u ? 1u : 0u) + 255u) / 256u : (unsigned)g.D * (unsigned)g.tiles; }
 
-#ifndef AEFFT_DEGRADE_HOSTCHECK
+#ifndef AEFFT_HOSTCHECK
 template <int R, bool SF32, bool DF32, bool WORDS>
 __global__ __launch_bounds__(256) void degrade_kernel(const DgArgs a)
 {

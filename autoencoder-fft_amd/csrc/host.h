@@ -1,5 +1,5 @@
 // Host-side interface of the C-ABI layer (include/aefft.h), shared by its units: aefft_capi.hip (context, workspaces, flags,
-// side streams, profiling), ops.hip (op helpers, op-level and spatial entry points), net.hip, net_forward.hip, net_score.hip and net_step.hip (resident network).
+// side streams, profiling), ops.hip (op helpers, op-level and spatial entry points), image_ops.hip (image-boundary entry points), net.hip, net_forward.hip, net_score.hip and net_step.hip (resident network).
 // The context and the profiling brackets, and the helpers one unit defines for another.  Nothing here is exported.
 #pragma once
 #include "../../include/aefft.h"
@@ -105,7 +105,8 @@ int ws_get(aefft_ctx* ctx, int slot, size_t bytes, void** out);
 int ensure_aux(aefft_ctx* ctx);
 int join_recon(aefft_ctx* ctx);
 
-// ---- ops.hip (all enqueue on ctx->cur) -------------------------------------------------
+// ---- ops.hip (all enqueue on ctx->cur); image_ops.hip defines nothing for another unit ----
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }   // (ops.hip and image_ops.hip: required pointers)
 long bins(int Nx, int Ny);
 int chk_size(aefft_ctx* ctx, int Nx, int Ny);
 bool net_size(int n);

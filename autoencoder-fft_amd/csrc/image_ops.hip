@@ -1,0 +1,275 @@
+// C-ABI layer (include/aefft.h), image boundary: the entry points between camera images as delivered and the library's planar frames.  Host code only:
+// every call checks its arguments, joins a deferred reconstruction and hands over to the launcher of its kernel file.
+#include "host.h"
+#include <climits>
+#include <cmath>
+
+using namespace aefft;
+
+// image boundary ------------------------------------------------------------------------------
+// the rules of include/aefft.h "image boundary", each once; where two calls word one rule differently, the words are an argument; nothing is enqueued
+// when one fails.  A rejection is AEFFT_EINVAL with "<call>: <rule>" as the context's last error
+struct Bad {
+    aefft_ctx* ctx; const char* fn;
+    int operator()(const std::string& rule) const { return fail(ctx, AEFFT_EINVAL, (std::string(fn) + ": " + rule).c_str()); }
+};
+static const size_t HALF = ~size_t(0) >> 1;          // what "fits the address space" means
+static bool dim_ok(int v) { return v >= 1 && v <= 8192; }
+static bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb)
+{
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+    return a0 < b0 + nb && b0 < a0 + na;
+}
+// the sizes of a batch of images or frames: D, B and the two sizes; `names` is how the call's sentence lists them, `others` the verdict on further sizes it lists
+static int chk_dims(const Bad& bad, int B, int D, int W, int H, const char* names = "W, H", bool others = true)
+{
+    if (D < 1 || D > 4) return bad("D must be 1..4 (grey, BGR, BGRA)");
+    if (B < 1 || !dim_ok(W) || !dim_ok(H) || !others) return bad(std::string("B must be >= 1 and ") + names + " in 1..8192");
+    return AEFFT_OK;
+}
+static int chk_frame_size(const Bad& bad, int Nx, int Ny) { return dim_ok(Nx) && dim_ok(Ny) ? AEFFT_OK : bad("Nx, Ny must be in 1..8192"); }
+// the image buffer rule: B buffers of `rows` rows, `live` bytes of each row used, a pitch between rows and a stride between buffers (read for
+// B > 1 only).  `extent` receives the bytes from the first buffer's first byte to the last one's last live byte
+struct RowWords { const char *pitch, *rows, *stride, *batch; };
+static const RowWords IMAGE_WORDS = {"pitch must be at least W * D bytes", "H * pitch does not fit the address space",
+                                     "image_stride must be at least (H - 1) * pitch + W * D bytes for B > 1", "B * image_stride does not fit the address space"};
+// (aefft_image_to_frames / aefft_frames_to_image have no stride argument: image b + 1 starts Ny * pitch behind image b, and one bound covers the batch)
+static const RowWords PACKED_WORDS = {"pitch must be at least Nx * D bytes", "B * Ny * pitch does not fit the address space", nullptr, nullptr};
+static const RowWords PLANE_WORDS = {"pitch too small: pitch[0] >= W (YUYV 2 W), NV12 pitch[1] >= 2 ceil(W / 2), I420 pitch[1], pitch[2] >= ceil(W / 2)",
+                                     "rows * pitch does not fit the address space", "stride too small: each used stride[k] must be at least (rows - 1) * "
+                                     "pitch[k] + the live bytes of a row for B > 1", "B * stride does not fit the address space"};
+static int chk_rows(const Bad& bad, const RowWords& w, size_t pitch, size_t stride, size_t live, size_t rows, int B, size_t* extent)
+{
+    if (pitch < live) return bad(w.pitch);
+    if (!w.stride) { rows *= (size_t)B; B = 1; }
+    if (pitch > HALF / rows) return bad(w.rows);
+    const size_t one = (rows - 1) * pitch + live;                              // the bytes of one buffer, up to its last row's live bytes
+    if (B > 1 && stride < one) return bad(w.stride);
+    if (B > 1 && stride > (HALF - one) / (size_t)(B - 1)) return bad(w.batch);
+    *extent = (B > 1 ? (size_t)(B - 1) * stride : 0) + one;
+    return AEFFT_OK;
+}
+static int chk_present_image(const Bad& bad, size_t pitch, size_t image_stride, int W, int H, int B, int D, size_t* extent)
+{
+    RET_IF(chk_dims(bad, B, D, W, H));
+    return chk_rows(bad, IMAGE_WORDS, pitch, image_stride, (size_t)W * D, (size_t)H, B, extent);
+}
+// the frames buffer rule: `count` (B, or the tile calls' T) frames of D * Nx * Ny elements, 8-bit or float, behind a 16-byte aligned pointer; `bytes`
+// receives their size.  `names`: the pointer(s) the alignment sentence speaks of; `int_rule`, where set: the sentence for a count beyond an int
+static int chk_frames_aligned16(const Bad& bad, const void* p, const char* names, const char* count_name, size_t count, int D, int Nx, int Ny, int u8, size_t* bytes, const char* int_rule = nullptr)
+{
+    if (!aligned16(p)) return bad(std::string(names) + " must be 16-byte aligned");
+    if (int_rule && count > (size_t)INT_MAX) return bad(int_rule);
+    const size_t per = (size_t)D * Nx * Ny * (u8 ? 1 : 4);                     // (at most 2^30 bytes of one frame set)
+    if (count > HALF / per) return bad(std::string(count_name) + " * D * Nx * Ny does not fit the address space");
+    *bytes = count * per;
+    return AEFFT_OK;
+}
+// the mode rule: LINEAR or AREA, and AREA from (sw, sh) to (dw, dh) does not enlarge; `needs` words that for the call's direction
+static int chk_mode(const Bad& bad, int mode, int sw, int sh, int dw, int dh, const char* needs)
+{
+    if (mode != AEFFT_RESIZE_LINEAR && mode != AEFFT_RESIZE_AREA) return bad("mode must be AEFFT_RESIZE_LINEAR or AEFFT_RESIZE_AREA");
+    if (mode == AEFFT_RESIZE_AREA && (dw > sw || dh > sh)) return bad(std::string("AEFFT_RESIZE_AREA does not enlarge: it needs ") + needs);
+    return AEFFT_OK;
+}
+
+// pack and unpack -----------------------------------------------------------------------------
+static int chk_image(const Bad& bad, const void* image_d, size_t pitch, const void* frames_d, int frames_u8, int B, int D, int Nx, int Ny)
+{
+    if (!bad.ctx || !image_d || !frames_d) return bad("null context, image or frames");
+    RET_IF(chk_dims(bad, B, D, Nx, Ny, "Nx, Ny"));
+    size_t extent = 0, fb = 0;                        // the bytes either side touches: the image up to the last row's Nx * D, the frames whole
+    RET_IF(chk_rows(bad, PACKED_WORDS, pitch, 0, (size_t)Nx * D, (size_t)Ny, B, &extent));
+    RET_IF(chk_frames_aligned16(bad, frames_d, "frames_d", "B", (size_t)B, D, Nx, Ny, frames_u8, &fb));
+    if (ranges_overlap(frames_d, fb, image_d, extent)) return bad("the frame and image ranges overlap (the op is out-of-place)");
+    return AEFFT_OK;
+}
+
+extern "C" int aefft_image_to_frames(aefft_ctx* ctx, const unsigned char* image_d, size_t pitch, void* frames_d, int frames_u8, int B, int D, int Nx, int Ny)
+{
+    RET_IF(chk_image(Bad{ctx, "aefft_image_to_frames"}, image_d, pitch, frames_d, frames_u8, B, D, Nx, Ny));
+    RET_IF(join_recon(ctx));                          // (frames_d may be a buffer a deferred reconstruction is still writing)
+    return launch_or_fail(ctx, KID_IMAGE, (double)B * D * Nx * Ny * (frames_u8 ? 2.0 : 5.0), "image_unpack",
+                          [&] { return launch_image_unpack(image_d, pitch, frames_d, !frames_u8, B, D, Nx, Ny, ctx->cur); });
+}
+
+extern "C" int aefft_frames_to_image(aefft_ctx* ctx, const void* frames_d, int frames_u8, unsigned char* image_d, size_t pitch, int B, int D, int Nx, int Ny)
+{
+    RET_IF(chk_image(Bad{ctx, "aefft_frames_to_image"}, image_d, pitch, frames_d, frames_u8, B, D, Nx, Ny));
+    RET_IF(join_recon(ctx));                          // (frames_d may be the reconstruction of a step whose inverse transform is still on the side stream)
+    return launch_or_fail(ctx, KID_IMAGE, (double)B * D * Nx * Ny * (frames_u8 ? 2.0 : 5.0), "image_pack",
+                          [&] { return launch_image_pack(frames_d, !frames_u8, image_d, pitch, B, D, Nx, Ny, ctx->cur); });
+}
+
+// resize in and out, overlay, degrade ---------------------------------------------------------
+extern "C" int aefft_image_resize_to_frames(aefft_ctx* ctx, const unsigned char* image_d, size_t pitch, size_t image_stride, int W, int H, int mode,
+                                            void* frames_d, int frames_u8, int B, int D, int Nx, int Ny)
+{
+    const Bad bad{ctx, "aefft_image_resize_to_frames"};
+    if (!ctx || !image_d || !frames_d) return bad("null context, image or frames");
+    RET_IF(chk_dims(bad, B, D, W, H, "W, H, Nx, Ny", dim_ok(Nx) && dim_ok(Ny)));
+    RET_IF(chk_mode(bad, mode, W, H, Nx, Ny, "Nx <= W and Ny <= H"));
+    size_t extent = 0, fb = 0;
+    RET_IF(chk_rows(bad, IMAGE_WORDS, pitch, image_stride, (size_t)W * D, (size_t)H, B, &extent));
+    RET_IF(chk_frames_aligned16(bad, frames_d, "frames_d", "B", (size_t)B, D, Nx, Ny, frames_u8, &fb));
+    if (ranges_overlap(frames_d, fb, image_d, extent)) return bad("the frame and image ranges overlap (the op is out-of-place)");
+    RET_IF(join_recon(ctx));                          // (frames_d may be a buffer a deferred reconstruction is still writing)
+    return launch_or_fail(ctx, KID_IMAGE, (double)B * D * ((double)W * H + (double)Nx * Ny * (frames_u8 ? 1.0 : 4.0)), "image_resize",
+                          [&] { return launch_image_resize(image_d, pitch, image_stride, W, H, mode, frames_d, !frames_u8, B, D, Nx, Ny, ctx->cur); });
+}
+
+extern "C" int aefft_frames_resize_to_image(aefft_ctx* ctx, const void* frames_d, int frames_u8, int Nx, int Ny, int mode,
+                                            unsigned char* image_d, size_t pitch, size_t image_stride, int W, int H, int B, int D)
+{
+    const Bad bad{ctx, "aefft_frames_resize_to_image"};
+    if (!ctx || !image_d || !frames_d) return bad("null context, image or frames");
+    RET_IF(chk_frame_size(bad, Nx, Ny));
+    size_t extent = 0, fb = 0;
+    RET_IF(chk_present_image(bad, pitch, image_stride, W, H, B, D, &extent));
+    RET_IF(chk_mode(bad, mode, Nx, Ny, W, H, "W <= Nx and H <= Ny"));
+    RET_IF(chk_frames_aligned16(bad, frames_d, "frames_d", "B", (size_t)B, D, Nx, Ny, frames_u8, &fb));
+    if (ranges_overlap(frames_d, fb, image_d, extent)) return bad("the frame and image ranges overlap (the op is out-of-place)");
+    RET_IF(join_recon(ctx));                          // (frames_d may be the reconstruction of a step whose inverse transform is still on the side stream)
+    return launch_or_fail(ctx, KID_IMAGE, (double)B * D * ((double)Nx * Ny * (frames_u8 ? 1.0 : 4.0) + (double)W * H), "frames_resize",
+                          [&] { return launch_frames_resize(frames_d, !frames_u8, Nx, Ny, mode, image_d, pitch, image_stride, W, H, B, D, ctx->cur); });
+}
+
+extern "C" int aefft_map_overlay_image(aefft_ctx* ctx, const float* map_d, int Mx, int My, float lo, float hi, int smooth, const unsigned char* lut_d, int alpha,
+                                       unsigned char* image_d, size_t pitch, size_t image_stride, int W, int H, int B, int D)
+{
+    const Bad bad{ctx, "aefft_map_overlay_image"};
+    if (!ctx || !map_d || !lut_d || !image_d) return bad("null context, map, lut or image");
+    if (Mx < 1 || My < 1 || Mx > 1024 || My > 1024) return bad("Mx, My must be in 1..1024");
+    size_t extent = 0;
+    RET_IF(chk_present_image(bad, pitch, image_stride, W, H, B, D, &extent));
+    if (alpha < 0 || alpha > 256) return bad("alpha must be 0..256");
+    const float inv = 255.0f / (hi - lo);
+    if (!std::isfinite(lo) || !std::isfinite(hi) || lo == hi || !std::isfinite(inv)) return bad("lo and hi must be finite and different (255 / (hi - lo) finite)");
+    if (!aligned16(map_d)) return bad("map_d must be 16-byte aligned");
+    if ((size_t)B > HALF / ((size_t)4 * Mx * My)) return bad("B * Mx * My does not fit the address space");
+    if (ranges_overlap(map_d, (size_t)B * Mx * My * 4, image_d, extent)) return bad("the map and image ranges overlap");
+    if (ranges_overlap(lut_d, (size_t)256 * D, image_d, extent)) return bad("the lut and image ranges overlap");
+    RET_IF(join_recon(ctx));                          // (image_d may hold a reconstruction that is still on the side stream)
+    return launch_or_fail(ctx, KID_IMAGE, (double)B * (4.0 * Mx * My + 2.0 * D * W * H) + 256.0 * D, "map_overlay",
+                          [&] { return launch_map_overlay(map_d, Mx, My, lo, inv, smooth, lut_d, alpha, image_d, pitch, image_stride, W, H, B, D, ctx->cur); });
+}
+
+extern "C" int aefft_frames_degrade(aefft_ctx* ctx, const void* src_d, int src_u8, void* dst_d, int dst_u8, int B, int D, int Nx, int Ny,
+                                    int blur, float sigma, float impulse, unsigned long long seed, unsigned long long first_frame)
+{
+    const Bad bad{ctx, "aefft_frames_degrade"};
+    if (!ctx || !src_d || !dst_d) return bad("null context, source or destination");
+    RET_IF(chk_dims(bad, B, D, Nx, Ny, "Nx, Ny"));
+    if (blur < 0 || blur > 4) return bad("blur must be 0..4");
+    if (!std::isfinite(sigma) || sigma < 0.f || sigma > 255.f) return bad("sigma must be finite and in 0..255");
+    if (!std::isfinite(impulse) || impulse < 0.f || impulse > 1.f) return bad("impulse must be finite and in 0..1");
+    size_t sb = 0, db = 0;
+    RET_IF(chk_frames_aligned16(bad, src_d, "src_d and dst_d", "B", (size_t)B, D, Nx, Ny, src_u8, &sb));
+    RET_IF(chk_frames_aligned16(bad, dst_d, "src_d and dst_d", "B", (size_t)B, D, Nx, Ny, dst_u8, &db));
+    const bool in_place = dst_d == src_d && blur == 0 && !src_u8 == !dst_u8;
+    if (!in_place && ranges_overlap(src_d, sb, dst_d, db)) return bad("the source and destination ranges overlap (in place needs dst_d == src_d, blur == 0 and src_u8 == dst_u8)");
+    RET_IF(join_recon(ctx));                          // (src_d may be a reconstruction that is still on the side stream)
+    return launch_or_fail(ctx, KID_IMAGE, (double)(sb + db), "frames_degrade",
+                          [&] { return launch_degrade(src_d, !src_u8, dst_d, !dst_u8, B, D, Nx, Ny, blur, sigma, impulse, seed, first_frame, ctx->cur); });
+}
+
+// YUV video -----------------------------------------------------------------------------------
+// the source bytes one image's conversion reads: the luma samples and, unless the order is GRAY, the chroma samples (YUYV: the rows whole)
+static double yuv_bytes(const aefft_yuv_desc& s, int order)
+{
+    const double W = s.W, H = s.H, Wc = (s.W + 1) / 2, Hc = (s.H + 1) / 2;
+    if (s.format == AEFFT_YUV_YUYV) return 2.0 * W * H;
+    return W * H + (order == AEFFT_YUV_GRAY ? 0.0 : 2.0 * Wc * Hc);
+}
+// the source rules aefft_yuv_to_image and aefft_yuv_resize_to_frames share: `D` receives the channels the order asks for, `used` the planes the call
+// reads and `extent[k]` the bytes of plane k over the B images, first byte to last
+static int chk_yuv_source(const Bad& bad, const aefft_yuv_desc* src, int order, int B, int* D, int* used, size_t* extent)
+{
+    if (src->format != AEFFT_YUV_NV12 && src->format != AEFFT_YUV_I420 && src->format != AEFFT_YUV_YUYV) return bad("format must be AEFFT_YUV_NV12, AEFFT_YUV_I420 or AEFFT_YUV_YUYV");
+    if (src->matrix != AEFFT_YUV_BT601 && src->matrix != AEFFT_YUV_BT709 && src->matrix != AEFFT_YUV_JPEG) return bad("matrix must be AEFFT_YUV_BT601, AEFFT_YUV_BT709 or AEFFT_YUV_JPEG");
+    if (order != AEFFT_YUV_BGR && order != AEFFT_YUV_RGB && order != AEFFT_YUV_GRAY) return bad("order must be AEFFT_YUV_BGR, AEFFT_YUV_RGB or AEFFT_YUV_GRAY");
+    *D = order == AEFFT_YUV_GRAY ? 1 : 3;
+    RET_IF(chk_dims(bad, B, *D, src->W, src->H));
+    const bool yuyv = src->format == AEFFT_YUV_YUYV;
+    if (yuyv && (src->W & 1)) return bad("YUYV needs an even W");
+    const size_t W = (size_t)src->W, H = (size_t)src->H, Wc = (W + 1) / 2, Hc = (H + 1) / 2;
+    // live bytes of a row and rows of each plane
+    const size_t live[3] = {yuyv ? 2 * W : W, src->format == AEFFT_YUV_NV12 ? 2 * Wc : Wc, Wc}, rows[3] = {H, Hc, Hc};
+    *used = order == AEFFT_YUV_GRAY || yuyv ? 1 : (src->format == AEFFT_YUV_NV12 ? 2 : 3);
+    for (int k = 0; k < *used; ++k) {
+        if (!src->plane[k]) return bad("null plane (NV12 needs plane[0..1], I420 plane[0..2], YUYV and AEFFT_YUV_GRAY plane[0])");
+        RET_IF(chk_rows(bad, PLANE_WORDS, src->pitch[k], src->stride[k], live[k], rows[k], B, &extent[k]));
+    }
+    return AEFFT_OK;
+}
+
+extern "C" int aefft_yuv_to_image(aefft_ctx* ctx, const aefft_yuv_desc* src, int order, unsigned char* image_d, size_t pitch, size_t image_stride, int B)
+{
+    const Bad bad{ctx, "aefft_yuv_to_image"};
+    if (!ctx || !src || !image_d) return bad("null context, descriptor or image");
+    int D = 0, used = 0;
+    size_t sext[3] = {0, 0, 0}, extent = 0;
+    RET_IF(chk_yuv_source(bad, src, order, B, &D, &used, sext));
+    RET_IF(chk_rows(bad, IMAGE_WORDS, pitch, image_stride, (size_t)src->W * D, (size_t)src->H, B, &extent));
+    for (int k = 0; k < used; ++k)
+        if (ranges_overlap(src->plane[k], sext[k], image_d, extent)) return bad("a source plane and the image range overlap (the op is out-of-place)");
+    RET_IF(join_recon(ctx));                          // (a plane may be a buffer the side stream is still writing)
+    return launch_or_fail(ctx, KID_IMAGE, (double)B * (yuv_bytes(*src, order) + (double)D * src->W * src->H), "yuv_to_image", [&] {
+        return launch_yuv_image(src->format, src->plane, src->pitch, src->stride, src->W, src->H, src->matrix, order, image_d, pitch, image_stride, B, ctx->cur);
+    });
+}
+
+extern "C" int aefft_yuv_resize_to_frames(aefft_ctx* ctx, const aefft_yuv_desc* src, int order, int mode, void* frames_d, int frames_u8, int B, int Nx, int Ny)
+{
+    const Bad bad{ctx, "aefft_yuv_resize_to_frames"};
+    if (!ctx || !src || !frames_d) return bad("null context, descriptor or frames");
+    int D = 0, used = 0;
+    size_t sext[3] = {0, 0, 0}, fb = 0;
+    RET_IF(chk_yuv_source(bad, src, order, B, &D, &used, sext));
+    RET_IF(chk_frame_size(bad, Nx, Ny));
+    RET_IF(chk_mode(bad, mode, src->W, src->H, Nx, Ny, "Nx <= W and Ny <= H"));
+    RET_IF(chk_frames_aligned16(bad, frames_d, "frames_d", "B", (size_t)B, D, Nx, Ny, frames_u8, &fb));
+    for (int k = 0; k < used; ++k)
+        if (ranges_overlap(src->plane[k], sext[k], frames_d, fb)) return bad("a source plane and the frame range overlap (the op is out-of-place)");
+    RET_IF(join_recon(ctx));                          // (frames_d may be a buffer a deferred reconstruction is still writing)
+    return launch_or_fail(ctx, KID_IMAGE, (double)B * (yuv_bytes(*src, order) + (double)(fb / (size_t)B)), "yuv_resize", [&] {
+        return launch_yuv_resize(src->format, src->plane, src->pitch, src->stride, src->W, src->H, src->matrix, order, mode, frames_d, !frames_u8, B, Nx, Ny, ctx->cur);
+    });
+}
+
+// tiled inference (include/aefft.h "tiled inference"): the plan is host arithmetic only --------
+extern "C" int aefft_tile_plan_make(const aefft_tile_desc* desc, aefft_tile_plan* plan) { return tile_plan(desc, plan) ? AEFFT_OK : AEFFT_EINVAL; }
+
+// the rules aefft_image_tiles_to_frames and aefft_frames_tiles_to_image share; `frame_bytes` receives the bytes of the T tile frames
+static int chk_tiles(const Bad& bad, const void* image_d, size_t pitch, size_t image_stride, const aefft_tile_desc* desc, const void* frames_d, int frames_u8, int B, int D, size_t* frame_bytes)
+{
+    if (!bad.ctx || !image_d || !frames_d || !desc) return bad("null context, image, frames or description");
+    aefft_tile_plan plan;
+    if (!tile_plan(desc, &plan)) return bad("the description is not one aefft_tile_plan_make takes (W, H in 1..8192; Nx, Ny in 2..2048; 0 <= 2 overlap <= N; 0 <= 2 rim <= overlap)");
+    size_t extent = 0;
+    RET_IF(chk_present_image(bad, pitch, image_stride, desc->W, desc->H, B, D, &extent));
+    const size_t T = (size_t)B * plan.ntx * plan.nty;                            // (at most 2^26 tiles of an image, at most 2^26 bytes of a tile)
+    RET_IF(chk_frames_aligned16(bad, frames_d, "frames_d", "T", T, D, desc->Nx, desc->Ny, frames_u8, frame_bytes, "B * ntx * nty tiles do not fit an int"));
+    if (ranges_overlap(frames_d, *frame_bytes, image_d, extent)) return bad("the frame and image ranges overlap (the op is out-of-place)");
+    return AEFFT_OK;
+}
+
+extern "C" int aefft_image_tiles_to_frames(aefft_ctx* ctx, const unsigned char* image_d, size_t pitch, size_t image_stride, const aefft_tile_desc* desc,
+                                           void* frames_d, int frames_u8, int B, int D)
+{
+    size_t fb = 0;
+    RET_IF(chk_tiles(Bad{ctx, "aefft_image_tiles_to_frames"}, image_d, pitch, image_stride, desc, frames_d, frames_u8, B, D, &fb));
+    RET_IF(join_recon(ctx));                          // (frames_d may be a buffer a deferred reconstruction is still writing)
+    return launch_or_fail(ctx, KID_IMAGE, (double)B * D * desc->W * desc->H + (double)fb, "tile_gather",
+                          [&] { return launch_tile_gather(image_d, pitch, image_stride, desc, frames_d, !frames_u8, B, D, ctx->cur); });
+}
+
+extern "C" int aefft_frames_tiles_to_image(aefft_ctx* ctx, const void* frames_d, int frames_u8, const aefft_tile_desc* desc, unsigned char* image_d,
+                                           size_t pitch, size_t image_stride, int B, int D)
+{
+    size_t fb = 0;
+    RET_IF(chk_tiles(Bad{ctx, "aefft_frames_tiles_to_image"}, image_d, pitch, image_stride, desc, frames_d, frames_u8, B, D, &fb));
+    RET_IF(join_recon(ctx));                          // (frames_d may be the reconstruction of a step whose inverse transform is still on the side stream)
+    return launch_or_fail(ctx, KID_IMAGE, (double)B * D * desc->W * desc->H + (double)fb, "tile_blend",
+                          [&] { return launch_tile_blend(frames_d, !frames_u8, desc, image_d, pitch, image_stride, B, D, ctx->cur); });
+}

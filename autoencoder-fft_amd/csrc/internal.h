@@ -1,4 +1,4 @@
-// Internal launch interface between the HIP kernel files and the C-ABI layer (aefft_capi.hip, ops.hip, net.hip, net_forward.hip, net_score.hip, net_step.hip).
+// Internal launch interface between the HIP kernel files and the C-ABI layer (aefft_capi.hip, ops.hip, image_ops.hip, net.hip, net_forward.hip, net_score.hip, net_step.hip).
 // Nothing here is exported; the public boundary is include/aefft.h and the three C++ headers.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,15 +1,12 @@
 // C-ABI layer (include/aefft.h), op level: the internal op helpers -- transform routes and size checks, contractions and their
 // descriptors, the gradient, the kernel-support transforms, the update -- which the network units (net.hip, net_step.hip) build on,
-// and the op-level, spatial and image-boundary entry points.
+// and the op-level and spatial entry points.  (The image-boundary entry points are in image_ops.hip.)
 #include "host.h"
 
 #include <algorithm>
-#include <climits>
 #include <cmath>
 
 using namespace aefft;
-
-static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // ------------------------------------------------------------------------------------------
 // internal op helpers (all enqueue on ctx->cur)
@@ -746,277 +743,4 @@ extern "C" int aefft_step_spatial(aefft_ctx* ctx, const float* in_d, float* hin_
     RET_IF(aefft_conv_spatial(ctx, hin_d, out_d, f_d, p_d, B, dM, dD, Nx, Ny, Nk, Nl, cpu_semantics));
     return backprop_spatial_impl(ctx, in_d, out_d, hin_d, c_d, b_d, f_d, p_d, dc_d, db_d, df_d, dp_d, ddc_d, ddb_d, ddf_d, ddp_d,
                                  B, dD, dM, Nx, Ny, Nk, Nl, delmax, alpha, tied, cpu_semantics, true);
-}
-
-// image boundary ------------------------------------------------------------------------------
-// the rules both directions share (include/aefft.h "image boundary"); nothing is enqueued when one fails
-static int chk_image(aefft_ctx* ctx, const char* fn, const void* image_d, size_t pitch, const void* frames_d, int frames_u8, int B, int D, int Nx, int Ny)
-{
-    const auto bad = [&](const char* rule) { return fail(ctx, AEFFT_EINVAL, (std::string(fn) + ": " + rule).c_str()); };
-    if (!ctx || !image_d || !frames_d) return bad("null context, image or frames");
-    if (D < 1 || D > 4) return bad("D must be 1..4 (grey, BGR, BGRA)");
-    if (B < 1 || Nx < 1 || Ny < 1 || Nx > 8192 || Ny > 8192) return bad("B must be >= 1 and Nx, Ny in 1..8192");
-    if (pitch < (size_t)Nx * D) return bad("pitch must be at least Nx * D bytes");
-    const size_t rows = (size_t)B * Ny;
-    if (pitch > (~size_t(0) >> 1) / rows) return bad("B * Ny * pitch does not fit the address space");
-    if (!aligned16(frames_d)) return bad("frames_d must be 16-byte aligned");
-    // the bytes either side touches: the frames whole, the image up to the last row's Nx * D
-    const uintptr_t f0 = reinterpret_cast<uintptr_t>(frames_d), f1 = f0 + (size_t)B * D * Nx * Ny * (frames_u8 ? 1 : 4);
-    const uintptr_t i0 = reinterpret_cast<uintptr_t>(image_d), i1 = i0 + (rows - 1) * pitch + (size_t)Nx * D;
-    if (f0 < i1 && i0 < f1) return bad("the frame and image ranges overlap (the op is out-of-place)");
-    return AEFFT_OK;
-}
-
-extern "C" int aefft_image_to_frames(aefft_ctx* ctx, const unsigned char* image_d, size_t pitch, void* frames_d, int frames_u8, int B, int D, int Nx, int Ny)
-{
-    RET_IF(chk_image(ctx, "aefft_image_to_frames", image_d, pitch, frames_d, frames_u8, B, D, Nx, Ny));
-    RET_IF(join_recon(ctx));                          // (frames_d may be a buffer a deferred reconstruction is still writing)
-    return launch_or_fail(ctx, KID_IMAGE, (double)B * D * Nx * Ny * (frames_u8 ? 2.0 : 5.0), "image_unpack",
-                          [&] { return launch_image_unpack(image_d, pitch, frames_d, !frames_u8, B, D, Nx, Ny, ctx->cur); });
-}
-
-extern "C" int aefft_frames_to_image(aefft_ctx* ctx, const void* frames_d, int frames_u8, unsigned char* image_d, size_t pitch, int B, int D, int Nx, int Ny)
-{
-    RET_IF(chk_image(ctx, "aefft_frames_to_image", image_d, pitch, frames_d, frames_u8, B, D, Nx, Ny));
-    RET_IF(join_recon(ctx));                          // (frames_d may be the reconstruction of a step whose inverse transform is still on the side stream)
-    return launch_or_fail(ctx, KID_IMAGE, (double)B * D * Nx * Ny * (frames_u8 ? 2.0 : 5.0), "image_pack",
-                          [&] { return launch_image_pack(frames_d, !frames_u8, image_d, pitch, B, D, Nx, Ny, ctx->cur); });
-}
-
-// the rules of aefft_image_resize_to_frames (include/aefft.h "image boundary"); nothing is enqueued when one fails
-static int chk_resize(aefft_ctx* ctx, const unsigned char* image_d, size_t pitch, size_t image_stride, int W, int H, int mode, const void* frames_d,
-                      int frames_u8, int B, int D, int Nx, int Ny)
-{
-    const auto bad = [&](const char* rule) { return fail(ctx, AEFFT_EINVAL, (std::string("aefft_image_resize_to_frames: ") + rule).c_str()); };
-    const auto in = [](int v) { return v >= 1 && v <= 8192; };
-    if (!ctx || !image_d || !frames_d) return bad("null context, image or frames");
-    if (D < 1 || D > 4) return bad("D must be 1..4 (grey, BGR, BGRA)");
-    if (B < 1 || !in(W) || !in(H) || !in(Nx) || !in(Ny)) return bad("B must be >= 1 and W, H, Nx, Ny in 1..8192");
-    if (mode != AEFFT_RESIZE_LINEAR && mode != AEFFT_RESIZE_AREA) return bad("mode must be AEFFT_RESIZE_LINEAR or AEFFT_RESIZE_AREA");
-    if (mode == AEFFT_RESIZE_AREA && (Nx > W || Ny > H)) return bad("AEFFT_RESIZE_AREA does not enlarge: it needs Nx <= W and Ny <= H");
-    if (pitch < (size_t)W * D) return bad("pitch must be at least W * D bytes");
-    const size_t half = ~size_t(0) >> 1;
-    if (pitch > half / (size_t)H) return bad("H * pitch does not fit the address space");
-    const size_t extent = (size_t)(H - 1) * pitch + (size_t)W * D;             // the bytes of one image, up to its last row's W * D
-    if (B > 1 && image_stride < extent) return bad("image_stride must be at least (H - 1) * pitch + W * D bytes for B > 1");
-    if (B > 1 && image_stride > (half - extent) / (size_t)(B - 1)) return bad("B * image_stride does not fit the address space");
-    if (!aligned16(frames_d)) return bad("frames_d must be 16-byte aligned");
-    const uintptr_t f0 = reinterpret_cast<uintptr_t>(frames_d), f1 = f0 + (size_t)B * D * Nx * Ny * (frames_u8 ? 1 : 4);
-    const uintptr_t i0 = reinterpret_cast<uintptr_t>(image_d), i1 = i0 + (B > 1 ? (size_t)(B - 1) * image_stride : 0) + extent;
-    if (f0 < i1 && i0 < f1) return bad("the frame and image ranges overlap (the op is out-of-place)");
-    return AEFFT_OK;
-}
-
-extern "C" int aefft_image_resize_to_frames(aefft_ctx* ctx, const unsigned char* image_d, size_t pitch, size_t image_stride, int W, int H, int mode,
-                                            void* frames_d, int frames_u8, int B, int D, int Nx, int Ny)
-{
-    RET_IF(chk_resize(ctx, image_d, pitch, image_stride, W, H, mode, frames_d, frames_u8, B, D, Nx, Ny));
-    RET_IF(join_recon(ctx));                          // (frames_d may be a buffer a deferred reconstruction is still writing)
-    return launch_or_fail(ctx, KID_IMAGE, (double)B * D * ((double)W * H + (double)Nx * Ny * (frames_u8 ? 1.0 : 4.0)), "image_resize",
-                          [&] { return launch_image_resize(image_d, pitch, image_stride, W, H, mode, frames_d, !frames_u8, B, D, Nx, Ny, ctx->cur); });
-}
-
-// the image rules aefft_frames_resize_to_image and aefft_map_overlay_image share (include/aefft.h "image boundary"): `extent` receives the bytes of
-// the B images, first byte to last
-template <class Bad>
-static int chk_present_image(const Bad& bad, size_t pitch, size_t image_stride, int W, int H, int B, int D, size_t* extent)
-{
-    const auto in = [](int v) { return v >= 1 && v <= 8192; };
-    if (D < 1 || D > 4) return bad("D must be 1..4 (grey, BGR, BGRA)");
-    if (B < 1 || !in(W) || !in(H)) return bad("B must be >= 1 and W, H in 1..8192");
-    if (pitch < (size_t)W * D) return bad("pitch must be at least W * D bytes");
-    const size_t half = ~size_t(0) >> 1;
-    if (pitch > half / (size_t)H) return bad("H * pitch does not fit the address space");
-    const size_t one = (size_t)(H - 1) * pitch + (size_t)W * D;                // the bytes of one image, up to its last row's W * D
-    if (B > 1 && image_stride < one) return bad("image_stride must be at least (H - 1) * pitch + W * D bytes for B > 1");
-    if (B > 1 && image_stride > (half - one) / (size_t)(B - 1)) return bad("B * image_stride does not fit the address space");
-    *extent = (B > 1 ? (size_t)(B - 1) * image_stride : 0) + one;
-    return AEFFT_OK;
-}
-static bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb)
-{
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-    return a0 < b0 + nb && b0 < a0 + na;
-}
-
-extern "C" int aefft_frames_resize_to_image(aefft_ctx* ctx, const void* frames_d, int frames_u8, int Nx, int Ny, int mode,
-                                            unsigned char* image_d, size_t pitch, size_t image_stride, int W, int H, int B, int D)
-{
-    const auto bad = [&](const char* rule) { return fail(ctx, AEFFT_EINVAL, (std::string("aefft_frames_resize_to_image: ") + rule).c_str()); };
-    if (!ctx || !image_d || !frames_d) return bad("null context, image or frames");
-    if (Nx < 1 || Ny < 1 || Nx > 8192 || Ny > 8192) return bad("Nx, Ny must be in 1..8192");
-    size_t extent = 0;
-    RET_IF(chk_present_image(bad, pitch, image_stride, W, H, B, D, &extent));
-    if (mode != AEFFT_RESIZE_LINEAR && mode != AEFFT_RESIZE_AREA) return bad("mode must be AEFFT_RESIZE_LINEAR or AEFFT_RESIZE_AREA");
-    if (mode == AEFFT_RESIZE_AREA && (W > Nx || H > Ny)) return bad("AEFFT_RESIZE_AREA does not enlarge: it needs W <= Nx and H <= Ny");
-    if (!aligned16(frames_d)) return bad("frames_d must be 16-byte aligned");
-    const size_t per = (size_t)D * Nx * Ny * (frames_u8 ? 1 : 4);              // (at most 2^30 bytes of one image's frames)
-    if ((size_t)B > (~size_t(0) >> 1) / per) return bad("B * D * Nx * Ny does not fit the address space");
-    if (ranges_overlap(frames_d, (size_t)B * per, image_d, extent)) return bad("the frame and image ranges overlap (the op is out-of-place)");
-    RET_IF(join_recon(ctx));                          // (frames_d may be the reconstruction of a step whose inverse transform is still on the side stream)
-    return launch_or_fail(ctx, KID_IMAGE, (double)B * D * ((double)Nx * Ny * (frames_u8 ? 1.0 : 4.0) + (double)W * H), "frames_resize",
-                          [&] { return launch_frames_resize(frames_d, !frames_u8, Nx, Ny, mode, image_d, pitch, image_stride, W, H, B, D, ctx->cur); });
-}
-
-extern "C" int aefft_map_overlay_image(aefft_ctx* ctx, const float* map_d, int Mx, int My, float lo, float hi, int smooth,
-                                       const unsigned char* lut_d, int alpha,
-                                       unsigned char* image_d, size_t pitch, size_t image_stride, int W, int H, int B, int D)
-{
-    const auto bad = [&](const char* rule) { return fail(ctx, AEFFT_EINVAL, (std::string("aefft_map_overlay_image: ") + rule).c_str()); };
-    if (!ctx || !map_d || !lut_d || !image_d) return bad("null context, map, lut or image");
-    if (Mx < 1 || My < 1 || Mx > 1024 || My > 1024) return bad("Mx, My must be in 1..1024");
-    size_t extent = 0;
-    RET_IF(chk_present_image(bad, pitch, image_stride, W, H, B, D, &extent));
-    if (alpha < 0 || alpha > 256) return bad("alpha must be 0..256");
-    const float inv = 255.0f / (hi - lo);
-    if (!std::isfinite(lo) || !std::isfinite(hi) || lo == hi || !std::isfinite(inv)) return bad("lo and hi must be finite and different (255 / (hi - lo) finite)");
-    if (!aligned16(map_d)) return bad("map_d must be 16-byte aligned");
-    if ((size_t)B > (~size_t(0) >> 1) / ((size_t)4 * Mx * My)) return bad("B * Mx * My does not fit the address space");
-    if (ranges_overlap(map_d, (size_t)B * Mx * My * 4, image_d, extent)) return bad("the map and image ranges overlap");
-    if (ranges_overlap(lut_d, (size_t)256 * D, image_d, extent)) return bad("the lut and image ranges overlap");
-    RET_IF(join_recon(ctx));                          // (image_d may hold a reconstruction that is still on the side stream)
-    return launch_or_fail(ctx, KID_IMAGE, (double)B * (4.0 * Mx * My + 2.0 * D * W * H) + 256.0 * D, "map_overlay",
-                          [&] { return launch_map_overlay(map_d, Mx, My, lo, inv, smooth, lut_d, alpha, image_d, pitch, image_stride, W, H, B, D, ctx->cur); });
-}
-
-extern "C" int aefft_frames_degrade(aefft_ctx* ctx, const void* src_d, int src_u8, void* dst_d, int dst_u8, int B, int D, int Nx, int Ny,
-                                    int blur, float sigma, float impulse, unsigned long long seed, unsigned long long first_frame)
-{
-    const auto bad = [&](const char* rule) { return fail(ctx, AEFFT_EINVAL, (std::string("aefft_frames_degrade: ") + rule).c_str()); };
-    if (!ctx || !src_d || !dst_d) return bad("null context, source or destination");
-    if (D < 1 || D > 4) return bad("D must be 1..4 (grey, BGR, BGRA)");
-    if (B < 1 || Nx < 1 || Ny < 1 || Nx > 8192 || Ny > 8192) return bad("B must be >= 1 and Nx, Ny in 1..8192");
-    if (blur < 0 || blur > 4) return bad("blur must be 0..4");
-    if (!std::isfinite(sigma) || sigma < 0.f || sigma > 255.f) return bad("sigma must be finite and in 0..255");
-    if (!std::isfinite(impulse) || impulse < 0.f || impulse > 1.f) return bad("impulse must be finite and in 0..1");
-    if (!aligned16(src_d) || !aligned16(dst_d)) return bad("src_d and dst_d must be 16-byte aligned");
-    const size_t per = (size_t)D * Nx * Ny, ss = src_u8 ? 1 : 4, ds = dst_u8 ? 1 : 4;   // (at most 2^28 elements of a frame)
-    if ((size_t)B > (~size_t(0) >> 1) / (4 * per)) return bad("B * D * Nx * Ny does not fit the address space");
-    const bool in_place = dst_d == src_d && blur == 0 && ss == ds;
-    if (!in_place && ranges_overlap(src_d, (size_t)B * per * ss, dst_d, (size_t)B * per * ds))
-        return bad("the source and destination ranges overlap (in place needs dst_d == src_d, blur == 0 and src_u8 == dst_u8)");
-    RET_IF(join_recon(ctx));                          // (src_d may be a reconstruction that is still on the side stream)
-    return launch_or_fail(ctx, KID_IMAGE, (double)B * per * (double)(ss + ds), "frames_degrade",
-                          [&] { return launch_degrade(src_d, !src_u8, dst_d, !dst_u8, B, D, Nx, Ny, blur, sigma, impulse, seed, first_frame, ctx->cur); });
-}
-
-// the source bytes one image's conversion reads: the luma samples and, unless the order is GRAY, the chroma samples (YUYV: the rows whole)
-static double yuv_bytes(const aefft_yuv_desc& s, int order)
-{
-    const double W = s.W, H = s.H, Wc = (s.W + 1) / 2, Hc = (s.H + 1) / 2;
-    if (s.format == AEFFT_YUV_YUYV) return 2.0 * W * H;
-    return W * H + (order == AEFFT_YUV_GRAY ? 0.0 : 2.0 * Wc * Hc);
-}
-// the source rules aefft_yuv_to_image and aefft_yuv_resize_to_frames share (include/aefft.h "image boundary"): `used` receives the planes the call
-// reads and `extent[k]` the bytes of plane k over the B images, first byte to last
-template <class Bad>
-static int chk_yuv_source(const Bad& bad, const aefft_yuv_desc* src, int order, int B, int* used, size_t* extent)
-{
-    const auto in = [](int v) { return v >= 1 && v <= 8192; };
-    if (src->format != AEFFT_YUV_NV12 && src->format != AEFFT_YUV_I420 && src->format != AEFFT_YUV_YUYV) return bad("format must be AEFFT_YUV_NV12, AEFFT_YUV_I420 or AEFFT_YUV_YUYV");
-    if (src->matrix != AEFFT_YUV_BT601 && src->matrix != AEFFT_YUV_BT709 && src->matrix != AEFFT_YUV_JPEG) return bad("matrix must be AEFFT_YUV_BT601, AEFFT_YUV_BT709 or AEFFT_YUV_JPEG");
-    if (order != AEFFT_YUV_BGR && order != AEFFT_YUV_RGB && order != AEFFT_YUV_GRAY) return bad("order must be AEFFT_YUV_BGR, AEFFT_YUV_RGB or AEFFT_YUV_GRAY");
-    if (B < 1 || !in(src->W) || !in(src->H)) return bad("B must be >= 1 and W, H in 1..8192");
-    const bool yuyv = src->format == AEFFT_YUV_YUYV;
-    if (yuyv && (src->W & 1)) return bad("YUYV needs an even W");
-    const size_t W = (size_t)src->W, H = (size_t)src->H, Wc = (W + 1) / 2, Hc = (H + 1) / 2;
-    // live bytes of a row and rows of each plane
-    const size_t live[3] = {yuyv ? 2 * W : W, src->format == AEFFT_YUV_NV12 ? 2 * Wc : Wc, Wc}, rows[3] = {H, Hc, Hc};
-    *used = order == AEFFT_YUV_GRAY || yuyv ? 1 : (src->format == AEFFT_YUV_NV12 ? 2 : 3);
-    const size_t half = ~size_t(0) >> 1;
-    for (int k = 0; k < *used; ++k) {
-        if (!src->plane[k]) return bad("null plane (NV12 needs plane[0..1], I420 plane[0..2], YUYV and AEFFT_YUV_GRAY plane[0])");
-        if (src->pitch[k] < live[k]) return bad("pitch too small: pitch[0] >= W (YUYV 2 W), NV12 pitch[1] >= 2 ceil(W / 2), I420 pitch[1], pitch[2] >= ceil(W / 2)");
-        if (src->pitch[k] > half / rows[k]) return bad("rows * pitch does not fit the address space");
-        const size_t one = (rows[k] - 1) * src->pitch[k] + live[k];
-        if (B > 1 && src->stride[k] < one) return bad("stride too small: each used stride[k] must be at least (rows - 1) * pitch[k] + the live bytes of a row for B > 1");
-        if (B > 1 && src->stride[k] > (half - one) / (size_t)(B - 1)) return bad("B * stride does not fit the address space");
-        extent[k] = (B > 1 ? (size_t)(B - 1) * src->stride[k] : 0) + one;
-    }
-    return AEFFT_OK;
-}
-
-extern "C" int aefft_yuv_to_image(aefft_ctx* ctx, const aefft_yuv_desc* src, int order, unsigned char* image_d, size_t pitch, size_t image_stride, int B)
-{
-    const auto bad = [&](const char* rule) { return fail(ctx, AEFFT_EINVAL, (std::string("aefft_yuv_to_image: ") + rule).c_str()); };
-    if (!ctx || !src || !image_d) return bad("null context, descriptor or image");
-    int used = 0;
-    size_t sext[3] = {0, 0, 0}, extent = 0;
-    RET_IF(chk_yuv_source(bad, src, order, B, &used, sext));
-    const int D = order == AEFFT_YUV_GRAY ? 1 : 3;
-    RET_IF(chk_present_image(bad, pitch, image_stride, src->W, src->H, B, D, &extent));
-    for (int k = 0; k < used; ++k)
-        if (ranges_overlap(src->plane[k], sext[k], image_d, extent)) return bad("a source plane and the image range overlap (the op is out-of-place)");
-    RET_IF(join_recon(ctx));                          // (a plane may be a buffer the side stream is still writing)
-    return launch_or_fail(ctx, KID_IMAGE, (double)B * (yuv_bytes(*src, order) + (double)D * src->W * src->H), "yuv_to_image", [&] {
-        return launch_yuv_image(src->format, src->plane, src->pitch, src->stride, src->W, src->H, src->matrix, order, image_d, pitch, image_stride, B, ctx->cur);
-    });
-}
-
-extern "C" int aefft_yuv_resize_to_frames(aefft_ctx* ctx, const aefft_yuv_desc* src, int order, int mode, void* frames_d, int frames_u8, int B, int Nx, int Ny)
-{
-    const auto bad = [&](const char* rule) { return fail(ctx, AEFFT_EINVAL, (std::string("aefft_yuv_resize_to_frames: ") + rule).c_str()); };
-    if (!ctx || !src || !frames_d) return bad("null context, descriptor or frames");
-    int used = 0;
-    size_t sext[3] = {0, 0, 0};
-    RET_IF(chk_yuv_source(bad, src, order, B, &used, sext));
-    if (Nx < 1 || Ny < 1 || Nx > 8192 || Ny > 8192) return bad("Nx, Ny must be in 1..8192");
-    if (mode != AEFFT_RESIZE_LINEAR && mode != AEFFT_RESIZE_AREA) return bad("mode must be AEFFT_RESIZE_LINEAR or AEFFT_RESIZE_AREA");
-    if (mode == AEFFT_RESIZE_AREA && (Nx > src->W || Ny > src->H)) return bad("AEFFT_RESIZE_AREA does not enlarge: it needs Nx <= W and Ny <= H");
-    if (!aligned16(frames_d)) return bad("frames_d must be 16-byte aligned");
-    const int D = order == AEFFT_YUV_GRAY ? 1 : 3;
-    const size_t per = (size_t)D * Nx * Ny * (frames_u8 ? 1 : 4);              // (at most 2^30 bytes of one image's frames)
-    if ((size_t)B > (~size_t(0) >> 1) / per) return bad("B * D * Nx * Ny does not fit the address space");
-    for (int k = 0; k < used; ++k)
-        if (ranges_overlap(src->plane[k], sext[k], frames_d, (size_t)B * per)) return bad("a source plane and the frame range overlap (the op is out-of-place)");
-    RET_IF(join_recon(ctx));                          // (frames_d may be a buffer a deferred reconstruction is still writing)
-    return launch_or_fail(ctx, KID_IMAGE, (double)B * (yuv_bytes(*src, order) + (double)per), "yuv_resize", [&] {
-        return launch_yuv_resize(src->format, src->plane, src->pitch, src->stride, src->W, src->H, src->matrix, order, mode, frames_d, !frames_u8, B, Nx, Ny, ctx->cur);
-    });
-}
-
-// tiled inference (include/aefft.h "tiled inference"): the plan is host arithmetic only
-extern "C" int aefft_tile_plan_make(const aefft_tile_desc* desc, aefft_tile_plan* plan) { return tile_plan(desc, plan) ? AEFFT_OK : AEFFT_EINVAL; }
-
-// the rules aefft_image_tiles_to_frames and aefft_frames_tiles_to_image share; `frame_bytes` receives the bytes of the T tile frames
-template <class Bad>
-static int chk_tiles(const Bad& bad, aefft_ctx* ctx, const void* image_d, size_t pitch, size_t image_stride, const aefft_tile_desc* desc, const void* frames_d,
-                     int frames_u8, int B, int D, size_t* frame_bytes)
-{
-    if (!ctx || !image_d || !frames_d || !desc) return bad("null context, image, frames or description");
-    aefft_tile_plan plan;
-    if (!tile_plan(desc, &plan))
-        return bad("the description is not one aefft_tile_plan_make takes (W, H in 1..8192; Nx, Ny in 2..2048; 0 <= 2 overlap <= N; 0 <= 2 rim <= overlap)");
-    size_t extent = 0;
-    RET_IF(chk_present_image(bad, pitch, image_stride, desc->W, desc->H, B, D, &extent));
-    if (!aligned16(frames_d)) return bad("frames_d must be 16-byte aligned");
-    const size_t tiles = (size_t)plan.ntx * plan.nty;                            // (at most 2^26 of an image)
-    if ((size_t)B > (size_t)INT_MAX / tiles) return bad("B * ntx * nty tiles do not fit an int");
-    const size_t per = (size_t)D * desc->Nx * desc->Ny * (frames_u8 ? 1 : 4);    // (at most 2^26 bytes of a tile)
-    if ((size_t)B * tiles > (~size_t(0) >> 1) / per) return bad("T * D * Nx * Ny does not fit the address space");
-    *frame_bytes = (size_t)B * tiles * per;
-    if (ranges_overlap(frames_d, *frame_bytes, image_d, extent)) return bad("the frame and image ranges overlap (the op is out-of-place)");
-    return AEFFT_OK;
-}
-
-extern "C" int aefft_image_tiles_to_frames(aefft_ctx* ctx, const unsigned char* image_d, size_t pitch, size_t image_stride, const aefft_tile_desc* desc,
-                                           void* frames_d, int frames_u8, int B, int D)
-{
-    const auto bad = [&](const char* rule) { return fail(ctx, AEFFT_EINVAL, (std::string("aefft_image_tiles_to_frames: ") + rule).c_str()); };
-    size_t fb = 0;
-    RET_IF(chk_tiles(bad, ctx, image_d, pitch, image_stride, desc, frames_d, frames_u8, B, D, &fb));
-    RET_IF(join_recon(ctx));                          // (frames_d may be a buffer a deferred reconstruction is still writing)
-    return launch_or_fail(ctx, KID_IMAGE, (double)B * D * desc->W * desc->H + (double)fb, "tile_gather",
-                          [&] { return launch_tile_gather(image_d, pitch, image_stride, desc, frames_d, !frames_u8, B, D, ctx->cur); });
-}
-
-extern "C" int aefft_frames_tiles_to_image(aefft_ctx* ctx, const void* frames_d, int frames_u8, const aefft_tile_desc* desc, unsigned char* image_d,
-                                           size_t pitch, size_t image_stride, int B, int D)
-{
-    const auto bad = [&](const char* rule) { return fail(ctx, AEFFT_EINVAL, (std::string("aefft_frames_tiles_to_image: ") + rule).c_str()); };
-    size_t fb = 0;
-    RET_IF(chk_tiles(bad, ctx, image_d, pitch, image_stride, desc, frames_d, frames_u8, B, D, &fb));
-    RET_IF(join_recon(ctx));                          // (frames_d may be the reconstruction of a step whose inverse transform is still on the side stream)
-    return launch_or_fail(ctx, KID_IMAGE, (double)B * D * desc->W * desc->H + (double)fb, "tile_blend",
-                          [&] { return launch_tile_blend(frames_d, !frames_u8, desc, image_d, pitch, image_stride, B, D, ctx->cur); });
 }

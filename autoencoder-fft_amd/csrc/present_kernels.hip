@@ -27,10 +27,10 @@
 //   4. frames_resize: the tile image leaves with the accesses that are contiguous on the image side: a lane per dword when image_d, pitch and
 //      image_stride are multiples of 4 (the dword that crosses the row's end W D split into its live bytes), a lane per byte otherwise.
 // No scratch, no atomics, no workspace.  The kernel bodies are plain C++ over (threadIdx, blockIdx, gridDim, __syncthreads) and an LDS pointer:
-// tools/present_hostcheck.cpp compiles this file for the host, threads as lanes, under the sanitizers (AEFFT_PRESENT_HOSTCHECK: it supplies
+// tools/present_hostcheck.cpp compiles this file for the host, threads as lanes, under the sanitizers (AEFFT_HOSTCHECK: tools/hostlanes.h supplies
 // those names and px_u8, and leaves the launchers out).
 #include <type_traits>
-#ifndef AEFFT_PRESENT_HOSTCHECK
+#ifndef AEFFT_HOSTCHECK
 #include "internal.h"
 #include "fft_common.h"
 #define RZ_HD __host__ __device__ __forceinline__
@@ -317,7 +317,7 @@ static inline OvArgs ov_geometry(const float* map, int Mx, int My, float lo, flo
     return g;
 }
 
-#ifndef AEFFT_PRESENT_HOSTCHECK
+#ifndef AEFFT_HOSTCHECK
 template <int D, bool F32, int MODE>
 __global__ __launch_bounds__(256) void frames_resize_kernel(const FrArgs a)
 {

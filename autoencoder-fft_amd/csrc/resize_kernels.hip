@@ -17,9 +17,9 @@
 // ascending run of at most 32 r bytes (r = W / Nx), so the dwords they touch are consecutive and on different banks up to r = 4 whatever the LDS
 // pitch (section 20 has the argument and what happens beyond).  No scratch, no atomics, no global byte gather on the aligned route.
 // The kernel body is plain C++ over (threadIdx, blockIdx, gridDim, __syncthreads) and an LDS pointer: tools/resize_hostcheck.cpp compiles this
-// file for the host, threads as lanes, under the sanitizers (AEFFT_RESIZE_HOSTCHECK: it supplies those names and leaves the launcher out).
+// file for the host, threads as lanes, under the sanitizers (AEFFT_HOSTCHECK: tools/hostlanes.h supplies those names and leaves the launcher out).
 #include <type_traits>
-#ifndef AEFFT_RESIZE_HOSTCHECK
+#ifndef AEFFT_HOSTCHECK
 #include "internal.h"
 #define RZ_HD __host__ __device__ __forceinline__
 #define RZ_UNIFORM(x) __builtin_amdgcn_readfirstlane(x)
@@ -223,7 +223,7 @@ static inline RzArgs rz_geometry(const unsigned char* image, size_t pitch, size_
     return g;
 }
 
-#ifndef AEFFT_RESIZE_HOSTCHECK
+#ifndef AEFFT_HOSTCHECK
 template <int D, bool F32, int MODE>
 __global__ __launch_bounds__(256) void resize_kernel(const RzArgs a)
 {

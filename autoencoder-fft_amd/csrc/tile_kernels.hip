@@ -24,9 +24,9 @@
 // LDS: an LDS row is RWP = 16 D + 1 dwords, four rows form a super-row of SR = 4 RWP + 2 = 64 D + 6 dwords.  The frame side's lanes q = 0..15 of a
 // run read dword g of rows 4 q + k: banks 6 q + g + const (mod 32), and 6 q runs through all 16 even residues, so the 32 lanes of a ds_read_b32 /
 // ds_write_b32 lane group (q = 0..15 x two neighbouring g) are on 32 different banks.  16 SR + 192 map words: 17.2 KiB at D = 4.  No scratch.
-// tools/tiles_hostcheck.cpp compiles this file for the host, threads as lanes, under the sanitizers (AEFFT_TILES_HOSTCHECK: it supplies the
+// tools/tiles_hostcheck.cpp compiles this file for the host, threads as lanes, under the sanitizers (AEFFT_HOSTCHECK: tools/hostlanes.h supplies the
 // launch variables, the barrier, float4 and px_u8).
-#ifndef AEFFT_TILES_HOSTCHECK
+#ifndef AEFFT_HOSTCHECK
 #include "internal.h"
 #include "fft_common.h"
 #define TL_HD __device__ __forceinline__
@@ -362,7 +362,7 @@ static inline bool tl_geometry(const aefft_tile_desc* desc, const unsigned char*
 static inline unsigned tl_grid_y(const TlArgs& g) { return (unsigned)(g.units < 65535 ? g.units : 65535); }   // unit = z grid.y + y (workgroups beyond return at once)
 static inline unsigned tl_grid_z(const TlArgs& g) { return ((unsigned)g.units + tl_grid_y(g) - 1) / tl_grid_y(g); }
 
-#ifndef AEFFT_TILES_HOSTCHECK
+#ifndef AEFFT_HOSTCHECK
 template <int D, bool F32>
 __global__ __launch_bounds__(256) void tile_gather_kernel(const TlArgs a)
 {

@@ -19,9 +19,9 @@
 // The 8-bit value is clamped in Q20 BEFORE the shift and packed with shifts and masks (the other order selected a packed
 // shift-and-saturate instruction whose device bytes were wrong).
 // Plain C++ over (threadIdx, blockIdx, gridDim, __syncthreads) and an LDS pointer: tools/yuv_hostcheck.cpp compiles this file for the host, threads
-// as lanes, under the sanitizers (AEFFT_YUV_HOSTCHECK: it supplies those names and leaves the launchers out).
+// as lanes, under the sanitizers (AEFFT_HOSTCHECK: tools/hostlanes.h supplies those names and leaves the launchers out).
 #include <type_traits>
-#ifndef AEFFT_YUV_HOSTCHECK
+#ifndef AEFFT_HOSTCHECK
 #include "internal.h"
 #define RZ_HD __host__ __device__ __forceinline__
 #define RZ_UNIFORM(x) __builtin_amdgcn_readfirstlane(x)
@@ -411,7 +411,7 @@ static inline YvArgs yv_geometry(const YvSrc& s, int mode, void* frames, int B, 
     return g;
 }
 
-#ifndef AEFFT_YUV_HOSTCHECK
+#ifndef AEFFT_HOSTCHECK
 template <int FMT, int D>
 __global__ __launch_bounds__(256) void yuv_image_kernel(const YiArgs a) { yuv_image_body<FMT, D>(a); }
 

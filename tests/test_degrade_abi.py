@@ -119,10 +119,12 @@ def test_degrade_kernels_use_no_scratch_and_cover_every_instantiation():
     assert "degrade_kernels.hip" in open(os.path.join(CSRC, "Makefile")).read()
     # the launcher is declared with the others, the entry point stands with the image calls and shares their helpers
     assert "hipError_t launch_degrade(" in open(os.path.join(CSRC, "internal.h")).read()
-    ops = open(os.path.join(CSRC, "ops.hip")).read()
+    ops = open(os.path.join(CSRC, "image_ops.hip")).read()
     entry = ops[ops.index('extern "C" int aefft_frames_degrade('):]
     assert ops.index("// image boundary") < ops.index('extern "C" int aefft_map_overlay_image(') < ops.index('extern "C" int aefft_frames_degrade(')
     assert "ranges_overlap(" in entry and "aligned16(" in entry and "KID_IMAGE" in entry and ops.count("static bool ranges_overlap(") == 1
+    rest = open(os.path.join(CSRC, "ops.hip")).read()
+    assert "aefft_image_" not in rest and "KID_IMAGE" not in rest
 
 
 # 5.
@@ -172,6 +174,9 @@ def test_the_host_check_program_is_there_and_stands_alone():
     src = open(path).read()
     assert '#include "../autoencoder-fft_amd/csrc/degrade_kernels.hip"' in src and "int main(" in src and "-fsanitize=address,undefined" in src
     assert "Python.h" not in src and "hip_runtime" not in src
+    lanes = open(os.path.join(ROOT, "tools", "hostlanes.h")).read()
+    assert '#include "hostlanes.h"' in src and "#define AEFFT_HOSTCHECK" in lanes
+    assert "Python.h" not in lanes and "hip_runtime" not in lanes and "LD_PRELOAD" not in lanes
     # the product never imports the restatement
     for dirpath, _, files in os.walk(os.path.join(ROOT, "autoencoder-fft_amd")):
         for f in files:

@@ -251,38 +251,43 @@ def test_argument_errors_leave_the_buffers_untouched(ctx):
     ap, bp = a.data_ptr(), b.data_ptr()
     assert ap % 16 == 0 and bp % 16 == 0
     inf, nan = float("inf"), float("nan")
-    # (src, src_u8, dst, dst_u8, B, D, Nx, Ny, blur, sigma, impulse, seed, first_frame), a word of the message
+    # (src, src_u8, dst, dst_u8, B, D, Nx, Ny, blur, sigma, impulse, seed, first_frame), the whole message behind the call's name
+    # the rules' full texts, as the library words them
+    NULL, DIM, RANGE = "null context, source or destination", "D must be 1..4 (grey, BGR, BGRA)", "B must be >= 1 and Nx, Ny in 1..8192"
+    BLUR, SIGMA, IMPULSE = "blur must be 0..4", "sigma must be finite and in 0..255", "impulse must be finite and in 0..1"
+    ALIGN = "src_d and dst_d must be 16-byte aligned"
+    OVERLAP = "the source and destination ranges overlap (in place needs dst_d == src_d, blur == 0 and src_u8 == dst_u8)"
     cases = [
-        ("null source", (None, 1, bp, 1, B, D, Nx, Ny, 0, 1.0, 0.0, 1, 0), "null"),
-        ("null destination", (ap, 1, None, 1, B, D, Nx, Ny, 0, 1.0, 0.0, 1, 0), "null"),
-        ("D = 0", (ap, 1, bp, 1, B, 0, Nx, Ny, 0, 1.0, 0.0, 1, 0), "D must be"),
-        ("D = 5", (ap, 1, bp, 1, 1, 5, Nx, Ny, 0, 1.0, 0.0, 1, 0), "D must be"),
-        ("B = 0", (ap, 1, bp, 1, 0, D, Nx, Ny, 0, 1.0, 0.0, 1, 0), "1..8192"),
-        ("Nx = 0", (ap, 1, bp, 1, B, D, 0, Ny, 0, 1.0, 0.0, 1, 0), "1..8192"),
-        ("Ny = 8193", (ap, 1, bp, 1, B, D, Nx, 8193, 0, 1.0, 0.0, 1, 0), "1..8192"),
-        ("blur = 5", (ap, 1, bp, 1, B, D, Nx, Ny, 5, 1.0, 0.0, 1, 0), "blur"),
-        ("blur = -1", (ap, 1, bp, 1, B, D, Nx, Ny, -1, 1.0, 0.0, 1, 0), "blur"),
-        ("sigma = -1", (ap, 1, bp, 1, B, D, Nx, Ny, 0, -1.0, 0.0, 1, 0), "sigma"),
-        ("sigma = 255.5", (ap, 1, bp, 1, B, D, Nx, Ny, 0, 255.5, 0.0, 1, 0), "sigma"),
-        ("sigma = nan", (ap, 1, bp, 1, B, D, Nx, Ny, 0, nan, 0.0, 1, 0), "sigma"),
-        ("sigma = inf", (ap, 1, bp, 1, B, D, Nx, Ny, 0, inf, 0.0, 1, 0), "sigma"),
-        ("impulse = -0.5", (ap, 1, bp, 1, B, D, Nx, Ny, 0, 1.0, -0.5, 1, 0), "impulse"),
-        ("impulse = 1.5", (ap, 1, bp, 1, B, D, Nx, Ny, 0, 1.0, 1.5, 1, 0), "impulse"),
-        ("impulse = nan", (ap, 1, bp, 1, B, D, Nx, Ny, 0, 1.0, nan, 1, 0), "impulse"),
-        ("source off by 4", (ap + 4, 0, bp, 1, B, D, Nx, Ny, 0, 1.0, 0.0, 1, 0), "16-byte"),
-        ("destination off by 8", (ap, 1, bp + 8, 0, B, D, Nx, Ny, 0, 1.0, 0.0, 1, 0), "16-byte"),
-        ("in place with a blur", (ap, 1, ap, 1, B, D, Nx, Ny, 1, 1.0, 0.0, 1, 0), "overlap"),
-        ("in place with another type", (ap, 1, ap, 0, B, D, Nx, Ny, 0, 1.0, 0.0, 1, 0), "overlap"),
-        ("in place with another type, float source", (ap, 0, ap, 1, B, D, Nx, Ny, 0, 1.0, 0.0, 1, 0), "overlap"),
-        ("overlap: shifted by 16", (ap, 1, ap + 16, 1, B, D, Nx, Ny, 0, 1.0, 0.0, 1, 0), "overlap"),
-        ("overlap: the destination ends in the source", (ap + n - 16, 1, ap, 1, B, D, Nx, Ny, 0, 1.0, 0.0, 1, 0), "overlap"),
-        ("overlap: the float destination reaches the source", (ap + 4 * n - 16, 1, ap, 0, B, D, Nx, Ny, 2, 1.0, 0.0, 1, 0), "overlap"),
+        ("null source", (None, 1, bp, 1, B, D, Nx, Ny, 0, 1.0, 0.0, 1, 0), NULL),
+        ("null destination", (ap, 1, None, 1, B, D, Nx, Ny, 0, 1.0, 0.0, 1, 0), NULL),
+        ("D = 0", (ap, 1, bp, 1, B, 0, Nx, Ny, 0, 1.0, 0.0, 1, 0), DIM),
+        ("D = 5", (ap, 1, bp, 1, 1, 5, Nx, Ny, 0, 1.0, 0.0, 1, 0), DIM),
+        ("B = 0", (ap, 1, bp, 1, 0, D, Nx, Ny, 0, 1.0, 0.0, 1, 0), RANGE),
+        ("Nx = 0", (ap, 1, bp, 1, B, D, 0, Ny, 0, 1.0, 0.0, 1, 0), RANGE),
+        ("Ny = 8193", (ap, 1, bp, 1, B, D, Nx, 8193, 0, 1.0, 0.0, 1, 0), RANGE),
+        ("blur = 5", (ap, 1, bp, 1, B, D, Nx, Ny, 5, 1.0, 0.0, 1, 0), BLUR),
+        ("blur = -1", (ap, 1, bp, 1, B, D, Nx, Ny, -1, 1.0, 0.0, 1, 0), BLUR),
+        ("sigma = -1", (ap, 1, bp, 1, B, D, Nx, Ny, 0, -1.0, 0.0, 1, 0), SIGMA),
+        ("sigma = 255.5", (ap, 1, bp, 1, B, D, Nx, Ny, 0, 255.5, 0.0, 1, 0), SIGMA),
+        ("sigma = nan", (ap, 1, bp, 1, B, D, Nx, Ny, 0, nan, 0.0, 1, 0), SIGMA),
+        ("sigma = inf", (ap, 1, bp, 1, B, D, Nx, Ny, 0, inf, 0.0, 1, 0), SIGMA),
+        ("impulse = -0.5", (ap, 1, bp, 1, B, D, Nx, Ny, 0, 1.0, -0.5, 1, 0), IMPULSE),
+        ("impulse = 1.5", (ap, 1, bp, 1, B, D, Nx, Ny, 0, 1.0, 1.5, 1, 0), IMPULSE),
+        ("impulse = nan", (ap, 1, bp, 1, B, D, Nx, Ny, 0, 1.0, nan, 1, 0), IMPULSE),
+        ("source off by 4", (ap + 4, 0, bp, 1, B, D, Nx, Ny, 0, 1.0, 0.0, 1, 0), ALIGN),
+        ("destination off by 8", (ap, 1, bp + 8, 0, B, D, Nx, Ny, 0, 1.0, 0.0, 1, 0), ALIGN),
+        ("in place with a blur", (ap, 1, ap, 1, B, D, Nx, Ny, 1, 1.0, 0.0, 1, 0), OVERLAP),
+        ("in place with another type", (ap, 1, ap, 0, B, D, Nx, Ny, 0, 1.0, 0.0, 1, 0), OVERLAP),
+        ("in place with another type, float source", (ap, 0, ap, 1, B, D, Nx, Ny, 0, 1.0, 0.0, 1, 0), OVERLAP),
+        ("overlap: shifted by 16", (ap, 1, ap + 16, 1, B, D, Nx, Ny, 0, 1.0, 0.0, 1, 0), OVERLAP),
+        ("overlap: the destination ends in the source", (ap + n - 16, 1, ap, 1, B, D, Nx, Ny, 0, 1.0, 0.0, 1, 0), OVERLAP),
+        ("overlap: the float destination reaches the source", (ap + 4 * n - 16, 1, ap, 0, B, D, Nx, Ny, 2, 1.0, 0.0, 1, 0), OVERLAP),
     ]
     # (sizes that overflow the address space cannot be reached through int arguments where size_t has 64 bits: B D Nx Ny 4 <= 2^61)
-    for what, args, word in cases:
+    for what, args, rule in cases:
         assert L.aefft_frames_degrade(ctx.h, *args) == aefft.EINVAL, what
         msg = L.aefft_last_error(ctx.h).decode()
-        assert msg.startswith("aefft_frames_degrade: ") and word in msg, (what, msg)
+        assert msg == "aefft_frames_degrade: " + rule, (what, msg)
     ctx.sync()
     assert (host(a) == 0x3C).all() and (host(b) == 0xC3).all()
     # what is NOT an error: the limits of sigma and impulse, neighbouring ranges, the in-place form

@@ -258,20 +258,23 @@ def test_argument_errors_leave_the_outputs_untouched(ctx):
     ip, fp = img.data_ptr(), frm.data_ptr()
     assert fp % 16 == 0
     n_f = B * D * Nx * Ny
+    # the rules' full texts, as the library words them
+    NULL, DIM, RANGE = "null context, image or frames", "D must be 1..4 (grey, BGR, BGRA)", "B must be >= 1 and Nx, Ny in 1..8192"
+    PITCH, ALIGN, OVERLAP = "pitch must be at least Nx * D bytes", "frames_d must be 16-byte aligned", "the frame and image ranges overlap (the op is out-of-place)"
     cases = [
-        ("D = 0", (ip, pitch, fp, 1, B, 0, Nx, Ny)), ("D = 5", (ip, 5 * Nx, fp, 1, B, 5, Nx, Ny)),
-        ("Nx = 0", (ip, pitch, fp, 1, B, D, 0, Ny)), ("Ny = 8193", (ip, pitch, fp, 1, B, D, Nx, 8193)), ("B = 0", (ip, pitch, fp, 1, 0, D, Nx, Ny)),
-        ("pitch = Nx D - 1", (ip, pitch - 1, fp, 1, B, D, Nx, Ny)),
-        ("null image", (None, pitch, fp, 1, B, D, Nx, Ny)), ("null frames", (ip, pitch, None, 1, B, D, Nx, Ny)),
-        ("frames off by 4", (ip, pitch, fp + 4, 0, 1, 1, 2, 2)),
-        ("overlap: frames inside the image", (ip, pitch, ip + 16, 1, B, D, Nx, Ny)),
-        ("overlap: image inside the float frames", (fp + n_f, pitch, fp, 0, 1, D, Nx, Ny)),
+        ("D = 0", (ip, pitch, fp, 1, B, 0, Nx, Ny), DIM), ("D = 5", (ip, 5 * Nx, fp, 1, B, 5, Nx, Ny), DIM),
+        ("Nx = 0", (ip, pitch, fp, 1, B, D, 0, Ny), RANGE), ("Ny = 8193", (ip, pitch, fp, 1, B, D, Nx, 8193), RANGE), ("B = 0", (ip, pitch, fp, 1, 0, D, Nx, Ny), RANGE),
+        ("pitch = Nx D - 1", (ip, pitch - 1, fp, 1, B, D, Nx, Ny), PITCH),
+        ("null image", (None, pitch, fp, 1, B, D, Nx, Ny), NULL), ("null frames", (ip, pitch, None, 1, B, D, Nx, Ny), NULL),
+        ("frames off by 4", (ip, pitch, fp + 4, 0, 1, 1, 2, 2), ALIGN),
+        ("overlap: frames inside the image", (ip, pitch, ip + 16, 1, B, D, Nx, Ny), OVERLAP),
+        ("overlap: image inside the float frames", (fp + n_f, pitch, fp, 0, 1, D, Nx, Ny), OVERLAP),
     ]
-    for what, (i_p, pt, f_p, u8, b, d, nx, ny) in cases:
-        for fn, args in ((L.aefft_image_to_frames, (ctx.h, i_p, pt, f_p, u8, b, d, nx, ny)), (L.aefft_frames_to_image, (ctx.h, f_p, u8, i_p, pt, b, d, nx, ny))):
-            assert fn(*args) == aefft.EINVAL, what
+    for what, (i_p, pt, f_p, u8, b, d, nx, ny), rule in cases:
+        for name, args in (("aefft_image_to_frames", (ctx.h, i_p, pt, f_p, u8, b, d, nx, ny)), ("aefft_frames_to_image", (ctx.h, f_p, u8, i_p, pt, b, d, nx, ny))):
+            assert getattr(L, name)(*args) == aefft.EINVAL, what
             msg = L.aefft_last_error(ctx.h).decode()
-            assert msg.startswith("aefft_") and len(msg) > 30, (what, msg)
+            assert msg == name + ": " + rule, (what, msg)
     ctx.sync()
     assert (host(img) == 0x3C).all() and (host(frm) == 0xC3).all()
     # layouts the C call cannot describe are refused by the binding; a library error surfaces with its message

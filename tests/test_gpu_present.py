@@ -403,69 +403,78 @@ def test_argument_errors_leave_the_buffers_untouched(ctx):
     ip, fp = img.data_ptr(), frm.data_ptr()
     assert fp % 16 == 0
     LIN, AREA = 0, 1
-    # (frames, u8, Nx, Ny, mode, image, pitch, stride, W, H, B, D), a word of the message
+    # (frames, u8, Nx, Ny, mode, image, pitch, stride, W, H, B, D), the whole message behind the call's name
+    # the rules' full texts, as the library words them
+    NULL, DIM, RANGE, FRANGE = "null context, image or frames", "D must be 1..4 (grey, BGR, BGRA)", "B must be >= 1 and W, H in 1..8192", "Nx, Ny must be in 1..8192"
+    MODE, AREA_RULE = "mode must be AEFFT_RESIZE_LINEAR or AEFFT_RESIZE_AREA", "AEFFT_RESIZE_AREA does not enlarge: it needs W <= Nx and H <= Ny"
+    PITCH, STRIDE = "pitch must be at least W * D bytes", "image_stride must be at least (H - 1) * pitch + W * D bytes for B > 1"
+    ROWS_FIT, BATCH_FIT = "H * pitch does not fit the address space", "B * image_stride does not fit the address space"
+    ALIGN, OVERLAP = "frames_d must be 16-byte aligned", "the frame and image ranges overlap (the op is out-of-place)"
     cases = [
-        ("null image", (fp, 1, Nx, Ny, LIN, None, pitch, stride, W, H, B, D), "null"),
-        ("null frames", (None, 1, Nx, Ny, LIN, ip, pitch, stride, W, H, B, D), "null"),
-        ("D = 0", (fp, 1, Nx, Ny, LIN, ip, pitch, stride, W, H, B, 0), "D must be"),
-        ("D = 5", (fp, 1, Nx, Ny, LIN, ip, 5 * W, 5 * W * H, W, H, B, 5), "D must be"),
-        ("B = 0", (fp, 1, Nx, Ny, LIN, ip, pitch, stride, W, H, 0, D), "1..8192"),
-        ("W = 0", (fp, 1, Nx, Ny, LIN, ip, pitch, stride, 0, H, B, D), "1..8192"),
-        ("H = 8193", (fp, 1, Nx, Ny, LIN, ip, pitch, stride, W, 8193, 1, D), "1..8192"),
-        ("Nx = 0", (fp, 1, 0, Ny, LIN, ip, pitch, stride, W, H, B, D), "1..8192"),
-        ("Ny = 8193", (fp, 1, Nx, 8193, LIN, ip, pitch, stride, W, H, B, D), "1..8192"),
-        ("mode = 2", (fp, 1, Nx, Ny, 2, ip, pitch, stride, W, H, B, D), "mode"),
-        ("mode = -1", (fp, 1, Nx, Ny, -1, ip, pitch, stride, W, H, B, D), "mode"),
-        ("AREA enlarging x", (fp, 1, Nx, Ny, AREA, ip, pitch, stride, Nx + 1, Ny, B, D), "AEFFT_RESIZE_AREA"),
-        ("AREA enlarging y", (fp, 1, Nx, Ny, AREA, ip, Nx * D, (Ny + 1) * Nx * D, Nx, Ny + 1, B, D), "AEFFT_RESIZE_AREA"),
-        ("pitch = W D - 1", (fp, 1, Nx, Ny, LIN, ip, pitch - 1, stride, W, H, B, D), "pitch"),
-        ("stride too small", (fp, 1, Nx, Ny, LIN, ip, pitch, (H - 1) * pitch + W * D - 1, W, H, B, D), "image_stride"),
-        ("stride = 0", (fp, 1, Nx, Ny, LIN, ip, pitch, 0, W, H, B, D), "image_stride"),
-        ("pitch overflows", (fp, 1, Nx, Ny, LIN, ip, 2 ** 62, stride, W, H, 1, D), "address space"),
-        ("stride overflows", (fp, 1, Nx, Ny, LIN, ip, pitch, 2 ** 62, W, H, 3, D), "address space"),
-        ("frames off by 4", (fp + 4, 0, Nx, Ny, LIN, ip, pitch, stride, W, H, B, D), "16-byte"),
-        ("overlap: frames inside the image", (ip + 16, 1, Nx, Ny, LIN, ip, pitch, stride, W, H, B, D), "overlap"),
-        ("overlap: image inside the float frames", (fp, 0, Nx, Ny, LIN, fp + 64, pitch, stride, W, H, B, D), "overlap"),
-        ("overlap: the second image only", (fp, 0, Nx, Ny, LIN, fp + 4 * B * D * Nx * Ny - stride - 32, pitch, stride, W, H, B, D), "overlap"),
+        ("null image", (fp, 1, Nx, Ny, LIN, None, pitch, stride, W, H, B, D), NULL),
+        ("null frames", (None, 1, Nx, Ny, LIN, ip, pitch, stride, W, H, B, D), NULL),
+        ("D = 0", (fp, 1, Nx, Ny, LIN, ip, pitch, stride, W, H, B, 0), DIM),
+        ("D = 5", (fp, 1, Nx, Ny, LIN, ip, 5 * W, 5 * W * H, W, H, B, 5), DIM),
+        ("B = 0", (fp, 1, Nx, Ny, LIN, ip, pitch, stride, W, H, 0, D), RANGE),
+        ("W = 0", (fp, 1, Nx, Ny, LIN, ip, pitch, stride, 0, H, B, D), RANGE),
+        ("H = 8193", (fp, 1, Nx, Ny, LIN, ip, pitch, stride, W, 8193, 1, D), RANGE),
+        ("Nx = 0", (fp, 1, 0, Ny, LIN, ip, pitch, stride, W, H, B, D), FRANGE),
+        ("Ny = 8193", (fp, 1, Nx, 8193, LIN, ip, pitch, stride, W, H, B, D), FRANGE),
+        ("mode = 2", (fp, 1, Nx, Ny, 2, ip, pitch, stride, W, H, B, D), MODE),
+        ("mode = -1", (fp, 1, Nx, Ny, -1, ip, pitch, stride, W, H, B, D), MODE),
+        ("AREA enlarging x", (fp, 1, Nx, Ny, AREA, ip, pitch, stride, Nx + 1, Ny, B, D), AREA_RULE),
+        ("AREA enlarging y", (fp, 1, Nx, Ny, AREA, ip, Nx * D, (Ny + 1) * Nx * D, Nx, Ny + 1, B, D), AREA_RULE),
+        ("pitch = W D - 1", (fp, 1, Nx, Ny, LIN, ip, pitch - 1, stride, W, H, B, D), PITCH),
+        ("stride too small", (fp, 1, Nx, Ny, LIN, ip, pitch, (H - 1) * pitch + W * D - 1, W, H, B, D), STRIDE),
+        ("stride = 0", (fp, 1, Nx, Ny, LIN, ip, pitch, 0, W, H, B, D), STRIDE),
+        ("pitch overflows", (fp, 1, Nx, Ny, LIN, ip, 2 ** 62, stride, W, H, 1, D), ROWS_FIT),
+        ("stride overflows", (fp, 1, Nx, Ny, LIN, ip, pitch, 2 ** 62, W, H, 3, D), BATCH_FIT),
+        ("frames off by 4", (fp + 4, 0, Nx, Ny, LIN, ip, pitch, stride, W, H, B, D), ALIGN),
+        ("overlap: frames inside the image", (ip + 16, 1, Nx, Ny, LIN, ip, pitch, stride, W, H, B, D), OVERLAP),
+        ("overlap: image inside the float frames", (fp, 0, Nx, Ny, LIN, fp + 64, pitch, stride, W, H, B, D), OVERLAP),
+        ("overlap: the second image only", (fp, 0, Nx, Ny, LIN, fp + 4 * B * D * Nx * Ny - stride - 32, pitch, stride, W, H, B, D), OVERLAP),
     ]
-    for what, args, word in cases:
+    for what, args, rule in cases:
         assert L.aefft_frames_resize_to_image(ctx.h, *args) == aefft.EINVAL, what
         msg = L.aefft_last_error(ctx.h).decode()
-        assert msg.startswith("aefft_frames_resize_to_image: ") and word in msg, (what, msg)
+        assert msg == "aefft_frames_resize_to_image: " + rule, (what, msg)
     mp = torch.full((1024,), 0x40, dtype=torch.uint8, device=dev)                    # floats 3.0039...: a map in its first 128 bytes
     lt = torch.full((256 * D + 64,), 0x77, dtype=torch.uint8, device=dev)
     m, l = mp.data_ptr(), lt.data_ptr()
     assert m % 16 == 0
     inf, nan = float("inf"), float("nan")
     # (map, Mx, My, lo, hi, smooth, lut, alpha, image, pitch, stride, W, H, B, D)
+    NULL, MRANGE, ALPHA = "null context, map, lut or image", "Mx, My must be in 1..1024", "alpha must be 0..256"
+    LOHI, ALIGN = "lo and hi must be finite and different (255 / (hi - lo) finite)", "map_d must be 16-byte aligned"
+    MAP_OVERLAP, LUT_OVERLAP = "the map and image ranges overlap", "the lut and image ranges overlap"
     cases = [
-        ("null map", (None, 4, 4, 0.0, 1.0, 1, l, 128, ip, pitch, stride, W, H, B, D), "null"),
-        ("null lut", (m, 4, 4, 0.0, 1.0, 1, None, 128, ip, pitch, stride, W, H, B, D), "null"),
-        ("null image", (m, 4, 4, 0.0, 1.0, 1, l, 128, None, pitch, stride, W, H, B, D), "null"),
-        ("Mx = 0", (m, 0, 4, 0.0, 1.0, 1, l, 128, ip, pitch, stride, W, H, B, D), "1..1024"),
-        ("My = 1025", (m, 4, 1025, 0.0, 1.0, 1, l, 128, ip, pitch, stride, W, H, 1, D), "1..1024"),
-        ("D = 5", (m, 4, 4, 0.0, 1.0, 1, l, 128, ip, 5 * W, 5 * W * H, W, H, B, 5), "D must be"),
-        ("B = 0", (m, 4, 4, 0.0, 1.0, 1, l, 128, ip, pitch, stride, W, H, 0, D), "1..8192"),
-        ("W = 8193", (m, 4, 4, 0.0, 1.0, 1, l, 128, ip, 8193 * D, stride, 8193, H, 1, D), "1..8192"),
-        ("H = 0", (m, 4, 4, 0.0, 1.0, 1, l, 128, ip, pitch, stride, W, 0, B, D), "1..8192"),
-        ("alpha = 257", (m, 4, 4, 0.0, 1.0, 1, l, 257, ip, pitch, stride, W, H, B, D), "alpha"),
-        ("alpha = -1", (m, 4, 4, 0.0, 1.0, 1, l, -1, ip, pitch, stride, W, H, B, D), "alpha"),
-        ("lo == hi", (m, 4, 4, 2.0, 2.0, 1, l, 128, ip, pitch, stride, W, H, B, D), "lo and hi"),
-        ("lo = nan", (m, 4, 4, nan, 1.0, 1, l, 128, ip, pitch, stride, W, H, B, D), "lo and hi"),
-        ("hi = inf", (m, 4, 4, 0.0, inf, 1, l, 128, ip, pitch, stride, W, H, B, D), "lo and hi"),
-        ("hi = -inf", (m, 4, 4, 0.0, -inf, 1, l, 128, ip, pitch, stride, W, H, B, D), "lo and hi"),
-        ("map off by 4", (m + 4, 4, 4, 0.0, 1.0, 1, l, 128, ip, pitch, stride, W, H, B, D), "16-byte"),
-        ("pitch = W D - 1", (m, 4, 4, 0.0, 1.0, 1, l, 128, ip, pitch - 1, stride, W, H, B, D), "pitch"),
-        ("stride too small", (m, 4, 4, 0.0, 1.0, 1, l, 128, ip, pitch, (H - 1) * pitch + W * D - 1, W, H, B, D), "image_stride"),
-        ("overlap: the map inside the image", (ip + 16, 4, 4, 0.0, 1.0, 1, l, 128, ip, pitch, stride, W, H, B, D), "overlap"),
-        ("overlap: the image inside the map", (m, 4, 4, 0.0, 1.0, 1, l, 128, m + 4 * B * 16 - 8, pitch, stride, W, H, B, D), "overlap"),
-        ("overlap: the table inside the image", (m, 4, 4, 0.0, 1.0, 1, ip + stride + 5, 128, ip, pitch, stride, W, H, B, D), "overlap"),
-        ("overlap: the image begins in the table", (m, 4, 4, 0.0, 1.0, 1, l, 128, l + 256 * D - 1, pitch, stride, W, H, B, D), "overlap"),
+        ("null map", (None, 4, 4, 0.0, 1.0, 1, l, 128, ip, pitch, stride, W, H, B, D), NULL),
+        ("null lut", (m, 4, 4, 0.0, 1.0, 1, None, 128, ip, pitch, stride, W, H, B, D), NULL),
+        ("null image", (m, 4, 4, 0.0, 1.0, 1, l, 128, None, pitch, stride, W, H, B, D), NULL),
+        ("Mx = 0", (m, 0, 4, 0.0, 1.0, 1, l, 128, ip, pitch, stride, W, H, B, D), MRANGE),
+        ("My = 1025", (m, 4, 1025, 0.0, 1.0, 1, l, 128, ip, pitch, stride, W, H, 1, D), MRANGE),
+        ("D = 5", (m, 4, 4, 0.0, 1.0, 1, l, 128, ip, 5 * W, 5 * W * H, W, H, B, 5), DIM),
+        ("B = 0", (m, 4, 4, 0.0, 1.0, 1, l, 128, ip, pitch, stride, W, H, 0, D), RANGE),
+        ("W = 8193", (m, 4, 4, 0.0, 1.0, 1, l, 128, ip, 8193 * D, stride, 8193, H, 1, D), RANGE),
+        ("H = 0", (m, 4, 4, 0.0, 1.0, 1, l, 128, ip, pitch, stride, W, 0, B, D), RANGE),
+        ("alpha = 257", (m, 4, 4, 0.0, 1.0, 1, l, 257, ip, pitch, stride, W, H, B, D), ALPHA),
+        ("alpha = -1", (m, 4, 4, 0.0, 1.0, 1, l, -1, ip, pitch, stride, W, H, B, D), ALPHA),
+        ("lo == hi", (m, 4, 4, 2.0, 2.0, 1, l, 128, ip, pitch, stride, W, H, B, D), LOHI),
+        ("lo = nan", (m, 4, 4, nan, 1.0, 1, l, 128, ip, pitch, stride, W, H, B, D), LOHI),
+        ("hi = inf", (m, 4, 4, 0.0, inf, 1, l, 128, ip, pitch, stride, W, H, B, D), LOHI),
+        ("hi = -inf", (m, 4, 4, 0.0, -inf, 1, l, 128, ip, pitch, stride, W, H, B, D), LOHI),
+        ("map off by 4", (m + 4, 4, 4, 0.0, 1.0, 1, l, 128, ip, pitch, stride, W, H, B, D), ALIGN),
+        ("pitch = W D - 1", (m, 4, 4, 0.0, 1.0, 1, l, 128, ip, pitch - 1, stride, W, H, B, D), PITCH),
+        ("stride too small", (m, 4, 4, 0.0, 1.0, 1, l, 128, ip, pitch, (H - 1) * pitch + W * D - 1, W, H, B, D), STRIDE),
+        ("overlap: the map inside the image", (ip + 16, 4, 4, 0.0, 1.0, 1, l, 128, ip, pitch, stride, W, H, B, D), MAP_OVERLAP),
+        ("overlap: the image inside the map", (m, 4, 4, 0.0, 1.0, 1, l, 128, m + 4 * B * 16 - 8, pitch, stride, W, H, B, D), MAP_OVERLAP),
+        ("overlap: the table inside the image", (m, 4, 4, 0.0, 1.0, 1, ip + stride + 5, 128, ip, pitch, stride, W, H, B, D), LUT_OVERLAP),
+        ("overlap: the image begins in the table", (m, 4, 4, 0.0, 1.0, 1, l, 128, l + 256 * D - 1, pitch, stride, W, H, B, D), LUT_OVERLAP),
     ]
-    for what, args, word in cases:
+    for what, args, rule in cases:
         assert L.aefft_map_overlay_image(ctx.h, *args) == aefft.EINVAL, what
         msg = L.aefft_last_error(ctx.h).decode()
-        assert msg.startswith("aefft_map_overlay_image: ") and word in msg, (what, msg)
+        assert msg == "aefft_map_overlay_image: " + rule, (what, msg)
     ctx.sync()
     assert (host(img) == 0x3C).all() and (host(frm) == 0xC3).all() and (host(mp) == 0x40).all() and (host(lt) == 0x77).all()
     # what is NOT an error: a stride of any value for one image; the smallest legal stride (a constant source: every pixel 0xC3)

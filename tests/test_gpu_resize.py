@@ -292,33 +292,38 @@ def test_argument_errors_leave_the_outputs_untouched(ctx):
     ip, fp = img.data_ptr(), frm.data_ptr()
     assert fp % 16 == 0
     LIN, AREA = 0, 1
-    # (image, pitch, stride, W, H, mode, frames, u8, B, D, Nx, Ny), a word of the message
+    # the rules' full texts, as the library words them
+    NULL, DIM, RANGE = "null context, image or frames", "D must be 1..4 (grey, BGR, BGRA)", "B must be >= 1 and W, H, Nx, Ny in 1..8192"
+    MODE, AREA_RULE = "mode must be AEFFT_RESIZE_LINEAR or AEFFT_RESIZE_AREA", "AEFFT_RESIZE_AREA does not enlarge: it needs Nx <= W and Ny <= H"
+    PITCH, STRIDE = "pitch must be at least W * D bytes", "image_stride must be at least (H - 1) * pitch + W * D bytes for B > 1"
+    ALIGN, OVERLAP = "frames_d must be 16-byte aligned", "the frame and image ranges overlap (the op is out-of-place)"
+    # (image, pitch, stride, W, H, mode, frames, u8, B, D, Nx, Ny), the whole message behind the call's name
     cases = [
-        ("null image", (None, pitch, stride, W, H, LIN, fp, 1, B, D, Nx, Ny), "null"),
-        ("null frames", (ip, pitch, stride, W, H, LIN, None, 1, B, D, Nx, Ny), "null"),
-        ("D = 0", (ip, pitch, stride, W, H, LIN, fp, 1, B, 0, Nx, Ny), "D must be"),
-        ("D = 5", (ip, 5 * W, 5 * W * H, W, H, LIN, fp, 1, B, 5, Nx, Ny), "D must be"),
-        ("B = 0", (ip, pitch, stride, W, H, LIN, fp, 1, 0, D, Nx, Ny), "1..8192"),
-        ("W = 0", (ip, pitch, stride, 0, H, LIN, fp, 1, B, D, Nx, Ny), "1..8192"),
-        ("H = 8193", (ip, pitch, stride, W, 8193, LIN, fp, 1, 1, D, Nx, Ny), "1..8192"),
-        ("Nx = 0", (ip, pitch, stride, W, H, LIN, fp, 1, B, D, 0, Ny), "1..8192"),
-        ("Ny = 8193", (ip, pitch, stride, W, H, LIN, fp, 1, B, D, Nx, 8193), "1..8192"),
-        ("mode = 2", (ip, pitch, stride, W, H, 2, fp, 1, B, D, Nx, Ny), "mode"),
-        ("mode = -1", (ip, pitch, stride, W, H, -1, fp, 1, B, D, Nx, Ny), "mode"),
-        ("AREA enlarging x", (ip, pitch, stride, W, H, AREA, fp, 1, B, D, W + 1, Ny), "AEFFT_RESIZE_AREA"),
-        ("AREA enlarging y", (ip, pitch, stride, W, H, AREA, fp, 1, B, D, Nx, H + 1), "AEFFT_RESIZE_AREA"),
-        ("pitch = W D - 1", (ip, pitch - 1, stride, W, H, LIN, fp, 1, B, D, Nx, Ny), "pitch"),
-        ("stride too small", (ip, pitch, (H - 1) * pitch + W * D - 1, W, H, LIN, fp, 1, B, D, Nx, Ny), "image_stride"),
-        ("stride = 0", (ip, pitch, 0, W, H, LIN, fp, 1, B, D, Nx, Ny), "image_stride"),
-        ("frames off by 4", (ip, pitch, stride, W, H, LIN, fp + 4, 0, B, D, Nx, Ny), "16-byte"),
-        ("overlap: frames inside the image", (ip, pitch, stride, W, H, LIN, ip + 16, 1, B, D, Nx, Ny), "overlap"),
-        ("overlap: image inside the float frames", (fp + 64, pitch, stride, W, H, LIN, fp, 0, B, D, Nx, Ny), "overlap"),
-        ("overlap: the second image only", (fp + 4 * B * D * Nx * Ny - stride - 32, pitch, stride, W, H, LIN, fp, 0, B, D, Nx, Ny), "overlap"),
+        ("null image", (None, pitch, stride, W, H, LIN, fp, 1, B, D, Nx, Ny), NULL),
+        ("null frames", (ip, pitch, stride, W, H, LIN, None, 1, B, D, Nx, Ny), NULL),
+        ("D = 0", (ip, pitch, stride, W, H, LIN, fp, 1, B, 0, Nx, Ny), DIM),
+        ("D = 5", (ip, 5 * W, 5 * W * H, W, H, LIN, fp, 1, B, 5, Nx, Ny), DIM),
+        ("B = 0", (ip, pitch, stride, W, H, LIN, fp, 1, 0, D, Nx, Ny), RANGE),
+        ("W = 0", (ip, pitch, stride, 0, H, LIN, fp, 1, B, D, Nx, Ny), RANGE),
+        ("H = 8193", (ip, pitch, stride, W, 8193, LIN, fp, 1, 1, D, Nx, Ny), RANGE),
+        ("Nx = 0", (ip, pitch, stride, W, H, LIN, fp, 1, B, D, 0, Ny), RANGE),
+        ("Ny = 8193", (ip, pitch, stride, W, H, LIN, fp, 1, B, D, Nx, 8193), RANGE),
+        ("mode = 2", (ip, pitch, stride, W, H, 2, fp, 1, B, D, Nx, Ny), MODE),
+        ("mode = -1", (ip, pitch, stride, W, H, -1, fp, 1, B, D, Nx, Ny), MODE),
+        ("AREA enlarging x", (ip, pitch, stride, W, H, AREA, fp, 1, B, D, W + 1, Ny), AREA_RULE),
+        ("AREA enlarging y", (ip, pitch, stride, W, H, AREA, fp, 1, B, D, Nx, H + 1), AREA_RULE),
+        ("pitch = W D - 1", (ip, pitch - 1, stride, W, H, LIN, fp, 1, B, D, Nx, Ny), PITCH),
+        ("stride too small", (ip, pitch, (H - 1) * pitch + W * D - 1, W, H, LIN, fp, 1, B, D, Nx, Ny), STRIDE),
+        ("stride = 0", (ip, pitch, 0, W, H, LIN, fp, 1, B, D, Nx, Ny), STRIDE),
+        ("frames off by 4", (ip, pitch, stride, W, H, LIN, fp + 4, 0, B, D, Nx, Ny), ALIGN),
+        ("overlap: frames inside the image", (ip, pitch, stride, W, H, LIN, ip + 16, 1, B, D, Nx, Ny), OVERLAP),
+        ("overlap: image inside the float frames", (fp + 64, pitch, stride, W, H, LIN, fp, 0, B, D, Nx, Ny), OVERLAP),
+        ("overlap: the second image only", (fp + 4 * B * D * Nx * Ny - stride - 32, pitch, stride, W, H, LIN, fp, 0, B, D, Nx, Ny), OVERLAP),
     ]
-    for what, args, word in cases:
+    for what, args, rule in cases:
         assert L.aefft_image_resize_to_frames(ctx.h, *args) == aefft.EINVAL, what
         msg = L.aefft_last_error(ctx.h).decode()
-        assert msg.startswith("aefft_image_resize_to_frames: ") and word in msg, (what, msg)
+        assert msg == "aefft_image_resize_to_frames: " + rule, (what, msg)
     # what is NOT an error: a stride of any value for one image; the smallest legal stride
     one = torch.full((D * Nx * Ny,), 0xEE, dtype=torch.uint8, device=dev)
     assert L.aefft_image_resize_to_frames(ctx.h, ip, pitch, 0, W, H, LIN, one.data_ptr(), 1, 1, D, Nx, Ny) == aefft.OK

@@ -236,40 +236,46 @@ def test_argument_errors_leave_the_buffers_untouched(ctx):
     assert ap % 16 == 0 and fp % 16 == 0
     good = aefft.TileDesc(W, H, Nx, Ny, V, V, M, M)
     desc = lambda **kw: aefft.TileDesc(*[kw.get(k, getattr(good, k)) for k, _ in aefft.TileDesc._fields_])
-    # (image, pitch, stride, description, frames, frames_u8, B, D), a word of the message
+    # (image, pitch, stride, description, frames, frames_u8, B, D), the whole message behind the call's name
+    # the rules' full texts, as the library words them
+    NULL, DIM, RANGE = "null context, image, frames or description", "D must be 1..4 (grey, BGR, BGRA)", "B must be >= 1 and W, H in 1..8192"
+    PLAN = "the description is not one aefft_tile_plan_make takes (W, H in 1..8192; Nx, Ny in 2..2048; 0 <= 2 overlap <= N; 0 <= 2 rim <= overlap)"
+    PITCH, STRIDE = "pitch must be at least W * D bytes", "image_stride must be at least (H - 1) * pitch + W * D bytes for B > 1"
+    ROWS_FIT, BATCH_FIT = "H * pitch does not fit the address space", "B * image_stride does not fit the address space"
+    ALIGN, OVERLAP, COUNT = "frames_d must be 16-byte aligned", "the frame and image ranges overlap (the op is out-of-place)", "B * ntx * nty tiles do not fit an int"
     cases = [
-        ("null image", (None, pitch, stride, good, fp, 1, 2, D), "null"),
-        ("null frames", (ap, pitch, stride, good, None, 1, 2, D), "null"),
-        ("null description", (ap, pitch, stride, None, fp, 1, 2, D), "null"),
-        ("W = 0", (ap, pitch, stride, desc(W=0), fp, 1, 2, D), "aefft_tile_plan_make"),
-        ("H = 8193", (ap, pitch, stride, desc(H=8193), fp, 1, 2, D), "aefft_tile_plan_make"),
-        ("Nx = 1", (ap, pitch, stride, desc(Nx=1), fp, 1, 2, D), "aefft_tile_plan_make"),
-        ("Ny = 2049", (ap, pitch, stride, desc(Ny=2049), fp, 1, 2, D), "aefft_tile_plan_make"),
-        ("2 V > N", (ap, pitch, stride, desc(overlap_x=5), fp, 1, 2, D), "aefft_tile_plan_make"),
-        ("V < 0", (ap, pitch, stride, desc(overlap_y=-1), fp, 1, 2, D), "aefft_tile_plan_make"),
-        ("2 M > V", (ap, pitch, stride, desc(rim_x=3), fp, 1, 2, D), "aefft_tile_plan_make"),
-        ("M < 0", (ap, pitch, stride, desc(rim_y=-1), fp, 1, 2, D), "aefft_tile_plan_make"),
-        ("D = 0", (ap, pitch, stride, good, fp, 1, 2, 0), "D must be"),
-        ("D = 5", (ap, 5 * W, 5 * W * H, good, fp, 1, 1, 5), "D must be"),
-        ("B = 0", (ap, pitch, stride, good, fp, 1, 0, D), "B must be"),
-        ("pitch too small", (ap, pitch - 1, stride, good, fp, 1, 2, D), "pitch"),
-        ("stride too small", (ap, pitch, stride - 1, good, fp, 1, 2, D), "image_stride"),
-        ("stride that overflows", (ap, pitch, 2 ** 63, good, fp, 1, 3, D), "address space"),
-        ("pitch that overflows", (ap, 2 ** 62, stride, good, fp, 1, 1, D), "address space"),
-        ("frames off by 4", (ap, pitch, stride, good, fp + 4, 1, 2, D), "16-byte"),
-        ("frames off by 8, float", (ap, pitch, stride, good, fp + 8, 0, 2, D), "16-byte"),
-        ("overlap: the frames begin in the images", (ap, pitch, stride, good, ap + 16, 1, 2, D), "overlap"),
-        ("overlap: the images begin in the float frames", (fp + 2 * 6 * 3 * 64 * 4 - 16, pitch, stride, good, fp, 0, 2, D), "overlap"),
-        ("a tile count beyond an int", (ap, 8192, 8192 * 8192, desc(W=8192, H=8192, Nx=2, Ny=2, overlap_x=1, overlap_y=1, rim_x=0, rim_y=0), fp, 1, 64, 1), "int"),
+        ("null image", (None, pitch, stride, good, fp, 1, 2, D), NULL),
+        ("null frames", (ap, pitch, stride, good, None, 1, 2, D), NULL),
+        ("null description", (ap, pitch, stride, None, fp, 1, 2, D), NULL),
+        ("W = 0", (ap, pitch, stride, desc(W=0), fp, 1, 2, D), PLAN),
+        ("H = 8193", (ap, pitch, stride, desc(H=8193), fp, 1, 2, D), PLAN),
+        ("Nx = 1", (ap, pitch, stride, desc(Nx=1), fp, 1, 2, D), PLAN),
+        ("Ny = 2049", (ap, pitch, stride, desc(Ny=2049), fp, 1, 2, D), PLAN),
+        ("2 V > N", (ap, pitch, stride, desc(overlap_x=5), fp, 1, 2, D), PLAN),
+        ("V < 0", (ap, pitch, stride, desc(overlap_y=-1), fp, 1, 2, D), PLAN),
+        ("2 M > V", (ap, pitch, stride, desc(rim_x=3), fp, 1, 2, D), PLAN),
+        ("M < 0", (ap, pitch, stride, desc(rim_y=-1), fp, 1, 2, D), PLAN),
+        ("D = 0", (ap, pitch, stride, good, fp, 1, 2, 0), DIM),
+        ("D = 5", (ap, 5 * W, 5 * W * H, good, fp, 1, 1, 5), DIM),
+        ("B = 0", (ap, pitch, stride, good, fp, 1, 0, D), RANGE),
+        ("pitch too small", (ap, pitch - 1, stride, good, fp, 1, 2, D), PITCH),
+        ("stride too small", (ap, pitch, stride - 1, good, fp, 1, 2, D), STRIDE),
+        ("stride that overflows", (ap, pitch, 2 ** 63, good, fp, 1, 3, D), BATCH_FIT),
+        ("pitch that overflows", (ap, 2 ** 62, stride, good, fp, 1, 1, D), ROWS_FIT),
+        ("frames off by 4", (ap, pitch, stride, good, fp + 4, 1, 2, D), ALIGN),
+        ("frames off by 8, float", (ap, pitch, stride, good, fp + 8, 0, 2, D), ALIGN),
+        ("overlap: the frames begin in the images", (ap, pitch, stride, good, ap + 16, 1, 2, D), OVERLAP),
+        ("overlap: the images begin in the float frames", (fp + 2 * 6 * 3 * 64 * 4 - 16, pitch, stride, good, fp, 0, 2, D), OVERLAP),
+        ("a tile count beyond an int", (ap, 8192, 8192 * 8192, desc(W=8192, H=8192, Nx=2, Ny=2, overlap_x=1, overlap_y=1, rim_x=0, rim_y=0), fp, 1, 64, 1), COUNT),
     ]
-    for what, (im, pi, st, de, fr, u8, b, d), word in cases:
+    for what, (im, pi, st, de, fr, u8, b, d), rule in cases:
         de = None if de is None else C.byref(de)
         assert L.aefft_image_tiles_to_frames(ctx.h, im, pi, st, de, fr, u8, b, d) == aefft.EINVAL, what
         msg = L.aefft_last_error(ctx.h).decode()
-        assert msg.startswith("aefft_image_tiles_to_frames: ") and word in msg, (what, msg)
+        assert msg == "aefft_image_tiles_to_frames: " + rule, (what, msg)
         assert L.aefft_frames_tiles_to_image(ctx.h, fr, u8, de, im, pi, st, b, d) == aefft.EINVAL, what
         msg = L.aefft_last_error(ctx.h).decode()
-        assert msg.startswith("aefft_frames_tiles_to_image: ") and word in msg, (what, msg)
+        assert msg == "aefft_frames_tiles_to_image: " + rule, (what, msg)
     ctx.sync()
     assert (host(a) == 0x3C).all() and (host(f) == 0xC3).all()
     # what is NOT an error: neighbouring ranges, a stride that is ignored for B == 1

@@ -325,39 +325,52 @@ def test_argument_errors_leave_the_outputs_untouched(ctx):
                 d[k] = v
         return _desc(**d)
 
-    # (descriptor, order, mode, frames, u8, B, Nx, Ny | image, pitch, stride), a word of the message; None for the descriptor: a null one
+    # (descriptor, order, mode, frames, u8, B, Nx, Ny | image, pitch, stride), the whole message behind the call's name; None for the descriptor: a null one
     rf = lambda d, order=0, mode=LIN, f=fp, u8=1, b=B, nx=Nx, ny=Ny: ("r", d, (order, mode, f, u8, b, nx, ny))
     im = lambda d, order=0, i=ip, pitch=W * 3, stride=W * H * 3, b=B: ("i", d, (order, i, pitch, stride, b))
+    # the rules' full texts, as the library words them
+    NULL_R, NULL_I = "null context, descriptor or frames", "null context, descriptor or image"
+    PLANE = "null plane (NV12 needs plane[0..1], I420 plane[0..2], YUYV and AEFFT_YUV_GRAY plane[0])"
+    FORMAT, MATRIX = "format must be AEFFT_YUV_NV12, AEFFT_YUV_I420 or AEFFT_YUV_YUYV", "matrix must be AEFFT_YUV_BT601, AEFFT_YUV_BT709 or AEFFT_YUV_JPEG"
+    ORDER, EVEN = "order must be AEFFT_YUV_BGR, AEFFT_YUV_RGB or AEFFT_YUV_GRAY", "YUYV needs an even W"
+    RANGE, FRANGE = "B must be >= 1 and W, H in 1..8192", "Nx, Ny must be in 1..8192"
+    MODE, AREA_RULE = "mode must be AEFFT_RESIZE_LINEAR or AEFFT_RESIZE_AREA", "AEFFT_RESIZE_AREA does not enlarge: it needs Nx <= W and Ny <= H"
+    PPITCH = "pitch too small: pitch[0] >= W (YUYV 2 W), NV12 pitch[1] >= 2 ceil(W / 2), I420 pitch[1], pitch[2] >= ceil(W / 2)"
+    PSTRIDE = "stride too small: each used stride[k] must be at least (rows - 1) * pitch[k] + the live bytes of a row for B > 1"
+    ROWS_FIT, BATCH_FIT = "rows * pitch does not fit the address space", "B * stride does not fit the address space"
+    IPITCH, ISTRIDE = "pitch must be at least W * D bytes", "image_stride must be at least (H - 1) * pitch + W * D bytes for B > 1"
+    ALIGN = "frames_d must be 16-byte aligned"
+    OVERLAP_R, OVERLAP_I = "a source plane and the frame range overlap (the op is out-of-place)", "a source plane and the image range overlap (the op is out-of-place)"
     cases = [
-        ("null descriptor", rf(None), "null"), ("null descriptor", im(None), "null"),
-        ("null frames", rf(var(nv), f=None), "null"), ("null image", im(var(nv), i=None), "null"),
-        ("null luma", rf(var(nv, planes={0: None})), "null plane"), ("null chroma", im(var(nv, planes={1: None})), "null plane"),
-        ("null V", rf(var(i4, planes={2: None})), "null plane"),
-        ("format = 3", rf(var(nv, fmt=3)), "format"), ("format = -1", im(var(nv, fmt=-1)), "format"),
-        ("matrix = 3", rf(var(nv, matrix=3)), "matrix"), ("order = 3", rf(var(nv), order=3), "order"), ("order = -1", im(var(nv), order=-1), "order"),
-        ("mode = 2", rf(var(nv), mode=2), "mode"),
-        ("B = 0", rf(var(nv), b=0), "1..8192"), ("W = 0", im(var(nv, W=0)), "1..8192"), ("H = 8193", rf(var(nv, H=8193), b=1), "1..8192"),
-        ("Nx = 0", rf(var(nv), nx=0), "1..8192"), ("Ny = 8193", rf(var(nv), ny=8193), "1..8192"),
-        ("YUYV odd W", rf(var(yu, W=W - 1)), "even"), ("YUYV odd W", im(var(yu, W=W - 1)), "even"),
-        ("luma pitch", rf(var(nv, pitches={0: W - 1})), "pitch"), ("NV12 chroma pitch", im(var(nv, pitches={1: 2 * Wc - 1})), "pitch"),
-        ("I420 V pitch", rf(var(i4, pitches={2: Wc - 1})), "pitch"), ("YUYV pitch", rf(var(yu, pitches={0: 2 * W - 1})), "pitch"),
-        ("luma stride", rf(var(nv, strides={0: W * H - 1})), "stride"), ("chroma stride", im(var(nv, strides={1: 0})), "stride"),
-        ("image pitch", im(var(nv), pitch=W * 3 - 1), "pitch"), ("image stride", im(var(nv), stride=W * H * 3 - 1), "image_stride"),
-        ("AREA enlarging x", rf(var(nv), mode=AREA, nx=W + 1), "AEFFT_RESIZE_AREA"), ("AREA enlarging y", rf(var(nv), mode=AREA, ny=H + 1), "AEFFT_RESIZE_AREA"),
-        ("frames off by 4", rf(var(nv), f=fp + 4, u8=0), "16-byte"),
-        ("overlap: frames inside the luma plane", rf(var(nv), f=yp + 16), "overlap"),
-        ("overlap: the chroma plane inside the float frames", rf(var(nv, planes={1: fp + 64}), u8=0), "overlap"),
-        ("overlap: the second image's V plane only", rf(var(i4, planes={2: fp - Wc * Hc - 2})), "overlap"),
-        ("overlap: image inside the luma plane", im(var(nv), i=yp + 8, pitch=W, stride=W * H, order=2), "overlap"),
-        ("rows * pitch overflows", rf(var(nv, pitches={0: 2 ** 62}), b=1), "address space"),
-        ("B * stride overflows", rf(var(nv, strides={0: 2 ** 63 + 8})), "address space"),
+        ("null descriptor", rf(None), NULL_R), ("null descriptor", im(None), NULL_I),
+        ("null frames", rf(var(nv), f=None), NULL_R), ("null image", im(var(nv), i=None), NULL_I),
+        ("null luma", rf(var(nv, planes={0: None})), PLANE), ("null chroma", im(var(nv, planes={1: None})), PLANE),
+        ("null V", rf(var(i4, planes={2: None})), PLANE),
+        ("format = 3", rf(var(nv, fmt=3)), FORMAT), ("format = -1", im(var(nv, fmt=-1)), FORMAT),
+        ("matrix = 3", rf(var(nv, matrix=3)), MATRIX), ("order = 3", rf(var(nv), order=3), ORDER), ("order = -1", im(var(nv), order=-1), ORDER),
+        ("mode = 2", rf(var(nv), mode=2), MODE),
+        ("B = 0", rf(var(nv), b=0), RANGE), ("W = 0", im(var(nv, W=0)), RANGE), ("H = 8193", rf(var(nv, H=8193), b=1), RANGE),
+        ("Nx = 0", rf(var(nv), nx=0), FRANGE), ("Ny = 8193", rf(var(nv), ny=8193), FRANGE),
+        ("YUYV odd W", rf(var(yu, W=W - 1)), EVEN), ("YUYV odd W", im(var(yu, W=W - 1)), EVEN),
+        ("luma pitch", rf(var(nv, pitches={0: W - 1})), PPITCH), ("NV12 chroma pitch", im(var(nv, pitches={1: 2 * Wc - 1})), PPITCH),
+        ("I420 V pitch", rf(var(i4, pitches={2: Wc - 1})), PPITCH), ("YUYV pitch", rf(var(yu, pitches={0: 2 * W - 1})), PPITCH),
+        ("luma stride", rf(var(nv, strides={0: W * H - 1})), PSTRIDE), ("chroma stride", im(var(nv, strides={1: 0})), PSTRIDE),
+        ("image pitch", im(var(nv), pitch=W * 3 - 1), IPITCH), ("image stride", im(var(nv), stride=W * H * 3 - 1), ISTRIDE),
+        ("AREA enlarging x", rf(var(nv), mode=AREA, nx=W + 1), AREA_RULE), ("AREA enlarging y", rf(var(nv), mode=AREA, ny=H + 1), AREA_RULE),
+        ("frames off by 4", rf(var(nv), f=fp + 4, u8=0), ALIGN),
+        ("overlap: frames inside the luma plane", rf(var(nv), f=yp + 16), OVERLAP_R),
+        ("overlap: the chroma plane inside the float frames", rf(var(nv, planes={1: fp + 64}), u8=0), OVERLAP_R),
+        ("overlap: the second image's V plane only", rf(var(i4, planes={2: fp - Wc * Hc - 2})), OVERLAP_R),
+        ("overlap: image inside the luma plane", im(var(nv), i=yp + 8, pitch=W, stride=W * H, order=2), OVERLAP_I),
+        ("rows * pitch overflows", rf(var(nv, pitches={0: 2 ** 62}), b=1), ROWS_FIT),
+        ("B * stride overflows", rf(var(nv, strides={0: 2 ** 63 + 8})), BATCH_FIT),
     ]
-    for what, (kind, d, args), word in cases:
+    for what, (kind, d, args), rule in cases:
         ref = None if d is None else C.byref(d)
         name, rc = ("aefft_yuv_resize_to_frames", L.aefft_yuv_resize_to_frames(ctx.h, ref, *args)) if kind == "r" else ("aefft_yuv_to_image", L.aefft_yuv_to_image(ctx.h, ref, *args))
         assert rc == aefft.EINVAL, what
         msg = L.aefft_last_error(ctx.h).decode()
-        assert msg.startswith(name + ": ") and word in msg, (what, msg)
+        assert msg == name + ": " + rule, (what, msg)
     # what is NOT an error: strides of any value for one image; the smallest legal strides; null chroma planes with GRAY
     one = torch.full((3 * Nx * Ny,), 0xEE, dtype=torch.uint8, device=dev)
     assert L.aefft_yuv_resize_to_frames(ctx.h, C.byref(var(nv, strides={0: 0, 1: 0})), 0, LIN, one.data_ptr(), 1, 1, Nx, Ny) == aefft.OK

@@ -174,6 +174,7 @@ def test_the_older_kernel_files_keep_their_kernels_and_the_taps_are_stated_once(
     assert "4096 * (n - s * den) + den" not in open(os.path.join(CSRC, "present_kernels.hip")).read()
     for tool in ("resize_hostcheck.cpp", "present_hostcheck.cpp"):
         assert os.path.exists(os.path.join(ROOT, "tools", tool))
+        assert '#include "hostlanes.h"' in open(os.path.join(ROOT, "tools", tool)).read()
 
 
 def test_python_layout_rules_need_no_device():

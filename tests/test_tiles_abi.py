@@ -282,10 +282,12 @@ def test_tile_kernels_use_no_scratch_and_cover_every_instantiation():
     # the launchers are declared with the others, the entry points stand with the image calls and share their helpers
     internal = open(os.path.join(CSRC, "internal.h")).read()
     assert "hipError_t launch_tile_gather(" in internal and "hipError_t launch_tile_blend(" in internal
-    ops = open(os.path.join(CSRC, "ops.hip")).read()
+    ops = open(os.path.join(CSRC, "image_ops.hip")).read()
     assert ops.index("// image boundary") < ops.index('extern "C" int aefft_yuv_resize_to_frames(') < ops.index('extern "C" int aefft_tile_plan_make(')
     entry = ops[ops.index('extern "C" int aefft_tile_plan_make('):]
     assert "ranges_overlap(" in entry and "aligned16(" in entry and entry.count("KID_IMAGE") == 2 and ops.count("static bool ranges_overlap(") == 1
+    rest = open(os.path.join(CSRC, "ops.hip")).read()
+    assert "aefft_image_" not in rest and "KID_IMAGE" not in rest
     # no code is shared with the other image kernels through a header
     src = open(os.path.join(CSRC, "tile_kernels.hip")).read()
     assert set(re.findall(r'#include "([^"]+)"', src)) == {"internal.h", "fft_common.h"}
@@ -298,6 +300,9 @@ def test_the_host_check_program_is_there_and_stands_alone():
     src = open(path).read()
     assert '#include "../autoencoder-fft_amd/csrc/tile_kernels.hip"' in src and "int main(" in src and "-fsanitize=address,undefined" in src
     assert "Python.h" not in src and "hip_runtime" not in src
+    lanes = open(os.path.join(ROOT, "tools", "hostlanes.h")).read()
+    assert '#include "hostlanes.h"' in src and "#define AEFFT_HOSTCHECK" in lanes
+    assert "Python.h" not in lanes and "hip_runtime" not in lanes and "LD_PRELOAD" not in lanes
     assert os.path.exists(os.path.join(ROOT, "tools", "tiles_bench.py"))
     # the product never imports the restatement
     for dirpath, _, files in os.walk(os.path.join(ROOT, "autoencoder-fft_amd")):

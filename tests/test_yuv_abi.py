@@ -178,8 +178,10 @@ def test_yuv_kernels_use_no_scratch_and_cover_what_the_launchers_name():
     mk = open(os.path.join(CSRC, "Makefile")).read()
     assert "yuv_kernels.hip" in mk.split("SRCS =")[1].split("\n")[0]
     assert "hipError_t launch_yuv_image(" in open(os.path.join(CSRC, "internal.h")).read() and "hipError_t launch_yuv_resize(" in open(os.path.join(CSRC, "internal.h")).read()
-    ops = open(os.path.join(CSRC, "ops.hip")).read()
+    ops = open(os.path.join(CSRC, "image_ops.hip")).read()
     assert ops.index("// image boundary") < ops.index('extern "C" int aefft_frames_degrade(') < ops.index('extern "C" int aefft_yuv_to_image(') < ops.index('extern "C" int aefft_yuv_resize_to_frames(')
+    rest = open(os.path.join(CSRC, "ops.hip")).read()
+    assert "aefft_image_" not in rest and "KID_IMAGE" not in rest
 
 
 def test_resize_kernels_still_hold_their_sixteen():
@@ -190,10 +192,13 @@ def test_resize_kernels_still_hold_their_sixteen():
 
 def test_host_check_source_is_present_and_stands_alone():
     src = open(os.path.join(ROOT, "tools", "yuv_hostcheck.cpp")).read()
-    assert "int main()" in src and '#include "../autoencoder-fft_amd/csrc/yuv_kernels.hip"' in src and "#define AEFFT_YUV_HOSTCHECK" in src
+    assert "int main()" in src and '#include "../autoencoder-fft_amd/csrc/yuv_kernels.hip"' in src
     assert "-fsanitize=address,undefined" in src and "hip/hip_runtime" not in src and "Python.h" not in src and "LD_PRELOAD" not in src
+    lanes = open(os.path.join(ROOT, "tools", "hostlanes.h")).read()
+    assert '#include "hostlanes.h"' in src and "#define AEFFT_HOSTCHECK" in lanes
+    assert "Python.h" not in lanes and "hip_runtime" not in lanes and "LD_PRELOAD" not in lanes
     kern = open(os.path.join(CSRC, "yuv_kernels.hip")).read()
-    assert "#ifndef AEFFT_YUV_HOSTCHECK" in kern
+    assert "#ifndef AEFFT_HOSTCHECK" in kern and "AEFFT_YUV_HOSTCHECK" not in kern
     # its restatement has a table of its own with the header's integers
     for _, ky, rows in R.TABLE.values():
         for n in (ky,) + tuple(v for ab in rows for v in ab if v):

@@ -9,37 +9,15 @@
 //
 // A stand-alone program: it is not loaded into Python and does not touch a GPU.  Exit status 0 and "all N runs exact" when every run is
 // bit-exact on every element of the destination.
-#include <math.h>
-#include <pthread.h>
-#include <stddef.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <thread>
-#include <vector>
-
-struct Dim3 { unsigned x, y, z; };
-static thread_local Dim3 threadIdx, blockIdx;
-static Dim3 gridDim;
-static pthread_barrier_t wg_barrier;
-static void __syncthreads() { pthread_barrier_wait(&wg_barrier); }
-struct float4 { float x, y, z, w; } __attribute__((aligned(16)));
-// SpinToImage_C's pixel rule as fft_common.h states it for the device
-static inline unsigned px_u8(float v) { return v > 0.f ? (unsigned)fminf(roundf(v), 255.f) : 0u; }
+#include "hostlanes.h"
 static inline unsigned dg_bytesum(unsigned x, unsigned acc) { return acc + (x & 255u) + ((x >> 8) & 255u) + ((x >> 16) & 255u) + (x >> 24); }
-#define __device__
-#define __forceinline__ inline
-#define DG_HD static inline
 #define DG_BYTESUM(x, acc) dg_bytesum((x), (acc))
-#define AEFFT_DEGRADE_HOSTCHECK
 #include "../autoencoder-fft_amd/csrc/degrade_kernels.hip"
+#include "hostcheck_ref.h"
 
 using namespace aefft;
 
 // ---- the formulas of include/aefft.h, restated -------------------------------------------------
-typedef long long i64;
 typedef unsigned long long u64;
 static void ref_mulhilo(uint32_t a, uint32_t b, uint32_t* hi, uint32_t* lo)
 {
@@ -62,40 +40,8 @@ static void ref_philox(const uint32_t ctr[4], const uint32_t key[2], uint32_t ou
     }
     memcpy(out, c, sizeof c);
 }
-// the reference's own rounding, without roundf: clamp, halves away from zero, NaN -> 0
-static unsigned px_ref(float v)
-{
-    if (!(v > 0.f)) return 0;
-    if (v >= 255.f) return 255;
-    return (unsigned)floor((double)v + 0.5);
-}
 static i64 binom(int n, int k) { i64 r = 1; for (int s = 1; s <= k; ++s) r = r * (n - k + s) / s; return r; }
 static int clampi(int v, int hi) { return v < 0 ? 0 : v > hi ? hi : v; }
-
-// ---- the launch: every workgroup of the grid, one after the other, its 256 lanes as threads -----
-template <class F> static void launch(unsigned gx, unsigned gy, unsigned gz, size_t lds_words, F body)
-{
-    void* lp = nullptr;
-    if (posix_memalign(&lp, 16, lds_words ? 4 * lds_words : 16)) abort();        // exactly what the kernel declares: LDS overruns show
-    unsigned* lds = (unsigned*)lp;
-    gridDim = Dim3{gx, gy, gz};
-    pthread_barrier_init(&wg_barrier, nullptr, 256);
-    std::vector<std::thread> th;
-    for (unsigned t = 0; t < 256; ++t)
-        th.emplace_back([&, t] {
-            for (unsigned bz = 0; bz < gridDim.z; ++bz)
-            for (unsigned by = 0; by < gridDim.y; ++by)
-                for (unsigned bx = 0; bx < gridDim.x; ++bx) {
-                    threadIdx = Dim3{t, 0, 0};
-                    blockIdx = Dim3{bx, by, bz};
-                    body(lds_words ? lds : nullptr);
-                    __syncthreads();                                             // (the next workgroup reuses this one's LDS)
-                }
-        });
-    for (auto& x : th) x.join();
-    pthread_barrier_destroy(&wg_barrier);
-    free(lds);
-}
 
 typedef void (*dg_fn)(const DgArgs&, unsigned*);
 template <int R, bool SF32, bool DF32, bool WORDS> static void dg_body(const DgArgs& a, unsigned* lds)
@@ -108,9 +54,6 @@ template <int R, bool SF32, bool DF32, bool WORDS> static void dg_body(const DgA
 static const dg_fn DG_BODIES[5][2][2][2] = {DG_ROW(0), DG_ROW(1), DG_ROW(2), DG_ROW(3), DG_ROW(4)};
 static const int DG_LDS[5] = {dg_lds_words(0), dg_lds_words(1), dg_lds_words(2), dg_lds_words(3), dg_lds_words(4)};
 
-static unsigned rnd_state = 12345;
-static unsigned rnd() { rnd_state = rnd_state * 1664525u + 1013904223u; return rnd_state >> 24; }
-static int runs = 0, failures = 0;
 static const float SPECIAL[] = {NAN, INFINITY, -INFINITY, -3.f, 300.f, 0.5f, 1.5f, 254.5f, 0.49999997f, 255.5f, 2.5f};
 
 struct Shape { int B, D, Nx, Ny; };
@@ -222,7 +165,5 @@ int main()
         }
     // the frames on grid.y x grid.z: five frames as 2 x 3, the sixth workgroup returns at once
     for (int R = 0; R <= 1; ++R) run(Shape{5, 3, 9, 11}, R, 25.f, 0.02f, false, false, false, 3, ~0ULL - 1, 2);
-    if (failures) printf("%d of %d runs FAILED\n", failures, runs);
-    else printf("all %d runs exact\n", runs);
-    return failures ? 1 : 0;
+    return report();
 }

@@ -8,58 +8,11 @@
 //
 // A stand-alone program: it is not loaded into Python and does not touch a GPU.  Exit status 0 and "all N runs exact" when every run is
 // byte-exact on the live bytes of the image and every other byte of the image's allocation is as it was.
-#include <math.h>
-#include <pthread.h>
-#include <stddef.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <thread>
-#include <vector>
-
-struct Dim3 { unsigned x, y, z; };
-static thread_local Dim3 threadIdx, blockIdx;
-static Dim3 gridDim;
-static pthread_barrier_t wg_barrier;
-static void __syncthreads() { pthread_barrier_wait(&wg_barrier); }
-struct float4 { float x, y, z, w; } __attribute__((aligned(16)));
-// SpinToImage_C's pixel rule as fft_common.h states it for the device
-static inline unsigned px_u8(float v) { return v > 0.f ? (unsigned)fminf(roundf(v), 255.f) : 0u; }
-#define __device__
-#define __forceinline__ inline
-#define RZ_HD static inline
-#define RZ_UNIFORM(x) (x)
-#define AEFFT_PRESENT_HOSTCHECK
+#include "hostlanes.h"
 #include "../autoencoder-fft_amd/csrc/present_kernels.hip"
+#include "hostcheck_ref.h"
 
 using namespace aefft;
-
-// ---- the formulas of include/aefft.h, restated -------------------------------------------------
-typedef long long i64;
-static i64 fdiv(i64 a, i64 b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
-static void linear_axis(int i, int S, int N, int* s0, int* s1, int* w)
-{
-    const i64 n = (2LL * i + 1) * S - N, den = 2LL * N;
-    i64 s = fdiv(n, den), r = n - s * den, ww = (4096 * r + den) / (2 * den);
-    if (s < 0) { s = 0; ww = 0; }
-    if (s >= S - 1) { s = S - 1; ww = 0; }
-    *s0 = (int)s; *s1 = (int)(s + 1 < S - 1 ? s + 1 : S - 1); *w = (int)ww;
-}
-static i64 overlap(int i, int k, int S, int N)
-{
-    const i64 hi = (i + 1LL) * S < (k + 1LL) * N ? (i + 1LL) * S : (k + 1LL) * N, lo = (i64)i * S > (i64)k * N ? (i64)i * S : (i64)k * N;
-    return hi > lo ? hi - lo : 0;
-}
-// the reference's own rounding, without roundf: clamp, halves away from zero, NaN -> 0
-static unsigned px_ref(float v)
-{
-    if (!(v > 0.f)) return 0;
-    if (v >= 255.f) return 255;
-    const double t = floor((double)v + 0.5);
-    return (unsigned)t;
-}
 
 struct Layout { size_t pitch, stride, off, extent; };
 // kind 0 tight, 1 pitch rounded up to 64, 2 pitch W D + 5 from a base off by one byte, 3 a region of interest at (3, 5) of a larger batch
@@ -74,35 +27,6 @@ static Layout layout(int kind, int B, int D, int W, int H)
     l.extent = (size_t)(B - 1) * l.stride + (size_t)(H - 1) * l.pitch + (size_t)W * D;   // the LAST byte the call may touch is at off + extent - 1
     return l;
 }
-
-// ---- the launch: every workgroup of the grid, one after the other, its 256 lanes as threads -----
-template <class F> static void launch(unsigned gx, unsigned gy, unsigned gz, size_t lds_words, F body)
-{
-    void* lp = nullptr;
-    if (posix_memalign(&lp, 16, 4 * lds_words)) abort();                         // exactly what the launcher asks for: LDS overruns show
-    unsigned* lds = (unsigned*)lp;
-    gridDim = Dim3{gx, gy, gz};
-    pthread_barrier_init(&wg_barrier, nullptr, 256);
-    std::vector<std::thread> th;
-    for (unsigned t = 0; t < 256; ++t)
-        th.emplace_back([&, t] {
-            for (unsigned bz = 0; bz < gridDim.z; ++bz)
-            for (unsigned by = 0; by < gridDim.y; ++by)
-                for (unsigned bx = 0; bx < gridDim.x; ++bx) {
-                    threadIdx = Dim3{t, 0, 0};
-                    blockIdx = Dim3{bx, by, bz};
-                    body(lds);
-                    __syncthreads();                                             // (the next workgroup reuses this one's LDS)
-                }
-        });
-    for (auto& x : th) x.join();
-    pthread_barrier_destroy(&wg_barrier);
-    free(lds);
-}
-
-static unsigned rnd_state = 12345;
-static unsigned rnd() { rnd_state = rnd_state * 1664525u + 1013904223u; return rnd_state >> 24; }
-static int runs = 0, failures = 0;
 
 // ---- frames -> image ----------------------------------------------------------------------------
 typedef void (*fr_fn)(const FrArgs&, unsigned*);
@@ -271,7 +195,5 @@ int main(int argc, char** argv)
                 run_overlay(s, kind, smooth, a, 0.25f, 7.5f);
                 run_overlay(s, kind, smooth, kind == 0 ? 256 : alphas[(runs + 2) % 5], 1.0f, -0.125f);   // hi < lo: the inverted scale
             }
-    if (failures) printf("%d of %d runs FAILED\n", failures, runs);
-    else printf("all %d runs exact\n", runs);
-    return failures ? 1 : 0;
+    return report();
 }

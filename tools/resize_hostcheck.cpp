@@ -8,48 +8,13 @@
 //
 // A stand-alone program: it is not loaded into Python and does not touch a GPU.  Exit status 0 and "all N runs exact" when every run is
 // byte-exact (float frames compared as bits) and every byte/element of the frames was written.
-#include <pthread.h>
-#include <stddef.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <thread>
-#include <vector>
-
-struct Dim3 { unsigned x, y, z; };
-static thread_local Dim3 threadIdx, blockIdx;
-static Dim3 gridDim;
-static pthread_barrier_t wg_barrier;
-static void __syncthreads() { pthread_barrier_wait(&wg_barrier); }
-struct float4 { float x, y, z, w; } __attribute__((aligned(16)));
-static inline float4 make_float4(float x, float y, float z, float w) { return float4{x, y, z, w}; }
-#define __device__
-#define __forceinline__ inline
-#define RZ_HD static inline
-#define RZ_UNIFORM(x) (x)
-#define AEFFT_RESIZE_HOSTCHECK
+#include "hostlanes.h"
 #include "../autoencoder-fft_amd/csrc/resize_kernels.hip"
+#include "hostcheck_ref.h"
 
 using namespace aefft;
 
 // ---- the formulas of include/aefft.h, restated -------------------------------------------------
-typedef long long i64;
-static i64 fdiv(i64 a, i64 b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
-static void linear_axis(int i, int S, int N, int* s0, int* s1, int* w)
-{
-    const i64 n = (2LL * i + 1) * S - N, den = 2LL * N;
-    i64 s = fdiv(n, den), r = n - s * den, ww = (4096 * r + den) / (2 * den);
-    if (s < 0) { s = 0; ww = 0; }
-    if (s >= S - 1) { s = S - 1; ww = 0; }
-    *s0 = (int)s; *s1 = (int)(s + 1 < S - 1 ? s + 1 : S - 1); *w = (int)ww;
-}
-static i64 overlap(int i, int k, int S, int N)
-{
-    const i64 hi = (i + 1LL) * S < (k + 1LL) * N ? (i + 1LL) * S : (k + 1LL) * N, lo = (i64)i * S > (i64)k * N ? (i64)i * S : (i64)k * N;
-    return hi > lo ? hi - lo : 0;
-}
 // want: [B][D][Nx][Ny] as the 8-bit pixel or, float frames, q (value = q * 2^-16)
 static void reference(const unsigned char* img, size_t pitch, size_t stride, int W, int H, int mode, bool f32, int B, int D, int Nx, int Ny, std::vector<unsigned>& want)
 {
@@ -88,39 +53,14 @@ static void reference(const unsigned char* img, size_t pitch, size_t stride, int
                 }
 }
 
-// ---- the launch: every workgroup of the grid, one after the other, its 256 lanes as threads -----
+// ---- the bodies the launcher chooses between ----------------------------------------------------
 typedef void (*body_fn)(const RzArgs&, unsigned*);
 template <int D, bool F32, int MODE> static void body(const RzArgs& a, unsigned* lds) { resize_body<D, F32, MODE>(a, lds); }
 #define ROW(D) {{body<D, false, 0>, body<D, false, 1>}, {body<D, true, 0>, body<D, true, 1>}}
 static const body_fn BODIES[4][2][2] = {ROW(1), ROW(2), ROW(3), ROW(4)};
 
-static void launch(const RzArgs& g, int D, bool f32, int mode, unsigned grid_y)
-{
-    const size_t words = (size_t)rz_lds_words(D, g.P, g.RB);
-    unsigned* lds = (unsigned*)malloc(4 * words);                                // exactly what the launcher asks for: LDS overruns show
-    gridDim = Dim3{(unsigned)(g.tx * g.ty), grid_y, 1};
-    pthread_barrier_init(&wg_barrier, nullptr, 256);
-    std::vector<std::thread> th;
-    for (unsigned t = 0; t < 256; ++t)
-        th.emplace_back([&, t] {
-            for (unsigned by = 0; by < gridDim.y; ++by)
-                for (unsigned bx = 0; bx < gridDim.x; ++bx) {
-                    threadIdx = Dim3{t, 0, 0};
-                    blockIdx = Dim3{bx, by, 0};
-                    BODIES[D - 1][f32][mode](g, lds);
-                    __syncthreads();                                             // (the next workgroup reuses this one's LDS)
-                }
-        });
-    for (auto& x : th) x.join();
-    pthread_barrier_destroy(&wg_barrier);
-    free(lds);
-}
-
 struct Shape { int B, D, W, H, Nx, Ny; };
-static unsigned rnd_state = 12345;
-static unsigned rnd() { rnd_state = rnd_state * 1664525u + 1013904223u; return rnd_state >> 24; }
 
-static int runs = 0, failures = 0;
 // kind 0 tight, 1 pitch rounded up to 64, 2 pitch W D + 5 from a base off by one byte, 3 a region of interest at (3, 5) of a larger batch
 static void run(const Shape& s, int kind, int mode, bool f32, unsigned grid_y = 0)
 {
@@ -140,7 +80,7 @@ static void run(const Shape& s, int kind, int mode, bool f32, unsigned grid_y = 
     unsigned char* frames = (unsigned char*)fp;
     memset(frames, 0xEE, n * es);
     const RzArgs g = rz_geometry(img, pitch, stride, W, H, mode, frames, B, D, Nx, Ny);
-    launch(g, D, f32, mode, grid_y ? grid_y : (unsigned)B);
+    launch((unsigned)(g.tx * g.ty), grid_y ? grid_y : (unsigned)B, 1u, (size_t)rz_lds_words(D, g.P, g.RB), [&](unsigned* lds) { BODIES[D - 1][f32][mode](g, lds); });
     std::vector<unsigned> want;
     reference(img, pitch, stride, W, H, mode, f32, B, D, Nx, Ny, want);
     size_t bad = 0;
@@ -174,7 +114,5 @@ int main()
             }
     // a folded grid: five images on two rows of workgroups
     for (int mode = 0; mode < 2; ++mode) run(Shape{5, 3, 11, 9, 8, 8}, 2, mode, false, 2);
-    if (failures) printf("%d of %d runs FAILED\n", failures, runs);
-    else printf("all %d runs exact\n", runs);
-    return failures ? 1 : 0;
+    return report();
 }

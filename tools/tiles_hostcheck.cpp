@@ -9,36 +9,14 @@
 //
 // A stand-alone program: it is not loaded into Python and does not touch a GPU.  Exit status 0 and "all N runs exact" when every run is
 // bit-exact on every byte of the destination, the bytes around it included.
-#include <math.h>
-#include <pthread.h>
-#include <stddef.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <thread>
-#include <vector>
-
 #include "../include/aefft.h"
-
-struct Dim3 { unsigned x, y, z; };
-static thread_local Dim3 threadIdx, blockIdx;
-static Dim3 gridDim;
-static pthread_barrier_t wg_barrier;
-static void __syncthreads() { pthread_barrier_wait(&wg_barrier); }
-struct float4 { float x, y, z, w; } __attribute__((aligned(16)));
-// SpinToImage_C's pixel rule as fft_common.h states it for the device
-static inline unsigned px_u8(float v) { return v > 0.f ? (unsigned)fminf(roundf(v), 255.f) : 0u; }
-#define TL_HD static inline
-#define TL_MHD static inline
-#define AEFFT_TILES_HOSTCHECK
+#include "hostlanes.h"
 #include "../autoencoder-fft_amd/csrc/tile_kernels.hip"
+#include "hostcheck_ref.h"
 
 using namespace aefft;
 
 // ---- the formulas of include/aefft.h, restated -------------------------------------------------
-typedef long long i64;
 struct RefAxis { int W, N, V, M, S, R, n, o0; i64 den; };
 static bool ref_axis(int W, int N, int V, int M, RefAxis* a)
 {
@@ -66,38 +44,14 @@ static i64 ref_weight(const RefAxis& a, int t, int x)
     if (t < a.n - 1 && k >= a.N - a.M - a.R) return 2 * (a.N - a.M - 1 - k) + 1;
     return a.den;
 }
-// the reference's own rounding, without roundf: clamp, halves away from zero, NaN -> 0
-static unsigned px_ref(float v)
-{
-    if (!(v > 0.f)) return 0;
-    if (v >= 255.f) return 255;
-    return (unsigned)floor((double)v + 0.5);
-}
 
-// ---- the launch: every workgroup of the grid, one after the other, its 256 lanes as threads; the units on grid.y x grid.z as the kernels take them -----
-template <class F> static void launch(unsigned gx, unsigned gy, unsigned gz, unsigned units, size_t lds_words, F body)
+// ---- the units on grid.y x grid.z as the kernels take them: a workgroup past the last unit returns at once ----
+template <class K> static void launch_units(const TlArgs& g, unsigned fold, size_t lds_words, K kernel)
 {
-    void* lp = nullptr;
-    if (posix_memalign(&lp, 16, 4 * lds_words)) abort();                         // exactly what the kernel declares: LDS overruns show
-    unsigned* lds = (unsigned*)lp;
-    gridDim = Dim3{gx, gy, gz};
-    pthread_barrier_init(&wg_barrier, nullptr, 256);
-    std::vector<std::thread> th;
-    for (unsigned t = 0; t < 256; ++t)
-        th.emplace_back([&, t] {
-            threadIdx = Dim3{t, 0, 0};
-            for (unsigned bz = 0; bz < gridDim.z; ++bz)
-            for (unsigned by = 0; by < gridDim.y; ++by)
-                for (unsigned bx = 0; bx < gridDim.x; ++bx) {
-                    blockIdx = Dim3{bx, by, bz};
-                    const unsigned u = blockIdx.z * gridDim.y + blockIdx.y;
-                    if (u < units) body(blockIdx.x, u, lds);
-                    __syncthreads();                                             // (the next workgroup reuses this one's LDS)
-                }
-        });
-    for (auto& x : th) x.join();
-    pthread_barrier_destroy(&wg_barrier);
-    free(lds);
+    launch(g.bx * g.by, fold ? fold : tl_grid_y(g), fold ? (g.units + fold - 1) / fold : tl_grid_z(g), lds_words, [&](unsigned* lds) {
+        const unsigned u = blockIdx.z * gridDim.y + blockIdx.y;
+        if (u < g.units) kernel(g, blockIdx.x, u, lds);
+    });
 }
 
 typedef void (*tl_fn)(const TlArgs&, unsigned, unsigned, unsigned*);
@@ -106,9 +60,6 @@ static const tl_fn GATHER[4][2] = TL_ROW(tile_gather_body);
 static const tl_fn BLEND[4][2] = TL_ROW(tile_blend_body);
 static const size_t LDS_WORDS[4] = {TlLds<1>::TOTAL, TlLds<2>::TOTAL, TlLds<3>::TOTAL, TlLds<4>::TOTAL};
 
-static unsigned rnd_state = 12345;
-static unsigned rnd() { rnd_state = rnd_state * 1664525u + 1013904223u; return rnd_state >> 24; }
-static int runs = 0, failures = 0;
 static const float SPECIAL[] = {NAN, INFINITY, -INFINITY, -3.f, 300.f, 0.5f, 1.5f, 254.5f, 0.49999997f, 255.5f, 2.5f};
 
 struct Case { int W, H, Nx, Ny, Vx, Vy, Mx, My; };
@@ -158,8 +109,7 @@ static void run(const Case& c, int D, int B, bool f32, int layout, unsigned fold
     size_t bad = 0;
     // gather
     if (!tl_geometry(&desc, src.p, src.pitch, src.stride, fr, B, false, &g)) abort();
-    launch(g.bx * g.by, fold ? fold : tl_grid_y(g), fold ? (g.units + fold - 1) / fold : tl_grid_z(g), g.units, LDS_WORDS[D - 1],
-           [&](unsigned blk, unsigned u, unsigned* lds) { GATHER[D - 1][f32](g, blk, u, lds); });
+    launch_units(g, fold, LDS_WORDS[D - 1], GATHER[D - 1][f32]);
     for (size_t f = 0; f < T; ++f) {
         const int tx = (int)(f % ax.n), ty = (int)(f / ax.n % ay.n);
         const size_t b = f / ax.n / ay.n;
@@ -176,8 +126,7 @@ static void run(const Case& c, int D, int B, bool f32, int layout, unsigned fold
     std::vector<unsigned char> before(dst.extent);
     for (size_t k = 0; k < dst.extent; ++k) before[k] = dst.p[k] = (unsigned char)rnd();
     if (!tl_geometry(&desc, dst.p, dst.pitch, dst.stride, fr, B, true, &g)) abort();
-    launch(g.bx * g.by, fold ? fold : tl_grid_y(g), fold ? (g.units + fold - 1) / fold : tl_grid_z(g), g.units, LDS_WORDS[D - 1],
-           [&](unsigned blk, unsigned u, unsigned* lds) { BLEND[D - 1][f32](g, blk, u, lds); });
+    launch_units(g, fold, LDS_WORDS[D - 1], BLEND[D - 1][f32]);
     for (size_t k = 0; k < dst.extent; ++k) {
         const size_t in = k % dst.stride, col = in % dst.pitch;
         const bool live = in < (size_t)(c.H - 1) * dst.pitch + (size_t)c.W * D && col < (size_t)c.W * D;
@@ -192,8 +141,7 @@ static void run(const Case& c, int D, int B, bool f32, int layout, unsigned fold
         } else ((unsigned char*)fr)[k] = px[k] = (unsigned char)rnd();
     }
     for (size_t k = 0; k < dst.extent; ++k) before[k] = dst.p[k] = (unsigned char)rnd();
-    launch(g.bx * g.by, fold ? fold : tl_grid_y(g), fold ? (g.units + fold - 1) / fold : tl_grid_z(g), g.units, LDS_WORDS[D - 1],
-           [&](unsigned blk, unsigned u, unsigned* lds) { BLEND[D - 1][f32](g, blk, u, lds); });
+    launch_units(g, fold, LDS_WORDS[D - 1], BLEND[D - 1][f32]);
     std::vector<unsigned char> want(before);
     const i64 dd = ax.den * ay.den;
     for (int b = 0; b < B; ++b)
@@ -255,7 +203,5 @@ int main()
     // each layout on one shape, and the units on a grid.y of three
     for (int v = 0; v < 4; ++v) run(cases[0], 3, 2, false, v, v == 0 ? 3 : 0);
     for (int v = 0; v < 4; ++v) run(cases[7], 3, 2, v & 1, v, v == 0 ? 3 : 0);
-    if (failures) printf("%d of %d runs FAILED\n", failures, runs);
-    else printf("all %d runs exact\n", runs);
-    return failures ? 1 : 0;
+    return report();
 }

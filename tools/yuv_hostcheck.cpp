@@ -9,39 +9,17 @@
 //
 // A stand-alone program: it is not loaded into Python and does not touch a GPU.  Exit status 0 and "all N runs exact" when every run is
 // byte-exact (float frames compared as bits) and every byte/element of the destination was written, and nothing beside it.
-#include <pthread.h>
-#include <stddef.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <thread>
-#include <vector>
-
-struct Dim3 { unsigned x, y, z; };
-static thread_local Dim3 threadIdx, blockIdx;
-static Dim3 gridDim;
-static pthread_barrier_t wg_barrier;
-static void __syncthreads() { pthread_barrier_wait(&wg_barrier); }
-struct float4 { float x, y, z, w; } __attribute__((aligned(16)));
-static inline float4 make_float4(float x, float y, float z, float w) { return float4{x, y, z, w}; }
-#define __device__
-#define __forceinline__ inline
-#define RZ_HD static inline
-#define RZ_UNIFORM(x) (x)
-#define AEFFT_YUV_HOSTCHECK
+#include "hostlanes.h"
 #include "../autoencoder-fft_amd/csrc/yuv_kernels.hip"
+#include "hostcheck_ref.h"
 
 using namespace aefft;
 
 // ---- include/aefft.h, restated -----------------------------------------------------------------
-typedef long long i64;
 // rows R, G, B: (a, b); then yoff, ky
 static const i64 TABLE[3][8] = {{0, 1673555, -410793, -852458, 2115221, 0, 16, 1220945},
                                 {0, 1879825, -223607, -558796, 2215014, 0, 16, 1220945},
                                 {0, 1470104, -360853, -748826, 1858077, 0, 0, 1048576}};
-static i64 fdiv(i64 a, i64 b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
 struct Planes { const unsigned char* p[3]; size_t pitch[3], stride[3]; };
 // the pixels p[b][y][x][d], tight
 static void convert_ref(int fmt, const Planes& s, int W, int H, int matrix, int order, int B, std::vector<unsigned char>& px)
@@ -68,19 +46,6 @@ static void convert_ref(int fmt, const Planes& s, int W, int H, int matrix, int 
                     px[(((size_t)b * H + y) * W + x) * D + d] = (unsigned char)(v < 0 ? 0 : v > 255 ? 255 : v);
                 }
             }
-}
-static void linear_axis(int i, int S, int N, int* s0, int* s1, int* w)
-{
-    const i64 n = (2LL * i + 1) * S - N, den = 2LL * N;
-    i64 s = fdiv(n, den), r = n - s * den, ww = (4096 * r + den) / (2 * den);
-    if (s < 0) { s = 0; ww = 0; }
-    if (s >= S - 1) { s = S - 1; ww = 0; }
-    *s0 = (int)s; *s1 = (int)(s + 1 < S - 1 ? s + 1 : S - 1); *w = (int)ww;
-}
-static i64 overlap(int i, int k, int S, int N)
-{
-    const i64 hi = (i + 1LL) * S < (k + 1LL) * N ? (i + 1LL) * S : (k + 1LL) * N, lo = (i64)i * S > (i64)k * N ? (i64)i * S : (i64)k * N;
-    return hi > lo ? hi - lo : 0;
 }
 // want: [B][D][Nx][Ny] as the 8-bit pixel or, float frames, q (value = q * 2^-16), from the tight pixels
 static void resize_ref(const unsigned char* img, int W, int H, int mode, bool f32, int B, int D, int Nx, int Ny, std::vector<unsigned>& want)
@@ -121,26 +86,7 @@ static void resize_ref(const unsigned char* img, int W, int H, int mode, bool f3
                 }
 }
 
-// ---- the launches: every workgroup of the grid, one after the other, its 256 lanes as threads -----
-template <class Body>
-static void launch(unsigned gx, unsigned gy, const Body& body)
-{
-    gridDim = Dim3{gx, gy, 1};
-    pthread_barrier_init(&wg_barrier, nullptr, 256);
-    std::vector<std::thread> th;
-    for (unsigned t = 0; t < 256; ++t)
-        th.emplace_back([&, t] {
-            for (unsigned by = 0; by < gridDim.y; ++by)
-                for (unsigned bx = 0; bx < gridDim.x; ++bx) {
-                    threadIdx = Dim3{t, 0, 0};
-                    blockIdx = Dim3{bx, by, 0};
-                    body();
-                    __syncthreads();                                             // (the next workgroup reuses this one's LDS)
-                }
-        });
-    for (auto& x : th) x.join();
-    pthread_barrier_destroy(&wg_barrier);
-}
+// ---- the bodies the launchers choose between ---------------------------------------------------
 typedef void (*resize_fn)(const YvArgs&, unsigned*);
 typedef void (*image_fn)(const YiArgs&);
 template <int F, int D> static void ibody(const YiArgs& a) { yuv_image_body<F, D>(a); }
@@ -150,8 +96,6 @@ template <int F, int D, bool T, int M> static void rbody(const YvArgs& a, unsign
 static const resize_fn RBODY[3][2][2][2] = {{RROW(0, 1), RROW(0, 3)}, {RROW(0, 1), RROW(1, 3)}, {RROW(2, 1), RROW(2, 3)}};
 static const image_fn IBODY[3][2] = {{ibody<0, 1>, ibody<0, 3>}, {ibody<0, 1>, ibody<1, 3>}, {ibody<2, 1>, ibody<2, 3>}};
 
-static unsigned rnd_state = 12345;
-static unsigned rnd() { rnd_state = rnd_state * 1664525u + 1013904223u; return rnd_state >> 24; }
 
 // the source planes of a run, each in an allocation of its own that ends with the plane's last live byte
 struct Source {
@@ -179,7 +123,6 @@ static void make_source(Source& s, int fmt, int W, int H, int order, int B, int 
     }
 }
 
-static int runs = 0, failures = 0;
 struct Shape { int B, W, H, Nx, Ny; };
 
 static void run_resize(const Shape& sh, int fmt, int matrix, int order, int kind, int mode, bool f32, unsigned grid_y = 0)
@@ -193,10 +136,8 @@ static void run_resize(const Shape& sh, int fmt, int matrix, int order, int kind
     unsigned char* frames = (unsigned char*)fp;
     memset(frames, 0xEE, n * es);
     const YvArgs g = yv_geometry(yv_source(fmt, src.pl.p, src.pl.pitch, src.pl.stride, W, H, matrix, order, B), mode, frames, B, D, Nx, Ny);
-    unsigned* lds = (unsigned*)malloc(4 * (size_t)yv_lds_words(D, g.P, g.RB));     // exactly what the launcher asks for: LDS overruns show
     const resize_fn body = RBODY[fmt][D == 3][f32][mode];
-    launch((unsigned)(g.tx * g.ty), grid_y ? grid_y : (unsigned)B, [&] { body(g, lds); });
-    free(lds);
+    launch((unsigned)(g.tx * g.ty), grid_y ? grid_y : (unsigned)B, 1u, (size_t)yv_lds_words(D, g.P, g.RB), [&](unsigned* lds) { body(g, lds); });
     std::vector<unsigned char> px;
     std::vector<unsigned> want;
     convert_ref(fmt, src.pl, W, H, matrix, order, B, px);
@@ -232,7 +173,7 @@ static void run_image(int B, int W, int H, int fmt, int matrix, int order, int k
     unsigned char* image = alloc + off;
     const YiArgs g = yi_geometry(yv_source(fmt, src.pl.p, src.pl.pitch, src.pl.stride, W, H, matrix, order, B), fmt, image, pitch, stride, B);
     const image_fn body = IBODY[fmt][D == 3];
-    launch((unsigned)(g.gx * g.gy), grid_y ? grid_y : (unsigned)B, [&] { body(g); });
+    launch((unsigned)(g.gx * g.gy), grid_y ? grid_y : (unsigned)B, 1u, 0, [&](unsigned*) { body(g); });
     std::vector<unsigned char> px;
     convert_ref(fmt, src.pl, W, H, matrix, order, B, px);
     std::vector<unsigned char> want(off + extent, 0xEE);
@@ -308,7 +249,5 @@ int main()
         }
     for (int fmt = 0; fmt < 3; ++fmt)
         for (int mode = 0; mode < 2; ++mode) run_resize(Shape{5, 12, 10, 8, 8}, fmt, 0, 0, 2, mode, false, 2);   // a folded grid
-    if (failures) printf("%d of %d runs FAILED\n", failures, runs);
-    else printf("all %d runs exact\n", runs);
-    return failures ? 1 : 0;
+    return report();
 }
