@@ -49,6 +49,12 @@ class YuvDesc(C.Structure):
                 ("plane", C.c_void_p * 3), ("pitch", C.c_size_t * 3), ("stride", C.c_size_t * 3)]
 
 
+class YuvDst(C.Structure):
+    """include/aefft.h aefft_yuv_dst"""
+    _fields_ = [("format", C.c_int), ("matrix", C.c_int), ("W", C.c_int), ("H", C.c_int),
+                ("plane", C.c_void_p * 3), ("pitch", C.c_size_t * 3), ("stride", C.c_size_t * 3)]
+
+
 class TileDesc(C.Structure):
     """include/aefft.h aefft_tile_desc"""
     _fields_ = [("W", C.c_int), ("H", C.c_int), ("Nx", C.c_int), ("Ny", C.c_int),
@@ -102,6 +108,8 @@ SIGNATURES = {
     "aefft_tile_plan_make": (_i, [C.POINTER(TileDesc), C.POINTER(TilePlan)]),
     "aefft_image_tiles_to_frames": (_i, [_vp, _vp, C.c_size_t, C.c_size_t, C.POINTER(TileDesc), _vp, _i, _i, _i]),
     "aefft_frames_tiles_to_image": (_i, [_vp, _vp, _i, C.POINTER(TileDesc), _vp, C.c_size_t, C.c_size_t, _i, _i]),
+    "aefft_image_to_yuv": (_i, [_vp, _vp, C.c_size_t, C.c_size_t, _i, C.POINTER(YuvDst), _i]),
+    "aefft_frames_resize_to_yuv": (_i, [_vp, _vp, _i, _i, _i, _i, _i, C.POINTER(YuvDst), _i]),
     "aefft_net_create": (_i, [_vp, C.POINTER(NetDesc), C.POINTER(_vp)]),
     "aefft_net_create_ex": (_i, [_vp, C.POINTER(NetDesc), C.c_uint, C.POINTER(_vp)]),
     "aefft_net_destroy": (None, [_vp]),
@@ -298,6 +306,36 @@ def _yuv_source(planes, fmt, matrix, order, what):
         raise ValueError(f"{what}: W, H must be in 1..8192")
     desc.W, desc.H = W, H
     return desc, B, W, H, 1 if order == "gray" else 3, views
+
+
+def yuv_plane_shapes(fmt, B, W, H):
+    """the shapes of the plane tensors of B images of W x H luma samples, as yuv_to_image takes and image_to_yuv returns them"""
+    Wc, Hc = (W + 1) // 2, (H + 1) // 2
+    return {"nv12": [(B, H, W), (B, Hc, Wc, 2)], "i420": [(B, H, W), (B, Hc, Wc), (B, Hc, Wc)], "yuyv": [(B, H, W // 2, 4)]}[fmt]
+
+
+def _yuv_dest(fmt, matrix, order, B, W, H, D, out, what):
+    """the checks of the calls that WRITE YUV planes that need no device: fmt, matrix and order are known names, the source has the channels the
+    order names (D), W is even for yuyv, and `out` -- None, or the tuple of uint8 plane tensors to fill, laid out as _yuv_source takes them and of
+    yuv_plane_shapes(fmt, B, W, H) -- fits.  Returns the filled YuvDst (None without `out`) and the views it points into."""
+    if fmt not in YUV_FORMATS or matrix not in YUV_MATRICES or order not in YUV_ORDERS:
+        raise ValueError(f"{what}: fmt must be one of {sorted(YUV_FORMATS)}, matrix of {sorted(YUV_MATRICES)}, order of {sorted(YUV_ORDERS)}")
+    if D != (1 if order == "gray" else 3):
+        raise ValueError(f"{what}: order {order!r} names {1 if order == 'gray' else 3} channel(s), the source has {D}")
+    if min(W, H) < 1 or W > 8192 or H > 8192:
+        raise ValueError(f"{what}: W, H must be in 1..8192")
+    if fmt == "yuyv" and W % 2:
+        raise ValueError(f"{what}: yuyv needs an even W")
+    if out is None:
+        return None, []
+    src, b, w, h, _, views = _yuv_source(out, fmt, matrix, "bgr", f"{what}: out")      # (every plane of the format, whatever the order)
+    if (b, w, h) != (B, W, H):
+        raise ValueError(f"{what}: out must be the planes of {B} images of {W} x {H}: shapes {yuv_plane_shapes(fmt, B, W, H)}")
+    dst = YuvDst()
+    dst.format, dst.matrix, dst.W, dst.H = src.format, src.matrix, W, H
+    for k in range(3):
+        dst.plane[k], dst.pitch[k], dst.stride[k] = src.plane[k], src.pitch[k], src.stride[k]
+    return dst, views
 
 
 def heat_lut(D=3):
@@ -830,6 +868,42 @@ class Context:
         elif out.dtype not in (torch.uint8, torch.float32) or tuple(out.shape) != (B, D, Nx, Ny) or not out.is_contiguous():
             raise ValueError(f"{what}: out must be a contiguous uint8 or float32 tensor of shape {(B, D, Nx, Ny)}")
         self.check(self.L.aefft_yuv_resize_to_frames(self.h, C.byref(desc), YUV_ORDERS[order], RESIZE_MODES[mode], _ptr(out), int(_is_u8(out)), B, Nx, Ny))
+        return out
+
+    def _yuv_out_planes(self, fmt, matrix, order, B, W, H, D, out, what):
+        """(the planes to return, the YuvDst over them, the views it points into): `out`, or fresh contiguous planes"""
+        dst, keep = _yuv_dest(fmt, matrix, order, B, W, H, D, out, what)
+        if dst is None:
+            out = tuple(self.empty(*s, dtype=torch.uint8) for s in yuv_plane_shapes(fmt, B, W, H))
+            dst, keep = _yuv_dest(fmt, matrix, order, B, W, H, D, out, what)
+        return out, dst, keep
+
+    def image_to_yuv(self, image, fmt, matrix="bt601", order="bgr", out=None):
+        """Colour conversion on the device, the way out (aefft_image_to_yuv), the mirror of yuv_to_image: `image` is a uint8 device tensor
+        [B][H][W][D] (or [H][W][D]) laid out as image_resize_to_frames takes it, D = 3 for order "bgr" / "rgb" and 1 for "gray" (every chroma sample
+        128).  Returns, or fills `out` with, the tuple of plane tensors yuv_to_image takes -- fmt "nv12": (y [B][H][W], uv [B][Hc][Wc][2]); "i420":
+        (y, u [B][Hc][Wc], v); "yuyv": (yuyv [B][H][W/2][4],), W even -- `out` planes may be strided views into one encoder surface.  Luma per
+        pixel, chroma the rounded box average of its live pixels; all-integer arithmetic (include/aefft.h).  One launch, nothing waits for the
+        device."""
+        what = "Context.image_to_yuv"
+        img, pitch, stride = _resize_layout(image, what)
+        B, H, W, D = img.shape
+        out, dst, keep = self._yuv_out_planes(fmt, matrix, order, B, W, H, D, out, what)      # (keep: the views the descriptor points into)
+        self.check(self.L.aefft_image_to_yuv(self.h, _ptr(img), pitch, stride, YUV_ORDERS[order], C.byref(dst), B))
+        return out
+
+    def frames_resize_to_yuv(self, frames, size, fmt, matrix="bt601", order="bgr", mode="linear", out=None):
+        """SpinToImage_C + resize + colour conversion on the device in one launch (aefft_frames_resize_to_yuv): `frames` uint8 or float32
+        [B][D][Nx][Ny] as frames_resize_to_image takes them, size = (W, H) and mode as there; fmt, matrix, order and `out` as for image_to_yuv.
+        Returns, or fills `out` with, the plane tensors -- bit for bit frames_resize_to_image followed by image_to_yuv, without the image in
+        between.  Nothing waits for the device."""
+        what = "Context.frames_resize_to_yuv"
+        B, D, Nx, Ny = _frames4(frames, what)
+        if mode not in RESIZE_MODES:
+            raise ValueError(f"{what}: mode must be one of {sorted(RESIZE_MODES)}")
+        W, H = _two_ints(size, what, "size must be (W, H)")
+        out, dst, keep = self._yuv_out_planes(fmt, matrix, order, B, W, H, D, out, what)      # (keep: the views the descriptor points into)
+        self.check(self.L.aefft_frames_resize_to_yuv(self.h, _ptr(frames), int(_is_u8(frames)), Nx, Ny, RESIZE_MODES[mode], YUV_ORDERS[order], C.byref(dst), B))
         return out
 
     def set_flags(self, *names):

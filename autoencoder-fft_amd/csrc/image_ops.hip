@@ -183,7 +183,10 @@ static double yuv_bytes(const aefft_yuv_desc& s, int order)
 }
 // the source rules aefft_yuv_to_image and aefft_yuv_resize_to_frames share: `D` receives the channels the order asks for, `used` the planes the call
 // reads and `extent[k]` the bytes of plane k over the B images, first byte to last
-static int chk_yuv_source(const Bad& bad, const aefft_yuv_desc* src, int order, int B, int* D, int* used, size_t* extent)
+// (Desc: aefft_yuv_desc, or the aefft_yuv_dst of the calls that write the planes -- the same fields; `gray_luma_only`: GRAY uses plane[0] alone, which
+// holds for a source; `null_rule` words the planes the side needs; `one[k]`, where asked for, receives the bytes of ONE image's plane k)
+template <class Desc>
+static int chk_yuv_planes(const Bad& bad, const Desc* src, int order, int B, bool gray_luma_only, const char* null_rule, int* D, int* used, size_t* extent, size_t* one = nullptr)
 {
     if (src->format != AEFFT_YUV_NV12 && src->format != AEFFT_YUV_I420 && src->format != AEFFT_YUV_YUYV) return bad("format must be AEFFT_YUV_NV12, AEFFT_YUV_I420 or AEFFT_YUV_YUYV");
     if (src->matrix != AEFFT_YUV_BT601 && src->matrix != AEFFT_YUV_BT709 && src->matrix != AEFFT_YUV_JPEG) return bad("matrix must be AEFFT_YUV_BT601, AEFFT_YUV_BT709 or AEFFT_YUV_JPEG");
@@ -195,12 +198,17 @@ static int chk_yuv_source(const Bad& bad, const aefft_yuv_desc* src, int order, 
     const size_t W = (size_t)src->W, H = (size_t)src->H, Wc = (W + 1) / 2, Hc = (H + 1) / 2;
     // live bytes of a row and rows of each plane
     const size_t live[3] = {yuyv ? 2 * W : W, src->format == AEFFT_YUV_NV12 ? 2 * Wc : Wc, Wc}, rows[3] = {H, Hc, Hc};
-    *used = order == AEFFT_YUV_GRAY || yuyv ? 1 : (src->format == AEFFT_YUV_NV12 ? 2 : 3);
+    *used = (gray_luma_only && order == AEFFT_YUV_GRAY) || yuyv ? 1 : (src->format == AEFFT_YUV_NV12 ? 2 : 3);
     for (int k = 0; k < *used; ++k) {
-        if (!src->plane[k]) return bad("null plane (NV12 needs plane[0..1], I420 plane[0..2], YUYV and AEFFT_YUV_GRAY plane[0])");
+        if (!src->plane[k]) return bad(null_rule);
         RET_IF(chk_rows(bad, PLANE_WORDS, src->pitch[k], src->stride[k], live[k], rows[k], B, &extent[k]));
+        if (one) one[k] = (rows[k] - 1) * src->pitch[k] + live[k];
     }
     return AEFFT_OK;
+}
+static int chk_yuv_source(const Bad& bad, const aefft_yuv_desc* src, int order, int B, int* D, int* used, size_t* extent)
+{
+    return chk_yuv_planes(bad, src, order, B, true, "null plane (NV12 needs plane[0..1], I420 plane[0..2], YUYV and AEFFT_YUV_GRAY plane[0])", D, used, extent);
 }
 
 extern "C" int aefft_yuv_to_image(aefft_ctx* ctx, const aefft_yuv_desc* src, int order, unsigned char* image_d, size_t pitch, size_t image_stride, int B)
@@ -234,6 +242,79 @@ extern "C" int aefft_yuv_resize_to_frames(aefft_ctx* ctx, const aefft_yuv_desc* 
     RET_IF(join_recon(ctx));                          // (frames_d may be a buffer a deferred reconstruction is still writing)
     return launch_or_fail(ctx, KID_IMAGE, (double)B * (yuv_bytes(*src, order) + (double)(fb / (size_t)B)), "yuv_resize", [&] {
         return launch_yuv_resize(src->format, src->plane, src->pitch, src->stride, src->W, src->H, src->matrix, order, mode, frames_d, !frames_u8, B, Nx, Ny, ctx->cur);
+    });
+}
+
+// YUV video out (include/aefft.h "aefft_image_to_yuv, aefft_frames_resize_to_yuv") ---------------
+// two batches of B buffers each, buffer i at base + i * stride (ascending, not meeting one another: chk_rows), n bytes long: does any buffer of one
+// meet any of the other?  NV12 surfaces in a batch interleave -- surface b's chroma lies between the lumas of b and b + 1 --, so the batches' whole
+// extents say nothing; one sweep over both in address order does
+static bool batches_overlap(const void* a, size_t sa, size_t na, const void* b, size_t sb, size_t nb, int B)
+{
+    if (B == 1) sa = sb = 0;
+    if (!ranges_overlap(a, (size_t)(B - 1) * sa + na, b, (size_t)(B - 1) * sb + nb)) return false;
+    for (int i = 0, j = 0; i < B && j < B;) {
+        const uintptr_t a0 = reinterpret_cast<uintptr_t>(a) + (size_t)i * sa, b0 = reinterpret_cast<uintptr_t>(b) + (size_t)j * sb;
+        if (a0 < b0 + nb && b0 < a0 + na) return true;
+        if (a0 + na <= b0 + nb) ++i; else ++j;       // (the one that ends first cannot meet a later buffer of the other)
+    }
+    return false;
+}
+// the destination rules aefft_image_to_yuv and aefft_frames_resize_to_yuv share: chk_yuv_planes with every plane of the format needed (GRAY writes
+// 128 into the chroma) and the planes not meeting one another; `D` receives the channels the order names, `used` the planes the call writes and
+// `one[k]` the bytes of one image's plane k
+static int chk_yuv_dest(const Bad& bad, const aefft_yuv_dst* dst, int order, int B, int* D, int* used, size_t* one)
+{
+    size_t extent[3] = {0, 0, 0};
+    RET_IF(chk_yuv_planes(bad, dst, order, B, false, "null plane (NV12 needs plane[0..1], I420 plane[0..2], YUYV plane[0])", D, used, extent, one));
+    for (int k = 0; k < *used; ++k)
+        for (int l = k + 1; l < *used; ++l)
+            if (batches_overlap(dst->plane[k], dst->stride[k], one[k], dst->plane[l], dst->stride[l], one[l], B)) return bad("two destination planes' byte ranges overlap");
+    return AEFFT_OK;
+}
+// no destination plane meets the source: B buffers of src_one bytes, src_stride apart
+static int chk_yuv_dest_source(const Bad& bad, const aefft_yuv_dst* dst, int used, const size_t* one, int B, const void* src, size_t src_stride, size_t src_one)
+{
+    for (int k = 0; k < used; ++k)
+        if (batches_overlap(dst->plane[k], dst->stride[k], one[k], src, src_stride, src_one, B)) return bad("a destination plane and the source range overlap (the op is out-of-place)");
+    return AEFFT_OK;
+}
+// the bytes one image's conversion writes: every plane of the format
+static double yuv_dst_bytes(const aefft_yuv_dst& d)
+{
+    const double W = d.W, H = d.H, Wc = (d.W + 1) / 2, Hc = (d.H + 1) / 2;
+    return d.format == AEFFT_YUV_YUYV ? 2.0 * W * H : W * H + 2.0 * Wc * Hc;
+}
+
+extern "C" int aefft_image_to_yuv(aefft_ctx* ctx, const unsigned char* image_d, size_t pitch, size_t image_stride, int order, const aefft_yuv_dst* dst, int B)
+{
+    const Bad bad{ctx, "aefft_image_to_yuv"};
+    if (!ctx || !dst || !image_d) return bad("null context, descriptor or image");
+    int D = 0, used = 0;
+    size_t one[3] = {0, 0, 0}, extent = 0;
+    RET_IF(chk_yuv_dest(bad, dst, order, B, &D, &used, one));
+    RET_IF(chk_present_image(bad, pitch, image_stride, dst->W, dst->H, B, D, &extent));
+    RET_IF(chk_yuv_dest_source(bad, dst, used, one, B, image_d, image_stride, (size_t)(dst->H - 1) * pitch + (size_t)dst->W * D));
+    RET_IF(join_recon(ctx));                          // (image_d may hold a reconstruction that is still on the side stream)
+    return launch_or_fail(ctx, KID_IMAGE, (double)B * ((double)D * dst->W * dst->H + yuv_dst_bytes(*dst)), "image_to_yuv", [&] {
+        return launch_image_yuv(image_d, pitch, image_stride, order, dst->format, dst->plane, dst->pitch, dst->stride, dst->W, dst->H, dst->matrix, B, ctx->cur);
+    });
+}
+
+extern "C" int aefft_frames_resize_to_yuv(aefft_ctx* ctx, const void* frames_d, int frames_u8, int Nx, int Ny, int mode, int order, const aefft_yuv_dst* dst, int B)
+{
+    const Bad bad{ctx, "aefft_frames_resize_to_yuv"};
+    if (!ctx || !dst || !frames_d) return bad("null context, descriptor or frames");
+    int D = 0, used = 0;
+    size_t one[3] = {0, 0, 0}, fb = 0;
+    RET_IF(chk_yuv_dest(bad, dst, order, B, &D, &used, one));
+    RET_IF(chk_frame_size(bad, Nx, Ny));
+    RET_IF(chk_mode(bad, mode, Nx, Ny, dst->W, dst->H, "W <= Nx and H <= Ny"));
+    RET_IF(chk_frames_aligned16(bad, frames_d, "frames_d", "B", (size_t)B, D, Nx, Ny, frames_u8, &fb));
+    RET_IF(chk_yuv_dest_source(bad, dst, used, one, B, frames_d, fb / (size_t)B, fb / (size_t)B));
+    RET_IF(join_recon(ctx));                          // (frames_d may be the reconstruction of a step whose inverse transform is still on the side stream)
+    return launch_or_fail(ctx, KID_IMAGE, (double)fb + (double)B * yuv_dst_bytes(*dst), "frames_to_yuv", [&] {
+        return launch_frames_yuv(frames_d, !frames_u8, Nx, Ny, mode, order, dst->format, dst->plane, dst->pitch, dst->stride, dst->W, dst->H, dst->matrix, B, ctx->cur);
     });
 }
 

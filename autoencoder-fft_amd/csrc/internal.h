@@ -102,6 +102,16 @@ hipError_t launch_yuv_image(int fmt, const unsigned char* const* plane, const si
                             unsigned char* image, size_t ipitch, size_t istride, int B, hipStream_t st);
 hipError_t launch_yuv_resize(int fmt, const unsigned char* const* plane, const size_t* pitch, const size_t* stride, int W, int H, int matrix, int order,
                              int mode, void* frames, bool f32, int B, int Nx, int Ny, hipStream_t st);
+// ---- yuv_out_kernels.hip (aefft_image_to_yuv, aefft_frames_resize_to_yuv) ----
+// the way back: B interleaved images of W x H pixels (layout as launch_image_resize's source; order 0 BGR / 1 RGB / 2 GRAY, D = 3, 3, 1), or frames
+// [B][D][Nx][Ny] resized to W x H as launch_frames_resize does it, -> the integer conversion of include/aefft.h (matrix 0 BT601 / 1 BT709 / 2 JPEG,
+// chroma the rounded box average of its live pixels) -> every plane of format 0 NV12 / 1 I420 / 2 YUYV (plane k of image b at plane[k] + b * stride[k]),
+// one launch each, no intermediate image.  W, H, Nx, Ny in 1..8192, YUYV: W even; any alignment of image, planes, pitches and strides, frames
+// 16-byte aligned (hipErrorInvalidValue for what the kernels cannot serve; the C entry points check the rest).
+hipError_t launch_image_yuv(const unsigned char* image, size_t ipitch, size_t istride, int order, int fmt, unsigned char* const* plane, const size_t* pitch,
+                            const size_t* stride, int W, int H, int matrix, int B, hipStream_t st);
+hipError_t launch_frames_yuv(const void* frames, bool f32, int Nx, int Ny, int mode, int order, int fmt, unsigned char* const* plane, const size_t* pitch,
+                             const size_t* stride, int W, int H, int matrix, int B, hipStream_t st);
 // ---- tile_kernels.hip (aefft_tile_plan_make, aefft_image_tiles_to_frames, aefft_frames_tiles_to_image) ----
 // the plan of include/aefft.h from a description: false, and nothing written, for a null pointer or a value out of range
 bool tile_plan(const aefft_tile_desc* desc, aefft_tile_plan* plan);

@@ -479,6 +479,71 @@ int aefft_image_tiles_to_frames(aefft_ctx* ctx, const unsigned char* image_d, si
 int aefft_frames_tiles_to_image(aefft_ctx* ctx, const void* frames_d, int frames_u8, const aefft_tile_desc* desc,
                                 unsigned char* image_d, size_t pitch, size_t image_stride, int B, int D);
 
+/* aefft_image_to_yuv, aefft_frames_resize_to_yuv: video OUT, the mirror of aefft_yuv_to_image / aefft_yuv_resize_to_frames -- interleaved 8-bit
+ * images, or the planar frames a net writes, to the NV12 surface a hardware encoder takes, the I420 planes of a software encoder or the YUYV
+ * buffer of a V4L2 loopback or capture-card sink.  The reference's display path ends in SpinToImage_C + imshow (autoencoder.cpp:217-223); a
+ * deployed restorer ends in an encoder, and these two calls close decoder -> frames -> net -> frames -> encoder on the device.
+ * Destination: the descriptor below, read on the host during the call (it need not outlive it), with EXACTLY the plane layouts, pitches,
+ * ceil-sized chroma planes and odd sizes of aefft_yuv_desc above.  W x H is the luma size, each in 1..8192; Wc = ceil(W / 2), Hc = ceil(H / 2).
+ * plane[k] are device pointers of ANY alignment, pitch[k] the bytes per row; for B > 1 image b's plane k starts at plane[k] + b * stride[k]
+ * (ignored when B == 1), each stride at least (rows - 1) * pitch[k] + the live bytes of a row.
+ *   AEFFT_YUV_NV12  plane[0] Y: H rows, Y(x, y) at y * pitch[0] + x, pitch[0] >= W.  plane[1]: Hc rows, U at y' * pitch[1] + 2 x', V one byte
+ *                   behind, pitch[1] >= 2 Wc.  One surface, plane[1] = plane[0] + pitch * surface_height, is the normal case.
+ *   AEFFT_YUV_I420  plane[0] as NV12; plane[1] is U and plane[2] is V, each Hc rows of Wc bytes, pitch[k] >= Wc.  YV12: swap the two pointers.
+ *   AEFFT_YUV_YUYV  plane[0] only; W must be even.  Y(x, y) at y * pitch[0] + 2 x, U at y * pitch[0] + 4 (x >> 1) + 1, V two bytes further;
+ *                   pitch[0] >= 2 W.
+ * order names the channels of the image or frames: AEFFT_YUV_BGR, AEFFT_YUV_RGB (D = 3) or AEFFT_YUV_GRAY (D = 1).
+ * aefft_image_to_yuv reads B images with the source layout of aefft_image_resize_to_frames: pixel (row y, column x), channel d, at
+ * y * pitch + x * D + d; any alignment; pitch >= W * D; image b at b * image_stride, image_stride >= (H - 1) * pitch + W * D for B > 1.
+ * aefft_frames_resize_to_yuv reads frames [B][D][Nx][Ny], 16-byte aligned, 8-bit when frames_u8 != 0, float through px_u8 otherwise, and resizes
+ * them to W x H by `mode` with every rule of aefft_frames_resize_to_image (AEFFT_RESIZE_AREA requires W <= Nx and H <= Ny).
+ * Arithmetic: all-integer, 32 bits, defined bit for bit.  With R, G, B the pixel's channels, one luma sample per pixel:
+ *   Y = yoff + ((yr R + yg G + yb B + 2^19) >> 20)                      in 16..235 (0..255 for JPEG) without a clamp
+ * For a chroma sample let S_R, S_G, S_B be the channel sums over the n LIVE pixels it covers -- NV12 and I420: the block (2x'..2x'+1, 2y'..2y'+1)
+ * cut to the image, n = 4, 2 at an odd edge, 1 at the odd corner; YUYV: the pair (2x', 2x'+1) of one row, n = 2:
+ *   U = clamp(128 + ((ur S_R + ug S_G + ub S_B + (n << 19)) >> (20 + log2 n)), 0, 255)          V likewise with (vr, vg, vb)
+ * The shifts are arithmetic shifts, i.e. the floor.  This is the rounded box average of the block: the counterpart of the nearest (replicated)
+ * chroma that aefft_yuv_to_image reads; no interpolation and no siting offset.  Every magnitude stays below 2^30.
+ *   matrix            yoff  ky        Y: (r, g, b)                U: (r, g, b)                   V: (r, g, b)
+ *   AEFFT_YUV_BT601   16    900542    (269262, 528618, 102662)    (-155423, -305128, 460551)     (460551, -385654, -74897)
+ *   AEFFT_YUV_BT709   16    900542    (191455, 644068, 65019)     (-105533, -355018, 460551)     (460551, -418321, -42230)
+ *   AEFFT_YUV_JPEG    0     1048576   (313524, 615514, 119538)    (-176932, -347356, 524288)     (524288, -439026, -85262)
+ * Derivation, in double with q(k) = round(k 2^20), Kr, Kb, Kg as for the table above, s_y = 219 / 255 and s_c = 224 / 255 for the limited
+ * ranges, both 1 for JPEG:  ky = q(s_y), yr = q(Kr s_y), yb = q(Kb s_y), yg = ky - yr - yb;  ub = vr = q(s_c / 2),
+ * ur = q(-Kr s_c / (2 (1 - Kb))), vb = q(-Kb s_c / (2 (1 - Kr)));  ug = -(ur + ub), vg = -(vr + vb).  The G entries are the remainders, so the U
+ * and V rows sum to exactly 0 and the Y row to ky; each G entry is within 0.55 of its own rounding.
+ * AEFFT_YUV_GRAY: Y = yoff + ((ky g + 2^19) >> 20), which is g itself for JPEG, and every chroma sample is written as 128.  All planes of the
+ * format are always written.
+ * Consequences: an image with R = G = B gives U = V = 128 everywhere and the planes of the GRAY order; RGB is BGR with the channel rows swapped; a
+ * chroma block of four equal pixels gives what one pixel would; a constant image gives constant planes.  aefft_frames_resize_to_yuv is, for every
+ * accepted argument and bit for bit, aefft_frames_resize_to_image into a tight image followed by aefft_image_to_yuv -- in one launch with no
+ * intermediate image; with W == Nx and H == Ny both modes give aefft_frames_to_image -> aefft_image_to_yuv.
+ * Writes: bytes of a plane row beyond its live bytes are never written -- W for Y, 2 ceil(W / 2) for NV12 chroma, ceil(W / 2) for I420 chroma,
+ * 2 W for YUYV -- and nothing is read from the destination.  Stores are whole dwords when every used plane pointer, pitch and stride is a
+ * multiple of 4, bytes otherwise; both routes give the same bytes.
+ * Relation to OpenCV: cv::cvtColor's RGB -> YUV conversions have the same form (fixed-point, averaged chroma for the planar formats) with OpenCV's
+ * OWN constants; they are not the ones above.  Differences of a grey level are to be expected; the difference is unmeasured (OpenCV was not
+ * available to the build).
+ * Both calls: one launch on the context's stream; no host synchronisation, no allocation, no workspace; safe under stream capture.  Out-of-place.
+ * Accounted under the profile id `image` with the bytes read plus the bytes written: the B W H D image bytes or the B D Nx Ny frame elements,
+ * plus B times the plane samples (W H luma and 2 Wc Hc chroma; YUYV 2 W H).
+ * AEFFT_EINVAL, with aefft_last_error starting with the call's name ("aefft_image_to_yuv: ", "aefft_frames_resize_to_yuv: ") and naming the rule,
+ * nothing enqueued and every output untouched: a null context, descriptor, source or needed plane; an unknown format, matrix, order or mode; a
+ * size or B out of range; YUYV with an odd W; a pitch or stride below the plane's live extent; an image pitch or stride that is too small; AREA
+ * with an enlarging axis; frames_d not 16-byte aligned; any two destination planes' byte ranges overlapping each other (image by image: the
+ * surfaces of a batch may interleave); any destination plane overlapping the source; sizes that overflow the address space. */
+typedef struct {
+    int format, matrix;                /* AEFFT_YUV_NV12 / I420 / YUYV; AEFFT_YUV_BT601 / BT709 / JPEG -- the enums above */
+    int W, H;                          /* luma size; 1..8192 */
+    unsigned char* plane[3];           /* device pointers, ANY alignment */
+    size_t pitch[3];                   /* bytes per row of each plane */
+    size_t stride[3];                  /* image b's plane k starts at plane[k] + b * stride[k]; ignored when B == 1 */
+} aefft_yuv_dst;
+int aefft_image_to_yuv(aefft_ctx* ctx, const unsigned char* image_d, size_t pitch, size_t image_stride, int order,
+                       const aefft_yuv_dst* dst, int B);
+int aefft_frames_resize_to_yuv(aefft_ctx* ctx, const void* frames_d, int frames_u8, int Nx, int Ny, int mode, int order,
+                               const aefft_yuv_dst* dst, int B);
+
 /* ---- network level: the resident, batched form of autoenc_fft / backprop_fft ------------------ */
 typedef struct {
     int D, Nx, Ny;        /* input frames [B][D][Nx][Ny] */
