@@ -10,31 +10,16 @@ import torch
 
 import np_ref as R
 import np_spatial as S
-from test_gpu_fft_path import host, relerr
-from test_gpu_sizes import _weights
-from test_gpu_infer import CASES, _LIVE, _case, _infer, _net, _rule, _scales, _track
+import frozen_cases as F
+from frozen_cases import CASES, PATHS, _case, _rule, _scales, _weights, host, relerr
+from frozen_cases import ctx, _close_nets  # noqa: F401  (fixtures: the module's context, and every tracked net closed behind each test)
+from test_gpu_infer import _infer, _train_streamed
 
 aefft = importlib.import_module("autoencoder-fft_amd")
 pytestmark = pytest.mark.gpu
 
 TOL = 1e-4      # the project's bound on the step's and the inference's reconstruction (test_gpu_infer.TOL)
-PATHS = ["", "NOOPFORM", "NOCHAIN", "NOOVERLAP", "GTAPS"]
 DECODE_CASES = ["64-1pair", "64-2pairs", "64-4pairs", "256-4pairs", "cfg2", "no-pooling", "640x480", "640x480-opform", "5x3", "D4", "tied"]
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    c = aefft.Context(0)
-    yield c
-    c.close()
-
-
-@pytest.fixture(autouse=True)
-def _close_nets(ctx):
-    """every net of a test is destroyed before the module's context is, also when an assertion ends the test early"""
-    yield
-    while _LIVE:
-        _LIVE.pop().close()
 
 
 def _decode_oracle(code, ws, scales, l):
@@ -99,7 +84,7 @@ def _want_form(name, path):
 @pytest.mark.parametrize("name", DECODE_CASES)
 def test_decode_against_the_oracle(ctx, flags, name, path):
     flags(path)
-    net = _net(ctx, name)
+    net = F.net(ctx, name)
     assert net.step_form() == _want_form(name, path)
     L = len(CASES[name][3])
     for rnd in range(2):            # the second pass over the pairs: every operator formed again after another pair's
@@ -124,7 +109,7 @@ def test_hidden_layers_narrower_than_the_input(ctx, flags, maps, scales, path, f
     D, N, B, L = 3, 64, 2, len(maps)
     rng = np.random.default_rng(7 + sum(maps) + L)
     ws = _weights(rng, D, maps, 3, 3)
-    net = _track(aefft.Net(ctx, D, N, N, maps, 3, scales, batch=B))
+    net = F.track(aefft.Net(ctx, D, N, N, maps, 3, scales, batch=B))
     for l, w in enumerate(ws):
         net.set_pair(l, *w)
     assert net.step_form() == form
@@ -148,7 +133,7 @@ def test_round_trip(ctx, flags, name):
     flags()
     ws, xs = _case(name)
     frames = ctx.dev(xs[0])
-    net = _net(ctx, name)
+    net = F.net(ctx, name)
     for l in range(len(ws)):
         g = net.dims[l]
         rec = ctx.empty(net.B, net.D, net.Nx, net.Ny); rec.fill_(float("nan"))
@@ -174,7 +159,7 @@ def test_u8_output_rule_is_exact(ctx, flags, Nx, Ny, smooth):
     B, D, maps, s = 2, 3, [4, 3], 2
     L = len(maps)
     rng = np.random.default_rng(Nx + Ny)
-    mk = lambda: _track(aefft.Net(ctx, D, Nx, Ny, maps, 3, s, batch=B, smooth_sizes=smooth, operator_form=smooth))
+    mk = lambda: F.track(aefft.Net(ctx, D, Nx, Ny, maps, 3, s, batch=B, smooth_sizes=smooth, operator_form=smooth))
     shape = lambda l: (B, maps[l], Nx // s ** (l + 1), Ny // s ** (l + 1))
     # (a) constant planes: zero decoder kernels of pair 0 leave recon[d] = p_0[d] / s^2 whatever the code holds.  Built on the CPU first: the
     # candidates that survive the library's float32 scale 1/(Nx Ny) exactly -- one below 0, one above 255, one exactly on .5 inside
@@ -226,36 +211,18 @@ def test_u8_output_rule_is_exact(ctx, flags, Nx, Ny, smooth):
 # ------------------------------------------------------------------------------------------
 # 4. training is undisturbed
 # ------------------------------------------------------------------------------------------
-def _train(ctx, name, with_decode, ready):
-    """three steps issued back to back, nothing between the calls that waits for the device or asks for the deferred MSE sums; with_decode:
-    [step, decode, step, decode(8-bit, another pair), step]"""
-    ws, xs = _case(name)
-    D, Nx, Ny, maps, *_ = CASES[name]
-    L = len(maps)
-    net = _net(ctx, name)
-    if ready:
-        net.set_input_ready(True)
-    steps = [ctx.dev(xs[0]), ctx.dev(xs[1]), ctx.dev(xs[0])]
+def _decode_streamed(name, ctx, net, steps):
+    """[step, decode, step, decode(8-bit, another pair), step]"""
+    L = net.npairs
     codes = [ctx.dev(_codes(name, 0)[0]), ctx.dev(_codes(name, L - 1)[0])]
-    recons = [ctx.empty(net.B, D, Nx, Ny) for _ in steps]
-    img32, img8 = ctx.empty(net.B, D, Nx, Ny), ctx.empty(net.B, D, Nx, Ny, dtype=torch.uint8)
-    gbuf = net.grad_buffer()
-    grads = [torch.empty_like(gbuf) for _ in steps]
-    ctx.sync()
-    for k, x in enumerate(steps):
-        net.step_grad(x, recons[k])
-        grads[k].copy_(gbuf)                      # (in stream order: the gradients, and the MSE tail the previous step's sums rode in on)
-        net.step_apply(0.02)                      # mse = None: the sums stay deferred
-        if with_decode and k == 0:
-            net.decode(codes[0], 0, img32)        # straight behind step_apply, straight in front of the next step_grad
-        if with_decode and k == 1:
+    img32, img8 = ctx.empty(net.B, net.D, net.Nx, net.Ny), ctx.empty(net.B, net.D, net.Nx, net.Ny, dtype=torch.uint8)
+
+    def hook(k, x):
+        if k == 0:
+            net.decode(codes[0], 0, img32)
+        if k == 1:
             net.decode(codes[1], L - 1, img8)
-    ctx.sync()
-    mse = ctx.empty(L); net.last_mse(mse); ctx.sync()
-    out = [host(r).copy() for r in recons] + [host(g).copy() for g in grads] + [host(mse).copy()]
-    out += [a for l in range(L) for a in net.get_pair(l)]
-    net.close()
-    return out
+    return hook
 
 
 @pytest.mark.parametrize("ready", [False, True])
@@ -265,9 +232,10 @@ def test_training_is_not_disturbed(ctx, flags, name, path, form, ready):
     """[step, decode, step, decode, step] against [step, step, step]: reconstructions, packed gradients with their MSE tail, MSEs and
     weights bit for bit"""
     flags(path)
-    assert _net(ctx, name).step_form() == form
-    plain = _train(ctx, name, False, ready)
-    mixed = _train(ctx, name, True, ready)
+    assert F.net(ctx, name).step_form() == form
+    setup = functools.partial(_decode_streamed, name)
+    plain = _train_streamed(ctx, name, ready, setup, False)
+    mixed = _train_streamed(ctx, name, ready, setup, True)
     assert len(plain) == len(mixed)
     for i, (a, b) in enumerate(zip(plain, mixed)):
         assert np.array_equal(a, b), i
@@ -278,14 +246,6 @@ def test_training_is_not_disturbed(ctx, flags, name, path, form, ready):
 # ------------------------------------------------------------------------------------------
 # 5. the cache, by launch counts
 # ------------------------------------------------------------------------------------------
-def _counted(ctx, net, code, l):
-    ctx.prof_enable(); ctx.prof_reset()
-    out = _decode(ctx, net, code, l)
-    counts = {k: v["launches"] for k, v in ctx.prof_read().items()}
-    ctx.prof_enable(False)
-    return out, counts
-
-
 @pytest.mark.parametrize("path", ["", "NOCHAIN"])
 def test_the_operator_is_cached_until_the_weights_or_the_pair_change(ctx, flags, path):
     """`moment` (the operator-form helpers' id) counts decode_op (1, when the operator is formed) and decode_apply (1)"""
@@ -294,9 +254,10 @@ def test_the_operator_is_cached_until_the_weights_or_the_pair_change(ctx, flags,
     ws, _ = _case(name)
     L = len(ws)
     s = _scales(CASES[name][6], L)
-    net = _net(ctx, name)
+    net = F.net(ctx, name)
     code1, ref1 = _codes(name, 1)
     code2, ref2 = _codes(name, 2)
+    _counted = lambda ctx, net, code, l: F.counted(ctx, lambda: _decode(ctx, net, code, l))
 
     def cached(c):
         assert c["moment"] == 1 and c["chain"] == 0 and c["kspec"] == 0 and c["contract"] == 0, c
@@ -341,7 +302,7 @@ def test_argument_errors_and_state(ctx, flags):
     name = "64-2pairs"
     ws, xs = _case(name)
     L = len(ws)
-    net = _net(ctx, name)
+    net = F.net(ctx, name)
     frames = ctx.dev(xs[0])
     rec = ctx.empty(net.B, net.D, net.Nx, net.Ny)
     pad = ctx.empty(rec.numel() + 4)
@@ -394,7 +355,7 @@ def test_spatial_net(ctx, flags):
     flags()
     rng = np.random.default_rng(3)
     D, N, maps, B, s = 3, 64, [4, 6], 2, 2
-    net = _track(aefft.Net(ctx, D, N, N, maps, 3, s, B, spatial=True))
+    net = F.track(aefft.Net(ctx, D, N, N, maps, 3, s, B, spatial=True))
     ws = _weights(rng, D, maps, 3, 3)
     for l, w in enumerate(ws):
         net.set_pair(l, *w)

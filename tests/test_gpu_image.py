@@ -9,9 +9,8 @@ import numpy as np
 import pytest
 import torch
 
-import test_gpu_infer as TI
-from test_gpu_fft_path import host
-from test_gpu_sizes import _weights
+from frozen_cases import _rule, _weights, host, track
+from frozen_cases import ctx, _close_nets  # noqa: F401  (fixtures: the module's context, and every tracked net closed behind each test)
 
 aefft = importlib.import_module("autoencoder-fft_amd")
 pytestmark = pytest.mark.gpu
@@ -22,23 +21,6 @@ SHAPES = [(1, 1, 8, 8), (2, 3, 10, 12), (3, 3, 66, 34), (1, 3, 130, 70), (2, 4, 
 PITCHES = ["tight", "pad64", "odd"]
 TAIL = 96          # bytes of the allocation behind the last image row
 PAD = 0xA5
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    c = aefft.Context(0)
-    yield c
-    c.close()
-
-
-_LIVE = []
-
-
-@pytest.fixture(autouse=True)
-def _close_nets(ctx):
-    yield
-    while _LIVE:
-        _LIVE.pop().close()
 
 
 def _layout(shape, kind):
@@ -169,7 +151,7 @@ def test_pack_of_float_frames_applies_spin_to_image(ctx, shape, kind):
     rng = np.random.default_rng(sum(shape) + 13 * len(kind))
     with np.errstate(invalid="ignore"):
         frames_h = _edge_values(rng, B * D * Nx * Ny).reshape(B, D, Nx, Ny)
-        want_px = np.ascontiguousarray(TI._rule(frames_h).transpose(0, 3, 2, 1))
+        want_px = np.ascontiguousarray(_rule(frames_h).transpose(0, 3, 2, 1))
         if B * D * Nx * Ny >= 2000:
             assert np.isnan(frames_h).any() and np.isinf(frames_h).any() and (frames_h % 1 == 0.5).sum() >= 250
     _pack_and_check(ctx, frames_h, want_px, shape, kind)
@@ -184,8 +166,7 @@ B_NET = 2
 
 def _small_net(ctx, name, seed=3):
     D, Nx, Ny, smooth = NETS[name]
-    net = aefft.Net(ctx, D, Nx, Ny, [2], 3, 1, batch=B_NET, smooth_sizes=smooth)
-    _LIVE.append(net)
+    net = track(aefft.Net(ctx, D, Nx, Ny, [2], 3, 1, batch=B_NET, smooth_sizes=smooth))
     for l, w in enumerate(_weights(np.random.default_rng(seed), D, [2], 3, 3)):
         net.set_pair(l, *w)
     return net

@@ -1,105 +1,22 @@
 """aefft_net_infer (Net.infer): frozen-weight inference over a batch -- reconstruction and every hidden pair's layer against the float64
 oracle in every form and route, infer == forward, the 8-bit output rule exactly on every row-pass route, 8-bit input bit for bit,
 training undisturbed bit for bit, the operator cache by the profiler's launch counts, layer exports, the spatial net and the errors."""
-import functools
 import importlib
 
 import numpy as np
 import pytest
 import torch
 
-import np_ref as R
-from test_gpu_fft_path import host, relerr
-from test_gpu_sizes import _weights
+import frozen_cases as F
+from frozen_cases import CASES, PATHS, _case, _oracle, _oracle_layers, _rule, _scales, _weights, host, relerr
+from frozen_cases import ctx, _close_nets  # noqa: F401  (fixtures: the module's context, and every tracked net closed behind each test)
 
 aefft = importlib.import_module("autoencoder-fft_amd")
 pytestmark = pytest.mark.gpu
 
 TOL = 1e-4      # the bound _check_two_steps holds the step's reconstruction to
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    c = aefft.Context(0)
-    yield c
-    c.close()
-
-
-_LIVE = []
-
-
-def _track(net):
-    _LIVE.append(net)
-    return net
-
-
-@pytest.fixture(autouse=True)
-def _close_nets(ctx):
-    """every net of a test is destroyed before the module's context is, also when an assertion ends the test early (a net that outlives
-    its context is destroyed by the garbage collector through a dangling context pointer)"""
-    yield
-    while _LIVE:
-        _LIVE.pop().close()
-
-
-# name: D, Nx, Ny, maps, Nk, Nl, scale, B, smooth_sizes, operator_form, tied, the form under the default switches
-CASES = {
-    "64-1pair": (3, 64, 64, [4], 5, 5, 2, 2, False, False, False, "operator_chain"),
-    "64-2pairs": (3, 64, 64, [4, 3], 5, 5, 2, 3, False, False, False, "operator_chain"),
-    "64-4pairs": (3, 64, 64, [4, 3, 4, 2], 3, 3, [2, 2, 1, 1], 2, False, False, False, "operator_chain"),
-    "256-1pair": (3, 256, 256, [4], 5, 5, 2, 2, False, False, False, "operator_chain"),
-    "256-2pairs": (1, 256, 256, [3, 4], 3, 3, 2, 2, False, False, False, "operator_chain"),
-    "256-4pairs": (3, 256, 256, [4, 3, 4, 2], 5, 5, 2, 2, False, False, False, "operator_chain"),
-    "cfg2": (3, 256, 256, [8, 16, 32], 5, 5, 2, 1, False, False, False, "operator_chain"),
-    # 8*3*512*257*8 B = 25 MB > 16 MB: the expand route (and a coarsest grid beyond the chain launch's 16384 bins)
-    "no-pooling": (3, 512, 512, [4], 5, 5, 1, 8, False, False, False, "operator"),
-    "640x480": (3, 640, 480, [4, 3], 5, 5, 2, 2, True, False, False, "per_frame"),
-    "640x480-opform": (3, 640, 480, [4, 3], 5, 5, 2, 2, True, True, False, "operator_chain"),
-    "240x320": (3, 240, 320, [4, 3], 3, 3, 2, 2, True, False, False, "per_frame"),
-    "240x320-opform": (3, 240, 320, [4, 3], 3, 3, 2, 2, True, True, False, "operator_chain"),
-    "5x3": (3, 64, 64, [4, 3], 5, 3, 2, 2, False, False, False, "per_frame"),
-    "D4": (4, 64, 64, [4, 3], 5, 5, 2, 2, False, False, False, "per_frame"),
-    "tied": (3, 64, 64, [4, 3], 5, 5, 2, 2, False, False, True, "operator_chain"),
-}
-PATHS = ["", "NOOPFORM", "NOCHAIN", "NOOVERLAP", "GTAPS"]
-
-
-def _scales(s, L):
-    return [s] * L if isinstance(s, int) else list(s)
-
-
-@functools.lru_cache(maxsize=None)
-def _case(name):
-    D, Nx, Ny, maps, Nk, Nl, s, B, *_rest, tied, _form = CASES[name]
-    rng = np.random.default_rng(sum(map(ord, name)))
-    ws = _weights(rng, D, maps, Nk, Nl)
-    if tied:        # decoder kernels are the encoder's, transposed over the channel pair
-        ws = [(c, b, np.ascontiguousarray(c.transpose(1, 0, 2, 3)), p) for c, b, f, p in ws]
-    xs = [np.floor(rng.uniform(0, 256, (B, D, Nx, Ny))) for _ in range(2)]
-    return ws, xs
-
-
-def _oracle_layers(x, ws, scales):
-    """np_ref.autoenc_fft (float64) of one frame: the list of layers 0..4L"""
-    L = len(ws)
-    net_c = [w[0] for w in ws] + [w[2] for w in ws[::-1]]
-    net_b = [w[1] for w in ws] + [w[3] for w in ws[::-1]]
-    return R.autoenc_fft(x, net_c, net_b, list(scales) + [-v for v in scales[::-1]])[0]
-
-
-@functools.lru_cache(maxsize=None)
-def _oracle(name, k=0):
-    ws, xs = _case(name)
-    s = _scales(CASES[name][6], len(ws))
-    return [_oracle_layers(x, ws, s) for x in xs[k]]
-
-
-def _net(ctx, name, ws=None):
-    D, Nx, Ny, maps, Nk, Nl, s, B, smooth, opform, *_ = CASES[name]
-    net = _track(aefft.Net(ctx, D, Nx, Ny, maps, Nk, s, batch=B, Nl=Nl, smooth_sizes=smooth, operator_form=opform))
-    for l, w in enumerate(ws if ws is not None else _case(name)[0]):
-        net.set_pair(l, *w)
-    return net
+ORDER = ["64-1pair", "64-2pairs", "64-4pairs", "256-1pair", "256-2pairs", "256-4pairs", "cfg2", "no-pooling", "640x480", "640x480-opform", "240x320",
+         "240x320-opform", "5x3", "D4", "tied"]
 
 
 def _infer(ctx, net, frames, pair=None, recon=True, u8=False):
@@ -134,10 +51,10 @@ def _check_against_oracle(ctx, net, name, k=0):
 # 1. against the oracle
 # ------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("path", PATHS)
-@pytest.mark.parametrize("name", list(CASES))
+@pytest.mark.parametrize("name", ORDER)
 def test_infer_against_the_oracle(ctx, flags, name, path):
     flags(path)
-    net = _net(ctx, name)
+    net = F.net(ctx, name)
     want = CASES[name][-1]
     if path == "NOOPFORM":
         want = "per_frame"
@@ -159,7 +76,7 @@ def test_infer_equals_forward(ctx, flags, name):
     ws, xs = _case(name)
     D, Nx, Ny, maps, *_ = CASES[name]
     frames = ctx.dev(xs[0])
-    net = _net(ctx, name)
+    net = F.net(ctx, name)
     rec_f = ctx.empty(net.B, D, Nx, Ny)
     net.forward(frames, rec_f)
     layers_f = [host(t).copy() for t in net.get_layers()]
@@ -181,13 +98,6 @@ def test_infer_equals_forward(ctx, flags, name):
 # ------------------------------------------------------------------------------------------
 # 3. the 8-bit output rule, exactly, on every row-pass route
 # ------------------------------------------------------------------------------------------
-def _rule(v):
-    """SpinToImage_C: clamp((int)round(v), 0, 255), halves away from zero, NaN -> 0"""
-    v = np.asarray(v, np.float64)
-    r = np.where(v >= 0, np.floor(v + 0.5), -np.floor(-v + 0.5))
-    return np.clip(np.nan_to_num(r, nan=0.0), 0, 255).astype(np.uint8)
-
-
 # the power-of-two row pass: every N of RowCfg, dense (no pooling) and -- N >= 128, Wc <= N/16 -- sparse (pooling by 8);
 # the mixed-radix row pass: one size per thread class T = 16 .. 256 (N <= 8 T), Wc = N/2 and Wc < N/2
 ROW_ROUTES = ([("pow2-dense", 16, n, 1) for n in (8, 16, 32, 64, 128, 256, 512, 1024, 2048)] +
@@ -210,7 +120,7 @@ def test_u8_output_rule_is_exact(ctx, flags, route, Nx, Ny, s):
     keep = [v for v in HALVES if np.float32(np.float32(v) * N) * inv == np.float32(v)]
     assert any(v < 0 for v in keep) and any(v > 255 for v in keep) and any(v > 0 and v % 1 == 0.5 for v in keep), keep
     D = len(keep)
-    net = _track(aefft.Net(ctx, D, Nx, Ny, [2], 3, s, batch=B, smooth_sizes=smooth))
+    net = F.track(aefft.Net(ctx, D, Nx, Ny, [2], 3, s, batch=B, smooth_sizes=smooth))
     z = lambda *sh: np.zeros(sh)
     net.set_pair(0, z(2, D, 3, 3), z(2), z(D, 2, 3, 3), np.array(keep) * s * s)
     frames = ctx.dev(np.floor(rng.uniform(0, 256, (B, D, Nx, Ny))))
@@ -224,7 +134,7 @@ def test_u8_output_rule_is_exact(ctx, flags, route, Nx, Ny, s):
     # ramp under the noise (pooling keeps it), the float64 oracle's image r0 of frame 0 with p = 0, and -- the image being linear in f and p (which enters as p / s^2) --
     # the decoder scaled per channel so that frame 0's image spans [-128, 384]
     D = 3
-    net = _track(aefft.Net(ctx, D, Nx, Ny, [2], 3, s, batch=B, smooth_sizes=smooth))
+    net = F.track(aefft.Net(ctx, D, Nx, Ny, [2], 3, s, batch=B, smooth_sizes=smooth))
     c, b, f, p = _weights(rng, D, [2], 3, 3)[0]
     ramp = np.add.outer(np.arange(Nx) / (Nx - 1.0), np.arange(Ny) / (Ny - 1.0)) / 2
     px = np.floor(255.0 * (0.75 * ramp + 0.25 * rng.uniform(0, 1, (B, D, Nx, Ny))))
@@ -255,7 +165,7 @@ def test_u8_frames_give_the_float_frames_results_bit_for_bit(ctx, flags, name):
     """(640 x 480: the mixed-radix row pass converts 8-bit pixels on load as well -- the smooth case the header's sentence is pinned by)"""
     flags()
     ws, xs = _case(name)
-    net = _net(ctx, name)
+    net = F.net(ctx, name)
     f32 = ctx.dev(xs[0])
     u8 = torch.as_tensor(xs[0].astype(np.uint8), device=f32.device)
     for l in range(len(ws)):
@@ -271,32 +181,14 @@ def test_u8_frames_give_the_float_frames_results_bit_for_bit(ctx, flags, name):
 # ------------------------------------------------------------------------------------------
 # 5. training is undisturbed
 # ------------------------------------------------------------------------------------------
-def _train(ctx, name, with_infer, ready):
-    ws, xs = _case(name)
-    D, Nx, Ny, maps, *_ = CASES[name]
-    L = len(maps)
-    net = _net(ctx, name)
-    if ready:
-        net.set_input_ready(True)
-    rng = np.random.default_rng(5)
-    steps = [ctx.dev(xs[0]), ctx.dev(xs[1]), ctx.dev(xs[0])]
-    others = [ctx.dev(np.floor(rng.uniform(0, 256, xs[0].shape))) for _ in range(2)]
-    ctx.sync()
-    out = []
-    for k, x in enumerate(steps):
-        recon = ctx.empty(net.B, D, Nx, Ny)
-        net.step_grad(x, recon)
-        ctx.sync()
-        g = host(net.grad_buffer()).copy()
-        net.step_apply(0.02)
-        ctx.sync()
-        mse = ctx.empty(L); net.last_mse(mse); ctx.sync()
-        out.append((host(recon).copy(), g, host(mse).copy(), [net.get_pair(l) for l in range(L)]))
-        if with_infer and k < 2:
-            _infer(ctx, net, steps[k] if k == 0 else others[k], k % L, u8=bool(k))
-    tail = host(net.grad_buffer()).copy()
-    net.close()
-    return out, tail
+def _infer_between(ctx, net, steps):
+    """behind the first step its own frames and pair 0, behind the second other frames, pair 1 % L and the 8-bit output"""
+    others = [ctx.dev(o) for o in F.other_frames(steps[0].shape)]
+
+    def hook(k, x):
+        if k < 2:
+            _infer(ctx, net, x if k == 0 else others[k], k % net.npairs, u8=bool(k))
+    return hook
 
 
 @pytest.mark.parametrize("ready", [False, True])
@@ -306,34 +198,24 @@ def test_training_is_not_disturbed(ctx, flags, name, path, form, ready):
     """[step, step, step] against [step, infer, step, infer(other frames), step]: reconstructions, packed gradients with their MSE tail,
     MSEs and weights after every step bit for bit (the momenta enter the next step's weights: there is no accessor of their own)"""
     flags(path)
-    plain, tail_p = _train(ctx, name, False, ready)
-    mixed, tail_m = _train(ctx, name, True, ready)
-    for k, (a, b) in enumerate(zip(plain, mixed)):
-        assert np.array_equal(a[0], b[0]), (k, "recon")
-        assert np.array_equal(a[1], b[1]), (k, "grads")
-        assert np.array_equal(a[2], b[2]), (k, "mse")
-        for l, (wa, wb) in enumerate(zip(a[3], b[3])):
-            for u, v in zip(wa, wb):
-                assert np.array_equal(u, v), (k, l)
-    assert np.array_equal(tail_p, tail_m)
+    plain = F.train(ctx, name, ready, _infer_between)
+    mixed = F.train(ctx, name, ready, _infer_between, at="readback")
+    F.assert_same_training(plain, mixed)
 
 
-def _train_streamed(ctx, name, with_infer, ready):
+def _train_streamed(ctx, name, ready, setup, mixed):
     """three steps with nothing between the calls that waits for the device or asks for the deferred MSE sums: every buffer exists up front,
-    the packed buffer is copied on the library's stream, and results are read back after the last step alone"""
+    the packed buffer is copied on the library's stream, and results are read back after the last step alone.  setup(ctx, net, steps) makes
+    the buffers of the interleaved calls, in both runs, and returns hook(k, x); mixed: it runs straight behind step_apply, straight in front
+    of the next step_grad"""
     ws, xs = _case(name)
-    D, Nx, Ny, maps, *_ = CASES[name]
-    L = len(maps)
-    net = _net(ctx, name)
+    L = len(ws)
+    net = F.net(ctx, name)
     if ready:
         net.set_input_ready(True)
-    rng = np.random.default_rng(5)
     steps = [ctx.dev(xs[0]), ctx.dev(xs[1]), ctx.dev(xs[0])]
-    other = torch.as_tensor(np.floor(rng.uniform(0, 256, xs[0].shape)).astype(np.uint8), device=steps[0].device)
-    recons = [ctx.empty(net.B, D, Nx, Ny) for _ in steps]
-    img32, img8 = ctx.empty(net.B, D, Nx, Ny), ctx.empty(net.B, D, Nx, Ny, dtype=torch.uint8)
-    g0, g1 = net.dims[0], net.dims[L - 1]
-    hid0, hid1 = ctx.empty(net.B, g0["dM"], g0["Nx"], g0["Ny"]), ctx.empty(net.B, g1["dM"], g1["Nx"], g1["Ny"])
+    recons = [ctx.empty(net.B, net.D, net.Nx, net.Ny) for _ in steps]
+    hook = setup(ctx, net, steps)
     gbuf = net.grad_buffer()
     grads = [torch.empty_like(gbuf) for _ in steps]
     ctx.sync()
@@ -341,16 +223,29 @@ def _train_streamed(ctx, name, with_infer, ready):
         net.step_grad(x, recons[k])
         grads[k].copy_(gbuf)                      # (in stream order: the gradients, and the MSE tail the previous step's sums rode in on)
         net.step_apply(0.02)                      # mse = None: the sums stay deferred
-        if with_infer and k == 0:
-            net.infer(x, img32, 0, hid0)          # straight behind step_apply, straight in front of the next step_grad
-        if with_infer and k == 1:
-            net.infer(other, img8, L - 1, hid1)
+        if mixed:
+            hook(k, x)
     ctx.sync()
     mse = ctx.empty(L); net.last_mse(mse); ctx.sync()
     out = [host(r).copy() for r in recons] + [host(g).copy() for g in grads] + [host(mse).copy()]
     out += [a for l in range(L) for a in net.get_pair(l)]
     net.close()
     return out
+
+
+def _infer_streamed(ctx, net, steps):
+    L = net.npairs
+    other = F.u8(ctx, F.other_frames(steps[0].shape)[0], steps[0])
+    img32, img8 = ctx.empty(net.B, net.D, net.Nx, net.Ny), ctx.empty(net.B, net.D, net.Nx, net.Ny, dtype=torch.uint8)
+    g0, g1 = net.dims[0], net.dims[L - 1]
+    hid0, hid1 = ctx.empty(net.B, g0["dM"], g0["Nx"], g0["Ny"]), ctx.empty(net.B, g1["dM"], g1["Nx"], g1["Ny"])
+
+    def hook(k, x):
+        if k == 0:
+            net.infer(x, img32, 0, hid0)
+        if k == 1:
+            net.infer(other, img8, L - 1, hid1)
+    return hook
 
 
 @pytest.mark.parametrize("ready", [False, True])
@@ -361,9 +256,9 @@ def test_training_is_not_disturbed_without_synchronisation(ctx, flags, name, pat
     reach the next step's packed-buffer tail through its gradient launch, across the infer) and, with set_input_ready(1), while the next
     step's input transform may run ahead on its side stream into the other input-spectra buffer"""
     flags(path)
-    assert _net(ctx, name).step_form() == form
-    plain = _train_streamed(ctx, name, False, ready)
-    mixed = _train_streamed(ctx, name, True, ready)
+    assert F.net(ctx, name).step_form() == form
+    plain = _train_streamed(ctx, name, ready, _infer_streamed, False)
+    mixed = _train_streamed(ctx, name, ready, _infer_streamed, True)
     assert len(plain) == len(mixed)
     for i, (a, b) in enumerate(zip(plain, mixed)):
         assert np.array_equal(a, b), i
@@ -380,7 +275,7 @@ def test_infer_behind_a_pending_step_grad_and_export_behind_a_hidden_layer(ctx, 
     ws, xs = _case(name)
     ref = _oracle(name)
     frames = ctx.dev(xs[0])
-    net = _net(ctx, name)
+    net = F.net(ctx, name)
     assert net.step_form() == form
     net.step_grad(frames)
     for l in (1, 2):
@@ -399,14 +294,6 @@ def test_infer_behind_a_pending_step_grad_and_export_behind_a_hidden_layer(ctx, 
 # ------------------------------------------------------------------------------------------
 # 6. the cache, by launch counts
 # ------------------------------------------------------------------------------------------
-def _counted(ctx, net, frames, pair):
-    ctx.prof_enable(); ctx.prof_reset()
-    out = _infer(ctx, net, frames, pair)
-    counts = {k: v["launches"] for k, v in ctx.prof_read().items()}
-    ctx.prof_enable(False)
-    return out, counts
-
-
 @pytest.mark.parametrize("path", ["", "NOCHAIN"])
 def test_operators_are_cached_until_the_weights_change(ctx, flags, path):
     """a pooled net (no expand launch): `moment` (the operator-form helpers' id) counts the hidden-operator kernel (1) and the expansion of the hidden planes (1)"""
@@ -415,10 +302,11 @@ def test_operators_are_cached_until_the_weights_change(ctx, flags, path):
     ws, xs = _case(name)
     L = len(ws)
     frames = ctx.dev(xs[0])
-    net = _net(ctx, name)
+    net = F.net(ctx, name)
     chain = path == ""
     heavy = ("chain", "kspec") if chain else ("contract", "kspec")
     ref = _oracle(name)
+    _counted = lambda ctx, net, frames, pair: F.counted(ctx, lambda: _infer(ctx, net, frames, pair))
 
     def ok(out, l, ref=ref):
         assert relerr(out[0], np.stack([q[-1] for q in ref])) < TOL and relerr(out[1], np.stack([q[2 * l + 2] for q in ref])) < TOL
@@ -465,7 +353,7 @@ def test_spatial_net(ctx, flags):
     flags()
     rng = np.random.default_rng(3)
     D, N, maps, B = 3, 64, [4, 6], 2
-    net = _track(aefft.Net(ctx, D, N, N, maps, 3, 2, B, spatial=True))
+    net = F.track(aefft.Net(ctx, D, N, N, maps, 3, 2, B, spatial=True))
     for l, w in enumerate(_weights(rng, D, maps, 3, 3)):
         net.set_pair(l, *w)
     frames = ctx.dev(np.floor(rng.uniform(0, 256, (B, D, N, N))))
@@ -486,7 +374,7 @@ def test_argument_errors_and_state(ctx, flags):
     flags()
     name = "64-2pairs"
     ws, xs = _case(name)
-    net = _net(ctx, name)
+    net = F.net(ctx, name)
     frames = ctx.dev(xs[0])
     rec = ctx.empty(net.B, net.D, net.Nx, net.Ny)
     hid = ctx.empty(net.B, 3, 16, 16)

@@ -2,82 +2,25 @@
 reconstruction on every row-pass route, with and without the store, 8-bit frames bit for bit, against the float64 oracle in every form,
 a trained net's small residual, frames independent of one another, training undisturbed bit for bit, the operator cache by the profiler's
 launch counts, state and errors, and the unfused routes (spatial net, chirp-z transforms)."""
-import functools
 import importlib
 
 import numpy as np
 import pytest
-import torch
 
-import test_gpu_infer as TI
-from test_gpu_fft_path import host, relerr
-from test_gpu_sizes import _weights
+import frozen_cases as F
+from frozen_cases import CASES, PATHS, _case, _identity_case, _oracle_recon, _weights, host, relerr
+from frozen_cases import ctx, _close_nets  # noqa: F401  (fixtures: the module's context, and every tracked net closed behind each test)
+from test_gpu_infer import TOL, _infer        # 1e-4: the bound test_gpu_infer.py holds the reconstruction to
 
 aefft = importlib.import_module("autoencoder-fft_amd")
 pytestmark = pytest.mark.gpu
 
-TOL = TI.TOL        # 1e-4: the bound test_gpu_infer.py holds the reconstruction to
-PATHS = TI.PATHS
 # The score against the returned float reconstruction.  Non-negative float32 terms summed along a chain of depth k carry at most k 2^-24
 # relative error; each term (x - r)^2 carries two more roundings.  The chains (DESIGN.md section 15): power-of-two row kernel 8 terms in the
 # lane + 6 butterfly levels + at most 4 waves = 18; mixed-radix row kernel 16 + 6 + 4 = 26; score_diff_kernel and the finish in double.
 # 4 * 32 * 2^-24 = 7.6e-6 < 1e-5.
 RTOL = 1e-5
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    c = aefft.Context(0)
-    yield c
-    c.close()
-
-
-_LIVE = []
-
-
-@pytest.fixture(autouse=True)
-def _close_nets(ctx):
-    yield
-    while _LIVE:
-        _LIVE.pop().close()
-
-
-# name: D, Nx, Ny, maps, Nk, Nl, scale, B, smooth_sizes, operator_form, tied, the form under the default switches (test_gpu_infer.py's layout;
-# the cases that file has are its own, with its cached frames, weights and oracle)
-CASES = {k: TI.CASES[k] for k in ("64-2pairs", "256-4pairs", "no-pooling", "240x320", "240x320-opform", "D4")}
-CASES["64x128"] = (3, 64, 128, [4], 3, 3, 2, 2, False, False, False, "operator_chain")       # rows and columns not interchangeable
-CASES["10x24"] = (1, 10, 24, [2], 3, 3, 1, 3, True, False, False, "per_frame")               # 5 row pairs per frame: partials across workgroup boundaries
 ORDER = ["64-2pairs", "64x128", "256-4pairs", "no-pooling", "240x320", "240x320-opform", "10x24", "D4"]
-
-
-@functools.lru_cache(maxsize=None)
-def _case(name):
-    if name in TI.CASES:
-        return TI._case(name)
-    D, Nx, Ny, maps, Nk, Nl, s, B, *_ = CASES[name]
-    rng = np.random.default_rng(sum(map(ord, name)))
-    ws = _weights(rng, D, maps, Nk, Nl)
-    xs = [np.floor(rng.uniform(0, 256, (B, D, Nx, Ny))) for _ in range(2)]
-    return ws, xs
-
-
-@functools.lru_cache(maxsize=None)
-def _oracle_recon(name):
-    """the float64 oracle's reconstruction (layer 4L of np_ref.autoenc_fft) of the case's first batch, [B][D][Nx][Ny]"""
-    if name in TI.CASES:
-        return np.stack([q[-1] for q in TI._oracle(name)])
-    ws, xs = _case(name)
-    s = TI._scales(CASES[name][6], len(ws))
-    return np.stack([TI._oracle_layers(x, ws, s)[-1] for x in xs[0]])
-
-
-def _net(ctx, name, ws=None):
-    D, Nx, Ny, maps, Nk, Nl, s, B, smooth, opform, *_ = CASES[name]
-    net = aefft.Net(ctx, D, Nx, Ny, maps, Nk, s, batch=B, Nl=Nl, smooth_sizes=smooth, operator_form=opform)
-    _LIVE.append(net)
-    for l, w in enumerate(ws if ws is not None else _case(name)[0]):
-        net.set_pair(l, *w)
-    return net
 
 
 def _score(ctx, net, frames, recon=True):
@@ -94,10 +37,6 @@ def _score(ctx, net, frames, recon=True):
 
 def _mean_sq(x, r):
     return ((np.asarray(x, np.float64) - np.asarray(r, np.float64)) ** 2).mean(axis=(1, 2, 3))
-
-
-def _u8(ctx, x, like):
-    return torch.as_tensor(np.asarray(x).astype(np.uint8), device=like.device)
 
 
 def _check_reduction(name, x, s, rec):
@@ -122,11 +61,11 @@ def _check_oracle(name, x, s, rec_o):
 def test_score_is_the_mean_square_of_the_returned_reconstruction(ctx, flags, name):
     flags()
     ws, xs = _case(name)
-    net = _net(ctx, name)
+    net = F.net(ctx, name)
     assert net.step_form() == CASES[name][-1]
     f32 = ctx.dev(xs[0])
-    u8 = _u8(ctx, xs[0], f32)
-    rec_i, _ = TI._infer(ctx, net, f32)
+    u8 = F.u8(ctx, xs[0], f32)
+    rec_i, _ = _infer(ctx, net, f32)
     s_f, rec_f = _score(ctx, net, f32)
     s_8, rec_8 = _score(ctx, net, u8)
     assert np.array_equal(rec_f, rec_i), (name, np.abs(rec_f - rec_i).max())
@@ -148,7 +87,7 @@ def test_score_against_the_oracle(ctx, flags, name, path):
     """the RMS norm's triangle inequality turns the per-pixel bound TOL * max|recon_o| of test_gpu_infer.py into this one"""
     flags(path)
     ws, xs = _case(name)
-    net = _net(ctx, name)
+    net = F.net(ctx, name)
     want = CASES[name][-1]
     if path == "NOOPFORM":
         want = "per_frame"
@@ -164,36 +103,18 @@ def test_score_against_the_oracle(ctx, flags, name, path):
 # ------------------------------------------------------------------------------------------
 # 4. a small residual
 # ------------------------------------------------------------------------------------------
-@functools.lru_cache(maxsize=None)
-def _identity_case():
-    """a one-pair net without pooling that nearly reproduces its input: c[m][d] = dM delta, f[d][m] = dD delta on the centre tap for m = d,
-    plus 1e-3 of that everywhere, zero biases.  (The oracle's s_o is 2.6e-5 of the mean squared pixel: residual ~0.75 on pixels up to 255.)"""
-    D, N, dM, Nk, B = 3, 64, 3, 3, 2
-    rng = np.random.default_rng(4)
-    q32 = lambda v: np.asarray(v, np.float32).astype(np.float64)
-    c = np.zeros((dM, D, Nk, Nk)); f = np.zeros((D, dM, Nk, Nk))
-    for m in range(dM):
-        c[m, m, Nk // 2, Nk // 2] = dM; f[m, m, Nk // 2, Nk // 2] = D
-    c = q32(c + 1e-3 * dM * rng.uniform(-1, 1, c.shape)); f = q32(f + 1e-3 * D * rng.uniform(-1, 1, f.shape))
-    w = (c, np.zeros(dM), f, np.zeros(D))
-    x = np.floor(rng.uniform(0, 256, (B, D, N, N)))
-    rec_o = np.stack([TI._oracle_layers(xb, [w], [1])[-1] for xb in x])
-    return (D, N, dM, Nk, B), w, x, rec_o
-
-
 def test_a_small_residual(ctx, flags):
     """the case a difference contracted into an FMA with the unrounded product fails: the residual is ~3e-3 of the pixels"""
     flags()
     (D, N, dM, Nk, B), w, x, rec_o = _identity_case()
     s_o = _mean_sq(x, rec_o)
     assert (s_o < 1e-4 * (x ** 2).mean(axis=(1, 2, 3))).all(), s_o
-    net = aefft.Net(ctx, D, N, N, [dM], Nk, 1, batch=B)
-    _LIVE.append(net)
+    net = F.track(aefft.Net(ctx, D, N, N, [dM], Nk, 1, batch=B))
     net.set_pair(0, *w)
     f32 = ctx.dev(x)
-    rec_i, _ = TI._infer(ctx, net, f32)
+    rec_i, _ = _infer(ctx, net, f32)
     s, rec = _score(ctx, net, f32)
-    s8, rec8 = _score(ctx, net, _u8(ctx, x, f32))
+    s8, rec8 = _score(ctx, net, F.u8(ctx, x, f32))
     s0, _ = _score(ctx, net, f32, recon=False)
     assert np.array_equal(rec, rec_i) and np.array_equal(rec8, rec_i)
     _check_reduction("identity", x, s, rec)
@@ -208,7 +129,7 @@ def test_a_frames_score_does_not_depend_on_the_others(ctx, flags):
     flags()
     name = "64-2pairs"
     ws, xs = _case(name)
-    net = _net(ctx, name)
+    net = F.net(ctx, name)
     s_a, _ = _score(ctx, net, ctx.dev(xs[0]), recon=False)
     x = xs[0].copy()
     x[1] = xs[1][1]
@@ -219,35 +140,16 @@ def test_a_frames_score_does_not_depend_on_the_others(ctx, flags):
 # ------------------------------------------------------------------------------------------
 # 6. training is undisturbed
 # ------------------------------------------------------------------------------------------
-def _train(ctx, name, with_score, ready):
-    ws, xs = _case(name)
-    D, Nx, Ny, maps, *_ = CASES[name]
-    L = len(maps)
-    net = _net(ctx, name)
-    if ready:
-        net.set_input_ready(True)
-    rng = np.random.default_rng(5)
-    steps = [ctx.dev(xs[0]), ctx.dev(xs[1]), ctx.dev(xs[0])]
-    other = _u8(ctx, np.floor(rng.uniform(0, 256, xs[0].shape)), steps[0])
-    sc, rec = ctx.empty(net.B), ctx.empty(net.B, D, Nx, Ny)
-    ctx.sync()
-    out = []
-    for k, x in enumerate(steps):
-        recon = ctx.empty(net.B, D, Nx, Ny)
-        net.step_grad(x, recon)
-        ctx.sync()
-        g = host(net.grad_buffer()).copy()
-        net.step_apply(0.02)                      # mse = None: the sums stay deferred across the score call
-        if with_score and k == 0:
+def _score_between(ctx, net, steps):
+    other = F.u8(ctx, F.other_frames(steps[0].shape)[0], steps[0])
+    sc, rec = ctx.empty(net.B), ctx.empty(net.B, net.D, net.Nx, net.Ny)
+
+    def hook(k, x):
+        if k == 0:
             net.score(x, sc, rec)                 # straight behind step_apply: the frames of the step, with the store
-        if with_score and k == 1:
+        if k == 1:
             net.score(other, sc, None)            # other frames, 8-bit, without the store
-        ctx.sync()
-        mse = ctx.empty(L); net.last_mse(mse); ctx.sync()
-        out.append((host(recon).copy(), g, host(mse).copy(), [net.get_pair(l) for l in range(L)]))
-    tail = host(net.grad_buffer()).copy()
-    net.close()
-    return out, tail
+    return hook
 
 
 @pytest.mark.parametrize("ready", [False, True])
@@ -257,37 +159,23 @@ def test_training_is_not_disturbed(ctx, flags, name, path, form, ready):
     """[step, step, step] against [step, score, step, score(other frames), step]: reconstructions, packed gradients with their MSE tail,
     MSEs and weights after every step bit for bit"""
     flags(path)
-    assert _net(ctx, name).step_form() == form
-    plain, tail_p = _train(ctx, name, False, ready)
-    mixed, tail_m = _train(ctx, name, True, ready)
-    for k, (a, b) in enumerate(zip(plain, mixed)):
-        assert np.array_equal(a[0], b[0]), (k, "recon")
-        assert np.array_equal(a[1], b[1]), (k, "grads")
-        assert np.array_equal(a[2], b[2]), (k, "mse")
-        for l, (wa, wb) in enumerate(zip(a[3], b[3])):
-            for u, v in zip(wa, wb):
-                assert np.array_equal(u, v), (k, l)
-    assert np.array_equal(tail_p, tail_m)
+    assert F.net(ctx, name).step_form() == form
+    plain = F.train(ctx, name, ready, _score_between)
+    mixed = F.train(ctx, name, ready, _score_between, at="apply")
+    F.assert_same_training(plain, mixed)
 
 
 # ------------------------------------------------------------------------------------------
 # 7. the cache, by launch counts
 # ------------------------------------------------------------------------------------------
-def _counted(ctx, net, frames, recon):
-    ctx.prof_enable(); ctx.prof_reset()
-    out = _score(ctx, net, frames, recon)
-    counts = {k: v["launches"] for k, v in ctx.prof_read().items()}
-    ctx.prof_enable(False)
-    return out, counts
-
-
 def test_operators_are_reused(ctx, flags):
     flags()
     name = "256-4pairs"
     ws, xs = _case(name)
     frames = ctx.dev(xs[0])
-    net = _net(ctx, name)
+    net = F.net(ctx, name)
     assert net.step_form() == "operator_chain"
+    _counted = lambda ctx, net, frames, recon: F.counted(ctx, lambda: _score(ctx, net, frames, recon))
     (s1, _), c = _counted(ctx, net, frames, True)
     assert c["chain"] >= 1 and c["score"] == 1, c
     (s2, _), c = _counted(ctx, net, frames, False)
@@ -309,7 +197,7 @@ def test_state_and_errors(ctx, flags):
     flags()
     name = "64-2pairs"
     ws, xs = _case(name)
-    net = _net(ctx, name)
+    net = F.net(ctx, name)
     frames = ctx.dev(xs[0])
     L = len(ws)
     # the call ends a pending step_grad
@@ -341,13 +229,12 @@ def test_spatial_net(ctx, flags):
     flags()
     rng = np.random.default_rng(3)
     D, N, maps, B = 3, 32, [4], 2
-    net = aefft.Net(ctx, D, N, N, maps, 3, 2, B, spatial=True)
-    _LIVE.append(net)
+    net = F.track(aefft.Net(ctx, D, N, N, maps, 3, 2, B, spatial=True))
     for l, w in enumerate(_weights(rng, D, maps, 3, 3)):
         net.set_pair(l, *w)
     x = np.floor(rng.uniform(0, 256, (B, D, N, N)))
     frames = ctx.dev(x)
-    rec_i, _ = TI._infer(ctx, net, frames)
+    rec_i, _ = _infer(ctx, net, frames)
     s, rec = _score(ctx, net, frames)
     assert np.array_equal(rec, rec_i)
     _check_reduction("spatial", x, s, rec)
@@ -357,7 +244,7 @@ def test_spatial_net(ctx, flags):
         net.score(frames, sc, None)
     rc_ = ctx.empty(B, D, N, N); rc_.fill_(float("nan"))
     with pytest.raises(aefft.AefftError, match=einval):
-        net.score(_u8(ctx, x, frames), sc, rc_)
+        net.score(F.u8(ctx, x, frames), sc, rc_)
     ctx.sync()
     assert np.isnan(host(sc)).all() and np.isnan(host(rc_)).all()
 
@@ -366,9 +253,9 @@ def test_chirpz_route(ctx, flags):
     flags("CHIRPZ")
     name = "240x320"
     ws, xs = _case(name)
-    net = _net(ctx, name)
+    net = F.net(ctx, name)
     frames = ctx.dev(xs[0])
-    rec_i, _ = TI._infer(ctx, net, frames)
+    rec_i, _ = _infer(ctx, net, frames)
     s, rec = _score(ctx, net, frames)
     assert np.array_equal(rec, rec_i)
     _check_reduction("chirpz", xs[0], s, rec)

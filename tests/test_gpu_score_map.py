@@ -2,107 +2,27 @@
 returned float reconstruction on every row-pass route and every tile, with and without the store, 8-bit frames bit for bit, score_d as a
 function of the map, against the float64 oracle in every form, a trained net's small residual, frames independent of one another, training
 undisturbed bit for bit, the launch counts by the profiler, state and errors, and the unfused routes (spatial net, chirp-z transforms)."""
-import functools
 import importlib
 
 import numpy as np
 import pytest
 import torch
 
-import test_gpu_infer as TI
-import test_gpu_score as TS
-from test_gpu_fft_path import host, relerr
-from test_gpu_sizes import _weights
+import frozen_cases as F
+from frozen_cases import CASES, PATHS, TILES, _case, _identity_case, _oracle_recon, _weights, host, relerr
+from frozen_cases import ctx, _close_nets  # noqa: F401  (fixtures: the module's context, and every tracked net closed behind each test)
+from test_gpu_infer import TOL, _infer        # 1e-4: the bound test_gpu_infer.py holds the reconstruction to
+from test_gpu_score import _score
 
 aefft = importlib.import_module("autoencoder-fft_amd")
 pytestmark = pytest.mark.gpu
 
-TOL = TI.TOL        # 1e-4: the bound test_gpu_infer.py holds the reconstruction to
-PATHS = TI.PATHS
 # A map entry against the returned float reconstruction: the project's bound 4 k 2^-24 with k <= 32.  The float32 chains (DESIGN.md section
 # 16): power-of-two row kernel 8 terms in the lane + at most 4 butterfly levels = 12; mixed-radix row kernel 4 + at most 5 = 9; the finish and
 # the unfused route in double.  4 * 32 * 2^-24 = 7.6e-6 < 1e-5.
 RTOL = 1e-5
-TILES = (8, 16, 32, 64)
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    c = aefft.Context(0)
-    yield c
-    c.close()
-
-
-_LIVE = []
-
-
-@pytest.fixture(autouse=True)
-def _close_nets(ctx):
-    yield
-    while _LIVE:
-        _LIVE.pop().close()
-
-
-# name: D, Nx, Ny, maps, Nk, Nl, scale, B, smooth_sizes, operator_form, tied, the form under the default switches (None: recorded, not asserted)
 OWN = ["64-2pairs", "64x128", "256-4pairs", "no-pooling", "240x320", "240x320-opform", "D4"]          # test_gpu_score.py's
-CASES = {k: TS.CASES[k] for k in OWN}
-CASES["24x40"] = (1, 24, 40, [2], 3, 3, 1, 3, True, False, False, None)        # mixed radix, T = 16; 12 row pairs per plane cross workgroup boundaries; the second j holds 4 live lanes of 16; only tile 8
-CASES["8x1024"] = (1, 8, 1024, [2], 3, 3, 1, 1, False, False, False, None)     # a row pair is the whole workgroup
-CASES["8x2048"] = (1, 8, 2048, [2], 3, 3, 1, 1, False, False, False, None)     # two positions per lane in different strips
-CASES["64x192"] = (1, 64, 192, [2], 3, 3, 1, 1, True, False, False, None)      # T = 32 with tile 64: 32-lane segments
-CASES["16x640"] = (1, 16, 640, [2], 3, 3, 1, 1, True, False, False, None)      # T = 128
-CASES["16x1280"] = (1, 16, 1280, [2], 3, 3, 1, 1, True, False, False, None)    # T = 256
 ORDER = OWN + ["24x40", "8x1024", "8x2048", "64x192", "16x640", "16x1280"]
-
-
-def _tiles(name):
-    """every tile that divides both axes"""
-    _, Nx, Ny, *_ = CASES[name]
-    return [t for t in TILES if Nx % t == 0 and Ny % t == 0]
-
-
-@functools.lru_cache(maxsize=None)
-def _case(name):
-    if name in TS.CASES:
-        return TS._case(name)
-    D, Nx, Ny, maps, Nk, Nl, s, B, *_ = CASES[name]
-    rng = np.random.default_rng(sum(map(ord, name)))
-    ws = _weights(rng, D, maps, Nk, Nl)
-    xs = [np.floor(rng.uniform(0, 256, (B, D, Nx, Ny))) for _ in range(2)]
-    return ws, xs
-
-
-@functools.lru_cache(maxsize=None)
-def _oracle_recon(name):
-    """the float64 oracle's reconstruction (layer 4L of np_ref.autoenc_fft) of the case's first batch, [B][D][Nx][Ny]"""
-    if name in TS.CASES:
-        return TS._oracle_recon(name)
-    ws, xs = _case(name)
-    s = TI._scales(CASES[name][6], len(ws))
-    return np.stack([TI._oracle_layers(x, ws, s)[-1] for x in xs[0]])
-
-
-def _net(ctx, name):
-    D, Nx, Ny, maps, Nk, Nl, s, B, smooth, opform, *_ = CASES[name]
-    net = aefft.Net(ctx, D, Nx, Ny, maps, Nk, s, batch=B, Nl=Nl, smooth_sizes=smooth, operator_form=opform)
-    _LIVE.append(net)
-    for l, w in enumerate(_case(name)[0]):
-        net.set_pair(l, *w)
-    return net
-
-
-def _form(net, name, path=""):
-    """the form the net reports: asserted for test_gpu_score.py's cases, recorded for the new shapes"""
-    form, want = net.step_form(), CASES[name][-1]
-    print(f"{name} {path}: step_form {form}")
-    if want is None:
-        return form
-    if path == "NOOPFORM":
-        want = "per_frame"
-    elif path == "NOCHAIN" and want == "operator_chain":
-        want = "operator"
-    assert form == want
-    return form
 
 
 def _map(ctx, net, frames, tile, recon=True, score=True):
@@ -130,10 +50,6 @@ def _block_mean_sq(x, r, t):
     return d.reshape(B, D, Nx // t, t, Ny // t, t).sum((1, 3, 5)) / (D * t * t)
 
 
-def _u8(ctx, x, like):
-    return torch.as_tensor(np.asarray(x).astype(np.uint8), device=like.device)
-
-
 def _check_reduction(name, x, m, rec, t):
     ref = _block_mean_sq(x, rec, t)
     assert m.shape == ref.shape, (name, m.shape, ref.shape)
@@ -154,9 +70,9 @@ def _check_oracle(name, x, m, rec_o, t):
 def test_the_cases_tiles_divide_their_grids():
     for name in ORDER:
         _, Nx, Ny, *_ = CASES[name]
-        assert _tiles(name), name
-        assert all(Nx % t == 0 and Ny % t == 0 for t in _tiles(name))
-    assert _tiles("24x40") == [8] and _tiles("64x192") == [8, 16, 32, 64] and _tiles("240x320") == [8, 16] and _tiles("8x2048") == [8]
+        assert F.tiles(name), name
+        assert all(Nx % t == 0 and Ny % t == 0 for t in F.tiles(name))
+    assert F.tiles("24x40") == [8] and F.tiles("64x192") == [8, 16, 32, 64] and F.tiles("240x320") == [8, 16] and F.tiles("8x2048") == [8]
 
 
 # ------------------------------------------------------------------------------------------
@@ -166,12 +82,12 @@ def test_the_cases_tiles_divide_their_grids():
 def test_map_is_the_block_mean_square_of_the_returned_reconstruction(ctx, flags, name):
     flags()
     ws, xs = _case(name)
-    net = _net(ctx, name)
-    _form(net, name)
+    net = F.net(ctx, name)
+    F._form(net, name)
     f32 = ctx.dev(xs[0])
-    u8 = _u8(ctx, xs[0], f32)
-    rec_i, _ = TI._infer(ctx, net, f32)
-    for t in _tiles(name):
+    u8 = F.u8(ctx, xs[0], f32)
+    rec_i, _ = _infer(ctx, net, f32)
+    for t in F.tiles(name):
         m_f, _, rec_f = _map(ctx, net, f32, t)
         m_8, _, rec_8 = _map(ctx, net, u8, t)
         assert np.array_equal(rec_f, rec_i), (name, t, np.abs(rec_f - rec_i).max())
@@ -190,10 +106,10 @@ def test_map_is_the_block_mean_square_of_the_returned_reconstruction(ctx, flags,
 def test_score_is_the_mean_of_the_map(ctx, flags, name):
     flags()
     ws, xs = _case(name)
-    net = _net(ctx, name)
+    net = F.net(ctx, name)
     f32 = ctx.dev(xs[0])
-    s_ref, _ = TS._score(ctx, net, f32, recon=False)          # aefft_net_score on the same frames
-    for t in _tiles(name):
+    s_ref, _ = _score(ctx, net, f32, recon=False)          # aefft_net_score on the same frames
+    for t in F.tiles(name):
         m, s, _ = _map(ctx, net, f32, t, recon=False)
         want = np.float32(m.astype(np.float64).mean((1, 2)))
         print(f"{name} tile {t}: score {s}, mean of the map {want}, aefft_net_score {s_ref}")
@@ -211,11 +127,11 @@ def test_map_against_the_oracle(ctx, flags, name, path):
     """the RMS norm's triangle inequality holds per tile as it does per frame: the per-pixel bound TOL * max|recon_o| of test_gpu_infer.py"""
     flags(path)
     ws, xs = _case(name)
-    net = _net(ctx, name)
-    _form(net, name, path)
+    net = F.net(ctx, name)
+    F._form(net, name, path)
     frames = ctx.dev(xs[0])
     for k in range(2):          # the second call from the cached operators
-        for t in _tiles(name):
+        for t in F.tiles(name):
             m, _, _ = _map(ctx, net, frames, t, recon=bool(k), score=bool(k))
             _check_oracle(f"{name} {path}", xs[0], m, _oracle_recon(name), t)
 
@@ -227,14 +143,13 @@ def test_map_against_the_oracle(ctx, flags, name, path):
 def test_a_small_residual(ctx, flags, tile):
     """the case a difference contracted into an FMA with the unrounded product fails: the residual is ~3e-3 of the pixels"""
     flags()
-    (D, N, dM, Nk, B), w, x, rec_o = TS._identity_case()
-    net = aefft.Net(ctx, D, N, N, [dM], Nk, 1, batch=B)
-    _LIVE.append(net)
+    (D, N, dM, Nk, B), w, x, rec_o = _identity_case()
+    net = F.track(aefft.Net(ctx, D, N, N, [dM], Nk, 1, batch=B))
     net.set_pair(0, *w)
     f32 = ctx.dev(x)
-    rec_i, _ = TI._infer(ctx, net, f32)
+    rec_i, _ = _infer(ctx, net, f32)
     m, _, rec = _map(ctx, net, f32, tile)
-    m8, _, rec8 = _map(ctx, net, _u8(ctx, x, f32), tile)
+    m8, _, rec8 = _map(ctx, net, F.u8(ctx, x, f32), tile)
     m0, _, _ = _map(ctx, net, f32, tile, recon=False)
     assert np.array_equal(rec, rec_i) and np.array_equal(rec8, rec_i)
     _check_reduction("identity", x, m, rec, tile)
@@ -249,7 +164,7 @@ def test_a_frames_map_does_not_depend_on_the_others(ctx, flags):
     flags()
     name = "64-2pairs"
     ws, xs = _case(name)
-    net = _net(ctx, name)
+    net = F.net(ctx, name)
     m_a, _, _ = _map(ctx, net, ctx.dev(xs[0]), 16, recon=False)
     x = xs[0].copy()
     x[1] = xs[1][1]
@@ -260,35 +175,17 @@ def test_a_frames_map_does_not_depend_on_the_others(ctx, flags):
 # ------------------------------------------------------------------------------------------
 # 7. training is undisturbed
 # ------------------------------------------------------------------------------------------
-def _train(ctx, name, with_map, ready):
-    ws, xs = _case(name)
-    D, Nx, Ny, maps, *_ = CASES[name]
-    L = len(maps)
-    net = _net(ctx, name)
-    if ready:
-        net.set_input_ready(True)
-    rng = np.random.default_rng(5)
-    steps = [ctx.dev(xs[0]), ctx.dev(xs[1]), ctx.dev(xs[0])]
-    other = _u8(ctx, np.floor(rng.uniform(0, 256, xs[0].shape)), steps[0])
-    m8, m32, sc, rec = ctx.empty(net.B, Nx // 8, Ny // 8), ctx.empty(net.B, Nx // 32, Ny // 32), ctx.empty(net.B), ctx.empty(net.B, D, Nx, Ny)
-    ctx.sync()
-    out = []
-    for k, x in enumerate(steps):
-        recon = ctx.empty(net.B, D, Nx, Ny)
-        net.step_grad(x, recon)
-        ctx.sync()
-        g = host(net.grad_buffer()).copy()
-        net.step_apply(0.02)                      # mse = None: the sums stay deferred across the map call
-        if with_map and k == 0:
+def _map_between(ctx, net, steps):
+    other = F.u8(ctx, F.other_frames(steps[0].shape)[0], steps[0])
+    m8, m32 = ctx.empty(net.B, net.Nx // 8, net.Ny // 8), ctx.empty(net.B, net.Nx // 32, net.Ny // 32)
+    sc, rec = ctx.empty(net.B), ctx.empty(net.B, net.D, net.Nx, net.Ny)
+
+    def hook(k, x):
+        if k == 0:
             net.score_map(x, 8, m8, sc, rec)      # straight behind step_apply: the frames of the step, with the store
-        if with_map and k == 1:
+        if k == 1:
             net.score_map(other, 32, m32, sc)     # other frames, 8-bit, without the store
-        ctx.sync()
-        mse = ctx.empty(L); net.last_mse(mse); ctx.sync()
-        out.append((host(recon).copy(), g, host(mse).copy(), [net.get_pair(l) for l in range(L)]))
-    tail = host(net.grad_buffer()).copy()
-    net.close()
-    return out, tail
+    return hook
 
 
 @pytest.mark.parametrize("ready", [False, True])
@@ -298,42 +195,27 @@ def test_training_is_not_disturbed(ctx, flags, name, path, form, ready):
     """[step, step, step] against [step, map, step, map(other frames, 8-bit, no recon), step]: reconstructions, packed gradients with their
     MSE tail, MSEs and weights after every step bit for bit"""
     flags(path)
-    assert _net(ctx, name).step_form() == form
-    plain, tail_p = _train(ctx, name, False, ready)
-    mixed, tail_m = _train(ctx, name, True, ready)
-    for k, (a, b) in enumerate(zip(plain, mixed)):
-        assert np.array_equal(a[0], b[0]), (k, "recon")
-        assert np.array_equal(a[1], b[1]), (k, "grads")
-        assert np.array_equal(a[2], b[2]), (k, "mse")
-        for l, (wa, wb) in enumerate(zip(a[3], b[3])):
-            for u, v in zip(wa, wb):
-                assert np.array_equal(u, v), (k, l)
-    assert np.array_equal(tail_p, tail_m)
+    assert F.net(ctx, name).step_form() == form
+    plain = F.train(ctx, name, ready, _map_between)
+    mixed = F.train(ctx, name, ready, _map_between, at="apply")
+    F.assert_same_training(plain, mixed)
 
 
 def test_score_is_the_same_before_and_after_a_map(ctx, flags):
     flags()
     name = "64-2pairs"
     ws, xs = _case(name)
-    net = _net(ctx, name)
+    net = F.net(ctx, name)
     frames = ctx.dev(xs[0])
-    s_a, _ = TS._score(ctx, net, frames, recon=False)
+    s_a, _ = _score(ctx, net, frames, recon=False)
     _map(ctx, net, ctx.dev(xs[1]), 8)
-    s_b, _ = TS._score(ctx, net, frames, recon=False)
+    s_b, _ = _score(ctx, net, frames, recon=False)
     assert np.array_equal(s_a, s_b)
 
 
 # ------------------------------------------------------------------------------------------
 # 8. launch counts
 # ------------------------------------------------------------------------------------------
-def _counted(ctx, net, frames, score):
-    ctx.prof_enable(); ctx.prof_reset()
-    out = _map(ctx, net, frames, 16, recon=False, score=score)
-    counts = {k: v["launches"] for k, v in ctx.prof_read().items()}
-    ctx.prof_enable(False)
-    return out, counts
-
-
 def _five(c):
     assert c["chain"] == 0 and c["kspec"] == 0 and c["contract"] == 0, c
     return c["r2c_rows"] == 1 and c["r2c_cols"] == 1 and c["c2r_cols"] == 1 and c["c2r_rows"] == 1 and c["score_map"] == 1
@@ -344,8 +226,9 @@ def test_launch_counts(ctx, flags):
     name = "256-4pairs"
     ws, xs = _case(name)
     frames = ctx.dev(xs[0])
-    net = _net(ctx, name)
+    net = F.net(ctx, name)
     assert net.step_form() == "operator_chain"
+    _counted = lambda ctx, net, frames, score: F.counted(ctx, lambda: _map(ctx, net, frames, 16, recon=False, score=score))
     (m1, _, _), c = _counted(ctx, net, frames, False)
     assert c["chain"] >= 1 and c["score_map"] == 1 and c["score"] == 0, c
     # the chain form with the operators at hand: R2C rows and columns, inverse columns with the operator on load, the mapping row pass, the map finish
@@ -382,7 +265,7 @@ def test_state_and_errors(ctx, flags):
     flags()
     name = "64-2pairs"
     ws, xs = _case(name)
-    net = _net(ctx, name)
+    net = F.net(ctx, name)
     frames = ctx.dev(xs[0])
     L = len(ws)
     # the call ends a pending step_grad
@@ -398,14 +281,12 @@ def test_state_and_errors(ctx, flags):
     for tile in (4, 12, 128, 0):
         _refused(ctx, net, frames, tile)
     for other, tiles in (("240x320", (32,)), ("24x40", (64,))):
-        n2 = _net(ctx, other)
+        n2 = F.net(ctx, other)
         for tile in tiles:
             _refused(ctx, n2, ctx.dev(_case(other)[1][0]), tile)
-    D, Nx, Ny, maps, Nk, Nl, s, B, smooth, opform, *_ = TS.CASES["10x24"]
-    n3 = aefft.Net(ctx, D, Nx, Ny, maps, Nk, s, batch=B, Nl=Nl, smooth_sizes=smooth, operator_form=opform)
-    _LIVE.append(n3)
+    n3 = F.net(ctx, "10x24")
     for tile in TILES:
-        _refused(ctx, n3, ctx.dev(TS._case("10x24")[1][0]), tile)
+        _refused(ctx, n3, ctx.dev(_case("10x24")[1][0]), tile)
     # pointers: AEFFT_EINVAL, outputs untouched
     mp = ctx.empty(net.B, net.Nx // 8, net.Ny // 8); mp.fill_(float("nan"))
     sc = ctx.empty(net.B); sc.fill_(float("nan"))
@@ -415,9 +296,9 @@ def test_state_and_errors(ctx, flags):
                  (frames, 8, mp, ctx.empty(net.B + 1)[1:], rc_), (frames, 8, mp, sc, rc_.reshape(-1)[1:])):
         with pytest.raises(aefft.AefftError, match=einval):
             net.score_map(*args)
-    F = aefft._ptr
-    assert net.L.aefft_net_score_map(net.h, F(frames), 0, 8, None, F(sc), F(rc_)) == aefft.EINVAL       # null map_d
-    assert net.L.aefft_net_score_map(None, F(frames), 0, 8, F(mp), F(sc), F(rc_)) == aefft.EINVAL       # null net
+    P = aefft._ptr
+    assert net.L.aefft_net_score_map(net.h, P(frames), 0, 8, None, P(sc), P(rc_)) == aefft.EINVAL       # null map_d
+    assert net.L.aefft_net_score_map(None, P(frames), 0, 8, P(mp), P(sc), P(rc_)) == aefft.EINVAL       # null net
     ctx.sync()
     assert np.isnan(host(mp)).all() and np.isnan(host(sc)).all() and np.isnan(host(rc_)).all()
 
@@ -429,13 +310,12 @@ def test_spatial_net(ctx, flags):
     flags()
     rng = np.random.default_rng(3)
     D, N, maps, B = 3, 32, [4], 2
-    net = aefft.Net(ctx, D, N, N, maps, 3, 2, B, spatial=True)
-    _LIVE.append(net)
+    net = F.track(aefft.Net(ctx, D, N, N, maps, 3, 2, B, spatial=True))
     for l, w in enumerate(_weights(rng, D, maps, 3, 3)):
         net.set_pair(l, *w)
     x = np.floor(rng.uniform(0, 256, (B, D, N, N)))
     frames = ctx.dev(x)
-    rec_i, _ = TI._infer(ctx, net, frames)
+    rec_i, _ = _infer(ctx, net, frames)
     for t in (8, 16):
         m, s, rec = _map(ctx, net, frames, t)
         assert np.array_equal(rec, rec_i)
@@ -447,7 +327,7 @@ def test_spatial_net(ctx, flags):
         net.score_map(frames, 8, mp, None, None)
     rc_ = ctx.empty(B, D, N, N); rc_.fill_(float("nan"))
     with pytest.raises(aefft.AefftError, match=einval):
-        net.score_map(_u8(ctx, x, frames), 8, mp, None, rc_)
+        net.score_map(F.u8(ctx, x, frames), 8, mp, None, rc_)
     ctx.sync()
     assert np.isnan(host(mp)).all() and np.isnan(host(rc_)).all()
 
@@ -456,9 +336,9 @@ def test_chirpz_route(ctx, flags):
     flags("CHIRPZ")
     name = "240x320"
     ws, xs = _case(name)
-    net = _net(ctx, name)
+    net = F.net(ctx, name)
     frames = ctx.dev(xs[0])
-    rec_i, _ = TI._infer(ctx, net, frames)
+    rec_i, _ = _infer(ctx, net, frames)
     m, _, rec = _map(ctx, net, frames, 16)
     assert np.array_equal(rec, rec_i)
     _check_reduction("chirpz", xs[0], m, rec, 16)

@@ -9,11 +9,12 @@ import numpy as np
 import pytest
 import torch
 
-import test_gpu_infer as TI
-import test_gpu_score as TS
-import test_gpu_score_map as TM
-from test_gpu_fft_path import host
-from test_gpu_sizes import _weights
+import frozen_cases as F
+from frozen_cases import CASES, _case, _weights, host
+from frozen_cases import ctx, _close_nets  # noqa: F401  (fixtures: the module's context, and every tracked net closed behind each test)
+from test_gpu_infer import _infer
+from test_gpu_score import _check_reduction as _check_score, _score
+from test_gpu_score_map import _check_reduction as _check_map, _map
 
 aefft = importlib.import_module("autoencoder-fft_amd")
 pytestmark = pytest.mark.gpu
@@ -21,36 +22,17 @@ pytestmark = pytest.mark.gpu
 NAMES = ["64-2pairs", "240x320", "D4"]
 
 
-@pytest.fixture(scope="module")
-def ctx():
-    c = aefft.Context(0)
-    yield c
-    c.close()
-
-
-@pytest.fixture(autouse=True)
-def _close_nets(ctx):
-    yield
-    while TM._LIVE:
-        TM._LIVE.pop().close()
-
-
 @functools.lru_cache(maxsize=None)
 def _target(name):
     """8-bit-valued pixels that have nothing to do with the case's frames"""
-    D, Nx, Ny, maps, Nk, Nl, s, B, *_ = TM.CASES[name]
+    D, Nx, Ny, maps, Nk, Nl, s, B, *_ = CASES[name]
     rng = np.random.default_rng(1000 + sum(map(ord, name)))
     return np.floor(rng.uniform(0, 256, (B, D, Nx, Ny)))
 
 
-def _nan(ctx, *shape):
-    t = ctx.empty(*shape); t.fill_(float("nan"))
-    return t
-
-
 def _score_t(ctx, net, frames, targets, recon=True):
-    sc = _nan(ctx, net.B)
-    rec = _nan(ctx, net.B, net.D, net.Nx, net.Ny) if recon else None
+    sc = F.nan(ctx, net.B)
+    rec = F.nan(ctx, net.B, net.D, net.Nx, net.Ny) if recon else None
     out = net.score_target(frames, targets, sc, rec)
     assert out[0] is sc and out[1] is rec
     ctx.sync()
@@ -58,9 +40,9 @@ def _score_t(ctx, net, frames, targets, recon=True):
 
 
 def _map_t(ctx, net, frames, targets, tile, recon=True, score=True):
-    m = _nan(ctx, net.B, net.Nx // tile, net.Ny // tile)
-    sc = _nan(ctx, net.B) if score else None
-    rec = _nan(ctx, net.B, net.D, net.Nx, net.Ny) if recon else None
+    m = F.nan(ctx, net.B, net.Nx // tile, net.Ny // tile)
+    sc = F.nan(ctx, net.B) if score else None
+    rec = F.nan(ctx, net.B, net.D, net.Nx, net.Ny) if recon else None
     if score:
         out = net.score_map_target(frames, targets, tile, m, sc, rec)
         assert out[0] is m and out[1] is sc and out[2] is rec
@@ -75,18 +57,18 @@ def _map_t(ctx, net, frames, targets, tile, recon=True, score=True):
 @pytest.mark.parametrize("name", NAMES)
 def test_the_frames_as_target_give_the_plain_calls_bits(ctx, flags, name):
     flags()
-    ws, xs = TM._case(name)
-    net = TM._net(ctx, name)
+    ws, xs = _case(name)
+    net = F.net(ctx, name)
     f32 = ctx.dev(xs[0])
-    u8 = TM._u8(ctx, xs[0], f32)
+    u8 = F.u8(ctx, xs[0], f32)
     for fr in (f32, u8):
-        s, rec = TS._score(ctx, net, fr)
+        s, rec = _score(ctx, net, fr)
         s_t, rec_t = _score_t(ctx, net, fr, fr)
         assert np.array_equal(s_t, s) and np.array_equal(rec_t, rec), name
         s_x, _ = _score_t(ctx, net, f32, fr, recon=False)            # (the same pixels in the other type)
         assert np.array_equal(s_x, s), name
-        for t in TM._tiles(name):
-            m, sm, _ = TM._map(ctx, net, fr, t)
+        for t in F.tiles(name):
+            m, sm, _ = _map(ctx, net, fr, t)
             m_t, sm_t, rec_t = _map_t(ctx, net, fr, fr, t)
             assert np.array_equal(m_t, m) and np.array_equal(sm_t, sm) and np.array_equal(rec_t, rec), (name, t)
 
@@ -95,18 +77,18 @@ def test_the_frames_as_target_give_the_plain_calls_bits(ctx, flags, name):
 def test_an_independent_target(ctx, flags, name):
     """the bounds of test_gpu_score.py / test_gpu_score_map.py (_check_reduction, RTOL) with the target in the frame's place"""
     flags()
-    ws, xs = TM._case(name)
+    ws, xs = _case(name)
     tg = _target(name)
-    net = TM._net(ctx, name)
+    net = F.net(ctx, name)
     f32 = ctx.dev(xs[0])
-    f8 = TM._u8(ctx, xs[0], f32)
+    f8 = F.u8(ctx, xs[0], f32)
     t32 = ctx.dev(tg)
-    t8 = TM._u8(ctx, tg, f32)
-    rec_i, _ = TI._infer(ctx, net, f32)
+    t8 = F.u8(ctx, tg, f32)
+    rec_i, _ = _infer(ctx, net, f32)
     s, rec = _score_t(ctx, net, f32, t32)
     assert np.array_equal(rec, rec_i), name
-    TS._check_reduction(name + " (target)", tg, s, rec)
-    s_plain, _ = TS._score(ctx, net, f32, recon=False)
+    _check_score(name + " (target)", tg, s, rec)
+    s_plain, _ = _score(ctx, net, f32, recon=False)
     assert not np.array_equal(s, s_plain), name                      # (the target entered)
     for fr, t in ((f32, t8), (f8, t32), (f8, t8)):
         s_b, rec_b = _score_t(ctx, net, fr, t)
@@ -114,10 +96,10 @@ def test_an_independent_target(ctx, flags, name):
     s_0, _ = _score_t(ctx, net, f32, t32, recon=False)
     s_80, _ = _score_t(ctx, net, f32, t8, recon=False)
     assert np.array_equal(s_0, s) and np.array_equal(s_80, s), name
-    for tile in TM._tiles(name):
+    for tile in F.tiles(name):
         m, sm, rec_m = _map_t(ctx, net, f32, t32, tile)
         assert np.array_equal(rec_m, rec_i), (name, tile)
-        TM._check_reduction(name + " (target)", tg, m, rec_m, tile)
+        _check_map(name + " (target)", tg, m, rec_m, tile)
         want = np.float32(m.astype(np.float64).mean((1, 2)))
         assert (np.abs(sm - want) <= np.spacing(np.abs(want))).all(), (name, tile)
         for fr, t, rc in ((f32, t8, True), (f8, t8, True), (f32, t32, False), (f32, t8, False)):
@@ -131,30 +113,29 @@ def test_spatial_net(ctx, flags):
     flags()
     rng = np.random.default_rng(3)
     D, N, maps, B = 3, 32, [4], 2
-    net = aefft.Net(ctx, D, N, N, maps, 3, 2, B, spatial=True)
-    TM._LIVE.append(net)
+    net = F.track(aefft.Net(ctx, D, N, N, maps, 3, 2, B, spatial=True))
     for l, w in enumerate(_weights(rng, D, maps, 3, 3)):
         net.set_pair(l, *w)
     x = np.floor(rng.uniform(0, 256, (B, D, N, N)))
     tg = np.floor(rng.uniform(0, 256, (B, D, N, N)))
     frames, targets = ctx.dev(x), ctx.dev(tg)
-    rec_i, _ = TI._infer(ctx, net, frames)
+    rec_i, _ = _infer(ctx, net, frames)
     s, rec = _score_t(ctx, net, frames, targets)
     assert np.array_equal(rec, rec_i)
-    TS._check_reduction("spatial (target)", tg, s, rec)
+    _check_score("spatial (target)", tg, s, rec)
     s_p, _ = _score_t(ctx, net, frames, frames)
-    assert np.array_equal(s_p, TS._score(ctx, net, frames)[0])
+    assert np.array_equal(s_p, _score(ctx, net, frames)[0])
     for t in (8, 16):
         m, sm, rec = _map_t(ctx, net, frames, targets, t)
         assert np.array_equal(rec, rec_i)
-        TM._check_reduction("spatial (target)", tg, m, rec, t)
+        _check_map("spatial (target)", tg, m, rec, t)
     # float frames and float targets only; the stored reconstruction is needed
     einval = f"aefft error {aefft.EINVAL}:"
-    sc, mp, rc_ = _nan(ctx, B), _nan(ctx, B, N // 8, N // 8), _nan(ctx, B, D, N, N)
+    sc, mp, rc_ = F.nan(ctx, B), F.nan(ctx, B, N // 8, N // 8), F.nan(ctx, B, D, N, N)
     with pytest.raises(aefft.AefftError, match=einval):
-        net.score_target(frames, TM._u8(ctx, tg, frames), sc, rc_)
+        net.score_target(frames, F.u8(ctx, tg, frames), sc, rc_)
     with pytest.raises(aefft.AefftError, match=einval):
-        net.score_map_target(TM._u8(ctx, x, frames), targets, 8, mp, sc, rc_)
+        net.score_map_target(F.u8(ctx, x, frames), targets, 8, mp, sc, rc_)
     with pytest.raises(aefft.AefftError, match=einval + ".*recon_d"):
         net.score_target(frames, targets, sc, None)
     with pytest.raises(aefft.AefftError, match=einval + ".*recon_d"):
@@ -166,20 +147,20 @@ def test_spatial_net(ctx, flags):
 def test_chirpz_route(ctx, flags):
     flags("CHIRPZ")
     name = "240x320"
-    ws, xs = TM._case(name)
+    ws, xs = _case(name)
     tg = _target(name)
-    net = TM._net(ctx, name)
+    net = F.net(ctx, name)
     frames, targets = ctx.dev(xs[0]), ctx.dev(tg)
-    rec_i, _ = TI._infer(ctx, net, frames)
+    rec_i, _ = _infer(ctx, net, frames)
     s, rec = _score_t(ctx, net, frames, targets)
     assert np.array_equal(rec, rec_i)
-    TS._check_reduction("chirpz (target)", tg, s, rec)
-    s8, _ = _score_t(ctx, net, frames, TM._u8(ctx, tg, frames))
+    _check_score("chirpz (target)", tg, s, rec)
+    s8, _ = _score_t(ctx, net, frames, F.u8(ctx, tg, frames))
     assert np.array_equal(s8, s)
     m, _, rec = _map_t(ctx, net, frames, targets, 16)
     assert np.array_equal(rec, rec_i)
-    TM._check_reduction("chirpz (target)", tg, m, rec, 16)
-    sc, mp = _nan(ctx, net.B), _nan(ctx, net.B, net.Nx // 16, net.Ny // 16)
+    _check_map("chirpz (target)", tg, m, rec, 16)
+    sc, mp = F.nan(ctx, net.B), F.nan(ctx, net.B, net.Nx // 16, net.Ny // 16)
     with pytest.raises(aefft.AefftError, match=f"aefft error {aefft.EINVAL}:.*recon_d"):
         net.score_target(frames, targets, sc, None)
     with pytest.raises(aefft.AefftError, match=f"aefft error {aefft.EINVAL}:.*recon_d"):
@@ -191,10 +172,10 @@ def test_chirpz_route(ctx, flags):
 def test_errors_leave_the_outputs_untouched(ctx, flags):
     flags()
     name = "64-2pairs"
-    ws, xs = TM._case(name)
-    net = TM._net(ctx, name)
+    ws, xs = _case(name)
+    net = F.net(ctx, name)
     frames, targets = ctx.dev(xs[0]), ctx.dev(_target(name))
-    sc, mp, rc_ = _nan(ctx, net.B), _nan(ctx, net.B, net.Nx // 8, net.Ny // 8), _nan(ctx, net.B, net.D, net.Nx, net.Ny)
+    sc, mp, rc_ = F.nan(ctx, net.B), F.nan(ctx, net.B, net.Nx // 8, net.Ny // 8), F.nan(ctx, net.B, net.D, net.Nx, net.Ny)
     einval = f"aefft error {aefft.EINVAL}:"
     off = lambda t: t.reshape(-1)[1:]
     for args in ((frames, None), (frames, off(targets)), (None, targets), (off(frames), targets)):

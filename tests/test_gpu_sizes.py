@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import np_ref as R
+from frozen_cases import _weights, q32  # noqa: F401  (defined there; the files that import them from here find them)
 from test_gpu_fft_path import host, relerr, weight_step_tol
 from test_shims import _p, wrap  # noqa: F401  (module fixture: the reference's entry points compiled against the product headers)
 
@@ -20,9 +21,6 @@ def ctx():
     c = aefft.Context(0)
     yield c
     c.close()
-
-
-q32 = lambda a: np.asarray(a, np.float32).astype(np.float64)
 
 
 # ------------------------------------------------------------------------------------------
@@ -101,15 +99,6 @@ def test_mixed_radix_and_chirpz_paths_agree(ctx, flags):
 # ------------------------------------------------------------------------------------------
 # 2. the network against the oracle
 # ------------------------------------------------------------------------------------------
-def _weights(rng, D, maps, Nk, Nl):
-    ws, dD = [], D
-    for dM in maps:
-        ws.append((q32(rng.uniform(-1, 1, (dM, dD, Nk, Nl))), q32(rng.uniform(-1, 1, dM)), q32(rng.uniform(-1, 1, (dD, dM, Nk, Nl))),
-                   q32(rng.uniform(-1, 1, dD))))
-        dD = dM
-    return ws
-
-
 def _net(ctx, D, Nx, Ny, ws, Nk, Nl, s, B):
     net = aefft.Net(ctx, D, Nx, Ny, [w[0].shape[0] for w in ws], Nk, s, batch=B, Nl=Nl, smooth_sizes=True)
     for l, w in enumerate(ws):

@@ -9,17 +9,15 @@ import numpy as np
 import pytest
 import torch
 
-import test_gpu_infer as TI
-import test_gpu_score as TS
-import test_gpu_score_map as TM
-from test_gpu_fft_path import host, relerr
-from test_gpu_sizes import _weights
+import frozen_cases as F
+from frozen_cases import PATHS, _case, _identity_case, _oracle_recon, _weights, host, relerr
+from frozen_cases import ctx, _close_nets  # noqa: F401  (fixtures: the module's context, and every tracked net closed behind each test)
+from test_gpu_infer import TOL, _infer
+from test_gpu_score_map import ORDER
 
 aefft = importlib.import_module("autoencoder-fft_amd")
 pytestmark = pytest.mark.gpu
 
-ORDER = TM.ORDER
-PATHS = TI.PATHS
 # 1. A map entry against float64 block SSIM of the RETURNED float reconstruction.  The largest absolute deviation measured on the MI355X over
 # every case and tile below is MEASURED_MAP; the bound is 4 x that, rounded up to one digit -- the margin is for the
 # rounding patterns of other inputs.  The measured value itself stays within 1e-4, the resolution SSIM is quoted at.
@@ -30,20 +28,6 @@ ATOL_MAP = 2e-4
 # rounded up to one digit.
 MEASURED_ORACLE = 4.75e-5
 ATOL_ORACLE = 2e-4
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    c = aefft.Context(0)
-    yield c
-    c.close()
-
-
-@pytest.fixture(autouse=True)
-def _close_nets(ctx):
-    yield
-    while TM._LIVE:
-        TM._LIVE.pop().close()
 
 
 def _f32(a):
@@ -66,7 +50,7 @@ def _targets(name, t):
     """the float64 oracle's reconstruction plus Gaussian noise whose amplitude is, per window of the map (the D channels of a t x t tile), a
     factor from U(0, 2) times that window's standard deviation -- the factors a stratified sample with both ends, one per window of the
     batch in random order, so that three windows spread as a thousand do.  (float32 values, data_range = max - min)"""
-    rec = TM._oracle_recon(name)
+    rec = _oracle_recon(name)
     B, D, Nx, Ny = rec.shape
     rng = np.random.default_rng(77 + t + sum(map(ord, name)))
     return _noisy(rng, rec, t)
@@ -84,22 +68,17 @@ def _noisy(rng, rec, t):
 def _spread(name, t):
     """the reference map, from the float64 oracle alone, spans at least [0.5, 0.95]: a map that is ~0 or ~1 everywhere tests nothing"""
     tg, L = _targets(name, t)
-    ref = _ssim_ref(tg, TM._oracle_recon(name), t, L)
+    ref = _ssim_ref(tg, _oracle_recon(name), t, L)
     assert ref.min() <= 0.5 and ref.max() >= 0.95, (name, t, ref.min(), ref.max())
     return ref
-
-
-def _nan(ctx, *shape):
-    v = ctx.empty(*shape); v.fill_(float("nan"))
-    return v
 
 
 def _ssim(ctx, net, frames, tile, targets=None, L=255.0, recon=True, score=True):
     """one aefft_net_ssim_map: (map, score or None, reconstruction or None) as host arrays; the outputs start as NaN.  (Net.ssim_map always hands
     a score buffer over: score_d = NULL goes through the C entry.)"""
-    m = _nan(ctx, net.B, net.Nx // tile, net.Ny // tile)
-    sc = _nan(ctx, net.B) if score else None
-    rec = _nan(ctx, net.B, net.D, net.Nx, net.Ny) if recon else None
+    m = F.nan(ctx, net.B, net.Nx // tile, net.Ny // tile)
+    sc = F.nan(ctx, net.B) if score else None
+    rec = F.nan(ctx, net.B, net.D, net.Nx, net.Ny) if recon else None
     if score:
         out = net.ssim_map(frames, tile, targets, L, m, sc, rec)
         assert out[0] is m and out[1] is sc and out[2] is rec
@@ -128,14 +107,14 @@ def test_the_recorded_deviation_is_within_the_resolution_ssim_is_quoted_at():
 # ------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", ORDER)
 def test_map_is_the_block_ssim_of_the_returned_reconstruction(ctx, flags, name):
-    refs = {t: _spread(name, t) for t in TM._tiles(name)}          # (before the GPU is touched)
+    refs = {t: _spread(name, t) for t in F.tiles(name)}          # (before the GPU is touched)
     flags()
-    ws, xs = TM._case(name)
-    net = TM._net(ctx, name)
-    TM._form(net, name)
+    ws, xs = _case(name)
+    net = F.net(ctx, name)
+    F._form(net, name)
     f32 = ctx.dev(xs[0])
-    rec_i, _ = TI._infer(ctx, net, f32)
-    for t in TM._tiles(name):
+    rec_i, _ = _infer(ctx, net, f32)
+    for t in F.tiles(name):
         tg, L = _targets(name, t)
         t32 = ctx.dev(tg)
         m, _, rec = _ssim(ctx, net, f32, t, t32, L)
@@ -143,19 +122,19 @@ def test_map_is_the_block_ssim_of_the_returned_reconstruction(ctx, flags, name):
         _check_map(f"{name} tile {t}", m, _ssim_ref(tg, rec, t, L), ATOL_MAP)
         # 2. without the store, 8-bit frames, a repeated call
         m0, _, _ = _ssim(ctx, net, f32, t, t32, L, recon=False)
-        m8, _, _ = _ssim(ctx, net, TM._u8(ctx, xs[0], f32), t, t32, L, recon=False)
+        m8, _, _ = _ssim(ctx, net, F.u8(ctx, xs[0], f32), t, t32, L, recon=False)
         m1, _, _ = _ssim(ctx, net, f32, t, t32, L)
         assert np.array_equal(m0, m) and np.array_equal(m8, m) and np.array_equal(m1, m), (name, t)
         # float and 8-bit targets of the same (integer-valued) pixels
         ti = np.clip(np.rint((tg - tg.min()) * (255.0 / L)), 0, 255)
         mi, _, rec = _ssim(ctx, net, f32, t, ctx.dev(ti), 255.0)
-        mi8, _, _ = _ssim(ctx, net, f32, t, TM._u8(ctx, ti, f32), 255.0, recon=False)
+        mi8, _, _ = _ssim(ctx, net, f32, t, F.u8(ctx, ti, f32), 255.0, recon=False)
         _check_map(f"{name} tile {t} (8-bit range)", mi, _ssim_ref(ti, rec, t, 255.0), ATOL_MAP)
         assert np.array_equal(mi8, mi), (name, t)
         # the frames as the target against no target (random weights: a map near 0, which does not count toward the spread)
         mf, _, rec = _ssim(ctx, net, f32, t, f32, 255.0)
         mn, _, _ = _ssim(ctx, net, f32, t, None, 255.0, recon=False)
-        mn8, _, _ = _ssim(ctx, net, TM._u8(ctx, xs[0], f32), t, None, 255.0, recon=False)
+        mn8, _, _ = _ssim(ctx, net, F.u8(ctx, xs[0], f32), t, None, 255.0, recon=False)
         _check_map(f"{name} tile {t} (no target)", mf, _ssim_ref(xs[0], rec, t, 255.0), ATOL_MAP)
         assert np.array_equal(mn, mf) and np.array_equal(mn8, mf), (name, t)
     assert refs
@@ -165,14 +144,13 @@ def test_map_is_the_block_ssim_of_the_returned_reconstruction(ctx, flags, name):
 def test_a_small_residual(ctx, flags, tile):
     """targets = None, L = 255 on a net that nearly reproduces its input: SSIM ~ 1 from a small residual"""
     flags()
-    (D, N, dM, Nk, B), w, x, rec_o = TS._identity_case()
-    net = aefft.Net(ctx, D, N, N, [dM], Nk, 1, batch=B)
-    TM._LIVE.append(net)
+    (D, N, dM, Nk, B), w, x, rec_o = _identity_case()
+    net = F.track(aefft.Net(ctx, D, N, N, [dM], Nk, 1, batch=B))
     net.set_pair(0, *w)
     f32 = ctx.dev(x)
-    rec_i, _ = TI._infer(ctx, net, f32)
+    rec_i, _ = _infer(ctx, net, f32)
     m, _, rec = _ssim(ctx, net, f32, tile)
-    m8, _, rec8 = _ssim(ctx, net, TM._u8(ctx, x, f32), tile)
+    m8, _, rec8 = _ssim(ctx, net, F.u8(ctx, x, f32), tile)
     m0, _, _ = _ssim(ctx, net, f32, tile, recon=False)
     assert np.array_equal(rec, rec_i) and np.array_equal(rec8, rec_i)
     ref = _ssim_ref(x, rec, tile, 255.0)
@@ -188,10 +166,10 @@ def test_a_small_residual(ctx, flags, tile):
 @pytest.mark.parametrize("name", ORDER)
 def test_score_is_the_mean_of_the_map(ctx, flags, name):
     flags()
-    ws, xs = TM._case(name)
-    net = TM._net(ctx, name)
+    ws, xs = _case(name)
+    net = F.net(ctx, name)
     f32 = ctx.dev(xs[0])
-    for t in TM._tiles(name):
+    for t in F.tiles(name):
         tg, L = _targets(name, t)
         t32 = ctx.dev(tg)
         m, s, _ = _ssim(ctx, net, f32, t, t32, L, recon=False)
@@ -207,14 +185,14 @@ def test_score_is_the_mean_of_the_map(ctx, flags, name):
 # ------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name,path", [(n, p) for n in ("64-2pairs", "256-4pairs") for p in PATHS] + [(n, "") for n in ORDER if n not in ("64-2pairs", "256-4pairs")])
 def test_map_against_the_oracle(ctx, flags, name, path):
-    refs = {t: _spread(name, t) for t in TM._tiles(name)}
+    refs = {t: _spread(name, t) for t in F.tiles(name)}
     flags(path)
-    ws, xs = TM._case(name)
-    net = TM._net(ctx, name)
-    TM._form(net, name, path)
+    ws, xs = _case(name)
+    net = F.net(ctx, name)
+    F._form(net, name, path)
     frames = ctx.dev(xs[0])
     for k in range(2):          # the second call from the cached operators
-        for t in TM._tiles(name):
+        for t in F.tiles(name):
             tg, L = _targets(name, t)
             m, _, _ = _ssim(ctx, net, frames, t, ctx.dev(tg), L, recon=bool(k), score=bool(k))
             _check_map(f"{name} {path} tile {t} (oracle)", m, refs[t], ATOL_ORACLE)
@@ -226,9 +204,9 @@ def test_map_against_the_oracle(ctx, flags, name, path):
 def test_a_frames_map_does_not_depend_on_the_others(ctx, flags):
     flags()
     name = "64-2pairs"
-    ws, xs = TM._case(name)
+    ws, xs = _case(name)
     tg, L = _targets(name, 16)
-    net = TM._net(ctx, name)
+    net = F.net(ctx, name)
     m_a, _, _ = _ssim(ctx, net, ctx.dev(xs[0]), 16, ctx.dev(tg), L, recon=False)
     x, t2 = xs[0].copy(), tg.copy()
     x[1] = xs[1][1]
@@ -242,38 +220,19 @@ def test_a_frames_map_does_not_depend_on_the_others(ctx, flags):
 # ------------------------------------------------------------------------------------------
 # 6. training is undisturbed
 # ------------------------------------------------------------------------------------------
-def _train(ctx, name, with_calls, ready):
-    ws, xs = TM._case(name)
-    D, Nx, Ny, maps, *_ = TM.CASES[name]
-    L = len(maps)
-    net = TM._net(ctx, name)
-    if ready:
-        net.set_input_ready(True)
-    rng = np.random.default_rng(5)
-    steps = [ctx.dev(xs[0]), ctx.dev(xs[1]), ctx.dev(xs[0])]
-    other = TM._u8(ctx, np.floor(rng.uniform(0, 256, xs[0].shape)), steps[0])
-    target = TM._u8(ctx, np.floor(rng.uniform(0, 256, xs[0].shape)), steps[0])
-    m8, m32, sc, rec = ctx.empty(net.B, Nx // 8, Ny // 8), ctx.empty(net.B, Nx // 32, Ny // 32), ctx.empty(net.B), ctx.empty(net.B, D, Nx, Ny)
-    ctx.sync()
-    out = []
-    for k, x in enumerate(steps):
-        recon = ctx.empty(net.B, D, Nx, Ny)
-        net.step_grad(x, recon)
-        ctx.sync()
-        g = host(net.grad_buffer()).copy()
-        net.step_apply(0.02)                      # mse = None: the sums stay deferred across the calls
-        if with_calls and k == 0:
+def _ssim_between(ctx, net, steps):
+    other, target = (F.u8(ctx, o, steps[0]) for o in F.other_frames(steps[0].shape))
+    m8, m32 = ctx.empty(net.B, net.Nx // 8, net.Ny // 8), ctx.empty(net.B, net.Nx // 32, net.Ny // 32)
+    sc, rec = ctx.empty(net.B), ctx.empty(net.B, net.D, net.Nx, net.Ny)
+
+    def hook(k, x):
+        if k == 0:
             net.ssim_map(x, 8, target, 255.0, m8, sc, rec)          # straight behind step_apply: the frames of the step, with the store
             net.score_map_target(x, target, 8, m8, sc)
-        if with_calls and k == 1:
+        if k == 1:
             net.score_map_target(other, target, 32, m32, sc, rec)
             net.ssim_map(other, 32, None, 255.0, m32, sc)           # other frames, 8-bit, without the store
-        ctx.sync()
-        mse = ctx.empty(L); net.last_mse(mse); ctx.sync()
-        out.append((host(recon).copy(), g, host(mse).copy(), [net.get_pair(l) for l in range(L)]))
-    tail = host(net.grad_buffer()).copy()
-    net.close()
-    return out, tail
+    return hook
 
 
 @pytest.mark.parametrize("ready", [False, True])
@@ -283,30 +242,15 @@ def test_training_is_not_disturbed(ctx, flags, name, path, form, ready):
     """[step, step, step] against [step, ssim + map_target, step, map_target + ssim (other frames, 8-bit, no recon), step]: reconstructions,
     packed gradients with their MSE tail, MSEs and weights after every step bit for bit"""
     flags(path)
-    assert TM._net(ctx, name).step_form() == form
-    plain, tail_p = _train(ctx, name, False, ready)
-    mixed, tail_m = _train(ctx, name, True, ready)
-    for k, (a, b) in enumerate(zip(plain, mixed)):
-        assert np.array_equal(a[0], b[0]), (k, "recon")
-        assert np.array_equal(a[1], b[1]), (k, "grads")
-        assert np.array_equal(a[2], b[2]), (k, "mse")
-        for l, (wa, wb) in enumerate(zip(a[3], b[3])):
-            for u, v in zip(wa, wb):
-                assert np.array_equal(u, v), (k, l)
-    assert np.array_equal(tail_p, tail_m)
+    assert F.net(ctx, name).step_form() == form
+    plain = F.train(ctx, name, ready, _ssim_between)
+    mixed = F.train(ctx, name, ready, _ssim_between, at="apply")
+    F.assert_same_training(plain, mixed)
 
 
 # ------------------------------------------------------------------------------------------
 # 7. launch counts
 # ------------------------------------------------------------------------------------------
-def _counted(ctx, net, frames, targets, score):
-    ctx.prof_enable(); ctx.prof_reset()
-    out = _ssim(ctx, net, frames, 16, targets, 255.0, recon=False, score=score)
-    counts = {k: v["launches"] for k, v in ctx.prof_read().items()}
-    ctx.prof_enable(False)
-    return out, counts
-
-
 def _five(c):
     assert c["chain"] == 0 and c["kspec"] == 0 and c["contract"] == 0 and c["score_map"] == 0, c
     return c["r2c_rows"] == 1 and c["r2c_cols"] == 1 and c["c2r_cols"] == 1 and c["c2r_rows"] == 1 and c["ssim"] == 1
@@ -315,11 +259,12 @@ def _five(c):
 def test_launch_counts(ctx, flags):
     flags()
     name = "256-4pairs"
-    ws, xs = TM._case(name)
+    ws, xs = _case(name)
     frames = ctx.dev(xs[0])
-    targets = TM._u8(ctx, xs[1], frames)
-    net = TM._net(ctx, name)
+    targets = F.u8(ctx, xs[1], frames)
+    net = F.net(ctx, name)
     assert net.step_form() == "operator_chain"
+    _counted = lambda ctx, net, frames, targets, score: F.counted(ctx, lambda: _ssim(ctx, net, frames, 16, targets, 255.0, recon=False, score=score))
     (m1, _, _), c = _counted(ctx, net, frames, targets, False)
     assert c["chain"] >= 1 and c["ssim"] == 1 and c["score"] == 0 and c["score_map"] == 0, c
     # the chain form with the operators at hand: R2C rows and columns, inverse columns with the operator on load, the SSIM row pass, the finish
@@ -343,8 +288,8 @@ def test_launch_counts(ctx, flags):
 # ------------------------------------------------------------------------------------------
 def _refused(ctx, net, frames, targets, tile, L, what):
     """AEFFT_EINVAL with the rule in the message, every output still NaN"""
-    m = _nan(ctx, net.B * max(net.Nx // 8, 1) * max(net.Ny // 8, 1))
-    sc, rec = _nan(ctx, net.B), _nan(ctx, net.B, net.D, net.Nx, net.Ny)
+    m = F.nan(ctx, net.B * max(net.Nx // 8, 1) * max(net.Ny // 8, 1))
+    sc, rec = F.nan(ctx, net.B), F.nan(ctx, net.B, net.D, net.Nx, net.Ny)
     with pytest.raises(aefft.AefftError, match=f"aefft error {aefft.EINVAL}:.*{what}"):
         net.ssim_map(frames, tile, targets, L, m, sc, rec)
     ctx.sync()
@@ -354,8 +299,8 @@ def _refused(ctx, net, frames, targets, tile, L, what):
 def test_state_and_errors(ctx, flags):
     flags()
     name = "64-2pairs"
-    ws, xs = TM._case(name)
-    net = TM._net(ctx, name)
+    ws, xs = _case(name)
+    net = F.net(ctx, name)
     frames = ctx.dev(xs[0])
     tg, L = _targets(name, 8)
     targets = ctx.dev(tg)
@@ -369,17 +314,17 @@ def test_state_and_errors(ctx, flags):
         net.step_apply(0.02)
     # layer exports are those of the call
     top = host(net.get_layer(4 * nL)).copy()
-    assert relerr(top, rec) < TI.TOL
+    assert relerr(top, rec) < TOL
     for tile in (4, 12, 128, 0):
         _refused(ctx, net, frames, targets, tile, L, "tile")
     for other, tiles in (("240x320", (32,)), ("24x40", (64,))):
-        n2 = TM._net(ctx, other)
+        n2 = F.net(ctx, other)
         for tile in tiles:
-            _refused(ctx, n2, ctx.dev(TM._case(other)[1][0]), None, tile, 255.0, "tile")
+            _refused(ctx, n2, ctx.dev(_case(other)[1][0]), None, tile, 255.0, "tile")
     for bad in (0.0, -255.0, float("nan"), float("inf")):
         _refused(ctx, net, frames, targets, 8, bad, "data_range")
     # pointers: AEFFT_EINVAL, outputs untouched
-    mp, sc, rc_ = _nan(ctx, net.B, net.Nx // 8, net.Ny // 8), _nan(ctx, net.B), _nan(ctx, net.B, net.D, net.Nx, net.Ny)
+    mp, sc, rc_ = F.nan(ctx, net.B, net.Nx // 8, net.Ny // 8), F.nan(ctx, net.B), F.nan(ctx, net.B, net.D, net.Nx, net.Ny)
     einval = f"aefft error {aefft.EINVAL}:"
     off = lambda t: t.reshape(-1)[1:]
     for args in ((None, 8, targets, L, mp, sc, rc_), (off(frames), 8, targets, L, mp, sc, rc_), (frames, 8, off(targets), L, mp, sc, rc_),
@@ -403,13 +348,12 @@ def test_spatial_net(ctx, flags):
     flags()
     rng = np.random.default_rng(3)
     D, N, maps, B = 3, 32, [4], 2
-    net = aefft.Net(ctx, D, N, N, maps, 3, 2, B, spatial=True)
-    TM._LIVE.append(net)
+    net = F.track(aefft.Net(ctx, D, N, N, maps, 3, 2, B, spatial=True))
     for l, w in enumerate(_weights(rng, D, maps, 3, 3)):
         net.set_pair(l, *w)
     x = np.floor(rng.uniform(0, 256, (B, D, N, N)))
     frames = ctx.dev(x)
-    rec_i, _ = TI._infer(ctx, net, frames)
+    rec_i, _ = _infer(ctx, net, frames)
     for t in (8, 16):
         # (targets from the net's own reconstruction: no oracle of the spatial net is needed for a spread)
         tg, L = _noisy(np.random.default_rng(t), rec_i, t)
@@ -421,14 +365,14 @@ def test_spatial_net(ctx, flags):
         assert (np.abs(s - np.float32(m.astype(np.float64).mean((1, 2)))) <= np.spacing(s)).all()
         mn, _, rec = _ssim(ctx, net, frames, t, None, 255.0)
         _check_map(f"spatial tile {t} (no target)", mn, _ssim_ref(x, rec, t, 255.0), ATOL_MAP)
-    mp, rc_ = _nan(ctx, B, N // 8, N // 8), _nan(ctx, B, D, N, N)
+    mp, rc_ = F.nan(ctx, B, N // 8, N // 8), F.nan(ctx, B, D, N, N)
     einval = f"aefft error {aefft.EINVAL}:"
     with pytest.raises(aefft.AefftError, match=einval + ".*recon_d"):
         net.ssim_map(frames, 8, None, 255.0, mp, None, None)
     with pytest.raises(aefft.AefftError, match=einval):
-        net.ssim_map(TM._u8(ctx, x, frames), 8, None, 255.0, mp, None, rc_)
+        net.ssim_map(F.u8(ctx, x, frames), 8, None, 255.0, mp, None, rc_)
     with pytest.raises(aefft.AefftError, match=einval):
-        net.ssim_map(frames, 8, TM._u8(ctx, x, frames), 255.0, mp, None, rc_)
+        net.ssim_map(frames, 8, F.u8(ctx, x, frames), 255.0, mp, None, rc_)
     ctx.sync()
     assert np.isnan(host(mp)).all() and np.isnan(host(rc_)).all()
 
@@ -437,19 +381,19 @@ def test_chirpz_route(ctx, flags):
     name = "240x320"
     ref_o = _spread(name, 16)
     flags("CHIRPZ")
-    ws, xs = TM._case(name)
+    ws, xs = _case(name)
     tg, L = _targets(name, 16)
-    net = TM._net(ctx, name)
+    net = F.net(ctx, name)
     frames = ctx.dev(xs[0])
-    rec_i, _ = TI._infer(ctx, net, frames)
+    rec_i, _ = _infer(ctx, net, frames)
     m, _, rec = _ssim(ctx, net, frames, 16, ctx.dev(tg), L)
     assert np.array_equal(rec, rec_i)
     _check_map("chirpz", m, _ssim_ref(tg, rec, 16, L), ATOL_MAP)
     ti = np.clip(np.rint((tg - tg.min()) * (255.0 / L)), 0, 255)
     mi, _, _ = _ssim(ctx, net, frames, 16, ctx.dev(ti), 255.0)
-    mi8, _, _ = _ssim(ctx, net, frames, 16, TM._u8(ctx, ti, frames), 255.0)
+    mi8, _, _ = _ssim(ctx, net, frames, 16, F.u8(ctx, ti, frames), 255.0)
     assert np.array_equal(mi8, mi)
-    mp = _nan(ctx, net.B, net.Nx // 16, net.Ny // 16)
+    mp = F.nan(ctx, net.B, net.Nx // 16, net.Ny // 16)
     with pytest.raises(aefft.AefftError, match=f"aefft error {aefft.EINVAL}:.*recon_d"):
         net.ssim_map(frames, 16, None, 255.0, mp, None, None)
     ctx.sync()

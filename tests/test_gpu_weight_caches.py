@@ -13,13 +13,14 @@ import importlib
 import numpy as np
 import pytest
 
-from test_gpu_fft_path import relerr
-from test_gpu_infer import CASES, TOL, _LIVE, _case, _infer, _net, _oracle_layers, _scales
+import frozen_cases as F
+from frozen_cases import CASES, _case, _oracle_layers, _scales, relerr
+from frozen_cases import ctx, _close_nets  # noqa: F401  (fixtures: the module's context, and every tracked net closed behind each test)
+from test_gpu_infer import TOL, _infer
 from test_gpu_decode import _codes, _decode, _decode_oracle
 
 aefft = importlib.import_module("autoencoder-fft_amd")
 pytestmark = pytest.mark.gpu
-
 
 
 def _hidden(name):
@@ -27,20 +28,6 @@ def _hidden(name):
     decoder, and expanding its hidden layer overwrites no next pair's input operator (a pair of scale 1 keeps its input in the buffer of the
     hidden layer before it), so the inference operators are still current when the weight-changing call is made"""
     return len(CASES[name][3]) - 1
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    c = aefft.Context(0)
-    yield c
-    c.close()
-
-
-@pytest.fixture(autouse=True)
-def _close_nets(ctx):
-    yield
-    while _LIVE:
-        _LIVE.pop().close()
 
 
 def _step(net, frames):
@@ -101,7 +88,7 @@ def test_no_cache_survives_a_weight_change(ctx, flags, name, path, form, call):
     h = _hidden(name)
     code = ctx.dev(_codes(name, h)[0])
     for l in ([0] if call == "step" else sorted({0, 1, L - 1})):      # the pair whose weights the call changes (the step changes every pair's)
-        net = _net(ctx, name)
+        net = F.net(ctx, name)
         assert net.step_form() == form
         _warm(ctx, net, frames, code, h)
         _step(net, frames)                        # warm: the step's operator sets and the bin-major record of the updated weights
@@ -109,7 +96,7 @@ def test_no_cache_survives_a_weight_change(ctx, flags, name, path, form, call):
         CALLS[call](net, l, frames)
         warm = _outputs(ctx, net, frames, code, h)
         ws = [net.get_pair(j) for j in range(L)]
-        fresh = _net(ctx, name, ws)
+        fresh = F.net(ctx, name, ws)
         cold = _outputs(ctx, fresh, frames, code, h)
         for k in warm:
             d = np.abs(warm[k].astype(np.float64) - cold[k]).max() / max(1.0, np.abs(cold[k]).max())
