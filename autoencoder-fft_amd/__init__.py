@@ -25,9 +25,7 @@ OK, EINVAL, EHIP, ENOMEM, ESTATE = 0, 1, 2, 3, 4
 FLAGS = {n: 1 << i for i, n in enumerate(
     ["NOLAZY", "NOCOMPACT", "NOQPATH", "NOFUSEMSE", "NOGROUP", "NOMFMA", "NOGFWD", "NOOVERLAP", "NOFUSECROP", "GTAPS",
      "NOPREFETCH", "NODEFER", "NOTILEDSPATIAL", "NOFAST", "NOSPLITK", "POISON", "NOOPFORM", "NOCHAIN", "NOFUSEUPD", "NOAHEAD", "NORCORR", "NOLAZYMSE", "SMALLOVERLAP", "CHAINMSE",
-     "CHIRPZ", "NOPRUNESMOOTH"])}
-# ... and the switch the header keeps apart from that table (bit 26); Context.set_flags takes the names of both
-DEV_FLAGS = {"NOSTATICCHAIN": 1 << 26}
+     "CHIRPZ", "NOPRUNESMOOTH", "NOSTATICCHAIN"])}
 NET_SMOOTH_SIZES = 1 << 0   # include/aefft.h AEFFT_NET_SMOOTH_SIZES (aefft_net_create_ex)
 NET_SPATIAL = 1 << 1        # include/aefft.h AEFFT_NET_SPATIAL: the coordinate-space training mode as a resident net
 NET_SMOOTH_OPFORM = 1 << 2  # include/aefft.h AEFFT_NET_SMOOTH_OPFORM: the operator-form training step on grids with a smooth axis
@@ -911,8 +909,7 @@ class Context:
         v = 0
         for nme in names:
             if nme:
-                key = nme.replace("AEFFT_", "").replace("F_", "")
-                v |= FLAGS[key] if key in FLAGS else DEV_FLAGS[key]
+                v |= FLAGS[nme.replace("AEFFT_", "").replace("F_", "")]
         self.check(self.L.aefft_ctx_set_flags(self.h, v))
 
     def get_flags(self):

@@ -96,15 +96,11 @@ enum {
                                    * net 3 -> 8,16,32,64 with its fused kernel compiled from a static table, in launches of more than one round of 1 536) */
     AEFFT_F_CHIRPZ = 1 << 24,      /* grids with a smooth axis, both axes up to 1024, through Bluestein's chirp-z transforms instead of the mixed-radix ones (the two
                                    * paths compared; power-of-two grids never take the mixed-radix passes) */
-    AEFFT_F_NOPRUNESMOOTH = 1 << 25 /* grids with a smooth axis: kernel spectra and weight gradients by pad + full R2C / full C2R + shrink instead of the
+    AEFFT_F_NOPRUNESMOOTH = 1 << 25, /* grids with a smooth axis: kernel spectra and weight gradients by pad + full R2C / full C2R + shrink instead of the
                                    * support-pruned transforms (the two routes compared; power-of-two grids are not affected) */
-};
-/* One more switch, bit 26 (kept apart from the table above and written as a plain constant: the ABI tests of earlier calls pin that table's
- * 26 entries).  AEFFT_FLAGS and aefft_ctx_set_flags take it like the others. */
-enum {
-    AEFFT_F_NOSTATICCHAIN = 0x04000000 /* operator form with the chain: the tail launch's per-bin steps from the step list in the kernel's arguments
-                                        * (the generic step code, which serves any net) even where the net's channel counts have a compile-time
-                                        * step table; the two routes give the same bits (aefft_net_tail_route says which one ran) */
+    AEFFT_F_NOSTATICCHAIN = 1 << 26 /* operator form with the chain: the tail launch's per-bin steps from the step list in the kernel's arguments
+                                   * (the generic step code, which serves any net) even where the net's channel counts have a compile-time
+                                   * step table; the two routes give the same bits (aefft_net_tail_route says which one ran) */
 };
 int aefft_ctx_set_flags(aefft_ctx* ctx, unsigned flags);
 unsigned aefft_ctx_get_flags(const aefft_ctx* ctx);

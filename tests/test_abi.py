@@ -1,36 +1,29 @@
 """CPU-side boundary checks: libaefft.so loads and exports every symbol include/aefft.h declares
 (no compute call is made -- there is no GPU here), and the Python prototype table covers them all."""
-import importlib
+import glob
 import os
 import re
 import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-aefft = importlib.import_module("autoencoder-fft_amd")
+import abi_checks as A
+from abi_checks import ROOT, aefft
 
 
 def _declared():
-    txt = open(os.path.join(ROOT, "include", "aefft.h")).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(aefft_[a-z0-9_]+)\s*\(", txt)))
+    return sorted(set(re.findall(r"\b(aefft_[a-z0-9_]+)\s*\(", A.header_code())))
 
 
 @pytest.fixture(scope="module")
 def built():
-    if not os.path.exists(aefft.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return aefft.lib()
+    return A.lib()
 
 
 def test_header_symbols_exported(built):
     names = _declared()
     assert len(names) >= 35
-    out = subprocess.run(["nm", "-D", "--defined-only", aefft.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    exported = set(l.split()[-1] for l in out.splitlines() if " T " in l)
-    missing = [n for n in names if n not in exported]
+    missing = [n for n in names if n not in A.exported()]
     assert not missing, missing
 
 
@@ -43,20 +36,16 @@ def test_data_parallel_library_exports_its_header():
     prototype table covers them"""
     if not os.path.exists(aefft.DP_LIB_PATH):
         subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "autoencoder-fft_amd", "csrc"), "dp"])
-    txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "aefft_dp.h")).read(), flags=re.S)
-    names = sorted(set(re.findall(r"\b(aefft_dp_[a-z0-9_]+)\s*\(", txt)))
+    names = sorted(set(re.findall(r"\b(aefft_dp_[a-z0-9_]+)\s*\(", A.header_code("aefft_dp.h"))))
     assert len(names) == 10 and names == sorted(aefft.DP_SIGNATURES)
-    out = subprocess.run(["nm", "-D", "--defined-only", aefft.DP_LIB_PATH], capture_output=True, text=True, check=True).stdout
-    exported = set(l.split()[-1] for l in out.splitlines() if " T " in l)
-    assert not [n for n in names if n not in exported]
+    assert not [n for n in names if n not in A.exported(aefft.DP_LIB_PATH)]
     aefft.dp_lib()
     und = subprocess.run(["nm", "-D", "--undefined-only", aefft.LIB_PATH], capture_output=True, text=True, check=True).stdout
     assert "nccl" not in und, "libaefft.so itself must not depend on RCCL"
 
 
 def test_flag_table_matches_header():
-    txt = open(os.path.join(ROOT, "include", "aefft.h")).read()
-    hdr = {m.group(1): 1 << int(m.group(2)) for m in re.finditer(r"AEFFT_F_([A-Z]+)\s*=\s*1\s*<<\s*(\d+)", txt)}
+    hdr = {m.group(1): 1 << int(m.group(2)) for m in re.finditer(r"AEFFT_F_([A-Z]+)\s*=\s*1\s*<<\s*(\d+)", A.header())}
     assert hdr == aefft.FLAGS and len(hdr) >= 16
 
 
@@ -107,29 +96,17 @@ def test_hot_kernels_do_not_spill():
     training step may use scratch memory (a spilled register is a memory round trip inside loops that are bound by exactly those; a second call site of
     an inlined body once turned the tail launch's 23 us into 195), and the launches whose residency the design counts on keep their register budgets
     (tail_kernel<lean, no fused MSE> <= 80, with it <= 96, kspec_group_kernel<5,5,1> <= 128)."""
-    import glob
-    import re
-    files = glob.glob(os.path.join(ROOT, "autoencoder-fft_amd", "csrc", "build", "*.rsrc"))
-    if not files:
-        pytest.skip("no resource tables (library built before the Makefile wrote them)")
+    A.lib()
     rows = {}
-    for f in files:
-        name = None
-        for line in open(f):
-            m = re.search(r"Function Name: (\S+)", line)
-            if m:
-                name = m.group(1); rows[name] = {}
-            for key, pat in (("scratch", r"ScratchSize \[bytes/lane\]: (\d+)"), ("vgprs", r" VGPRs: (\d+)")):
-                m = re.search(pat, line)
-                if m and name:
-                    rows[name][key] = int(m.group(1))
+    for f in glob.glob(os.path.join(A.CSRC, "build", "*.rsrc")):
+        rows.update({name: ints for name, (_, ints) in A.rsrc(os.path.basename(f)).items()})
     assert len(rows) > 50
     legacy = ("contract_kernelILi",)          # the scalar-FMA contraction (AEFFT_F_NOMFMA / odd shapes): 20 bytes, not on the step's path
-    spills = {k: v["scratch"] for k, v in rows.items() if v.get("scratch", 0) > 0 and not any(t in k for t in legacy)}
+    spills = {k: v["ScratchSize"] for k, v in rows.items() if v.get("ScratchSize", 0) > 0 and not any(t in k for t in legacy)}
     assert not spills, spills
     budget = {"tail_kernelILb1ELb0E": 80, "tail_kernelILb1ELb1E": 96, "kspec_group_kernelILi5ELi5ELi1E": 128, "msgrad_kernelILi8E": 128, "msgrad_kernelILi4E": 96, "wgrad_taps_kernelILi5E": 128}
     for frag, cap in budget.items():
         hit = [k for k in rows if frag in k]
         assert hit, frag
         for k in hit:
-            assert rows[k]["vgprs"] <= cap, (k, rows[k])
+            assert rows[k]["VGPRs"] <= cap, (k, rows[k])

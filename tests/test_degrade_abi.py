@@ -3,54 +3,25 @@ header's statement of the rules; every instantiation of the kernel in the back e
 that needs no device; the Python layout rules; the host check program; and the definition itself on the numpy restatement of degrade_ref.py --
 Philox's published known answers and the statistics of the noise and the impulses, every bound derived from the sample count."""
 import ctypes as C
-import importlib
 import inspect
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import abi_checks as A
 import degrade_ref as R
+from abi_checks import CSRC, ROOT, aefft
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-aefft = importlib.import_module("autoencoder-fft_amd")
-CSRC = os.path.join(ROOT, "autoencoder-fft_amd", "csrc")
 NAME = "aefft_frames_degrade"
-CTYPES = {"aefft_ctx*": C.c_void_p, "const void*": C.c_void_p, "void*": C.c_void_p, "int": C.c_int, "float": C.c_float, "unsigned long long": C.c_ulonglong}
-TYPES = ["aefft_ctx*", "const void*", "int", "void*", "int", "int", "int", "int", "int", "int", "float", "float", "unsigned long long", "unsigned long long"]
-NAMES = ["ctx", "src_d", "src_u8", "dst_d", "dst_u8", "B", "D", "Nx", "Ny", "blur", "sigma", "impulse", "seed", "first_frame"]
-
-
-def _header():
-    return open(os.path.join(ROOT, "include", "aefft.h")).read()
-
-
-def _lib():
-    if not os.path.exists(aefft.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return aefft.lib()
+ARGS = ["aefft_ctx* ctx", "const void* src_d", "int src_u8", "void* dst_d", "int dst_u8", "int B", "int D", "int Nx", "int Ny", "int blur", "float sigma", "float impulse",
+        "unsigned long long seed", "unsigned long long first_frame"]
 
 
 # 1.
 def test_declared_exported_and_prototyped():
-    txt = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
-    m = re.search(r"int\s+%s\s*\(([^)]*)\)" % NAME, txt)
-    assert m, f"include/aefft.h does not declare {NAME}"
-    args = [" ".join(a.split()) for a in m.group(1).split(",")]
-    assert len(args) == len(TYPES), args
-    for a, w, n in zip(args, TYPES, NAMES):
-        assert a == f"{w} {n}", (a, w, n)
-    _lib()
-    out = subprocess.run(["nm", "-D", "--defined-only", aefft.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert any(l.split()[-1] == NAME and " T " in l for l in out.splitlines())
-    res, argt = aefft.SIGNATURES[NAME]
-    assert res is C.c_int and len(argt) == len(TYPES)
-    for t, w in zip(argt, TYPES):
-        assert t is CTYPES[w], w
+    A.check_call(NAME, ARGS)
     p = inspect.signature(aefft.Context.frames_degrade).parameters
     assert list(p) == ["self", "frames", "blur", "sigma", "impulse", "seed", "first_frame", "out", "dtype"]
     assert p["frames"].default is inspect.Parameter.empty
@@ -59,15 +30,12 @@ def test_declared_exported_and_prototyped():
 
 # 2.
 def test_the_call_stands_behind_map_overlay_in_the_image_boundary_block():
-    h = _header()
-    assert h.index("int aefft_map_overlay_image(") < h.index("int aefft_frames_degrade(") < h.index("/* ---- network level")
-    assert h.index("int aefft_map_overlay_image(") < h.index("/* aefft_frames_degrade") < h.index("int aefft_frames_degrade(")
+    A.in_order(A.header(), "int aefft_map_overlay_image(", "/* aefft_frames_degrade", "int aefft_frames_degrade(", "/* ---- network level")
 
 
 # 3.
 def test_header_states_the_rules():
-    h = _header()
-    doc = h[h.index("/* aefft_frames_degrade"):h.index("int aefft_frames_degrade(")]
+    doc = A.doc("/* aefft_frames_degrade", "int aefft_frames_degrade(")
     for word in ("[B][D][Nx][Ny]", "16-byte aligned", "D in 1..4", "1..8192", "odd sizes included", "B >= 1",
                  # 1.
                  "px_u8(src[b][d][i][j])", "NaN -> 0", "clamp to 0..255", "halves away from zero", "first turned into pixels",
@@ -100,22 +68,8 @@ def test_header_states_the_rules():
 def test_degrade_kernels_use_no_scratch_and_cover_every_instantiation():
     """build/degrade_kernels.rsrc: degrade_kernel<R, SF32, DF32, WORDS> for R = 0..4 x {8-bit, float} source x {8-bit, float} destination x
     {elements, dwords} -- what the launcher selects -- nothing else, each with zero scratch and zero spills"""
-    _lib()
-    path = os.path.join(CSRC, "build", "degrade_kernels.rsrc")
-    assert os.path.exists(path), f"{path}: the build writes the back end's resource table beside every object (csrc/Makefile)"
-    got = set()
-    for b in re.split(r"(?=remark: [^\n]*Function Name: )", open(path).read()):
-        m = re.search(r"Function Name: (\S+)", b)
-        if not m:
-            continue
-        k = re.search(r"\d+degrade_kernelILi(\d)ELb([01])ELb([01])ELb([01])EEE", m.group(1))
-        assert k, m.group(1)
-        got.add((int(k.group(1)),) + tuple(k.group(i) == "1" for i in (2, 3, 4)))
-        for key in ("ScratchSize \\[bytes/lane\\]", "SGPRs Spill", "VGPRs Spill"):
-            v = re.search(key + r": (\d+)", b)
-            assert v and int(v.group(1)) == 0, (m.group(1), key)
-    tf = (False, True)
-    assert got == {(r, s, d, w) for r in range(5) for s in tf for d in tf for w in tf}
+    [got] = A.instantiations("degrade_kernels.rsrc", r"\d+degrade_kernelILi(\d)ELb([01])ELb([01])ELb([01])EEE")
+    assert got == {(r, s, d, w) for r in "01234" for s in "01" for d in "01" for w in "01"}
     assert "degrade_kernels.hip" in open(os.path.join(CSRC, "Makefile")).read()
     # the launcher is declared with the others, the entry point stands with the image calls and shares their helpers
     assert "hipError_t launch_degrade(" in open(os.path.join(CSRC, "internal.h")).read()
@@ -129,16 +83,15 @@ def test_degrade_kernels_use_no_scratch_and_cover_every_instantiation():
 
 # 5.
 def test_null_context_is_einval_without_a_device():
-    L = _lib()
+    L = A.lib()
     buf = (C.c_ubyte * 2048)()
     base = C.addressof(buf)
     base += -base % 16
-    einval = int(re.search(r"AEFFT_EINVAL\s*=\s*(-?\d+)", _header()).group(1))
     src, dst = C.c_void_p(base), C.c_void_p(base + 1024)
     for su8, du8 in ((1, 1), (0, 1), (1, 0), (0, 0)):
-        assert L.aefft_frames_degrade(None, src, su8, dst, du8, 1, 3, 4, 4, 2, 25.0, 0.02, 7, 0) == einval
-    assert L.aefft_frames_degrade(None, src, 1, src, 1, 1, 3, 4, 4, 0, 25.0, 0.02, 7, 0) == einval
-    assert L.aefft_frames_degrade(None, None, 0, None, 0, 0, 0, 0, 0, 0, 0.0, 0.0, 0, 0) == einval
+        assert L.aefft_frames_degrade(None, src, su8, dst, du8, 1, 3, 4, 4, 2, 25.0, 0.02, 7, 0) == A.EINVAL
+    assert L.aefft_frames_degrade(None, src, 1, src, 1, 1, 3, 4, 4, 0, 25.0, 0.02, 7, 0) == A.EINVAL
+    assert L.aefft_frames_degrade(None, None, 0, None, 0, 0, 0, 0, 0, 0, 0.0, 0.0, 0, 0) == A.EINVAL
     assert bytes(buf) == bytes(2048)
 
 
@@ -169,14 +122,7 @@ def test_python_layout_rules_need_no_device():
 
 # 7.
 def test_the_host_check_program_is_there_and_stands_alone():
-    path = os.path.join(ROOT, "tools", "degrade_hostcheck.cpp")
-    assert os.path.exists(path)
-    src = open(path).read()
-    assert '#include "../autoencoder-fft_amd/csrc/degrade_kernels.hip"' in src and "int main(" in src and "-fsanitize=address,undefined" in src
-    assert "Python.h" not in src and "hip_runtime" not in src
-    lanes = open(os.path.join(ROOT, "tools", "hostlanes.h")).read()
-    assert '#include "hostlanes.h"' in src and "#define AEFFT_HOSTCHECK" in lanes
-    assert "Python.h" not in lanes and "hip_runtime" not in lanes and "LD_PRELOAD" not in lanes
+    A.host_check_stands_alone("degrade_hostcheck.cpp", "degrade_kernels.hip")
     # the product never imports the restatement
     for dirpath, _, files in os.walk(os.path.join(ROOT, "autoencoder-fft_amd")):
         for f in files:

@@ -1,41 +1,16 @@
 """aefft_net_infer at the boundary (no GPU): declared, exported and prototyped; Net.infer's signature; the argument errors that need no
 device; the development-switch tables unchanged; the new row-pass instantiations in the back end's resource tables (no scratch)."""
 import ctypes as C
-import importlib
 import inspect
 import os
-import re
-import subprocess
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-aefft = importlib.import_module("autoencoder-fft_amd")
-NFLAGS = 26      # AEFFT_F_* switches of the library
-
-
-def _header():
-    return open(os.path.join(ROOT, "include", "aefft.h")).read()
-
-
-def _lib():
-    if not os.path.exists(aefft.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return aefft.lib()
+import abi_checks as A
+from abi_checks import ROOT, aefft
 
 
 def test_declared_exported_and_prototyped():
-    txt = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
-    m = re.search(r"int\s+aefft_net_infer\s*\(([^)]*)\)", txt)
-    assert m, "include/aefft.h does not declare aefft_net_infer"
-    args = [a.strip() for a in m.group(1).split(",")]
-    assert len(args) == 7
-    assert args[1].startswith("const void*") and args[3].startswith("void*") and args[6].startswith("float*")
-    _lib()
-    out = subprocess.run(["nm", "-D", "--defined-only", aefft.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert any(l.split()[-1] == "aefft_net_infer" and " T " in l for l in out.splitlines())
-    res, argt = aefft.SIGNATURES["aefft_net_infer"]
-    assert res is C.c_int and len(argt) == 7
-    assert [argt[i] for i in (2, 4, 5)] == [C.c_int] * 3
+    A.check_call("aefft_net_infer", ["aefft_net* net", "const void* frames_d", "int frames_u8", "void* recon_d", "int recon_u8", "int hidden_pair",
+                                     "float* hidden_d"])
 
 
 def test_net_infer_signature():
@@ -45,51 +20,30 @@ def test_net_infer_signature():
 
 
 def test_null_net_is_einval_without_a_device():
-    L = _lib()
+    L = A.lib()
     buf = (C.c_float * 64)()
-    einval = int(re.search(r"AEFFT_EINVAL\s*=\s*(-?\d+)", _header()).group(1))
-    assert L.aefft_net_infer(None, C.cast(buf, C.c_void_p), 0, C.cast(buf, C.c_void_p), 0, 0, None) == einval
-    assert L.aefft_net_infer(None, None, 1, None, 1, -1, None) == einval
+    assert L.aefft_net_infer(None, C.cast(buf, C.c_void_p), 0, C.cast(buf, C.c_void_p), 0, 0, None) == A.EINVAL
+    assert L.aefft_net_infer(None, None, 1, None, 1, -1, None) == A.EINVAL
 
 
 def test_header_describes_the_call_and_the_u8_sizes():
-    h = _header()
-    doc = h[h.index("Frozen-weight inference"):h.index("int aefft_net_infer")]
+    doc = A.doc("Frozen-weight inference", "int aefft_net_infer")
     for word in ("SpinToImage_C", "aefft_net_step_form", "aefft_net_set_pair", "aefft_net_step_apply", "AEFFT_EINVAL", "16-byte aligned"):
         assert word in doc, word
-    u8 = h[h.index("The same calls on 8-BIT frames"):h.index("int aefft_net_step_grad_u8")]
+    u8 = A.doc("The same calls on 8-BIT frames", "int aefft_net_step_grad_u8")
     assert "Power-of-two frame\n * sizes" not in u8 and "smooth sizes" in u8
 
 
 def test_flag_tables_are_unchanged():
     """the call adds no development switch and no net option: the header's AEFFT_F_* bits and the aefft_net_create_ex options are the ones
     the library had, and Context.set_flags takes every switch by name"""
-    bits = dict((n, int(b)) for n, b in re.findall(r"\b(AEFFT_F_[A-Z0-9]+)\s*=\s*1\s*<<\s*(\d+)", _header()))
-    assert len(bits) == NFLAGS and len(set(bits.values())) == NFLAGS
-    assert not [n for n in bits if "INFER" in n or "U8" in n]
-    opts = re.findall(r"\b(AEFFT_NET_[A-Z_]+)\s*=\s*1u\s*<<\s*\d+", _header())
-    assert opts == ["AEFFT_NET_SMOOTH_SIZES", "AEFFT_NET_SPATIAL", "AEFFT_NET_SMOOTH_OPFORM"]
     src = open(os.path.join(ROOT, "autoencoder-fft_amd", "__init__.py")).read()
-    for n in bits:
+    for n in A.tables_unchanged("INFER", "U8")[0]:
         assert n[len("AEFFT_F_"):] in src, n
 
 
 def test_new_row_pass_instantiations_use_no_scratch():
     """build/<file>.rsrc (the back end's resource table): every 8-bit-output row kernel is there, with zero scratch and no spills"""
-    _lib()
-    build = os.path.join(ROOT, "autoencoder-fft_amd", "csrc", "build")
-    seen = 0
-    for fn, pat in (("fft_kernels.rsrc", r"c2r_rows_kernelILi\d+ELb[01]ELb1E"), ("fft_mixed_kernels.rsrc", r"mix_c2r_rows_kernelILi\d+ELb1E")):
-        path = os.path.join(build, fn)
-        assert os.path.exists(path), f"{path}: the build writes the back end's resource table beside every object (csrc/Makefile)"
-        txt = open(path).read()
-        blocks = re.split(r"(?=remark: [^\n]*Function Name: )", txt)
-        for b in blocks:
-            m = re.search(r"Function Name: (\S+)", b)
-            if not m or not re.search(pat, m.group(1)):
-                continue
-            seen += 1
-            for key in ("ScratchSize \\[bytes/lane\\]", "SGPRs Spill", "VGPRs Spill"):
-                v = re.search(key + r": (\d+)", b)
-                assert v and int(v.group(1)) == 0, (m.group(1), key)
-    assert seen == 14 + 5, seen
+    [dense] = A.instantiations("fft_kernels.rsrc", r"(\S*c2r_rows_kernelILi\d+ELb[01]ELb1E\S*)", every=False)
+    [mixed] = A.instantiations("fft_mixed_kernels.rsrc", r"(\S*mix_c2r_rows_kernelILi\d+ELb1E\S*)", every=False)
+    assert len(dense) + len(mixed) == 14 + 5, (sorted(dense), sorted(mixed))

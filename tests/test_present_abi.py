@@ -3,67 +3,34 @@ prototyped; the Context methods and heat_lut; the argument error that needs no d
 instantiation of the two kernels in the back end's resource table (no scratch, no spills); the tap formulas stated once; the Python layout
 rules."""
 import ctypes as C
-import importlib
 import inspect
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-aefft = importlib.import_module("autoencoder-fft_amd")
-CSRC = os.path.join(ROOT, "autoencoder-fft_amd", "csrc")
-CTYPES = {"aefft_ctx*": C.c_void_p, "const void*": C.c_void_p, "const float*": C.c_void_p, "const unsigned char*": C.c_void_p, "unsigned char*": C.c_void_p,
-          "size_t": C.c_size_t, "int": C.c_int, "float": C.c_float}
+import abi_checks as A
+from abi_checks import CSRC, ROOT, aefft
+
 CALLS = {
-    "aefft_frames_resize_to_image": (
-        ["aefft_ctx*", "const void*", "int", "int", "int", "int", "unsigned char*", "size_t", "size_t", "int", "int", "int", "int"],
-        ["ctx", "frames_d", "frames_u8", "Nx", "Ny", "mode", "image_d", "pitch", "image_stride", "W", "H", "B", "D"]),
-    "aefft_map_overlay_image": (
-        ["aefft_ctx*", "const float*", "int", "int", "float", "float", "int", "const unsigned char*", "int", "unsigned char*", "size_t", "size_t", "int", "int", "int", "int"],
-        ["ctx", "map_d", "Mx", "My", "lo", "hi", "smooth", "lut_d", "alpha", "image_d", "pitch", "image_stride", "W", "H", "B", "D"]),
+    "aefft_frames_resize_to_image": ["aefft_ctx* ctx", "const void* frames_d", "int frames_u8", "int Nx", "int Ny", "int mode", "unsigned char* image_d", "size_t pitch",
+                                     "size_t image_stride", "int W", "int H", "int B", "int D"],
+    "aefft_map_overlay_image": ["aefft_ctx* ctx", "const float* map_d", "int Mx", "int My", "float lo", "float hi", "int smooth", "const unsigned char* lut_d", "int alpha",
+                                "unsigned char* image_d", "size_t pitch", "size_t image_stride", "int W", "int H", "int B", "int D"],
 }
-
-
-def _header():
-    return open(os.path.join(ROOT, "include", "aefft.h")).read()
-
-
-def _lib():
-    if not os.path.exists(aefft.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return aefft.lib()
 
 
 @pytest.mark.parametrize("name", sorted(CALLS))
 def test_declared_exported_and_prototyped(name):
-    types, names = CALLS[name]
-    txt = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
-    _lib()
-    out = subprocess.run(["nm", "-D", "--defined-only", aefft.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    m = re.search(r"int\s+%s\s*\(([^)]*)\)" % name, txt)
-    assert m, f"include/aefft.h does not declare {name}"
-    args = [" ".join(a.split()) for a in m.group(1).split(",")]
-    assert len(args) == len(types), args
-    for a, w, n in zip(args, types, names):
-        assert a == f"{w} {n}", (a, w, n)
-    assert any(l.split()[-1] == name and " T " in l for l in out.splitlines())
-    res, argt = aefft.SIGNATURES[name]
-    assert res is C.c_int and len(argt) == len(types)
-    for t, w in zip(argt, types):
-        assert t is CTYPES[w], w
+    A.check_call(name, CALLS[name])
 
 
 def test_both_calls_stand_in_the_image_boundary_block():
-    h = _header()
-    assert (h.index("int aefft_image_resize_to_frames(") < h.index("int aefft_frames_resize_to_image(") < h.index("int aefft_map_overlay_image(")
-            < h.index("/* ---- network level"))
+    A.in_order(A.header(), "int aefft_image_resize_to_frames(", "int aefft_frames_resize_to_image(", "int aefft_map_overlay_image(", "/* ---- network level")
     # the mode enum and its text are where and what they were
-    assert h.count("enum { AEFFT_RESIZE_LINEAR = 0, AEFFT_RESIZE_AREA = 1 };") == 1 and aefft.RESIZE_MODES == {"linear": 0, "area": 1}
+    assert A.header().count("enum { AEFFT_RESIZE_LINEAR = 0, AEFFT_RESIZE_AREA = 1 };") == 1 and aefft.RESIZE_MODES == {"linear": 0, "area": 1}
 
 
 def test_context_methods_and_heat_lut():
@@ -91,23 +58,21 @@ def test_context_methods_and_heat_lut():
 
 
 def test_null_context_is_einval_without_a_device():
-    L = _lib()
+    L = A.lib()
     buf = (C.c_ubyte * 2048)()
     base = C.addressof(buf)
     base += -base % 16
-    einval = int(re.search(r"AEFFT_EINVAL\s*=\s*(-?\d+)", _header()).group(1))
     frames, image, lut = C.c_void_p(base), C.c_void_p(base + 256), C.c_void_p(base + 1024)
     for mode in (0, 1):
-        assert L.aefft_frames_resize_to_image(None, frames, 1, 4, 4, mode, image, 12, 48, 4, 4, 1, 3) == einval
-    assert L.aefft_frames_resize_to_image(None, None, 0, 0, 0, 0, None, 0, 0, 0, 0, 0, 0) == einval
-    assert L.aefft_map_overlay_image(None, frames, 2, 2, 0.0, 1.0, 1, lut, 128, image, 12, 48, 4, 4, 1, 3) == einval
-    assert L.aefft_map_overlay_image(None, None, 0, 0, 0.0, 0.0, 0, None, 0, None, 0, 0, 0, 0, 0, 0) == einval
+        assert L.aefft_frames_resize_to_image(None, frames, 1, 4, 4, mode, image, 12, 48, 4, 4, 1, 3) == A.EINVAL
+    assert L.aefft_frames_resize_to_image(None, None, 0, 0, 0, 0, None, 0, 0, 0, 0, 0, 0) == A.EINVAL
+    assert L.aefft_map_overlay_image(None, frames, 2, 2, 0.0, 1.0, 1, lut, 128, image, 12, 48, 4, 4, 1, 3) == A.EINVAL
+    assert L.aefft_map_overlay_image(None, None, 0, 0, 0.0, 0.0, 0, None, 0, None, 0, 0, 0, 0, 0, 0) == A.EINVAL
     assert bytes(buf) == bytes(2048)
 
 
 def test_header_states_the_rules():
-    h = _header()
-    one = h[h.index("/* aefft_frames_resize_to_image"):h.index("int aefft_frames_resize_to_image(")]
+    one = A.doc("/* aefft_frames_resize_to_image", "int aefft_frames_resize_to_image(")
     for word in ("mirror of aefft_image_resize_to_frames", "autoencoder.cpp:217-223", "16-byte aligned", "p[y][x] = frames[b][d][x][y]", "px_u8(frames[b][d][x][y])",
                  "clamp((int)round(v), 0, 255)", "halves away from zero", "NaN -> 0", "first turned into pixels, then resized", "b * image_stride",
                  "y * pitch + x * D + d", "pitch >= W * D", "image_stride >= (H - 1) * pitch + W * D", "ANY alignment", "never written", "region of interest",
@@ -116,7 +81,7 @@ def test_header_states_the_rules():
                  "no intermediate image", "unmeasured", "One launch", "no allocation", "no workspace", "stream capture", "Out-of-place", "AEFFT_EINVAL",
                  '"aefft_frames_resize_to_image: "', "unknown mode", "enlarging axis", "overlap", "overflow the address space"):
         assert word in one, word
-    two = h[h.index("/* aefft_map_overlay_image"):h.index("int aefft_map_overlay_image(")]
+    two = A.doc("/* aefft_map_overlay_image", "int aefft_map_overlay_image(")
     for word in ("in place", "[B][Mx][My]", "16-byte aligned", "Mx along image columns", "My contiguous", "1..1024", "256 * D bytes", "k * D + d", "any alignment",
                  "ships no colour map", "alpha in 0..256", "hi < lo inverts the scale", "inv = 255.0f / (hi - lo)", "px_u8((map[b][I][J] - lo) * inv)",
                  "each rounded to float32", "NaN -> 0", "halves away from zero", "k0[floor(x Mx / W)][floor(y My / H)]", "AEFFT_RESIZE_LINEAR taps",
@@ -126,40 +91,19 @@ def test_header_states_the_rules():
         assert word in two, word
 
 
-def _resource_blocks(name):
-    _lib()
-    path = os.path.join(CSRC, "build", name)
-    assert os.path.exists(path), f"{path}: the build writes the back end's resource table beside every object (csrc/Makefile)"
-    for b in re.split(r"(?=remark: [^\n]*Function Name: )", open(path).read()):
-        m = re.search(r"Function Name: (\S+)", b)
-        if m:
-            yield m.group(1), b
-
-
 def test_present_kernels_use_no_scratch_and_cover_every_instantiation():
     """build/present_kernels.rsrc: frames_resize_kernel<D, F32, MODE> for D = 1..4 x {8-bit, float} x {linear, area} and map_overlay_kernel<D> for
     D = 1..4 -- what the two launchers select -- nothing else, each with zero scratch and zero spills"""
-    resize, overlay = set(), set()
-    for fn, b in _resource_blocks("present_kernels.rsrc"):
-        k = re.search(r"\d+frames_resize_kernelILi(\d)ELb([01])ELi([01])EEE", fn)
-        o = re.search(r"\d+map_overlay_kernelILi(\d)EEE", fn)
-        assert k or o, fn
-        if k:
-            resize.add((int(k.group(1)), k.group(2) == "1", int(k.group(3))))
-        else:
-            overlay.add(int(o.group(1)))
-        for key in ("ScratchSize \\[bytes/lane\\]", "SGPRs Spill", "VGPRs Spill"):
-            v = re.search(key + r": (\d+)", b)
-            assert v and int(v.group(1)) == 0, (fn, key)
-    assert resize == {(d, f, m) for d in (1, 2, 3, 4) for f in (False, True) for m in (0, 1)}
-    assert overlay == {1, 2, 3, 4}
+    resize, overlay = A.instantiations("present_kernels.rsrc", r"\d+frames_resize_kernelILi(\d)ELb([01])ELi([01])EEE", r"\d+map_overlay_kernelILi(\d)EEE")
+    assert resize == {(d, f, m) for d in "1234" for f in "01" for m in "01"}
+    assert overlay == {(d,) for d in "1234"}
     assert "present_kernels.hip" in open(os.path.join(CSRC, "Makefile")).read()
 
 
 def test_the_older_kernel_files_keep_their_kernels_and_the_taps_are_stated_once():
-    got = {re.search(r"aefft\d+(\w+?_kernel)I", fn).group(1) for fn, _ in _resource_blocks("resize_kernels.rsrc")}
-    assert got == {"resize_kernel"} and len(list(_resource_blocks("resize_kernels.rsrc"))) == 16
-    got = {re.search(r"aefft\d+(\w+?_kernel)I", fn).group(1) for fn, _ in _resource_blocks("image_kernels.rsrc")}
+    got = {re.search(r"aefft\d+(\w+?_kernel)I", fn).group(1) for fn in A.rsrc("resize_kernels.rsrc")}
+    assert got == {"resize_kernel"} and len(A.rsrc("resize_kernels.rsrc")) == 16
+    got = {re.search(r"aefft\d+(\w+?_kernel)I", fn).group(1) for fn in A.rsrc("image_kernels.rsrc")}
     assert got == {"image_unpack_kernel", "image_pack_kernel"}
     # one definition of the tap formulas, in the header both kernel files include
     defs = {}

@@ -3,56 +3,28 @@ needs no device; the header's description of the arithmetic; the development-swi
 instantiation of the resize kernel in the back end's resource table (no scratch, no spills), D = 1..4 x {8-bit, float} x {linear, area}; the
 Python layout helper."""
 import ctypes as C
-import importlib
 import inspect
 import os
 import re
-import subprocess
 
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-aefft = importlib.import_module("autoencoder-fft_amd")
-NFLAGS = 26      # AEFFT_F_* switches of the library
+import abi_checks as A
+from abi_checks import CSRC, aefft
+
 NAME = "aefft_image_resize_to_frames"
-ARGS = ["aefft_ctx*", "const unsigned char*", "size_t", "size_t", "int", "int", "int", "void*", "int", "int", "int", "int", "int"]
-NAMES = ["ctx", "image_d", "pitch", "image_stride", "W", "H", "mode", "frames_d", "frames_u8", "B", "D", "Nx", "Ny"]
-CTYPES = {"aefft_ctx*": C.c_void_p, "const unsigned char*": C.c_void_p, "void*": C.c_void_p, "size_t": C.c_size_t, "int": C.c_int}
-
-
-def _header():
-    return open(os.path.join(ROOT, "include", "aefft.h")).read()
-
-
-def _lib():
-    if not os.path.exists(aefft.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return aefft.lib()
+ARGS = ["aefft_ctx* ctx", "const unsigned char* image_d", "size_t pitch", "size_t image_stride", "int W", "int H", "int mode", "void* frames_d", "int frames_u8",
+        "int B", "int D", "int Nx", "int Ny"]
 
 
 def test_declared_exported_and_prototyped():
-    txt = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
-    _lib()
-    out = subprocess.run(["nm", "-D", "--defined-only", aefft.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    m = re.search(r"int\s+%s\s*\(([^)]*)\)" % NAME, txt)
-    assert m, f"include/aefft.h does not declare {NAME}"
-    args = [" ".join(a.split()) for a in m.group(1).split(",")]
-    assert len(args) == len(ARGS), args
-    for a, w, n in zip(args, ARGS, NAMES):
-        assert a == f"{w} {n}", (a, w, n)
-    assert any(l.split()[-1] == NAME and " T " in l for l in out.splitlines())
-    res, argt = aefft.SIGNATURES[NAME]
-    assert res is C.c_int and len(argt) == len(ARGS)
-    for t, w in zip(argt, ARGS):
-        assert t is CTYPES[w], w
+    A.check_call(NAME, ARGS)
     # in the image-boundary block: after aefft_frames_to_image, before the network level
-    h = _header()
-    assert h.index("int aefft_frames_to_image(") < h.index("enum { AEFFT_RESIZE_LINEAR") < h.index("int " + NAME) < h.index("/* ---- network level")
+    A.in_order(A.header(), "int aefft_frames_to_image(", "enum { AEFFT_RESIZE_LINEAR", "int " + NAME, "/* ---- network level")
 
 
 def test_mode_values_are_pinned():
-    m = re.search(r"enum\s*\{\s*AEFFT_RESIZE_LINEAR\s*=\s*(\d+)\s*,\s*AEFFT_RESIZE_AREA\s*=\s*(\d+)\s*\}", _header())
+    m = re.search(r"enum\s*\{\s*AEFFT_RESIZE_LINEAR\s*=\s*(\d+)\s*,\s*AEFFT_RESIZE_AREA\s*=\s*(\d+)\s*\}", A.header())
     assert m and (int(m.group(1)), int(m.group(2))) == (0, 1)
     assert aefft.RESIZE_MODES == {"linear": 0, "area": 1}
 
@@ -65,20 +37,18 @@ def test_context_method_signature():
 
 
 def test_null_context_is_einval_without_a_device():
-    L = _lib()
+    L = A.lib()
     buf = (C.c_ubyte * 512)()
-    einval = int(re.search(r"AEFFT_EINVAL\s*=\s*(-?\d+)", _header()).group(1))
     src, dst = C.cast(buf, C.c_void_p), C.c_void_p(C.addressof(buf) + 256)
     f = L.aefft_image_resize_to_frames
     for mode in (0, 1):
-        assert f(None, src, 24, 192, 8, 8, mode, dst, 1, 1, 3, 4, 4) == einval
-    assert f(None, None, 0, 0, 0, 0, 0, None, 0, 0, 0, 0, 0) == einval
+        assert f(None, src, 24, 192, 8, 8, mode, dst, 1, 1, 3, 4, 4) == A.EINVAL
+    assert f(None, None, 0, 0, 0, 0, 0, None, 0, 0, 0, 0, 0) == A.EINVAL
     assert bytes(buf) == bytes(512)
 
 
 def test_header_describes_the_call():
-    h = _header()
-    doc = h[h.index("/* aefft_image_resize_to_frames"):h.index("enum { AEFFT_RESIZE_LINEAR")]
+    doc = A.doc("/* aefft_image_resize_to_frames", "enum { AEFFT_RESIZE_LINEAR")
     for word in ("autoencoder.cpp:124-125", "b * image_stride", "y * pitch + x * D + d", "pitch >= W * D", "image_stride >= (H - 1) * pitch + W * D",
                  "ANY alignment", "region\n * of interest", "image_d + y0 * pitch + x0 * D", "never read", "16-byte aligned", "destination column i, destination row j",
                  "D in 1..4", "1..8192", "all-integer", "half-pixel centres", "edges replicated", "1/2048", "n = (2i+1) S - N", "den = 2N", "s = floor(n / den)",
@@ -92,43 +62,22 @@ def test_header_describes_the_call():
 
 def test_flag_option_and_profiler_tables_are_unchanged():
     """the call adds no development switch, no net option and no profiling id (it is accounted under `image`)"""
-    bits = dict((n, int(b)) for n, b in re.findall(r"\b(AEFFT_F_[A-Z0-9]+)\s*=\s*1\s*<<\s*(\d+)", _header()))
-    assert len(bits) == NFLAGS and len(set(bits.values())) == NFLAGS
-    assert not [n for n in bits if "RESIZE" in n or "IMAGE" in n]
-    opts = re.findall(r"\b(AEFFT_NET_[A-Z_]+)\s*=\s*1u\s*<<\s*\d+", _header())
-    assert opts == ["AEFFT_NET_SMOOTH_SIZES", "AEFFT_NET_SPATIAL", "AEFFT_NET_SMOOTH_OPFORM"]
-    L = _lib()
-    L.aefft_prof_name.restype = C.c_char_p
-    names = [L.aefft_prof_name(k).decode() for k in range(L.aefft_prof_count())]
-    assert names[-2:] == ["target", "ssim"] and names.count("image") == 1 and not [n for n in names if "image_" in n]
+    names = A.tables_unchanged("RESIZE", "IMAGE", profiler=("image_",))[1]
+    assert names.count("image") == 1
 
 
 def test_resize_kernels_use_no_scratch_and_cover_every_instantiation():
     """build/resize_kernels.rsrc: resize_kernel<D, F32, MODE> for D = 1..4 x {8-bit, float} x {linear, area} -- what launch_image_resize's switch
     selects -- nothing else, each with zero scratch and zero spills; the launcher's source names exactly those"""
-    _lib()
-    csrc = os.path.join(ROOT, "autoencoder-fft_amd", "csrc")
-    path = os.path.join(csrc, "build", "resize_kernels.rsrc")
-    assert os.path.exists(path), f"{path}: the build writes the back end's resource table beside every object (csrc/Makefile)"
-    got = set()
-    for b in re.split(r"(?=remark: [^\n]*Function Name: )", open(path).read()):
-        m = re.search(r"Function Name: (\S+)", b)
-        if not m:
-            continue
-        k = re.search(r"\d+resize_kernelILi(\d)ELb([01])ELi([01])EEE", m.group(1))
-        assert k, m.group(1)
-        got.add((int(k.group(1)), k.group(2) == "1", int(k.group(3))))
-        for key in ("ScratchSize \\[bytes/lane\\]", "SGPRs Spill", "VGPRs Spill"):
-            v = re.search(key + r": (\d+)", b)
-            assert v and int(v.group(1)) == 0, (m.group(1), key)
-    want = {(d, f, m) for d in (1, 2, 3, 4) for f in (False, True) for m in (0, 1)}
+    [got] = A.instantiations("resize_kernels.rsrc", r"\d+resize_kernelILi(\d)ELb([01])ELi([01])EEE")
+    want = {(d, f, m) for d in "1234" for f in "01" for m in "01"}
     assert got == want, sorted(got ^ want)
-    src = open(os.path.join(csrc, "resize_kernels.hip")).read()
+    src = open(os.path.join(CSRC, "resize_kernels.hip")).read()
     assert re.findall(r"RZ_CASES\((\d)\)", src.split("switch (D * 4")[1]) == ["1", "2", "3", "4"]
     assert "RZ_CASE(DD, 0, 0) RZ_CASE(DD, 0, 1) RZ_CASE(DD, 1, 0) RZ_CASE(DD, 1, 1)" in src
-    assert "resize_kernels.hip" in open(os.path.join(csrc, "Makefile")).read()
+    assert "resize_kernels.hip" in open(os.path.join(CSRC, "Makefile")).read()
     # image_kernels.hip is left alone: the resize kernels live in a file of their own
-    assert "resize" not in open(os.path.join(csrc, "image_kernels.hip")).read()
+    assert "resize" not in open(os.path.join(CSRC, "image_kernels.hip")).read()
 
 
 def test_python_layout_rules_need_no_device():

@@ -2,42 +2,14 @@
 device; the development-switch tables unchanged; the two score kernels and every scoring instantiation of the two inverse row kernels in
 the back end's resource tables (no scratch, no spills)."""
 import ctypes as C
-import importlib
 import inspect
-import os
-import re
-import subprocess
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-aefft = importlib.import_module("autoencoder-fft_amd")
-NFLAGS = 26      # AEFFT_F_* switches of the library
-
-
-def _header():
-    return open(os.path.join(ROOT, "include", "aefft.h")).read()
-
-
-def _lib():
-    if not os.path.exists(aefft.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return aefft.lib()
+import abi_checks as A
+from abi_checks import aefft
 
 
 def test_declared_exported_and_prototyped():
-    txt = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
-    m = re.search(r"int\s+aefft_net_score\s*\(([^)]*)\)", txt)
-    assert m, "include/aefft.h does not declare aefft_net_score"
-    args = [a.strip() for a in m.group(1).split(",")]
-    assert len(args) == 5
-    assert args[0].startswith("aefft_net*") and args[1].startswith("const void*") and args[2].startswith("int")
-    assert args[3].startswith("float*") and args[4].startswith("float*")
-    _lib()
-    out = subprocess.run(["nm", "-D", "--defined-only", aefft.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert any(l.split()[-1] == "aefft_net_score" and " T " in l for l in out.splitlines())
-    res, argt = aefft.SIGNATURES["aefft_net_score"]
-    assert res is C.c_int and len(argt) == 5
-    assert argt[2] is C.c_int
+    A.check_call("aefft_net_score", ["aefft_net* net", "const void* frames_d", "int frames_u8", "float* score_d", "float* recon_d"])
 
 
 def test_net_score_signature():
@@ -47,17 +19,15 @@ def test_net_score_signature():
 
 
 def test_null_net_is_einval_without_a_device():
-    L = _lib()
+    L = A.lib()
     buf = (C.c_float * 64)()
-    einval = int(re.search(r"AEFFT_EINVAL\s*=\s*(-?\d+)", _header()).group(1))
     fp = C.cast(buf, C.POINTER(C.c_float))
-    assert L.aefft_net_score(None, C.cast(buf, C.c_void_p), 0, fp, fp) == einval
-    assert L.aefft_net_score(None, None, 1, None, None) == einval
+    assert L.aefft_net_score(None, C.cast(buf, C.c_void_p), 0, fp, fp) == A.EINVAL
+    assert L.aefft_net_score(None, None, 1, None, None) == A.EINVAL
 
 
 def test_header_describes_the_call():
-    h = _header()
-    doc = h[h.index("Per-frame reconstruction error"):h.index("int aefft_net_score")]
+    doc = A.doc("Per-frame reconstruction error", "int aefft_net_score")
     for word in ("autoenc_fft", "fft_backproplib.cu:1331-1376", "Parseval", "mse_fft", ":480-498", ":1178-1192", "2*dM", "ROUNDED", "contracting",
                  "bit for bit what aefft_net_infer writes", "no 8-bit reconstruction", "aefft_net_step_form", "aefft_net_step_grad", "AEFFT_ESTATE",
                  "no atomics", "does not depend on the other frames", "AEFFT_F_CHIRPZ", "AEFFT_EINVAL", "16-byte aligned", "no allocation"):
@@ -66,49 +36,16 @@ def test_header_describes_the_call():
 
 def test_flag_tables_are_unchanged():
     """the call adds no development switch and no net option"""
-    bits = dict((n, int(b)) for n, b in re.findall(r"\b(AEFFT_F_[A-Z0-9]+)\s*=\s*1\s*<<\s*(\d+)", _header()))
-    assert len(bits) == NFLAGS and len(set(bits.values())) == NFLAGS
-    assert not [n for n in bits if "SCORE" in n]
-    opts = re.findall(r"\b(AEFFT_NET_[A-Z_]+)\s*=\s*1u\s*<<\s*\d+", _header())
-    assert opts == ["AEFFT_NET_SMOOTH_SIZES", "AEFFT_NET_SPATIAL", "AEFFT_NET_SMOOTH_OPFORM"]
-
-
-def _blocks(fn):
-    path = os.path.join(ROOT, "autoencoder-fft_amd", "csrc", "build", fn)
-    assert os.path.exists(path), f"{path}: the build writes the back end's resource table beside every object (csrc/Makefile)"
-    for b in re.split(r"(?=remark: [^\n]*Function Name: )", open(path).read()):
-        m = re.search(r"Function Name: (\S+)", b)
-        if m:
-            yield m.group(1), b
-
-
-def _no_scratch(name, block):
-    for key in ("ScratchSize \\[bytes/lane\\]", "SGPRs Spill", "VGPRs Spill"):
-        v = re.search(key + r": (\d+)", block)
-        assert v and int(v.group(1)) == 0, (name, key)
+    A.tables_unchanged("SCORE")
 
 
 def test_score_kernels_use_no_scratch():
     """build/<file>.rsrc (the back end's resource table): score_finish_kernel, both score_diff_kernel instantiations, and every scoring
     instantiation of the two inverse row kernels -- the last template argument (1: float frames, 2: 8-bit frames) behind U8 = false: nine
     dense and five sparse sizes of the power-of-two kernel, five thread classes of the mixed-radix one, each for both frame types"""
-    _lib()
-    seen = {"score_finish_kernel": 0, "score_diff_kernel": 0}
-    for name, b in _blocks("score_kernels.rsrc"):
-        for k in seen:
-            if k in name:
-                seen[k] += 1
-                _no_scratch(name, b)
-    assert seen == {"score_finish_kernel": 1, "score_diff_kernel": 2}, seen
-    rows = {}
-    for fn, pat in (("fft_kernels.rsrc", r"\d+c2r_rows_kernelILi(\d+)ELb([01])ELb0ELi([12])EEE"), ("fft_mixed_kernels.rsrc", r"mix_c2r_rows_kernelILi(\d+)ELb0ELi([12])EEE")):
-        got = set()
-        for name, b in _blocks(fn):
-            m = re.search(pat, name)
-            if m:
-                got.add(m.groups())
-                _no_scratch(name, b)
-        rows[fn] = got
+    finish, diff = A.instantiations("score_kernels.rsrc", r"(\S*score_finish_kernel\S*)", r"(\S*score_diff_kernel\S*)", every=False)
+    assert (len(finish), len(diff)) == (1, 2), (finish, diff)
+    rows = A.scoring_rows("12")
     sizes = [8, 16, 32, 64, 128, 256, 512, 1024, 2048]
     want = {(str(n), sp, sc) for n in sizes for sp in "01" for sc in "12" if sp == "0" or n >= 128}
     assert rows["fft_kernels.rsrc"] == want, sorted(rows["fft_kernels.rsrc"] ^ want)

@@ -2,19 +2,18 @@
 symbols, the host-side functions against the compiled reference (CPU), and the vector entry points
 against the oracle (GPU)."""
 import ctypes as C
-import importlib
 import os
 import subprocess
 
 import numpy as np
 import pytest
 
+import abi_checks as A
 import cpu
 import np_ref as R
 import np_spatial as S
+from abi_checks import ROOT, aefft
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-aefft = importlib.import_module("autoencoder-fft_amd")
 FP = C.POINTER(C.c_float)
 
 # SURVEY.md Appendix D: the symbols autoencoder.cpp imports (libstdc++ mangling)
@@ -45,9 +44,7 @@ def _p(a):
 
 @pytest.fixture(scope="module")
 def wrap():
-    if not os.path.exists(aefft.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
+    A.lib()
     out = os.path.join(ROOT, "tests", "_shim_wrap.so")
     src = os.path.join(ROOT, "tests", "shim_wrap.cpp")
     libdir = os.path.dirname(aefft.LIB_PATH)
@@ -61,9 +58,7 @@ def wrap():
 
 
 def test_reference_symbols_exported():
-    out = subprocess.run(["nm", "-D", "--defined-only", aefft.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    exported = set(l.split()[-1] for l in out.splitlines())
-    assert not [s for s in WANTED if s not in exported]
+    assert not [s for s in WANTED if s not in A.exported()]
 
 
 def test_headers_declare_the_reference_manglings(tmp_path):

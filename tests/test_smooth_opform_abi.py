@@ -1,24 +1,17 @@
 """AEFFT_NET_SMOOTH_OPFORM at the boundary (no GPU): the header's value, the Python constant and Net's keyword, and the exported symbol
 set of libaefft.so -- the option adds no entry point."""
-import importlib
 import inspect
-import os
 import re
-import subprocess
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-aefft = importlib.import_module("autoencoder-fft_amd")
-
-
-def _header():
-    return open(os.path.join(ROOT, "include", "aefft.h")).read()
+import abi_checks as A
+from abi_checks import aefft
 
 
 def test_header_declares_the_option_as_bit_2():
-    m = re.search(r"AEFFT_NET_SMOOTH_OPFORM\s*=\s*1u\s*<<\s*(\d+)", _header())
+    m = re.search(r"AEFFT_NET_SMOOTH_OPFORM\s*=\s*1u\s*<<\s*(\d+)", A.header())
     assert m and int(m.group(1)) == 2
     # in the option enum of aefft_net_create_ex, next to its neighbours
-    enum = re.search(r"enum\s*\{([^}]*AEFFT_NET_SMOOTH_SIZES[^}]*)\}", _header()).group(1)
+    enum = re.search(r"enum\s*\{([^}]*AEFFT_NET_SMOOTH_SIZES[^}]*)\}", A.header()).group(1)
     assert "AEFFT_NET_SMOOTH_OPFORM" in enum and "AEFFT_NET_SPATIAL" in enum
 
 
@@ -32,13 +25,8 @@ def test_python_constant_and_keyword():
 
 def test_exported_symbols_are_the_declared_ones():
     """every aefft_* symbol libaefft.so exports is one include/aefft.h declares, and the reverse: the option came without an entry point"""
-    if not os.path.exists(aefft.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    txt = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
-    declared = set(re.findall(r"\b(aefft_[a-z0-9_]+)\s*\(", txt))
-    out = subprocess.run(["nm", "-D", "--defined-only", aefft.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    exported = set(l.split()[-1] for l in out.splitlines() if " T " in l and l.split()[-1].startswith("aefft_"))
+    declared = set(re.findall(r"\b(aefft_[a-z0-9_]+)\s*\(", A.header_code()))
+    exported = {n for n in A.exported() if n.startswith("aefft_")}
     assert exported == declared, (sorted(exported - declared), sorted(declared - exported))
     assert exported == set(aefft.SIGNATURES)
     assert not [n for n in exported if "opform" in n]

@@ -1,30 +1,20 @@
 """CPU-side checks of the spatial net's surface (no compute call is made): include/aefft.h declares AEFFT_NET_SPATIAL, AEFFT_FORM_SPATIAL
 and aefft_net_set_inertia, libaefft.so exports the function, and the Python constants match the header."""
-import importlib
-import os
 import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-aefft = importlib.import_module("autoencoder-fft_amd")
+import abi_checks as A
+from abi_checks import aefft
 
 
 @pytest.fixture(scope="module")
 def built():
-    if not os.path.exists(aefft.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return aefft.lib()
-
-
-def _header():
-    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "aefft.h")).read(), flags=re.S)
+    return A.lib()
 
 
 def test_header_declares_the_spatial_net():
-    txt = _header()
+    txt = A.header_code()
     m = re.search(r"AEFFT_NET_SPATIAL\s*=\s*1u?\s*<<\s*(\d+)", txt)
     assert m and int(m.group(1)) == 1
     assert 1 << int(m.group(1)) == aefft.NET_SPATIAL
@@ -33,8 +23,7 @@ def test_header_declares_the_spatial_net():
 
 
 def test_set_inertia_exported_and_checks_its_net(built):
-    out = subprocess.run(["nm", "-D", "--defined-only", aefft.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert "aefft_net_set_inertia" in set(l.split()[-1] for l in out.splitlines() if " T " in l)
+    assert "aefft_net_set_inertia" in A.exported()
     assert "aefft_net_set_inertia" in aefft.SIGNATURES
     assert built.aefft_net_set_inertia(None, 0.5) == aefft.EINVAL
 

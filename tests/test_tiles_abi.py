@@ -4,21 +4,18 @@ against the numpy restatement of tiles_ref.py on a sweep; the properties of the 
 two tiles per axis, the kept areas cover the image, blend(gather(x)) == x); the argument errors that need no device; the Python layout rules;
 every instantiation of the kernels in the back end's resource table (no scratch, no spills); the host check program."""
 import ctypes as C
-import importlib
 import inspect
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import abi_checks as A
 import tiles_ref as R
+from abi_checks import CSRC, ROOT, aefft
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-aefft = importlib.import_module("autoencoder-fft_amd")
-CSRC = os.path.join(ROOT, "autoencoder-fft_amd", "csrc")
 PLAN, GATHER, BLEND = "aefft_tile_plan_make", "aefft_image_tiles_to_frames", "aefft_frames_tiles_to_image"
 PROTOS = {
     PLAN: ["const aefft_tile_desc* desc", "aefft_tile_plan* plan"],
@@ -28,17 +25,6 @@ PROTOS = {
             "size_t image_stride", "int B", "int D"],
 }
 FIELDS = ["ntx", "nty", "ox0", "oy0", "step_x", "step_y", "ramp_x", "ramp_y"]
-
-
-def _header():
-    return open(os.path.join(ROOT, "include", "aefft.h")).read()
-
-
-def _lib():
-    if not os.path.exists(aefft.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return aefft.lib()
 
 
 def _sweep():
@@ -55,24 +41,11 @@ WIDTHS = list(range(1, 41)) + [130, 641, 1920]
 
 # 1.
 def test_declared_exported_and_prototyped():
-    txt = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
     for name, want in PROTOS.items():
-        m = re.search(r"int\s+%s\s*\(([^)]*)\)" % name, txt)
-        assert m, f"include/aefft.h does not declare {name}"
-        assert [" ".join(a.split()) for a in m.group(1).split(",")] == want
+        A.check_call(name, want, {"const aefft_tile_desc*": aefft.TileDesc, "aefft_tile_plan*": aefft.TilePlan})
     for struct, fields in (("aefft_tile_desc", ["W", "H", "Nx", "Ny", "overlap_x", "overlap_y", "rim_x", "rim_y"]), ("aefft_tile_plan", FIELDS)):
-        m = re.search(r"typedef\s+struct\s*\{([^}]*)\}\s*%s\s*;" % struct, txt)
-        assert m, struct
-        assert re.findall(r"\b(?!int\b)([A-Za-z_0-9]+)\s*[,;]", m.group(1)) == fields
-    _lib()
-    out = subprocess.run(["nm", "-D", "--defined-only", aefft.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    for name in PROTOS:
-        assert any(l.split()[-1] == name and " T " in l for l in out.splitlines()), name
-    vp, i, sz = C.c_void_p, C.c_int, C.c_size_t
-    td, tp = C.POINTER(aefft.TileDesc), C.POINTER(aefft.TilePlan)
-    assert aefft.SIGNATURES[PLAN] == (i, [td, tp])
-    assert aefft.SIGNATURES[GATHER] == (i, [vp, vp, sz, sz, td, vp, i, i, i])
-    assert aefft.SIGNATURES[BLEND] == (i, [vp, vp, i, td, vp, sz, sz, i, i])
+        decls = A.struct_fields(struct)
+        assert all(d.startswith("int ") for d in decls) and [n for d in decls for n in d[len("int "):].split(", ")] == fields
     assert [f[0] for f in aefft.TileDesc._fields_] == ["W", "H", "Nx", "Ny", "overlap_x", "overlap_y", "rim_x", "rim_y"]
     assert [f[0] for f in aefft.TilePlan._fields_] == FIELDS
     assert all(f[1] is C.c_int for f in aefft.TileDesc._fields_ + aefft.TilePlan._fields_)
@@ -87,16 +60,13 @@ def test_declared_exported_and_prototyped():
 
 # 2.
 def test_the_calls_stand_behind_yuv_resize_in_the_image_boundary_block():
-    h = _header()
-    pos = [h.index("int aefft_yuv_resize_to_frames("), h.index("/* aefft_tile_plan_make"), h.index("} aefft_tile_desc;"), h.index("} aefft_tile_plan;"),
-           h.index("int %s(" % PLAN), h.index("int %s(" % GATHER), h.index("int %s(" % BLEND), h.index("/* ---- network level")]
-    assert pos == sorted(pos)
+    A.in_order(A.header(), "int aefft_yuv_resize_to_frames(", "/* aefft_tile_plan_make", "} aefft_tile_desc;", "} aefft_tile_plan;", "int %s(" % PLAN,
+               "int %s(" % GATHER, "int %s(" % BLEND, "/* ---- network level")
 
 
 # 3.
 def test_header_states_the_formulas():
-    h = _header()
-    doc = " ".join(re.sub(r"\n \* ", "\n", h[h.index("/* aefft_tile_plan_make"):h.index("} aefft_tile_desc;")]).split())      # (without the comment's margin)
+    doc = A.doc("/* aefft_tile_plan_make", "} aefft_tile_desc;", margin=False)
     for word in ("S = N - V", "R = V - 2M", "n = max(1, ceil((W - N + 2M) / S) + 1)", "[o_t + M, o_t + N - M)", "E = (n-1) S + N - 2M - W >= 0",
                  "o_0 = -M - floor(E / 2)", "o_t = o_0 + t S", "integer arithmetic only", "1..8192", "2..2048", "0 <= 2 V <= N", "0 <= 2 M <= V",
                  "at most two tiles per axis", "(1920, 512, 64, 8) gives n = 5, S = 448, R = 48, o_0 = -192", "(13, 8, 4, 1) gives n = 3, S = 4, R = 2, o_0 = -1",
@@ -125,7 +95,7 @@ def _make(L, W, H, Nx, Ny, vx, vy, mx, my):
 
 
 def test_the_plan_equals_the_restatement_on_a_sweep():
-    L = _lib()
+    L = A.lib()
     n = 0
     for k, (N, V, M) in enumerate(_sweep()):
         for W in WIDTHS:
@@ -185,7 +155,7 @@ def test_blend_of_gather_is_the_image_on_the_restatement():
 
 # 7.
 def test_every_illegal_description_is_einval_and_leaves_the_plan_untouched():
-    L = _lib()
+    L = A.lib()
     good = dict(W=13, H=9, Nx=8, Ny=8, vx=4, vy=4, mx=1, my=1)
     assert _make(L, **good)[0] == aefft.OK
     for bad in (dict(W=0), dict(W=8193), dict(H=0), dict(H=-1), dict(H=8193), dict(Nx=1), dict(Nx=2049), dict(Ny=1), dict(Ny=0), dict(Ny=2049),
@@ -213,7 +183,7 @@ def test_every_illegal_description_is_einval_and_leaves_the_plan_untouched():
 
 # 8.
 def test_null_context_is_einval_without_a_device():
-    L = _lib()
+    L = A.lib()
     buf = (C.c_ubyte * 4096)()
     base = C.addressof(buf)
     base += -base % 16
@@ -263,21 +233,8 @@ def test_python_layout_rules_need_no_device():
 def test_tile_kernels_use_no_scratch_and_cover_every_instantiation():
     """build/tile_kernels.rsrc: tile_gather_kernel<D, F32> and tile_blend_kernel<D, F32> for D = 1..4 x {8-bit, float} frames -- what the launcher
     selects (the dword and element routes are chosen inside a kernel) -- nothing else, each with zero scratch and zero spills"""
-    _lib()
-    path = os.path.join(CSRC, "build", "tile_kernels.rsrc")
-    assert os.path.exists(path), f"{path}: the build writes the back end's resource table beside every object (csrc/Makefile)"
-    got = set()
-    for b in re.split(r"(?=remark: [^\n]*Function Name: )", open(path).read()):
-        m = re.search(r"Function Name: (\S+)", b)
-        if not m:
-            continue
-        k = re.search(r"\d+tile_(gather|blend)_kernelILi(\d)ELb([01])EEE", m.group(1))
-        assert k, m.group(1)
-        got.add((k.group(1), int(k.group(2)), k.group(3) == "1"))
-        for key in ("ScratchSize \\[bytes/lane\\]", "SGPRs Spill", "VGPRs Spill"):
-            v = re.search(key + r": (\d+)", b)
-            assert v and int(v.group(1)) == 0, (m.group(1), key)
-    assert got == {(k, d, f) for k in ("gather", "blend") for d in (1, 2, 3, 4) for f in (False, True)}
+    [got] = A.instantiations("tile_kernels.rsrc", r"\d+tile_(gather|blend)_kernelILi(\d)ELb([01])EEE")
+    assert got == {(k, d, f) for k in ("gather", "blend") for d in "1234" for f in "01"}
     assert "tile_kernels.hip" in open(os.path.join(CSRC, "Makefile")).read()
     # the launchers are declared with the others, the entry points stand with the image calls and share their helpers
     internal = open(os.path.join(CSRC, "internal.h")).read()
@@ -295,14 +252,7 @@ def test_tile_kernels_use_no_scratch_and_cover_every_instantiation():
 
 # 11.
 def test_the_host_check_program_is_there_and_stands_alone():
-    path = os.path.join(ROOT, "tools", "tiles_hostcheck.cpp")
-    assert os.path.exists(path)
-    src = open(path).read()
-    assert '#include "../autoencoder-fft_amd/csrc/tile_kernels.hip"' in src and "int main(" in src and "-fsanitize=address,undefined" in src
-    assert "Python.h" not in src and "hip_runtime" not in src
-    lanes = open(os.path.join(ROOT, "tools", "hostlanes.h")).read()
-    assert '#include "hostlanes.h"' in src and "#define AEFFT_HOSTCHECK" in lanes
-    assert "Python.h" not in lanes and "hip_runtime" not in lanes and "LD_PRELOAD" not in lanes
+    A.host_check_stands_alone("tiles_hostcheck.cpp", "tile_kernels.hip")
     assert os.path.exists(os.path.join(ROOT, "tools", "tiles_bench.py"))
     # the product never imports the restatement
     for dirpath, _, files in os.walk(os.path.join(ROOT, "autoencoder-fft_amd")):

@@ -4,67 +4,34 @@ layouts); the development-switch, net-option and profiler tables unchanged; ever
 (no scratch, no spills) and resize_kernels.rsrc still at its 16; the stand-alone host check; the coefficient table re-derived from Kr, Kb; properties
 of the numpy restatement (tests/yuv_ref.py), among them its distance from the real formula over all 2^24 triples; the Python argument checks."""
 import ctypes as C
-import importlib
 import inspect
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import abi_checks as A
 import yuv_ref as R
+from abi_checks import CSRC, aefft
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "autoencoder-fft_amd", "csrc")
-aefft = importlib.import_module("autoencoder-fft_amd")
-NFLAGS = 26      # AEFFT_F_* switches of the library
 PROTOS = {
     "aefft_yuv_to_image": ["aefft_ctx* ctx", "const aefft_yuv_desc* src", "int order", "unsigned char* image_d", "size_t pitch", "size_t image_stride", "int B"],
     "aefft_yuv_resize_to_frames": ["aefft_ctx* ctx", "const aefft_yuv_desc* src", "int order", "int mode", "void* frames_d", "int frames_u8", "int B", "int Nx", "int Ny"],
 }
 
 
-def _header():
-    return open(os.path.join(ROOT, "include", "aefft.h")).read()
-
-
-def _lib():
-    if not os.path.exists(aefft.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return aefft.lib()
-
-
 def test_declared_exported_prototyped_and_placed():
-    h = _header()
-    txt = re.sub(r"/\*.*?\*/", "", h, flags=re.S)
-    _lib()
-    out = subprocess.run(["nm", "-D", "--defined-only", aefft.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    ctypes_of = {"aefft_ctx*": C.c_void_p, "unsigned char*": C.c_void_p, "void*": C.c_void_p, "size_t": C.c_size_t, "int": C.c_int}
     for name, want in PROTOS.items():
-        m = re.search(r"int\s+%s\s*\(([^)]*)\)" % name, txt)
-        assert m, f"include/aefft.h does not declare {name}"
-        assert [" ".join(a.split()) for a in m.group(1).split(",")] == want
-        assert any(l.split()[-1] == name and " T " in l for l in out.splitlines()), name
-        res, argt = aefft.SIGNATURES[name]
-        assert res is C.c_int and len(argt) == len(want)
-        for t, w in zip(argt, want):
-            typ = w.rsplit(" ", 1)[0]
-            if typ == "const aefft_yuv_desc*":
-                assert t._type_ is aefft.YuvDesc
-            else:
-                assert t is ctypes_of[typ], w
+        A.check_call(name, want, {"const aefft_yuv_desc*": aefft.YuvDesc})
     # the block stands behind aefft_frames_degrade and in front of the network level, enums and descriptor in front of the two calls
-    order = ["int aefft_frames_degrade(", "/* aefft_yuv_to_image, aefft_yuv_resize_to_frames", "enum { AEFFT_YUV_NV12", "enum { AEFFT_YUV_BT601",
-             "enum { AEFFT_YUV_BGR", "} aefft_yuv_desc;", "int aefft_yuv_to_image(", "int aefft_yuv_resize_to_frames(", "/* ---- network level"]
-    at = [h.index(w) for w in order]
-    assert at == sorted(at)
+    A.in_order(A.header(), "int aefft_frames_degrade(", "/* aefft_yuv_to_image, aefft_yuv_resize_to_frames", "enum { AEFFT_YUV_NV12", "enum { AEFFT_YUV_BT601",
+               "enum { AEFFT_YUV_BGR", "} aefft_yuv_desc;", "int aefft_yuv_to_image(", "int aefft_yuv_resize_to_frames(", "/* ---- network level")
 
 
 def test_enum_values_are_pinned():
-    h = _header()
+    h = A.header()
     for names, table in ((("NV12", "I420", "YUYV"), aefft.YUV_FORMATS), (("BT601", "BT709", "JPEG"), aefft.YUV_MATRICES), (("BGR", "RGB", "GRAY"), aefft.YUV_ORDERS)):
         m = re.search(r"enum\s*\{\s*" + r"\s*,\s*".join(r"AEFFT_YUV_%s\s*=\s*(\d+)" % n for n in names) + r"\s*\}", h)
         assert m and [int(v) for v in m.groups()] == [0, 1, 2], names
@@ -73,9 +40,7 @@ def test_enum_values_are_pinned():
 
 
 def test_descriptor_structure_has_the_headers_fields_in_order():
-    body = re.search(r"typedef struct \{([^}]*)\} aefft_yuv_desc;", re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)).group(1)
-    decls = [" ".join(d.split()) for d in body.split(";") if d.strip()]
-    assert decls == ["int format, matrix", "int W, H", "const unsigned char* plane[3]", "size_t pitch[3]", "size_t stride[3]"]
+    assert A.struct_fields("aefft_yuv_desc") == ["int format, matrix", "int W, H", "const unsigned char* plane[3]", "size_t pitch[3]", "size_t stride[3]"]
     f = aefft.YuvDesc._fields_
     assert [n for n, _ in f] == ["format", "matrix", "W", "H", "plane", "pitch", "stride"]
     assert [t for _, t in f[:4]] == [C.c_int] * 4
@@ -95,26 +60,24 @@ def test_context_method_signatures():
 
 
 def test_null_context_is_einval_without_a_device():
-    L = _lib()
+    L = A.lib()
     buf = (C.c_ubyte * 1024)()
     base = C.addressof(buf)
-    einval = int(re.search(r"AEFFT_EINVAL\s*=\s*(-?\d+)", _header()).group(1))
     d = aefft.YuvDesc()
     d.format, d.matrix, d.W, d.H = 0, 0, 8, 8
     d.plane[0], d.plane[1] = base, base + 64
     d.pitch[0], d.pitch[1] = 8, 8
     dst = C.c_void_p(base + 512)
-    assert L.aefft_yuv_to_image(None, C.byref(d), 0, dst, 24, 192, 1) == einval
+    assert L.aefft_yuv_to_image(None, C.byref(d), 0, dst, 24, 192, 1) == A.EINVAL
     for mode in (0, 1):
-        assert L.aefft_yuv_resize_to_frames(None, C.byref(d), 0, mode, dst, 1, 1, 4, 4) == einval
-    assert L.aefft_yuv_to_image(None, None, 0, None, 0, 0, 0) == einval
-    assert L.aefft_yuv_resize_to_frames(None, None, 0, 0, None, 0, 0, 0, 0) == einval
+        assert L.aefft_yuv_resize_to_frames(None, C.byref(d), 0, mode, dst, 1, 1, 4, 4) == A.EINVAL
+    assert L.aefft_yuv_to_image(None, None, 0, None, 0, 0, 0) == A.EINVAL
+    assert L.aefft_yuv_resize_to_frames(None, None, 0, 0, None, 0, 0, 0, 0) == A.EINVAL
     assert bytes(buf) == bytes(1024)
 
 
 def test_header_describes_the_calls():
-    h = _header()
-    doc = h[h.index("/* aefft_yuv_to_image, aefft_yuv_resize_to_frames"):h.index("enum { AEFFT_YUV_NV12")]
+    doc = A.doc("/* aefft_yuv_to_image, aefft_yuv_resize_to_frames", "enum { AEFFT_YUV_NV12")
     ints = [n for _, ky, rows in R.TABLE.values() for n in (ky,) + tuple(v for ab in rows for v in ab if v)]
     assert len(ints) == 15
     for n in ints:
@@ -133,48 +96,22 @@ def test_header_describes_the_calls():
 
 def test_flag_option_and_profiler_tables_are_unchanged():
     """the calls add no development switch, no net option and no profiling id (they are accounted under `image`)"""
-    bits = dict((n, int(b)) for n, b in re.findall(r"\b(AEFFT_F_[A-Z0-9]+)\s*=\s*1\s*<<\s*(\d+)", _header()))
-    assert len(bits) == NFLAGS and len(set(bits.values())) == NFLAGS
-    assert not [n for n in bits if "YUV" in n]
-    opts = re.findall(r"\b(AEFFT_NET_[A-Z_]+)\s*=\s*1u\s*<<\s*\d+", _header())
-    assert opts == ["AEFFT_NET_SMOOTH_SIZES", "AEFFT_NET_SPATIAL", "AEFFT_NET_SMOOTH_OPFORM"]
-    L = _lib()
-    L.aefft_prof_name.restype = C.c_char_p
-    names = [L.aefft_prof_name(k).decode() for k in range(L.aefft_prof_count())]
-    assert names[-2:] == ["target", "ssim"] and names.count("image") == 1 and not [n for n in names if "yuv" in n]
-
-
-def _rsrc(name):
-    path = os.path.join(CSRC, "build", name)
-    assert os.path.exists(path), f"{path}: the build writes the back end's resource table beside every object (csrc/Makefile)"
-    return [b for b in re.split(r"(?=remark: [^\n]*Function Name: )", open(path).read()) if "Function Name: " in b]
+    names = A.tables_unchanged("YUV", profiler=("yuv",))[1]
+    assert names.count("image") == 1
 
 
 def test_yuv_kernels_use_no_scratch_and_cover_what_the_launchers_name():
     """build/yuv_kernels.rsrc: yuv_image_kernel<FMT, D> and yuv_resize_kernel<FMT, D, F32, MODE> for exactly the (FMT, D) the two launchers' switches
     name -- every format with D = 3, NV12 and YUYV with D = 1 (GRAY reads the luma plane only, which I420 lays out as NV12 does) -- each with zero
     scratch and zero spills; not specialised on matrix or order"""
-    _lib()
     src = open(os.path.join(CSRC, "yuv_kernels.hip")).read()
     image_named = {(int(f), int(d)) for f, d in re.findall(r"YI_CASE\((\d), (\d)\)", src)}
     resize_named = {(int(f), int(d)) for f, d in re.findall(r"YV_CASES\((\d), (\d)\)", src)}
     assert image_named == resize_named == {(0, 1), (0, 3), (1, 3), (2, 1), (2, 3)}
     assert "YV_CASE(FF, DD, 0, 0) YV_CASE(FF, DD, 0, 1) YV_CASE(FF, DD, 1, 0) YV_CASE(FF, DD, 1, 1)" in src
-    image, resize = set(), set()
-    for b in _rsrc("yuv_kernels.rsrc"):
-        name = re.search(r"Function Name: (\S+)", b).group(1)
-        ki = re.search(r"\d+yuv_image_kernelILi(\d)ELi(\d)EEE", name)
-        kr = re.search(r"\d+yuv_resize_kernelILi(\d)ELi(\d)ELb([01])ELi([01])EEE", name)
-        assert ki or kr, name
-        if ki:
-            image.add((int(ki.group(1)), int(ki.group(2))))
-        else:
-            resize.add((int(kr.group(1)), int(kr.group(2)), kr.group(3) == "1", int(kr.group(4))))
-        for key in ("ScratchSize \\[bytes/lane\\]", "SGPRs Spill", "VGPRs Spill"):
-            v = re.search(key + r": (\d+)", b)
-            assert v and int(v.group(1)) == 0, (name, key)
-    assert image == image_named
-    assert resize == {(f, d, t, m) for f, d in resize_named for t in (False, True) for m in (0, 1)}
+    image, resize = A.instantiations("yuv_kernels.rsrc", r"\d+yuv_image_kernelILi(\d)ELi(\d)EEE", r"\d+yuv_resize_kernelILi(\d)ELi(\d)ELb([01])ELi([01])EEE")
+    assert image == {(str(f), str(d)) for f, d in image_named}
+    assert resize == {(str(f), str(d), t, m) for f, d in resize_named for t in "01" for m in "01"}
     mk = open(os.path.join(CSRC, "Makefile")).read()
     assert "yuv_kernels.hip" in mk.split("SRCS =")[1].split("\n")[0]
     assert "hipError_t launch_yuv_image(" in open(os.path.join(CSRC, "internal.h")).read() and "hipError_t launch_yuv_resize(" in open(os.path.join(CSRC, "internal.h")).read()
@@ -185,18 +122,13 @@ def test_yuv_kernels_use_no_scratch_and_cover_what_the_launchers_name():
 
 
 def test_resize_kernels_still_hold_their_sixteen():
-    _lib()
-    names = [re.search(r"Function Name: (\S+)", b).group(1) for b in _rsrc("resize_kernels.rsrc")]
-    assert len(names) == 16 and all(re.search(r"\d+resize_kernelILi[1-4]ELb[01]ELi[01]EEE", n) for n in names) and len(set(names)) == 16
+    names = list(A.rsrc("resize_kernels.rsrc"))
+    assert len(names) == 16 and all(re.search(r"\d+resize_kernelILi[1-4]ELb[01]ELi[01]EEE", n) for n in names)
 
 
 def test_host_check_source_is_present_and_stands_alone():
-    src = open(os.path.join(ROOT, "tools", "yuv_hostcheck.cpp")).read()
-    assert "int main()" in src and '#include "../autoencoder-fft_amd/csrc/yuv_kernels.hip"' in src
-    assert "-fsanitize=address,undefined" in src and "hip/hip_runtime" not in src and "Python.h" not in src and "LD_PRELOAD" not in src
-    lanes = open(os.path.join(ROOT, "tools", "hostlanes.h")).read()
-    assert '#include "hostlanes.h"' in src and "#define AEFFT_HOSTCHECK" in lanes
-    assert "Python.h" not in lanes and "hip_runtime" not in lanes and "LD_PRELOAD" not in lanes
+    src = A.host_check_stands_alone("yuv_hostcheck.cpp", "yuv_kernels.hip")
+    assert "int main()" in src and "LD_PRELOAD" not in src
     kern = open(os.path.join(CSRC, "yuv_kernels.hip")).read()
     assert "#ifndef AEFFT_HOSTCHECK" in kern and "AEFFT_YUV_HOSTCHECK" not in kern
     # its restatement has a table of its own with the header's integers

@@ -6,23 +6,19 @@ stand-alone host check; the coefficient table re-derived from Kr, Kb with the re
 (tests/yuv_out_ref.py), among them its distance from the real formula and the round trip through yuv_ref.convert over all 2^24 (R, G, B); the
 Python argument checks."""
 import ctypes as C
-import importlib
 import inspect
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import abi_checks as A
 import yuv_out_ref as R
 import yuv_ref as RI
+from abi_checks import CSRC, aefft
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "autoencoder-fft_amd", "csrc")
-aefft = importlib.import_module("autoencoder-fft_amd")
-NFLAGS = 26      # AEFFT_F_* switches of the library
 PROTOS = {
     "aefft_image_to_yuv": ["aefft_ctx* ctx", "const unsigned char* image_d", "size_t pitch", "size_t image_stride", "int order", "const aefft_yuv_dst* dst", "int B"],
     "aefft_frames_resize_to_yuv": ["aefft_ctx* ctx", "const void* frames_d", "int frames_u8", "int Nx", "int Ny", "int mode", "int order", "const aefft_yuv_dst* dst", "int B"],
@@ -30,53 +26,23 @@ PROTOS = {
 DOC_START = "/* aefft_image_to_yuv, aefft_frames_resize_to_yuv"
 
 
-def _header():
-    return open(os.path.join(ROOT, "include", "aefft.h")).read()
-
-
-def _lib():
-    if not os.path.exists(aefft.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return aefft.lib()
-
-
 def _table_ints():
     return [n for yoff, ky, *rows in R.TABLE.values() for n in (ky,) + tuple(v for row in rows for v in row)]
 
 
 def test_declared_exported_prototyped_and_placed():
-    h = _header()
-    txt = re.sub(r"/\*.*?\*/", "", h, flags=re.S)
-    _lib()
-    out = subprocess.run(["nm", "-D", "--defined-only", aefft.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    ctypes_of = {"aefft_ctx*": C.c_void_p, "const unsigned char*": C.c_void_p, "const void*": C.c_void_p, "size_t": C.c_size_t, "int": C.c_int}
+    h = A.header()
     for name, want in PROTOS.items():
-        m = re.search(r"int\s+%s\s*\(([^)]*)\)" % name, txt)
-        assert m, f"include/aefft.h does not declare {name}"
-        assert [" ".join(a.split()) for a in m.group(1).split(",")] == want
-        assert any(l.split()[-1] == name and " T " in l for l in out.splitlines()), name
-        res, argt = aefft.SIGNATURES[name]
-        assert res is C.c_int and len(argt) == len(want)
-        for t, w in zip(argt, want):
-            typ = w.rsplit(" ", 1)[0]
-            if typ == "const aefft_yuv_dst*":
-                assert t._type_ is aefft.YuvDst
-            else:
-                assert t is ctypes_of[typ], w
+        A.check_call(name, want, {"const aefft_yuv_dst*": aefft.YuvDst})
     # the block stands behind the tile calls and in front of the network level, the descriptor in front of the two calls
-    order = ["int aefft_frames_tiles_to_image(", DOC_START, "} aefft_yuv_dst;", "int aefft_image_to_yuv(", "int aefft_frames_resize_to_yuv(", "/* ---- network level"]
-    at = [h.index(w) for w in order]
-    assert at == sorted(at)
+    A.in_order(h, "int aefft_frames_tiles_to_image(", DOC_START, "} aefft_yuv_dst;", "int aefft_image_to_yuv(", "int aefft_frames_resize_to_yuv(", "/* ---- network level")
     # the existing enums serve both directions: none is declared again
     for e in ("enum { AEFFT_YUV_NV12", "enum { AEFFT_YUV_BT601", "enum { AEFFT_YUV_BGR"):
-        assert h.count(e) == 1 and h.index(e) < at[1]
+        assert h.count(e) == 1 and h.index(e) < h.index(DOC_START)
 
 
 def test_descriptor_structure_has_the_headers_fields_in_order():
-    body = re.search(r"typedef struct \{([^}]*)\} aefft_yuv_dst;", re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)).group(1)
-    decls = [" ".join(d.split()) for d in body.split(";") if d.strip()]
-    assert decls == ["int format, matrix", "int W, H", "unsigned char* plane[3]", "size_t pitch[3]", "size_t stride[3]"]
+    assert A.struct_fields("aefft_yuv_dst") == ["int format, matrix", "int W, H", "unsigned char* plane[3]", "size_t pitch[3]", "size_t stride[3]"]
     f = aefft.YuvDst._fields_
     assert [n for n, _ in f] == ["format", "matrix", "W", "H", "plane", "pitch", "stride"]
     assert [t for _, t in f[:4]] == [C.c_int] * 4
@@ -96,26 +62,24 @@ def test_context_method_signatures():
 
 
 def test_null_context_is_einval_without_a_device():
-    L = _lib()
+    L = A.lib()
     buf = (C.c_ubyte * 1024)()
     base = C.addressof(buf)
-    einval = int(re.search(r"AEFFT_EINVAL\s*=\s*(-?\d+)", _header()).group(1))
     d = aefft.YuvDst()
     d.format, d.matrix, d.W, d.H = 0, 0, 8, 8
     d.plane[0], d.plane[1] = base, base + 64
     d.pitch[0], d.pitch[1] = 8, 8
     src = C.c_void_p(base + 512)
-    assert L.aefft_image_to_yuv(None, src, 24, 192, 0, C.byref(d), 1) == einval
+    assert L.aefft_image_to_yuv(None, src, 24, 192, 0, C.byref(d), 1) == A.EINVAL
     for mode in (0, 1):
-        assert L.aefft_frames_resize_to_yuv(None, src, 1, 8, 8, mode, 0, C.byref(d), 1) == einval
-    assert L.aefft_image_to_yuv(None, None, 0, 0, 0, None, 0) == einval
-    assert L.aefft_frames_resize_to_yuv(None, None, 0, 0, 0, 0, 0, None, 0) == einval
+        assert L.aefft_frames_resize_to_yuv(None, src, 1, 8, 8, mode, 0, C.byref(d), 1) == A.EINVAL
+    assert L.aefft_image_to_yuv(None, None, 0, 0, 0, None, 0) == A.EINVAL
+    assert L.aefft_frames_resize_to_yuv(None, None, 0, 0, 0, 0, 0, None, 0) == A.EINVAL
     assert bytes(buf) == bytes(1024)
 
 
 def test_header_describes_the_calls():
-    h = _header()
-    doc = " ".join(re.sub(r"\n \*", "\n", h[h.index(DOC_START):h.index("} aefft_yuv_dst;")]).split())      # (without the comment's margin and line breaks)
+    doc = A.doc(DOC_START, "} aefft_yuv_dst;", margin=False)
     ints = _table_ints()
     assert len(ints) == 30
     for n in ints:
@@ -141,48 +105,22 @@ def test_header_describes_the_calls():
 
 def test_flag_option_and_profiler_tables_are_unchanged():
     """the calls add no development switch, no net option and no profiling id (they are accounted under `image`)"""
-    bits = dict((n, int(b)) for n, b in re.findall(r"\b(AEFFT_F_[A-Z0-9]+)\s*=\s*1\s*<<\s*(\d+)", _header()))
-    assert len(bits) == NFLAGS and len(set(bits.values())) == NFLAGS
-    assert not [n for n in bits if "YUV" in n]
-    opts = re.findall(r"\b(AEFFT_NET_[A-Z_]+)\s*=\s*1u\s*<<\s*\d+", _header())
-    assert opts == ["AEFFT_NET_SMOOTH_SIZES", "AEFFT_NET_SPATIAL", "AEFFT_NET_SMOOTH_OPFORM"]
-    L = _lib()
-    L.aefft_prof_name.restype = C.c_char_p
-    names = [L.aefft_prof_name(k).decode() for k in range(L.aefft_prof_count())]
-    assert names[-2:] == ["target", "ssim"] and names.count("image") == 1 and not [n for n in names if "yuv" in n]
-
-
-def _rsrc(name):
-    path = os.path.join(CSRC, "build", name)
-    assert os.path.exists(path), f"{path}: the build writes the back end's resource table beside every object (csrc/Makefile)"
-    return [b for b in re.split(r"(?=remark: [^\n]*Function Name: )", open(path).read()) if "Function Name: " in b]
+    names = A.tables_unchanged("YUV", profiler=("yuv",))[1]
+    assert names.count("image") == 1
 
 
 def test_yuv_out_kernels_use_no_scratch_and_cover_what_the_launchers_name():
     """build/yuv_out_kernels.rsrc: image_yuv_kernel<FMT, D> and frames_yuv_kernel<FMT, D, F32, MODE> for exactly the (FMT, D) the two launchers'
     switches name -- every format with D = 3 and with D = 1 (GRAY has kernels of its own for every format: I420 fills two chroma planes where NV12
     fills one) -- each with zero scratch and zero spills; not specialised on matrix or order"""
-    _lib()
     src = open(os.path.join(CSRC, "yuv_out_kernels.hip")).read()
     image_named = {(int(f), int(d)) for f, d in re.findall(r"YO_CASE\((\d), (\d)\)", src)}
     frames_named = {(int(f), int(d)) for f, d in re.findall(r"FY_CASES\((\d), (\d)\)", src)}
     assert image_named == frames_named == {(f, d) for f in (0, 1, 2) for d in (1, 3)}
     assert "FY_CASE(FF, DD, 0, 0) FY_CASE(FF, DD, 0, 1) FY_CASE(FF, DD, 1, 0) FY_CASE(FF, DD, 1, 1)" in src
-    image, frames = set(), set()
-    for b in _rsrc("yuv_out_kernels.rsrc"):
-        name = re.search(r"Function Name: (\S+)", b).group(1)
-        ki = re.search(r"\d+image_yuv_kernelILi(\d)ELi(\d)EEE", name)
-        kf = re.search(r"\d+frames_yuv_kernelILi(\d)ELi(\d)ELb([01])ELi([01])EEE", name)
-        assert ki or kf, name
-        if ki:
-            image.add((int(ki.group(1)), int(ki.group(2))))
-        else:
-            frames.add((int(kf.group(1)), int(kf.group(2)), kf.group(3) == "1", int(kf.group(4))))
-        for key in ("ScratchSize \\[bytes/lane\\]", "SGPRs Spill", "VGPRs Spill"):
-            v = re.search(key + r": (\d+)", b)
-            assert v and int(v.group(1)) == 0, (name, key)
-    assert image == image_named
-    assert frames == {(f, d, t, m) for f, d in frames_named for t in (False, True) for m in (0, 1)}
+    image, frames = A.instantiations("yuv_out_kernels.rsrc", r"\d+image_yuv_kernelILi(\d)ELi(\d)EEE", r"\d+frames_yuv_kernelILi(\d)ELi(\d)ELb([01])ELi([01])EEE")
+    assert image == {(str(f), str(d)) for f, d in image_named}
+    assert frames == {(str(f), str(d), t, m) for f, d in frames_named for t in "01" for m in "01"}
     mk = open(os.path.join(CSRC, "Makefile")).read()
     assert "yuv_out_kernels.hip" in mk.split("SRCS =")[1].split("\n")[0]
     internal = open(os.path.join(CSRC, "internal.h")).read()
@@ -195,18 +133,16 @@ def test_yuv_out_kernels_use_no_scratch_and_cover_what_the_launchers_name():
 
 
 def test_the_pinned_kernel_files_still_hold_their_kernels():
-    _lib()
-    names = [re.search(r"Function Name: (\S+)", b).group(1) for b in _rsrc("resize_kernels.rsrc")]
-    assert len(names) == 16 and all(re.search(r"\d+resize_kernelILi[1-4]ELb[01]ELi[01]EEE", n) for n in names) and len(set(names)) == 16
-    names = [re.search(r"Function Name: (\S+)", b).group(1) for b in _rsrc("yuv_kernels.rsrc")]
-    assert len(names) == 25 and len(set(names)) == 25 and all("yuv_image_kernel" in n or "yuv_resize_kernel" in n for n in names)
+    names = list(A.rsrc("resize_kernels.rsrc"))
+    assert len(names) == 16 and all(re.search(r"\d+resize_kernelILi[1-4]ELb[01]ELi[01]EEE", n) for n in names)
+    names = list(A.rsrc("yuv_kernels.rsrc"))
+    assert len(names) == 25 and all("yuv_image_kernel" in n or "yuv_resize_kernel" in n for n in names)
 
 
 def test_host_check_source_is_present_and_stands_alone():
-    src = open(os.path.join(ROOT, "tools", "yuv_out_hostcheck.cpp")).read()
-    assert "int main()" in src and '#include "../autoencoder-fft_amd/csrc/yuv_out_kernels.hip"' in src
-    assert "-fsanitize=address,undefined" in src and "hip/hip_runtime" not in src and "Python.h" not in src and "LD_PRELOAD" not in src
-    assert '#include "hostlanes.h"' in src and src.index('#include "hostlanes.h"') < src.index("yuv_out_kernels.hip\"")
+    src = A.host_check_stands_alone("yuv_out_hostcheck.cpp", "yuv_out_kernels.hip")
+    assert "int main()" in src and "LD_PRELOAD" not in src
+    assert src.index('#include "hostlanes.h"') < src.index("yuv_out_kernels.hip\"")
     kern = open(os.path.join(CSRC, "yuv_out_kernels.hip")).read()
     assert "#ifndef AEFFT_HOSTCHECK" in kern
     # its restatement has a table of its own with the header's integers, and takes nothing from the kernels' tap header
