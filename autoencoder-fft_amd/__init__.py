@@ -108,6 +108,7 @@ SIGNATURES = {
     "aefft_frames_tiles_to_image": (_i, [_vp, _vp, _i, C.POINTER(TileDesc), _vp, C.c_size_t, C.c_size_t, _i, _i]),
     "aefft_image_to_yuv": (_i, [_vp, _vp, C.c_size_t, C.c_size_t, _i, C.POINTER(YuvDst), _i]),
     "aefft_frames_resize_to_yuv": (_i, [_vp, _vp, _i, _i, _i, _i, _i, C.POINTER(YuvDst), _i]),
+    "aefft_image_compare_map": (_i, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_size_t, C.c_size_t, _i, _i, _i, _i, _i, _i, _i, _fp, _fp]),
     "aefft_net_create": (_i, [_vp, C.POINTER(NetDesc), C.POINTER(_vp)]),
     "aefft_net_create_ex": (_i, [_vp, C.POINTER(NetDesc), C.c_uint, C.POINTER(_vp)]),
     "aefft_net_destroy": (None, [_vp]),
@@ -501,6 +502,47 @@ def _frames_tiles_args(frames, size, overlap, rim, out):
     return desc, shape
 
 
+COMPARE_METRICS = {"mse": 0, "ssim": 1}      # AEFFT_COMPARE_MSE, AEFFT_COMPARE_SSIM
+
+
+def cells_for_tile(W, H, tile):
+    """The cell grid (Mx, My) = (ceil(W / tx), ceil(H / ty)) that Context.image_compare_map takes for cells of about `tile` pixels a side on an
+    image of W x H: `tile` is an int or an (x, y) pair in 1..64.  The cells are then floor(W / Mx) or ceil(W / Mx) <= tx columns wide."""
+    what = "cells_for_tile"
+    tx, ty = _pair(tile, what, "tile")
+    try:
+        W, H = int(W), int(H)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: W, H must be ints") from None
+    if not (1 <= tx <= 64 and 1 <= ty <= 64) or W < 1 or H < 1:
+        raise ValueError(f"{what}: tile must be in 1..64 per axis and W, H positive")
+    return -(-W // tx), -(-H // ty)
+
+
+def _image_compare_args(a, b, cells, metric, map, score):
+    """the checks of Context.image_compare_map that need no device: (a as [B][H][W][D], its pitch and stride, b likewise, its pitch and stride,
+    (Mx, My), the metric's value); `map` and `score`, when given, are checked for shape, dtype and layout"""
+    what = "Context.image_compare_map"
+    ia, pa, sa = _resize_layout(a, f"{what}: a")
+    ib, pb, sb = _resize_layout(b, f"{what}: b")
+    if tuple(ia.shape) != tuple(ib.shape):
+        raise ValueError(f"{what}: a and b must have one shape; got {tuple(a.shape)} and {tuple(b.shape)}")
+    B, H, W, D = ia.shape
+    if not 1 <= D <= 4 or W > 8192 or H > 8192:
+        raise ValueError(f"{what}: D must be 1..4 and W, H in 1..8192")
+    if metric not in COMPARE_METRICS:
+        raise ValueError(f"{what}: metric must be one of {sorted(COMPARE_METRICS)}")
+    Mx, My = _two_ints(cells, what, "cells must be (Mx, My)")
+    if not (1 <= Mx <= min(W, 1024) and 1 <= My <= min(H, 1024)) or -(-W // Mx) > 64 or -(-H // My) > 64:
+        raise ValueError(f"{what}: cells must be 1 <= Mx <= min(W, 1024), 1 <= My <= min(H, 1024) with cells of at most 64 x 64 pixels; got "
+                         f"{(Mx, My)} for an image of {W} x {H}")
+    if map is not None and (map.dtype != torch.float32 or tuple(map.shape) != (B, Mx, My) or not map.is_contiguous()):
+        raise ValueError(f"{what}: map must be a contiguous float32 tensor of shape {(B, Mx, My)}")
+    if score is not None and score is not False and (score.dtype != torch.float32 or tuple(score.shape) != (B,) or not score.is_contiguous()):
+        raise ValueError(f"{what}: score must be a contiguous float32 tensor of shape {(B,)}, None or False")
+    return ia, pa, sa, ib, pb, sb, (Mx, My), COMPARE_METRICS[metric]
+
+
 class Context:
     """aefft_ctx on torch's current device, enqueuing on torch's current stream by default."""
 
@@ -788,6 +830,25 @@ class Context:
                                                   _ptr(img), pitch, stride, W, H, B, D))
         return image
 
+    def image_compare_map(self, a, b, cells, metric="mse", map=None, score=None):
+        """Where two images differ, at their own resolution (aefft_image_compare_map): `a` and `b` are uint8 device tensors [B][H][W][D] or
+        [H][W][D] of one shape, each contiguous, row-padded or a region of interest with its own pitch and stride (b may be a itself);
+        cells = (Mx, My), the grid of at most 64 x 64-pixel cells (cells_for_tile gives it from a cell size).  map[b][I][J] is the mean squared
+        error ("mse") or the mean SSIM of the channels ("ssim", data range 255) over the pixels x, y with floor(x Mx / W) = I and
+        floor(y My / H) = J -- what map_overlay(smooth=False) colours with that entry --, score[b] the pixel-weighted mean of the map; both are
+        defined bit for bit from integer sums (include/aefft.h).  `map` (float32 [B][Mx][My]) and `score` (float32 [B]) are allocated when None;
+        score=False skips the score and its launch.  Nothing waits for the device.  Returns (map, score)."""
+        ia, pa, sa, ib, pb, sb, (Mx, My), m = _image_compare_args(a, b, cells, metric, map, score)
+        B, H, W, D = ia.shape
+        if map is None:
+            map = self.empty(B, Mx, My)
+        if score is None:
+            score = self.empty(B)
+        elif score is False:
+            score = None
+        self.check(self.L.aefft_image_compare_map(self.h, _ptr(ia), pa, sa, _ptr(ib), pb, sb, W, H, B, D, m, Mx, My, _ptr(map), _ptr(score)))
+        return map, score
+
     def frames_degrade(self, frames, blur=0, sigma=0.0, impulse=0.0, seed=0, first_frame=0, out=None, dtype=None):
         """The degraded input of target training from the clean frames (aefft_frames_degrade), one launch: `frames` uint8 or float32
         [B][D][Nx][Ny] (float values become pixels first) -> the binomial blur of radius `blur` in 0..4 (2 blur + 1 taps per axis, edges
@@ -1047,6 +1108,16 @@ class Net:
         for k in range(0, Tp, self.B):
             self.infer(tiles[k:k + self.B], recon[k:k + self.B])
         return self.ctx.frames_tiles_to_image(recon[:T], (W, H), overlap, rim, out=out)
+
+    def score_tiled(self, image, overlap, rim=0, tile=16, metric="mse", target=None, map=None, score=None, out=None):
+        """Reconstruction error at the image's own resolution: infer_tiled(image, overlap, rim) into `out`, then Context.image_compare_map of
+        `target` (the image itself when None) against `out` on cells_for_tile(W, H, tile) -- cells of about `tile` pixels a side, an int or an
+        (x, y) pair in 1..64; metric "mse" or "ssim".  `map`, `score` and `out` are allocated when None; score=False skips the score.  An FFT
+        net only (ValueError on a spatial net).  Nothing waits for the device.  Returns (map, score, out)."""
+        out = self.infer_tiled(image, overlap, rim, out=out)          # (its checks are this call's: an FFT net, a uint8 image [B][H][W][D])
+        cells = cells_for_tile(out.shape[2], out.shape[1], tile)
+        map, score = self.ctx.image_compare_map(image if target is None else target, out, cells, metric, map=map, score=score)
+        return map, score, out
 
     def score(self, frames, score=None, recon=None):
         """Per-frame reconstruction error under the current weights (aefft_net_score): score[b] = mean over the frame's D*Nx*Ny pixels of

@@ -318,6 +318,32 @@ extern "C" int aefft_frames_resize_to_yuv(aefft_ctx* ctx, const void* frames_d, 
     });
 }
 
+// compare (include/aefft.h "aefft_image_compare_map") -----------------------------------------
+extern "C" int aefft_image_compare_map(aefft_ctx* ctx, const unsigned char* a_d, size_t a_pitch, size_t a_stride, const unsigned char* b_d, size_t b_pitch,
+                                       size_t b_stride, int W, int H, int B, int D, int metric, int Mx, int My, float* map_d, float* score_d)
+{
+    const Bad bad{ctx, "aefft_image_compare_map"};
+    if (!ctx || !a_d || !b_d || !map_d) return bad("null context, image or map");
+    RET_IF(chk_dims(bad, B, D, W, H));
+    if (Mx < 1 || My < 1 || Mx > 1024 || My > 1024 || Mx > W || My > H) return bad("Mx must be in 1..min(W, 1024) and My in 1..min(H, 1024)");
+    if ((W + Mx - 1) / Mx > 64 || (H + My - 1) / My > 64) return bad("a cell side above 64: ceil(W / Mx) and ceil(H / My) must be at most 64");
+    if (metric != AEFFT_COMPARE_MSE && metric != AEFFT_COMPARE_SSIM) return bad("metric must be AEFFT_COMPARE_MSE or AEFFT_COMPARE_SSIM");
+    size_t ea = 0, eb = 0;                            // each image by the image buffer rule, the sentence led by the image's name
+    RET_IF(chk_rows(Bad{ctx, "aefft_image_compare_map: a_d"}, IMAGE_WORDS, a_pitch, a_stride, (size_t)W * D, (size_t)H, B, &ea));
+    RET_IF(chk_rows(Bad{ctx, "aefft_image_compare_map: b_d"}, IMAGE_WORDS, b_pitch, b_stride, (size_t)W * D, (size_t)H, B, &eb));
+    if (!aligned16(map_d) || !aligned16(score_d)) return bad("map_d and score_d must be 16-byte aligned");
+    if ((size_t)B > HALF / ((size_t)4 * Mx * My) || (size_t)B * My > (size_t)INT_MAX) return bad("B * Mx * My does not fit the address space or B * My an int");
+    const size_t mb = (size_t)B * Mx * My * 4, sb = (size_t)B * 4;
+    if (ranges_overlap(map_d, mb, a_d, ea) || ranges_overlap(map_d, mb, b_d, eb)) return bad("the map and image ranges overlap");
+    if (score_d && (ranges_overlap(score_d, sb, a_d, ea) || ranges_overlap(score_d, sb, b_d, eb))) return bad("the score and image ranges overlap");
+    if (score_d && ranges_overlap(score_d, sb, map_d, mb)) return bad("the score and map ranges overlap");
+    RET_IF(join_recon(ctx));                          // (either image may hold a reconstruction that is still on the side stream)
+    RET_IF(launch_or_fail(ctx, KID_IMAGE, (double)B * (2.0 * W * H * D + 4.0 * Mx * My), "compare_map",
+                          [&] { return launch_compare_map(a_d, a_pitch, a_stride, b_d, b_pitch, b_stride, W, H, B, D, metric, Mx, My, map_d, ctx->cur); }));
+    if (!score_d) return AEFFT_OK;                    // (the finish reads the map the launch before it wrote: its bytes are accounted there)
+    return launch_or_fail(ctx, KID_IMAGE, 0.0, "compare_score", [&] { return launch_compare_score(map_d, score_d, W, H, B, Mx, My, ctx->cur); });
+}
+
 // tiled inference (include/aefft.h "tiled inference"): the plan is host arithmetic only --------
 extern "C" int aefft_tile_plan_make(const aefft_tile_desc* desc, aefft_tile_plan* plan) { return tile_plan(desc, plan) ? AEFFT_OK : AEFFT_EINVAL; }
 

@@ -123,6 +123,15 @@ hipError_t launch_tile_gather(const unsigned char* image, size_t pitch, size_t s
                               hipStream_t st);
 hipError_t launch_tile_blend(const void* frames, bool f32, const aefft_tile_desc* desc, unsigned char* image, size_t pitch, size_t stride, int B, int D,
                              hipStream_t st);
+// ---- compare_kernels.hip (aefft_image_compare_map) ----
+// two batches of B interleaved images of W x H pixels of D channels, each with its own pitch and stride and of any alignment -> map [B][Mx][My]: per
+// cell (cell I: columns [ceil(I W / Mx), ceil((I+1) W / Mx)), rows alike) the mean squared error (metric 0) or the mean SSIM of the channels
+// (metric 1), from integer sums (include/aefft.h).  W, H in 1..8192, D in 1..4, Mx <= min(W, 1024), My <= min(H, 1024), cells of at most 64 x 64
+// pixels, pitches >= W D (hipErrorInvalidValue otherwise).  One launch.
+hipError_t launch_compare_map(const unsigned char* a, size_t a_pitch, size_t a_stride, const unsigned char* b, size_t b_pitch, size_t b_stride, int W, int H,
+                              int B, int D, int metric, int Mx, int My, float* map, hipStream_t st);
+// score[b] = the pixel-weighted mean of map[b] as stored, added along J, then along I, in double.  One launch.
+hipError_t launch_compare_score(const float* map, float* score, int W, int H, int B, int Mx, int My, hipStream_t st);
 size_t fft_mid_elems(long planes, int Nx, int Wc);   // complex elements needed in `mid`
 // sizes that are not powers of two (cufftPlanMany takes any size, fft.cu:773-779): even n in 8..1024 through Bluestein's chirp-z form on the
 // power-of-two LDS passes; rows -> transpose -> rows -> transpose.  w1, w2: workspaces of fft_any_ws_elems complex each.

@@ -540,6 +540,46 @@ int aefft_image_to_yuv(aefft_ctx* ctx, const unsigned char* image_d, size_t pitc
 int aefft_frames_resize_to_yuv(aefft_ctx* ctx, const void* frames_d, int frames_u8, int Nx, int Ny, int mode, int order,
                                const aefft_yuv_dst* dst, int B);
 
+/* aefft_image_compare_map: where two images differ, at the images' own resolution -- a per-cell mean squared error or SSIM map of two interleaved
+ * 8-bit images (the camera image and the blended reconstruction of tiled inference, or a clean target and a restored image) and, optionally, the
+ * per-image score; the map is what aefft_map_overlay_image paints.
+ * a_d, b_d: B images each of W x H pixels of D channels in the layout of aefft_image_resize_to_frames -- pixel (row y, column x), channel d, at
+ * y * pitch + x * D + d; pointer, pitch and stride of any alignment; pitch >= W * D; for B > 1 stride >= (H - 1) * pitch + W * D (ignored when
+ * B == 1); bytes of a row beyond W * D are never read.  Each image has its own pitch and stride (a region of interest of a padded buffer against a
+ * tight one).  Both are only read: a_d == b_d and any overlap of the two are allowed.  map_d: float [B][Mx][My], My contiguous, 16-byte aligned
+ * -- the layout aefft_net_score_map writes and aefft_map_overlay_image reads.  score_d: float [B], 16-byte aligned, or NULL.
+ * Cells: pixel column x belongs to cell I = floor(x Mx / W), row y to J = floor(y My / H) -- step 3 of aefft_map_overlay_image read backwards, so
+ * smooth = 0 colours exactly the pixels an entry was computed from, whatever W and H are.  Cell I covers the columns [ceil(I W / Mx),
+ * ceil((I+1) W / Mx)), nx_I = floor(W / Mx) or ceil(W / Mx) of them; rows alike; with W = t Mx the cells are the t x t tiles.  W, H in 1..8192,
+ * D in 1..4, B >= 1, 1 <= Mx <= min(W, 1024), 1 <= My <= min(H, 1024), ceil(W / Mx) <= 64 and ceil(H / My) <= 64: a cell has
+ * n = nx_I ny_J <= 4096 pixels.  B * My <= 2^31 - 1 (the cell rows of a batch are counted in an int).
+ * Definition -- integers up to a stated handful of IEEE double operations, so that numpy gives the same bits.  x, r: the bytes of a and b.
+ *   AEFFT_COMPARE_MSE:   e = sum over d < D and the cell's pixels of (x - r)^2 (< 2^31);  map = (float)((double)e / (double)(D n)).
+ *   AEFFT_COMPARE_SSIM:  data range 255, C1 = 6.5025, C2 = 58.5225, uniform weights, population statistics: the formula of aefft_net_ssim_map
+ *     cleared of its denominators.  Per channel d, with the integer moments Sx, Sr, Sxx, Srr, Sxr of the cell, K1 = 65025 and K2 = 585225:
+ *       A1 = 20000 Sx Sr + K1 n^2              A2 = 20000 (n Sxr - Sx Sr) + K2 n^2   (may be negative)
+ *       B1 = 10000 (Sx^2 + Sr^2) + K1 n^2      B2 = 10000 (n Sxx - Sx^2 + n Srr - Sr^2) + K2 n^2
+ *     exact in signed 64 bits (magnitudes below 2.3e16), B1, B2 > 0;  ssim_d = ((double)A1 * (double)A2) / ((double)B1 * (double)B2): four
+ *     conversions (round to nearest even), two products, one division -- nothing that can contract into an FMA;
+ *     map = (float)((ssim_0 + ... + ssim_{D-1}) / (double)D), added in ascending d.
+ * Identical images give exactly 0.0f (MSE) and exactly 1.0f (SSIM); swapping a and b gives the same bits.
+ * Score (score_d != NULL), a function of the map AS STORED, its pixel-weighted mean: r_I = ((m[I][0] n_I0 + m[I][1] n_I1) + ...) in double,
+ * ascending J; S = ((r_0 + r_1) + ...), ascending I; score[b] = (float)(S / (double)(W H)).  Each product of a float with an integer <= 4096 is
+ * exact in double.  For MSE the score is the image's mean squared error up to the float rounding of the entries -- PSNR = 10 log10(255^2 / score)
+ * --, for SSIM the pixel-weighted mean SSIM.
+ * One launch on the context's stream, two with score_d (a small finish kernel that reads the map back); no host synchronisation, no allocation,
+ * no workspace, no global atomics (every cell is owned by one workgroup); safe under stream capture.  Accounted under the profile id `image` with
+ * 2 B W H D + 4 B Mx My bytes.
+ * AEFFT_EINVAL, with aefft_last_error starting "aefft_image_compare_map: " and naming the rule, nothing enqueued and both outputs untouched: a
+ * null context, source or map; a size, D, B, Mx or My out of range; a cell side above 64; an unknown metric; a pitch or stride that is too small;
+ * map_d or score_d not 16-byte aligned; map_d or score_d overlapping either image or each other; sizes that overflow the address space or B * My beyond an int. */
+enum { AEFFT_COMPARE_MSE = 0, AEFFT_COMPARE_SSIM = 1 };
+int aefft_image_compare_map(aefft_ctx* ctx,
+                            const unsigned char* a_d, size_t a_pitch, size_t a_stride,
+                            const unsigned char* b_d, size_t b_pitch, size_t b_stride,
+                            int W, int H, int B, int D, int metric, int Mx, int My,
+                            float* map_d, float* score_d /* nullable */);
+
 /* ---- network level: the resident, batched form of autoenc_fft / backprop_fft ------------------ */
 typedef struct {
     int D, Nx, Ny;        /* input frames [B][D][Nx][Ny] */
