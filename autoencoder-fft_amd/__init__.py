@@ -65,6 +65,12 @@ class TilePlan(C.Structure):
                 ("step_x", C.c_int), ("step_y", C.c_int), ("ramp_x", C.c_int), ("ramp_y", C.c_int)]
 
 
+class Region(C.Structure):
+    """include/aefft.h aefft_region (32 bytes; REGION is the numpy form)"""
+    _fields_ = [("i0", C.c_int), ("j0", C.c_int), ("i1", C.c_int), ("j1", C.c_int), ("area", C.c_int), ("peak_i", C.c_int), ("peak_j", C.c_int),
+                ("peak", C.c_float)]
+
+
 _lib = None
 _vp, _fp, _i, _l, _f = C.c_void_p, C.c_void_p, C.c_int, C.c_long, C.c_float   # device float* passed as void*
 
@@ -109,6 +115,9 @@ SIGNATURES = {
     "aefft_image_to_yuv": (_i, [_vp, _vp, C.c_size_t, C.c_size_t, _i, C.POINTER(YuvDst), _i]),
     "aefft_frames_resize_to_yuv": (_i, [_vp, _vp, _i, _i, _i, _i, _i, C.POINTER(YuvDst), _i]),
     "aefft_image_compare_map": (_i, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, C.c_size_t, C.c_size_t, _i, _i, _i, _i, _i, _i, _i, _fp, _fp]),
+    "aefft_map_regions_workspace": (C.c_size_t, [_i, _i, _i]),
+    "aefft_map_regions": (_i, [_vp, _fp, _fp, _i, _i, _i, _i, _f, _f, _i, _i, _vp, _vp, _i, _vp, _vp, C.c_size_t]),
+    "aefft_region_to_pixels": (_i, [C.POINTER(Region), _i, _i, _i, _i] + [C.POINTER(_i)] * 4),
     "aefft_net_create": (_i, [_vp, C.POINTER(NetDesc), C.POINTER(_vp)]),
     "aefft_net_create_ex": (_i, [_vp, C.POINTER(NetDesc), C.c_uint, C.POINTER(_vp)]),
     "aefft_net_destroy": (None, [_vp]),
@@ -543,6 +552,61 @@ def _image_compare_args(a, b, cells, metric, map, score):
     return ia, pa, sa, ib, pb, sb, (Mx, My), COMPARE_METRICS[metric]
 
 
+REGIONS_SENSE = {"above": 0, "below": 1}     # AEFFT_REGIONS_ABOVE, AEFFT_REGIONS_BELOW
+# aefft_region as a numpy structured dtype: regions.cpu().numpy().view(REGION)[..., 0] of the int32 tensor [B][max_regions][8] Context.map_regions returns
+REGION = np.dtype([("i0", "<i4"), ("j0", "<i4"), ("i1", "<i4"), ("j1", "<i4"), ("area", "<i4"), ("peak_i", "<i4"), ("peak_j", "<i4"), ("peak", "<f4")])
+
+
+def _map_regions_args(map, lo, hi, ref, sense, connectivity, min_area, max_regions, labels, regions, count):
+    """the checks of Context.map_regions that need no device: (map as [B][Mx][My], lo, hi, the sense's value, connectivity, min_area, max_regions);
+    `ref`, `labels`, `regions` and `count`, when given, are checked for shape, dtype and layout"""
+    what = "Context.map_regions"
+    if map.dtype != torch.float32 or map.dim() not in (2, 3) or not map.is_contiguous():
+        raise ValueError(f"{what}: map must be a contiguous float32 tensor [B][Mx][My] or [Mx][My]")
+    m = map if map.dim() == 3 else map[None]
+    B, Mx, My = m.shape
+    if not (1 <= Mx <= 1024 and 1 <= My <= 1024 and B >= 1 and B * Mx * My <= 2 ** 31 - 1):
+        raise ValueError(f"{what}: Mx, My must be in 1..1024, B >= 1 and B * Mx * My <= 2^31 - 1")
+    if sense not in REGIONS_SENSE:
+        raise ValueError(f"{what}: sense must be one of {sorted(REGIONS_SENSE)}")
+    if connectivity not in (4, 8) or isinstance(connectivity, bool):
+        raise ValueError(f"{what}: connectivity must be 4 or 8")
+    try:
+        lo = float(lo)
+        hi = lo if hi is None else float(hi)
+        min_area, max_regions = int(min_area), int(max_regions)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: lo, hi must be numbers and min_area, max_regions ints") from None
+    with np.errstate(over="ignore"):
+        finite = bool(np.isfinite(np.float32(lo)) and np.isfinite(np.float32(hi)))         # (as floats: what the library receives)
+    if not finite or (lo > hi if sense == "above" else hi > lo):
+        raise ValueError(f"{what}: lo and hi must be finite, lo <= hi for sense='above' and hi <= lo for sense='below'")
+    if min_area < 1 or not 0 <= max_regions <= 65536:
+        raise ValueError(f"{what}: min_area must be >= 1 and max_regions in 0..65536")
+    if ref is not None and (ref.dtype != torch.float32 or tuple(ref.shape) != (Mx, My) or not ref.is_contiguous()):
+        raise ValueError(f"{what}: ref must be a contiguous float32 tensor of shape {(Mx, My)}")
+    if labels is not None and (labels.dtype != torch.int32 or tuple(labels.shape) != (B, Mx, My) or not labels.is_contiguous()):
+        raise ValueError(f"{what}: labels must be a contiguous int32 tensor of shape {(B, Mx, My)}")
+    if regions is not None and (max_regions == 0 or regions.dtype != torch.int32 or tuple(regions.shape) != (B, max_regions, 8) or not regions.is_contiguous()):
+        raise ValueError(f"{what}: regions must be a contiguous int32 tensor of shape {(B, max_regions, 8)} (None when max_regions == 0)")
+    if count is not None and (count.dtype != torch.int32 or tuple(count.shape) != (B,) or not count.is_contiguous()):
+        raise ValueError(f"{what}: count must be a contiguous int32 tensor of shape {(B,)}")
+    return m, lo, hi, REGIONS_SENSE[sense], connectivity, min_area, max_regions
+
+
+def region_pixels(region, cells, W, H):
+    """The half-open pixel box (x0, y0, x1, y1) of a region on an image of W x H (aefft_region_to_pixels: Context.image_compare_map's cell rule,
+    x0 = ceil(i0 W / Mx), x1 = ceil((i1 + 1) W / Mx), rows alike): `region` is one REGION record, a Region, or anything with i0, j0, i1, j1;
+    cells = (Mx, My).  Host arithmetic; ValueError for bounds outside the grid or sizes outside image_compare_map's ranges."""
+    Mx, My = _two_ints(cells, "region_pixels", "cells must be (Mx, My)")
+    get = (lambda k: int(region[k])) if not isinstance(region, Region) else (lambda k: int(getattr(region, k)))
+    r = Region(get("i0"), get("j0"), get("i1"), get("j1"), 0, 0, 0, 0.0)
+    box = [C.c_int() for _ in range(4)]
+    if lib().aefft_region_to_pixels(C.byref(r), Mx, My, int(W), int(H), *[C.byref(v) for v in box]) != OK:
+        raise ValueError(f"region_pixels: bounds {(r.i0, r.j0, r.i1, r.j1)} outside the grid {(Mx, My)}, or W, H outside 1..8192, or more cells than pixels")
+    return tuple(v.value for v in box)
+
+
 class Context:
     """aefft_ctx on torch's current device, enqueuing on torch's current stream by default."""
 
@@ -849,6 +913,31 @@ class Context:
         self.check(self.L.aefft_image_compare_map(self.h, _ptr(ia), pa, sa, _ptr(ib), pb, sb, W, H, B, D, m, Mx, My, _ptr(map), _ptr(score)))
         return map, score
 
+    def map_regions(self, map, lo, hi=None, ref=None, sense="above", connectivity=8, min_area=1, max_regions=256, labels=None, regions=None, count=None):
+        """Detections from a map (aefft_map_regions): `map` is float32 [B][Mx][My] or [Mx][My] as Net.score_map, Net.ssim_map and
+        Context.image_compare_map return it, `ref` an optional per-cell baseline [Mx][My] subtracted first.  A cell is foreground when
+        v >= lo (sense "above") or v <= lo ("below": an SSIM map), strong when it passes `hi` too (hi=None: hi = lo, a plain threshold); the
+        4- or 8-connected components with a strong cell and at least `min_area` cells are numbered 1..n in the order of their first cell
+        (index I * My + J).  labels (int32 [B][Mx][My]) holds the numbers, 0 elsewhere; regions (int32 [B][max_regions][8], the bytes of
+        aefft_region: regions.cpu().numpy().view(REGION)[..., 0]) the first min(n, max_regions) boxes with area and peak, the rest untouched
+        (zeros when allocated here); count (int32 [B]) holds n.  max_regions=0 skips the regions (None is returned for them).  Everything is
+        allocated when None; the workspace is cached per shape.  Six launches, nothing waits for the device.  Returns (labels, regions, count)."""
+        m, lo, hi, s, conn, min_area, max_regions = _map_regions_args(map, lo, hi, ref, sense, connectivity, min_area, max_regions, labels, regions, count)
+        B, Mx, My = m.shape
+        if labels is None:
+            labels = self.empty(B, Mx, My, dtype=torch.int32)
+        if regions is None and max_regions:
+            regions = torch.zeros(B, max_regions, 8, dtype=torch.int32, device=m.device)
+        if count is None:
+            count = self.empty(B, dtype=torch.int32)
+        cache = self.__dict__.setdefault("_regions_work", {})
+        work = cache.get((B, Mx, My))
+        if work is None:
+            work = cache[(B, Mx, My)] = self.empty(self.L.aefft_map_regions_workspace(Mx, My, B), dtype=torch.uint8)
+        self.check(self.L.aefft_map_regions(self.h, _ptr(m), _ptr(ref), Mx, My, B, s, lo, hi, conn, min_area, _ptr(labels), _ptr(regions), max_regions,
+                                            _ptr(count), _ptr(work), work.numel()))
+        return labels, regions, count
+
     def frames_degrade(self, frames, blur=0, sigma=0.0, impulse=0.0, seed=0, first_frame=0, out=None, dtype=None):
         """The degraded input of target training from the clean frames (aefft_frames_degrade), one launch: `frames` uint8 or float32
         [B][D][Nx][Ny] (float values become pixels first) -> the binomial blur of radius `blur` in 0..4 (2 blur + 1 taps per axis, edges
@@ -1118,6 +1207,19 @@ class Net:
         cells = cells_for_tile(out.shape[2], out.shape[1], tile)
         map, score = self.ctx.image_compare_map(image if target is None else target, out, cells, metric, map=map, score=score)
         return map, score, out
+
+    def detect_tiled(self, image, overlap, rim=0, tile=16, metric="mse", lo=None, hi=None, ref=None, connectivity=8, min_area=1, max_regions=256,
+                     target=None, out=None):
+        """Detections at the image's own resolution: score_tiled(image, overlap, rim, tile, metric, target, out=out) without the score, then
+        Context.map_regions of its map with sense "below" when metric == "ssim" and "above" otherwise (`lo` is required; hi, ref, connectivity,
+        min_area and max_regions as there).  Context.region_pixels / region_pixels(region, cells_for_tile(W, H, tile), W, H) carries a box to
+        pixels.  An FFT net only.  Nothing waits for the device.  Returns (labels, regions, count, map, out)."""
+        if lo is None:
+            raise ValueError("Net.detect_tiled: lo (the threshold) is required")
+        map, _, out = self.score_tiled(image, overlap, rim, tile=tile, metric=metric, target=target, score=False, out=out)
+        labels, regions, count = self.ctx.map_regions(map, lo, hi, ref=ref, sense="below" if metric == "ssim" else "above", connectivity=connectivity,
+                                                      min_area=min_area, max_regions=max_regions)
+        return labels, regions, count, map, out
 
     def score(self, frames, score=None, recon=None):
         """Per-frame reconstruction error under the current weights (aefft_net_score): score[b] = mean over the frame's D*Nx*Ny pixels of

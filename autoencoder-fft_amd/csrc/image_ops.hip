@@ -318,6 +318,52 @@ extern "C" int aefft_frames_resize_to_yuv(aefft_ctx* ctx, const void* frames_d, 
     });
 }
 
+// regions (include/aefft.h "aefft_map_regions") ------------------------------------------------
+extern "C" size_t aefft_map_regions_workspace(int Mx, int My, int B) { return map_regions_workspace(Mx, My, B); }
+
+extern "C" int aefft_map_regions(aefft_ctx* ctx, const float* map_d, const float* ref_d, int Mx, int My, int B, int sense, float lo, float hi, int connectivity,
+                                 int min_area, int* labels_d, aefft_region* regions_d, int max_regions, int* count_d, void* work_d, size_t work_bytes)
+{
+    const Bad bad{ctx, "aefft_map_regions"};
+    if (!ctx || !map_d || !labels_d || !count_d || !work_d) return bad("null context, map, labels, count or workspace");
+    if (Mx < 1 || My < 1 || Mx > 1024 || My > 1024) return bad("Mx, My must be in 1..1024");
+    if (B < 1) return bad("B must be >= 1");
+    if ((long long)B * Mx * My > (long long)INT_MAX) return bad("B * Mx * My does not fit an int");
+    if (sense != AEFFT_REGIONS_ABOVE && sense != AEFFT_REGIONS_BELOW) return bad("sense must be AEFFT_REGIONS_ABOVE or AEFFT_REGIONS_BELOW");
+    if (connectivity != 4 && connectivity != 8) return bad("connectivity must be 4 or 8");
+    if (!std::isfinite(lo) || !std::isfinite(hi)) return bad("lo and hi must be finite");
+    if (sense == AEFFT_REGIONS_ABOVE ? lo > hi : hi > lo) return bad("lo and hi in the wrong order: AEFFT_REGIONS_ABOVE needs lo <= hi, AEFFT_REGIONS_BELOW hi <= lo");
+    if (min_area < 1) return bad("min_area must be >= 1");
+    if (max_regions < 0 || max_regions > 65536) return bad("max_regions must be in 0..65536");
+    if ((regions_d == nullptr) != (max_regions == 0)) return bad("regions_d must be NULL exactly when max_regions == 0");
+    if (!aligned16(map_d) || !aligned16(ref_d) || !aligned16(labels_d) || !aligned16(regions_d) || !aligned16(count_d) || !aligned16(work_d))
+        return bad("map_d, ref_d, labels_d, regions_d, count_d and work_d must be 16-byte aligned");
+    const size_t need = map_regions_workspace(Mx, My, B);
+    if (work_bytes < need) return bad("work_bytes is below aefft_map_regions_workspace(Mx, My, B)");
+    const size_t cells = (size_t)Mx * My, mb = (size_t)B * cells * 4;
+    // the outputs and the workspace against the inputs and one another (a null pointer has no range)
+    struct Range { const void* p; size_t n; bool out; };
+    const Range r[6] = {{map_d, mb, false}, {ref_d, ref_d ? cells * 4 : 0, false}, {labels_d, mb, true},
+                        {regions_d, (size_t)B * max_regions * sizeof(aefft_region), true}, {count_d, (size_t)B * 4, true}, {work_d, need, true}};
+    for (int i = 0; i < 6; ++i)
+        for (int j = i + 1; j < 6; ++j)
+            if ((r[i].out || r[j].out) && r[i].n && r[j].n && ranges_overlap(r[i].p, r[i].n, r[j].p, r[j].n))
+                return bad("the labels, regions, count and workspace ranges overlap an input or each other");
+    RET_IF(join_recon(ctx));                          // (the map may come out of a reconstruction that is still on the side stream)
+    return launch_or_fail(ctx, KID_IMAGE, (double)B * cells * 24.0 + 32.0 * B * max_regions, "map_regions", [&] {
+        return launch_map_regions(map_d, ref_d, Mx, My, B, sense, lo, hi, connectivity, min_area, labels_d, regions_d, max_regions, count_d, work_d, ctx->cur);
+    });
+}
+
+extern "C" int aefft_region_to_pixels(const aefft_region* r, int Mx, int My, int W, int H, int* x0, int* y0, int* x1, int* y1)
+{
+    if (!r || !x0 || !y0 || !x1 || !y1 || !dim_ok(W) || !dim_ok(H) || Mx < 1 || My < 1 || Mx > 1024 || My > 1024 || Mx > W || My > H) return AEFFT_EINVAL;
+    if (r->i0 < 0 || r->i0 > r->i1 || r->i1 >= Mx || r->j0 < 0 || r->j0 > r->j1 || r->j1 >= My) return AEFFT_EINVAL;
+    *x0 = (r->i0 * W + Mx - 1) / Mx; *x1 = ((r->i1 + 1) * W + Mx - 1) / Mx;      // ((i1 + 1) W <= 2^23)
+    *y0 = (r->j0 * H + My - 1) / My; *y1 = ((r->j1 + 1) * H + My - 1) / My;
+    return AEFFT_OK;
+}
+
 // compare (include/aefft.h "aefft_image_compare_map") -----------------------------------------
 extern "C" int aefft_image_compare_map(aefft_ctx* ctx, const unsigned char* a_d, size_t a_pitch, size_t a_stride, const unsigned char* b_d, size_t b_pitch,
                                        size_t b_stride, int W, int H, int B, int D, int metric, int Mx, int My, float* map_d, float* score_d)

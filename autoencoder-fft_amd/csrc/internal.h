@@ -132,6 +132,14 @@ hipError_t launch_compare_map(const unsigned char* a, size_t a_pitch, size_t a_s
                               int B, int D, int metric, int Mx, int My, float* map, hipStream_t st);
 // score[b] = the pixel-weighted mean of map[b] as stored, added along J, then along I, in double.  One launch.
 hipError_t launch_compare_score(const float* map, float* score, int W, int H, int B, int Mx, int My, hipStream_t st);
+// ---- regions_kernels.hip (aefft_map_regions) ----
+// map [B][Mx][My] (minus ref [Mx][My] where given) -> labels [B][Mx][My], regions [B][max_regions] (null exactly when max_regions == 0), count [B]:
+// hysteresis threshold, connected components, the kept ones numbered in index order (include/aefft.h).  work: map_regions_workspace bytes, 16 a cell.
+// Mx, My in 1..1024, B Mx My < 2^31, sense 0 / 1, connectivity 4 / 8, min_area >= 1, max_regions in 0..65536 (hipErrorInvalidValue otherwise).  Six
+// launches, integer atomics only, no workgroup waits for another.
+size_t map_regions_workspace(int Mx, int My, int B);      // 0 for sizes the launcher does not take
+hipError_t launch_map_regions(const float* map, const float* ref, int Mx, int My, int B, int sense, float lo, float hi, int connectivity, int min_area,
+                              int* labels, aefft_region* regions, int max_regions, int* count, void* work, hipStream_t st);
 size_t fft_mid_elems(long planes, int Nx, int Wc);   // complex elements needed in `mid`
 // sizes that are not powers of two (cufftPlanMany takes any size, fft.cu:773-779): even n in 8..1024 through Bluestein's chirp-z form on the
 // power-of-two LDS passes; rows -> transpose -> rows -> transpose.  w1, w2: workspaces of fft_any_ws_elems complex each.

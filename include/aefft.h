@@ -580,6 +580,53 @@ int aefft_image_compare_map(aefft_ctx* ctx,
                             int W, int H, int B, int D, int metric, int Mx, int My,
                             float* map_d, float* score_d /* nullable */);
 
+/* aefft_map_regions: detections from a map -- hysteresis threshold, connected components, a label map, per-region boxes with area and peak, and a
+ * per-image count, on the device: the step a caller of aefft_net_score_map, aefft_net_ssim_map or aefft_image_compare_map otherwise takes on the
+ * host, behind a copy and a synchronisation.
+ * map_d: float [B][Mx][My], My contiguous -- the layout the map calls write and the overlay reads.  ref_d: an optional per-cell baseline
+ * [Mx][My] shared by the batch (a calibration map from nominal footage), or NULL.  labels_d: int [B][Mx][My].  regions_d: aefft_region
+ * [B][max_regions], NULL exactly when max_regions == 0.  count_d: int [B].  work_d: work_bytes >= aefft_map_regions_workspace(Mx, My, B) bytes
+ * (16 a cell; 0 from the query means sizes the call does not take).  Mx, My in 1..1024; B >= 1 and B * Mx * My <= 2^31 - 1; min_area >= 1;
+ * max_regions in 0..65536; every pointer 16-byte aligned; the output buffers and the workspace disjoint from the inputs and from each other;
+ * lo and hi finite.  A cell is (I, J), I along Mx (the image's columns) and J along My (its rows); its linear index is I * My + J.
+ * Definition, exact -- nothing is rounded but the one subtraction:
+ *   1. Value: v = map[b][I][J] when ref_d is NULL, otherwise v = map[b][I][J] - ref[I][J], rounded once to float32.  A -0 result counts as +0.
+ *   2. Foreground: AEFFT_REGIONS_ABOVE requires lo <= hi; a cell is foreground when v >= lo and strong when v >= hi.  AEFFT_REGIONS_BELOW (an
+ *      SSIM map, where low is bad) requires hi <= lo; a cell is foreground when v <= lo and strong when v <= hi.  NaN is background, because
+ *      every comparison with it is false; +inf and -inf are ordinary values.
+ *   3. Components: the maximal connected sets of foreground cells of one image under 4- or 8-connectivity on the (I, J) grid; there is no
+ *      wrap-around and nothing connects across images.
+ *   4. Kept: a component is kept when it holds at least one strong cell and area >= min_area.  hi == lo means a plain threshold.
+ *   5. Numbering: the kept components of image b are numbered 1..n in ascending order of their smallest linear index I * My + J.
+ *      labels[b][I][J] is that number; background cells and cells of dropped components get 0.  count[b] = n, also when n > max_regions.
+ *   6. Regions: regions[b * max_regions + r - 1] is written for r <= min(n, max_regions): the inclusive bounds, the area in cells, and the peak
+ *      -- the maximal v under ABOVE, the minimal v under BELOW, at the smallest linear index that attains it.  Entries from index
+ *      min(n, max_regions) on are left untouched.
+ *   7. aefft_region_to_pixels: aefft_image_compare_map's cell rule, host arithmetic -- the half-open pixel ranges x0 = ceil(i0 W / Mx),
+ *      x1 = ceil((i1+1) W / Mx), y0 = ceil(j0 H / My), y1 = ceil((j1+1) H / My); the full grid gives (0, 0, W, H).  AEFFT_EINVAL for a null
+ *      pointer, bounds outside the grid (0 <= i0 <= i1 < Mx, 0 <= j0 <= j1 < My) or sizes outside that call's ranges (W, H in 1..8192,
+ *      1 <= Mx <= min(W, 1024), 1 <= My <= min(H, 1024)).
+ * Six launches on the context's stream (a tiled union-find: tiles in LDS, the tile edges by atomicMin, the sums by integer add / min / max and
+ * one 64-bit max); no host synchronisation, no allocation (the caller supplies the workspace); safe under stream capture; no workgroup waits for
+ * another; the result is a function of the inputs alone, on every run.  Accounted under the profile id `image` with
+ * B Mx My (4 + 4 + 16) + 32 B max_regions bytes.
+ * AEFFT_EINVAL, with aefft_last_error starting "aefft_map_regions: " and naming the rule, nothing enqueued and every output untouched: a null
+ * pointer; a size out of range; an unknown sense or connectivity; lo / hi that are non-finite or in the wrong order for the sense; misalignment;
+ * overlap; work_bytes below the query; regions_d and max_regions disagreeing; B * Mx * My beyond an int. */
+typedef struct {
+    int i0, j0, i1, j1;   /* inclusive cell bounds: I (image columns) in i0..i1, J (image rows) in j0..j1 */
+    int area;             /* cells */
+    int peak_i, peak_j;   /* the peak's cell */
+    float peak;           /* the peak's value v */
+} aefft_region;           /* 32 bytes, no padding */
+enum { AEFFT_REGIONS_ABOVE = 0, AEFFT_REGIONS_BELOW = 1 };   /* BELOW: an SSIM map, where low is bad */
+size_t aefft_map_regions_workspace(int Mx, int My, int B);   /* bytes; 0 on invalid sizes; at most 16 B per cell */
+int aefft_map_regions(aefft_ctx* ctx, const float* map_d, const float* ref_d /* nullable, [Mx][My] */,
+                      int Mx, int My, int B, int sense, float lo, float hi, int connectivity /* 4 or 8 */, int min_area,
+                      int* labels_d /* [B][Mx][My] */, aefft_region* regions_d /* nullable */, int max_regions,
+                      int* count_d /* [B] */, void* work_d, size_t work_bytes);
+int aefft_region_to_pixels(const aefft_region* r, int Mx, int My, int W, int H, int* x0, int* y0, int* x1, int* y1);  /* host arithmetic */
+
 /* ---- network level: the resident, batched form of autoenc_fft / backprop_fft ------------------ */
 typedef struct {
     int D, Nx, Ny;        /* input frames [B][D][Nx][Ny] */
