@@ -53,6 +53,13 @@ class YuvDst(C.Structure):
                 ("plane", C.c_void_p * 3), ("pitch", C.c_size_t * 3), ("stride", C.c_size_t * 3)]
 
 
+class RawDesc(C.Structure):
+    """include/aefft.h aefft_raw_desc"""
+    _fields_ = [("pattern", C.c_int), ("container", C.c_int), ("bits", C.c_int), ("W", C.c_int), ("H", C.c_int),
+                ("data", C.c_void_p), ("pitch", C.c_size_t), ("stride", C.c_size_t), ("black", C.c_int), ("white", C.c_int),
+                ("gain", C.c_float * 3), ("method", C.c_int), ("ccm", C.POINTER(C.c_float)), ("lut_d", C.c_void_p)]
+
+
 class TileDesc(C.Structure):
     """include/aefft.h aefft_tile_desc"""
     _fields_ = [("W", C.c_int), ("H", C.c_int), ("Nx", C.c_int), ("Ny", C.c_int),
@@ -118,6 +125,7 @@ SIGNATURES = {
     "aefft_map_regions_workspace": (C.c_size_t, [_i, _i, _i]),
     "aefft_map_regions": (_i, [_vp, _fp, _fp, _i, _i, _i, _i, _f, _f, _i, _i, _vp, _vp, _i, _vp, _vp, C.c_size_t]),
     "aefft_region_to_pixels": (_i, [C.POINTER(Region), _i, _i, _i, _i] + [C.POINTER(_i)] * 4),
+    "aefft_raw_to_image": (_i, [_vp, C.POINTER(RawDesc), _i, _vp, C.c_size_t, C.c_size_t, _i]),
     "aefft_net_create": (_i, [_vp, C.POINTER(NetDesc), C.POINTER(_vp)]),
     "aefft_net_create_ex": (_i, [_vp, C.POINTER(NetDesc), C.c_uint, C.POINTER(_vp)]),
     "aefft_net_destroy": (None, [_vp]),
@@ -344,6 +352,92 @@ def _yuv_dest(fmt, matrix, order, B, W, H, D, out, what):
     for k in range(3):
         dst.plane[k], dst.pitch[k], dst.stride[k] = src.plane[k], src.pitch[k], src.stride[k]
     return dst, views
+
+
+RAW_PATTERNS = {"rggb": 0, "grbg": 1, "gbrg": 2, "bggr": 3, "mono": 4}      # AEFFT_RAW_RGGB .. AEFFT_RAW_MONO: GenICam's names (BayerRG = "rggb")
+RAW_CONTAINERS = {"u8": 0, "u16": 1, "packed": 2}                            # AEFFT_RAW_U8, AEFFT_RAW_U16, AEFFT_RAW_PACKED
+DEMOSAIC_METHODS = {"bilinear": 0, "mhc": 1}                                 # AEFFT_DEMOSAIC_BILINEAR, AEFFT_DEMOSAIC_MHC
+
+
+def _raw_source(raw, pattern, bits, packed, black, white, gains, method, order, ccm, what):
+    """the checks of Context.raw_to_image that need no device: (the filled RawDesc without its table, B, W, H, D, what the descriptor points
+    into).  `raw` is a uint8 tensor [B][H][bytes] or [H][bytes] -- bits == 8: one sample a byte; packed: GenICam 10p / 12p rows, the last axis
+    the row's ceil(W * bits / 8) bytes, so W = 8 * bytes // bits -- or an int16 / uint16 tensor [B][H][W] or [H][W] with the sample in the low
+    `bits` bits; contiguous, or a view with stride(-1) == 1, a row pitch and any sufficient batch stride."""
+    import torch
+    if pattern not in RAW_PATTERNS or method not in DEMOSAIC_METHODS or (pattern != "mono" and order not in ("bgr", "rgb")):
+        raise ValueError(f"{what}: pattern must be one of {sorted(RAW_PATTERNS)}, method of {sorted(DEMOSAIC_METHODS)}, order 'bgr' or 'rgb'")
+    words = tuple(getattr(torch, n) for n in ("int16", "uint16") if hasattr(torch, n))
+    if not isinstance(raw, torch.Tensor) or raw.dtype not in (torch.uint8,) + words or raw.dim() not in (2, 3):
+        raise ValueError(f"{what}: raw must be a uint8, int16 or uint16 tensor [B][H][W] or [H][W] (uint8 packed: the rows' bytes)")
+    bits = int(bits)
+    if raw.dtype == torch.uint8:
+        container = "packed" if packed else "u8"
+        if (packed and bits not in (10, 12)) or (not packed and bits != 8):
+            raise ValueError(f"{what}: a uint8 tensor holds 8-bit samples, or with packed=True 10- or 12-bit ones")
+    else:
+        container = "u16"
+        if packed or not 9 <= bits <= 16:
+            raise ValueError(f"{what}: a 16-bit tensor holds samples of 9..16 bits, not packed")
+    v = raw if raw.dim() == 3 else raw.unsqueeze(0)
+    B, H, cols = v.shape
+    es = v.element_size()
+    sb, sy, sx = v.stride()
+    if min(B, H, cols) < 1 or (cols > 1 and sx != 1):
+        raise ValueError(f"{what}: raw must be non-empty with stride(-1) == 1; got shape {tuple(raw.shape)} with strides {tuple(raw.stride())}")
+    W = 8 * cols // bits if packed else cols
+    live = cols * es
+    pitch = sy * es if H > 1 else live
+    extent = (H - 1) * pitch + live
+    stride = sb * es if B > 1 else extent
+    if pitch < live or stride < extent:
+        raise ValueError(f"{what}: rows or images of raw overlap; got shape {tuple(raw.shape)} with strides {tuple(raw.stride())}")
+    if not (4 <= W <= 8192 and 4 <= H <= 8192):
+        raise ValueError(f"{what}: W, H must be in 4..8192, got {(W, H)}")
+    white = (1 << bits) - 1 if white is None else int(white)
+    black = int(black)
+    if not 0 <= black < white <= (1 << bits) - 1:
+        raise ValueError(f"{what}: black and white must satisfy 0 <= black < white <= 2^bits - 1")
+    mono = pattern == "mono"
+    try:
+        g = [float(x) for x in ([gains] if isinstance(gains, (int, float)) else gains)]
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: gains must be three numbers (R, G, B), or one for mono") from None
+    if len(g) not in ((1, 3) if mono else (3,)) or not all(np.isfinite(x) and 0.0 <= x <= 64.0 for x in g):
+        raise ValueError(f"{what}: gains must be three finite numbers (R, G, B) in 0..64, or one for mono")
+    desc = RawDesc()
+    desc.pattern, desc.container, desc.bits, desc.W, desc.H = RAW_PATTERNS[pattern], RAW_CONTAINERS[container], bits, W, H
+    desc.data, desc.pitch, desc.stride, desc.black, desc.white = v.data_ptr(), pitch, stride, black, white
+    for k in range(3):
+        desc.gain[k] = g[k if k < len(g) else 0]
+    desc.method = DEMOSAIC_METHODS[method]
+    keep = [v]
+    if ccm is not None and not mono:
+        m = np.asarray(ccm, dtype=np.float32).reshape(-1)
+        if m.size != 9 or not np.isfinite(m).all() or (np.abs(m) >= 4).any():
+            raise ValueError(f"{what}: ccm must be 9 finite numbers (3 x 3, row-major, out = ccm * (R, G, B)) below 4 in magnitude")
+        arr = (C.c_float * 9)(*m.tolist())
+        desc.ccm = C.cast(arr, C.POINTER(C.c_float))
+        keep.append(arr)
+    return desc, B, W, H, 1 if mono else 3, keep
+
+
+def gamma_lut(gamma=2.2):
+    """The 4096-byte table of Context.raw_to_image for a power law, as a numpy uint8 array: entry k stands for the linear value k / 16 grey
+    levels, lut[k] = floor(255 * (min(k, 4080) / 4080) ** (1 / gamma) + 0.5) in double; entries above 4080 (never read) repeat 255."""
+    gamma = float(gamma)
+    if not np.isfinite(gamma) or gamma <= 0:
+        raise ValueError("gamma_lut: gamma must be finite and positive")
+    x = np.minimum(np.arange(4096, dtype=np.float64), 4080.0) / 4080.0
+    return np.floor(255.0 * x ** (1.0 / gamma) + 0.5).astype(np.uint8)
+
+
+def srgb_lut():
+    """The 4096-byte table of Context.raw_to_image for the sRGB transfer curve (IEC 61966-2-1), as a numpy uint8 array: with
+    x = min(k, 4080) / 4080, lut[k] = floor(255 * (12.92 x if x <= 0.0031308 else 1.055 x ** (1 / 2.4) - 0.055) + 0.5) in double."""
+    x = np.minimum(np.arange(4096, dtype=np.float64), 4080.0) / 4080.0
+    y = np.where(x <= 0.0031308, 12.92 * x, 1.055 * x ** (1.0 / 2.4) - 0.055)
+    return np.floor(255.0 * y + 0.5).astype(np.uint8)
 
 
 def heat_lut(D=3):
@@ -995,6 +1089,38 @@ class Context:
         if tuple(img.shape) != (B, H, W, D):
             raise ValueError(f"{what}: out must have shape {(B, H, W, D)}")
         self.check(self.L.aefft_yuv_to_image(self.h, C.byref(desc), YUV_ORDERS[order], _ptr(img), pitch, stride, B))
+        return out
+
+    def raw_to_image(self, raw, pattern, bits=8, packed=False, black=0, white=None, gains=(1, 1, 1), method="mhc", order="bgr", ccm=None, lut=None, out=None):
+        """Raw sensor data to 8-bit images on the device (aefft_raw_to_image), one launch: `raw` is a uint8 device tensor [B][H][W] (or [H][W])
+        of 8-bit samples, with packed=True the bytes [B][H][ceil(W * bits / 8)] of GenICam 10p / 12p rows, or an int16 / uint16 tensor [B][H][W]
+        with the sample in the low `bits` (9..16) bits; contiguous or a view with a row pitch and any sufficient batch stride.  `pattern` is
+        GenICam's name of the mosaic -- "rggb" (BayerRG), "grbg", "gbrg", "bggr" -- or "mono"; `black` and `white` (None: 2**bits - 1) the sensor
+        levels mapped to 0 and 255, `gains` the white balance (R, G, B; mono: one number or the first), applied before the demosaic "mhc"
+        (Malvar-He-Cutler, 5 x 5) or "bilinear"; `ccm` an optional 3 x 3 colour matrix (out = ccm * (R, G, B)); `lut` an optional 4096-byte
+        table indexed in sixteenths of a linear grey level (gamma_lut, srgb_lut: a numpy array, uploaded here, or a uint8 device tensor).
+        Returns, or fills `out` with, the uint8 image rows [B][H][W][D], D = 3 in `order` "bgr" or "rgb", D = 1 for mono; `out` may be a
+        row-padded view or a region of interest.  All-integer arithmetic (include/aefft.h).  Nothing waits for the device."""
+        what = "Context.raw_to_image"
+        desc, B, W, H, D, keep = _raw_source(raw, pattern, bits, packed, black, white, gains, method, order, ccm, what)
+        if lut is not None:
+            if isinstance(lut, np.ndarray):
+                if lut.dtype != np.uint8 or lut.size != 4096:
+                    raise ValueError(f"{what}: lut must hold 4096 uint8 entries")
+                cache = self.__dict__.setdefault("_raw_luts", {})              # (uploaded once a table and kept: the launch may still be queued on return)
+                key = lut.tobytes()
+                if key not in cache:
+                    cache[key] = torch.as_tensor(np.frombuffer(key, dtype=np.uint8).copy(), device=f"cuda:{self.device}")
+                lut = cache[key]
+            elif not isinstance(lut, torch.Tensor) or lut.dtype != torch.uint8 or lut.numel() != 4096 or not lut.is_contiguous():
+                raise ValueError(f"{what}: lut must be a numpy array or a contiguous uint8 device tensor of 4096 entries")
+            desc.lut_d = lut.data_ptr()
+        if out is None:
+            out = self.empty(B, H, W, D, dtype=torch.uint8)
+        img, pitch, stride = _resize_layout(out, what)
+        if tuple(img.shape) != (B, H, W, D):
+            raise ValueError(f"{what}: out must have shape {(B, H, W, D)}")
+        self.check(self.L.aefft_raw_to_image(self.h, C.byref(desc), YUV_ORDERS.get(order, 0), _ptr(img), pitch, stride, B))
         return out
 
     def yuv_resize_to_frames(self, planes, fmt, size, matrix="bt601", order="bgr", mode="linear", out=None, dtype=torch.uint8):

@@ -364,6 +364,44 @@ extern "C" int aefft_region_to_pixels(const aefft_region* r, int Mx, int My, int
     return AEFFT_OK;
 }
 
+// raw sensor data (include/aefft.h "aefft_raw_to_image") ----------------------------------------
+static const RowWords RAW_WORDS = {"pitch too small: U8 pitch >= W, U16 pitch >= 2 W, PACKED pitch >= ceil(W * bits / 8)", "H * pitch does not fit the address space",
+                                   "stride must be at least (H - 1) * pitch + the live bytes of a row for B > 1", "B * stride does not fit the address space"};
+
+extern "C" int aefft_raw_to_image(aefft_ctx* ctx, const aefft_raw_desc* src, int order, unsigned char* image_d, size_t pitch, size_t image_stride, int B)
+{
+    const Bad bad{ctx, "aefft_raw_to_image"};
+    if (!ctx || !src || !src->data || !image_d) return bad("null context, descriptor, data or image");
+    if (src->pattern < AEFFT_RAW_RGGB || src->pattern > AEFFT_RAW_MONO) return bad("pattern must be AEFFT_RAW_RGGB, _GRBG, _GBRG, _BGGR or _MONO");
+    if (src->container != AEFFT_RAW_U8 && src->container != AEFFT_RAW_U16 && src->container != AEFFT_RAW_PACKED) return bad("container must be AEFFT_RAW_U8, AEFFT_RAW_U16 or AEFFT_RAW_PACKED");
+    if (src->method != AEFFT_DEMOSAIC_BILINEAR && src->method != AEFFT_DEMOSAIC_MHC) return bad("method must be AEFFT_DEMOSAIC_BILINEAR or AEFFT_DEMOSAIC_MHC");
+    const bool mono = src->pattern == AEFFT_RAW_MONO;
+    if (!mono && order != AEFFT_YUV_BGR && order != AEFFT_YUV_RGB) return bad("order must be AEFFT_YUV_BGR or AEFFT_YUV_RGB");
+    const int bits = src->bits, D = mono ? 1 : 3;
+    if (src->container == AEFFT_RAW_U8 ? bits != 8 : src->container == AEFFT_RAW_U16 ? (bits < 9 || bits > 16) : (bits != 10 && bits != 12))
+        return bad("bits must be 8 for AEFFT_RAW_U8, 9..16 for AEFFT_RAW_U16 and 10 or 12 for AEFFT_RAW_PACKED");
+    if (B < 1 || src->W < 4 || src->W > 8192 || src->H < 4 || src->H > 8192) return bad("B must be >= 1 and W, H in 4..8192");
+    if (src->container == AEFFT_RAW_U16 && ((reinterpret_cast<uintptr_t>(src->data) | src->pitch | (B > 1 ? src->stride : 0)) & 1u))
+        return bad("AEFFT_RAW_U16 needs data, pitch and stride to be multiples of 2");
+    const size_t W = (size_t)src->W, H = (size_t)src->H;
+    const size_t live = src->container == AEFFT_RAW_U8 ? W : src->container == AEFFT_RAW_U16 ? 2 * W : (W * bits + 7) / 8;
+    size_t sext = 0, extent = 0;
+    RET_IF(chk_rows(bad, RAW_WORDS, src->pitch, src->stride, live, H, B, &sext));
+    RET_IF(chk_rows(bad, IMAGE_WORDS, pitch, image_stride, W * D, H, B, &extent));
+    if (src->black < 0 || src->black >= src->white || src->white > (1 << bits) - 1) return bad("black and white must satisfy 0 <= black < white <= 2^bits - 1");
+    for (int c = 0; c < D; ++c) {
+        if (!std::isfinite(src->gain[c]) || src->gain[c] < 0.f || src->gain[c] > 64.f) return bad("every gain must be finite and in 0..64");
+        if (raw_multiplier(src->gain[c], src->black, src->white) > 1073741824.0) return bad("gain * 255 * 65536 / (white - black) exceeds 2^30");
+    }
+    for (int k = 0; k < 9 && !mono && src->ccm; ++k)
+        if (!std::isfinite(src->ccm[k]) || std::fabs(src->ccm[k]) >= 4.f) return bad("every ccm entry must be finite and below 4 in magnitude");
+    if (ranges_overlap(src->data, sext, image_d, extent)) return bad("the source and image ranges overlap (the op is out-of-place)");
+    if (src->lut_d && ranges_overlap(src->lut_d, 4096, image_d, extent)) return bad("the table and image ranges overlap");
+    RET_IF(join_recon(ctx));                          // (the source may be a buffer the side stream is still writing)
+    return launch_or_fail(ctx, KID_IMAGE, (double)B * (double)H * ((double)live + (double)(W * D)) + (src->lut_d ? 4096.0 : 0.0), "raw_to_image",
+                          [&] { return launch_raw_image(*src, order, image_d, pitch, image_stride, B, ctx->cur); });
+}
+
 // compare (include/aefft.h "aefft_image_compare_map") -----------------------------------------
 extern "C" int aefft_image_compare_map(aefft_ctx* ctx, const unsigned char* a_d, size_t a_pitch, size_t a_stride, const unsigned char* b_d, size_t b_pitch,
                                        size_t b_stride, int W, int H, int B, int D, int metric, int Mx, int My, float* map_d, float* score_d)

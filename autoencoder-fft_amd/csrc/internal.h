@@ -140,6 +140,13 @@ hipError_t launch_compare_score(const float* map, float* score, int W, int H, in
 size_t map_regions_workspace(int Mx, int My, int B);      // 0 for sizes the launcher does not take
 hipError_t launch_map_regions(const float* map, const float* ref, int Mx, int My, int B, int sense, float lo, float hi, int connectivity, int min_area,
                               int* labels, aefft_region* regions, int max_regions, int* count, void* work, hipStream_t st);
+// ---- bayer_kernels.hip (aefft_raw_to_image) ----
+// B raw images of W x H samples (the descriptor of include/aefft.h: Bayer pattern or MONO, U8 / U16 / PACKED container, black, white, gains, demosaic
+// method, colour matrix, table) -> B interleaved 8-bit images of D = 3 channels (order 0 BGR / 1 RGB) or, MONO, D = 1: layout as launch_yuv_image's
+// destination.  W, H in 4..8192; any alignment of either side (U16: even); hipErrorInvalidValue for what the kernels cannot serve, the C entry
+// point checks the rest.  One launch.  raw_multiplier: the Q16 multiplier m_c of a gain as the launcher quantises it (an integer in a double).
+double raw_multiplier(float gain, int black, int white);
+hipError_t launch_raw_image(const aefft_raw_desc& d, int order, unsigned char* image, size_t ipitch, size_t istride, int B, hipStream_t st);
 size_t fft_mid_elems(long planes, int Nx, int Wc);   // complex elements needed in `mid`
 // sizes that are not powers of two (cufftPlanMany takes any size, fft.cu:773-779): even n in 8..1024 through Bluestein's chirp-z form on the
 // power-of-two LDS passes; rows -> transpose -> rows -> transpose.  w1, w2: workspaces of fft_any_ws_elems complex each.

@@ -627,6 +627,85 @@ int aefft_map_regions(aefft_ctx* ctx, const float* map_d, const float* ref_d /* 
                       int* count_d /* [B] */, void* work_d, size_t work_bytes);
 int aefft_region_to_pixels(const aefft_region* r, int Mx, int My, int W, int H, int* x0, int* y0, int* x1, int* y1);  /* host arithmetic */
 
+/* aefft_raw_to_image: sensor data as delivered -- what a GigE / USB3 Vision or MIPI industrial camera sends: the raw colour-filter mosaic
+ * (BayerRG8, BayerRG12, BayerRG12p, ...) or Mono8 / Mono12 / Mono16, one linear sample per pixel with a black level and often more than 8 bits --
+ * to the interleaved 8-bit image the image calls take (aefft_image_resize_to_frames, aefft_image_tiles_to_frames, aefft_image_compare_map, the
+ * tiled net calls).  Black level, white balance, demosaic, colour matrix and the gamma table are applied on the device, in one launch, before the
+ * value is cut to 8 bits; everything behind the host's quantisations is integer arithmetic, so the result is defined bit for bit.
+ * Source: the descriptor below, read on the host during the call (it need not outlive it; neither need ccm).  W x H samples, each in 4..8192,
+ * odd sizes included.  Row y of image b starts at data + b * stride + y * pitch (stride is ignored when B == 1); data is a device pointer of ANY
+ * alignment.  Sample x of a row, r:
+ *   AEFFT_RAW_U8      the byte at x; bits == 8; pitch >= W.
+ *   AEFFT_RAW_U16     the little-endian 16-bit word at 2 x, the value in its low `bits` bits, bits in 9..16 (bits of the word above `bits` are
+ *                     ignored); pitch >= 2 W; data, pitch and stride must be multiples of 2.
+ *   AEFFT_RAW_PACKED  GenICam's 10p / 12p (bits == 10 or 12): bits [x * bits, (x + 1) * bits) of the row's bytes read as a little-endian bit
+ *                     stream (bit k of the stream is bit k mod 8 of byte k / 8); pitch >= ceil(W * bits / 8).  The MIPI RAW10 / RAW12 byte
+ *                     order (the high bytes of a group first, the low bits gathered in a trailing byte) is a different layout and is out of scope.
+ * Source bytes beyond a row's live bytes (W, 2 W, ceil(W * bits / 8)) are never read.  For B > 1 stride must be at least (H - 1) * pitch + the live
+ * bytes of a row.
+ * Pattern: the name gives the colours of pixels (0,0), (1,0) of row 0 and (0,1), (1,1) of row 1 -- AEFFT_RAW_RGGB: R G / G B, GRBG: G R / B G,
+ * GBRG: G B / R G, BGGR: B G / G R.  This is GenICam's naming (BayerRG = RGGB).  OpenCV's COLOR_Bayer* names are shifted by one pixel: they name
+ * pixels (1,1), (2,1) of the mosaic, so COLOR_BayerBG2BGR is the conversion for a GenICam BayerRG sensor.  A region of interest is pointer
+ * arithmetic on the caller's side (U8, U16; PACKED when x0 * bits is a multiple of 8); an odd x0 or y0 offset selects the other pattern.
+ *   1. Linearise.  Once on the host, in double, per colour c: m_c = floor(gain_c * 255 * 65536 / (white - black) + 0.5); AEFFT_EINVAL if
+ *      m_c > 2^30.  Per sample of colour c: s = max(r - black, 0), u = min(s * m_c, 255 << 16), the product as in 64 bits.  u is the sample in Q16
+ *      grey levels, below 2^24.  (Clamping s at ceil((255 << 16) / m_c) first and multiplying in 32 bits gives the same bits.)  Samples are
+ *      white-balanced and clipped BEFORE the demosaic.  0 <= black < white <= 2^bits - 1; gain[] is R, G, B, each finite and in 0..64.
+ *   2. Borders.  An index outside the image is reflected without repeating the edge: -1 -> 1, -2 -> 2, W -> W - 2, W + 1 -> W - 3 (rows alike).
+ *      This keeps the mosaic's parity.
+ *   3. Demosaic.  At each pixel the native colour is u itself; the two missing colours v come from the filters below over the samples u around
+ *      it, c the sample at the pixel, N, S, E, W its neighbours, NE .. SW the diagonal ones, N2, S2, E2, W2 those two pixels away.  "R" stands for
+ *      the colour being produced and swaps with B by symmetry.
+ *      AEFFT_DEMOSAIC_BILINEAR (rounded means):
+ *        G at an R/B site    (N + S + E + W + 2) >> 2
+ *        R at a G site       (a + b + 1) >> 1 of its two R neighbours (E, W in an R row; N, S in a B row)
+ *        R at a B site       (NE + NW + SE + SW + 2) >> 2
+ *      AEFFT_DEMOSAIC_MHC (Malvar-He-Cutler's gradient-corrected 5 x 5 filters, scaled to sixteenths): v = clamp((sum + 8) >> 4, 0, 255 << 16),
+ *      >> an arithmetic shift; 32 bits suffice (|sum| < 2^29):
+ *        G at an R/B site                   8 c + 4 (N + S + E + W) - 2 (N2 + S2 + E2 + W2)
+ *        R at a G site, R in the same row   10 c + 8 (E + W) - 2 (E2 + W2) + (N2 + S2) - 2 (NE + NW + SE + SW)
+ *        R at a G site, R in the same column  the transpose: 10 c + 8 (N + S) - 2 (N2 + S2) + (E2 + W2) - 2 (NE + NW + SE + SW)
+ *        R at a B site                      12 c + 4 (NE + NW + SE + SW) - 3 (N2 + S2 + E2 + W2)
+ *      Every filter's coefficients sum to 16: a constant mosaic gives a constant image under both methods.
+ *   4. Colour matrix.  ccm is a HOST pointer to 9 floats, row-major, out = ccm * (R, G, B); NULL is the identity and gives the identity's bits.
+ *      c_ij = floor(ccm_ij * 1024 + 0.5) once on the host (floor, so negatives round to nearest too); each entry finite and |entry| < 4.
+ *      q_j = (v_j + 128) >> 8 (the native colour's v is u);  o_i = sum_j c_ij q_j, which is Q18 with |o| < 2^30.
+ *   5. Output byte.  Without a table (lut_d == NULL): clamp((o + 2^17) >> 18, 0, 255).  With lut_d, a DEVICE pointer to 4096 bytes of any
+ *      alignment: lut[clamp((o + 2^13) >> 14, 0, 4080)] -- the table is indexed in sixteenths of a grey level of the LINEAR value, so gamma is
+ *      applied before the value is cut to 8 bits; entries above 4080 are never read.  The identity table (lut[k] = (k + 8) >> 4) is NOT promised to
+ *      equal the no-table route: it rounds twice.  Channels are stored B, G, R (order AEFFT_YUV_BGR) or R, G, B (AEFFT_YUV_RGB): D = 3.
+ *   6. AEFFT_RAW_MONO.  Step 1 with gain[0], no demosaic: q = (u + 128) >> 8, o = 1024 q, then step 5.  D = 1; order, ccm and method's filters
+ *      are ignored (method must still be a known value).
+ * Consequences: with 8-bit samples, black 0, white 255, gains 1, no ccm and no table every pixel's native channel is its raw byte; a constant
+ * mosaic gives a constant image; a PACKED source gives the bytes of the U16 source that holds the same samples.
+ * Destination: the layout and rules of aefft_yuv_to_image -- pixel (row y, column x), channel d, at y * pitch + x * D + d; pitch >= W * D; image b
+ * at b * image_stride, image_stride >= (H - 1) * pitch + W * D for B > 1 (ignored when B == 1); any alignment: dword stores when image_d, pitch and
+ * image_stride are all multiples of 4, byte stores otherwise, the same bytes on both routes; bytes beyond W * D of a row are never written.
+ * One launch on the context's stream; no host synchronisation, no allocation, no workspace; safe under stream capture.  Out-of-place.  Accounted
+ * under the profile id `image` with the bytes read plus the bytes written: B H times the live bytes of a source row, plus B W H D image bytes,
+ * plus 4096 with a table.
+ * AEFFT_EINVAL, with aefft_last_error starting "aefft_raw_to_image: " and naming the rule, nothing enqueued and the outputs untouched: a null
+ * context, descriptor, data or image; an unknown pattern, container, method or order; a `bits` value the container does not take; a size or B out
+ * of range; a U16 pointer, pitch or stride that is odd; a pitch or stride too small; black / white out of order or out of range; a gain or ccm
+ * entry that is not finite or out of range; m_c > 2^30; source, table and destination ranges that overlap; sizes that overflow the address
+ * space. */
+enum { AEFFT_RAW_RGGB = 0, AEFFT_RAW_GRBG = 1, AEFFT_RAW_GBRG = 2, AEFFT_RAW_BGGR = 3, AEFFT_RAW_MONO = 4 };  /* pattern */
+enum { AEFFT_RAW_U8 = 0, AEFFT_RAW_U16 = 1, AEFFT_RAW_PACKED = 2 };                                         /* container */
+enum { AEFFT_DEMOSAIC_BILINEAR = 0, AEFFT_DEMOSAIC_MHC = 1 };
+typedef struct {
+    int pattern, container, bits;      /* bits: 8 (U8); 9..16 (U16, little endian, value in the low bits); 10 or 12 (PACKED) */
+    int W, H;                          /* 4..8192 each, odd sizes included */
+    const void* data;                  /* device pointer, ANY alignment (U16: a multiple of 2) */
+    size_t pitch, stride;              /* bytes per row; image b at data + b * stride, ignored when B == 1 */
+    int black, white;                  /* 0 <= black < white <= 2^bits - 1 */
+    float gain[3];                     /* R, G, B (MONO: gain[0]); finite, 0..64 */
+    int method;
+    const float* ccm;                  /* HOST float[9], row-major, out = ccm * (R,G,B); nullable = identity; |entry| < 4; ignored for MONO */
+    const unsigned char* lut_d;        /* DEVICE, 4096 bytes, nullable; any alignment */
+} aefft_raw_desc;
+int aefft_raw_to_image(aefft_ctx* ctx, const aefft_raw_desc* src, int order /* AEFFT_YUV_BGR | _RGB; MONO: ignored, D = 1 */,
+                       unsigned char* image_d, size_t pitch, size_t image_stride, int B);
+
 /* ---- network level: the resident, batched form of autoenc_fft / backprop_fft ------------------ */
 typedef struct {
     int D, Nx, Ny;        /* input frames [B][D][Nx][Ny] */
