@@ -126,6 +126,11 @@ SIGNATURES = {
     "aefft_map_regions": (_i, [_vp, _fp, _fp, _i, _i, _i, _i, _f, _f, _i, _i, _vp, _vp, _i, _vp, _vp, C.c_size_t]),
     "aefft_region_to_pixels": (_i, [C.POINTER(Region), _i, _i, _i, _i] + [C.POINTER(_i)] * 4),
     "aefft_raw_to_image": (_i, [_vp, C.POINTER(RawDesc), _i, _vp, C.c_size_t, C.c_size_t, _i]),
+    "aefft_map_stats_bytes": (C.c_size_t, [_i, _i]),
+    "aefft_map_stats_update": (_i, [_vp, _fp, _i, _i, _i, _vp, C.c_size_t]),
+    "aefft_map_stats_merge": (_i, [_vp, _vp, _vp, _i, _i, C.c_size_t]),
+    "aefft_map_stats_finish": (_i, [_vp, _vp, C.c_size_t, _i, _i, _i, _i, _f, _i, _f, _fp]),
+    "aefft_map_peak": (_i, [_vp, _fp, _fp, _i, _i, _i, _i, _fp, _vp]),
     "aefft_net_create": (_i, [_vp, C.POINTER(NetDesc), C.POINTER(_vp)]),
     "aefft_net_create_ex": (_i, [_vp, C.POINTER(NetDesc), C.c_uint, C.POINTER(_vp)]),
     "aefft_net_destroy": (None, [_vp]),
@@ -701,6 +706,109 @@ def region_pixels(region, cells, W, H):
     return tuple(v.value for v in box)
 
 
+CALIB_MODE = {"sigma": 0, "rank": 1}         # AEFFT_CALIB_SIGMA, AEFFT_CALIB_RANK
+
+
+def map_stats_bytes(Mx, My):
+    """aefft_map_stats_bytes without the library: 52 bytes a cell rounded up to a multiple of 16; 0 for sizes outside 1..1024"""
+    return (52 * Mx * My + 15) // 16 * 16 if 1 <= Mx <= 1024 and 1 <= My <= 1024 else 0
+
+
+def _stats_state(state, Mx, My, what, name="state"):
+    """a calibration state of Mx x My cells: a contiguous 1-D uint8 tensor of at least map_stats_bytes(Mx, My) bytes"""
+    need = map_stats_bytes(Mx, My)
+    if not need:
+        raise ValueError(f"{what}: Mx, My must be in 1..1024")
+    if not isinstance(state, torch.Tensor) or state.dtype != torch.uint8 or state.dim() != 1 or not state.is_contiguous() or state.numel() < need:
+        raise ValueError(f"{what}: {name} must be a contiguous 1-D uint8 tensor of at least {need} bytes (Context.map_stats({Mx}, {My}))")
+    return state
+
+
+def map_stats_view(state, Mx, My):
+    """The five planes of a calibration state as tensor views, in the layout include/aefft.h states: (S1, S2, hi, lo, c) with S1, S2 float64
+    [Mx][My], hi, lo float32 [4][Mx][My] (hi[0] the largest, lo[0] the smallest; only the first min(c, 4) slots are live) and c int32 [Mx][My]."""
+    Mx, My = _two_ints((Mx, My), "map_stats_view", "Mx, My must be ints")
+    s = _stats_state(state, Mx, My, "map_stats_view")
+    n = Mx * My
+    return (s[:8 * n].view(torch.float64).view(Mx, My), s[8 * n:16 * n].view(torch.float64).view(Mx, My), s[16 * n:32 * n].view(torch.float32).view(4, Mx, My),
+            s[32 * n:48 * n].view(torch.float32).view(4, Mx, My), s[48 * n:52 * n].view(torch.int32).view(Mx, My))
+
+
+def _maps3(map, what):
+    """a batch of maps as [B][Mx][My]"""
+    if not isinstance(map, torch.Tensor) or map.dtype != torch.float32 or map.dim() not in (2, 3) or not map.is_contiguous():
+        raise ValueError(f"{what}: map must be a contiguous float32 tensor [B][Mx][My] or [Mx][My]")
+    m = map if map.dim() == 3 else map[None]
+    B, Mx, My = m.shape
+    if not (1 <= Mx <= 1024 and 1 <= My <= 1024 and B >= 1 and B * Mx * My <= 2 ** 31 - 1):
+        raise ValueError(f"{what}: Mx, My must be in 1..1024, B >= 1 and B * Mx * My <= 2^31 - 1")
+    return m
+
+
+def _map_stats_update_args(state, map):
+    """the checks of Context.map_stats_update that need no device: map as [B][Mx][My]"""
+    what = "Context.map_stats_update"
+    m = _maps3(map, what)
+    _stats_state(state, m.shape[1], m.shape[2], what)
+    return m
+
+
+def _map_stats_merge_args(dst, src, cells):
+    """the checks of Context.map_stats_merge that need no device: (Mx, My) -- `cells`, or what Context.map_stats noted on dst or src"""
+    what = "Context.map_stats_merge"
+    if cells is None:
+        cells = getattr(dst, "cells", None) or getattr(src, "cells", None)
+    if cells is None:
+        raise ValueError(f"{what}: cells=(Mx, My) is needed for states that do not come from Context.map_stats")
+    Mx, My = _two_ints(cells, what, "cells must be (Mx, My)")
+    _stats_state(dst, Mx, My, what, "dst")
+    _stats_state(src, Mx, My, what, "src")
+    if dst.data_ptr() == src.data_ptr():
+        raise ValueError(f"{what}: dst and src must be two states")
+    return Mx, My
+
+
+def _map_stats_finish_args(state, cells, mode, sense, k, rank, empty, ref):
+    """the checks of Context.map_stats_finish that need no device: (Mx, My, the mode's value, the sense's value, k, rank, empty)"""
+    what = "Context.map_stats_finish"
+    Mx, My = _two_ints(cells, what, "cells must be (Mx, My)")
+    _stats_state(state, Mx, My, what)
+    if mode not in CALIB_MODE:
+        raise ValueError(f"{what}: mode must be one of {sorted(CALIB_MODE)}")
+    if sense not in REGIONS_SENSE:
+        raise ValueError(f"{what}: sense must be one of {sorted(REGIONS_SENSE)}")
+    try:
+        k, empty = float(k), float(empty)
+        if isinstance(rank, bool) or int(rank) != rank:
+            raise ValueError
+        rank = int(rank)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: k and empty must be numbers and rank an int") from None
+    with np.errstate(over="ignore"):
+        finite = bool(np.isfinite(np.float32(k)))                                # (as a float: what the library receives)
+    if not finite or not 1 <= rank <= 4:
+        raise ValueError(f"{what}: k must be finite and rank in 1..4")
+    if ref is not None and (not isinstance(ref, torch.Tensor) or ref.dtype != torch.float32 or tuple(ref.shape) != (Mx, My) or not ref.is_contiguous()):
+        raise ValueError(f"{what}: ref must be a contiguous float32 tensor of shape {(Mx, My)}")
+    return Mx, My, CALIB_MODE[mode], REGIONS_SENSE[sense], k, rank, empty
+
+
+def _map_peak_args(map, ref, sense, peak, cell):
+    """the checks of Context.map_peak that need no device: (map as [B][Mx][My], the sense's value)"""
+    what = "Context.map_peak"
+    m = _maps3(map, what)
+    B, Mx, My = m.shape
+    if sense not in REGIONS_SENSE:
+        raise ValueError(f"{what}: sense must be one of {sorted(REGIONS_SENSE)}")
+    if ref is not None and (not isinstance(ref, torch.Tensor) or ref.dtype != torch.float32 or tuple(ref.shape) != (Mx, My) or not ref.is_contiguous()):
+        raise ValueError(f"{what}: ref must be a contiguous float32 tensor of shape {(Mx, My)}")
+    if peak is not None and (not isinstance(peak, torch.Tensor) or peak.dtype != torch.float32 or tuple(peak.shape) != (B,) or not peak.is_contiguous()):
+        raise ValueError(f"{what}: peak must be a contiguous float32 tensor of shape {(B,)}")
+    if cell is not None and (not isinstance(cell, torch.Tensor) or cell.dtype != torch.int32 or tuple(cell.shape) != (B,) or not cell.is_contiguous()):
+        raise ValueError(f"{what}: cell must be a contiguous int32 tensor of shape {(B,)}")
+    return m, REGIONS_SENSE[sense]
+
+
 class Context:
     """aefft_ctx on torch's current device, enqueuing on torch's current stream by default."""
 
@@ -1032,6 +1140,59 @@ class Context:
                                             _ptr(count), _ptr(work), work.numel()))
         return labels, regions, count
 
+    def map_stats(self, Mx, My):
+        """An empty calibration state for maps of Mx x My cells: a zeroed uint8 device tensor of aefft_map_stats_bytes(Mx, My) bytes (all-zero
+        bytes are the empty state; map_stats_view shows its planes).  The grid is noted on the tensor as `cells` for map_stats_merge."""
+        Mx, My = _two_ints((Mx, My), "Context.map_stats", "Mx, My must be ints")
+        need = self.L.aefft_map_stats_bytes(Mx, My)
+        if not need:
+            raise ValueError("Context.map_stats: Mx, My must be in 1..1024")
+        state = torch.zeros(need, dtype=torch.uint8, device=f"cuda:{self.device}")
+        state.cells = (Mx, My)
+        return state
+
+    def map_stats_update(self, state, map):
+        """The maps of nominal footage enter a calibration state (aefft_map_stats_update): `map` is float32 [B][Mx][My] or [Mx][My] as the map
+        calls return it, `state` what map_stats(Mx, My) gave.  Per cell, in ascending b: a non-finite value is skipped; otherwise the sums of the
+        values and of their squares (double), the count and the four largest and four smallest values take it in.  In place, one launch,
+        nothing waits for the device.  Returns `state`."""
+        m = _map_stats_update_args(state, map)
+        B, Mx, My = m.shape
+        self.check(self.L.aefft_map_stats_update(self.h, _ptr(m), Mx, My, B, _ptr(state), state.numel()))
+        return state
+
+    def map_stats_merge(self, dst, src, cells=None):
+        """Two sessions' or two ranks' states as one (aefft_map_stats_merge): `src` enters `dst` -- the sums and counts add, the extremes are the
+        four largest and smallest of both.  cells=(Mx, My) is needed only for states that do not come from map_stats.  Returns `dst`."""
+        Mx, My = _map_stats_merge_args(dst, src, cells)
+        self.check(self.L.aefft_map_stats_merge(self.h, _ptr(dst), _ptr(src), Mx, My, min(dst.numel(), src.numel())))
+        return dst
+
+    def map_stats_finish(self, state, cells, mode="rank", sense="above", k=3.0, rank=1, empty=float("inf"), ref=None):
+        """The baseline map_regions takes as `ref`, out of a calibration state (aefft_map_stats_finish): cells = (Mx, My).  mode "rank": the
+        rank-th largest (sense "above") or smallest ("below") value each cell saw, rank in 1..4 -- the nominal footage's maximum with rank - 1
+        outliers tolerated, exact; mode "sigma": mean + k * standard deviation in double (k negative for "below").  A cell that counted nothing
+        gets `empty` (inf: never foreground under "above").  `ref` (float32 [Mx][My]) is allocated when None.  Returns `ref`."""
+        Mx, My, m, s, k, rank, empty = _map_stats_finish_args(state, cells, mode, sense, k, rank, empty, ref)
+        if ref is None:
+            ref = self.empty(Mx, My)
+        self.check(self.L.aefft_map_stats_finish(self.h, _ptr(state), state.numel(), Mx, My, m, s, k, rank, empty, _ptr(ref)))
+        return ref
+
+    def map_peak(self, map, ref=None, sense="above", peak=None, cell=None):
+        """The per-image peak of map - ref (aefft_map_peak): the image-level anomaly score, and over nominal footage the number map_regions' `hi`
+        is chosen from.  `map` is float32 [B][Mx][My] or [Mx][My], `ref` an optional baseline [Mx][My]; peak[b] (float32 [B]) is the largest
+        (sense "above") or smallest ("below") value over the cells that are not NaN, cell[b] (int32 [B]) the smallest index I * My + J that
+        attains it; an image of NaN only gives NaN and -1.  One launch, nothing waits for the device.  Returns (peak, cell)."""
+        m, s = _map_peak_args(map, ref, sense, peak, cell)
+        B, Mx, My = m.shape
+        if peak is None:
+            peak = self.empty(B)
+        if cell is None:
+            cell = self.empty(B, dtype=torch.int32)
+        self.check(self.L.aefft_map_peak(self.h, _ptr(m), _ptr(ref), Mx, My, B, s, _ptr(peak), _ptr(cell)))
+        return peak, cell
+
     def frames_degrade(self, frames, blur=0, sigma=0.0, impulse=0.0, seed=0, first_frame=0, out=None, dtype=None):
         """The degraded input of target training from the clean frames (aefft_frames_degrade), one launch: `frames` uint8 or float32
         [B][D][Nx][Ny] (float values become pixels first) -> the binomial blur of radius `blur` in 0..4 (2 blur + 1 taps per axis, edges
@@ -1346,6 +1507,17 @@ class Net:
         labels, regions, count = self.ctx.map_regions(map, lo, hi, ref=ref, sense="below" if metric == "ssim" else "above", connectivity=connectivity,
                                                       min_area=min_area, max_regions=max_regions)
         return labels, regions, count, map, out
+
+    def calibrate_tiled(self, image, overlap, rim=0, tile=16, metric="mse", state=None, target=None):
+        """Nominal footage into a calibration state: score_tiled(image, overlap, rim, tile, metric, target) without the score, then
+        Context.map_stats_update of its map into `state` (Context.map_stats of the map's grid when None).  Context.map_stats_finish(state,
+        cells_for_tile(W, H, tile), ...) then gives the `ref` detect_tiled takes.  An FFT net only.  Nothing waits for the device.  Returns
+        (state, map)."""
+        map, _, _ = self.score_tiled(image, overlap, rim, tile=tile, metric=metric, target=target, score=False)
+        if state is None:
+            state = self.ctx.map_stats(map.shape[1], map.shape[2])
+        self.ctx.map_stats_update(state, map)
+        return state, map
 
     def score(self, frames, score=None, recon=None):
         """Per-frame reconstruction error under the current weights (aefft_net_score): score[b] = mean over the frame's D*Nx*Ny pixels of

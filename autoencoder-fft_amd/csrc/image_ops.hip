@@ -364,6 +364,78 @@ extern "C" int aefft_region_to_pixels(const aefft_region* r, int Mx, int My, int
     return AEFFT_OK;
 }
 
+// calibration (include/aefft.h "aefft_map_stats_update") ----------------------------------------
+extern "C" size_t aefft_map_stats_bytes(int Mx, int My) { return map_stats_bytes(Mx, My); }
+
+// the rules the calibration calls share: the grid, the batch and a state of at least the query's bytes (stats_d null: the call has no state)
+static int chk_calib(const Bad& bad, int Mx, int My, int B, const void* stats_d, size_t stats_bytes, const char* stats_names)
+{
+    if (Mx < 1 || My < 1 || Mx > 1024 || My > 1024) return bad("Mx, My must be in 1..1024");
+    if (B < 1) return bad("B must be >= 1");
+    if ((long long)B * Mx * My > (long long)INT_MAX) return bad("B * Mx * My does not fit an int");
+    if (stats_d && stats_bytes < map_stats_bytes(Mx, My)) return bad(std::string(stats_names) + " is below aefft_map_stats_bytes(Mx, My)");
+    return AEFFT_OK;
+}
+static bool sense_ok(int sense) { return sense == AEFFT_REGIONS_ABOVE || sense == AEFFT_REGIONS_BELOW; }
+
+extern "C" int aefft_map_stats_update(aefft_ctx* ctx, const float* map_d, int Mx, int My, int B, void* stats_d, size_t stats_bytes)
+{
+    const Bad bad{ctx, "aefft_map_stats_update"};
+    if (!ctx || !map_d || !stats_d) return bad("null context, map or state");
+    RET_IF(chk_calib(bad, Mx, My, B, stats_d, stats_bytes, "stats_bytes"));
+    if (!aligned16(map_d) || !aligned16(stats_d)) return bad("map_d and stats_d must be 16-byte aligned");
+    const size_t n = (size_t)Mx * My, need = map_stats_bytes(Mx, My);
+    if (ranges_overlap(map_d, (size_t)B * n * 4, stats_d, need)) return bad("the map and state ranges overlap");
+    RET_IF(join_recon(ctx));                          // (the map may come out of a reconstruction that is still on the side stream)
+    return launch_or_fail(ctx, KID_IMAGE, 4.0 * B * n + 104.0 * n, "map_stats_update", [&] { return launch_map_stats_update(map_d, Mx, My, B, stats_d, ctx->cur); });
+}
+
+extern "C" int aefft_map_stats_merge(aefft_ctx* ctx, void* dst_d, const void* src_d, int Mx, int My, size_t stats_bytes)
+{
+    const Bad bad{ctx, "aefft_map_stats_merge"};
+    if (!ctx || !dst_d || !src_d) return bad("null context, dst or src state");
+    RET_IF(chk_calib(bad, Mx, My, 1, dst_d, stats_bytes, "stats_bytes"));
+    if (!aligned16(dst_d) || !aligned16(src_d)) return bad("dst_d and src_d must be 16-byte aligned");
+    const size_t n = (size_t)Mx * My, need = map_stats_bytes(Mx, My);
+    if (ranges_overlap(dst_d, need, src_d, need)) return bad("the dst and src state ranges overlap");
+    RET_IF(join_recon(ctx));
+    return launch_or_fail(ctx, KID_IMAGE, 156.0 * n, "map_stats_merge", [&] { return launch_map_stats_merge(dst_d, src_d, Mx, My, ctx->cur); });
+}
+
+extern "C" int aefft_map_stats_finish(aefft_ctx* ctx, const void* stats_d, size_t stats_bytes, int Mx, int My, int mode, int sense, float k, int rank, float empty,
+                                      float* ref_d)
+{
+    const Bad bad{ctx, "aefft_map_stats_finish"};
+    if (!ctx || !stats_d || !ref_d) return bad("null context, state or ref");
+    RET_IF(chk_calib(bad, Mx, My, 1, stats_d, stats_bytes, "stats_bytes"));
+    if (mode != AEFFT_CALIB_SIGMA && mode != AEFFT_CALIB_RANK) return bad("mode must be AEFFT_CALIB_SIGMA or AEFFT_CALIB_RANK");
+    if (!sense_ok(sense)) return bad("sense must be AEFFT_REGIONS_ABOVE or AEFFT_REGIONS_BELOW");
+    if (rank < 1 || rank > 4) return bad("rank must be in 1..4");
+    if (!std::isfinite(k)) return bad("k must be finite");
+    if (!aligned16(stats_d) || !aligned16(ref_d)) return bad("stats_d and ref_d must be 16-byte aligned");
+    const size_t n = (size_t)Mx * My;
+    if (ranges_overlap(stats_d, map_stats_bytes(Mx, My), ref_d, n * 4)) return bad("the state and ref ranges overlap");
+    RET_IF(join_recon(ctx));
+    return launch_or_fail(ctx, KID_IMAGE, 56.0 * n, "map_stats_finish",
+                          [&] { return launch_map_stats_finish(stats_d, Mx, My, mode, sense, k, rank, empty, ref_d, ctx->cur); });
+}
+
+extern "C" int aefft_map_peak(aefft_ctx* ctx, const float* map_d, const float* ref_d, int Mx, int My, int B, int sense, float* peak_d, int* cell_d)
+{
+    const Bad bad{ctx, "aefft_map_peak"};
+    if (!ctx || !map_d || !peak_d || !cell_d) return bad("null context, map, peak or cell");
+    RET_IF(chk_calib(bad, Mx, My, B, nullptr, 0, ""));
+    if (!sense_ok(sense)) return bad("sense must be AEFFT_REGIONS_ABOVE or AEFFT_REGIONS_BELOW");
+    if (!aligned16(map_d) || !aligned16(ref_d) || !aligned16(peak_d) || !aligned16(cell_d)) return bad("map_d, ref_d, peak_d and cell_d must be 16-byte aligned");
+    const size_t n = (size_t)Mx * My, mb = (size_t)B * n * 4, ob = (size_t)B * 4;
+    if (ranges_overlap(peak_d, ob, cell_d, ob) || ranges_overlap(peak_d, ob, map_d, mb) || ranges_overlap(cell_d, ob, map_d, mb) ||
+        (ref_d && (ranges_overlap(peak_d, ob, ref_d, n * 4) || ranges_overlap(cell_d, ob, ref_d, n * 4))))
+        return bad("the peak and cell ranges overlap an input or each other");
+    RET_IF(join_recon(ctx));
+    return launch_or_fail(ctx, KID_IMAGE, 4.0 * B * n + (ref_d ? 4.0 * n : 0.0) + 8.0 * B, "map_peak",
+                          [&] { return launch_map_peak(map_d, ref_d, Mx, My, B, sense, peak_d, cell_d, ctx->cur); });
+}
+
 // raw sensor data (include/aefft.h "aefft_raw_to_image") ----------------------------------------
 static const RowWords RAW_WORDS = {"pitch too small: U8 pitch >= W, U16 pitch >= 2 W, PACKED pitch >= ceil(W * bits / 8)", "H * pitch does not fit the address space",
                                    "stride must be at least (H - 1) * pitch + the live bytes of a row for B > 1", "B * stride does not fit the address space"};

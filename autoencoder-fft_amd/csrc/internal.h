@@ -147,6 +147,18 @@ hipError_t launch_map_regions(const float* map, const float* ref, int Mx, int My
 // point checks the rest.  One launch.  raw_multiplier: the Q16 multiplier m_c of a gain as the launcher quantises it (an integer in a double).
 double raw_multiplier(float gain, int black, int white);
 hipError_t launch_raw_image(const aefft_raw_desc& d, int order, unsigned char* image, size_t ipitch, size_t istride, int B, hipStream_t st);
+// ---- calib_kernels.hip (aefft_map_stats_update / _merge / _finish, aefft_map_peak) ----
+// The calibration state of Mx x My cells: map_stats_bytes bytes (52 a cell rounded up to 16; 0 for sizes outside 1..1024), planar -- double S1, S2,
+// float hi[4], lo[4], int c --, all-zero bytes when empty (include/aefft.h).  update: the B maps [B][Mx][My] enter the state in ascending b, in place.
+// merge: src (only read) enters dst.  finish: ref [Mx][My] from a state, mode 0 SIGMA (mean + k sd in double) / 1 RANK (hi[rank-1], lo[rank-1] under
+// sense 1), `empty` for a cell that counted nothing.  peak: the maximal (sense 0) or minimal (sense 1) map - ref (ref nullable) of each image over
+// its non-NaN cells and the smallest index that attains it; NaN and -1 for an image of NaN only.  One launch each, no atomics, no workspace.
+// Mx, My in 1..1024, B >= 1, B Mx My < 2^31, rank in 1..4 (hipErrorInvalidValue otherwise); the C entry points check the rest.
+size_t map_stats_bytes(int Mx, int My);
+hipError_t launch_map_stats_update(const float* map, int Mx, int My, int B, void* stats, hipStream_t st);
+hipError_t launch_map_stats_merge(void* dst, const void* src, int Mx, int My, hipStream_t st);
+hipError_t launch_map_stats_finish(const void* stats, int Mx, int My, int mode, int sense, float k, int rank, float empty, float* ref, hipStream_t st);
+hipError_t launch_map_peak(const float* map, const float* ref, int Mx, int My, int B, int sense, float* peak, int* cell, hipStream_t st);
 size_t fft_mid_elems(long planes, int Nx, int Wc);   // complex elements needed in `mid`
 // sizes that are not powers of two (cufftPlanMany takes any size, fft.cu:773-779): even n in 8..1024 through Bluestein's chirp-z form on the
 // power-of-two LDS passes; rows -> transpose -> rows -> transpose.  w1, w2: workspaces of fft_any_ws_elems complex each.

@@ -706,6 +706,65 @@ typedef struct {
 int aefft_raw_to_image(aefft_ctx* ctx, const aefft_raw_desc* src, int order /* AEFFT_YUV_BGR | _RGB; MONO: ignored, D = 1 */,
                        unsigned char* image_d, size_t pitch, size_t image_stride, int B);
 
+/* aefft_map_stats_update, aefft_map_stats_merge, aefft_map_stats_finish, aefft_map_peak: the baseline aefft_map_regions subtracts (its ref_d, "a
+ * calibration map from nominal footage") learned on the device -- streaming per-cell statistics of the maps of nominal footage, the merge of two
+ * such states, the baseline map out of a state, and the per-image peak of map - ref, which is both the image-level anomaly score and the number a
+ * threshold is chosen from.  Without them a caller pulls every nominal map to the host, behind a copy and a synchronisation.
+ * Maps are float [B][Mx][My], My contiguous -- the layout the map calls write; a cell is (I, J) with the linear index I * My + J; n = Mx * My.
+ * Mx, My in 1..1024; B >= 1 and B * Mx * My <= 2^31 - 1; every pointer 16-byte aligned.
+ * The state is caller-owned device memory of aefft_map_stats_bytes(Mx, My) bytes: 52 * Mx * My rounded up to a multiple of 16 (0 from the query
+ * means sizes the calls do not take).  Its layout is planar and part of the interface:
+ *   [0, 8n)     double S1[n]      the sum of the counted values
+ *   [8n, 16n)   double S2[n]      the sum of their squares
+ *   [16n, 32n)  float hi[4][n]    the largest values seen, hi[0] the largest
+ *   [32n, 48n)  float lo[4][n]    the smallest values seen, lo[0] the smallest
+ *   [48n, 52n)  int c[n]          the number of values counted
+ * All-zero bytes are the empty state: there is no reset call, hipMemsetAsync starts a calibration.  Only the first min(c, 4) slots of hi and lo
+ * are live; the others hold +0.0f, so that the hi, lo and c bytes of a state are a function of the multiset of values alone, whatever order the
+ * footage arrived in.  The total number of frames per cell is the caller's bound: c <= 2^31 - 1.
+ *   1. aefft_map_stats_update.  Per cell, for b = 0 .. B-1 in ascending order: x = map[b][I][J].  A non-finite x (NaN, +inf, -inf) is skipped
+ *      and not counted; -0 counts as +0; otherwise S1 = S1 + (double)x, S2 = S2 + (double)x * (double)x, c = c + 1, each sum rounded once, and x
+ *      enters hi if it is among the four largest seen so far and lo if it is among the four smallest.  Multiplicity is kept: equal values occupy
+ *      several slots.  The product of two floats is exact in double, so S2's bits do not depend on whether the product is fused into the addition.
+ *      The state is updated in place.
+ *   2. aefft_map_stats_merge.  Per cell: S1 = S1_dst + S1_src and S2 alike, one addition each; c = c_dst + c_src; hi is the four largest of the
+ *      up to eight live values, lo the four smallest; dead slots end up +0.0f.  src is only read; dst and src must not overlap.  hi, lo and c of
+ *      a merged state equal those of one run over all the footage; S1 and S2 are the sums in the order the merge defines.
+ *   3. aefft_map_stats_finish writes ref_d, float [Mx][My], exactly what aefft_map_regions takes.  In both modes a cell with c == 0 gets `empty`,
+ *      which is any float: +inf under ABOVE switches the cell off, as map - inf is never foreground.
+ *      AEFFT_CALIB_RANK: rank in 1..4, r = min(rank, c); ref = hi[r-1] under AEFFT_REGIONS_ABOVE, lo[r-1] under AEFFT_REGIONS_BELOW -- the
+ *      per-cell maximum (minimum) of the nominal footage with rank - 1 outliers tolerated.  No arithmetic: exact, and independent of the order
+ *      the footage arrived in.  k is ignored but must be finite.
+ *      AEFFT_CALIB_SIGMA: k is a finite float, negative for BELOW; sense and rank are ignored but must be valid values.  In double, each
+ *      operation rounded once, in this order: mean = S1 / (double)c.  If c == 1, sd = 0; otherwise p = S1 * mean, d = S2 - p, d = d < 0 ? 0 : d,
+ *      var = d / (double)(c - 1), sd = sqrt(var), correctly rounded.  t = (double)k * sd.  ref = (float)(mean + t).  p and t are rounded products:
+ *      neither is fused into the subtraction or addition it feeds.
+ *      The accepted limit of the S2 - S1^2 / c form: the variance loses about log2(mean^2 / var) of double's 53 bits to cancellation.  That is
+ *      fine for error and SSIM maps (values up to 65025 that vary by more than a millionth of their mean keep a dozen bits or more); it is not a
+ *      general-purpose variance.
+ *   4. aefft_map_peak.  v is exactly aefft_map_regions' step 1: map[b][I][J] when ref_d is NULL, otherwise map[b][I][J] - ref[I][J], rounded once
+ *      to float32; a -0 result counts as +0.  peak[b] is the maximal v under AEFFT_REGIONS_ABOVE and the minimal v under AEFFT_REGIONS_BELOW over
+ *      the cells whose v is not NaN (+inf and -inf are ordinary values); cell[b] is the smallest linear index I * My + J that attains it.  An
+ *      image of NaN only gives peak = NaN (the quiet NaN 0x7FC00000) and cell = -1.  peak_d: float [B]; cell_d: int [B].
+ * One launch each on the context's stream: a lane owns a cell and walks b (update: the order of the sums is the definition, nothing reduces over
+ * b in parallel), or a workgroup owns an image and reduces an order-preserving 64-bit key by integer max (peak).  No atomics, no float
+ * reduction, no workspace, no host synchronisation, no allocation; safe under stream capture; the result is a function of the inputs alone, on
+ * every run.  The peak is sized for the common maps, up to 240 x 135 cells an image; larger maps are served, one workgroup an image.  Accounted
+ * under the profile id `image` with 4 B n + 104 n bytes (update), 156 n (merge), 56 n (finish) and 4 B n (+ 4 n with ref_d) + 8 B (peak).
+ * AEFFT_EINVAL, with aefft_last_error starting with the call's name ("aefft_map_stats_update: ", "aefft_map_stats_merge: ",
+ * "aefft_map_stats_finish: ", "aefft_map_peak: ") and naming the rule, nothing enqueued and every output and the state untouched: a null context
+ * or pointer (ref_d of aefft_map_peak may be NULL); Mx, My outside 1..1024; B < 1 or B * Mx * My beyond an int; a pointer that is not 16-byte
+ * aligned; stats_bytes below the query; an unknown mode or sense; rank outside 1..4; a non-finite k; outputs that overlap inputs or each other
+ * (the state and the map, dst and src, the state and ref_d, peak_d and cell_d and the peak's inputs). */
+enum { AEFFT_CALIB_SIGMA = 0, AEFFT_CALIB_RANK = 1 };   /* mode of aefft_map_stats_finish */
+size_t aefft_map_stats_bytes(int Mx, int My);           /* 52 * Mx * My rounded up to 16; 0 on invalid sizes */
+int aefft_map_stats_update(aefft_ctx* ctx, const float* map_d, int Mx, int My, int B, void* stats_d, size_t stats_bytes);
+int aefft_map_stats_merge(aefft_ctx* ctx, void* dst_d, const void* src_d, int Mx, int My, size_t stats_bytes);
+int aefft_map_stats_finish(aefft_ctx* ctx, const void* stats_d, size_t stats_bytes, int Mx, int My, int mode, int sense /* AEFFT_REGIONS_* */,
+                           float k, int rank, float empty, float* ref_d /* [Mx][My] */);
+int aefft_map_peak(aefft_ctx* ctx, const float* map_d, const float* ref_d /* nullable, [Mx][My] */, int Mx, int My, int B, int sense,
+                   float* peak_d /* [B] */, int* cell_d /* [B] */);
+
 /* ---- network level: the resident, batched form of autoenc_fft / backprop_fft ------------------ */
 typedef struct {
     int D, Nx, Ny;        /* input frames [B][D][Nx][Ny] */
