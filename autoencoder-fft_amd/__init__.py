@@ -78,6 +78,11 @@ class Region(C.Structure):
                 ("peak", C.c_float)]
 
 
+class Affine(C.Structure):
+    """include/aefft.h aefft_affine: six Q24 coefficients of the row-major 2 x 3 matrix (48 bytes)"""
+    _fields_ = [("a", C.c_longlong * 6)]
+
+
 _lib = None
 _vp, _fp, _i, _l, _f = C.c_void_p, C.c_void_p, C.c_int, C.c_long, C.c_float   # device float* passed as void*
 
@@ -131,6 +136,9 @@ SIGNATURES = {
     "aefft_map_stats_merge": (_i, [_vp, _vp, _vp, _i, _i, C.c_size_t]),
     "aefft_map_stats_finish": (_i, [_vp, _vp, C.c_size_t, _i, _i, _i, _i, _f, _i, _f, _fp]),
     "aefft_map_peak": (_i, [_vp, _fp, _fp, _i, _i, _i, _i, _fp, _vp]),
+    "aefft_affine_make": (_i, [C.POINTER(C.c_double), C.POINTER(Affine)]),
+    "aefft_image_warp_affine": (_i, [_vp, _vp, C.c_size_t, C.c_size_t, _i, _i, _vp, _i, _i, _i, C.c_uint, _vp, C.c_size_t, C.c_size_t, _i, _i, _i, _i]),
+    "aefft_image_remap": (_i, [_vp, _vp, C.c_size_t, C.c_size_t, _i, _i, _vp, _i, _i, C.c_uint, _vp, C.c_size_t, C.c_size_t, _i, _i, _i, _i]),
     "aefft_net_create": (_i, [_vp, C.POINTER(NetDesc), C.POINTER(_vp)]),
     "aefft_net_create_ex": (_i, [_vp, C.POINTER(NetDesc), C.c_uint, C.POINTER(_vp)]),
     "aefft_net_destroy": (None, [_vp]),
@@ -809,6 +817,165 @@ def _map_peak_args(map, ref, sense, peak, cell):
     return m, REGIONS_SENSE[sense]
 
 
+WARP_INTERP = {"nearest": 0, "linear": 1}                    # AEFFT_WARP_NEAREST, AEFFT_WARP_LINEAR
+WARP_BORDER = {"constant": 0, "replicate": 1, "reflect": 2}  # AEFFT_BORDER_CONSTANT, AEFFT_BORDER_REPLICATE, AEFFT_BORDER_REFLECT
+_I32_MIN, _I32_MAX = -2 ** 31, 2 ** 31 - 1
+
+
+def affine_q(m):
+    """The Q24 coefficients aefft_image_warp_affine takes (aefft_affine_make; host arithmetic, no device): `m` is a 2 x 3 matrix or B of them
+    (B x 2 x 3), destination pixel -> source position, u = m00 x + m01 y + m02, v = m10 x + m11 y + m12.  Returns the int64 array (B, 6),
+    a[k] = m[k] * 2^24 rounded to nearest, ties to even; ValueError for what the library refuses (a non-finite entry, a scale above 32, an
+    offset above 32768 pixels)."""
+    what = "affine_q"
+    try:
+        a = np.ascontiguousarray(np.asarray(m, dtype=np.float64))
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: the matrix must be numbers, 2 x 3 or B x 2 x 3") from None
+    if a.shape == (2, 3):
+        a = a[None]
+    if a.ndim != 3 or a.shape[1:] != (2, 3) or a.shape[0] < 1:
+        raise ValueError(f"{what}: the matrix must be 2 x 3 or B x 2 x 3; got shape {np.shape(m)}")
+    rows = a.reshape(-1, 6)
+    out = np.empty(rows.shape, np.int64)
+    for k, row in enumerate(rows):
+        q = Affine()
+        if lib().aefft_affine_make(row.ctypes.data_as(C.POINTER(C.c_double)), C.byref(q)) != OK:
+            raise ValueError(f"{what}: every entry must be finite, the four linear entries at most 32 and the two offsets at most 32768 pixels in "
+                             f"magnitude; got {row.tolist()}")
+        out[k] = list(q.a)
+    return out
+
+
+def _table_size(size, what):
+    Wd, Hd = _two_ints(size, what, "size must be (Wd, Hd)")
+    if not (1 <= Wd <= 8192 and 1 <= Hd <= 8192):
+        raise ValueError(f"{what}: size must be in 1..8192 per axis")
+    return Wd, Hd
+
+
+def _table_q11(u, v, dead=None):
+    """t = rint(2048 * u) clipped to int32, as the int32 table [Hd][Wd][2], x first; `dead` entries get INT32_MIN, which is outside any image"""
+    t = np.stack([np.clip(np.rint(2048.0 * u), _I32_MIN, _I32_MAX), np.clip(np.rint(2048.0 * v), _I32_MIN, _I32_MAX)], axis=-1)
+    t[~np.isfinite(t)] = _I32_MIN
+    if dead is not None:
+        t[dead] = _I32_MIN
+    return np.ascontiguousarray(t.astype(np.int32))
+
+
+def affine_table(m, size):
+    """The table Context.image_remap takes for ONE affine (host numpy): exactly the (tx, ty) aefft_image_warp_affine forms from affine_q(m), in
+    integer arithmetic -- the two calls then give the same bytes.  size = (Wd, Hd).  Returns np.int32 [Hd][Wd][2], x first."""
+    what = "affine_table"
+    Wd, Hd = _table_size(size, what)
+    q = affine_q(m)
+    if q.shape[0] != 1:
+        raise ValueError(f"{what}: one 2 x 3 matrix")
+    a = q[0]
+    y, x = np.meshgrid(np.arange(Hd, dtype=np.int64), np.arange(Wd, dtype=np.int64), indexing="ij")
+    # (within affine_q's ranges |U| < 2^43: neither the wrap nor the clamp of the definition is active)
+    t = np.stack([(a[0] * x + a[1] * y + a[2] + 4096) >> 13, (a[3] * x + a[4] * y + a[5] + 4096) >> 13], axis=-1)
+    return np.ascontiguousarray(np.clip(t, _I32_MIN, _I32_MAX).astype(np.int32))
+
+
+def homography_table(Hm, size):
+    """The table of a plane-to-plane homography (host numpy, float64): `Hm` is 3 x 3, destination pixel -> source position,
+    u = (h00 x + h01 y + h02) / (h20 x + h21 y + h22) and v alike.  A non-positive denominator gives INT32_MIN for both entries, which is outside
+    any image.  size = (Wd, Hd).  Returns np.int32 [Hd][Wd][2], t = rint(2048 u) clipped to int32."""
+    what = "homography_table"
+    Wd, Hd = _table_size(size, what)
+    h = np.asarray(Hm, dtype=np.float64)
+    if h.shape != (3, 3) or not np.isfinite(h).all():
+        raise ValueError(f"{what}: Hm must be a finite 3 x 3 matrix")
+    y, x = np.meshgrid(np.arange(Hd, dtype=np.float64), np.arange(Wd, dtype=np.float64), indexing="ij")
+    den = h[2, 0] * x + h[2, 1] * y + h[2, 2]
+    dead = ~(den > 0.0)
+    den = np.where(dead, 1.0, den)
+    return _table_q11((h[0, 0] * x + h[0, 1] * y + h[0, 2]) / den, (h[1, 0] * x + h[1, 1] * y + h[1, 2]) / den, dead)
+
+
+def undistort_table(K, dist, size, new_K=None):
+    """The table that undoes a lens (host numpy, float64): the Brown-Conrady forward model evaluated at each ideal destination pixel --
+    cv::initUndistortRectifyMap without the rotation; there is no inversion, the undistort map IS the forward model.  `K` is the 3 x 3 camera
+    matrix (fx, fy, cx, cy are read from it), dist = (k1, k2, p1, p2[, k3]), new_K the camera matrix of the ideal image (default K),
+    size = (Wd, Hd).  With xn = (x - cx') / fx', yn = (y - cy') / fy', r2 = xn^2 + yn^2 and c = 1 + k1 r2 + k2 r2^2 + k3 r2^3:
+    xd = xn c + 2 p1 xn yn + p2 (r2 + 2 xn^2), yd = yn c + p1 (r2 + 2 yn^2) + 2 p2 xn yn, u = fx xd + cx, v = fy yd + cy.
+    Returns np.int32 [Hd][Wd][2]."""
+    what = "undistort_table"
+    Wd, Hd = _table_size(size, what)
+    k = np.asarray(K, dtype=np.float64)
+    n = k if new_K is None else np.asarray(new_K, dtype=np.float64)
+    d = np.asarray(dist, dtype=np.float64).reshape(-1)
+    if k.shape != (3, 3) or n.shape != (3, 3) or d.size not in (4, 5) or not (np.isfinite(k).all() and np.isfinite(n).all() and np.isfinite(d).all()):
+        raise ValueError(f"{what}: K and new_K must be finite 3 x 3 matrices and dist (k1, k2, p1, p2[, k3])")
+    if k[0, 0] == 0 or k[1, 1] == 0 or n[0, 0] == 0 or n[1, 1] == 0:
+        raise ValueError(f"{what}: the focal lengths must not be zero")
+    k1, k2, p1, p2 = d[:4]
+    k3 = d[4] if d.size == 5 else 0.0
+    y, x = np.meshgrid(np.arange(Hd, dtype=np.float64), np.arange(Wd, dtype=np.float64), indexing="ij")
+    xn, yn = (x - n[0, 2]) / n[0, 0], (y - n[1, 2]) / n[1, 1]
+    r2 = xn * xn + yn * yn
+    c = 1.0 + k1 * r2 + k2 * r2 * r2 + k3 * r2 * r2 * r2
+    xd = xn * c + 2.0 * p1 * xn * yn + p2 * (r2 + 2.0 * xn * xn)
+    yd = yn * c + p1 * (r2 + 2.0 * yn * yn) + 2.0 * p2 * xn * yn
+    return _table_q11(k[0, 0] * xd + k[0, 2], k[1, 1] * yd + k[1, 2])
+
+
+def _warp_common(what, image, interp, border, value, out, Wd, Hd):
+    """what image_warp and image_remap share: (the image as [B][H][W][D], pitch, stride, interp value, border value, border_value)"""
+    img, pitch, stride = _resize_layout(image, what)
+    B, H, W, D = img.shape
+    if not 1 <= D <= 4 or W > 8192 or H > 8192:
+        raise ValueError(f"{what}: D must be 1..4 and W, H in 1..8192")
+    if interp not in WARP_INTERP:
+        raise ValueError(f"{what}: interp must be one of {sorted(WARP_INTERP)}")
+    if border not in WARP_BORDER:
+        raise ValueError(f"{what}: border must be one of {sorted(WARP_BORDER)}")
+    try:
+        vals = [value] * D if isinstance(value, (int, np.integer)) and not isinstance(value, bool) else list(value)
+        if len(vals) != D or any(isinstance(v, bool) or int(v) != v or not 0 <= int(v) <= 255 for v in vals):
+            raise TypeError
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: value must be an int in 0..255 or one per channel ({D})") from None
+    if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.dim() != 4 or tuple(out.shape) != (B, Hd, Wd, D)):
+        raise ValueError(f"{what}: out must be a uint8 tensor of shape {(B, Hd, Wd, D)}")
+    return img, pitch, stride, WARP_INTERP[interp], WARP_BORDER[border], sum(int(v) << (8 * d) for d, v in enumerate(vals))
+
+
+def _image_warp_args(image, matrix, size, interp, border, value, out):
+    """the checks of Context.image_warp that need no device: (the image as [B][H][W][D], pitch, stride, the affines -- an int64 numpy array
+    (nm, 6) to upload, or the caller's int64 tensor as it is --, (Wd, Hd), interp value, border value, border_value)"""
+    what = "Context.image_warp"
+    if image.dtype != torch.uint8 or image.dim() not in (3, 4):
+        raise ValueError(f"{what}: the image must be a uint8 tensor [B][H][W][D] or [H][W][D]")
+    B = image.shape[0] if image.dim() == 4 else 1
+    H, W = image.shape[-3], image.shape[-2]
+    Wd, Hd = (W, H) if size is None else _table_size(size, what)
+    if isinstance(matrix, torch.Tensor) and matrix.dtype == torch.int64:
+        q = matrix
+        if q.dim() != 2 or q.shape[1] != 6 or not q.is_contiguous():
+            raise ValueError(f"{what}: an int64 matrix tensor must be contiguous, (nm, 6)")
+    else:
+        q = affine_q(matrix.detach().cpu().numpy() if isinstance(matrix, torch.Tensor) else matrix)
+    if q.shape[0] not in (1, B):
+        raise ValueError(f"{what}: {q.shape[0]} matrices for {B} images (one for the batch, or one per image)")
+    img, pitch, stride, i, b, v = _warp_common(what, image, interp, border, value, out, Wd, Hd)
+    return img, pitch, stride, q, (Wd, Hd), i, b, v
+
+
+def _image_remap_args(image, table, interp, border, value, out):
+    """the checks of Context.image_remap that need no device: (the image as [B][H][W][D], pitch, stride, (Wd, Hd), interp value, border value,
+    border_value)"""
+    what = "Context.image_remap"
+    if not isinstance(table, torch.Tensor) or table.dtype != torch.int32 or table.dim() != 3 or table.shape[2] != 2 or not table.is_contiguous() or min(table.shape) < 1:
+        raise ValueError(f"{what}: table must be a contiguous int32 tensor [Hd][Wd][2]")
+    Hd, Wd = int(table.shape[0]), int(table.shape[1])
+    if Wd > 8192 or Hd > 8192:
+        raise ValueError(f"{what}: the table's size must be in 1..8192 per axis")
+    img, pitch, stride, i, b, v = _warp_common(what, image, interp, border, value, out, Wd, Hd)
+    return img, pitch, stride, (Wd, Hd), i, b, v
+
+
 class Context:
     """aefft_ctx on torch's current device, enqueuing on torch's current stream by default."""
 
@@ -1192,6 +1359,36 @@ class Context:
             cell = self.empty(B, dtype=torch.int32)
         self.check(self.L.aefft_map_peak(self.h, _ptr(m), _ptr(ref), Mx, My, B, s, _ptr(peak), _ptr(cell)))
         return peak, cell
+
+    def image_warp(self, image, matrix, size=None, interp="linear", border="constant", value=0, out=None):
+        """Images through an affine transform (aefft_image_warp_affine), one launch: `image` is a uint8 device tensor [B][H][W][D] or [H][W][D],
+        contiguous, row-padded or a region of interest; `matrix` maps a DESTINATION pixel to the source position it samples (cv::warpAffine
+        with WARP_INVERSE_MAP) -- a 2 x 3 matrix for the batch or B x 2 x 3, one per image, as floats (quantised by affine_q and uploaded), or
+        an int64 device tensor (nm, 6) of Q24 coefficients used as it is (nothing is copied: the pose stays on the device).  size = (Wd, Hd)
+        defaults to the source's size; interp "nearest" or "linear"; border "constant" (`value`: an int for all channels or one per
+        channel), "replicate" or "reflect".  Defined bit for bit in integer arithmetic (include/aefft.h).  `out` (uint8 [B][Hd][Wd][D], any
+        pitch) is allocated when None.  Returns out."""
+        img, pitch, stride, q, (Wd, Hd), i, b, v = _image_warp_args(image, matrix, size, interp, border, value, out)
+        B, H, W, D = img.shape
+        if not isinstance(q, torch.Tensor):
+            q = torch.from_numpy(q).to(img.device)
+        if out is None:
+            out = self.empty(B, Hd, Wd, D, dtype=torch.uint8)
+        o, opitch, ostride = _resize_layout(out, "Context.image_warp: out")
+        self.check(self.L.aefft_image_warp_affine(self.h, _ptr(img), pitch, stride, W, H, _ptr(q), q.shape[0], i, b, v, _ptr(o), opitch, ostride, Wd, Hd, B, D))
+        return out
+
+    def image_remap(self, image, table, interp="linear", border="constant", value=0, out=None):
+        """Images through a per-pixel table (aefft_image_remap: a lens, a homography), one launch: `table` is an int32 device tensor
+        [Hd][Wd][2] of source positions times 2048, x first, shared by the batch (undistort_table, homography_table and affine_table make
+        it on the host; any int32 value is legal).  `image`, interp, border, value and out as in image_warp.  Returns out."""
+        img, pitch, stride, (Wd, Hd), i, b, v = _image_remap_args(image, table, interp, border, value, out)
+        B, H, W, D = img.shape
+        if out is None:
+            out = self.empty(B, Hd, Wd, D, dtype=torch.uint8)
+        o, opitch, ostride = _resize_layout(out, "Context.image_remap: out")
+        self.check(self.L.aefft_image_remap(self.h, _ptr(img), pitch, stride, W, H, _ptr(table), i, b, v, _ptr(o), opitch, ostride, Wd, Hd, B, D))
+        return out
 
     def frames_degrade(self, frames, blur=0, sigma=0.0, impulse=0.0, seed=0, first_frame=0, out=None, dtype=None):
         """The degraded input of target training from the clean frames (aefft_frames_degrade), one launch: `frames` uint8 or float32

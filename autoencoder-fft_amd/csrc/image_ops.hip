@@ -364,6 +364,71 @@ extern "C" int aefft_region_to_pixels(const aefft_region* r, int Mx, int My, int
     return AEFFT_OK;
 }
 
+// align and rectify (include/aefft.h "aefft_image_warp_affine, aefft_image_remap") ---------------
+extern "C" int aefft_affine_make(const double m[6], aefft_affine* out)
+{
+    if (!m || !out) return AEFFT_EINVAL;
+    aefft_affine q;
+    for (int k = 0; k < 6; ++k) {
+        const double limit = k % 3 == 2 ? 549755813888.0 : 536870912.0;           // 2^39 for the offsets, 2^29 for the others
+        if (!std::isfinite(m[k])) return AEFFT_EINVAL;
+        const double a = std::nearbyint(m[k] * 16777216.0);                        // (the product is exact; to nearest, ties to even)
+        if (std::fabs(a) > limit) return AEFFT_EINVAL;
+        q.a[k] = (long long)a;
+    }
+    *out = q;
+    return AEFFT_OK;
+}
+
+// the rules the two calls share: both images by the image buffer rule, each sentence led by the image's name, and the destination clear of the
+// source; `de` receives the destination's extent
+static int chk_warp(const Bad& bad, const void* src_d, size_t src_pitch, size_t src_stride, int Ws, int Hs, int interp, int border, const void* dst_d,
+                    size_t dst_pitch, size_t dst_stride, int Wd, int Hd, int B, int D, size_t* de)
+{
+    RET_IF(chk_dims(bad, B, D, Ws, Hs, "Ws, Hs, Wd, Hd", dim_ok(Wd) && dim_ok(Hd)));
+    if (interp != AEFFT_WARP_NEAREST && interp != AEFFT_WARP_LINEAR) return bad("interp must be AEFFT_WARP_NEAREST or AEFFT_WARP_LINEAR");
+    if (border != AEFFT_BORDER_CONSTANT && border != AEFFT_BORDER_REPLICATE && border != AEFFT_BORDER_REFLECT)
+        return bad("border must be AEFFT_BORDER_CONSTANT, AEFFT_BORDER_REPLICATE or AEFFT_BORDER_REFLECT");
+    size_t se = 0;
+    const std::string src_name = std::string(bad.fn) + ": src_d", dst_name = std::string(bad.fn) + ": dst_d";
+    RET_IF(chk_rows(Bad{bad.ctx, src_name.c_str()}, IMAGE_WORDS, src_pitch, src_stride, (size_t)Ws * D, (size_t)Hs, B, &se));
+    RET_IF(chk_rows(Bad{bad.ctx, dst_name.c_str()}, IMAGE_WORDS, dst_pitch, dst_stride, (size_t)Wd * D, (size_t)Hd, B, de));
+    if (ranges_overlap(src_d, se, dst_d, *de)) return bad("the source and destination ranges overlap (the op is out-of-place)");
+    return AEFFT_OK;
+}
+
+extern "C" int aefft_image_warp_affine(aefft_ctx* ctx, const unsigned char* src_d, size_t src_pitch, size_t src_stride, int Ws, int Hs, const aefft_affine* m_d, int nm,
+                                       int interp, int border, unsigned border_value, unsigned char* dst_d, size_t dst_pitch, size_t dst_stride, int Wd, int Hd,
+                                       int B, int D)
+{
+    const Bad bad{ctx, "aefft_image_warp_affine"};
+    if (!ctx || !src_d || !m_d || !dst_d) return bad("null context, source, affines or destination");
+    size_t de = 0;
+    RET_IF(chk_warp(bad, src_d, src_pitch, src_stride, Ws, Hs, interp, border, dst_d, dst_pitch, dst_stride, Wd, Hd, B, D, &de));
+    if (nm != 1 && nm != B) return bad("nm must be 1 (one affine for the batch) or B (one per image)");
+    if (!aligned16(m_d)) return bad("m_d must be 16-byte aligned");
+    if (ranges_overlap(m_d, (size_t)nm * sizeof(aefft_affine), dst_d, de)) return bad("the affines and the destination range overlap");
+    RET_IF(join_recon(ctx));                          // (the source may hold a reconstruction that is still on the side stream)
+    return launch_or_fail(ctx, KID_IMAGE, (double)B * D * ((double)Ws * Hs + (double)Wd * Hd) + 48.0 * nm, "image_warp_affine", [&] {
+        return launch_image_warp_affine(src_d, src_pitch, src_stride, Ws, Hs, m_d, nm, interp, border, border_value, dst_d, dst_pitch, dst_stride, Wd, Hd, B, D, ctx->cur);
+    });
+}
+
+extern "C" int aefft_image_remap(aefft_ctx* ctx, const unsigned char* src_d, size_t src_pitch, size_t src_stride, int Ws, int Hs, const int* map_d, int interp,
+                                 int border, unsigned border_value, unsigned char* dst_d, size_t dst_pitch, size_t dst_stride, int Wd, int Hd, int B, int D)
+{
+    const Bad bad{ctx, "aefft_image_remap"};
+    if (!ctx || !src_d || !map_d || !dst_d) return bad("null context, source, table or destination");
+    size_t de = 0;
+    RET_IF(chk_warp(bad, src_d, src_pitch, src_stride, Ws, Hs, interp, border, dst_d, dst_pitch, dst_stride, Wd, Hd, B, D, &de));
+    if (!aligned16(map_d)) return bad("map_d must be 16-byte aligned");
+    if (ranges_overlap(map_d, (size_t)8 * Wd * Hd, dst_d, de)) return bad("the table and the destination range overlap");
+    RET_IF(join_recon(ctx));                          // (the source may hold a reconstruction that is still on the side stream)
+    return launch_or_fail(ctx, KID_IMAGE, (double)B * D * ((double)Ws * Hs + (double)Wd * Hd) + 8.0 * Wd * Hd, "image_remap", [&] {
+        return launch_image_remap(src_d, src_pitch, src_stride, Ws, Hs, map_d, interp, border, border_value, dst_d, dst_pitch, dst_stride, Wd, Hd, B, D, ctx->cur);
+    });
+}
+
 // calibration (include/aefft.h "aefft_map_stats_update") ----------------------------------------
 extern "C" size_t aefft_map_stats_bytes(int Mx, int My) { return map_stats_bytes(Mx, My); }
 

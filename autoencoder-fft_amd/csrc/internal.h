@@ -159,6 +159,16 @@ hipError_t launch_map_stats_update(const float* map, int Mx, int My, int B, void
 hipError_t launch_map_stats_merge(void* dst, const void* src, int Mx, int My, hipStream_t st);
 hipError_t launch_map_stats_finish(const void* stats, int Mx, int My, int mode, int sense, float k, int rank, float empty, float* ref, hipStream_t st);
 hipError_t launch_map_peak(const float* map, const float* ref, int Mx, int My, int B, int sense, float* peak, int* cell, hipStream_t st);
+// ---- warp_kernels.hip (aefft_image_warp_affine, aefft_image_remap) ----
+// B interleaved 8-bit source images (pitch, stride, Ws x Hs) sampled into B destination images (their own pitch, stride, Wd x Hd) at the source
+// position (tx, ty) / 2048 of every destination pixel (include/aefft.h): from nm (1 or B) Q24 affines on the device, or from the table
+// int [Hd][Wd][2] the batch shares.  interp 0 NEAREST / 1 LINEAR, border 0 CONSTANT (bval: channel d's byte at bits 8 d) / 1 REPLICATE / 2 REFLECT.
+// One launch each, no atomics, no workspace.  D in 1..4, sizes in 1..8192, B >= 1, the pitches at least a row (hipErrorInvalidValue otherwise);
+// the C entry points check the rest.
+hipError_t launch_image_warp_affine(const unsigned char* src, size_t spitch, size_t sstride, int Ws, int Hs, const aefft_affine* m, int nm, int interp, int border,
+                                    unsigned bval, unsigned char* dst, size_t dpitch, size_t dstride, int Wd, int Hd, int B, int D, hipStream_t st);
+hipError_t launch_image_remap(const unsigned char* src, size_t spitch, size_t sstride, int Ws, int Hs, const int* map, int interp, int border, unsigned bval,
+                              unsigned char* dst, size_t dpitch, size_t dstride, int Wd, int Hd, int B, int D, hipStream_t st);
 size_t fft_mid_elems(long planes, int Nx, int Wc);   // complex elements needed in `mid`
 // sizes that are not powers of two (cufftPlanMany takes any size, fft.cu:773-779): even n in 8..1024 through Bluestein's chirp-z form on the
 // power-of-two LDS passes; rows -> transpose -> rows -> transpose.  w1, w2: workspaces of fft_any_ws_elems complex each.

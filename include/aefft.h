@@ -765,6 +765,65 @@ int aefft_map_stats_finish(aefft_ctx* ctx, const void* stats_d, size_t stats_byt
 int aefft_map_peak(aefft_ctx* ctx, const float* map_d, const float* ref_d /* nullable, [Mx][My] */, int Mx, int My, int B, int sense,
                    float* peak_d /* [B] */, int* cell_d /* [B] */);
 
+/* aefft_image_warp_affine, aefft_image_remap: align and rectify -- the geometric stage in front of the per-cell chain (aefft_image_compare_map,
+ * the calibrated baseline, aefft_map_peak, aefft_map_regions), which assumes that the scene sits on the same pixels in every image.  The lens and
+ * the camera's view of the plane are fixed calibrations, one per-pixel table for every frame (aefft_image_remap); the part arrives shifted and
+ * rotated, one affine per image from a fiducial, an encoder or a matcher (aefft_image_warp_affine).
+ * Images: source and destination are interleaved 8-bit images with the layout and rules of aefft_image_resize_to_frames -- pixel (row y, column
+ * x), channel d, is the byte at  y * pitch + x * D + d; pointer, pitch and stride may have ANY alignment; pitch >= W * D; for B > 1,
+ * stride >= (H - 1) * pitch + W * D (ignored when B == 1); bytes of a row beyond W * D are never read or written.  Source and destination each
+ * have their own size (Ws, Hs / Wd, Hd), pitch and stride.  D in 1..4; Ws, Hs, Wd, Hd in 1..8192; B >= 1.  Out of place: source and destination
+ * byte ranges must not overlap.
+ * Direction: the transform maps a DESTINATION pixel to the source position it samples -- cv::warpAffine with WARP_INVERSE_MAP, and cv::remap.
+ * Integer coordinates are pixel centres.  NOT byte-identical to OpenCV, which keeps 5 fraction bits of the position where this keeps 11; the
+ * difference is unmeasured (OpenCV was not available to the build).
+ * Source position in Q11: both calls reduce to a pair (tx, ty) of signed 32-bit integers per destination pixel, the source position times 2048.
+ *   aefft_image_remap reads the pair from the table  int map[Hd][Wd][2], x first, 16-byte aligned, shared by all B images.  Any int32 value is
+ *     legal.
+ *   aefft_image_warp_affine computes it from aefft_affine: six coefficients in Q24 (48 bytes), on the device, 16-byte aligned; nm of them, nm == 1
+ *     (shared by the batch) or nm == B (one per image).  For destination column x and row y:  U = a[0] x + a[1] y + a[2]  and
+ *     V = a[3] x + a[4] y + a[5]  in wrapping 64-bit arithmetic;  tx = clamp((U + 2^12) >> 13, -2^31, 2^31 - 1)  with an arithmetic shift, ty the
+ *     same from V.  The host cannot see the coefficients: the wrap and the clamp make the call defined for every bit pattern, and whatever the
+ *     coefficients are, no byte outside the source images is read, because every index passes the border rule.  Within the ranges that
+ *     aefft_affine_make accepts neither the wrap nor the clamp is ever active (|tx| stays below 2^30 + 2^27 at x, y = 8191).
+ *   aefft_affine_make (host arithmetic only, like aefft_tile_plan_make): a[k] = m[k] * 2^24 rounded to nearest, ties to even, for the row-major
+ *     2 x 3 matrix m.  AEFFT_EINVAL, with nothing written, for a null pointer, a non-finite entry, |a[0]|, |a[1]|, |a[3]|, |a[4]| > 2^29 (a scale
+ *     of 32) or |a[2]|, |a[5]| > 2^39 (an offset of 32768 pixels).  Q24 keeps a rotation's error over 8192 pixels below 2^-11 pixel; Q16 would not.
+ * Sampling, per axis with S = Ws or Hs:
+ *   AEFFT_WARP_NEAREST  sx = (tx + 1024) >> 11 (halves up), rows alike.  One tap.
+ *   AEFFT_WARP_LINEAR   sx = tx >> 11 and wx = tx & 2047, rows alike.  The taps are (sy, sx), (sy, sx+1), (sy+1, sx), (sy+1, sx+1):
+ *     v = (2048-wy) ((2048-wx) p00 + wx p01) + wy ((2048-wx) p10 + wx p11)  < 2^30;  the byte is (v + 2^21) >> 22 -- the resize's weights and
+ *     rounding.
+ * Border: the rule is applied to each tap on its own, per axis.
+ *   AEFFT_BORDER_CONSTANT   a tap with sx outside 0..Ws-1 or sy outside 0..Hs-1 has the value (border_value >> 8 d) & 255 for channel d.
+ *   AEFFT_BORDER_REPLICATE  clamp(s, 0, S-1).
+ *   AEFFT_BORDER_REFLECT    reflection without repeating the edge pixel (OpenCV's BORDER_REFLECT_101), iterated so that it is defined for any
+ *     reach: for S = 1 the result is 0; otherwise P = 2(S-1), m = s mod P taken non-negative, r = m when m < S, else P - m.
+ *   border_value is ignored under the other two rules.
+ * Consequences, for both interpolations and all three borders: the identity gives the source's bytes; an integer translation gives the shifted
+ * bytes, with the border rule in the uncovered strip; the quarter turns are exact -- {0, 1, 0, -1, 0, Hs-1} gives the source turned clockwise
+ * (numpy's rot90(src, -1): dst[y][x] = src[Hs-1-x][y]) and {0, -1, Ws-1, 1, 0, 0} the source turned counter-clockwise (rot90(src, 1)), both
+ * into a destination of Hs x Ws --; a half-pixel offset between bytes 10 and 20 gives 15; a transform that lands entirely outside the
+ * source gives the constant everywhere; aefft_image_remap with the table (tx, ty) of an affine equals aefft_image_warp_affine with that affine,
+ * byte for byte.
+ * Both device calls: one launch each on the context's stream; no host synchronisation, no allocation, no workspace, no atomics; safe under
+ * stream capture.  Every accepted alignment gives the same bytes (destination pointer, pitch and stride multiples of 4: dword stores; bytes
+ * otherwise).  Accounted under the profile id `image` with B D (Ws Hs + Wd Hd) bytes plus 48 nm for the affines or 8 Wd Hd for the table.
+ * AEFFT_EINVAL, with aefft_last_error starting with the call's name ("aefft_image_warp_affine: ", "aefft_image_remap: ") and naming the rule,
+ * nothing enqueued and the destination untouched: a null context or pointer; D, B or a size out of range; nm not 1 or B; an unknown interp or
+ * border; a pitch or stride that is too small; m_d or map_d not 16-byte aligned; the destination overlapping the source, the affines or the
+ * table; sizes that overflow the address space. */
+enum { AEFFT_WARP_NEAREST = 0, AEFFT_WARP_LINEAR = 1 };
+enum { AEFFT_BORDER_CONSTANT = 0, AEFFT_BORDER_REPLICATE = 1, AEFFT_BORDER_REFLECT = 2 };
+typedef struct { long long a[6]; } aefft_affine;   /* Q24: a[k] = m[k] * 2^24 of the row-major 2 x 3 matrix (destination -> source) */
+int aefft_affine_make(const double m[6], aefft_affine* out);   /* host arithmetic */
+int aefft_image_warp_affine(aefft_ctx* ctx, const unsigned char* src_d, size_t src_pitch, size_t src_stride, int Ws, int Hs,
+                            const aefft_affine* m_d, int nm, int interp, int border, unsigned border_value,
+                            unsigned char* dst_d, size_t dst_pitch, size_t dst_stride, int Wd, int Hd, int B, int D);
+int aefft_image_remap(aefft_ctx* ctx, const unsigned char* src_d, size_t src_pitch, size_t src_stride, int Ws, int Hs,
+                      const int* map_d, int interp, int border, unsigned border_value,
+                      unsigned char* dst_d, size_t dst_pitch, size_t dst_stride, int Wd, int Hd, int B, int D);
+
 /* ---- network level: the resident, batched form of autoenc_fft / backprop_fft ------------------ */
 typedef struct {
     int D, Nx, Ny;        /* input frames [B][D][Nx][Ny] */
