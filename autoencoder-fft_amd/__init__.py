@@ -10,6 +10,7 @@ Import with:  aefft = importlib.import_module("autoencoder-fft_amd")
 import atexit
 import ctypes as C
 import os
+import math
 
 import numpy as np
 import torch
@@ -83,6 +84,11 @@ class Affine(C.Structure):
     _fields_ = [("a", C.c_longlong * 6)]
 
 
+class Shift(C.Structure):
+    """include/aefft.h aefft_shift: the estimated shift of one image (16 bytes; SHIFT is the numpy form)"""
+    _fields_ = [("dx", C.c_float), ("dy", C.c_float), ("response", C.c_float), ("cell", C.c_int)]
+
+
 _lib = None
 _vp, _fp, _i, _l, _f = C.c_void_p, C.c_void_p, C.c_int, C.c_long, C.c_float   # device float* passed as void*
 
@@ -139,6 +145,10 @@ SIGNATURES = {
     "aefft_affine_make": (_i, [C.POINTER(C.c_double), C.POINTER(Affine)]),
     "aefft_image_warp_affine": (_i, [_vp, _vp, C.c_size_t, C.c_size_t, _i, _i, _vp, _i, _i, _i, C.c_uint, _vp, C.c_size_t, C.c_size_t, _i, _i, _i, _i]),
     "aefft_image_remap": (_i, [_vp, _vp, C.c_size_t, C.c_size_t, _i, _i, _vp, _i, _i, C.c_uint, _vp, C.c_size_t, C.c_size_t, _i, _i, _i, _i]),
+    "aefft_register_spec_floats": (C.c_size_t, [_i, _i]),
+    "aefft_register_workspace": (C.c_size_t, [_i, _i, _i]),
+    "aefft_frames_register_ref": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _fp, _vp, C.c_size_t]),
+    "aefft_frames_register": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _fp, _i, _f, _f, C.c_double, C.c_double, _vp, _vp, _vp, C.c_size_t]),
     "aefft_net_create": (_i, [_vp, C.POINTER(NetDesc), C.POINTER(_vp)]),
     "aefft_net_create_ex": (_i, [_vp, C.POINTER(NetDesc), C.c_uint, C.POINTER(_vp)]),
     "aefft_net_destroy": (None, [_vp]),
@@ -976,6 +986,41 @@ def _image_remap_args(image, table, interp, border, value, out):
     return img, pitch, stride, (Wd, Hd), i, b, v
 
 
+REGISTER_WINDOW = {"hann": 0, "nowindow": 1}                  # AEFFT_REGISTER_HANN, AEFFT_REGISTER_NOWINDOW
+# aefft_shift as a numpy record
+SHIFT = np.dtype([("dx", "<f4"), ("dy", "<f4"), ("response", "<f4"), ("cell", "<i4")])
+
+
+class RegisterRef:
+    """What Context.frames_register_ref returns: the reference spectra [nref][Nx][Ny/2+1] (complex64, on the device), the window they were made
+    with and the sizes"""
+
+    def __init__(self, spec, window, D, Nx, Ny):
+        self.spec, self.window, self.D, self.Nx, self.Ny = spec, window, D, Nx, Ny
+        self.nref = spec.shape[0]
+
+
+def _register_args(frames, ref, cutoff, min_response, scale):
+    """the checks of Context.frames_register that need no device: (B, D, Nx, Ny, scale_x, scale_y)"""
+    what = "Context.frames_register"
+    B, D, Nx, Ny = _frames4(frames, what)
+    if not isinstance(ref, RegisterRef):
+        raise ValueError(f"{what}: ref must be what Context.frames_register_ref returned")
+    if (ref.D, ref.Nx, ref.Ny) != (D, Nx, Ny) or ref.nref not in (1, B):
+        raise ValueError(f"{what}: the reference was made from {ref.nref} frames of D, Nx, Ny = {(ref.D, ref.Nx, ref.Ny)}; the frames need 1 or {B} of {(D, Nx, Ny)}")
+    if not 0.0 < float(cutoff) <= 1.0:
+        raise ValueError(f"{what}: cutoff must be in (0, 1]")
+    if math.isnan(float(min_response)):
+        raise ValueError(f"{what}: min_response must not be NaN")
+    try:
+        sx, sy = (float(v) for v in scale)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: scale must be (scale_x, scale_y)") from None
+    if not (0.0 < sx <= 32.0 and 0.0 < sy <= 32.0):
+        raise ValueError(f"{what}: scale_x and scale_y must be in (0, 32]")
+    return B, D, Nx, Ny, sx, sy
+
+
 class Context:
     """aefft_ctx on torch's current device, enqueuing on torch's current stream by default."""
 
@@ -1389,6 +1434,55 @@ class Context:
         o, opitch, ostride = _resize_layout(out, "Context.image_remap: out")
         self.check(self.L.aefft_image_remap(self.h, _ptr(img), pitch, stride, W, H, _ptr(table), i, b, v, _ptr(o), opitch, ostride, Wd, Hd, B, D))
         return out
+
+    def _register_work(self, Nx, Ny, B, what):
+        need = self.L.aefft_register_workspace(Nx, Ny, B)
+        if not need:
+            raise ValueError(f"{what}: Nx, Ny must be powers of two in 8..2048 or even sizes in 10..2048 with no prime factor above 5, and B * Nx * Ny below 2^29")
+        return self.empty(need, dtype=torch.uint8), need
+
+    def frames_register_ref(self, frames, window="hann"):
+        """The reference side of the phase correlation (aefft_frames_register_ref): `frames` is uint8 or float32 [nref][D][Nx][Ny], nref = 1 for a
+        reference the batch shares or one per image.  Channel sum, window ("hann", or "nowindow" for periodic content) and the library's R2C.
+        Returns a RegisterRef holding the spectra, the window and the sizes.  The first call at a new size may allocate transform workspace."""
+        what = "Context.frames_register_ref"
+        nref, D, Nx, Ny = _frames4(frames, what, "[nref][D][Nx][Ny]")
+        if window not in REGISTER_WINDOW:
+            raise ValueError(f"{what}: window must be one of {sorted(REGISTER_WINDOW)}")
+        work, need = self._register_work(Nx, Ny, nref, what)
+        spec = self.empty(nref, Nx, Ny // 2 + 1, dtype=torch.complex64)
+        self.check(self.L.aefft_frames_register_ref(self.h, _ptr(frames), int(_is_u8(frames)), nref, D, Nx, Ny, REGISTER_WINDOW[window], _ptr(spec), _ptr(work), need))
+        return RegisterRef(spec, window, D, Nx, Ny)
+
+    def frames_register(self, frames, ref, cutoff=0.5, min_response=0.0, scale=(1.0, 1.0), affine=False):
+        """The shift of each frame against the reference by phase correlation (aefft_frames_register): `frames` uint8 or float32 [B][D][Nx][Ny],
+        `ref` from frames_register_ref (one reference or B).  Returns the shifts as a uint8 device tensor [B][16] -- view it on the host with
+        .cpu().numpy().view(SHIFT): dx, dy (frame cells, + when the image is the reference moved toward larger indices), response, cell --
+        and with affine=True the pair (shifts, affines): an int64 device tensor (B, 6) of Q24 coefficients with the offsets dx * scale[0],
+        dy * scale[1] (image pixels per frame cell), the identity where response < min_response, which Context.image_warp takes as it is.
+        Nothing waits for the device."""
+        B, D, Nx, Ny, sx, sy = _register_args(frames, ref, cutoff, min_response, scale)
+        work, need = self._register_work(Nx, Ny, B, "Context.frames_register")
+        shifts = self.empty(B, 16, dtype=torch.uint8)
+        aff = self.empty(B, 6, dtype=torch.int64) if affine else None
+        self.check(self.L.aefft_frames_register(self.h, _ptr(frames), int(_is_u8(frames)), B, D, Nx, Ny, REGISTER_WINDOW[ref.window], _ptr(ref.spec), ref.nref,
+                                                float(cutoff), float(min_response), sx, sy, _ptr(shifts), _ptr(aff), _ptr(work), need))
+        return (shifts, aff) if affine else shifts
+
+    def image_align(self, image, ref, frame_size, cutoff=0.5, min_response=0.0, mode="linear", interp="linear", border="replicate", value=0, out=None):
+        """Images put back on the reference's pixels in one call: aefft_image_resize_to_frames to frame_size = (Nx, Ny), aefft_frames_register
+        against `ref` (from frames_register_ref at that size) with scale = (W / Nx, H / Ny), then aefft_image_warp_affine with the affines as
+        they lie on the device.  `image` uint8 [B][H][W][D] or [H][W][D]; mode is the resize's, interp, border, value and out the warp's.
+        Returns (out, shifts, affines)."""
+        what = "Context.image_align"
+        img, _, _ = _resize_layout(image, what)
+        B, H, W, D = img.shape
+        Nx, Ny = _two_ints(frame_size, what, "frame_size must be (Nx, Ny)")
+        if Nx < 1 or Ny < 1 or W > 32 * Nx or H > 32 * Ny:
+            raise ValueError(f"{what}: frame_size must be positive and at least (W / 32, H / 32)")
+        frames = self.image_resize_to_frames(img, (Nx, Ny), mode=mode)
+        shifts, aff = self.frames_register(frames, ref, cutoff=cutoff, min_response=min_response, scale=(W / Nx, H / Ny), affine=True)
+        return self.image_warp(img, aff, interp=interp, border=border, value=value, out=out), shifts, aff
 
     def frames_degrade(self, frames, blur=0, sigma=0.0, impulse=0.0, seed=0, first_frame=0, out=None, dtype=None):
         """The degraded input of target training from the clean frames (aefft_frames_degrade), one launch: `frames` uint8 or float32

@@ -1,5 +1,5 @@
 // Host-side interface of the C-ABI layer (include/aefft.h), shared by its units: aefft_capi.hip (context, workspaces, flags,
-// side streams, profiling), ops.hip (op helpers, op-level and spatial entry points), image_ops.hip (image-boundary entry points), net.hip, net_forward.hip, net_score.hip and net_step.hip (resident network).
+// side streams, profiling), ops.hip (op helpers, op-level and spatial entry points), image_ops.hip (image-boundary entry points), register_ops.hip (registration), net.hip, net_forward.hip, net_score.hip and net_step.hip (resident network).
 // The context and the profiling brackets, and the helpers one unit defines for another.  Nothing here is exported.
 #pragma once
 #include "../../include/aefft.h"

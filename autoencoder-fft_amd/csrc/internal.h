@@ -169,6 +169,20 @@ hipError_t launch_image_warp_affine(const unsigned char* src, size_t spitch, siz
                                     unsigned bval, unsigned char* dst, size_t dpitch, size_t dstride, int Wd, int Hd, int B, int D, hipStream_t st);
 hipError_t launch_image_remap(const unsigned char* src, size_t spitch, size_t sstride, int Ws, int Hs, const int* map, int interp, int border, unsigned bval,
                               unsigned char* dst, size_t dpitch, size_t dstride, int Wd, int Hd, int B, int D, hipStream_t st);
+// ---- register_kernels.hip (aefft_frames_register, aefft_frames_register_ref) ----
+// The kernels around the two transforms of the phase correlation (include/aefft.h).  prepare: planes [B][Nx][Ny] = window times the channel sum of
+// the frames [B][D][Nx][Ny] (8-bit or float), window 0 HANN / 1 NOWINDOW.  cross: spec [B][Nx][Ny/2+1] becomes the normalised cross-power with ref
+// (nref 1 or B spectra) over the bins with |u| <= umax, |v| <= vmax and not (|u| <= low and |v| <= low), 0 elsewhere, in place.  peak: two launches,
+// register_parts partials an image into `part`, then the shift of each surface [B][Nx][Ny] and, with `affine` non-null, its affine.
+// register_workspace: the bytes of planes | spectra | partials, each rounded up to 16, with the offsets of the last two; 0 for sizes that are no
+// power of two in 8..2048 or even smooth size in 10..2048, B < 1 or B Nx Ny >= 2^29.  register_kept: the kept bins K of the full spectrum and the
+// three index limits; -1 for a cutoff outside (0, 1].  No atomics; D in 1..4 (hipErrorInvalidValue otherwise); the C entry points check the rest.
+size_t register_workspace(int Nx, int Ny, int B, size_t* spec_at = nullptr, size_t* part_at = nullptr);
+long long register_kept(int Nx, int Ny, int window, float cutoff, int* umax, int* vmax, int* low);
+hipError_t launch_register_prepare(const void* frames, int frames_u8, float* planes, int B, int D, int Nx, int Ny, int window, hipStream_t st);
+hipError_t launch_register_cross(float2* spec, const float2* ref, int nref, int B, int Nx, int Ny, int window, int umax, int vmax, int low, hipStream_t st);
+hipError_t launch_register_peak(const float* surf, void* part, int B, int Nx, int Ny, float min_response, double scale_x, double scale_y, aefft_shift* shift,
+                                aefft_affine* affine, hipStream_t st);
 size_t fft_mid_elems(long planes, int Nx, int Wc);   // complex elements needed in `mid`
 // sizes that are not powers of two (cufftPlanMany takes any size, fft.cu:773-779): even n in 8..1024 through Bluestein's chirp-z form on the
 // power-of-two LDS passes; rows -> transpose -> rows -> transpose.  w1, w2: workspaces of fft_any_ws_elems complex each.

@@ -824,6 +824,62 @@ int aefft_image_remap(aefft_ctx* ctx, const unsigned char* src_d, size_t src_pit
                       const int* map_d, int interp, int border, unsigned border_value,
                       unsigned char* dst_d, size_t dst_pitch, size_t dst_stride, int Wd, int Hd, int B, int D);
 
+/* aefft_frames_register_ref, aefft_frames_register: estimate the shift by phase correlation -- the pose that aefft_image_warp_affine consumes,
+ * computed on the device with the library's own transforms against a stored reference spectrum.  Translation only; rotation and scale are not
+ * estimated.
+ * Inputs: frames [B][D][Nx][Ny], 8-bit (frames_u8) or float, 16-byte aligned; axis i is the image column and axis j the image row, as
+ * aefft_image_to_frames defines them.  D in 1..4, B >= 1, B Nx Ny < 2^29; Nx and Ny are sizes the per-bin ops accept: powers of two in 8..2048 or
+ * even smooth sizes in 10..2048.
+ * Steps:
+ *   1. prepare      g[b][i][j] = wx[i] wy[j] sum_d p[b][d][i][j] in float.  AEFFT_REGISTER_HANN: the periodic Hann window
+ *                   w[n] = 0.5 - 0.5 cos(2 pi n / N).  AEFFT_REGISTER_NOWINDOW: w = 1, for periodic content (and the exact case below).
+ *   2. transform    G = r2c(g), unnormalised, [Nx][Ny/2+1] complex, by the route aefft_r2c takes on that grid.  aefft_frames_register_ref stops
+ *                   here: spec_d receives G of each of the nref frames.
+ *   3. cross-power  R = G_img conj(G_ref) per bin; Q = R / |R| where the bin is kept and |R| > 0, otherwise Q = 0.  A bin (u, v) (signed
+ *                   frequencies) is kept when 2|u| <= cutoff Nx and 2|v| <= cutoff Ny and it is not in the dropped low set: the DC bin alone
+ *                   under NOWINDOW, the nine bins with |u| <= 1 and |v| <= 1 under HANN (a Hann-windowed constant has its whole spectrum in
+ *                   those nine, so dropping them removes the image mean's pull toward zero shift without a pass over the image).  cutoff is a
+ *                   float in (0, 1].  K is the number of kept bins of the FULL Nx x Ny spectrum: host arithmetic, independent of the data.
+ *   4. surface      s = c2r(Q) / K (scale = 1 / K in the transform).  A pure circular shift whose kept bins are all non-zero gives 1 at one
+ *                   cell and (nearly) 0 elsewhere.
+ *   5. peak         the largest s[b][i][j], the smallest index i Ny + j on ties (-0 counts as +0, a NaN is no candidate), at (pi, pj).  Over
+ *                   its 5 x 5 circular neighbourhood with weights w = max(s, 0), accumulated in double in ascending (di, dj):
+ *                   cx = sum w di / sum w, cy alike over dj (0 when sum w is 0).  dx = pi + cx, reduced by Nx when >= Nx / 2; dy alike with
+ *                   Ny; response = s[pi][pj]; cell = pi Ny + pj.  One aefft_shift (16 bytes) per image.
+ *   6. affine       (affine_d non-null) with the host doubles scale_x, scale_y -- image pixels per frame cell, each in (0, 32] --: when
+ *                   response >= min_response (false for NaN)  a = {2^24, 0, rint((double)dx scale_x 2^24), 0, 2^24, rint((double)dy scale_y 2^24)},
+ *                   otherwise the identity {2^24, 0, 0, 0, 2^24, 0}.  rint is to nearest, ties to even, in double, on the device; the offsets
+ *                   stay within aefft_affine_make's 2^39.
+ * Sign: if the image is the reference moved by +d, img(x) = ref(x - d), then (dx, dy) = +d; the affine maps destination to source,
+ * src = dst + d, so aefft_image_warp_affine with it puts the image back on the reference's pixels.  Example: frames = np.roll(ref, 3, axis=-2)
+ * gives dx = 3, dy = 0 and a[2] = 3 * 2^24.
+ * Non-finite float frames give unspecified numbers; cell is always inside the grid and nothing is read or written out of range.
+ * Reference: ref_spec_d holds nref spectra as aefft_frames_register_ref wrote them with the same Nx, Ny and window; nref == 1 (shared by the
+ * batch) or nref == B (one per image).
+ * Workspace: work_d is the caller's, 16-byte aligned, at least aefft_register_workspace(Nx, Ny, B) bytes (nref for B in
+ * aefft_frames_register_ref): round16(4 B Nx Ny) for the windowed planes, which the surface reuses, + round16(8 B Nx (Ny/2+1)) for the image
+ * spectra + round16(8 B ceil(Nx Ny / 4096)) for the peak partials.  The transforms take the context's transform workspace exactly as aefft_r2c
+ * does: the first call at a new size may allocate (and, on a smooth axis size, build that size's table), so it must not be the first one made
+ * under stream capture; later calls are safe under capture.
+ * Both calls: launches on the context's stream only -- prepare, the transform, and for aefft_frames_register the cross-power, the inverse
+ * transform and a two-stage peak (many workgroups an image write partials, one finishes); no host synchronisation, no atomics, no workgroup
+ * waits for another; the same inputs give the same bytes from run to run.  The three kernels are accounted under the profile id `image`, the
+ * transforms under their own ids.
+ * AEFFT_EINVAL, with aefft_last_error starting with the call's name ("aefft_frames_register: ", "aefft_frames_register_ref: ") and naming the
+ * rule, nothing enqueued and the outputs untouched: a null context or required pointer (affine_d may be NULL); D, B, nref or a size out of
+ * range; an unknown window; cutoff outside (0, 1] or NaN; a cutoff that keeps no bin (K = 0); a scale outside (0, 32] or non-finite; a pointer
+ * that is not 16-byte aligned; work_bytes too small; outputs that overlap inputs, the workspace or each other. */
+enum { AEFFT_REGISTER_HANN = 0, AEFFT_REGISTER_NOWINDOW = 1 };
+typedef struct { float dx, dy, response; int cell; } aefft_shift;
+size_t aefft_register_spec_floats(int Nx, int Ny);          /* 2 Nx (Ny/2+1); 0 on invalid sizes */
+size_t aefft_register_workspace(int Nx, int Ny, int B);     /* bytes; 0 on invalid sizes */
+int aefft_frames_register_ref(aefft_ctx* ctx, const void* frames_d, int frames_u8, int nref, int D, int Nx, int Ny, int window,
+                              float* spec_d /* [nref][Nx][Ny/2+1] complex */, void* work_d, size_t work_bytes);
+int aefft_frames_register(aefft_ctx* ctx, const void* frames_d, int frames_u8, int B, int D, int Nx, int Ny, int window,
+                          const float* ref_spec_d, int nref /* 1 or B */, float cutoff, float min_response,
+                          double scale_x, double scale_y, aefft_shift* shift_d, aefft_affine* affine_d /* nullable */,
+                          void* work_d, size_t work_bytes);
+
 /* ---- network level: the resident, batched form of autoenc_fft / backprop_fft ------------------ */
 typedef struct {
     int D, Nx, Ny;        /* input frames [B][D][Nx][Ny] */

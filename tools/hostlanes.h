@@ -36,6 +36,7 @@ static inline unsigned px_u8(float v) { return v > 0.f ? (unsigned)fminf(roundf(
 #define CM_HD static inline
 #define BA_HD static inline
 #define WP_HD static inline
+#define RG_HD static inline
 
 // the launch: every workgroup of the grid, one after the other, its 256 lanes as threads; body(lds) is one lane's run of the kernel body
 template <class F> static void launch(unsigned gx, unsigned gy, unsigned gz, size_t lds_words, F body)
