@@ -37,16 +37,13 @@
 #define RZ_UNIFORM(x) __builtin_amdgcn_readfirstlane(x)
 #endif
 #include "resize_taps.h"
+#include "resize_tile.h"                         // fr_stage_runs, fr_band_sums, fr_round_tile: steps 2 and 3, shared with yuv_out_kernels.hip
 
 namespace aefft {
 
-constexpr int PR_TY = 32;                        // destination rows of a full tile
+// (the tile constants PR_TY, PR_CW, PR_NH, PR_RPL, pr_ceil_div and pr_div_u8: resize_tile.h)
 constexpr int PR_BAND_WORDS = 8704;              // dwords of staged runs a workgroup holds (34 KiB: one column of D runs of 8192 + 3 bytes fits)
-constexpr int PR_CW = 64;                        // bytes of a full tile row: a wave's lanes, one byte column each
-constexpr int PR_NH = 256 / PR_CW;               // waves of the workgroup: wave h owns the rows h, h + 4, h + 8, ...
-constexpr int PR_RPL = PR_TY / PR_NH;            // rows of the tile a lane owns: 8
 RZ_HD int pr_tx_full(int D) { return (PR_CW / D) & ~3; }   // destination columns of a full tile: 64, 32, 20, 16
-RZ_HD int pr_ceil_div(int a, int b) { return (a + b - 1) / b; }
 // the tile for source sizes (Sx, Sy) -> destination sizes (W, H): a full tile (txf x tyf), each side divided by the axis' reduction ratio (rounded up)
 RZ_HD void pr_tile(int txf, int tyf, int Sx, int Sy, int W, int H, int* TX, int* TY)
 {
@@ -57,15 +54,6 @@ RZ_HD void pr_tile(int txf, int tyf, int Sx, int Sy, int W, int H, int* TX, int*
 // next to nothing per tile, so a larger tile only spreads the taps and the colour table over more pixels
 constexpr int OV_TY = 32;
 RZ_HD int ov_tx_full(int D) { return rz_min(128, 256 / D) & ~3; }   // 128, 128, 84, 64
-// 0 <= q = floor(n / den) <= 255 without a 64-bit division: a float estimate (off by one at most), then corrected exactly
-RZ_HD unsigned pr_div_u8(unsigned long long n, unsigned long long den)
-{
-    unsigned q = (unsigned)((float)n / (float)den);
-    q = q > 255u ? 255u : q;
-    while ((unsigned long long)q * den > n) --q;
-    while ((unsigned long long)(q + 1) * den <= n) ++q;
-    return q;
-}
 
 // ---- frames -> image ------------------------------------------------------------------------------
 struct FrArgs {
@@ -89,7 +77,6 @@ __device__ __forceinline__ void frames_resize_body(const FrArgs& a, unsigned* ld
     unsigned char* tileb = reinterpret_cast<unsigned char*>(tile);
     unsigned* band = tile + PR_CW / 4 * PR_TY;
     const unsigned char* bandb = reinterpret_cast<const unsigned char*>(band);
-    unsigned char* bandb_w = reinterpret_cast<unsigned char*>(band);
     const int tid = (int)threadIdx.x;
     const int ty_i = (int)blockIdx.x / a.tx;
     const int i0 = ((int)blockIdx.x - ty_i * a.tx) * a.TX, j0 = ty_i * a.TY;
@@ -122,50 +109,13 @@ __device__ __forceinline__ void frames_resize_body(const FrArgs& a, unsigned* ld
         for (int k = 0; k < PR_RPL; ++k) acc[k] = 0;
         for (int xb = xs; xb < xe; xb += a.XB) {
             const int nxb = rz_min(a.XB, xe - xb);
-            // run n = (x - xb) D + d of the band: the bytes frames[b][d][x][ya ..] at dword n P.  Consecutive lanes: consecutive units of a run -- a
-            // dword (a float4 of float frames) when Ny % 4 == 0, an element otherwise -- then the next run
-#pragma unroll 2
-            for (int idx = tid; idx < (D * nxb) << a.ush; idx += 256) {
-                const int run = idx >> a.ush, u = idx & ((1 << a.ush) - 1), x = run / D, dd = run - x * D;
-                if (u >= nru) continue;
-                const size_t o = ((b * D + dd) * a.Nx + (xb + x)) * (size_t)a.Ny + ya + (a.frm_words ? 4 * u : u);   // (dwords: ya + 4 u + 3 < Ny, a multiple of 4)
-                if (a.frm_words) {
-                    unsigned v;
-                    if (F32) {
-                        const float4 f = *reinterpret_cast<const float4*>(static_cast<const float*>(a.frames) + o);
-                        v = px_u8(f.x) | px_u8(f.y) << 8 | px_u8(f.z) << 16 | px_u8(f.w) << 24;
-                    } else v = *reinterpret_cast<const unsigned*>(static_cast<const unsigned char*>(a.frames) + o);
-                    band[run * a.P + u] = v;
-                } else bandb_w[4 * run * a.P + u] = F32 ? (unsigned char)px_u8(static_cast<const float*>(a.frames)[o]) : static_cast<const unsigned char*>(a.frames)[o];
-            }
+            fr_stage_runs<D, F32>(tid, a.frames, b, a.Nx, a.Ny, xb, nxb, ya, nru, a.ush, a.frm_words, a.P, band);
             __syncthreads();
-            const int x_end = rz_min(X.lo + X.cnt, xb + nxb);
-#pragma unroll 1
-            for (int x = rz_max(X.lo, xb); x < x_end; ++x) {
-                const unsigned char* run = bandb + 4 * ((x - xb) * D + d) * a.P - ya;
-                const unsigned wx = (unsigned)rz_weight(X, x, a.W);
-#pragma unroll
-                for (int k = 0; k < PR_RPL; ++k) {
-                    const RzTap Y = yt[rz_min(PR_NH * k + h, nrows - 1)];         // (the same in every lane of the wave)
-                    const int lo = Y.lo, cnt = MODE == RZ_AREA ? RZ_UNIFORM(Y.cnt) : Y.cnt, wf = Y.wf, wl = cnt > 1 ? Y.wl : 0;
-                    const unsigned char* p = run + lo;
-                    unsigned v = (unsigned)wf * p[0];                            // the vertical sum of the run: at most 255 * 8192
-                    if (MODE == RZ_AREA)
-#pragma unroll 1
-                        for (int y = 1; y < cnt - 1; ++y) v += (unsigned)a.H * p[y];
-                    v += (unsigned)wl * p[cnt - 1];
-                    acc[k] += (acc_t)wx * v;
-                }
-            }
+            fr_band_sums<D, MODE>(X, yt, bandb, a.P, d, h, nrows, xb, nxb, ya, a.W, a.H, acc);
             __syncthreads();
         }
         // the finished bytes to the tile in image order, then out with the accesses that are contiguous on the image side
-        const unsigned long long nn = (unsigned long long)a.Nx * a.Ny;
-#pragma unroll
-        for (int k = 0; k < PR_RPL; ++k) {
-            const unsigned px = MODE == RZ_LINEAR ? (unsigned)((acc[k] + (1u << 21)) >> 22) : pr_div_u8(2 * (unsigned long long)acc[k] + nn, 2 * nn);
-            tileb[PR_CW * (h * PR_RPL + k) + c] = (unsigned char)px;
-        }
+        fr_round_tile<MODE>(acc, (unsigned long long)a.Nx * a.Ny, tileb, h, c);
         __syncthreads();
         unsigned char* img = a.image + b * a.stride + (size_t)j0 * a.pitch + (size_t)i0 * D;
         // a lane per dword of a row when image_d, pitch and image_stride are multiples of 4, per byte otherwise

@@ -25,6 +25,7 @@
 #define RZ_UNIFORM(x) __builtin_amdgcn_readfirstlane(x)
 #endif
 #include "resize_taps.h"                         // RzTap, rz_tap, rz_weight: the tap formulas, shared with present_kernels.hip
+#include "resize_tile.h"                         // rz_band_sums, rz_store_block: the phases behind the staging, shared with yuv_kernels.hip
 
 namespace aefft {
 
@@ -118,81 +119,12 @@ __device__ __forceinline__ void resize_body(const RzArgs& a, unsigned* lds)
                 }
             }
             __syncthreads();
-            if (MODE == RZ_LINEAR) {
-                // LINEAR: a destination row has one or two source rows.  The lane takes its four destination rows one after the other; the horizontal
-                // sum of a source row is formed once and kept for the next destination row when that starts on the same source row (y1 = y0')
-                int h_row = -1;
-                unsigned h = 0;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const RzTap Y = yt[rz_min(4 * q + k, nrows - 1)];
-                    const int cnt = 4 * q + k < nrows ? Y.cnt : 0;               // (a row beyond the tile, a lane without a block: no trips)
-#pragma unroll 1
-                    for (int r = 0; r < cnt; ++r) {
-                        const int y = Y.lo + r - yb;
-                        const bool in = (unsigned)y < (unsigned)nr;              // (false: a row of another band)
-                        if (in && y != h_row) {
-                            const unsigned char* p = col + 4 * y * a.P;
-                            h = (unsigned)X.wf * p[0];
-                            if (X.cnt > 1) h += (unsigned)X.wl * p[D];
-                            h_row = y;
-                        }
-                        acc[k] += (acc_t)(!in ? 0u : (r == 0 ? (unsigned)Y.wf : (unsigned)Y.wl)) * h;
-                    }
-                }
-            } else {
-                // AREA: the lane runs ONCE over the source rows of its block; a row's horizontal sum goes to the one or two destination rows it overlaps
-                RzTap Y[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) Y[k] = yt[rz_min(4 * q + k, nrows - 1)];
-                const int y_first = Y[0].lo, y_end = own ? Y[3].lo + Y[3].cnt : 0;   // (Y[3]: the block's last live row)
-#pragma unroll
-                for (int k = 1; k < 4; ++k)
-                    if (4 * q + k >= nrows) Y[k].cnt = 0;
-#pragma unroll 1
-                for (int y = rz_max(y_first, yb); y < rz_min(y_end, yb + nr); ++y) {
-                    const unsigned char* p = col + 4 * (y - yb) * a.P;
-                    unsigned h = (unsigned)X.wf * p[0];
-#pragma unroll 1
-                    for (int x = 1; x < X.cnt - 1; ++x) h += (unsigned)a.Nx * p[x * D];
-                    if (X.cnt > 1) h += (unsigned)X.wl * p[(X.cnt - 1) * D];
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) acc[k] += (acc_t)(unsigned)rz_weight(Y[k], y, a.Ny) * h;
-                }
-            }
+            rz_band_sums<D, MODE>(X, yt, col, a.P, q, nrows, own, yb, nr, a.Nx, a.Ny, acc);
             __syncthreads();
         }
         if (!own) continue;
         const size_t o = (((size_t)b * D + d) * a.Nx + (i0 + i)) * (size_t)a.Ny + (j0 + 4 * q);
-        unsigned px[4] = {0u, 0u, 0u, 0u};                                       // 8-bit frames: the pixel; float frames: value * 2^16 (< 2^24)
-        if (MODE == RZ_LINEAR) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) px[k] = F32 ? (unsigned)((acc[k] + 32u) >> 6) : (unsigned)((acc[k] + (1u << 21)) >> 22);
-        } else {
-            const unsigned long long wh = (unsigned long long)a.W * a.H;
-#pragma unroll 1
-            for (int k = 0; k < 4; ++k) {                                        // (one copy of the 64-bit division; the selects keep acc and px in registers)
-                const unsigned long long num = k == 0 ? acc[0] : k == 1 ? acc[1] : k == 2 ? acc[2] : acc[3];
-                const unsigned v = F32 ? (unsigned)((65536ull * num + wh / 2) / wh) : (unsigned)((2 * num + wh) / (2 * wh));
-                px[0] = k == 0 ? v : px[0]; px[1] = k == 1 ? v : px[1]; px[2] = k == 2 ? v : px[2]; px[3] = k == 3 ? v : px[3];
-            }
-        }
-        if (F32) {
-            float* f = static_cast<float*>(a.frames) + o;
-            const float s = 1.0f / 65536.0f;
-            if (a.frm_words) *reinterpret_cast<float4*>(f) = make_float4((float)px[0] * s, (float)px[1] * s, (float)px[2] * s, (float)px[3] * s);
-            else
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    if (4 * q + k < nrows) f[k] = (float)px[k] * s;
-        } else {
-            unsigned char* f = static_cast<unsigned char*>(a.frames) + o;
-            if (a.frm_words) *reinterpret_cast<unsigned*>(f) = px[0] | px[1] << 8 | px[2] << 16 | px[3] << 24;
-            else
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    if (4 * q + k < nrows) f[k] = (unsigned char)px[k];
-        }
+        rz_store_block<F32, MODE>(acc[0], acc[1], acc[2], acc[3], (unsigned long long)a.W * a.H, a.frames, o, a.frm_words, q, nrows);
     }
 }
 

@@ -3,6 +3,8 @@
 // form: destination index i reads source indices lo .. lo + cnt - 1 with weight wf on the first, wl on the last (cnt > 1) and N, the destination
 // size, on those between:
 //   LINEAR  lo = x0, cnt = 1 or 2, wf = 2048 - w, wl = w                       AREA  lo = floor(i S / N), the overlaps o(i, lo), N, .., N, o(i, hi)
+// What the tile bodies do with the taps -- the sums over a staged band and the roundings -- is stated once as well, in resize_tile.h, which
+// includes this header.
 // Plain C++: the including file defines RZ_HD (the function qualifiers); tools/resize_hostcheck.cpp and tools/present_hostcheck.cpp compile this
 // header for the host.
 #pragma once

@@ -11,7 +11,7 @@
 //                                          SAME band layout (byte 4 r P + x D + d - a0, a0 = (xs & ~3) D: a 4-pixel group is D whole dwords).
 //                                          Lanes run along the groups of a row (consecutive dwords of Y, of NV12 chroma): the items are counted off
 //                                          in rows of 2^lw >= the widest tile's groups (the launcher's choice), 256 per pass.  Behind the band
-//                                          everything is the resize's arithmetic restated (see yuv_body).
+//                                          everything is the resize's arithmetic, from resize_tile.h (see yuv_body).
 //   yuv_image_kernel<FMT, D>               element-wise, no LDS: a lane owns one item, so each chroma sample is loaded once, and stores 4 D bytes
 //                                          per row -- D dwords when image_d, pitch and image_stride are multiples of 4, bytes otherwise.
 // Loads: dwords (halves for I420 chroma) when every used plane pointer, pitch and stride is a multiple of 4, bytes otherwise, and bytes for the
@@ -27,6 +27,7 @@
 #define RZ_UNIFORM(x) __builtin_amdgcn_readfirstlane(x)
 #endif
 #include "resize_taps.h"                         // RzTap, rz_tap, rz_weight: the tap formulas of every kernel that resizes
+#include "resize_tile.h"                         // rz_band_sums, rz_store_block: the phases behind the staging, shared with resize_kernels.hip
 
 namespace aefft {
 
@@ -268,11 +269,11 @@ __device__ __forceinline__ void yuv_stage(const YvArgs& a, int b, int xs, int xe
     }
 }
 
-// The tile body.  Everything but the call of yuv_stage RESTATES resize_body (resize_kernels.hip; DESIGN.md section 20 has the argument for each
-// step): the same taps, bands, LINEAR / AREA loops, accumulators, roundings and stores over the same band layout.  It is a second copy, not a shared
-// header, because resize_kernels.hip's 16 kernels are pinned to their resource numbers and moving this text into a template over the staging
-// changed them (DESIGN.md section 23 has the figures); a change of the arithmetic has to be made in both, and the composition test
-// (tests/test_gpu_yuv.py: fused == yuv_to_image -> image_resize_to_frames, bit for bit) fails when only one has it.
+// The tile body: resize_body's (resize_kernels.hip; DESIGN.md section 20 has the argument for each step) with yuv_stage as its staging and the
+// arguments' copy in LDS.  The taps, the lane's block and the band loop are this body's own, as they are there; the arithmetic behind the
+// staging -- the LINEAR / AREA sums over a band, the roundings and the stores -- is resize_tile.h's rz_band_sums and rz_store_block, which both
+// bodies call with scalars (DESIGN.md section 23 has the register tables before and after).  The composition test (tests/test_gpu_yuv.py: fused ==
+// yuv_to_image -> image_resize_to_frames, bit for bit) holds the two stagings to the same band layout.
 template <int FMT, int D, bool F32, int MODE>
 __device__ __forceinline__ void yuv_body(const YvArgs& a, unsigned* lds)
 {
@@ -308,81 +309,12 @@ __device__ __forceinline__ void yuv_body(const YvArgs& a, unsigned* lds)
             const int nr = rz_min(a.RB, ye - yb);
             yuv_stage<FMT, D>(*reinterpret_cast<const YvArgs*>(args), b, xs, xe, yb, nr, rows);
             __syncthreads();
-            if (MODE == RZ_LINEAR) {
-                // LINEAR: a destination row has one or two source rows.  The lane takes its four destination rows one after the other; the horizontal
-                // sum of a source row is formed once and kept for the next destination row when that starts on the same source row (y1 = y0')
-                int h_row = -1;
-                unsigned h = 0;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const RzTap Y = yt[rz_min(4 * q + k, nrows - 1)];
-                    const int cnt = 4 * q + k < nrows ? Y.cnt : 0;               // (a row beyond the tile, a lane without a block: no trips)
-#pragma unroll 1
-                    for (int r = 0; r < cnt; ++r) {
-                        const int y = Y.lo + r - yb;
-                        const bool in = (unsigned)y < (unsigned)nr;              // (false: a row of another band)
-                        if (in && y != h_row) {
-                            const unsigned char* p = col + 4 * y * a.P;
-                            h = (unsigned)X.wf * p[0];
-                            if (X.cnt > 1) h += (unsigned)X.wl * p[D];
-                            h_row = y;
-                        }
-                        acc[k] += (acc_t)(!in ? 0u : (r == 0 ? (unsigned)Y.wf : (unsigned)Y.wl)) * h;
-                    }
-                }
-            } else {
-                // AREA: the lane runs ONCE over the source rows of its block; a row's horizontal sum goes to the one or two destination rows it overlaps
-                RzTap Y[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) Y[k] = yt[rz_min(4 * q + k, nrows - 1)];
-                const int y_first = Y[0].lo, y_end = own ? Y[3].lo + Y[3].cnt : 0;   // (Y[3]: the block's last live row)
-#pragma unroll
-                for (int k = 1; k < 4; ++k)
-                    if (4 * q + k >= nrows) Y[k].cnt = 0;
-#pragma unroll 1
-                for (int y = rz_max(y_first, yb); y < rz_min(y_end, yb + nr); ++y) {
-                    const unsigned char* p = col + 4 * (y - yb) * a.P;
-                    unsigned h = (unsigned)X.wf * p[0];
-#pragma unroll 1
-                    for (int x = 1; x < X.cnt - 1; ++x) h += (unsigned)a.Nx * p[x * D];
-                    if (X.cnt > 1) h += (unsigned)X.wl * p[(X.cnt - 1) * D];
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) acc[k] += (acc_t)(unsigned)rz_weight(Y[k], y, a.Ny) * h;
-                }
-            }
+            rz_band_sums<D, MODE>(X, yt, col, a.P, q, nrows, own, yb, nr, a.Nx, a.Ny, acc);
             __syncthreads();
         }
         if (!own) continue;
         const size_t o = (((size_t)b * D + d) * a.Nx + (i0 + i)) * (size_t)a.Ny + (j0 + 4 * q);
-        unsigned px[4] = {0u, 0u, 0u, 0u};                                       // 8-bit frames: the pixel; float frames: value * 2^16 (< 2^24)
-        if (MODE == RZ_LINEAR) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) px[k] = F32 ? (unsigned)((acc[k] + 32u) >> 6) : (unsigned)((acc[k] + (1u << 21)) >> 22);
-        } else {
-            const unsigned long long wh = (unsigned long long)a.s.W * a.s.H;
-#pragma unroll 1
-            for (int k = 0; k < 4; ++k) {                                        // (one copy of the 64-bit division; the selects keep acc and px in registers)
-                const unsigned long long num = k == 0 ? acc[0] : k == 1 ? acc[1] : k == 2 ? acc[2] : acc[3];
-                const unsigned v = F32 ? (unsigned)((65536ull * num + wh / 2) / wh) : (unsigned)((2 * num + wh) / (2 * wh));
-                px[0] = k == 0 ? v : px[0]; px[1] = k == 1 ? v : px[1]; px[2] = k == 2 ? v : px[2]; px[3] = k == 3 ? v : px[3];
-            }
-        }
-        if (F32) {
-            float* f = static_cast<float*>(a.frames) + o;
-            const float s = 1.0f / 65536.0f;
-            if (a.frm_words) *reinterpret_cast<float4*>(f) = make_float4((float)px[0] * s, (float)px[1] * s, (float)px[2] * s, (float)px[3] * s);
-            else
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    if (4 * q + k < nrows) f[k] = (float)px[k] * s;
-        } else {
-            unsigned char* f = static_cast<unsigned char*>(a.frames) + o;
-            if (a.frm_words) *reinterpret_cast<unsigned*>(f) = px[0] | px[1] << 8 | px[2] << 16 | px[3] << 24;
-            else
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    if (4 * q + k < nrows) f[k] = (unsigned char)px[k];
-        }
+        rz_store_block<F32, MODE>(acc[0], acc[1], acc[2], acc[3], (unsigned long long)a.s.W * a.s.H, a.frames, o, a.frm_words, q, nrows);
     }
 }
 

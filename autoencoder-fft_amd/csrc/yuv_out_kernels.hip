@@ -32,6 +32,7 @@
 #define RZ_UNIFORM(x) __builtin_amdgcn_readfirstlane(x)
 #endif
 #include "resize_taps.h"                         // RzTap, rz_tap, rz_weight: the tap formulas of every kernel that resizes
+#include "resize_tile.h"                         // fr_stage_runs, fr_band_sums, fr_round_tile and the tile constants, shared with present_kernels.hip
 
 namespace aefft {
 
@@ -227,21 +228,8 @@ static inline YoArgs yo_geometry(const YoDst& s, int fmt, const unsigned char* i
 }
 
 // ---- frames -> resize -> yuv -------------------------------------------------------------------------
-constexpr int FY_TY = 32;                        // destination rows of a full tile
+// (the tile is frames_resize_kernel's: PR_TY, PR_CW, PR_NH, PR_RPL and pr_ceil_div of resize_tile.h)
 constexpr int FY_BAND_WORDS = 8704;              // dwords of staged runs a workgroup holds (34 KiB: one column of D runs of 8192 + 3 bytes fits)
-constexpr int FY_CW = 64;                        // bytes of a full tile row: a wave's lanes, one byte column each
-constexpr int FY_NH = 256 / FY_CW;               // waves of the workgroup: wave h owns the rows h, h + 4, h + 8, ...
-constexpr int FY_RPL = FY_TY / FY_NH;            // rows of the tile a lane owns: 8
-RZ_HD int fy_ceil_div(int a, int b) { return (a + b - 1) / b; }
-// 0 <= q = floor(n / den) <= 255 without a 64-bit division: a float estimate (off by one at most), then corrected exactly
-RZ_HD unsigned fy_div_u8(unsigned long long n, unsigned long long den)
-{
-    unsigned q = (unsigned)((float)n / (float)den);
-    q = q > 255u ? 255u : q;
-    while ((unsigned long long)q * den > n) --q;
-    while ((unsigned long long)(q + 1) * den <= n) ++q;
-    return q;
-}
 
 struct FyArgs {
     const void* frames;
@@ -252,16 +240,15 @@ struct FyArgs {
     int ush;                                     // log2 of the lanes a run gets while staging
     bool frm_words;
 };
-// LDS of a launch, in dwords: the taps (TX + TY of 4), the finished tile in image order (FY_TY row slots of FY_CW bytes) and the band
-RZ_HD int fy_lds_words(int D, const FyArgs& g) { return 4 * (g.TX + g.TY) + FY_CW / 4 * FY_TY + D * g.XB * g.P; }
+// LDS of a launch, in dwords: the taps (TX + TY of 4), the finished tile in image order (PR_TY row slots of PR_CW bytes) and the band
+RZ_HD int fy_lds_words(int D, const FyArgs& g) { return 4 * (g.TX + g.TY) + PR_CW / 4 * PR_TY + D * g.XB * g.P; }
 
-// The tile body.  Steps 1 to 3 RESTATE frames_resize_body (present_kernels.hip; DESIGN.md section 21 has the argument for each step): the same
-// taps, bands, staging, sums and roundings into the same tile image in LDS.  It is a second copy, not a shared header, because the kernels of
-// present_kernels.hip and resize_kernels.hip are pinned to their resource numbers and moving such a body into a template over its last step
-// changed them (DESIGN.md section 23 has the figures); a change of the resize arithmetic has to be made in both, and the composition test
-// (tests/test_gpu_yuv_out.py: fused == frames_resize_to_image -> image_to_yuv, bit for bit) fails when only one has it.  Two differences in
-// step 3: a lane beyond the row's live bytes sums the LAST PIXEL's channel d again (not the last byte), and a row slot beyond the tile's rows the
-// last row (as there), so that the tile image holds replicated pixels wherever an item reaches beyond the image.  Step 4 is this file's.
+// The tile body: frames_resize_body's (present_kernels.hip; DESIGN.md section 21 has the argument for each step) with another step 4.  The taps (step 1),
+// the lane and the band loop are this body's own, as they are there; steps 2 and 3 -- the run staging, the sums over a band and the rounding into the
+// tile image in LDS -- are resize_tile.h's fr_stage_runs, fr_band_sums and fr_round_tile, which both bodies call with scalars (DESIGN.md section 23 has the
+// register tables before and after).  One difference in the lane: beyond the row's live bytes it sums the LAST PIXEL's channel d again (not the
+// last byte), and a row slot beyond the tile's rows the last row (as there), so that the tile image holds replicated pixels wherever an item
+// reaches beyond the image.  Step 4 is this file's.
 template <int FMT, int D, bool F32, int MODE>
 __device__ __forceinline__ void frames_yuv_body(const FyArgs& a, unsigned* lds)
 {
@@ -272,9 +259,8 @@ __device__ __forceinline__ void frames_yuv_body(const FyArgs& a, unsigned* lds)
     RzTap* yt = xt + a.TX;
     unsigned* tile = lds + 4 * (a.TX + a.TY);
     unsigned char* tileb = reinterpret_cast<unsigned char*>(tile);
-    unsigned* band = tile + FY_CW / 4 * FY_TY;
+    unsigned* band = tile + PR_CW / 4 * PR_TY;
     const unsigned char* bandb = reinterpret_cast<const unsigned char*>(band);
-    unsigned char* bandb_w = reinterpret_cast<unsigned char*>(band);
     const int tid = (int)threadIdx.x;
     const int ty_i = (int)blockIdx.x / a.tx;
     const int i0 = ((int)blockIdx.x - ty_i * a.tx) * a.TX, j0 = ty_i * a.TY;     // (NV12, I420: TY is even, so j0 is)
@@ -289,75 +275,39 @@ __device__ __forceinline__ void frames_yuv_body(const FyArgs& a, unsigned* lds)
     const int nyb = ye - ya, nwy = (nyb + 3) >> 2;                               // (nwy <= P: the launcher sized P over every tile)
     const int rowlive = ncols * D;                                               // bytes of a tile row (at most 64)
     // the lane: byte column c = i D + d of the tile row x the rows h, h + 4, .., h + 28 (h the same in a wave)
-    const int c = tid % FY_CW, h = RZ_UNIFORM(tid / FY_CW);
+    const int c = tid % PR_CW, h = RZ_UNIFORM(tid / PR_CW);
     const int cc = c < rowlive ? c : rowlive - D + c % D, d = cc % D;            // (beyond the live bytes: the last pixel's channel again)
     const int nru = a.frm_words ? nwy : nyb;                                     // units of a staged run: dwords, or elements
     const RzTap X = xt[cc / D];
     // grid.y, grid.z: the images
     const size_t b = (size_t)blockIdx.z * gridDim.y + blockIdx.y;
     if (b >= (size_t)a.B) return;
-    acc_t acc[FY_RPL];
+    acc_t acc[PR_RPL];
 #pragma unroll
-    for (int k = 0; k < FY_RPL; ++k) acc[k] = 0;
+    for (int k = 0; k < PR_RPL; ++k) acc[k] = 0;
     for (int xb = xs; xb < xe; xb += a.XB) {
         const int nxb = rz_min(a.XB, xe - xb);
-        // run n = (x - xb) D + d of the band: the bytes frames[b][d][x][ya ..] at dword n P
-#pragma unroll 2
-        for (int idx = tid; idx < (D * nxb) << a.ush; idx += 256) {
-            const int run = idx >> a.ush, u = idx & ((1 << a.ush) - 1), x = run / D, dd = run - x * D;
-            if (u >= nru) continue;
-            const size_t o = ((b * D + dd) * a.Nx + (xb + x)) * (size_t)a.Ny + ya + (a.frm_words ? 4 * u : u);   // (dwords: ya + 4 u + 3 < Ny, a multiple of 4)
-            if (a.frm_words) {
-                unsigned v;
-                if (F32) {
-                    const float4 f = *reinterpret_cast<const float4*>(static_cast<const float*>(a.frames) + o);
-                    v = px_u8(f.x) | px_u8(f.y) << 8 | px_u8(f.z) << 16 | px_u8(f.w) << 24;
-                } else v = *reinterpret_cast<const unsigned*>(static_cast<const unsigned char*>(a.frames) + o);
-                band[run * a.P + u] = v;
-            } else bandb_w[4 * run * a.P + u] = F32 ? (unsigned char)px_u8(static_cast<const float*>(a.frames)[o]) : static_cast<const unsigned char*>(a.frames)[o];
-        }
+        fr_stage_runs<D, F32>(tid, a.frames, b, a.Nx, a.Ny, xb, nxb, ya, nru, a.ush, a.frm_words, a.P, band);
         __syncthreads();
-        const int x_end = rz_min(X.lo + X.cnt, xb + nxb);
-#pragma unroll 1
-        for (int x = rz_max(X.lo, xb); x < x_end; ++x) {
-            const unsigned char* run = bandb + 4 * ((x - xb) * D + d) * a.P - ya;
-            const unsigned wx = (unsigned)rz_weight(X, x, W);
-#pragma unroll
-            for (int k = 0; k < FY_RPL; ++k) {
-                const RzTap Y = yt[rz_min(FY_NH * k + h, nrows - 1)];             // (the same in every lane of the wave)
-                const int lo = Y.lo, cnt = MODE == RZ_AREA ? RZ_UNIFORM(Y.cnt) : Y.cnt, wf = Y.wf, wl = cnt > 1 ? Y.wl : 0;
-                const unsigned char* p = run + lo;
-                unsigned v = (unsigned)wf * p[0];                                // the vertical sum of the run: at most 255 * 8192
-                if (MODE == RZ_AREA)
-#pragma unroll 1
-                    for (int y = 1; y < cnt - 1; ++y) v += (unsigned)H * p[y];
-                v += (unsigned)wl * p[cnt - 1];
-                acc[k] += (acc_t)wx * v;
-            }
-        }
+        fr_band_sums<D, MODE>(X, yt, bandb, a.P, d, h, nrows, xb, nxb, ya, W, H, acc);
         __syncthreads();
     }
-    // the finished bytes to the tile in image order: row r = 4 k + h in slot FY_RPL h + k, all FY_TY slots and FY_CW columns of it written
-    const unsigned long long nn = (unsigned long long)a.Nx * a.Ny;
-#pragma unroll
-    for (int k = 0; k < FY_RPL; ++k) {
-        const unsigned px = MODE == RZ_LINEAR ? (unsigned)((acc[k] + (1u << 21)) >> 22) : fy_div_u8(2 * (unsigned long long)acc[k] + nn, 2 * nn);
-        tileb[FY_CW * (h * FY_RPL + k) + c] = (unsigned char)px;
-    }
+    // the finished bytes to the tile in image order: row r = 4 k + h in slot PR_RPL h + k, all PR_TY slots and PR_CW columns of it written
+    fr_round_tile<MODE>(acc, (unsigned long long)a.Nx * a.Ny, tileb, h, c);
     __syncthreads();
     // 4. a lane per item -- group g of 4 pixels (D whole dwords of a tile row) x item row pp, the groups counted off in 16 --: its rows from LDS,
     //    the conversion, and the stores of image_yuv_kernel
     unsigned char* pl[3] = {a.s.plane[0] + b * a.s.stride[0], a.s.plane[1] + b * a.s.stride[1], a.s.plane[2] + b * a.s.stride[2]};
     const int ng = (ncols + 3) >> 2, np = (nrows + RSH) >> RSH;
-    for (int idx = tid; idx < np * (FY_CW / 4); idx += 256) {
-        const int g = idx % (FY_CW / 4), pp = idx / (FY_CW / 4);
+    for (int idx = tid; idx < np * (PR_CW / 4); idx += 256) {
+        const int g = idx % (PR_CW / 4), pp = idx / (PR_CW / 4);
         if (g >= ng) continue;
         unsigned in[RSH + 1][D];
 #pragma unroll
         for (int r = 0; r <= RSH; ++r) {
-            const int row = (pp << RSH) + r, slot = (row % FY_NH) * FY_RPL + row / FY_NH;   // (row <= nrows <= 31: a slot beyond the rows holds the last row)
+            const int row = (pp << RSH) + r, slot = (row % PR_NH) * PR_RPL + row / PR_NH;   // (row <= nrows <= 31: a slot beyond the rows holds the last row)
 #pragma unroll
-            for (int n = 0; n < D; ++n) in[r][n] = tile[FY_CW / 4 * slot + g * D + n];
+            for (int n = 0; n < D; ++n) in[r][n] = tile[PR_CW / 4 * slot + g * D + n];
         }
         unsigned yw[2], cw[2];
         yo_convert<FMT, D>(a.s.k, in, yw, cw);
@@ -374,10 +324,10 @@ static inline FyArgs fy_geometry(const YoDst& s, int fmt, const void* frames, in
     FyArgs g;
     g.frames = frames; g.s = s; g.Nx = Nx; g.Ny = Ny; g.B = B;
     const int W = s.W, H = s.H;
-    g.TX = rz_max(4, (((FY_CW / D) & ~3) / fy_ceil_div(Nx, W)) & ~3);
-    g.TY = rz_max(1, FY_TY / fy_ceil_div(Ny, H));
+    g.TX = rz_max(4, (((PR_CW / D) & ~3) / pr_ceil_div(Nx, W)) & ~3);
+    g.TY = rz_max(1, PR_TY / pr_ceil_div(Ny, H));
     if (fmt != YO_YUYV) g.TY = rz_max(2, g.TY & ~1);
-    g.tx = fy_ceil_div(W, g.TX); g.ty = fy_ceil_div(H, g.TY);
+    g.tx = pr_ceil_div(W, g.TX); g.ty = pr_ceil_div(H, g.TY);
     g.frm_words = (Ny & 3) == 0;
     int nx = 1, nyb = 1;
     for (int t = 0; t < g.tx; ++t) {

@@ -21,9 +21,11 @@ pytestmark = pytest.mark.gpu
 
 # (B, D, Nx, Ny, W, H): identity; enlarging to an odd destination with W D no dword multiple (edge clamps); reducing to odd; exact 2x (AREA = the
 # rounded block mean); several tiles with remainders, Ny % 4 == 2 (the element route on the frame side); ratios 20 and 12.5 (bands); the workload's
-# own direction; 255 Nx Ny >= 2^32 (AREA only: the 64-bit sum)
+# own direction; 255 Nx Ny >= 2^32 (AREA only: the 64-bit sum); an x-reduction of 128 whose tiles need more source columns than a band holds, so
+# that the sums run across bands (fr_geometry: to 16 x 4 AREA needs 512 columns with XB = 322, LINEAR needs 386 and XB is 386 -- one band --; to
+# 16 x 8 LINEAR needs 386 with XB = 322 too)
 SHAPES = [(1, 1, 8, 8, 8, 8), (2, 3, 8, 8, 11, 9), (1, 3, 16, 8, 7, 5), (2, 4, 64, 64, 32, 32), (1, 3, 66, 34, 130, 70), (1, 2, 200, 150, 10, 12),
-          (2, 3, 256, 256, 640, 480), (1, 1, 8192, 2064, 8, 6)]
+          (2, 3, 256, 256, 640, 480), (1, 1, 8192, 2064, 8, 6), (1, 3, 2048, 64, 16, 4), (1, 3, 2048, 64, 16, 8)]
 BIG = (1, 1, 8192, 2064, 8, 6)
 PITCHES = ["tight", "pad64", "odd"]
 MODES = ["linear", "area"]

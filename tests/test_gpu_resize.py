@@ -19,9 +19,10 @@ pytestmark = pytest.mark.gpu
 
 # (B, D, W, H, Nx, Ny): identity; odd source with W D no dword multiple; enlarging (edge clamps at both ends, w reaching 2048); exact 2x (AREA = the
 # block mean); more than one tile with remainders and Ny % 4 == 2; ratios 20 and 12.5 (the footprint that needs bands of source rows); the
-# reference's own case; AREA with ~30 x 17 source pixels per cell (the 64-bit sum)
+# reference's own case; AREA with ~30 x 17 source pixels per cell (the 64-bit sum); ONE tile whose rows are so wide that a band holds 5 of the 50
+# (LINEAR) or 64 (AREA) source rows it needs (rz_geometry: P = 1465 / 1537, RB = 5): every sum runs across ten bands or more
 SHAPES = [(1, 1, 8, 8, 8, 8), (2, 3, 11, 9, 8, 8), (1, 3, 7, 5, 16, 8), (2, 4, 64, 64, 32, 32), (1, 3, 130, 70, 66, 34), (1, 2, 200, 150, 10, 12),
-          (2, 3, 640, 480, 256, 256), (1, 3, 1920, 1080, 64, 64)]
+          (2, 3, 640, 480, 256, 256), (1, 3, 1920, 1080, 64, 64), (1, 3, 2048, 64, 21, 4)]
 PITCHES = ["tight", "pad64", "odd"]
 MODES = ["linear", "area"]
 CASES = [(s, m) for s in SHAPES for m in MODES if m == "linear" or (s[4] <= s[2] and s[5] <= s[3])]

@@ -26,9 +26,10 @@ GUARD = 64         # bytes behind an output that must stay as they were
 # (W, H) of the plain call: one tile; odd sizes (NV12, I420: the last chroma column and row serve one pixel) / an odd height (YUYV); several blocks
 IMAGE_SHAPES = {"nv12": [(8, 8), (11, 9), (130, 70)], "i420": [(8, 8), (11, 9), (130, 70)], "yuyv": [(8, 8), (12, 9), (130, 70)]}
 # (B, W, H, Nx, Ny) of the fused call: identity; odd source; enlarging; exact 2x; several tiles with remainders and Ny % 4 == 2; bands of source rows;
-# the camera case; a thumbnail of 1080p (AREA's 64-bit sum, many bands)
+# the camera case; a thumbnail of 1080p (AREA's 64-bit sum, many bands); ONE tile whose rows are so wide that a band holds 5 of the 50 (LINEAR) or
+# 64 (AREA) source rows it needs (yv_geometry: P = 1465 / 1537, RB = 5): every sum runs across ten bands or more
 RESIZE_SHAPES = [(1, 8, 8, 8, 8), (2, 11, 9, 8, 8), (1, 6, 4, 16, 8), (2, 64, 64, 32, 32), (1, 130, 70, 66, 34), (1, 200, 150, 10, 12), (2, 640, 480, 256, 256),
-                 (1, 1920, 1080, 64, 64)]
+                 (1, 1920, 1080, 64, 64), (1, 2048, 64, 21, 4)]
 RESIZE_CASES = [(s, f, m) for s in RESIZE_SHAPES for f in FORMATS for m in MODES
                 if (f != "yuyv" or s[1] % 2 == 0) and (m == "linear" or (s[3] <= s[1] and s[4] <= s[2]))]
 

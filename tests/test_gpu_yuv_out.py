@@ -28,9 +28,11 @@ GUARD = 64         # bytes behind a plane's allocation that must stay as they we
 # several blocks with a group that crosses the row's end
 IMAGE_SHAPES = {"nv12": [(8, 8), (11, 9), (130, 70)], "i420": [(8, 8), (11, 9), (130, 70)], "yuyv": [(8, 8), (12, 9), (130, 70)]}
 # (B, Nx, Ny, W, H) of the fused call: identity; enlarging to odd; reduction; enlarging; several tiles; strong reduction; a y-reduction of 43 (the
-# present kernel's tile would be one row high); the camera case; 1080p
+# present kernel's tile would be one row high); the camera case; 1080p; an x-reduction of 128 whose tiles need more source columns than a band
+# holds, so that the sums run across bands (fy_geometry: to 16 x 4 AREA needs 512 columns with XB = 322, LINEAR needs 386 and XB is 386 -- one
+# band --; to 16 x 8 LINEAR needs 386 with XB = 322 too)
 RESIZE_SHAPES = [(1, 8, 8, 8, 8), (2, 8, 8, 11, 9), (1, 16, 8, 6, 4), (2, 32, 32, 64, 64), (1, 66, 34, 130, 70), (1, 64, 64, 10, 12), (1, 64, 512, 10, 12),
-                 (2, 256, 256, 640, 480), (1, 64, 64, 1920, 1080)]
+                 (2, 256, 256, 640, 480), (1, 64, 64, 1920, 1080), (1, 2048, 64, 16, 4), (1, 2048, 64, 16, 8)]
 RESIZE_CASES = [(s, f, m) for s in RESIZE_SHAPES for f in FORMATS for m in MODES
                 if (f != "yuyv" or s[3] % 2 == 0) and (m == "linear" or (s[3] <= s[1] and s[4] <= s[2]))]
 

@@ -116,6 +116,14 @@ def test_the_older_kernel_files_keep_their_kernels_and_the_taps_are_stated_once(
     for fn in ("resize_kernels.hip", "present_kernels.hip"):
         assert '#include "resize_taps.h"' in open(os.path.join(CSRC, fn)).read()
     assert "4096 * (n - s * den) + den" not in open(os.path.join(CSRC, "present_kernels.hip")).read()
+    # one statement of what the tile bodies do with the taps -- AREA's vertical weight in the band sums, AREA's rounding of float frames, the
+    # correction loop of pr_div_u8 -- in the header all four kernel files that resize through a staged band include
+    srcs = {fn: open(os.path.join(CSRC, fn)).read() for fn in os.listdir(CSRC) if fn.endswith((".hip", ".h", ".cpp"))}
+    for text in ("rz_weight(Y[k], y,", "65536ull * num", "while ((unsigned long long)q * den > n) --q;"):
+        assert [fn for fn in srcs if text in srcs[fn]] == ["resize_tile.h"], text
+    assert len(re.findall(r"unsigned\s+pr_div_u8\s*\(", srcs["resize_tile.h"])) == 1 and "fy_div_u8" not in "".join(srcs.values())
+    for fn in ("resize_kernels.hip", "yuv_kernels.hip", "present_kernels.hip", "yuv_out_kernels.hip"):
+        assert '#include "resize_tile.h"' in srcs[fn], fn
     for tool in ("resize_hostcheck.cpp", "present_hostcheck.cpp"):
         assert os.path.exists(os.path.join(ROOT, "tools", tool))
         assert '#include "hostlanes.h"' in open(os.path.join(ROOT, "tools", tool)).read()

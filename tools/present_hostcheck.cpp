@@ -58,39 +58,7 @@ static void run_resize(const Shape& s, int kind, int mode, bool f32, unsigned gr
     const FrArgs g = fr_geometry(fp, Nx, Ny, mode, alloc + l.off, l.pitch, l.stride, W, H, B, D);
     launch((unsigned)(g.tx * g.ty), grid_y ? grid_y : (unsigned)B, grid_y ? ((unsigned)B + grid_y - 1) / grid_y : 1u, (size_t)fr_lds_words(D, g), [&](unsigned* lds) { FR_BODIES[D - 1][f32][mode](g, lds); });
     // the expected image over a copy of the allocation as it was: every byte outside the live pixels must be unchanged
-    std::vector<std::vector<i64>> ox(W, std::vector<i64>(Nx, 0)), oy(H, std::vector<i64>(Ny, 0));
-    if (mode == 1) {
-        for (int i = 0; i < W; ++i) for (int k = 0; k < Nx; ++k) ox[i][k] = overlap(i, k, Nx, W);
-        for (int j = 0; j < H; ++j) for (int k = 0; k < Ny; ++k) oy[j][k] = overlap(j, k, Ny, H);
-    }
-    for (int b = 0; b < B; ++b)
-        for (int d = 0; d < D; ++d) {
-            const unsigned char* p = px.data() + ((size_t)b * D + d) * Nx * Ny;  // p[x * Ny + y]
-            for (int y = 0; y < H; ++y)
-                for (int x = 0; x < W; ++x) {
-                    unsigned out;
-                    if (mode == 0) {
-                        int x0, x1, wx, y0, y1, wy;
-                        linear_axis(x, Nx, W, &x0, &x1, &wx);
-                        linear_axis(y, Ny, H, &y0, &y1, &wy);
-                        const i64 v = (2048LL - wy) * ((2048LL - wx) * p[(size_t)x0 * Ny + y0] + (i64)wx * p[(size_t)x1 * Ny + y0]) +
-                                      (i64)wy * ((2048LL - wx) * p[(size_t)x0 * Ny + y1] + (i64)wx * p[(size_t)x1 * Ny + y1]);
-                        out = (unsigned)((v + (1LL << 21)) >> 22);
-                    } else {
-                        i64 num = 0;
-                        for (int sx = 0; sx < Nx; ++sx) {
-                            if (!ox[x][sx]) continue;
-                            i64 col = 0;
-                            for (int sy = 0; sy < Ny; ++sy)
-                                if (oy[y][sy]) col += oy[y][sy] * p[(size_t)sx * Ny + sy];
-                            num += ox[x][sx] * col;
-                        }
-                        const i64 nn = (i64)Nx * Ny;
-                        out = (unsigned)((2 * num + nn) / (2 * nn));
-                    }
-                    before[l.off + b * l.stride + y * l.pitch + (size_t)x * D + d] = (unsigned char)out;
-                }
-        }
+    frames_to_image_ref(px.data(), B, D, Nx, Ny, mode, W, H, before.data() + l.off, l.pitch, l.stride);
     const size_t bad = [&] { size_t c = 0; for (size_t k = 0; k < l.off + l.extent; ++k) c += before[k] != alloc[k]; return c; }();
     ++runs;
     if (bad) {

@@ -1,7 +1,7 @@
 // aefft_image_resize_to_frames without a device: the kernel source itself -- autoencoder-fft_amd/csrc/resize_kernels.hip,
 // body and launch geometry -- compiled for the HOST, 256 threads as the lanes of a workgroup and a barrier for __syncthreads, under the
 // sanitizers, with the source, frame and LDS buffers allocated at exactly their live extent, against a C restatement of include/aefft.h's
-// formulas in 64-bit integers (which shares nothing with the kernel's taps).
+// formulas in 64-bit integers (hostcheck_ref.h's image_to_frames_ref, which shares nothing with the kernel's taps).
 //
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -pthread -Wno-unknown-pragmas
 //       -o resize_hostcheck tools/resize_hostcheck.cpp   (one line),   then   ./resize_hostcheck
@@ -13,45 +13,6 @@
 #include "hostcheck_ref.h"
 
 using namespace aefft;
-
-// ---- the formulas of include/aefft.h, restated -------------------------------------------------
-// want: [B][D][Nx][Ny] as the 8-bit pixel or, float frames, q (value = q * 2^-16)
-static void reference(const unsigned char* img, size_t pitch, size_t stride, int W, int H, int mode, bool f32, int B, int D, int Nx, int Ny, std::vector<unsigned>& want)
-{
-    want.assign((size_t)B * D * Nx * Ny, 0);
-    std::vector<std::vector<i64>> ox(Nx, std::vector<i64>(W, 0)), oy(Ny, std::vector<i64>(H, 0));
-    if (mode == 1) {
-        for (int i = 0; i < Nx; ++i) for (int k = 0; k < W; ++k) ox[i][k] = overlap(i, k, W, Nx);
-        for (int j = 0; j < Ny; ++j) for (int k = 0; k < H; ++k) oy[j][k] = overlap(j, k, H, Ny);
-    }
-    for (int b = 0; b < B; ++b)
-        for (int d = 0; d < D; ++d)
-            for (int i = 0; i < Nx; ++i)
-                for (int j = 0; j < Ny; ++j) {
-                    const unsigned char* p = img + b * stride + d;
-                    unsigned out;
-                    if (mode == 0) {
-                        int x0, x1, wx, y0, y1, wy;
-                        linear_axis(i, W, Nx, &x0, &x1, &wx);
-                        linear_axis(j, H, Ny, &y0, &y1, &wy);
-                        const i64 v = (2048LL - wy) * ((2048LL - wx) * p[y0 * pitch + x0 * D] + (i64)wx * p[y0 * pitch + x1 * D]) +
-                                      (i64)wy * ((2048LL - wx) * p[y1 * pitch + x0 * D] + (i64)wx * p[y1 * pitch + x1 * D]);
-                        out = f32 ? (unsigned)((v + 32) >> 6) : (unsigned)((v + (1LL << 21)) >> 22);
-                    } else {
-                        i64 num = 0;
-                        for (int y = 0; y < H; ++y) {
-                            if (!oy[j][y]) continue;
-                            i64 row = 0;
-                            for (int x = 0; x < W; ++x)
-                                if (ox[i][x]) row += ox[i][x] * p[y * pitch + x * D];
-                            num += oy[j][y] * row;
-                        }
-                        const i64 wh = (i64)W * H;
-                        out = f32 ? (unsigned)((65536 * num + wh / 2) / wh) : (unsigned)((2 * num + wh) / (2 * wh));
-                    }
-                    want[(((size_t)b * D + d) * Nx + i) * Ny + j] = out;
-                }
-}
 
 // ---- the bodies the launcher chooses between ----------------------------------------------------
 typedef void (*body_fn)(const RzArgs&, unsigned*);
@@ -82,7 +43,7 @@ static void run(const Shape& s, int kind, int mode, bool f32, unsigned grid_y = 
     const RzArgs g = rz_geometry(img, pitch, stride, W, H, mode, frames, B, D, Nx, Ny);
     launch((unsigned)(g.tx * g.ty), grid_y ? grid_y : (unsigned)B, 1u, (size_t)rz_lds_words(D, g.P, g.RB), [&](unsigned* lds) { BODIES[D - 1][f32][mode](g, lds); });
     std::vector<unsigned> want;
-    reference(img, pitch, stride, W, H, mode, f32, B, D, Nx, Ny, want);
+    image_to_frames_ref(img, pitch, stride, W, H, mode, f32, B, D, Nx, Ny, want);      // [B][D][Nx][Ny] as the 8-bit pixel or, float frames, q
     size_t bad = 0;
     for (size_t k = 0; k < n; ++k) {
         if (f32) {

@@ -1,8 +1,8 @@
 // aefft_yuv_to_image and aefft_yuv_resize_to_frames without a device: the kernel source itself --
 // autoencoder-fft_amd/csrc/yuv_kernels.hip, both bodies and both launch geometries -- compiled for the HOST, 256 threads as the lanes of a workgroup
 // and a barrier for __syncthreads, under the sanitizers, with every source plane, the image, the frames and the LDS allocated at exactly their
-// live extent, against a scalar C restatement of include/aefft.h in 64-bit integers (its own coefficient table, its own chroma gather, its own
-// resize: it shares nothing with the kernel, resize_taps.h included).
+// live extent, against a scalar C restatement of include/aefft.h in 64-bit integers (its own coefficient table, its own chroma gather, and
+// hostcheck_ref.h's resize: it shares nothing with the kernel, resize_taps.h and resize_tile.h included).
 //
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -pthread -Wno-unknown-pragmas
 //       -o yuv_hostcheck tools/yuv_hostcheck.cpp   (one line),   then   ./yuv_hostcheck
@@ -47,45 +47,6 @@ static void convert_ref(int fmt, const Planes& s, int W, int H, int matrix, int 
                 }
             }
 }
-// want: [B][D][Nx][Ny] as the 8-bit pixel or, float frames, q (value = q * 2^-16), from the tight pixels
-static void resize_ref(const unsigned char* img, int W, int H, int mode, bool f32, int B, int D, int Nx, int Ny, std::vector<unsigned>& want)
-{
-    const size_t pitch = (size_t)W * D, stride = pitch * H;
-    want.assign((size_t)B * D * Nx * Ny, 0);
-    std::vector<std::vector<i64>> ox(Nx, std::vector<i64>(W, 0)), oy(Ny, std::vector<i64>(H, 0));
-    if (mode == 1) {
-        for (int i = 0; i < Nx; ++i) for (int k = 0; k < W; ++k) ox[i][k] = overlap(i, k, W, Nx);
-        for (int j = 0; j < Ny; ++j) for (int k = 0; k < H; ++k) oy[j][k] = overlap(j, k, H, Ny);
-    }
-    for (int b = 0; b < B; ++b)
-        for (int d = 0; d < D; ++d)
-            for (int i = 0; i < Nx; ++i)
-                for (int j = 0; j < Ny; ++j) {
-                    const unsigned char* p = img + b * stride + d;
-                    unsigned out;
-                    if (mode == 0) {
-                        int x0, x1, wx, y0, y1, wy;
-                        linear_axis(i, W, Nx, &x0, &x1, &wx);
-                        linear_axis(j, H, Ny, &y0, &y1, &wy);
-                        const i64 v = (2048LL - wy) * ((2048LL - wx) * p[y0 * pitch + x0 * D] + (i64)wx * p[y0 * pitch + x1 * D]) +
-                                      (i64)wy * ((2048LL - wx) * p[y1 * pitch + x0 * D] + (i64)wx * p[y1 * pitch + x1 * D]);
-                        out = f32 ? (unsigned)((v + 32) >> 6) : (unsigned)((v + (1LL << 21)) >> 22);
-                    } else {
-                        i64 num = 0;
-                        for (int y = 0; y < H; ++y) {
-                            if (!oy[j][y]) continue;
-                            i64 row = 0;
-                            for (int x = 0; x < W; ++x)
-                                if (ox[i][x]) row += ox[i][x] * p[y * pitch + x * D];
-                            num += oy[j][y] * row;
-                        }
-                        const i64 wh = (i64)W * H;
-                        out = f32 ? (unsigned)((65536 * num + wh / 2) / wh) : (unsigned)((2 * num + wh) / (2 * wh));
-                    }
-                    want[(((size_t)b * D + d) * Nx + i) * Ny + j] = out;
-                }
-}
-
 // ---- the bodies the launchers choose between ---------------------------------------------------
 typedef void (*resize_fn)(const YvArgs&, unsigned*);
 typedef void (*image_fn)(const YiArgs&);
@@ -141,7 +102,7 @@ static void run_resize(const Shape& sh, int fmt, int matrix, int order, int kind
     std::vector<unsigned char> px;
     std::vector<unsigned> want;
     convert_ref(fmt, src.pl, W, H, matrix, order, B, px);
-    resize_ref(px.data(), W, H, mode, f32, B, D, Nx, Ny, want);
+    image_to_frames_ref(px.data(), (size_t)W * D, (size_t)W * D * H, W, H, mode, f32, B, D, Nx, Ny, want);   // (from the tight pixels)
     size_t bad = 0;
     for (size_t k = 0; k < n; ++k) {
         if (f32) {

@@ -2,7 +2,8 @@
 // autoencoder-fft_amd/csrc/yuv_out_kernels.hip, both bodies and both launch geometries -- compiled for the HOST, 256 threads as the lanes of a
 // workgroup and a barrier for __syncthreads, under the sanitizers, with every destination plane, the source image, the frames and the LDS in
 // allocations of their own that end at the last live byte, against a scalar C restatement of include/aefft.h in 64-bit integers (its own
-// coefficient table, its own chroma blocks with their live counts, its own resize: it shares nothing with the kernels, resize_taps.h included).
+// coefficient table, its own chroma blocks with their live counts, and hostcheck_ref.h's resize: it shares nothing with the kernels, resize_taps.h
+// and resize_tile.h included).
 //
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -pthread -Wno-unknown-pragmas
 //       -o yuv_out_hostcheck tools/yuv_out_hostcheck.cpp   (one line),   then   ./yuv_out_hostcheck
@@ -40,45 +41,6 @@ static unsigned char chroma_ref(const unsigned char* img, int W, int H, int D, i
     const i64* k = TABLE[matrix] + 5 + 3 * which;
     const i64 v = 128 + fdiv(k[0] * S[0] + k[1] * S[1] + k[2] * S[2] + (n << 19), 1LL << (20 + lg));
     return (unsigned char)(v < 0 ? 0 : v > 255 ? 255 : v);
-}
-
-// the image [B][H][W][D], tight, from frames' pixels px [B][D][Nx][Ny]: include/aefft.h's resize formulas with the roles swapped
-static void resize_ref(const unsigned char* px, int B, int D, int Nx, int Ny, int mode, int W, int H, std::vector<unsigned char>& img)
-{
-    img.assign((size_t)B * H * W * D, 0);
-    std::vector<std::vector<i64>> ox(W, std::vector<i64>(Nx, 0)), oy(H, std::vector<i64>(Ny, 0));
-    if (mode == 1) {
-        for (int i = 0; i < W; ++i) for (int k = 0; k < Nx; ++k) ox[i][k] = overlap(i, k, Nx, W);
-        for (int j = 0; j < H; ++j) for (int k = 0; k < Ny; ++k) oy[j][k] = overlap(j, k, Ny, H);
-    }
-    for (int b = 0; b < B; ++b)
-        for (int d = 0; d < D; ++d) {
-            const unsigned char* p = px + ((size_t)b * D + d) * Nx * Ny;         // p[x * Ny + y]
-            for (int j = 0; j < H; ++j)
-                for (int i = 0; i < W; ++i) {
-                    i64 out;
-                    if (mode == 0) {
-                        int x0, x1, wx, y0, y1, wy;
-                        linear_axis(i, Nx, W, &x0, &x1, &wx);
-                        linear_axis(j, Ny, H, &y0, &y1, &wy);
-                        const i64 v = (2048LL - wy) * ((2048LL - wx) * p[(size_t)x0 * Ny + y0] + (i64)wx * p[(size_t)x1 * Ny + y0]) +
-                                      (i64)wy * ((2048LL - wx) * p[(size_t)x0 * Ny + y1] + (i64)wx * p[(size_t)x1 * Ny + y1]);
-                        out = (v + (1LL << 21)) >> 22;
-                    } else {
-                        i64 num = 0;
-                        for (int x = 0; x < Nx; ++x) {
-                            if (!ox[i][x]) continue;
-                            i64 col = 0;
-                            for (int y = 0; y < Ny; ++y)
-                                if (oy[j][y]) col += oy[j][y] * p[(size_t)x * Ny + y];
-                            num += ox[i][x] * col;
-                        }
-                        const i64 nn = (i64)Nx * Ny;
-                        out = (2 * num + nn) / (2 * nn);
-                    }
-                    img[(((size_t)b * H + j) * W + i) * D + d] = (unsigned char)out;
-                }
-        }
 }
 
 // ---- the bodies the launchers choose between ---------------------------------------------------
@@ -183,8 +145,8 @@ static void run_frames(const Shape& sh, int fmt, int matrix, int order, int kind
         if (f32) ((float*)fp)[k] = (float)px[k] + ((rnd() & 1) ? 0.25f : -0.25f);   // (float frames holding the same pixels)
         else ((unsigned char*)fp)[k] = px[k];
     }
-    std::vector<unsigned char> img;
-    resize_ref(px.data(), B, D, Nx, Ny, mode, W, H, img);
+    std::vector<unsigned char> img((size_t)B * H * W * D);                      // the image [B][H][W][D], tight
+    frames_to_image_ref(px.data(), B, D, Nx, Ny, mode, W, H, img.data(), (size_t)W * D, (size_t)W * D * H);
     Dest dst;
     make_dest(dst, fmt, W, H, B, kind, img.data(), D, matrix, order);
     const FyArgs g = fy_geometry(yo_dest(fmt, dst.p, dst.pitch, dst.stride, W, H, matrix, order, B), fmt, fp, Nx, Ny, mode, B, D);
